@@ -1,13 +1,19 @@
 #!/usr/bin/env python3
 """Benchmark of the Dr.VAE ELBO train step on MI355X (contract: see the task brief).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg1|cfg4|wide(=cfg5)]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg1|cfg4|wide(=cfg5)] [--full]
+                  [--dump-outputs DIR]
 
 One "step" = one full train step (Philox noise + stacked forward + hand-written backward
 + gradient all-reduce + fused Adam) over one synthetic minibatch per GPU, inputs resident
-in HBM.  Prints ONE JSON line on rank 0 with the whole-job samples/s (rows x L), the
-roofline of the dominant kernel (the fp32 MFMA GEMM family, timed with HIP events on its
-launch stream) and a bounded CPU baseline (the oracle on this box's host cores).
+in HBM.  Prints ONE JSON line on rank 0 with the whole-job samples/s (rows x L) of K timed
+steps.  A plain run does nothing else: set-up, W warm-up steps, the K timed steps, the
+outputs of the last one (``--dump-outputs``) and the line.  ``--full`` adds everything
+measured next to the headline: a longer steady-state region, the roofline of the dominant
+kernel (the fp32 MFMA GEMM family, timed with HIP events on its launch stream), a bounded
+CPU baseline (the oracle on this box's host cores) with the ELBO parity against it, the
+captured-exchange probe of data-parallel runs, and the realistic-feed, fit-epoch and
+other-workload legs of cfg 2.
 """
 import argparse
 import ctypes
@@ -42,6 +48,7 @@ WORKLOADS['cfg4_mmd'] = ('vfae', 150, 2, {'add_noise_var': 0.0, 'use_s': True, '
                          'VFAE/SSVAE with use_s + use_MMD (rbf_fourier penalty per data group and sample in the captured '
                          'step): 978 genes, z1=z2=100, enc 800, dec 600, batch 150/GPU, L=2')
 FP32_MFMA_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 peak (dense, exact fp32)
+DUMP_BUDGET_BYTES = 60 << 20       # --dump-outputs: all files together stay below 64 MB
 
 
 def profiled_roofline(workload):
@@ -88,6 +95,30 @@ def build(workload, device, rank, world, seed=123):
     sv = ((rank * rows + np.arange(rows)) // 4 % cfg.dim_s) if cfg.use_s else None
     eng.set_batch(t('x1'), t('x2'), batch['y'], hx, hy, counts=counts, s=sv)
     return cfg, eng, arena, batch, desc
+
+
+def snapshot_outputs(eng, arena, seed=20240):
+    """What a caller of the timed step receives after its last step: the loss scalars (``eng.losses()``) and the trained
+    parameters (fp32, the reference state_dict's names), as name -> host array.  When the parameters exceed
+    ``DUMP_BUDGET_BYTES`` every one of them is cut to a fixed, seeded sample of its elements (in proportion to its size,
+    flat row-major positions in ascending order): the same positions in every run of the same workload."""
+    out = {'loss_' + k: np.array(v, dtype=np.float64) for k, v in eng.losses().items()}
+    total = sum(int(np.prod(s)) for s in arena.shapes.values())
+    frac = min(1.0, (DUMP_BUDGET_BYTES // 4 - len(out)) / max(total, 1))
+    for i, name in enumerate(arena.shapes):
+        p = arena.p(name).detach()
+        if frac < 1.0:
+            n = p.numel()
+            idx = np.sort(np.random.default_rng([seed, i]).choice(n, max(1, int(n * frac)), replace=False))
+            p = p.reshape(-1)[torch.from_numpy(idx).to(p.device)]
+        out['param_' + name] = p.float().cpu().numpy()
+    return out
+
+
+def write_outputs(outputs, path):
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def cpu_baseline(workload, budget_s=12.0, threads=4):
@@ -464,10 +495,11 @@ class _Watchdog:
 _WATCHDOG = _Watchdog()
 
 
-def measure(args, workload, feed, steps, warmup, device, rank, world, steady_s=0.0, exchange_probe=False):
+def measure(args, workload, feed, steps, warmup, device, rank, world, steady_s=0.0, exchange_probe=False, dump=False):
     """Build the workload, capture its train step and time exactly ``steps`` replays (barrier + synchronize on both
     sides, MAX over ranks); with ``steady_s`` a second, longer region of about that many seconds is timed as well.
-    Returns (result dict, context for the roofline leg)."""
+    ``dump``: the outputs of the last timed step (``snapshot_outputs``) are taken right behind the timed region, before
+    anything else runs, into the context's ``outputs``.  Returns (result dict, context for the roofline leg)."""
     from drvae_amd import dist as D
     import torch.distributed as dist
     cfg, eng, arena, batch, desc = build(workload, device, rank, world)
@@ -594,6 +626,7 @@ def measure(args, workload, feed, steps, warmup, device, rank, world, steady_s=0
     t_enq = time.perf_counter() - t0       # host time to enqueue the steps (if ~dt the host is the bound)
     barrier()
     dt = over_ranks(time.perf_counter() - t0)
+    outputs = snapshot_outputs(eng, arena) if dump else None
     # a second, longer region (same step, same barriers) next to the contract's K steps: >= ``steady_s`` seconds of
     # back-to-back replays, so that the driver's utilisation sampler sees the device busy and the number does not
     # hang on a few milliseconds
@@ -643,7 +676,7 @@ def measure(args, workload, feed, steps, warmup, device, rank, world, steady_s=0
     }
     if exchange is not None:
         out['exchange'] = exchange
-    return out, dict(eng=eng, cfg=cfg, batch=batch, rows=rows, dp=dp)
+    return out, dict(eng=eng, cfg=cfg, batch=batch, rows=rows, dp=dp, outputs=outputs)
 
 
 def captured_exchange_probe(args, ctx, device, rank, world, single_ms):
@@ -768,7 +801,16 @@ def main():
     ap.add_argument('--stall-timeout', type=float, default=300.0,
                     help='multi-rank: a rank that makes no progress for this many seconds exits with code 5')
     ap.add_argument('--fail-rank', type=int, default=-1, help='test hook: this rank exits (code 3) right after joining')
+    ap.add_argument('--full', action='store_true',
+                    help='everything next to the headline: steady region, roofline, CPU baseline and ELBO parity, the '
+                         'captured-exchange probe, and the realistic-feed / fit-epoch / other-workload legs (cfg2); the '
+                         '--no-* options above switch single parts off again')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the loss scalars and the trained parameters of the last timed step as DIR/<name>.npy '
+                         '(a fixed, seeded sample of each parameter where they exceed 60 MB)')
     args = ap.parse_args()
+    if not args.full:            # a plain run: set-up, warm-up, the timed steps, the outputs, the line
+        args.no_steady = args.no_roofline = args.no_cpu_baseline = args.no_extras = args.no_exchange_modes = True
     if args.workload == 'cfg5':
         args.workload = 'wide'
 
@@ -796,8 +838,11 @@ def main():
     if world > 1:
         _WATCHDOG.start(args.stall_timeout, rank)
     res, ctx = measure(args, args.workload, args.feed, args.steps, args.warmup, device, rank, world,
-                       steady_s=0.0 if args.no_steady else 3.2, exchange_probe=True)
+                       steady_s=0.0 if args.no_steady else 3.2, exchange_probe=args.full,
+                       dump=bool(args.dump_outputs) and rank == 0)
     _WATCHDOG.stop()
+    if ctx['outputs'] is not None:
+        write_outputs(ctx.pop('outputs'), args.dump_outputs)
     ok, dp = res['finite'], ctx['dp']
     out = {'metric': 'DrVAE ELBO training samples/sec (batch x L)', 'value': res['value'], 'unit': 'samples/s',
            'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': res['ms_per_step'],

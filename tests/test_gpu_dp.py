@@ -115,7 +115,7 @@ def test_step_path_over_rccl_single_rank(dev):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--steps', '12', '--warmup', '3', '--no-cpu-baseline',
+    cmd = [sys.executable, os.path.join(root, 'bench.py'), '--steps', '12', '--warmup', '3', '--full', '--no-cpu-baseline',
            '--no-roofline', '--no-steady', '--no-extras']
 
     def run(*args, **env):
@@ -181,7 +181,7 @@ def test_bench_self_launch_eight_ranks_one_gpu(dev):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '8', '--steps', '6', '--warmup', '2',
-                          '--no-cpu-baseline', '--no-roofline', '--no-steady', '--no-extras'], env=_bench_env(),
+                          '--full', '--no-cpu-baseline', '--no-roofline', '--no-steady', '--no-extras'], env=_bench_env(),
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]

@@ -11,7 +11,7 @@ d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('$wl dp_fork=$f', d['ms_per_step'], 'ticks/step', [round(t / 630) for t in d['chain_wait_ticks'][1::2]])"
     done
   done
-  python3 bench.py --workload $wl --dp-exchange single --steps 600 --warmup 30 --no-extras --no-cpu-baseline --no-roofline --no-steady --no-exchange-modes 2>/dev/null | python3 -c "
+  python3 bench.py --workload $wl --dp-exchange single --steps 600 --warmup 30 --full --no-extras --no-cpu-baseline --no-roofline --no-steady --no-exchange-modes 2>/dev/null | python3 -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('$wl single', d['ms_per_step'], d.get('exchange'))"

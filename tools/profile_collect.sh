@@ -30,14 +30,14 @@ done
 unset PMC_EXTRA
 for wl in cfg2 cfg1 cfg4 wide; do
   if [ $wl = wide ]; then ST="--steps 6 --warmup 2"; else ST="--steps 300 --warmup 20"; fi
-  python3 bench.py --workload $wl $ST --no-extras --no-cpu-baseline > $O/${wl}_bench.json 2> $O/${wl}_bench.err
+  python3 bench.py --workload $wl $ST --full --no-extras --no-cpu-baseline > $O/${wl}_bench.json 2> $O/${wl}_bench.err
   # every figure of bench.py's roofline block that a profiler has to supply, derived from the files above
   python3 tools/roofline_from_profile.py $O/$wl --commit "${COMMIT:-unknown}" --out $O/${wl}_roofline.json > /dev/null 2>&1
   cp $O/${wl}_roofline.json profiles/${R}_${wl}_roofline.json
   python3 tools/step_profile.py $wl > $O/${wl}_step_isolated.txt 2>&1
 done
 # the headline once more WITH the roofline files in place: the line to commit as profiles/<round>_cfg2_bench.json
-python3 bench.py --steps 300 --warmup 20 > $O/cfg2_bench_final.json 2> $O/cfg2_bench_final.err
+python3 bench.py --steps 300 --warmup 20 --full > $O/cfg2_bench_final.json 2> $O/cfg2_bench_final.err
 ( python3 tools/gemm_bench.py --tilings 0; python3 tools/pair_bench.py; python3 tools/heads_bench.py; python3 tools/pipe_check.py --tilings 40 --big --vendor; python3 tools/blas_ref.py ) > $O/gemm_vs_vendor.txt 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/k_eval -o p -- python3 tools/eval_bench.py 10 > $O/eval_bench.txt 2>&1
 python3 tools/kstats.py $O/k_eval 24 > $O/eval_kernel_stats.txt 2>&1
