@@ -111,12 +111,11 @@ class _Chain:
             x = [self.out[li]]
         return self.out[-1]
 
-    def backward(self, dpre_last, inputs, dinputs=None, wbranch=None, publish_after_last=None, publish_first=None,
-                 db_last_done=False, klq=None):
+    def backward(self, dpre_last, inputs, dinputs=None, publish_after_last=None, publish_first=None, db_last_done=False,
+                 klq=None):
         """dpre_last: gradient w.r.t. the last layer's pre-activation.  ``dinputs``: per input
         source a list of (dst, alpha, beta) destinations for its gradient (or None to skip).
-        ``wbranch``: optional side stream for the weight-gradient GEMMs (they are leaves: only
-        Adam reads them), so that they overlap the dx chain.  ``publish_after_last`` = (flag, counter, add):
+        ``publish_after_last`` = (flag, counter, add):
         the first launch AFTER the last layer's launches publishes the flag on entry (= both gradients of the
         last layer are final and its weights are no longer read); ``publish_first``: the chain's FIRST launch
         does (= everything in front of this backward pass is complete).  ``db_last_done``: the
@@ -135,22 +134,11 @@ class _Chain:
             if li == len(self.layers) - 2 and publish_after_last is not None:
                 pending_pub = publish_after_last
 
-            def wgrad(l=l, srcs=srcs, dpre=dpre, db=db):
-                dW = l.raw if l.g is not None else l.dW
-                c0 = 0
-                for si, s in enumerate(srcs):
-                    w = s.shape[1]
-                    K.linear_bwd_weight(dW[:, c0:c0 + w], dpre, s, dbias=db if si == 0 else None, overread=True,
-                                        npad=len(srcs) == 1 and l.g is None and self._pad_ok(s))
-                    c0 += w
-                if l.g is not None:
-                    K.wn_bwd(l.dW, l.dg, l.raw, l.W, l.g, l.norm)
-
             # the layer's weight- and data-gradient both only need dpre: one paired launch when the
             # layer has a single input source, no WeightNorm and a single data-gradient destination
             single_dst = li > 0 or (dinputs is not None and len(srcs) == 1 and dinputs[0] is not None
                                     and len(dinputs[0]) == 1)
-            if wbranch is None and l.g is None and len(srcs) == 1 and single_dst:
+            if l.g is None and len(srcs) == 1 and single_dst:
                 if li > 0:
                     prev = self.layers[li - 1]
                     K.linear_bwd_pair(l.dW, db, self.dpre[li - 1], dpre, srcs[0], l.W, yref=self.out[li - 1],
@@ -171,11 +159,15 @@ class _Chain:
             if pending_pub is not None:      # (no paired launch for this layer: a launch of its own)
                 K.flag_publish(*pending_pub)
                 pending_pub = None
-            if wbranch is not None:
-                with wbranch:
-                    wgrad()
-            else:
-                wgrad()
+            dW = l.raw if l.g is not None else l.dW
+            c0 = 0
+            for si, s in enumerate(srcs):
+                w = s.shape[1]
+                K.linear_bwd_weight(dW[:, c0:c0 + w], dpre, s, dbias=db if si == 0 else None, overread=True,
+                                    npad=len(srcs) == 1 and l.g is None and self._pad_ok(s))
+                c0 += w
+            if l.g is not None:
+                K.wn_bwd(l.dW, l.dg, l.raw, l.W, l.g, l.norm)
             if li > 0:
                 prev = self.layers[li - 1]
                 K.linear_bwd_data(self.dpre[li - 1], dpre, l.W, kscale=l.scale, yref=self.out[li - 1], act=prev.act0,
@@ -189,6 +181,4 @@ class _Chain:
                         K.linear_bwd_data(dst, dpre, l.W[:, c0:c0 + w], kscale=l.scale, alpha=alpha, beta=beta,
                                           overread=True)
                     c0 += w
-        if wbranch is not None:
-            wbranch.join()
         return took_klq

@@ -200,34 +200,16 @@ class FusedStep(StepSchedule):
         self.seed = seed
         self.training = True
         self.fuse_bwd = False               # set by train_step/capture: forward is followed by backward
-        # train-step scheduling of the classifier/fprop side chain (tuning 'sched'): 1 = graph fork/join per
-        # pass, 3 = one graph fork/join per step, 5 (default) = two single-stream graphs (main chain / side
-        # chain) launched on two streams per step and ordered ONLY by device flags (dv_flag_publish /
-        # dv_flag_wait): no graph edges, no events.  (Also tried and dropped: an extra cross edge, 0.37 ms;
-        # the side chain as a second ROOT of one graph with flags, 0.42 ms -- the executor starts it late.)
+        # train-step scheduling of the classifier/fprop side chain (tuning 'sched'): 3 = one graph fork/join per step,
+        # 5 (default) = two single-stream graphs (main chain / side chain) launched on two streams per step and ordered
+        # ONLY by device flags (dv_flag_publish / dv_flag_wait): no graph edges, no events.  (Also tried and dropped: a
+        # fork/join per pass; an extra cross edge, 0.37 ms; the side chain as a second ROOT of one graph with flags,
+        # 0.42 ms -- the executor starts it late.)
         self.sched = T.get('sched')
-        self._rec = 'both'
-        self.late_leaf = bool(T.get('late_leaf'))
-        self.side_adam = bool(T.get('side_adam'))
-        self.fold_join = bool(T.get('fold_join'))
         # the row work that consumes both heads of a block (the reparameterised samples; forward AND backward of
         # the reconstruction log-likelihood) leaves the heads' own GEMM launch (dv_gemm_heads)
         self.fuse_heads = bool(T.get('fuse_heads'))
-        # the side chain's second wait rides on the row kernel behind it (dv_wait argument of dv_kl_rows_fwd)
-        # instead of being a launch of its own
-        self.fold_waits = bool(T.get('fold_waits'))
-        # the side chain's tail (bit mask): 1 / 4 = its two publishes ride on the entry of the launch behind them
-        # (classifier dW; the counter launch), 2 = the wait in front of the next step's Philox draws is a park of the
-        # draw launch itself -- measured SLOWER (356 workgroups polling one flag: +10 us/step), hence off
-        self.fold_tail = T.get('fold_tail')
-        self.noise_ahead = False          # set by capture(): the side chain draws the NEXT step's noise behind the join
-        self._noise_stale = True          # (then) the noise buffer does not hold the draws of the current Philox counter
-        self._adam_n = None
-        self._split_capture = False
-        self._adam_gate = None
-        self._side_graph = None
-        self._flag_side = None
-        self._after_decoder_bwd = None
+        self._init_schedule_state()
         self.side_ctr = torch.zeros(1, dtype=torch.int32, device=self.dev)   # the side chain's own step count
         self.side_t = torch.ones(1, dtype=torch.int32, device=self.dev)      # ... + 1: the optimiser step it works on
         self.flags = torch.zeros(8, dtype=torch.int32, device=self.dev)
@@ -242,7 +224,6 @@ class FusedStep(StepSchedule):
         # than they hide: cfg 1 0.167 -> 0.175 ms)
         self.branch = _Branch(self.dev, enabled=concurrent and cfg.has_y)
         self.concurrent = bool(concurrent)
-        self.wbranch = _Branch(self.dev, enabled=concurrent and bool(T.get('wbranch')))   # measured slower on MI355X (third graph branch): off
         self._build_layers()
 
     # ------------------------------------------------------------------ layer table
@@ -290,8 +271,7 @@ class FusedStep(StepSchedule):
                                act='sigmoid' if cfg.cont else 'identity'))
             self.L_clf = layers
             # single Linear with <= 8 classes: dedicated wave-per-row kernels instead of MFMA tiles
-            self.clf_small = (not cfg.h_clf) and cfg.dim_y <= 8 and not wn and not cfg.clf_1sig and not cfg.cont and \
-                bool(T.get('clf_small'))
+            self.clf_small = (not cfg.h_clf) and cfg.dim_y <= 8 and not wn and not cfg.clf_1sig and not cfg.cont
             self.L_top = self._gauss(cfg.top_name, len(cfg.h_en_z3), 'lv', shift_second=-2.0)
             self.L_dz1 = self._gauss('decoder_z1', len(cfg.h_de_z1), 'lv', shift_second=-2.0)
 
@@ -342,8 +322,7 @@ class FusedStep(StepSchedule):
         for old in list(self._plans):
             if len(self._plans) <= self.max_plans:
                 break
-            if old != keep and old != getattr(self, '_graph_key', None) and old not in getattr(self, '_captures', {}) \
-                    and old not in self.pinned_plans:
+            if old != keep and old != self._graph_key and old not in self._captures and old not in self.pinned_plans:
                 del self._plans[old]
 
     def set_structure(self, has_x2, has_y, counts=None):
@@ -494,7 +473,7 @@ class FusedStep(StepSchedule):
         q(z1|x1), q(z2|x2), perturbation function, samples), then two independent chains -- ``_decoder_forward`` (the big
         GEMMs + NLL) and ``_side_forward`` (fprop / classifier: many small launches).  How the two chains are ordered
         depends on ``_mode()``: 5 = each chain is recorded into its own graph (``_rec`` says which one is being recorded)
-        and device flags order them; 3 / 1 = one graph, fork/join per step / per pass; 0 = plain evaluation."""
+        and device flags order them; 3 = one graph, one fork/join per step; 0 = plain evaluation."""
         cfg, p = self.cfg, self.plan
         if not self.fuse_bwd and self.dev.type == 'cuda' and not torch.cuda.is_current_stream_capturing():
             self.join_side()        # an evaluation forward reads parameters the side chain's tail may still be updating
@@ -524,16 +503,15 @@ class FusedStep(StepSchedule):
                 # workgroups for ~45 us slowed the main chain by 14 % (0.204 -> 0.233 ms).  The second wait has
                 # nothing left to wait for when the side chain reaches it: it rides on the KL row kernel behind it
                 K.flag_wait(*w0)
-                fold = self.fold_waits and not cfg.cont
                 self._side_forward(Qmu, Qlv, Z1blk, (lambda: K.flag_wait(*w2)) if two else None,
-                                   mid_park=w2 if (two and fold) else None)
+                                   mid_park=w2 if (two and not cfg.cont) else None)
                 return
             pub = (self.flags[2:3] if two else self.flags[0:1], self.step_dev, 1)
             if self.L_decx[0].g is not None:             # WeightNorm: the chain's first launch is not the GEMM
                 K.flag_publish(pub[0], pub[1], 1)
                 pub = None
         else:
-            if not getattr(self, '_late_fork', False):
+            if not self._late_fork:
                 self.branch.fork()
             pub = None
         self._decoder_forward(pub)
@@ -544,7 +522,7 @@ class FusedStep(StepSchedule):
                   dict(qidx=p.qz2_idx, pidx=p.pidx, reps=L, free_bits=True, kl_min=cfg.kl_min)) if klz2 else None
             if cfg.kind == 'pvae':      # (its KL rows against the prior: the main chain's own, the backward reads their raw values)
                 zp = ((p.KLP, p.KLPraw, Qmu, Qlv), dict(prior=(0.0, 0.0), free_bits=True, kl_min=cfg.kl_min))
-                if klz2 and T.get('kl_pair'):                # ... next to the pairs' rows: one launch for both sets
+                if klz2:                # ... next to the pairs' rows: one launch for both sets
                     K.kl_rows_fwd_pair(zp, z2)
                     z2 = None
                 else:
@@ -661,15 +639,15 @@ class FusedStep(StepSchedule):
         else:
             # chip-filling heads in a train step: the product runs with the plain epilogue, the NLL row pass behind it
             # adds the bias and applies softplus + shift on its way (wide configuration: 10.87 -> 9.97 ms for the launch)
-            raw_ok = bool(gauss and T.get('raw_heads') and p.c_decx.raw_last_ok() and p.c_decx.layers[-1].act1 == 'softplus'
+            raw_ok = bool(gauss and p.c_decx.raw_last_ok() and p.c_decx.layers[-1].act1 == 'softplus'
                           and (not self._heads_small(p.DPX) or T.get('raw_heads') == 2))     # (2: any size -- tests)
             raw = raw_ok and self.fuse_bwd
             # an EVALUATION pass over many rows (whole-set evaluation, round 5): the heads are needed for the row terms only
             # -- plain product, finished inside the row pass (32768 x 1956 x 600: 737 -> 589 us for the product, and no
             # 256 MB of finished heads written and read back)
-            raw_eval = raw_ok and not self.fuse_bwd and not self.training and bool(T.get('nll_cs'))
+            raw_eval = raw_ok and not self.fuse_bwd and not self.training
             PX = p.c_decx.forward(p.dec_in, publish=pub, raw_last=raw or raw_eval)
-            if getattr(self, '_late_fork', False):       # (chip-filling step: the side chain starts HERE, next to the row pass below)
+            if self._late_fork:       # (chip-filling step: the side chain starts HERE, next to the row pass below)
                 self.branch.fork()
         if self._nll_fused:
             raw_eval = False
@@ -686,7 +664,7 @@ class FusedStep(StepSchedule):
             lh = p.c_decx.layers[-1]
             K.nll_rows_fwd(p.NLL, p.XIN, PX[:, :X], PX[:, X:], mode=GAUSS_SIGMA, xidx=p.tgt, bias=(lh.b[:X], lh.b[X:]),
                            sd_shift=lh.shift1)
-        elif self.fuse_bwd and raw and p.NLLC is not None and T.get('nll_cs'):
+        elif self.fuse_bwd and raw and p.NLLC is not None:
             # ... and the heads' bias gradient with it (column sums of the gradients this pass writes: no second pass over them)
             lh = p.c_decx.layers[-1]
             K.nll_rows_raw_cs(p.NLLC, p.DPX[:, :X], p.DPX[:, X:], p.NLLWS, p.c_nll, p.XIN, PX[:, :X], PX[:, X:],
@@ -821,7 +799,7 @@ class FusedStep(StepSchedule):
         awaited only by the NEXT captured step (tail gating), so whatever else touches parameters, moments or loss scalars
         on the current stream -- ``losses()``, an eager ``train_step``, an evaluation forward, ``capture()``, a checkpoint
         -- goes through here first (one event record + wait; no host sync)."""
-        if getattr(self, '_side_graph', None) is not None and self.dev.type == 'cuda':
+        if self._side_graph is not None and self.dev.type == 'cuda':
             torch.cuda.current_stream().wait_stream(self.flag_side)
 
     def _dual_capable(self):
@@ -831,21 +809,18 @@ class FusedStep(StepSchedule):
         cfg = self.cfg
         if cfg.has_y:
             return self.branch.on
-        return bool(cfg.kind == 'pvae' and self.concurrent and T.get('pvae_tail') and self.late_leaf and self.side_adam
-                    and cfg.optim_alg == 'adam' and self.fold_join)
+        return bool(cfg.kind == 'pvae' and self.concurrent and cfg.optim_alg == 'adam')
 
     def _late_ok(self):
         """the side chain carries the step's leaf work (classifier dW, heads' optimiser half, loss scalars) behind the join"""
         cfg = self.cfg
-        return bool(self.late_leaf and not cfg.cont and cfg.optim_alg == 'adam'
-                    and (self.clf_small if cfg.has_y else self._dual_capable()))
+        return bool(not cfg.cont and cfg.optim_alg == 'adam' and (self.clf_small if cfg.has_y else self._dual_capable()))
 
     def _tail_gated(self):
         """dual-graph train step (ONE pair of graphs) whose side chain runs its half of the optimiser sweep and the loss
         scalars behind the join: the optimiser launch gates on the classifier's gradient only, and the NEXT step's first
         launch waits for the tail's end"""
-        cfg = self.cfg
-        if not (self._mode() == 5 and self._late_ok() and not getattr(self, '_split_kind', False) and T.get('tail_gate')):
+        if not (self._mode() == 5 and self._late_ok() and not self._split_kind):
             return False
         if not self._side_adam_layout()[0]:     # (= ``side_adam`` of backward(): the tail then holds the flag-4 wait launch)
             return False
@@ -859,8 +834,7 @@ class FusedStep(StepSchedule):
         heads = self.L_decx[-1]
         g0 = self.arena.grad.storage_offset()
         hs = min(heads.dW.storage_offset(), heads.db.storage_offset()) - g0
-        ok = bool(self.side_adam and len(self.L_decx) > 1 and heads.g is None and not self.wbranch.on
-                  and hs % 4 == 0 and self.arena.n_live == self.arena.n_params
+        ok = bool(len(self.L_decx) > 1 and heads.g is None and hs % 4 == 0 and self.arena.n_live == self.arena.n_params
                   and max(heads.dW.storage_offset() + span(heads.dW),
                           heads.db.storage_offset() + heads.db.numel()) - g0 >= self.arena.n_live - 3)
         return ok, hs
@@ -876,27 +850,23 @@ class FusedStep(StepSchedule):
         """the encoder heads' sample epilogue also fills the z1 columns of the fprop input (the class columns are
         written when the labels are: ``_Plan._refresh_onehot`` / ``dv_batch_feed``)"""
         cfg, p = self.cfg, self.plan
-        return bool(self.fuse_heads and self._heads_small(p.DPX) and cfg.has_y and not cfg.cont and p.Mf
-                    and T.get('fprop_heads'))
+        return bool(self.fuse_heads and self._heads_small(p.DPX) and cfg.has_y and not cfg.cont and p.Mf)
 
     def _fprop_tail(self):
         """train step: the fprop rows' KL forward and the z1 term's backward ride on the classifier-head launch
         (``dv_fprop_kl``)"""
         cfg, p = self.cfg, self.plan
-        return bool(self.fuse_bwd and self.fuse_heads and self.clf_small and cfg.has_y and not cfg.cont and p.Mf
-                    and T.get('fprop_tail'))
+        return bool(self.fuse_bwd and self.fuse_heads and self.clf_small and cfg.has_y and not cfg.cont and p.Mf)
 
     def _klz2_on_main(self):
-        """dual-graph train step: the pairs' KL(q(z2|x2)||p(z2|z1)) rows run on the main chain (tuning klz2_main=0: on
-        the side chain, as in every other schedule)"""
+        """dual-graph train step: the pairs' KL(q(z2|x2)||p(z2|z1)) rows run on the main chain (in every other schedule:
+        on the side chain)"""
         # (not with the batch-independent plan: its worst-case decoder rows make the main chain the longer one again,
-        # the side chain parks ~13 us per step behind it -- sampler feed 0.250 -> 0.248 ms with the rows on the side chain)
-        on = T.get('klz2_main')
-        if on < 0:
-            # (... the every-row-may-be-anything plan; the bucketed ones are close to a structure plan's rows and keep the
-            # rows on the main chain: sampler feed 0.2181 -> 0.2140 ms in a same-box A/B)
-            p = self.plan
-            on = 0 if (p is not None and p.universal and len(p.key) <= 3) else 1
+        # the side chain parks ~13 us per step behind it -- sampler feed 0.250 -> 0.248 ms with the rows on the side chain;
+        # that is the every-row-may-be-anything plan: the bucketed ones are close to a structure plan's rows and keep the
+        # rows on the main chain, sampler feed 0.2181 -> 0.2140 ms in a same-box A/B)
+        p = self.plan
+        on = not (p is not None and p.universal and len(p.key) <= 3)
         return bool(self._mode() == 5 and not self.cfg.cont and self.cfg.has_y and on)
 
     def _mmd_penalty(self):
@@ -980,7 +950,7 @@ class FusedStep(StepSchedule):
         chain assemble the scalars (they are a leaf of the step: only the host reads them)."""
         cfg, p = self.cfg, self.plan
         L = cfg.L
-        nll = p.NLLP if getattr(self, '_nll_fused', False) else (p.NLLC if getattr(self, '_nll_cs', False) else p.NLL)
+        nll = p.NLLP if self._nll_fused else (p.NLLC if self._nll_cs else p.NLL)
         # (per-tile / per-chunk partials: a row's sum is its term)
         rl = nll.shape[1] if nll.dim() == 2 else 1
         if p.universal:      # normalisers and group masks are per-row weights written by dv_batch_masks
@@ -1003,7 +973,7 @@ class FusedStep(StepSchedule):
             terms.append((p.MMDval, None, 1.0 / p.n_tot, 4))
         bump = ()
         if after is not None or bump_counters:     # this launch also advances the step / Philox counters
-            bump = [(self.step_dev, 1)] + ([(self.rng_ctr, self._rng_pending)] if getattr(self, '_rng_pending', 0) else [])
+            bump = [(self.step_dev, 1)] + ([(self.rng_ctr, self._rng_pending)] if self._rng_pending else [])
             self._rng_pending = 0
             self._ctr_bumped = True
         # (train steps also add their scalars to ``loss_sum``: a ``fit`` epoch reads the sums once, at its end)
@@ -1031,7 +1001,7 @@ class FusedStep(StepSchedule):
         # two-graph split ``replay`` makes the launching stream wait for the side stream before the all-reduce, so the
         # leaf work may still move behind the join (only the optimiser half cannot: it follows the exchange); the
         # overlapped / captured exchanges keep everything in front of the join
-        split_kind = getattr(self, '_split_kind', False)
+        split_kind = self._split_kind
         late = mode == 5 and self._late_ok() and split_kind in (False, True)
         leaf = []
         # ... and HALF of the optimiser sweep moves there too: the decoder heads (the tail of the arena, half of
@@ -1050,7 +1020,7 @@ class FusedStep(StepSchedule):
         cap_fork = self._cap_fork(mode, split_kind, side_ok)
         # the loss scalars (a leaf: only the host / the exchange reads them) are assembled by the side chain behind
         # the join, once the main chain has published that its reconstruction rows are final
-        side_loss = side_adam or (late and split_kind is True and len(self.L_decx) > 1 and not self.wbranch.on)
+        side_loss = side_adam or (late and split_kind is True and len(self.L_decx) > 1)
 
         # ---- main chain: reconstruction terms, d/d(mu, pre-softplus) straight from the per-row
         # coefficients, then back through the decoder (the three big GEMMs)
@@ -1062,17 +1032,16 @@ class FusedStep(StepSchedule):
             K.nll_rows_bwd(p.DPX[:, :X], p.DPX[:, X:], p.c_nll, p.XIN, PX[:, :X], PX[:, X:], mode=GAUSS_SIGMA,
                            xidx=p.tgt, sd_act='softplus', sd_shift=1e-3)
         if mode == 5 and self._rec == 'side':
-            self._side_backward(Qmu, Qlv, Z1blk, mode, late, leaf)
+            self._side_backward(Qmu, Qlv, Z1blk, late, leaf)
             self._side_graph_tail(late, leaf, side_loss, side_adam, hs, cap_fork=cap_fork)
             return
-        if mode < 2:
+        if mode == 0:
             self.branch.fork()
         elif mode == 3:
             self.branch._forked = True       # one fork/join per step: the side chain simply continues
         p.c_decx.backward(p.DPX, p.dec_in, [[(p.DZDEC, 1.0, 0.0)]] + [None] * (len(p.dec_in) - 1),
-                          wbranch=self.wbranch if self.wbranch.on else None,
                           publish_after_last=(self.flags[4:5], self.step_dev, 1) if side_loss else None,
-                          db_last_done=bool(self.fuse_bwd and getattr(self, '_nll_cs', False)))
+                          db_last_done=bool(self.fuse_bwd and self._nll_cs))
         if p.DZMMD is not None:
             # model-level MMD penalty (use_s extension): its gradient w.r.t. the z1 / z2 samples was computed in
             # forward() through the block-level MMD kernels (see ``_mmd_penalty``)
@@ -1081,20 +1050,19 @@ class FusedStep(StepSchedule):
             self._after_decoder_bwd()        # decoder_x gradients are final: graph split point of the overlapped exchange
         if mode != 5:
             with self.branch:
-                self._side_backward(Qmu, Qlv, Z1blk, mode, late, leaf)
+                self._side_backward(Qmu, Qlv, Z1blk, late, leaf)
             self.branch.join()
         # (only where the join does not wait: every workgroup of the consumer polls the flag, and a long wait -- VFAE:
         # its side chain is the longer one, 30 us/step -- slows the very chain it waits for: 0.184 -> 0.208 ms)
         # ... and only where the parked grid is a small fraction of what the chip holds resident (256 CUs x 8
         # workgroups): a consumer grid that filled the chip would leave the side chain nowhere to run
-        fold_join = (mode == 5 and side_loss and self.fold_join and cfg.has_pert
-                     and (B * Z1 + 255) // 256 <= 256)
+        fold_join = mode == 5 and side_loss and cfg.has_pert and (B * Z1 + 255) // 256 <= 256
         park = bump = None
         if fold_join:
             # no launch of its own for the join: the first consumer of the side chain's gradients (below) parks on
             # the flag itself, and the counters ride on the sample-backward launch
             park = (self.flags[1:2], self.step_dev, self.sync_err[0:2])
-            bump = [(self.step_dev, 1)] + ([(self.rng_ctr, self._rng_pending)] if getattr(self, '_rng_pending', 0) else [])
+            bump = [(self.step_dev, 1)] + ([(self.rng_ctr, self._rng_pending)] if self._rng_pending else [])
             self._rng_pending = 0
             self._ctr_bumped = True
         elif mode == 5:    # the launch that assembles the loss scalars also parks on the side chain's flag
@@ -1145,7 +1113,7 @@ class FusedStep(StepSchedule):
         p.c_enc.backward(DQ, p.enc_in, None,
                          publish_first=(self.flags[5:6], self.step_dev, 0) if ((late or cap_fork) and self.noise_ahead) else None)
 
-    def _side_backward(self, Qmu, Qlv, Z1blk, mode, late, leaf):
+    def _side_backward(self, Qmu, Qlv, Z1blk, late, leaf):
         """the side chain's share of the backward pass: y-marginalisation, fprop blocks, classifier -> ``DZ1B`` (its share
         of d/dz1) and ``DZ2F``.  ``late``: the classifier's weight gradient is deferred (appended to ``leaf``: a leaf of the step
         -- only the optimiser reads it -- that runs behind the side chain's publish)"""
@@ -1160,8 +1128,6 @@ class FusedStep(StepSchedule):
             else:
                 K.smalln_bwd_weight(*args, ws=ws)
 
-        if self.fuse_bwd and mode == 1:
-            self._loss_scalars()         # leaf work, off the critical path
         if cfg.has_y and cfg.cont:
             Y, Z3 = cfg.dim_y, cfg.dim_z3
             PZ1, Q3, QYm = p.c_dz1.out[-1], p.c_top.out[-1], p.c_clf.out[-1]
@@ -1199,7 +1165,7 @@ class FusedStep(StepSchedule):
                 # d/dz3 (``DV_EPI_KLQ``: the side chain in front of the join is a chain of dependent launches -- one less),
                 # else a row pass behind it
                 klq = dict(out=p.DQ3, q=Q3, eps=p.E3, coef=p.CFP, raw=p.KL3raw, kl_min=cfg.kl_min, Z=Z3) \
-                    if (self.fuse_bwd and T.get('klq_epi')) else None
+                    if self.fuse_bwd else None
                 if not p.c_dz1.backward(p.DPZ1, [p.Z3IN], [[(p.DZ3IN, 1.0, 0.0)]], klq=klq):
                     K.kl_rows_bwd(p.DQ3[:, :Z3], p.DQ3[:, Z3:], None, None, p.CFP, p.KL3raw, Q3[:, :Z3], Q3[:, Z3:],
                                   prior=(0.0, 0.0), free_bits=True, kl_min=cfg.kl_min, dz=p.DZ3IN[:, :Z3], eps=p.E3)
@@ -1259,8 +1225,7 @@ class FusedStep(StepSchedule):
             return
         # DZ1B / DZ2F / side gradients are final: published on entry of the first leaf launch behind them (the
         # classifier's weight gradient) where there is one, else by a launch of its own
-        tail = (self.fold_tail & 1) and late and len(leaf) > 0
-        if tail:
+        if late and leaf:
             leaf[0](pub=(self.flags[1:2], self.side_ctr, 1))
             for fn in leaf[1:]:
                 fn()
@@ -1282,28 +1247,23 @@ class FusedStep(StepSchedule):
                 self._loss_scalars()   # a leaf too; the wait above also covers the main chain's NLL rows
             if self.noise_ahead:
                 # the next step's N(0,1) draws: every reader of this step's is through once the encoder
-                # backward has started (the main chain publishes that), and the Philox counter has advanced;
-                # the draw launch parks on that flag itself (``fold_tail``) or behind a wait launch
-                w5 = (self.flags[5:6], self.side_ctr, self.sync_err[10:12])
-                if self.fold_tail & 2:
-                    K.fill_normal_rows(p.noise, p.noise_desc, self.seed, self.rng_ctr, park=w5)
-                else:
-                    K.flag_wait(*w5)
-                    K.fill_normal_rows(p.noise, p.noise_desc, self.seed, self.rng_ctr)
+                # backward has started (the main chain publishes that), and the Philox counter has advanced.
+                # (A park of the draw launch itself instead of the wait launch was measured slower: 356
+                # workgroups polling one flag, +10 us/step)
+                K.flag_wait(self.flags[5:6], self.side_ctr, self.sync_err[10:12])
+                K.fill_normal_rows(p.noise, p.noise_desc, self.seed, self.rng_ctr)
             # ... and now the side chain's late work is final: published by the counter launch on entry
-            if self.fold_tail & 4:
-                K.counters_add2(self.side_ctr, 1, self.side_t, 1, publish=(self.flags[3:4], self.side_ctr, 1))
-                return
-            K.flag_publish(self.flags[3:4], self.side_ctr)
+            K.counters_add2(self.side_ctr, 1, self.side_t, 1, publish=(self.flags[3:4], self.side_ctr, 1))
+            return
         K.counters_add2(self.side_ctr, 1, self.side_t, 1)
 
     # -------------------------------------------------------------------- optimiser
     def optimizer_step(self, gscale=1.0):
         """torch.optim.Adam with coupled L2 on EVERY parameter (src/DGMMixin.py:36)."""
         cfg, a = self.cfg, self.arena
-        if getattr(self, '_ctr_bumped', False):
+        if self._ctr_bumped:
             self._ctr_bumped = False          # the loss-scalar launch of this step already advanced them
-        elif getattr(self, '_rng_pending', 0):
+        elif self._rng_pending:
             K.counters_add2(self.step_dev, 1, self.rng_ctr, self._rng_pending)
             self._rng_pending = 0
         else:

@@ -738,7 +738,7 @@ class _EvalGraph:
         with its (mu | std) heads as one product -- 3 launches of 2n rows instead of 6 of n (the block modules compute
         every head with a launch of its own).  The small blocks in between are the model's own modules."""
         from .chain import _Chain
-        from . import kernels as K, tuning as T
+        from . import kernels as K
         m, ds, kind = self.model, self.ds, self.model.kind
         eng = m.engine()
         n, Z, X = int(ds.x1.shape[0]), eng.cfg.dim_z1, eng.cfg.dim_x
@@ -781,7 +781,7 @@ class _EvalGraph:
         # the decoder's heads as a PLAIN product where the one-pass reconstruction statistics finish them on their way
         # (bias, softplus + shift: ``dv_recon_rows`` / ``dv_col_moments``): 16384 x 1956 x 600 at the raw product's 126 instead of 104 TF/s
         lh = eng.L_decx[-1]
-        raw = bool(X <= K.RECON_ROWS_MAX_X and self.c_dec.raw_last_ok() and lh.act1 == 'softplus' and T.get('raw_heads'))
+        raw = bool(X <= K.RECON_ROWS_MAX_X and self.c_dec.raw_last_ok() and lh.act1 == 'softplus')
         PX = self.c_dec.forward([self.zd], raw_last=raw)
         res['px_bias'] = (lh.b[:X], lh.b[X:2 * X], lh.shift1) if raw else None
         res['px1'] = (PX[:n, :X], PX[:n, X:2 * X])

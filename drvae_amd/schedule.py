@@ -9,7 +9,6 @@ import weakref
 import torch
 
 from . import kernels as K
-from . import tuning as T
 
 
 def _masked_stream(bits, device):
@@ -35,7 +34,7 @@ def _masked_stream(bits, device):
     return torch.cuda.ExternalStream(st.value, device=device)
 
 
-SYNC_POLL = T.get('sync_poll')     # steps between two polls of the wait-error words
+SYNC_POLL = 64                # steps between two polls of the wait-error words
 
 _PINNED_POOL = []             # pinned int32 buffers of retired engines (see ``_poll_sync``)
 _PARTITION_STREAMS = {}      # device index -> {reserved CUs -> (main stream, side stream) | None}
@@ -49,6 +48,7 @@ class _Branch:
     def __init__(self, device, enabled=True):
         self.on = enabled and torch.device(device).type == 'cuda'
         self.side = torch.cuda.Stream(device=device) if self.on else None
+        self._forked = False
 
     def fork(self):
         """mark the point of the current stream the side chain depends on; the chain itself may be
@@ -61,7 +61,7 @@ class _Branch:
 
     def __enter__(self):
         if self.on:
-            if not getattr(self, '_forked', False):
+            if not self._forked:
                 self.side.wait_stream(torch.cuda.current_stream())
             self._forked = False
             self._ctx = torch.cuda.stream(self.side)
@@ -86,22 +86,54 @@ class StepSchedule:
     """scheduling half of ``FusedStep`` (see the module docstring); relies on its forward / backward /
     optimizer_step / draw_noise and on its plan, arena and counters"""
 
+    def _init_schedule_state(self):
+        """the host-side state of the schedule, all of it: what ``capture()`` leaves (``_CAPTURE_STATE``), how the step
+        being recorded is split, and the bookkeeping of replays"""
+        # what capture() leaves: see _CAPTURE_STATE
+        self._graphs = []                 # the captured graph(s) of the main chain, in replay order
+        self._side_graph = None           # dual-graph schedule: the side chain's graph
+        self._split_capture = False       # captured in pieces around a gradient exchange
+        self._split_kind = False          # False | True (two graphs) | 'overlap' | 'captured'
+        self.noise_ahead = False          # the side chain draws the NEXT step's noise behind the join
+        self._graph_key = None            # key of the plan the graphs point into
+        self._graph_feed = None           # ... its graph-resident feed at capture time
+        self._graph_mmd_sig = None        # ... its nuisance-class composition (use_MMD)
+        self._captured_allreduce = None   # the collective captured into the step ('captured' exchange)
+        self._graph_noise = None          # the ``add_noise`` the graphs were captured with (None: any; set by fit)
+        self._captures = {}               # plan key -> the above, kept by ``stash_capture``
+        # the step being recorded
+        self._rec = 'both'                # 'both' | the dual-graph schedule's 'main' / 'side' chain
+        self._late_fork = False           # chip-filling step: the side chain forks behind the decoder heads' product
+        self._after_decoder_bwd = None    # graph split point of the overlapped exchange
+        self._nll_fused = False           # which buffer holds this pass's reconstruction rows: NLLP ...
+        self._nll_cs = False              # ... NLLC (else NLL)
+        self._rng_pending = 0             # Philox draw events not yet added to the counter
+        self._ctr_bumped = False          # the loss-scalar launch has advanced the step / Philox counters
+        self._adam_n = None               # the main chain's share of the optimiser sweep (dual-graph step)
+        self._adam_gate = None            # ... and the flag it gates the classifier's slice on
+        # replays
+        self._noise_stale = True          # the noise buffer does not hold the draws of the current Philox counter
+        self._flag_side = None            # the stream the side graph is launched on (``flag_side``)
+        self._flags_ok = None             # None: not probed yet (``_flags_usable``)
+        self._side_cus = None             # CUs reserved by ``tune_partition`` (None: DRVAE_SIDE_CUS / 64)
+        self._since_poll = 0
+        self._sync_host = None            # pinned landing buffer of the error words: from the pool on first poll
+        self._sync_event = None
+
     # ------------------------------------------------ several captured plans side by side
     def stash_capture(self):
         """remember the graphs just captured for the current plan (a feed that switches between a few plans from step
         to step -- ``DeviceBatcher(pair_bucket=...)`` -- captures each once and swaps them with ``use_capture``)"""
-        if not hasattr(self, '_captures'):
-            self._captures = {}
         assert self._graph_key == self.plan.key, 'stash_capture right after capture(): another plan is current'
-        self._captures[self.plan.key] = {k: getattr(self, k, None) for k in _CAPTURE_STATE}
+        self._captures[self.plan.key] = {k: getattr(self, k) for k in _CAPTURE_STATE}
 
     def use_capture(self, key):
         """make the plan ``key`` and its captured graphs current; False when it has not been captured yet"""
-        cap = getattr(self, '_captures', {}).get(key)
+        cap = self._captures.get(key)
         if cap is None or cap['_graph_feed'] is not self._plans[key].live_feed or \
                 cap['_graph_noise'] not in (None, self.add_noise):
             return False
-        if getattr(self, '_graph_key', None) != key:
+        if self._graph_key != key:
             for k, v in cap.items():
                 setattr(self, k, v)
             self.plan = self._plans[key]
@@ -115,9 +147,7 @@ class StepSchedule:
             return 0
         if self._rec != 'both':
             return 5
-        if self.sched == 5:
-            return 3                 # eager steps of the dual-graph schedule use plain stream edges
-        return 3 if self.sched == 3 else 1
+        return 3                     # one fork/join per step (eager steps of the dual-graph schedule, too)
 
     # ------------------------------------------------------------------- hipGraph
     def _launch_sequence(self, allreduce=None):
@@ -172,8 +202,7 @@ class StepSchedule:
         cfg = self.cfg
         # (under a CAPTURED exchange too: the side chain then draws behind the join and sweeps its half behind the collective)
         cap_fork = bool(dual and split_for_allreduce == 'captured' and self._cap_fork(5, 'captured', self._side_adam_layout()[0]))
-        self.noise_ahead = bool(dual and (split_for_allreduce in (False, True) or cap_fork) and self._late_ok()
-                                and T.get('noise_ahead'))
+        self.noise_ahead = bool(dual and (split_for_allreduce in (False, True) or cap_fork) and self._late_ok())
         self._noise_stale = True
         if dual:
             self._rec = 'main'
@@ -183,19 +212,13 @@ class StepSchedule:
         gc.collect()
         gc_was_on = gc.isenabled()
         gc.disable()
-        # a chip-filling step (wide configuration) is captured on ONE stream: its side chain is 0.5 ms of small launches
-        # next to 31 ms of products that want every CU; as a graph branch they squeeze in between the resident GEMM
-        # workgroups of the other queue and cost more than they hide (measured, round 4: 32.0 ms with the fork/join,
-        # 31.5 ms in order on one stream)
-        branch_on = self.branch.on
-        self._late_fork = False
-        if branch_on and not dual and not self._latency_bound() and T.get('wide_single') == 2:
-            # (round 6) ... or as a branch forked LATE: behind the decoder heads' product, next to the HBM-bound NLL row pass
-            # -- the one stretch of the main chain that leaves the matrix pipes idle -- and joined behind the decoder's
-            # backward products (the side chain's 0.4 ms of small launches are through long before)
-            self._late_fork = True
-        elif branch_on and not dual and not self._latency_bound() and T.get('wide_single'):
-            self.branch.on = False
+        # a chip-filling step (wide configuration): its side chain is 0.5 ms of small launches next to 31 ms of products that
+        # want every CU.  Forked at the start of the step they squeeze in between the resident GEMM workgroups of the other
+        # queue and cost more than they hide (round 4: 32.0 ms with the fork/join, 31.5 ms in order on one stream); forked
+        # LATE -- behind the decoder heads' product, next to the HBM-bound NLL row pass, the one stretch of the main chain
+        # that leaves the matrix pipes idle -- and joined behind the decoder's backward products, they win (round 6, cfg 5:
+        # 31.09-31.15 -> 30.87-30.89 ms; the side chain's 0.4 ms are through long before the join)
+        self._late_fork = self.branch.on and not dual and not self._latency_bound()
         try:
             self._capture_main(split_for_allreduce)
             if dual:
@@ -213,7 +236,6 @@ class StepSchedule:
                 self._side_graph = gs
         finally:
             self._rec = 'both'
-            self.branch.on = branch_on
             self._late_fork = False
             if gc_was_on:
                 gc.enable()
@@ -242,18 +264,17 @@ class StepSchedule:
         """(main, side) CU-masked streams reserving ``n_side`` CUs for the side chain (cached)"""
         cache = _PARTITION_STREAMS.setdefault(torch.device(self.dev).index or 0, {})   # per device, process-wide:
         n_side = int(n_side)
-        if (n_side, bool(T.get('part_xcd'))) not in cache:                    # masked streams own hardware queues, so engines share them
+        if n_side not in cache:                    # masked streams own hardware queues, so engines share them
             n_cu = torch.cuda.get_device_properties(self.dev).multi_processor_count
             words = (n_cu + 31) // 32
             side_bits, all_bits = [0] * words, [0] * words
-            # bit i of a CU mask = XCD i % 8, shader engine (i / 8) % 4 of it, CU i / 32 of that engine (tools/cumask_probe.hip).
-            # 'part_xcd': the reserve is WHOLE XCDs (the last n_side / 32 of the eight) -- the side chain then has L2s of its
-            # own, the main chain keeps six (five, ...) undivided ones; default: the first n_side bits = n_side / 32 CUs of
-            # every shader engine of every XCD
-            by_xcd = bool(T.get('part_xcd')) and n_side % 32 == 0 and 0 < n_side < n_cu and n_cu == 256
+            # bit i of a CU mask = XCD i % 8, shader engine (i / 8) % 4 of it, CU i / 32 of that engine (tools/cumask_probe.hip):
+            # the first n_side bits = n_side / 32 CUs of every shader engine of every XCD.  (The reserve as whole XCDs, L2s of
+            # the side chain's own, was measured slower: every hand-over between the chains becomes a cross-XCD miss -- cfg 2
+            # 0.199 -> 0.243 ms, profiles/r04_experiments.md)
             for i in range(n_cu):
                 all_bits[i // 32] |= 1 << (i % 32)
-                if (i % 8 >= 8 - n_side // 32) if by_xcd else (i < min(n_side, n_cu - 1)):
+                if i < min(n_side, n_cu - 1):
                     side_bits[i // 32] |= 1 << (i % 32)
             main_bits = [a & ~b for a, b in zip(all_bits, side_bits)]
             try:
@@ -265,8 +286,8 @@ class StepSchedule:
                 import warnings
                 warnings.warn('drvae_amd: CU partition unavailable (%s)' % e)
                 pair = None
-            cache[(n_side, bool(T.get('part_xcd')))] = pair
-        return cache[(n_side, bool(T.get('part_xcd')))]
+            cache[n_side] = pair
+        return cache[n_side]
 
     def partition(self, n_side=None):
         """Context manager: run the train step with the GPU's compute units split between the two
@@ -282,7 +303,7 @@ class StepSchedule:
         if not self._partition_applicable():
             return contextlib.nullcontext()
         if n_side is None:
-            n_side = getattr(self, '_side_cus', None) or int(os.environ.get('DRVAE_SIDE_CUS', '64'))
+            n_side = self._side_cus or int(os.environ.get('DRVAE_SIDE_CUS', '64'))
         pair = self._part_streams(n_side)
         if pair is None:
             return contextlib.nullcontext()
@@ -372,10 +393,10 @@ class StepSchedule:
         streams onto a few queues, so probe candidates until one qualifies (the CU-masked stream of
         ``partition()`` has a queue of its own); otherwise fall back to graph edges.  (High-priority
         streams are avoided on purpose: with one in the process, captured fork/joins ran 2.4x slower.)"""
-        if getattr(self, '_flags_ok', None) is None:
+        if self._flags_ok is None:
             ok = self._probe(self.flag_side)
             tries = 0
-            while not ok and not getattr(self, '_part', None) and tries < 8:
+            while not ok and tries < 8:
                 self._flag_side = torch.cuda.Stream(device=self.dev)
                 ok = self._probe(self._flag_side)
                 tries += 1
@@ -406,11 +427,11 @@ class StepSchedule:
         first (waiting for it bounds how far the host runs ahead to two periods of queued steps, so the device
         never idles on it).  A timed-out wait therefore raises within two periods even in a ``replay()`` loop
         that never reads the losses."""
-        self._since_poll = getattr(self, '_since_poll', 0) + 1
+        self._since_poll += 1
         if self._since_poll < SYNC_POLL:
             return
         self._since_poll = 0
-        if getattr(self, '_sync_host', None) is None:
+        if self._sync_host is None:
             # pinned landing buffers are pooled for the life of the process: returning one to torch's host
             # allocator queries its events, which is illegal while ANY stream is capturing -- and garbage
             # collection may run in the middle of a later capture
@@ -420,7 +441,6 @@ class StepSchedule:
                 self._sync_host = torch.zeros(self.sync_err.numel(), dtype=torch.int32).pin_memory()
                 ctypes.pythonapi.Py_IncRef(ctypes.py_object(self._sync_host))   # never deallocated, not even at exit
             weakref.finalize(self, _PINNED_POOL.append, self._sync_host).atexit = False
-            self._sync_event = None
         if self._sync_event is not None:
             self._sync_event.synchronize()
             words = self._sync_host.tolist()
@@ -473,28 +493,25 @@ class StepSchedule:
         else:
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
-                self._launch_sequence(allreduce=getattr(self, '_captured_allreduce', None))
+                self._launch_sequence(allreduce=self._captured_allreduce)
             self._graphs = [g]
 
     def replay(self, allreduce=None):
         """One captured train step.  New data is fed by copying into plan.x1 / plan.x2 in place."""
         assert self._graph_key == self.plan.key, 'batch structure changed: capture again'
         assert self._graph_feed is self.plan.live_feed, 'input source changed (epoch feed <-> explicit batch): capture again'
-        assert getattr(self, '_graph_mmd_sig', None) == getattr(self.plan, 'mmd_sig', None), \
+        assert self._graph_mmd_sig == getattr(self.plan, 'mmd_sig', None), \
             'use_MMD: the nuisance classes of the batch changed (the penalty compares row sets): capture again'
         self.plan.set_beta(self.beta_pert())      # 0.01 on iteration 0, 1.0 afterwards (device-side coefficients)
         if self.noise_ahead and self._noise_stale:        # first replay (or an eager draw since): this step's noise
             K.fill_normal_rows(self.plan.noise, self.plan.noise_desc, self.seed, self.rng_ctr)
             self._noise_stale = False
-        # (the host needs ~60 us per graph launch: with the side chain's graph launched first -- it only parks on the z1 flag -- the
-        # step's first kernels started a launch later whenever the device had run dry: after a host sync, i.e. at the head of every
-        # timed region and of every epoch; 20 steps behind a sync: 0.1905 -> 0.188 ms per step, steady state 0.183 either way)
-        main_first = self._side_graph is not None and T.get('main_first')
-        if self._side_graph is not None and not main_first:         # first: its wait kernel is parked before the main chain publishes
-            with torch.cuda.stream(self.flag_side):
-                self._side_graph.replay()
+        # the main chain's graph goes first (the host needs ~60 us per graph launch: with the side chain's graph launched first --
+        # it only parks on the z1 flag -- the step's first kernels started a launch later whenever the device had run dry: after a
+        # host sync, i.e. at the head of every timed region and of every epoch; 20 steps behind a sync: 0.1905 -> 0.188 ms per
+        # step, steady state 0.183 either way)
         self._graphs[0].replay()
-        if main_first:
+        if self._side_graph is not None:
             with torch.cuda.stream(self.flag_side):
                 self._side_graph.replay()
         if len(self._graphs) == 3:               # overlapped exchange: ``allreduce`` has start()/finish()
