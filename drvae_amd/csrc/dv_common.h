@@ -20,9 +20,38 @@
     } while (0)
 
 // ---------------------------------------------------------------- activations
+// expm1(z) for -0.5 <= z <= 0 without cancellation: the Taylor polynomial to z^8 (next term z^9 / 9! < 1.1e-8 |z|: a
+// fifth of an ulp)
+__device__ __forceinline__ float dv_expm1_small(float z) {
+    float p = fmaf(z, 2.48015873e-5f, 1.98412698e-4f);      // 1/8!, 1/7!
+    p = fmaf(p, z, 1.38888889e-3f);                          // 1/6!
+    p = fmaf(p, z, 8.33333333e-3f);                          // 1/5!
+    p = fmaf(p, z, 4.16666667e-2f);                          // 1/4!
+    p = fmaf(p, z, 1.66666667e-1f);                          // 1/3!
+    p = fmaf(p, z, 0.5f);
+    p = fmaf(p, z, 1.f);
+    return p * z;
+}
+
+// log(1 + e) for 0 <= e <= 1 on the hardware log, given r1 = 1 / (1 + e): log(u) + (e - (u - 1)) / u with u = fl(1 + e).
+// The second term is what rounding 1 + e lost (e - (u - 1) is that rounding error, exactly); for a softplus far below
+// zero (a sigma head near its floor) it is most of the result, and log(u) alone is off by up to 6e-8 absolute.
+__device__ __forceinline__ float dv_log1p_hw(float e, float r1) {
+    const float u = 1.f + e;
+    return fmaf(e - (u - 1.f), r1, __logf(u));
+}
+
+// softplus'(x) = sigmoid(x) from the output y = softplus(x): -expm1(-y).  1 - exp(-y) cancels for small y (y ~ e^x: a
+// relative error of ~1e-7 / y, 17 % at x = -15); y >= 0.5 keeps it (>= 0.39: an ulp of exp is <= 1.6 ulp of it), below
+// that the polynomial.  Branch-free: both on min(y, 0.5), selected at the end.
+__device__ __forceinline__ float dv_softplus_slope_from_y(float y) {
+    const float p = -dv_expm1_small(-fminf(y, 0.5f));
+    return y < 0.5f ? p : 1.f - __expf(-y);
+}
+
 // Forward value and derivative-from-OUTPUT (so backward never needs the pre-activation):
 //   elu(a=1):  y = x>0 ? x : expm1(x)         dy/dx = y>0 ? 1 : y+1
-//   softplus:  y = x>20 ? x : log1p(exp(x))   dy/dx = 1-exp(-y)        (torch beta=1, threshold=20)
+//   softplus:  y = x>20 ? x : log1p(exp(x))   dy/dx = -expm1(-y)       (torch beta=1, threshold=20)
 //   sigmoid:   dy/dx = y(1-y);  tanh: 1-y^2;  relu: y>0;  leaky(0.1): y>0?1:0.1
 //   selu:      y = l*(x>0?x:a*expm1(x))       dy/dx = y>0 ? l : y+l*a
 //   softsign:  y = x/(1+|x|)                  dy/dx = (1-|y|)^2
@@ -33,18 +62,11 @@ __device__ __forceinline__ float dv_act(int act, float x) {
             // expm1 on ONE hardware transcendental (round 5; round 3's Kahan quotient took three -- exp, log, rcp -- and the
             // hidden layers' epilogues run this on every element: +37 us of VALU time on a 32768 x 600 product):
             //   x <= -0.5: exp(x) - 1 loses nothing that matters (|result| >= 0.39: an ulp of exp is <= 1.6 ulp of it);
-            //   -0.5 < x <= 0: the Taylor polynomial to x^8 (next term x^9 / 9! < 1.1e-8 |x|: a fifth of an ulp).
+            //   -0.5 < x <= 0: dv_expm1_small.
             // Branch-free: both on min(x, 0), selected at the end.
             const float xm = fminf(x, 0.f);
             const float e = __expf(xm) - 1.f;
-            float p = fmaf(xm, 2.48015873e-5f, 1.98412698e-4f);      // 1/8!, 1/7!
-            p = fmaf(p, xm, 1.38888889e-3f);                          // 1/6!
-            p = fmaf(p, xm, 8.33333333e-3f);                          // 1/5!
-            p = fmaf(p, xm, 4.16666667e-2f);                          // 1/4!
-            p = fmaf(p, xm, 1.66666667e-1f);                          // 1/3!
-            p = fmaf(p, xm, 0.5f);
-            p = fmaf(p, xm, 1.f);
-            const float r = xm > -0.5f ? p * xm : e;
+            const float r = xm > -0.5f ? dv_expm1_small(xm) : e;
             return x > 0.f ? x : r;
         }
         case DV_ACT_SOFTPLUS: {
@@ -72,7 +94,7 @@ __device__ __forceinline__ float dv_act(int act, float x) {
 __device__ __forceinline__ float dv_dact_from_y(int act, float y) {
     switch (act) {
         case DV_ACT_ELU: return y > 0.f ? 1.f : y + 1.f;
-        case DV_ACT_SOFTPLUS: return 1.f - expf(-y);
+        case DV_ACT_SOFTPLUS: return dv_softplus_slope_from_y(y);
         case DV_ACT_SIGMOID: return y * (1.f - y);
         case DV_ACT_TANH: return 1.f - y * y;
         case DV_ACT_RELU: return y > 0.f ? 1.f : 0.f;

@@ -111,11 +111,11 @@ __device__ __forceinline__ void heads_epilogue(const dv_gemm_desc& g, const dv_h
         if (use_res) a0 += g.resid[(int64_t)rc * g.ldr + cc0];
         if (he.mode == DV_HEADS_NLL && g.act1 == DV_ACT_SOFTPLUS) {
             // the decoder's sigma head on hardware transcendentals (one exp, two logs, two reciprocals per element):
-            //   p = pre-activation, e = exp(-|p|): softplus(p) = max(p, 0) + log(1 + e), sigmoid(p) = (p >= 0 ? 1 : e) / (1 + e)
+            //   p = pre-activation, e = exp(-|p|): softplus(p) = max(p, 0) + log1p(e), sigmoid(p) = (p >= 0 ? 1 : e) / (1 + e)
             const float pre = v1 * g.alpha * sc1 + bi1;
             const float e_ = __expf(-fabsf(pre));
             const float r1 = __frcp_rn(1.f + e_);
-            const float sd = fmaxf(pre, 0.f) + __logf(1.f + e_) + g.shift1;
+            const float sd = fmaxf(pre, 0.f) + dv_log1p_hw(e_, r1) + g.shift1;
             const float sig = (pre >= 0.f ? 1.f : e_) * r1;
             const float is = __frcp_rn(sd);
             const float xv = he.x[(int64_t)(he.xidx ? he.xidx[rc] : rc) * he.ldx + cc0];

@@ -454,7 +454,7 @@ __device__ __forceinline__ float nll_term(int mode, float x, float m, float s) {
 __device__ __forceinline__ float nll_raw_term(float shift, float xv, float mraw, float sraw, float bm, float bs) {
     const float a = sraw + bs;
     const float e = __expf(-fabsf(a));
-    const float sdv = fmaxf(a, 0.f) + __logf(1.f + e) + shift;
+    const float sdv = fmaxf(a, 0.f) + dv_log1p_hw(e, __frcp_rn(1.f + e)) + shift;
     const float t = (xv - (mraw + bm)) * __frcp_rn(sdv);
     return kLog2Pi + 2.f * __logf(sdv) + t * t;
 }
@@ -525,8 +525,9 @@ __global__ __launch_bounds__(256) void nll_rows_fwd_kernel(const float* __restri
 // per-row log-likelihoods with coefficients known before the forward pass, so d/d(mu, pre-act of
 // sd) can be emitted while the row sum is being formed (3 reads + 2 writes per element instead
 // of 6 + 2 over two launches)
-__device__ __forceinline__ void nll_fb_elem(int mode, int sd_act, float sd_shift, float c, float xv, float m, float s,
-                                            float& acc, float& gm, float& gs) {
+// ds = d sd / d (pre-activation of sd), see sd_finish
+__device__ __forceinline__ void nll_fb_elem(int mode, float ds, float c, float xv, float m, float s, float& acc, float& gm,
+                                            float& gs) {
     const float d = xv - m;
     if (mode == DV_GAUSS_SIGMA) {
         const float v = s * s;
@@ -539,9 +540,27 @@ __device__ __forceinline__ void nll_fb_elem(int mode, int sd_act, float sd_shift
         gm = d * iv;
         gs = -0.5f * (1.f - d * d * iv);
     }
-    if (sd_act != DV_ACT_IDENTITY) gs *= dv_dact_from_y(sd_act, s - sd_shift);
+    gs *= ds;
     gm *= c;
     gs *= c;
+}
+
+// (sd, d sd / d pre) of one element: finished heads (raw == false) hold sd, its activation's slope is taken from the
+// output; raw heads hold pre - bias and are finished here, the softplus slope taken from the pre-activation itself
+// (sigmoid(a): from the output it is sd - shift, which has lost all but a few bits of softplus(a) near the floor)
+__device__ __forceinline__ float sd_finish(bool raw, int act, float shift, float v, float bias, float& ds) {
+    if (!raw) {
+        ds = act == DV_ACT_IDENTITY ? 1.f : dv_dact_from_y(act, v - shift);
+        return v;
+    }
+    const float a = v + bias, s = dv_act(act, a) + shift;
+    if (act == DV_ACT_SOFTPLUS) {
+        const float e = __expf(-fabsf(a));
+        ds = (a >= 0.f ? 1.f : e) * __frcp_rn(1.f + e);
+    } else {
+        ds = act == DV_ACT_IDENTITY ? 1.f : dv_dact_from_y(act, s - shift);
+    }
+    return s;
 }
 
 template <bool VEC2>
@@ -573,33 +592,36 @@ __global__ __launch_bounds__(256) void nll_rows_fwdbwd_kernel(const float* __res
         // softplus in its 128x128 tiles' epilogue) and this HBM-bound pass applies them on its way
         const bool raw = bias_mu != nullptr;
         auto fin_m = [&](float v, int g) { return raw ? v + bias_mu[g] : v; };
-        auto fin_s = [&](float v, int g) { return raw ? dv_act(sd_act, v + bias_sd[g]) + sd_shift : v; };
+        auto fin_s = [&](float v, int g, float& ds) { return sd_finish(raw, sd_act, sd_shift, v, raw ? bias_sd[g] : 0.f, ds); };
         if (VEC2) {
             const int X2 = X >> 1;
             for (int q = threadIdx.x; q < X2; q += 256) {
                 const float2 xv = reinterpret_cast<const float2*>(xr)[q];
                 float2 mv = reinterpret_cast<const float2*>(mr)[q];
                 float2 sv = reinterpret_cast<const float2*>(sr)[q];
+                float2 ds;
                 mv.x = fin_m(mv.x, 2 * q);
                 mv.y = fin_m(mv.y, 2 * q + 1);
-                sv.x = fin_s(sv.x, 2 * q);
-                sv.y = fin_s(sv.y, 2 * q + 1);
+                sv.x = fin_s(sv.x, 2 * q, ds.x);
+                sv.y = fin_s(sv.y, 2 * q + 1, ds.y);
                 float2 gm, gs;
-                nll_fb_elem(mode, sd_act, sd_shift, c, xv.x, mv.x, sv.x, acc, gm.x, gs.x);
-                nll_fb_elem(mode, sd_act, sd_shift, c, xv.y, mv.y, sv.y, acc, gm.y, gs.y);
+                nll_fb_elem(mode, ds.x, c, xv.x, mv.x, sv.x, acc, gm.x, gs.x);
+                nll_fb_elem(mode, ds.y, c, xv.y, mv.y, sv.y, acc, gm.y, gs.y);
                 reinterpret_cast<float2*>(gmr)[q] = gm;
                 reinterpret_cast<float2*>(gsr)[q] = gs;
             }
             if ((X & 1) && threadIdx.x == 0) {
-                float gm, gs;
-                nll_fb_elem(mode, sd_act, sd_shift, c, xr[X - 1], fin_m(mr[X - 1], X - 1), fin_s(sr[X - 1], X - 1), acc, gm, gs);
+                float gm, gs, ds;
+                const float s = fin_s(sr[X - 1], X - 1, ds);
+                nll_fb_elem(mode, ds, c, xr[X - 1], fin_m(mr[X - 1], X - 1), s, acc, gm, gs);
                 gmr[X - 1] = gm;
                 gsr[X - 1] = gs;
             }
         } else {
             for (int g = threadIdx.x; g < X; g += 256) {
-                float gm, gs;
-                nll_fb_elem(mode, sd_act, sd_shift, c, xr[g], fin_m(mr[g], g), fin_s(sr[g], g), acc, gm, gs);
+                float gm, gs, ds;
+                const float s = fin_s(sr[g], g, ds);
+                nll_fb_elem(mode, ds, c, xr[g], fin_m(mr[g], g), s, acc, gm, gs);
                 gmr[g] = gm;
                 gsr[g] = gs;
             }
@@ -616,13 +638,13 @@ __global__ __launch_bounds__(256) void nll_rows_fwdbwd_kernel(const float* __res
 // the size it exists for (wide configuration: 8192 rows x 20000 genes, 2.9 GB of traffic): four genes per lane and the
 // hardware transcendentals -- one exp, two logs, two reciprocals per gene instead of the library softplus / log / exp /
 // divisions, which made the pass compute-bound (1.0 ms; this form 0.6 ms = the HBM time).
-//   a = sd_raw + b_sd;  e = exp(-|a|);  softplus(a) = max(a, 0) + log(1 + e);  sigmoid(a) = (a >= 0 ? 1 : e) / (1 + e)
+//   a = sd_raw + b_sd;  e = exp(-|a|);  softplus(a) = max(a, 0) + log1p(e);  sigmoid(a) = (a >= 0 ? 1 : e) / (1 + e)
 __device__ __forceinline__ void nll_raw_sp_elem(float c, float shift, float xv, float mraw, float sraw, float bm, float bs,
                                                 float& acc, float& gm, float& gs) {
     const float m = mraw + bm, a = sraw + bs;
     const float e = __expf(-fabsf(a));
     const float r1 = __frcp_rn(1.f + e);
-    const float s = fmaxf(a, 0.f) + __logf(1.f + e) + shift;
+    const float s = fmaxf(a, 0.f) + dv_log1p_hw(e, r1) + shift;
     const float sig = (a >= 0.f ? 1.f : e) * r1;
     const float is = __frcp_rn(s), d = xv - m, t = d * is;
     acc += kLog2Pi + 2.f * __logf(s) + t * t;
@@ -766,7 +788,7 @@ __global__ __launch_bounds__(256) void nll_rows_raw_cs_kernel(NllCsArgs a) {
 // dpre[r,g] = coef[r] * d log p / d a (the gradient w.r.t. the head's pre-activation a).
 //   Bernoulli: pc = clamp(v, 1e-10, 1 - 1e-10) (the clamp of src/blocks.py:463 applied to this decoder's probabilities);
 //              log p = x log pc + (1-x) log(1-pc);  d/da = x - v inside the clamp, 0 outside
-//   Poisson  : log p = x log v - v - lgamma(x+1);   d/da = (x/v - 1) * (1 - exp(-(v - shift)))
+//   Poisson  : log p = x log v - v - lgamma(x+1);   d/da = (x/v - 1) * sigmoid(a), sigmoid(a) = -expm1(-(v - shift))
 __device__ __forceinline__ float rec_term(int kind, float shift, float xv, float v, float& g) {
     if (kind == DV_REC_BERNOULLI) {
         const float lo = 1e-10f, hi = (float)(1.0 - 1e-10);
@@ -774,7 +796,7 @@ __device__ __forceinline__ float rec_term(int kind, float shift, float xv, float
         g = (v > lo && v < hi) ? xv - v : 0.f;
         return xv * logf(pc) + (1.f - xv) * logf(1.f - pc);
     }
-    g = (xv / v - 1.f) * (1.f - expf(-(v - shift)));
+    g = (xv / v - 1.f) * dv_softplus_slope_from_y(v - shift);
     return xv * logf(v) - v - lgammaf(xv + 1.f);
 }
 

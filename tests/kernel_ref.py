@@ -58,7 +58,7 @@ def dact_from_y(a, y):
     if a == 'elu':
         return torch.where(y > 0, one, y + 1)
     if a == 'softplus':
-        return 1 - torch.exp(-y)
+        return -torch.expm1(-y)
     if a == 'sigmoid':
         return y * (1 - y)
     if a == 'tanh':
@@ -160,8 +160,10 @@ def linear_heads(out, x, W, bias=None, *, split, x2=None, scale=None, act0=0, ac
     """the unfused sequence ``dv_gemm_heads`` replaces: heads GEMM, then reparam_fwd / nll_rows_fwdbwd"""
     M, N = out.shape
     heads = torch.zeros(M, N, device=out.device) if nll is not None else out
-    linear_fwd(heads, x, W, bias, x2=x2, scale=scale, split=split, act0=act0, act1=act1, shift0=shift0, shift1=shift1,
-               resid=resid, resid_cols=resid_cols, publish=publish, kpad=kpad)
+    # (the NLL epilogue of a softplus sigma head takes its slope from the pre-activation: the heads' raw form below)
+    sp = nll is not None and _name(act1) == 'softplus'
+    linear_fwd(heads, x, W, bias, x2=x2, scale=scale, split=split, act0=act0, act1=0 if sp else act1, shift0=shift0,
+               shift1=0.0 if sp else shift1, resid=resid, resid_cols=resid_cols, publish=publish, kpad=kpad)
     mu, sd = heads[:, :split], heads[:, split:]
     if sample is not None:
         g = sample.get
@@ -180,8 +182,9 @@ def linear_heads(out, x, W, bias=None, *, split, x2=None, scale=None, act0=0, ac
                     g('out4')[int(g('out4_ptr')[s_]):int(g('out4_ptr')[s_ + 1])] = z
     else:
         rows = torch.zeros(M, device=out.device)
+        zero = torch.zeros(split, device=out.device)
         nll_rows_fwdbwd(rows, out[:, :split], out[:, split:], nll['coef'], nll['x'], mu, sd, mode=GAUSS_SIGMA,
-                        xidx=nll.get('xidx'), sd_act=act1, sd_shift=shift1)
+                        xidx=nll.get('xidx'), sd_act=act1, sd_shift=shift1, bias=(zero, zero) if sp else None)
         nll['part'].zero_()
         nll['part'][:, 0] = rows              # (any split of a row's sum over the tiles is as good)
 
@@ -467,17 +470,26 @@ def rec_nll_rows(out, x, v, *, kind, shift=0.0, xidx=None, coef=None, dpre=None)
         g = torch.where((v > lo) & (v < hi), xs - v, torch.zeros_like(v))
     else:
         out.copy_((xs * v.log() - v - torch.lgamma(xs + 1)).sum(1))
-        g = (xs / v - 1) * (1 - torch.exp(-(v - shift)))
+        g = (xs / v - 1) * -torch.expm1(-(v - shift))
     if coef is not None:
         dpre.copy_(coef[:, None] * g)
 
 
 def nll_rows_fwdbwd(out, dmu, dsd, coef, x, mu, sd, *, mode=GAUSS_SIGMA, xidx=None, sd_act=0, sd_shift=0.0, bias=None):
-    if bias is not None:          # raw heads: finished here
-        mu = mu + bias[0]
-        sd = act_fwd(sd_act, sd + bias[1]) + sd_shift
+    if bias is None:
+        nll_rows_fwd(out, x, mu, sd, mode=mode, xidx=xidx)
+        nll_rows_bwd(dmu, dsd, coef, x, mu, sd, mode=mode, xidx=xidx, sd_act=sd_act, sd_shift=sd_shift)
+        return
+    # raw heads: finished here; the softplus slope is taken from the pre-activation (sigmoid), the others' from the output
+    pre = sd + bias[1]
+    mu = mu + bias[0]
+    sd = act_fwd(sd_act, pre) + sd_shift
     nll_rows_fwd(out, x, mu, sd, mode=mode, xidx=xidx)
-    nll_rows_bwd(dmu, dsd, coef, x, mu, sd, mode=mode, xidx=xidx, sd_act=sd_act, sd_shift=sd_shift)
+    if _name(sd_act) != 'softplus':
+        nll_rows_bwd(dmu, dsd, coef, x, mu, sd, mode=mode, xidx=xidx, sd_act=sd_act, sd_shift=sd_shift)
+        return
+    nll_rows_bwd(dmu, dsd, coef, x, mu, sd, mode=mode, xidx=xidx)
+    dsd.mul_(torch.sigmoid(pre))
 
 
 P_MIN = 1e-10
