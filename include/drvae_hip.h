@@ -909,7 +909,15 @@ int dv_flag_wait(int32_t* flag, const int32_t* ctr, int32_t add, int32_t* err, i
 
 /* out[i] ~ N(0,1), Philox4x32-10 keyed by `seed`, counter = ctr_dev[0..1] (uint64 as two
  * int32 words, device) + i/4, Box-Muller on the four outputs.  (the `normal_()` draws of
- * src/blocks.py:172,210 and src/DrVAE.py:405,415 moved on device). */
+ * src/blocks.py:172,210 and src/DrVAE.py:405,415 moved on device).
+ * Both generators, precisely (tests/philox_ref.py is this paragraph in numpy, tests/test_gpu_philox.py compares every
+ * element): a 32-bit word x becomes the uniform u = (float(x) + 0.5f) * 2^-32, evaluated in fp32 -- u is never 0
+ * (u(0) = 2^-33, hence |z| <= sqrt(-2 ln 2^-33) < 6.77) and is exactly 1 for x >= 2^32 - 128 (float(x) rounds to 2^32),
+ * where the radius and with it that pair of normals is exactly 0.  Output words 0 / 1 are the radius / angle of lanes
+ * 0, 1 (r cos a, r sin a with r = sqrt(-2 ln u0), a = 2 pi u1), words 2 / 3 those of lanes 2, 3.
+ * dv_fill_normal's counter is (lo, hi, 0, 0) of ctr + i/4 under the key (seed_lo, seed_hi): with ctr + i/4 < 2^32 that
+ * is the row-keyed stream below at (global row 0, draw id 0, event 0) under the same seed -- the two forms must not
+ * share a seed.  (The train step uses the row-keyed form only.) */
 int dv_fill_normal(float* out, int64_t n, uint64_t seed, const int32_t* ctr_dev, dv_stream_t stream);
 /* Row-keyed form for the train step's noise arena (SURVEY.md 8(e) "RNG under DP": results must not depend
  * on the number of ranks).  desc = n_rows x {offset into arena (floats), width, draw id, GLOBAL minibatch

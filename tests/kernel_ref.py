@@ -973,24 +973,25 @@ def batch_masks(B, L, *, n_tot, kl_rate, pert_rate, yl_rate, beta, c_nll, w_recl
             label[:LB] = torch.where(one_slot.repeat(L) != 0, y[src].to(label.dtype).repeat(L), label[:LB])
 
 
+def _event(ctr_dev):
+    return 0 if ctr_dev is None else ((int(ctr_dev[1]) & 0xffffffff) << 32 | (int(ctr_dev[0]) & 0xffffffff))
+
+
 def fill_normal_rows(arena, desc, seed, ctr_dev=None, park=None):
-    """Stand-in only (NOT bit-compatible with the device Philox stream), but keyed the same way: a value
-    depends on (seed, step, draw id, global row, column) only."""
+    """dv_fill_normal_rows as specified (tests/philox_ref.py, float32 of its float64 value): the device's numbers up to
+    the fp32 rounding of its Box-Muller transform"""
+    from tests import philox_ref
     if park is not None:
         flag_wait(*park)
-    base = 0 if ctr_dev is None else (int(ctr_dev[1]) << 32 | (int(ctr_dev[0]) & 0xffffffff))
-    g = torch.Generator(device='cpu')
-    for off, width, draw, grow in desc.cpu().tolist():
-        g.manual_seed((((seed * 1000003 + base) * 1000003 + draw) * 1000003 + grow) % (1 << 62))
-        arena[off:off + width] = torch.randn(width, generator=g).to(arena.device)
+    offsets, z, _, _ = philox_ref.rows_table(desc.cpu().numpy(), seed, _event(ctr_dev))
+    arena.view(-1)[torch.from_numpy(offsets).to(arena.device)] = torch.from_numpy(z.astype(np.float32)).to(arena.device)
 
 
 def fill_normal(out, seed, ctr_dev=None):
-    """Stand-in only (NOT bit-compatible with the device Philox stream)."""
-    g = torch.Generator(device='cpu')
-    base = 0 if ctr_dev is None else (int(ctr_dev[1]) << 32 | (int(ctr_dev[0]) & 0xffffffff))
-    g.manual_seed((seed * 1000003 + base) % (1 << 62))
-    out.copy_(torch.randn(out.shape, generator=g).to(out.device))
+    """dv_fill_normal as specified (tests/philox_ref.py, float32 of its float64 value)"""
+    from tests import philox_ref
+    z = philox_ref.flat(out.numel(), seed, _event(ctr_dev))[0]
+    out.copy_(torch.from_numpy(z.astype(np.float32)).view(out.shape).to(out.device))
 
 
 def nll_raw_cs_shape(M, X):
