@@ -125,6 +125,13 @@ class NllRawCs(C.Structure):     # dv_nll_raw_cs_desc
                 ('bias_mu', _p), ('bias_sd', _p), ('ws', _p), ('ldw', _i64), ('sd_off', _i64), ('row_blocks', _i32)]
 
 
+class MmdGrouped(C.Structure):   # dv_mmd_grouped_desc
+    _fields_ = [('z', _p), ('ldz', _i64), ('n_z', _i32), ('Z', _i32), ('kind', _i32), ('R', _i32), ('n_groups', _i32),
+                ('n_entries', _i32), ('max_rows', _i32), ('S', _i32), ('B', _i32), ('grp_ptr', _p), ('rows', _p), ('src', _p),
+                ('cls', _p), ('W', _p), ('b', _p), ('a', _f), ('c', _f), ('w', _f), ('fac', _f), ('theta', _p), ('diff', _p),
+                ('cnt', _p), ('m2', _p), ('value', _p), ('dz', _p), ('ldd', _i64)]
+
+
 class LossTerm(C.Structure):
     _fields_ = [('x', _p), ('w', _p), ('n', _i32), ('scale', _f), ('out', _i32), ('row_len', _i32)]
 
@@ -181,6 +188,9 @@ SIGNATURES = {
     'dv_ycont_bwd': [_p, _i64, _p, _p, _f, _i32, _p, _p, _p, _i64, _p, _i64, _i32, _i32, _i32, _p, _i64, _p, _p],
     'dv_mmd_rff_fwd': [_p, _i64, _i32, _p, _i64, _i32, _i32, _f, _p, _p, _p],
     'dv_mmd_rff_bwd': [_p, _i64, _i32, _i32, _p, _p, _f, _p, _i64, _p],
+    'dv_nuisance_feed': [_p, _p, _i32, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _i64, _p, _i64, _p, _p],
+    'dv_mmd_grouped_fwd': [C.POINTER(MmdGrouped), _p],
+    'dv_mmd_grouped_bwd': [C.POINTER(MmdGrouped), _p],
     'dv_rows_gather': [_p, _i64, _p, _i32, _i32, _p, _i64, _f, _p, _i32, _p, _i64, C.POINTER(Wait), _p],
     'dv_batch_feed': [C.POINTER(BatchFeed), C.POINTER(BatchMasks), C.POINTER(Wait), _p],
     'dv_batch_masks': [C.POINTER(BatchMasks), _p, _i32, _p, _p, _i32, _i32, _p],

@@ -115,7 +115,11 @@ def identity(x1, x2):
     return ops.MMDIdentity.apply(x1, x2)
 
 
-def mmd_fourier(x1, x2, bandwidth=2., dim_r=500):
+MMD_RFF_DIM = 500            # random features per draw (dim_r of src/blocks.py:40)
+MMD_RFF_BANDWIDTH = 2.       # ... and the bandwidth `mmd_objective` evaluates them with (src/blocks.py:66)
+
+
+def mmd_fourier(x1, x2, bandwidth=MMD_RFF_BANDWIDTH, dim_r=MMD_RFF_DIM):
     """Random-Fourier-feature MMD (src/blocks.py:40-55): draws W~N(0,1) (Z,dim_r) then
     b~U(0,1) (dim_r), in that order, from the framework generator like the reference."""
     z = x1.size(1)
@@ -134,7 +138,7 @@ def mmd_objective(x1, x2, kernel='rbf', bandwidths=1. / (2 * (np.array([1., 2., 
     if kernel == 'identity':
         return torch.sqrt(fn(x1, x2))
     if kernel == 'rbf_fourier':
-        return torch.sqrt(fn(x1, x2, bandwidth=2.))
+        return torch.sqrt(fn(x1, x2, bandwidth=MMD_RFF_BANDWIDTH))
     # the bandwidth mixture, its means and its derivative on HIP row kernels around the three Gram products on the MFMA
     # GEMM (``ops.MMDMix``).  No ATen fallback (host tensors are refused by the launchers); the row kernels hold at most
     # 8 bandwidths (the reference's default: 5)

@@ -117,8 +117,16 @@ class DeviceBatcher:
     straight into the fused step's input buffers (see the module docstring)."""
 
     def __init__(self, dataset, weights, batch_size, group_counts=None, seed=0, mode='stratified', generator='device',
-                 pair_bucket=None, label_bucket=None):
-        """``mode='stratified'`` (default): every batch has the SAME composition (the expected counts of the four
+                 pair_bucket=None, label_bucket=None, carry_s=False):
+        """``carry_s=True`` (stratified mode, single process; models conditioned on the nuisance variable, ``use_s``,
+        with or without ``use_MMD``): the nuisance classes travel as device data -- ``bind`` selects the plan that carries
+        them (``_Plan.carry_nuisance``), ``begin_epoch`` installs the dataset's ``s`` column with the feed, the captured
+        step gathers the classes of its batch itself (``dv_nuisance_feed``) and the MMD penalty reads class membership
+        inside its two grouped launches: an epoch is ``len(self)`` replays of ONE captured step whatever the batches'
+        composition of classes.  A term of the penalty with an empty side (a data group of a batch without a row of the
+        class, or with nothing else) is defined as 0 on this path.  Still refused: sampler mode with ``use_s``, and
+        ``use_MMD`` under data parallelism.  The default keeps the host-driven routes and their refusals.
+        ``mode='stratified'`` (default): every batch has the SAME composition (the expected counts of the four
         groups under the weights, or ``group_counts``) -- rows within a group drawn with replacement by weight;
         the step runs on the plan of exactly that structure.
         ``mode='sampler'``: the reference's pipeline to the letter (src/run_drvae.py:150-166):
@@ -174,8 +182,9 @@ class DeviceBatcher:
         self.batch_specs = None           # (bucketed) plan of every batch of the current epoch table: (pair slots, a, b)
         self._k = 0                       # (bucketed) batches handed out since begin_epoch
         self.n_switch = 0                 # (bucketed) how many times a step ran on another plan than the one before
+        self.carry_s = bool(carry_s)
         self.cpu_stream = generator == 'cpu'
-        self.dp = None                    # (rank, world) under data parallelism: set by ``bind(dp=...)``
+        self.dp = None                   # (rank, world) under data parallelism: set by ``bind(dp=...)``
         if mode == 'sampler':
             self.weights = w.float()
             self.weights_cpu = torch.as_tensor(weights, dtype=torch.float64).cpu().reshape(-1)
@@ -226,7 +235,11 @@ class DeviceBatcher:
         if self.dp is not None:
             assert not engine.cfg.use_MMD, 'use_MMD: the MMD penalty is a cross-row term, it cannot be sharded over ranks'
             engine.row0 = self.rank * self.batch_size
-        if engine.cfg.use_s and (engine.cfg.use_MMD or self.mode == 'sampler'):
+        carry = bool(self.carry_s and engine.cfg.use_s)
+        if carry and self.mode == 'sampler':
+            raise NotImplementedError('DeviceBatcher(carry_s=True): the nuisance classes are carried on stratified device '
+                                      'batches (a fixed batch structure); sampler mode runs on the batch-independent plan')
+        if engine.cfg.use_s and not carry and (engine.cfg.use_MMD or self.mode == 'sampler'):
             raise NotImplementedError('DeviceBatcher: models conditioned on the nuisance variable (use_s extension) run on '
                                       'stratified device batches without the MMD penalty (its row lists are host knowledge); '
                                       'otherwise feed them through run_on_batch / a tuple loader')
@@ -244,7 +257,7 @@ class DeviceBatcher:
             n_lab = int(self.has_y.sum()) if cfg.has_y else 0
             n_tot = n_lab if (cfg.kind == 'vfae' and not cfg.semi_supervised) else self.batch_size
             counts = tuple(self.world * c for c in (n_tot, int(self.has_x2.sum()) if cfg.has_pert else 0, n_lab))
-        engine.set_structure(self.has_x2, self.has_y, counts)
+        engine.set_structure(self.has_x2, self.has_y, counts, carry_s=carry)
         self._bound, self._bound_plan = sig, engine.plan
         return engine.plan
 
@@ -256,7 +269,7 @@ class DeviceBatcher:
         rank's columns of the global table.  ``table``: the GLOBAL table (n_batches, world x batch_size) given instead of
         drawn (tests; replaying a recorded epoch)."""
         eng, p = self.engine, self.engine.plan
-        if eng.cfg.use_s:
+        if eng.cfg.use_s and not p.carry_s:
             raise NotImplementedError('use_s: the graph-resident epoch feed does not carry the nuisance classes; use feed()')
         n_b = len(self) if n_batches is None else n_batches
         fd = p.feed
@@ -275,6 +288,8 @@ class DeviceBatcher:
                 fd.hx32, fd.hy32 = self.hx32, self.hy32
                 if fd.y32 is None:
                     fd.y32 = self.hy32
+            if eng.cfg.use_s:       # the dataset's nuisance column: read by the step's dv_nuisance_feed launch
+                fd.s32 = self.ds.s.reshape(-1).to(torch.int32).contiguous()
             p.feed = fd
         else:
             self._refresh_feed_rows(fd)
@@ -335,7 +350,7 @@ class DeviceBatcher:
         the GPU idle.  The batcher's generator is consumed in the same order as
         without it -- the tables are the same.  Not with ``generator='cpu'``: that stream is torch's DEFAULT generator,
         whose order against the caller's other draws is the reference's."""
-        if self.cpu_stream or self.engine.cfg.use_s:
+        if self.cpu_stream or (self.engine.cfg.use_s and not self.carry_s):
             return
         n_b = len(self) if n_batches is None else n_batches
         dev = self.ds.x1.device

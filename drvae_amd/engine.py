@@ -190,6 +190,10 @@ class FusedStep(StepSchedule):
         self.universal = False
         self.universal_pair_slots = None      # (set_batch on the universal plan) only the first so many rows may be pairs
         self.universal_labeled_range = None   # ... and rows [a, b) are labeled for sure (one fprop row each)
+        # ``use_s`` models: explicit batches (``set_batch``) go to plans that carry the nuisance classes on the device
+        # (``_Plan.carry_nuisance``; ``s`` may then be a device tensor, no host round trip, and the MMD penalty runs as its
+        # two grouped launches) -- the plans ``DeviceBatcher(carry_s=True)`` binds.  Default: the host-list plans
+        self.carry_s = False
         self.plan = None
         self._plans = {}                    # plans by batch structure (a handful of signatures in practice)
         self.max_plans = 8
@@ -325,10 +329,12 @@ class FusedStep(StepSchedule):
             if old != keep and old != self._graph_key and old not in self._captures and old not in self.pinned_plans:
                 del self._plans[old]
 
-    def set_structure(self, has_x2, has_y, counts=None):
+    def set_structure(self, has_x2, has_y, counts=None, carry_s=None):
         """Select (or build) the plan for a batch STRUCTURE: which rows are pairs / labeled.
-        Returns (plan, rows) where ``rows`` are the participating row positions."""
+        Returns (plan, rows) where ``rows`` are the participating row positions.  ``carry_s`` (``use_s`` models; default:
+        ``self.carry_s``): the plan that carries the nuisance classes on the device -- a plan of its own."""
         cfg = self.cfg
+        carry = bool(cfg.use_s and (self.carry_s if carry_s is None else carry_s))
         has_x2 = np.asarray(has_x2.cpu() if torch.is_tensor(has_x2) else has_x2).astype(bool).reshape(-1)
         has_y = np.asarray(has_y.cpu() if torch.is_tensor(has_y) else has_y).astype(bool).reshape(-1)
         if not cfg.has_pert:
@@ -341,10 +347,14 @@ class FusedStep(StepSchedule):
         # the plan (index lists, buffers, captured graph) depends on the group STRUCTURE only; the
         # class labels of the labeled rows are data and are refreshed in place
         key = (len(rows), has_x2[rows].tobytes(), has_y[rows].tobytes(), counts, self.row0)
+        if carry:
+            key = key + ('carry_s',)
         if self.plan is None or self.plan.key != key:
             self.plan = self._plans.get(key)
             if self.plan is None:
                 self.plan = self._plans[key] = _Plan(self, rows, has_x2[rows], has_y[rows], counts, key)
+                if carry:
+                    self.plan.carry_nuisance()
                 self._evict_plans(key)
         return self.plan, rows
 
@@ -357,6 +367,12 @@ class FusedStep(StepSchedule):
         if cfg.use_s:
             assert s is not None, 'use_s: the nuisance classes of the batch are needed'
             p = self._set_batch(x1, x2, y, has_x2, has_y, counts)
+            if p.carry_s:       # device to device: the same launch the epoch feed runs, on the batch's own classes
+                sd = (s if torch.is_tensor(s) else torch.as_tensor(np.asarray(s))).reshape(-1).to(self.dev)
+                if len(p.rows) != sd.numel():
+                    sd = sd.index_select(0, torch.as_tensor(p.rows, device=self.dev))
+                p.set_s_device(sd)
+                return p
             sv = np.asarray(s.cpu() if torch.is_tensor(s) else s).astype(np.int64).reshape(-1)
             p.set_s_host(sv[p.rows])
             return p
@@ -589,6 +605,12 @@ class FusedStep(StepSchedule):
                          onehot2=p.FPIN[:, Z1:] if (lab and p.Mf) else None,
                          yf=fd.yf if (cfg.has_y and cfg.cont) else None,
                          ylab=p.ylab if (cfg.has_y and cfg.cont) else None, masks=masks)
+            if cfg.use_s:
+                # the nuisance classes of the same batch of the table: one-hot columns of the stacked encoder / decoder
+                # rows and the class vector the MMD penalty reads (a launch of its own: the feed's descriptor stays as it is)
+                assert p.carry_s and getattr(fd, 's32', None) is not None, 'use_s: this feed does not carry the nuisance classes'
+                K.nuisance_feed(p.SOHe, p.SOHd, p.s_cls, fd.s32, table=fd.table, n_batches=fd.n_batches, ctr=self.step_dev,
+                                base=fd.base, pair_rows=p.pair_idx if Np else None, L=L)
         else:
             K.rows_gather(p.XIN, p.XSRC, p.xin_idx, noise=p.EX if sigma else None, sigma=sigma, park=start_park)
         # ---- q(z1|x1), q(z2|x2): one pass of the shared encoder; the samples (src/blocks.py:170-174) -- z1
@@ -879,6 +901,17 @@ class FusedStep(StepSchedule):
         graph-safe device generator; a captured step is valid for the composition of nuisance classes it was
         captured with (``replay`` checks)."""
         cfg, p = self.cfg, self.plan
+        if p.mmd_grouped is not None:
+            # device-carried nuisance classes: ALL terms in one launch per direction, membership read from ``s_cls``; fresh
+            # random features for every term from torch's graph-safe device generator (two launches), kept readable in the
+            # stacked buffers.  An empty side of a term and a zero difference are defined as value 0, gradient 0 (DESIGN.md 9)
+            g = p.mmd_grouped
+            if g['W'] is not None:
+                g['W'].normal_()
+                g['b'].uniform_()
+            K.mmd_grouped_fwd(g)
+            K.mmd_grouped_bwd(g)
+            return
         if cfg.kernel_MMD in ('rbf_fourier', 'identity') and getattr(p, 'mmd_items', None) and T.get('mmd_explicit'):
             return self._mmd_penalty_launches()
         from . import blocks as blk

@@ -230,7 +230,8 @@ class FitMixin:
         batcher.bind(eng, counts=getattr(self, '_global_counts', None), dp=self._dp)
         eng.add_noise = bool(self.add_noise)
         eng.iters = self.finished_training_iters
-        resident_feed = not eng.cfg.use_s      # (the nuisance classes travel with host-driven gathers: feed())
+        # (use_s: the nuisance classes travel with the feed when the batcher carries them; else host-driven gathers: feed())
+        resident_feed = not eng.cfg.use_s or bool(getattr(batcher, 'carry_s', False))
         if resident_feed:
             batcher.begin_epoch()           # this epoch's index table; the graph gathers batch b itself
             if getattr(batcher, 'bucketed', False):

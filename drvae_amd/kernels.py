@@ -688,6 +688,55 @@ def mmd_identity_bwd(dx, diff, gout, coef):
                                                _stream()), 'dv_mmd_identity_bwd')
 
 
+def nuisance_feed(sohe, sohd, cls, s32, *, table=None, n_batches=0, ctr=None, base=None, pair_rows=None, L=1):
+    """classes of a batch's rows -> one-hot columns of the stacked encoder (``sohe``) / decoder (``sohd``) rows and the
+    class vector ``cls`` (B, int32); ``s32``: the dataset's column read through batch (ctr - base) of ``table``, or
+    (``table`` None) the batch's own B classes.  See ``dv_nuisance_feed``"""
+    B, S = cls.numel(), sohe.shape[1]
+    Np = pair_rows.numel() if pair_rows is not None else 0
+    assert sohe.shape[0] == B + Np and sohd.shape[0] == L * B + 2 * L * Np and sohd.shape[1] == S
+    assert table is None or (tuple(table.shape) == (n_batches, B) and table.is_contiguous())
+    assert table is not None or s32.numel() == B
+    _lib.check(_lib.load().dv_nuisance_feed(_i32(s32), _i32(table), n_batches, _i32(ctr), _i32(base), B, _i32(pair_rows), Np,
+                                            L, S, _f32(sohe), _ld(sohe), _f32(sohd), _ld(sohd), _i32(cls), _stream()),
+               'dv_nuisance_feed')
+
+
+MMD_GROUPED_KIND = {'identity': 0, 'rbf_fourier': 1}
+MMD_MAX_CLASSES = 8         # DV_MMD_MAX_CLASSES
+
+
+def _mmd_grouped_desc(g):
+    """``g``: the operands of the grouped MMD penalty by name (``_Plan``'s term table, see ``dv_mmd_grouped_desc``)"""
+    z, dz, rff = g['z'], g['dz'], g['kind'] == 'rbf_fourier'
+    n_groups, E, Kc = g['grp_ptr'].numel() - 1, g['rows'].numel(), (1 if g['S'] == 2 else g['S'])
+    D = g['R'] if rff else z.shape[1]
+    assert g['src'].numel() == E and tuple(g['diff'].shape) == (n_groups * Kc, D) and g['diff'].is_contiguous()
+    assert tuple(g['cnt'].shape) == (n_groups, g['S']) and g['m2'].numel() == n_groups * Kc and dz.shape == z.shape
+    if rff:
+        assert tuple(g['W'].shape) == (n_groups * Kc, z.shape[1], g['R']) and g['W'].is_contiguous()
+        assert tuple(g['b'].shape) == (n_groups * Kc, g['R']) and g['b'].is_contiguous()
+        assert tuple(g['theta'].shape) == (Kc * E, g['R']) and g['theta'].is_contiguous()
+    return _lib.MmdGrouped(z=_f32(z), ldz=_ld(z), n_z=z.shape[0], Z=z.shape[1], kind=MMD_GROUPED_KIND[g['kind']],
+                           R=g['R'] if rff else 0, n_groups=n_groups, n_entries=E, max_rows=g['max_rows'], S=g['S'],
+                           B=g['cls'].numel(), grp_ptr=_i32(g['grp_ptr']), rows=_i32(g['rows']), src=_i32(g['src']),
+                           cls=_i32(g['cls']), W=_f32(g['W']) if rff else None, b=_f32(g['b']) if rff else None, a=g['a'],
+                           c=g['c'], w=g['w'], fac=g['fac'], theta=_f32(g['theta']) if rff else None, diff=_f32(g['diff']),
+                           cnt=_i32(g['cnt']), m2=_f32(g['m2']), value=_f32(g['value']), dz=_f32(dz), ldd=_ld(dz))
+
+
+def mmd_grouped_fwd(g):
+    """feature-mean differences of every MMD term of a step, one launch (``dv_mmd_grouped_fwd``)"""
+    d = _mmd_grouped_desc(g)
+    _lib.check(_lib.load().dv_mmd_grouped_fwd(C.byref(d), _stream()), 'dv_mmd_grouped_fwd')
+
+
+def mmd_grouped_bwd(g):
+    """the penalty's value and its gradient w.r.t. the sample rows, one launch (``dv_mmd_grouped_bwd``)"""
+    d = _mmd_grouped_desc(g)
+    _lib.check(_lib.load().dv_mmd_grouped_bwd(C.byref(d), _stream()), 'dv_mmd_grouped_bwd')
+
+
 def rows_gather(out, src, idx=None, *, noise=None, sigma=0.0, onehot_cls=None, n_classes=0, width=None, park=None):
     n = out.shape[0]
     W = (src.shape[1] if src is not None else 0) if width is None else width

@@ -243,6 +243,68 @@ class _Plan:
         """the installed epoch feed if it is the current input source, else None (inputs come from XSRC)"""
         return self.feed if self.feed_active else None
 
+    # device-carried nuisance classes (``carry_nuisance``): the classes of the batch's rows are DEVICE data -- written by
+    # ``set_s_device`` or by the epoch feed's dv_nuisance_feed launch -- and the MMD penalty reads them inside its two
+    # grouped launches: nothing of such a plan depends on the batch's composition of classes
+    carry_s = False
+    mmd_grouped = None
+
+    def carry_nuisance(self):
+        """make this plan one that carries the nuisance classes on the device (called once, right after construction):
+        the class vector ``s_cls`` and, with ``use_MMD``, the penalty's constant term table and every buffer of its two
+        launches (``dv_mmd_grouped_fwd`` / ``_bwd``), from the batch STRUCTURE alone.  Term groups in the reference's
+        order of data groups (src/DrVAE.py:585-608; src/PVAE.py:441-453; src/VFAE.py:421-433), per Monte-Carlo sample, on
+        z1 and (pairs) z2 (src/DrVAE.py:537-540): the rows ``l B + idx_g`` / ``o2 + l Np + slot[idx_g]`` of the stacked
+        sample rows"""
+        from .blocks import MMD_RFF_BANDWIDTH, MMD_RFF_DIM
+        cfg, dev = self._cfg, self.ZDEC.device
+        assert cfg.use_s and not self.universal
+        L, B, Np, Z, S = cfg.L, self.B, self.Np, cfg.dim_z1, cfg.dim_s
+        i32 = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.int32, device=dev)
+        zf = lambda *s: torch.zeros(*s, device=dev)
+        self.carry_s = True
+        self.s_cls = i32(np.zeros(B))
+        if not cfg.use_MMD:
+            return self
+        assert cfg.kernel_MMD in K.MMD_GROUPED_KIND, 'use_MMD on device-carried nuisance classes: kernel_MMD rbf_fourier | identity'
+        assert 2 <= S <= K.MMD_MAX_CLASSES and B > 0
+        hx = self._hx_host
+        hy = self._has_y_host.astype(bool) if cfg.has_y else np.zeros(B, bool)
+        if cfg.kind == 'drvae':
+            masks = [hy & ~hx, ~hy & ~hx, hy & hx, ~hy & hx]
+        elif cfg.kind == 'pvae':
+            masks = [~hx, hx]
+        else:
+            masks = [hy, ~hy]
+        slot = np.full(B, -1, np.int64)
+        slot[self.pair_host] = np.arange(Np)
+        rows, src, ptr = [], [], [0]
+        for m in masks:
+            idx = np.nonzero(m)[0]
+            if len(idx) == 0:
+                continue
+            for l in range(L):
+                for r in [l * B + idx] + ([self.o2 + l * Np + slot[idx]] if hx[idx[0]] else []):
+                    rows.append(r)
+                    src.append(idx)
+                    ptr.append(ptr[-1] + len(idx))
+        n_groups, E, Kc = len(rows), ptr[-1], (1 if S == 2 else S)
+        # every sample row sits in exactly one group: the backward launch WRITES every row of DZMMD, no zero fill
+        assert sorted(np.concatenate(rows).tolist()) == list(range(self.o3))
+        rff = cfg.kernel_MMD == 'rbf_fourier'
+        R = MMD_RFF_DIM if rff else 0
+        self.mmd_grouped = dict(
+            z=self.ZDEC[:self.o3], dz=self.DZMMD, kind=cfg.kernel_MMD, R=R, S=S, cls=self.s_cls, grp_ptr=i32(ptr),
+            rows=i32(np.concatenate(rows)), src=i32(np.concatenate(src)), max_rows=int(np.diff(ptr).max()),
+            a=math.sqrt(2. / MMD_RFF_BANDWIDTH) / math.sqrt(Z), c=math.sqrt(2. / R) if rff else 1.0,
+            w=(1.0 if S == 2 else 1.0 / S) / L, fac=-cfg.mmd_rate / self.n_tot,
+            diff=zf(n_groups * Kc, R if rff else Z), cnt=torch.zeros(n_groups, S, dtype=torch.int32, device=dev),
+            m2=zf(n_groups * Kc), value=self.MMDval,
+            # fresh W ~ N(0,1), b ~ U(0,1) for every term of every step (src/blocks.py:40-55), stacked
+            W=zf(n_groups * Kc, Z, R) if rff else None, b=zf(n_groups * Kc, R) if rff else None,
+            theta=zf(Kc * E, R) if rff else None)
+        return self
+
     def set_s_host(self, sv):
         """nuisance classes of this batch's rows (``use_s`` extension): one-hot columns of the stacked encoder
         and decoder rows, and the row lists of the model-level MMD penalty (per data group and sample)"""
@@ -311,6 +373,10 @@ class _Plan:
         the one-hot columns of the stacked encoder / decoder rows are rebuilt device to device, no host round trip.
         Not with the model-level MMD penalty, whose row lists are host knowledge (``set_s_host``)."""
         cfg = self._cfg
+        if self.carry_s:       # one launch: the one-hot columns and the class vector the grouped MMD penalty reads
+            sv = s_dev.reshape(-1).to(torch.int32).contiguous()
+            K.nuisance_feed(self.SOHe, self.SOHd, self.s_cls, sv, pair_rows=self.pair_idx if self.Np else None, L=cfg.L)
+            return
         assert not cfg.use_MMD, 'use_MMD: the penalty needs the nuisance classes on the host (set_s_host)'
         L = cfg.L
         sv = s_dev.reshape(-1).to(torch.int32)

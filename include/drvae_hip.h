@@ -791,6 +791,68 @@ int dv_mmd_identity_fwd(const float* x1, int64_t ld1, int32_t n1, const float* x
 int dv_mmd_identity_bwd(const float* diff, const float* gout, float coef, int32_t n, int32_t Z, float* dx, int64_t ldd,
                         dv_stream_t stream);
 
+/* ------------------------------------------- the nuisance variable s as device data (use_s / use_MMD extension)
+ * dv_nuisance_feed: the classes of a batch's rows, gathered like dv_batch_feed gathers the rows themselves --
+ * batch b = clamp(ctr[0] - base[0], 0, n_batches-1) of the epoch's index table, c_i = s[table[b, i]] (s: the dataset's
+ * column, int32); table == NULL: s is batch-local, c_i = s[i].  One launch, constant arguments (capturable):
+ *   cls[i] = c_i                                     (B)
+ *   sohe[r, k] = (k == c_i(r)),  k < S:  encoder rows  r <  B: i = r;   r >= B: i = pair_rows[r - B]        (B + Np rows)
+ *   sohd[r, k] = (k == c_i(r)):          decoder rows  r < L B: i = r % B;  then L Np + L Np rows of the pairs,
+ *                                                      i = pair_rows[j % Np]                          (L B + 2 L Np rows)
+ * -- `torch.cat([x, one_hot(s)], 1)` of src/DrVAE.py:134-135,179-180 for the stacked rows of the fused step. */
+int dv_nuisance_feed(const int32_t* s, const int32_t* table, int32_t n_batches, const int32_t* ctr, const int32_t* base,
+                     int32_t B, const int32_t* pair_rows, int32_t Np, int32_t L, int32_t S, float* sohe, int64_t lde,
+                     float* sohd, int64_t ldd, int32_t* cls, dv_stream_t stream);
+/* Model-level MMD penalty between the nuisance classes' latent samples (src/DrVAE.py:394-398,537-540; src/DGMMixin.py:42-66)
+ * for ALL terms of a step, class membership read from `cls` inside the launch.  A term GROUP g (data group, Monte-Carlo
+ * sample, latent z1 | z2) is a constant list of rows of z: entries [grp_ptr[g], grp_ptr[g+1]) of `rows` (row of z) and
+ * `src` (batch row of that sample: its class is cls[src]).  For every class k < K (K = S, or 1 when S == 2: the first
+ * class against the rest only) there is a term t = g K + k; with n0 / n1 the group's rows inside / outside class k and
+ * u_j = [c_j == k] / n0 - [c_j != k] / n1:
+ *   kind 1 (rbf_fourier): theta[(k E + e), r] = a z_j . W[t, :, r] + 2 pi b[t, r]   (E = n_entries, e = the row's entry)
+ *                         diff[t, r] = c sum_j u_j cos(theta_jr)                     (D = R columns)
+ *   kind 0 (identity):    diff[t, d] = sum_j u_j z_j[d]                              (D = Z columns)
+ *   m2[t] = sum_d diff[t, d]^2;   value[0] = sum_t -w sqrt(m2[t])
+ *   dz[row_j, :] = sum_k d(fac * -w sqrt(m2[t])) / d z_j        (every row of z belongs to exactly ONE group: written, not added)
+ * Defined edge cases: a term with an empty side (n0 == 0 or n1 == 0) has diff = 0; a term with m2 == 0 has value 0 and
+ * gradient 0 (no division by zero).
+ * _fwd writes cnt (n_groups x S: the group's rows per class), theta (kind 1) and diff; _bwd reads them back (theta is read
+ * back, not recomputed: half the backward's products for K E R floats that stay in L2) and writes m2, value and dz.
+ * No atomics: one writer per element.  _bwd: DV_ERR_UNSUPPORTED when 8 rows of (R + Z) floats do not fit 60 KB of LDS. */
+#define DV_MMD_MAX_CLASSES 8
+typedef struct dv_mmd_grouped_desc {
+    const float* z;
+    int64_t ldz;
+    int32_t n_z;         /* rows of z / dz */
+    int32_t Z;
+    int32_t kind;
+    int32_t R;
+    int32_t n_groups;
+    int32_t n_entries;   /* grp_ptr[n_groups] */
+    int32_t max_rows;    /* the longest group */
+    int32_t S;
+    int32_t B;           /* entries of cls */
+    const int32_t* grp_ptr;
+    const int32_t* rows;
+    const int32_t* src;
+    const int32_t* cls;
+    const float* W;      /* (n_groups K, Z, R) */
+    const float* b;      /* (n_groups K, R) */
+    float a;
+    float c;
+    float w;
+    float fac;
+    float* theta;        /* (K n_entries, R) */
+    float* diff;         /* (n_groups K, D) */
+    int32_t* cnt;        /* (n_groups, S) */
+    float* m2;           /* (n_groups K) */
+    float* value;
+    float* dz;
+    int64_t ldd;
+} dv_mmd_grouped_desc;
+int dv_mmd_grouped_fwd(const dv_mmd_grouped_desc* d, dv_stream_t stream);
+int dv_mmd_grouped_bwd(const dv_mmd_grouped_desc* d, dv_stream_t stream);
+
 /* The tail of a whole-set evaluation (round 5) in three launches instead of ~75 small library ones:
  * dv_recon_finalize: out[0..3] = rmse, variance-weighted R^2, mean per-row Pearson r, mean log-likelihood (float64) from
  *   dv_recon_row_stats' rows (M_all x 6; `sel`: the n rows that count, NULL = rows 0..n-1), dv_col_moments' partials over
