@@ -33,7 +33,7 @@ from ._lib import GAUSS_LOGVAR, GAUSS_SIGMA
 from .arena import N_LOSS, ParamArena, span
 from .chain import _Chain, _Lin, _pad4
 from .plan import LOSS_IDX, _Plan
-from .schedule import StepSchedule, _Branch
+from .schedule import DUAL, EVAL, FORK_JOIN, StepSchedule, StepSync, _Branch
 
 
 
@@ -216,8 +216,8 @@ class FusedStep(StepSchedule):
         self._init_schedule_state()
         self.side_ctr = torch.zeros(1, dtype=torch.int32, device=self.dev)   # the side chain's own step count
         self.side_t = torch.ones(1, dtype=torch.int32, device=self.dev)      # ... + 1: the optimiser step it works on
-        self.flags = torch.zeros(8, dtype=torch.int32, device=self.dev)
-        self.sync_err = torch.zeros(14, dtype=torch.int32, device=self.dev)  # (error, ticks parked) x 7 wait sites
+        self.sync = StepSync(self.dev)      # the flags / (error, ticks parked) words of the chains' hand-shake, by name
+        self.flags, self.sync_err = self.sync.flags, self.sync.err
         self.add_noise = True               # `fit(add_noise=...)` flag of the reference (src/DrVAE.py:769)
         # classifier/fprop chain || decoder chain.  PVAE's side chain is one tiny KL kernel: a second stream
         # costs it far more than it hides (measured 0.19 ms single-stream vs 0.9 ms forked), so it runs serial
@@ -455,7 +455,7 @@ class FusedStep(StepSchedule):
         Philox counter is advanced later, together with the step counter, by ``optimizer_step`` (one
         launch less on the train step's critical path)."""
         n = 1       # the Philox counter counts draw EVENTS (row-keyed draws: see ``_Plan.noise_desc``)
-        if self._rec == 'main' and self.noise_ahead:
+        if self._rec == 'main' and self._tail.noise_ahead:
             self._rng_pending = n         # dual-graph step: the side chain of the PREVIOUS step has drawn them
             return
         desc = self.plan.noise_desc
@@ -488,8 +488,8 @@ class FusedStep(StepSchedule):
         """The forward pass as a launch sequence; this function only schedules its phases: ``_encoder_forward`` (inputs,
         q(z1|x1), q(z2|x2), perturbation function, samples), then two independent chains -- ``_decoder_forward`` (the big
         GEMMs + NLL) and ``_side_forward`` (fprop / classifier: many small launches).  How the two chains are ordered
-        depends on ``_mode()``: 5 = each chain is recorded into its own graph (``_rec`` says which one is being recorded)
-        and device flags order them; 3 = one graph, one fork/join per step; 0 = plain evaluation."""
+        depends on ``_mode()``: DUAL = each chain is recorded into its own graph (``_rec`` says which one is being recorded)
+        and device flags order them; FORK_JOIN = one graph, one fork/join per step; EVAL = plain evaluation."""
         cfg, p = self.cfg, self.plan
         if not self.fuse_bwd and self.dev.type == 'cuda' and not torch.cuda.is_current_stream_capturing():
             self.join_side()        # an evaluation forward reads parameters the side chain's tail may still be updating
@@ -507,13 +507,12 @@ class FusedStep(StepSchedule):
         # ---- two independent chains from here: the classifier / fprop chain (many small launches)
         # runs on a side stream next to the decoder chain (the big GEMMs)
         mode = self._mode()
-        if mode == 5:
-            two = cfg.has_pert                      # flag 0: z1 samples final; flag 2: z2Fz1 samples final
+        if mode == DUAL:
+            two = cfg.has_pert                      # the decoder's first launch publishes its input final: z2Fz1 samples, else z1
             if rec == 'side' and not cfg.has_y:
                 return              # (PVAE: the side chain is the step's tail only, see ``_side_graph_tail``)
             if rec == 'side':
-                w0 = (self.flags[0:1], self.side_ctr, self.sync_err[2:4])
-                w2 = (self.flags[2:3], self.side_ctr, self.sync_err[4:6])
+                w0, w2 = self.sync.wait('z1', self.side_ctr), self.sync.wait('z2f', self.side_ctr)
                 # the FIRST wait is long by design (the side graph is launched first and sits out the encoder): it
                 # stays a one-thread launch -- folded into the 180-workgroup gather behind it, the polling of 180
                 # workgroups for ~45 us slowed the main chain by 14 % (0.204 -> 0.233 ms).  The second wait has
@@ -522,17 +521,17 @@ class FusedStep(StepSchedule):
                 self._side_forward(Qmu, Qlv, Z1blk, (lambda: K.flag_wait(*w2)) if two else None,
                                    mid_park=w2 if (two and not cfg.cont) else None)
                 return
-            pub = (self.flags[2:3] if two else self.flags[0:1], self.step_dev, 1)
+            pub = self.sync.pub('z2f' if two else 'z1', self.step_dev)
             if self.L_decx[0].g is not None:             # WeightNorm: the chain's first launch is not the GEMM
-                K.flag_publish(pub[0], pub[1], 1)
+                K.flag_publish(*pub)
                 pub = None
         else:
             if not self._late_fork:
                 self.branch.fork()
             pub = None
         self._decoder_forward(pub)
-        if mode == 5:
-            klz2 = (self._klz2_on_main() or not cfg.has_y) and cfg.has_pert and Np
+        if mode == DUAL:
+            klz2 = (self._tail.klz2_on_main or not cfg.has_y) and cfg.has_pert and Np
             P2 = p.c_z2F.out[-1] if klz2 else None
             z2 = ((p.KLZ2, p.KLZ2raw, Qmu, Qlv, P2[:, :Z1], P2[:, Z1:]),
                   dict(qidx=p.qz2_idx, pidx=p.pidx, reps=L, free_bits=True, kl_min=cfg.kl_min)) if klz2 else None
@@ -548,7 +547,7 @@ class FusedStep(StepSchedule):
             return             # main-chain graph: the side chain lives in its own graph on the side stream
         with self.branch:
             self._side_forward(Qmu, Qlv, Z1blk)
-        if mode == 3:
+        if mode == FORK_JOIN:
             return             # train step, single fork/join: the side chain runs on into its backward
         self.branch.join()
         if self.fuse_bwd:
@@ -566,12 +565,10 @@ class FusedStep(StepSchedule):
         fd = p.live_feed if (self.fuse_bwd and self.training) else None
         # (dual-graph schedule) the step's first launch is where the main chain meets the PREVIOUS step's side chain: its
         # tail (its half of the optimiser sweep, the loss scalars, this step's noise, its counters) must be through --
-        # flag 3, published by the tail's last launch.  The optimiser launch used to park on that flag (4.3 us per step
+        # flag ``tail``, published by the tail's last launch.  The optimiser launch used to park on that flag (4.3 us per step
         # at cfg 2, 7.6 us with the sampler feed: the tail is 44-49 us of serial launches against 35 us of main-chain
-        # launches behind the join); it only needs the classifier's gradient (flag 6)
-        start_park = None
-        if rec == 'main' and self._tail_gated():
-            start_park = (self.flags[3:4], self.step_dev, self.sync_err[12:14], 0)
+        # launches behind the join); it only needs the classifier's gradient (flag ``clf_dw``)
+        start_park = self.sync.wait('next_step', self.step_dev, add=0) if (rec == 'main' and self._tail.tail_gated) else None
         masks = None
         if p.universal:
             # which rows of THIS batch are pairs / labeled -> coefficient and weight vectors, on the device (with
@@ -617,7 +614,6 @@ class FusedStep(StepSchedule):
         # for every row and z2 for the pairs, drawn from q(z1|x1), not q(z2|x2) (quirk 1, src/DrVAE.py:427) --
         # leave the heads' launch itself (``fuse_heads``) or one launch of their own
         fuse = self.fuse_heads and self._heads_small(p.DPX)
-        Z1blk = p.ZDEC[:L * B]
         if fuse:
             # (... and every z1 sample is copied into the z1 columns of its fprop rows on the way out: the side
             # chain's gather is gone)
@@ -633,7 +629,7 @@ class FusedStep(StepSchedule):
         if cfg.has_pert:
             # (dual-graph schedule) entry of this launch = the z1 samples are final: lets the side
             # chain's fprop start before the perturbation function has run
-            pub1 = (self.flags[0:1], self.step_dev, 1) if rec == 'main' else None
+            pub1 = self.sync.pub('z1', self.step_dev) if rec == 'main' else None
             if fuse:
                 # z2Fz1 sample, the classifier input z2Fz1 - z1, and the decoder's copy for the pairs
                 p.c_z2F.forward([Z1blk], resid=Z1blk, publish=pub1, heads=dict(sample=dict(
@@ -701,11 +697,11 @@ class FusedStep(StepSchedule):
         else:
             K.nll_rows_fwd(p.NLL, p.XIN, PX[:, :X], PX[:, X:], mode=GAUSS_SIGMA, xidx=p.tgt)
 
-    def _side_forward(self, Qmu, Qlv, Z1blk, mid=None, first_park=None, mid_park=None):
+    def _side_forward(self, Qmu, Qlv, Z1blk, mid=None, mid_park=None):
         """fprop first: it only needs the z1 samples, so (dual-graph schedule) it can start before
-        the perturbation function has run; ``mid`` then waits for the z2Fz1 samples.  ``first_park`` / ``mid_park``
-        (dual-graph schedule): the two waits ride on the launch that follows them where that is a row kernel
-        with a small grid (one launch less each); else ``mid`` / a wait launch of its own."""
+        the perturbation function has run; ``mid`` then waits for the z2Fz1 samples.  ``mid_park``
+        (dual-graph schedule): that wait rides on the launch that follows it where that is a row kernel
+        with a small grid (one launch less); else ``mid``, a wait launch of its own."""
         cfg, p = self.cfg, self.plan
         B, Np, L, Z1 = p.B, p.Np, cfg.L, cfg.dim_z1
         if cfg.kind == 'pvae':
@@ -736,19 +732,11 @@ class FusedStep(StepSchedule):
                           kl_min=cfg.kl_min, add=p.KL3)
             return
         # ---- fprop over (labeled: true class | unlabeled: every class)
-        # (a parked launch polls from every workgroup: small grids only -- the C side refuses more than 512)
-        if first_park is not None and not (cfg.has_y and p.Mf and (p.Mf * (Z1 + cfg.dim_y) + 255) // 256 <= 256):
-            K.flag_wait(*first_park)
-            first_park = None
         if cfg.has_y:
             if p.Mf:
                 Z3, Y = cfg.dim_z3, cfg.dim_y
-                if self._fprop_from_heads():
-                    if first_park is not None:
-                        K.flag_wait(*first_park)
-                else:
-                    K.rows_gather(p.FPIN, Z1blk, p.fp_src, onehot_cls=p.fp_cls, n_classes=Y,
-                                  park=(first_park[0], first_park[1], first_park[2]) if first_park is not None else None)
+                if not self._fprop_from_heads():
+                    K.rows_gather(p.FPIN, Z1blk, p.fp_src, onehot_cls=p.fp_cls, n_classes=Y)
                 # (evaluation passes over many fprop rows -- whole-set evaluation: 24576 -- take the plain product + row pass:
                 # the 32 x (16 + 16) paired-heads tiles are the latency-bound sizes' kernel; 3.33 -> 3.27 ms per pair)
                 if self.fuse_heads and (self.fuse_bwd or p.Mf < 8192):
@@ -775,7 +763,8 @@ class FusedStep(StepSchedule):
         # main chain's z2Fz1 backward and the loss scalars -- in the dual-graph train step the MAIN chain computes
         # it (it has time to spare in front of the join, the side chain has not); then the wait for the z2Fz1
         # samples rides on the classifier launch
-        klz2_here = cfg.has_pert and Np and not self._klz2_on_main()
+        klz2_here = cfg.has_pert and Np and not self._tail.klz2_on_main
+        # (a parked launch polls from every workgroup: small grids only -- the C side refuses more than 512)
         clf_park = (mid_park is not None and not klz2_here and cfg.has_y and self.clf_small
                     and (L * B + 3) // 4 <= 256)
         fold_mid = mid_park is not None and klz2_here and (L * Np + 3) // 4 <= 256
@@ -784,8 +773,7 @@ class FusedStep(StepSchedule):
         if klz2_here:
             P2 = p.c_z2F.out[-1]
             K.kl_rows_fwd(p.KLZ2, p.KLZ2raw, Qmu, Qlv, P2[:, :Z1], P2[:, Z1:], qidx=p.qz2_idx, pidx=p.pidx,
-                          reps=L, free_bits=True, kl_min=cfg.kl_min,
-                          park=(mid_park[0], mid_park[1], mid_park[2]) if fold_mid else None)
+                          reps=L, free_bits=True, kl_min=cfg.kl_min, park=mid_park if fold_mid else None)
         # ---- q(y|.)
         if cfg.has_y:
             if cfg.kind == 'drvae':
@@ -803,8 +791,7 @@ class FusedStep(StepSchedule):
                     fk = dict(Q=p.c_enc.out[-1], qidx=p.fp_q, P=p.c_dz1.out[-1], Q3=p.c_top.out[-1], Z1=Z1,
                               Z3=cfg.dim_z3, kl_min=cfg.kl_min, raw1=p.KL1raw, raw3=p.KL3raw, dq=p.DQFP, dp=p.DPZ1)
                 K.smalln_fwd(p.QY, None, clf_in[0], lc.W, lc.b, clf_in[1] if len(clf_in) > 1 else None,
-                             ymarg=ym if self.fuse_bwd else None,
-                             park=(mid_park[0], mid_park[1], mid_park[2]) if clf_park else None, fprop_kl=fk)
+                             ymarg=ym if self.fuse_bwd else None, park=mid_park if clf_park else None, fprop_kl=fk)
             else:
                 K.softmax_clamp_fwd(p.QY, p.c_clf.forward(clf_in), sigmoid1=cfg.clf_1sig)
             if self.fuse_bwd and self.clf_small:
@@ -824,32 +811,15 @@ class FusedStep(StepSchedule):
         if self._side_graph is not None and self.dev.type == 'cuda':
             torch.cuda.current_stream().wait_stream(self.flag_side)
 
-    def _dual_capable(self):
+    def _dual_capable(self, on_gpu=None):
         """may this model's train step run as two flag-ordered graphs?  With a classifier the side chain is the fprop /
         classifier chain and the step's tail; PVAE (no classifier) has only the tail to give it -- the decoder heads' half of
         the optimiser sweep, the loss scalars, the next step's noise (cfg 1: 20 serial launches -> 16 + a 4-launch tail)"""
+        # (``on_gpu``: see ``_step_tail``)
         cfg = self.cfg
         if cfg.has_y:
-            return self.branch.on
+            return self.branch.on if on_gpu is None else bool(self.concurrent and on_gpu)
         return bool(cfg.kind == 'pvae' and self.concurrent and cfg.optim_alg == 'adam')
-
-    def _late_ok(self):
-        """the side chain carries the step's leaf work (classifier dW, heads' optimiser half, loss scalars) behind the join"""
-        cfg = self.cfg
-        return bool(not cfg.cont and cfg.optim_alg == 'adam' and (self.clf_small if cfg.has_y else self._dual_capable()))
-
-    def _tail_gated(self):
-        """dual-graph train step (ONE pair of graphs) whose side chain runs its half of the optimiser sweep and the loss
-        scalars behind the join: the optimiser launch gates on the classifier's gradient only, and the NEXT step's first
-        launch waits for the tail's end"""
-        if not (self._mode() == 5 and self._late_ok() and not self._split_kind):
-            return False
-        if not self._side_adam_layout()[0]:     # (= ``side_adam`` of backward(): the tail then holds the flag-4 wait launch)
-            return False
-        # ... where the step's first launch is the graph-resident feed (a few dozen workgroups that can park): sampler feed
-        # 0.213 -> 0.2074 ms.  With the resident batch the first launch is the input gather (856 workgroups; parked with
-        # 128 it is slower by itself and waits the 4 us the optimiser launch used to wait: 0.1932 -> 0.198 ms)
-        return self.plan.live_feed is not None or T.get('tail_gate') == 2
 
     def _side_adam_layout(self):
         """(may the side chain sweep the decoder heads' half of the arena?, first element of that half)"""
@@ -866,7 +836,7 @@ class FusedStep(StepSchedule):
         restored checkpoint, a capture)"""
         self.side_ctr.copy_(self.step_dev)
         self.side_t.copy_(self.step_dev + 1)
-        self.flags[3:4].copy_(self.step_dev)
+        self.sync.flag('tail').copy_(self.step_dev)
 
     def _fprop_from_heads(self):
         """the encoder heads' sample epilogue also fills the z1 columns of the fprop input (the class columns are
@@ -879,17 +849,6 @@ class FusedStep(StepSchedule):
         (``dv_fprop_kl``)"""
         cfg, p = self.cfg, self.plan
         return bool(self.fuse_bwd and self.fuse_heads and self.clf_small and cfg.has_y and not cfg.cont and p.Mf)
-
-    def _klz2_on_main(self):
-        """dual-graph train step: the pairs' KL(q(z2|x2)||p(z2|z1)) rows run on the main chain (in every other schedule:
-        on the side chain)"""
-        # (not with the batch-independent plan: its worst-case decoder rows make the main chain the longer one again,
-        # the side chain parks ~13 us per step behind it -- sampler feed 0.250 -> 0.248 ms with the rows on the side chain;
-        # that is the every-row-may-be-anything plan: the bucketed ones are close to a structure plan's rows and keep the
-        # rows on the main chain, sampler feed 0.2181 -> 0.2140 ms in a same-box A/B)
-        p = self.plan
-        on = not (p is not None and p.universal and len(p.key) <= 3)
-        return bool(self._mode() == 5 and not self.cfg.cont and self.cfg.has_y and on)
 
     def _mmd_penalty(self):
         """Model-level MMD penalty of the ``use_s`` extension (src/DrVAE.py:394-398,537-540): minus the MMD between
@@ -1025,35 +984,9 @@ class FusedStep(StepSchedule):
         DQ = p.DQ
         Z1blk, DZ1 = p.ZDEC[:L * B], p.DZDEC[:L * B]
         # ---- side chain: y-marginalisation, fprop, classifier -> DZ1B (its share of d/dz1), DZ2F
-        mode = self._mode()
-
-        # (dual-graph schedule) the classifier's weight gradient is a leaf -- only the optimiser reads it --
-        # and the side chain is the one the join waits for: it runs AFTER the side chain has published its
-        # data gradients, and the optimiser launch gates that slice of the arena on a flag of its own
-        # Under data parallelism every gradient (and the loss tail) must be final before the exchange: with the plain
-        # two-graph split ``replay`` makes the launching stream wait for the side stream before the all-reduce, so the
-        # leaf work may still move behind the join (only the optimiser half cannot: it follows the exchange); the
-        # overlapped / captured exchanges keep everything in front of the join
-        split_kind = self._split_kind
-        late = mode == 5 and self._late_ok() and split_kind in (False, True)
-        leaf = []
-        # ... and HALF of the optimiser sweep moves there too: the decoder heads (the tail of the arena, half of
-        # all parameters) are final and no longer read once the heads' backward products are through -- the
-        # launch after them publishes that -- so the side chain updates them next to the main chain's tail
-        g0 = self.arena.grad.storage_offset()
-        side_ok, hs = self._side_adam_layout()
-        side_adam = late and not split_kind and side_ok
-        # the gradient exchange captured INTO the step's graph (data parallelism, ``split_kind == 'captured'``): every gradient
-        # and the loss scalars are final in front of the collective, so no leaf work moves behind the join -- but the side chain,
-        # idle behind it, draws the NEXT step's noise (the main chain's graph then no longer starts with the draw) and the
-        # sweep's first workgroup orders the next step behind that.  Measured (one-rank RCCL, same box): cfg 2 0.2042 -> 0.2007 ms,
-        # cfg 4 0.1799 -> 0.1769; the heads' half of the sweep behind the collective on the side chain's 64 CUs as well
-        # (a flag published on entry of the main chain's sweep): 0.2124 / 0.1871 -- half the arena through a quarter of the
-        # chip's bandwidth takes longer than the whole sweep on the rest (profiles/r06_experiments.md)
-        cap_fork = self._cap_fork(mode, split_kind, side_ok)
-        # the loss scalars (a leaf: only the host / the exchange reads them) are assembled by the side chain behind
-        # the join, once the main chain has published that its reconstruction rows are final
-        side_loss = side_adam or (late and split_kind is True and len(self.L_decx) > 1)
+        # (dual-graph schedule: what the side chain carries behind the join is decided in ``_step_tail``)
+        mode, t = self._mode(), self._tail
+        late, leaf = t.late, []
 
         # ---- main chain: reconstruction terms, d/d(mu, pre-softplus) straight from the per-row
         # coefficients, then back through the decoder (the three big GEMMs)
@@ -1064,16 +997,16 @@ class FusedStep(StepSchedule):
         elif not self.fuse_bwd:
             K.nll_rows_bwd(p.DPX[:, :X], p.DPX[:, X:], p.c_nll, p.XIN, PX[:, :X], PX[:, X:], mode=GAUSS_SIGMA,
                            xidx=p.tgt, sd_act='softplus', sd_shift=1e-3)
-        if mode == 5 and self._rec == 'side':
+        if mode == DUAL and self._rec == 'side':
             self._side_backward(Qmu, Qlv, Z1blk, late, leaf)
-            self._side_graph_tail(late, leaf, side_loss, side_adam, hs, cap_fork=cap_fork)
+            self._side_graph_tail(leaf)
             return
-        if mode == 0:
+        if mode == EVAL:
             self.branch.fork()
-        elif mode == 3:
+        elif mode == FORK_JOIN:
             self.branch._forked = True       # one fork/join per step: the side chain simply continues
         p.c_decx.backward(p.DPX, p.dec_in, [[(p.DZDEC, 1.0, 0.0)]] + [None] * (len(p.dec_in) - 1),
-                          publish_after_last=(self.flags[4:5], self.step_dev, 1) if side_loss else None,
+                          publish_after_last=self.sync.pub('rows', self.step_dev) if t.side_loss else None,
                           db_last_done=bool(self.fuse_bwd and self._nll_cs))
         if p.DZMMD is not None:
             # model-level MMD penalty (use_s extension): its gradient w.r.t. the z1 / z2 samples was computed in
@@ -1081,42 +1014,35 @@ class FusedStep(StepSchedule):
             p.DZDEC[:p.o3].add_(p.DZMMD)
         if self._after_decoder_bwd is not None:
             self._after_decoder_bwd()        # decoder_x gradients are final: graph split point of the overlapped exchange
-        if mode != 5:
+        if mode != DUAL:
             with self.branch:
                 self._side_backward(Qmu, Qlv, Z1blk, late, leaf)
             self.branch.join()
-        # (only where the join does not wait: every workgroup of the consumer polls the flag, and a long wait -- VFAE:
-        # its side chain is the longer one, 30 us/step -- slows the very chain it waits for: 0.184 -> 0.208 ms)
-        # ... and only where the parked grid is a small fraction of what the chip holds resident (256 CUs x 8
-        # workgroups): a consumer grid that filled the chip would leave the side chain nowhere to run
-        fold_join = mode == 5 and side_loss and cfg.has_pert and (B * Z1 + 255) // 256 <= 256
         park = bump = None
-        if fold_join:
+        if t.fold_join:
             # no launch of its own for the join: the first consumer of the side chain's gradients (below) parks on
             # the flag itself, and the counters ride on the sample-backward launch
-            park = (self.flags[1:2], self.step_dev, self.sync_err[0:2])
+            park = self.sync.wait('join', self.step_dev)
             bump = [(self.step_dev, 1)] + ([(self.rng_ctr, self._rng_pending)] if self._rng_pending else [])
             self._rng_pending = 0
             self._ctr_bumped = True
-        elif mode == 5:    # the launch that assembles the loss scalars also parks on the side chain's flag
-            self._loss_scalars(after=(self.flags[1:2], self.step_dev, self.sync_err[0:2], 1, K.WAIT_SPINS),
-                               terms_elsewhere=side_loss)
-        elif mode == 3:         # (the step / Philox counters ride on this launch: two launches less in front of the optimiser)
+        elif mode == DUAL:    # the launch that assembles the loss scalars also parks on the side chain's flag
+            self._loss_scalars(after=self.sync.wait('join', self.step_dev), terms_elsewhere=t.side_loss)
+        elif mode == FORK_JOIN:         # (the step / Philox counters ride on this launch: two launches less in front of the optimiser)
             self._loss_scalars(bump_counters=True)
-        if mode == 5 and late and not split_kind:      # (the step counter is advanced before the optimiser launch: counter + 0 by then)
+        if t.adam_gated:      # (the optimiser's gate waits with counter + 0: the step counter is advanced before it)
             if cfg.has_y:
-                lc = self.L_clf[0]
+                lc, g0 = self.L_clf[0], self.arena.grad.storage_offset()
                 lo = min(lc.dW.storage_offset(), lc.db.storage_offset()) - g0
                 hi = max(lc.dW.storage_offset() + span(lc.dW), lc.db.storage_offset() + lc.db.numel()) - g0
             else:       # (no classifier, no leaf gradient in flight: the first workgroup's elements stand in for the slice --
-                lo, hi = 0, 4       # the gate is what orders the NEXT step behind the side chain's tail, see ``_tail_gated``)
-            self._adam_gate = (self.flags[6:7] if self._tail_gated() else self.flags[3:4], self.step_dev, 0,
-                               self.sync_err[6:8], lo, hi)
-            self._adam_n = hs if side_adam else None
-        if cap_fork:
+                lo, hi = 0, 4       # the gate is what orders the NEXT step behind the side chain's tail, see ``_step_tail``)
+            self._adam_gate = self.sync.gate('clf_dw' if t.tail_gated else 'tail', self.step_dev, lo, hi)
+            self._adam_n = t.hs if t.side_adam else None
+        if t.cap_fork:
             # (the sweep's first workgroup also parks on the side chain's "tail through" flag: what orders the NEXT step --
             # its first launch reads the noise the side chain has drawn -- behind it)
-            self._adam_gate = (self.flags[3:4], self.step_dev, 0, self.sync_err[6:8], 0, 4)
+            self._adam_gate = self.sync.gate('tail', self.step_dev, 0, 4)
         if cfg.has_pert:
             P2 = p.c_z2F.out[-1]
             # everything that hangs on the z2Fz1 samples, one launch: scatter-back of the decoded
@@ -1144,7 +1070,7 @@ class FusedStep(StepSchedule):
                           # of a dv_kl_rows_bwd launch behind them (cfg 1: one launch less on the critical chain)
                           prior=(p.c_klp, p.KLPraw, cfg.kl_min, Qmu) if cfg.kind == 'pvae' else None)
         p.c_enc.backward(DQ, p.enc_in, None,
-                         publish_first=(self.flags[5:6], self.step_dev, 0) if ((late or cap_fork) and self.noise_ahead) else None)
+                         publish_first=self.sync.pub('noise', self.step_dev, 0) if t.noise_ahead else None)
 
     def _side_backward(self, Qmu, Qlv, Z1blk, late, leaf):
         """the side chain's share of the backward pass: y-marginalisation, fprop blocks, classifier -> ``DZ1B`` (its share
@@ -1238,57 +1164,38 @@ class FusedStep(StepSchedule):
                 else:
                     p.c_clf.backward(p.DLOG, [Z1blk], [[(p.DZ1B, 1.0, b1)]])
 
-    def _cap_fork(self, mode, split_kind, side_ok):
-        """data-parallel step with the exchange captured into its graph: does the side chain, idle behind the join, draw the
-        NEXT step's noise (``noise_ahead``, as in the single-GPU step)?"""
-        return bool(mode == 5 and split_kind == 'captured' and side_ok and self._late_ok() and self.cfg.has_y
-                    and T.get('dp_fork'))
-
-    def _side_graph_tail(self, late, leaf, side_loss, side_adam, hs, cap_fork=False):
+    def _side_graph_tail(self, leaf):
         """(dual-graph schedule) what the side chain's graph runs behind its backward pass: publish its data gradients, the
         deferred leaf launches, the decoder heads' half of the optimiser sweep, the loss scalars, the NEXT step's noise, its
         own counters"""
-        cfg, p = self.cfg, self.plan
-        if cap_fork:
-            K.flag_publish(self.flags[1:2], self.side_ctr)         # DZ1B / DZ2F / every side gradient is final (the join)
-            if self.noise_ahead:      # the next step's draws: this step's readers are through once the encoder backward has started
-                K.flag_wait(self.flags[5:6], self.side_ctr, self.sync_err[10:12])
-                K.fill_normal_rows(p.noise, p.noise_desc, self.seed, self.rng_ctr)
-            K.counters_add2(self.side_ctr, 1, self.side_t, 1, publish=(self.flags[3:4], self.side_ctr, 1))
-            return
-        # DZ1B / DZ2F / side gradients are final: published on entry of the first leaf launch behind them (the
-        # classifier's weight gradient) where there is one, else by a launch of its own
-        if late and leaf:
-            leaf[0](pub=(self.flags[1:2], self.side_ctr, 1))
+        cfg, p, t, sync, ctr = self.cfg, self.plan, self._tail, self.sync, self.side_ctr
+        # DZ1B / DZ2F / every side gradient is final (the join): published on entry of the first leaf launch behind them
+        # (the classifier's weight gradient) where there is one, else by a launch of its own
+        if leaf:
+            leaf[0](pub=sync.pub('join', ctr))
             for fn in leaf[1:]:
                 fn()
         else:
-            K.flag_publish(self.flags[1:2], self.side_ctr)
-            for fn in leaf:
-                fn()
-        if late:
-            if side_loss:
-                a = self.arena
-                # (entry of this launch = the deferred leaf launches, i.e. the classifier's weight gradient, are through:
-                # flag 6, what the main chain's optimiser launch gates its classifier slice on)
-                K.flag_wait(self.flags[4:5], self.side_ctr, self.sync_err[8:10],
-                            publish=(self.flags[6:7], self.side_ctr, 1) if self._tail_gated() else None)
-                if side_adam:
-                    K.adam_l2(a.param[hs:a.n_live], a.grad[hs:a.n_live], a.exp_avg[hs:a.n_live],
-                              a.exp_avg_sq[hs:a.n_live], self.side_t, lr=cfg.learning_rate,
-                              weight_decay=cfg.weight_decay, halt=self.sync_err)
-                self._loss_scalars()   # a leaf too; the wait above also covers the main chain's NLL rows
-            if self.noise_ahead:
-                # the next step's N(0,1) draws: every reader of this step's is through once the encoder
-                # backward has started (the main chain publishes that), and the Philox counter has advanced.
-                # (A park of the draw launch itself instead of the wait launch was measured slower: 356
-                # workgroups polling one flag, +10 us/step)
-                K.flag_wait(self.flags[5:6], self.side_ctr, self.sync_err[10:12])
-                K.fill_normal_rows(p.noise, p.noise_desc, self.seed, self.rng_ctr)
-            # ... and now the side chain's late work is final: published by the counter launch on entry
-            K.counters_add2(self.side_ctr, 1, self.side_t, 1, publish=(self.flags[3:4], self.side_ctr, 1))
-            return
-        K.counters_add2(self.side_ctr, 1, self.side_t, 1)
+            K.flag_publish(*sync.pub('join', ctr))
+        if t.side_loss:
+            a, hs = self.arena, t.hs
+            # (entry of this launch = the deferred leaf launches, i.e. the classifier's weight gradient, are through:
+            # flag ``clf_dw``, what the main chain's optimiser launch gates its classifier slice on)
+            K.flag_wait(*sync.wait('rows', ctr), publish=sync.pub('clf_dw', ctr) if t.tail_gated else None)
+            if t.side_adam:
+                K.adam_l2(a.param[hs:a.n_live], a.grad[hs:a.n_live], a.exp_avg[hs:a.n_live],
+                          a.exp_avg_sq[hs:a.n_live], self.side_t, lr=cfg.learning_rate,
+                          weight_decay=cfg.weight_decay, halt=self.sync_err)
+            self._loss_scalars()   # a leaf too; the wait above also covers the main chain's NLL rows
+        if t.noise_ahead:
+            # the next step's N(0,1) draws: every reader of this step's is through once the encoder
+            # backward has started (the main chain publishes that), and the Philox counter has advanced.
+            # (A park of the draw launch itself instead of the wait launch was measured slower: 356
+            # workgroups polling one flag, +10 us/step)
+            K.flag_wait(*sync.wait('noise', ctr))
+            K.fill_normal_rows(p.noise, p.noise_desc, self.seed, self.rng_ctr)
+        # ... and now the side chain's late work is final: published by the counter launch on entry
+        K.counters_add2(ctr, 1, self.side_t, 1, publish=sync.pub('tail', ctr) if (t.late or t.cap_fork) else None)
 
     # -------------------------------------------------------------------- optimiser
     def optimizer_step(self, gscale=1.0):
@@ -1304,7 +1211,7 @@ class FusedStep(StepSchedule):
         if self._rec == 'both' and self.sched == 5 and self._dual_capable():
             # eager step: the side chain's counters follow, and so does the "side chain's tail is through" flag that the
             # NEXT captured step's first launch waits for (published on entry: counter + 1 = the advanced value)
-            K.counters_add2(self.side_ctr, 1, self.side_t, 1, publish=(self.flags[3:4], self.side_ctr, 1))
+            K.counters_add2(self.side_ctr, 1, self.side_t, 1, publish=self.sync.pub('tail', self.side_ctr))
         step = K.adamax_l2 if cfg.optim_alg == 'adamax' else K.adam_l2    # exp_avg_sq doubles as Adamax's exp_inf
         n = a.n_live                      # parameters without gradients sit behind it (untouched, like torch)
         if self._adam_n is not None:      # dual-graph step: the side chain sweeps the rest (the decoder heads)
@@ -1324,15 +1231,7 @@ class FusedStep(StepSchedule):
             self.set_noise(noise)
         else:
             self.draw_noise(bump=False)
-        self.fuse_bwd = True
-        try:
-            self.forward()
-            self.backward()
-            if allreduce is not None:
-                allreduce(self.arena.xchg)
-            self.optimizer_step()
-        finally:
-            self.fuse_bwd = False
+        self._launch_sequence(allreduce=allreduce, draw=False)
         self.iters += 1
 
     def losses(self):

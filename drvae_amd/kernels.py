@@ -8,6 +8,7 @@ dimension.  There is no CPU path here: tensors must live on the GPU.
 """
 import ctypes as C
 import os
+from typing import Any, NamedTuple, Optional
 
 import torch
 
@@ -123,8 +124,9 @@ def _gemm_desc(Cm, A, B, a_kc, b_kc, *, A2=None, a_kscale=None, alpha=1.0, beta=
     d.yref, d.ldy = _f32(yref, 'yref'), _ld(yref)
     d.a_colsum, d.colsum_beta = _f32(a_colsum, 'a_colsum'), colsum_beta
     d.flags = 3 if overread else 0
-    if publish is not None:                 # (flag, counter, add): publish on kernel entry, see dv_flag_publish
-        d.pub_flag, d.pub_ctr, d.pub_add = _i32(publish[0]), _i32(publish[1]), publish[2]
+    if publish is not None:                 # ``Publish``: on kernel entry, see dv_flag_publish
+        publish = Publish(*publish)
+        d.pub_flag, d.pub_ctr, d.pub_add = _i32(publish.flag), _i32(publish.ctr), publish.add
     d.tune = _tune_ptr()
     return d
 
@@ -283,25 +285,50 @@ def reparam_bwd(dmu, dsd, dz, eps, sd, *, mode=GAUSS_LOGVAR, src_idx=None, reps=
                'dv_reparam_bwd')
 
 
+# The arguments that order one launch against the other chain (``schedule.StepSync`` builds them by name).  A plain
+# tuple in the same field order is accepted wherever one of them is.
+class Wait(NamedTuple):        # park until ``flag`` >= ``ctr`` + ``add``, at most ``max_spins`` polls (None: WAIT_SPINS);
+    # a time-out sets ``err``
+    flag: Any
+    ctr: Any
+    err: Any
+    add: int = 1
+    max_spins: Optional[int] = None
+
+
+class Publish(NamedTuple):     # ``flag`` = ``ctr`` + ``add``, on entry of the launch
+    flag: Any
+    ctr: Any
+    add: int = 1
+
+
+class Gate(NamedTuple):        # the optimiser sweep's elements [``lo``, ``hi``) wait like a ``Wait`` (mind ``add`` / ``err``)
+    flag: Any
+    ctr: Any
+    add: int
+    err: Any
+    lo: int
+    hi: int
+
+
 def _wait(park):
-    """(flag, ctr, err[, add[, max_spins]]) -> dv_wait (None: no wait)"""
+    """``Wait`` -> dv_wait (None: no wait)"""
     if park is None:
         return None
-    flag, ctr, err = park[:3]
+    park = Wait(*park)
     w = _lib.Wait()
-    w.flag, w.ctr, w.err = _i32(flag), _i32(ctr), _i32(err)
-    w.add = park[3] if len(park) > 3 else 1
-    w.max_spins = park[4] if len(park) > 4 and park[4] is not None else WAIT_SPINS
+    w.flag, w.ctr, w.err, w.add = _i32(park.flag), _i32(park.ctr), _i32(park.err), park.add
+    w.max_spins = WAIT_SPINS if park.max_spins is None else park.max_spins
     return C.byref(w)
 
 
 def _publish(pub):
-    """(flag, ctr[, add]) -> dv_publish (None: nothing published)"""
+    """``Publish`` -> dv_publish (None: nothing published)"""
     if pub is None:
         return None
+    pub = Publish(*pub)
     w = _lib.Publish()
-    w.flag, w.ctr = _i32(pub[0]), _i32(pub[1])
-    w.add = pub[2] if len(pub) > 2 else 1
+    w.flag, w.ctr, w.add = _i32(pub.flag), _i32(pub.ctr), pub.add
     return C.byref(w)
 
 
@@ -882,7 +909,7 @@ def rank_metrics(out, counts, proba, y32, *, pred32=None, sel=None, c0=1, n_cls=
 
 def loss_assemble(loss, terms, w_elbo, w_cmpl, after=None, bump=(), halt=None, accum=None):
     """terms: list of (x, w_or_None, scale, out_index); see ``dv_loss_assemble``.  ``after`` =
-    (flag, counter, err, add, max_spins): park like ``flag_wait`` inside the same launch first;
+    a ``Wait``: park like ``flag_wait`` inside the same launch first;
     ``bump`` = up to two (counter, inc): advanced at the end of the launch;
     ``halt``: the (err, ticks) pairs of the step's waits -- any error set: the scalars come out NaN;
     ``accum`` (8 floats): running sums, ``accum += loss`` in the same launch."""
@@ -892,16 +919,13 @@ def loss_assemble(loss, terms, w_elbo, w_cmpl, after=None, bump=(), halt=None, a
         x, w, scale, out = term[:4]
         arr[i].x, arr[i].w, arr[i].n, arr[i].scale, arr[i].out = _f32(x), _f32(w), x.numel(), scale, out
         arr[i].row_len = term[4] if len(term) > 4 else 1
-    if after is None and bump:
-        after = (None, None, None, 0, 1)      # no wait: only the counters ride on the launch
-    if after is None:
+    if after is None and not bump:
         _lib.check(_lib.load().dv_loss_assemble(arr, len(terms), _f32(w_elbo), _f32(w_cmpl), _f32(loss), hp, hn,
                                                 _f32(accum), _stream()), 'dv_loss_assemble')
     else:
-        flag, ctr, err, add, spins = after
-        _lib.check(_lib.load().dv_loss_assemble_after(
-            _wait((flag, ctr, err, add, spins)) if flag is not None else None, arr, len(terms), _f32(w_elbo),
-            _f32(w_cmpl), _f32(loss), _bump(bump), hp, hn, _f32(accum), _stream()), 'dv_loss_assemble_after')
+        # (``after`` None: no wait, only the counters ride on the launch)
+        _lib.check(_lib.load().dv_loss_assemble_after(_wait(after), arr, len(terms), _f32(w_elbo), _f32(w_cmpl), _f32(loss),
+                                                      _bump(bump), hp, hn, _f32(accum), _stream()), 'dv_loss_assemble_after')
 
 
 def axpby(y, x, a=1.0, b=0.0):
@@ -912,7 +936,7 @@ def axpby(y, x, a=1.0, b=0.0):
 # ------------------------------------------------------------------------- optimiser
 def adam_l2(p, g, m, v, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, gate=None,
             halt=None):
-    """``gate`` = (flag, counter, add, err, lo, hi): elements [lo, hi) wait for the flag (``dv_adam_l2_gated``);
+    """``gate`` = a ``Gate``: elements [lo, hi) wait for the flag (``dv_adam_l2_gated``);
     ``halt``: the (err, ticks) pairs of the step's waits -- any error set: nothing is updated"""
     assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
     hp, hn = _halt(halt)
@@ -921,9 +945,10 @@ def adam_l2(p, g, m, v, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weigh
         _lib.check(_lib.load().dv_adam_l2(_f32(p), _f32(g), _f32(m), _f32(v), p.numel(), C.byref(h), _i32(step_dev), hp, hn,
                                           _stream()), 'dv_adam_l2')
     else:
-        flag, ctr, add, err, lo, hi = gate
+        gate = Gate(*gate)
         _lib.check(_lib.load().dv_adam_l2_gated(_f32(p), _f32(g), _f32(m), _f32(v), p.numel(), C.byref(h), _i32(step_dev),
-                                                _wait((flag, ctr, err, add)), lo, hi, hp, hn, _stream()), 'dv_adam_l2_gated')
+                                                _wait(Wait(gate.flag, gate.ctr, gate.err, gate.add)), gate.lo, gate.hi, hp, hn,
+                                                _stream()), 'dv_adam_l2_gated')
 
 
 def adamax_l2(p, g, m, u, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None):
@@ -946,7 +971,7 @@ WAIT_SPINS = int(os.environ.get('DRVAE_WAIT_SPINS', '4000000'))
 
 
 def flag_wait(flag, ctr, err, add=1, max_spins=None, publish=None):
-    """``publish`` = (flag, counter[, add]): published on entry of the wait launch"""
+    """the arguments of a ``Wait``; ``publish`` = a ``Publish``: goes out on entry of the wait launch"""
     max_spins = WAIT_SPINS if max_spins is None else max_spins
     _lib.check(_lib.load().dv_flag_wait(_i32(flag), _i32(ctr), add, _i32(err), max_spins, _publish(publish), _stream()),
                'dv_flag_wait')
@@ -957,7 +982,7 @@ def counter_add(counter, inc=1):
 
 
 def counters_add2(c1, inc1, c2, inc2, publish=None):
-    """``publish`` = (flag, ctr[, add]) goes out on entry, before the counters move (ctr may be one of them)"""
+    """``publish`` = a ``Publish``: goes out on entry, before the counters move (ctr may be one of them)"""
     _lib.check(_lib.load().dv_counters_add2(_i32(c1), c1.numel(), inc1, _i32(c2), c2.numel(), inc2, _publish(publish),
                                             _stream()), 'dv_counters_add2')
 

@@ -1,20 +1,22 @@
 """How the launch sequence of the fused train step is put on the GPU: hipGraph capture / replay, the
 dual-graph schedule (main chain and side chain as two single-stream graphs ordered by device flags),
 the CU partition of the two chains, and the data-parallel graph splits.  Mixed into ``FusedStep``."""
+import contextlib
 import ctypes
 import gc
 import os
 import weakref
+from typing import NamedTuple
 
 import torch
 
 from . import kernels as K
+from . import tuning as T
 
 
 def _masked_stream(bits, device):
     """a HIP stream whose kernels only run on the CUs set in ``bits`` (hipExtStreamCreateWithCUMask),
     wrapped for torch; lives for the rest of the process"""
-    import ctypes
     hip = ctypes.CDLL('libamdhip64.so')
     st = ctypes.c_void_p()
     arr = (ctypes.c_uint32 * len(bits))(*bits)
@@ -35,6 +37,84 @@ def _masked_stream(bits, device):
 
 
 SYNC_POLL = 64                # steps between two polls of the wait-error words
+
+# what ``_mode()`` answers: how the pass being issued orders the step's two chains
+EVAL, FORK_JOIN, DUAL = 'evaluation pass', 'one graph with a fork/join', 'one chain of the dual-graph step'
+
+# ---------------------------------------------------------------- the device-flag protocol of the dual-graph step
+# The one statement of how the two single-stream graphs of a step are ordered (DESIGN.md section 6 prints the same
+# table).  A flag is published with the value ``counter + add`` on entry of a launch and awaited as ``counter + add`` by
+# the other chain; the main chain counts in ``step_dev``, the side chain in ``side_ctr``.  ``flags`` has one word per row
+# of FLAGS, ``sync_err`` an (error, ticks parked) pair per row of SITES, in this order: the layout is part of what
+# ``bench.py``, ``fit`` and the tests read (``sync_err[0::2]``).
+#   (name, publishing chain, goes unawaited)      published on entry of ...; ``goes unawaited``: nothing may wait for it
+FLAGS = (
+    ('z1', 'main', True),       # the z2Fz1 heads launch (VFAE: the decoder's first launch): the z1 samples are final.
+    #                             Unawaited by PVAE (its side chain is the tail only; the publish stays part of the
+    #                             captured launch arguments)
+    ('join', 'side', False),    # the first leaf launch behind the side chain's backward, else a launch of its own: every
+    #                             side-chain data gradient is final
+    ('z2f', 'main', True),      # the decoder's first launch, models with a perturbation function: the z2Fz1 samples are
+    #                             final.  Unawaited by PVAE, as ``z1``
+    ('tail', 'side', True),     # the side chain's counter launch: its tail is through.  Unawaited under a two-graph
+    #                             exchange split (``replay`` orders the streams on the host); eager steps publish it from
+    #                             ``optimizer_step`` for the next captured step
+    ('rows', 'main', False),    # the launch behind the decoder heads' backward products: reconstruction rows final
+    ('noise', 'main', False),   # the encoder backward's first launch: this step's noise has no reader left
+    ('clf_dw', 'side', False),  # the wait launch of site ``rows``: the classifier's dW is through
+    ('unused', None, False),    # (allocated: the layout of ``flags`` stays)
+)
+#   (name, waiting chain, flags awaited)           the launch that waits
+SITES = (
+    ('join', 'main', ('join',)),               # park of ``z2f_post_bwd``, else ``loss_assemble(after=...)``
+    ('z1', 'side', ('z1',)),                   # the side chain's first launch, a ``flag_wait``
+    ('z2f', 'side', ('z2f',)),                 # park of ``smalln_fwd`` / of the pairs' KL rows, else a ``flag_wait``
+    ('adam_gate', 'main', ('tail', 'clf_dw')),   # the optimiser sweep's gated slice; ``clf_dw`` when the tail is gated
+    ('rows', 'side', ('rows',)),               # the ``flag_wait`` in front of the tail's Adam half / loss scalars
+    ('noise', 'side', ('noise',)),             # the ``flag_wait`` in front of the draw-ahead
+    ('next_step', 'main', ('tail',)),          # tail-gated step: the NEXT step's first launch waits for the previous tail
+)
+FLAG_INDEX = {f[0]: i for i, f in enumerate(FLAGS)}
+SITE_INDEX = {s[0]: i for i, s in enumerate(SITES)}
+
+
+class StepSync:
+    """the flag and error words of one engine, asked by the names of FLAGS / SITES"""
+    # (so a wait cannot be built with another site's error slot, or for a flag its site does not await)
+
+    def __init__(self, device):
+        self.flags = torch.zeros(len(FLAGS), dtype=torch.int32, device=device)
+        self.err = torch.zeros(2 * len(SITES), dtype=torch.int32, device=device)
+
+    def flag(self, name):
+        return self.flags[FLAG_INDEX[name]:FLAG_INDEX[name] + 1]
+
+    def pub(self, name, ctr, add=1):
+        return K.Publish(self.flag(name), ctr, add)
+
+    def wait(self, site, ctr, add=1, max_spins=None, flag=None):
+        i, flags = SITE_INDEX[site], SITES[SITE_INDEX[site]][2]
+        assert flag is None or flag in flags, (site, flag)
+        return K.Wait(self.flag(flag or flags[0]), ctr, self.err[2 * i:2 * i + 2], add, max_spins)
+
+    def gate(self, flag, ctr, lo, hi):
+        w = self.wait('adam_gate', ctr, 0, flag=flag)        # (the step counter is advanced before the sweep: counter + 0)
+        return K.Gate(w.flag, w.ctr, w.add, w.err, lo, hi)
+
+
+class Tail(NamedTuple):
+    """what the side chain of a recorded step carries behind the join (``_step_tail``); default: no dual-graph step"""
+    dual: bool = False             # two flag-ordered graphs
+    late: bool = False             # the step's leaf work (classifier dW, ...) runs behind the join
+    adam_gated: bool = False       # ... so the optimiser sweep gates the classifier's slice on a flag
+    side_adam: bool = False        # ... and the decoder heads' half of the sweep runs on the side chain,
+    hs: int = 0                    #     which starts at this element of the arena
+    side_loss: bool = False        # ... and the loss scalars
+    cap_fork: bool = False         # captured exchange: the side chain draws ahead behind the join
+    tail_gated: bool = False       # the NEXT step's first launch waits for the tail, the sweep for the classifier's dW only
+    noise_ahead: bool = False      # the side chain draws the NEXT step's noise
+    klz2_on_main: bool = False     # the pairs' KL(q(z2|x2)||p(z2|z1)) rows run on the main chain
+    fold_join: bool = False        # the join rides on its first consumer (``z2f_post_bwd`` parks)
 
 _PINNED_POOL = []             # pinned int32 buffers of retired engines (see ``_poll_sync``)
 _PARTITION_STREAMS = {}      # device index -> {reserved CUs -> (main stream, side stream) | None}
@@ -78,8 +158,8 @@ class _Branch:
 
 
 # what ``capture()`` leaves on the engine: kept per plan by ``stash_capture`` / swapped back in by ``use_capture``
-_CAPTURE_STATE = ('_graphs', '_side_graph', '_split_capture', '_split_kind', 'noise_ahead', '_graph_key', '_graph_feed',
-                  '_graph_mmd_sig', '_captured_allreduce', '_graph_noise')
+_CAPTURE_STATE = ('_graphs', '_side_graph', 'noise_ahead', '_graph_key', '_graph_feed', '_graph_mmd_sig',
+                  '_captured_allreduce', '_graph_noise')
 
 
 class StepSchedule:
@@ -92,8 +172,6 @@ class StepSchedule:
         # what capture() leaves: see _CAPTURE_STATE
         self._graphs = []                 # the captured graph(s) of the main chain, in replay order
         self._side_graph = None           # dual-graph schedule: the side chain's graph
-        self._split_capture = False       # captured in pieces around a gradient exchange
-        self._split_kind = False          # False | True (two graphs) | 'overlap' | 'captured'
         self.noise_ahead = False          # the side chain draws the NEXT step's noise behind the join
         self._graph_key = None            # key of the plan the graphs point into
         self._graph_feed = None           # ... its graph-resident feed at capture time
@@ -102,7 +180,8 @@ class StepSchedule:
         self._graph_noise = None          # the ``add_noise`` the graphs were captured with (None: any; set by fit)
         self._captures = {}               # plan key -> the above, kept by ``stash_capture``
         # the step being recorded
-        self._rec = 'both'                # 'both' | the dual-graph schedule's 'main' / 'side' chain
+        self._rec = 'both'                # 'both' | the dual-graph schedule's 'main' / 'side' chain (``_recording``)
+        self._tail = Tail()               # ... and what its side chain carries
         self._late_fork = False           # chip-filling step: the side chain forks behind the decoder heads' product
         self._after_decoder_bwd = None    # graph split point of the overlapped exchange
         self._nll_fused = False           # which buffer holds this pass's reconstruction rows: NLLP ...
@@ -143,24 +222,100 @@ class StepSchedule:
         return True
 
     def _mode(self):
-        if not self.fuse_bwd:
-            return 0
-        if self._rec != 'both':
-            return 5
-        return 3                     # one fork/join per step (eager steps of the dual-graph schedule, too)
+        # (eager steps of the dual-graph schedule fork and join, too)
+        return EVAL if not self.fuse_bwd else DUAL if self._rec != 'both' else FORK_JOIN
+
+    def _step_tail(self, split_kind, on_gpu=None):
+        """how the train step of the current plan is recorded under the exchange form ``split_kind``: a ``Tail``"""
+        # ``split_kind``: False | True (two graphs) | 'overlap' | 'captured'.  Decided HERE, once per recording (``capture``),
+        # and read by forward / backward / the side chain's tail: copies of a condition that disagree deadlock the step into
+        # a wait time-out.  ``on_gpu``: what the device contributes -- a side stream on a hardware queue of its own; None:
+        # ask it (CPU tests of the recorded sequence pass True)
+        cfg, p = self.cfg, self.plan
+        # two flag-ordered graphs only for the latency-bound steps: once the decoder products alone fill the chip many
+        # times over (wide configuration) the side chain's small kernels, squeezed in between the resident GEMM
+        # workgroups of a second queue, cost more than they hide (36.7 ms dual, 35.9 ms as one graph with a fork/join)
+        # (not PVAE under a gradient exchange: its side chain is the step's tail only (optimiser half, loss scalars, noise);
+        # the optimiser half cannot move there then and the rest does not pay for the second graph -- one-rank RCCL, cfg 1:
+        # 0.1848 -> 0.1913 split, 0.1695 -> 0.1737 captured)
+        if not (self.sched == 5 and self._dual_capable(on_gpu) and self._latency_bound() and
+                (self._flags_usable() if on_gpu is None else on_gpu) and (cfg.has_y or not split_kind)):
+            return Tail()
+        # the side chain carries the step's leaf work (classifier dW, heads' optimiser half, loss scalars) behind the join
+        late_ok = bool(not cfg.cont and cfg.optim_alg == 'adam' and (self.clf_small if cfg.has_y else True))
+        # (dual-graph schedule) the classifier's weight gradient is a leaf -- only the optimiser reads it --
+        # and the side chain is the one the join waits for: it runs AFTER the side chain has published its
+        # data gradients, and the optimiser launch gates that slice of the arena on a flag of its own
+        # Under data parallelism every gradient (and the loss tail) must be final before the exchange: with the plain
+        # two-graph split ``replay`` makes the launching stream wait for the side stream before the all-reduce, so the
+        # leaf work may still move behind the join (only the optimiser half cannot: it follows the exchange); the
+        # overlapped / captured exchanges keep everything in front of the join
+        late = late_ok and split_kind in (False, True)
+        # ... and HALF of the optimiser sweep moves there too: the decoder heads (the tail of the arena, half of
+        # all parameters) are final and no longer read once the heads' backward products are through -- the
+        # launch after them publishes that -- so the side chain updates them next to the main chain's tail
+        side_ok, hs = self._side_adam_layout()
+        side_adam = late and not split_kind and side_ok
+        # the gradient exchange captured INTO the step's graph (data parallelism, ``split_kind == 'captured'``): every gradient
+        # and the loss scalars are final in front of the collective, so no leaf work moves behind the join -- but the side chain,
+        # idle behind it, draws the NEXT step's noise (the main chain's graph then no longer starts with the draw) and the
+        # sweep's first workgroup orders the next step behind that.  Measured (one-rank RCCL, same box): cfg 2 0.2042 -> 0.2007 ms,
+        # cfg 4 0.1799 -> 0.1769; the heads' half of the sweep behind the collective on the side chain's 64 CUs as well
+        # (a flag published on entry of the main chain's sweep): 0.2124 / 0.1871 -- half the arena through a quarter of the
+        # chip's bandwidth takes longer than the whole sweep on the rest (profiles/r06_experiments.md)
+        cap_fork = bool(split_kind == 'captured' and side_ok and late_ok and cfg.has_y and T.get('dp_fork'))
+        # the loss scalars (a leaf: only the host / the exchange reads them) are assembled by the side chain behind
+        # the join, once the main chain has published that its reconstruction rows are final
+        side_loss = side_adam or (late and split_kind is True and len(self.L_decx) > 1)
+        # tail gating: dual-graph train step (ONE pair of graphs) whose side chain runs its half of the optimiser sweep (the
+        # tail then holds the wait launch of site ``rows``) and the loss scalars behind the join: the optimiser launch gates on
+        # the classifier's gradient only, and the NEXT step's first launch waits for the tail's end
+        # ... where the step's first launch is the graph-resident feed (a few dozen workgroups that can park): sampler feed
+        # 0.213 -> 0.2074 ms.  With the resident batch the first launch is the input gather (856 workgroups; parked with
+        # 128 it is slower by itself and waits the 4 us the optimiser launch used to wait: 0.1932 -> 0.198 ms)
+        tail_gated = side_adam and (p.live_feed is not None or T.get('tail_gate') == 2)
+        # the pairs' KL rows on the main chain (in every other schedule: on the side chain)
+        # (not with the batch-independent plan: its worst-case decoder rows make the main chain the longer one again,
+        # the side chain parks ~13 us per step behind it -- sampler feed 0.250 -> 0.248 ms with the rows on the side chain;
+        # that is the every-row-may-be-anything plan: the bucketed ones are close to a structure plan's rows and keep the
+        # rows on the main chain, sampler feed 0.2181 -> 0.2140 ms in a same-box A/B)
+        klz2_on_main = not cfg.cont and cfg.has_y and not (p.universal and len(p.key) <= 3)
+        # the join rides on its first consumer
+        # (only where the join does not wait: every workgroup of the consumer polls the flag, and a long wait -- VFAE:
+        # its side chain is the longer one, 30 us/step -- slows the very chain it waits for: 0.184 -> 0.208 ms)
+        # ... and only where the parked grid is a small fraction of what the chip holds resident (256 CUs x 8
+        # workgroups): a consumer grid that filled the chip would leave the side chain nowhere to run
+        fold_join = side_loss and cfg.has_pert and (p.B * cfg.dim_z1 + 255) // 256 <= 256
+        # (noise drawn ahead under a CAPTURED exchange too: the side chain then draws behind the join and sweeps its half
+        # behind the collective)
+        return Tail(dual=True, late=late, adam_gated=late and not split_kind, side_adam=side_adam, hs=hs, side_loss=side_loss,
+                    cap_fork=cap_fork, tail_gated=tail_gated, noise_ahead=late or cap_fork, klz2_on_main=klz2_on_main,
+                    fold_join=fold_join)
+
+    @contextlib.contextmanager
+    def _recording(self, chain, tail):
+        """the passes issued inside are the ``chain`` ('main' | 'side') of the dual-graph step decided as ``tail``"""
+        self._rec, self._tail = chain, tail
+        try:
+            yield
+        finally:
+            self._rec, self._tail = 'both', Tail()
 
     # ------------------------------------------------------------------- hipGraph
-    def _launch_sequence(self, allreduce=None):
+    def _launch_sequence(self, allreduce=None, draw=True, optimizer=True):
+        """the train pass: [draw] + forward + backward [+ exchange + optimiser]; the only place that sets ``fuse_bwd``"""
         self.fuse_bwd = True
         try:
-            self.draw_noise(bump=False)
+            if draw:
+                self.draw_noise(bump=False)
             self.forward()
             self.backward()
-            if allreduce is not None:
+            if optimizer and allreduce is not None:
                 allreduce(self.arena.xchg)
-            self.optimizer_step()
         finally:
             self.fuse_bwd = False
+        if optimizer:
+            self.optimizer_step()
 
     def capture(self, split_for_allreduce=False, allreduce=None):
         """Capture the train step (Philox noise + forward + backward + Adam: ~100 launches)
@@ -188,24 +343,9 @@ class StepSchedule:
         torch.cuda.synchronize()
         self._graphs = []
         self._side_graph = None
-        # two flag-ordered graphs only for the latency-bound steps: once the decoder products alone fill the chip many
-        # times over (wide configuration) the side chain's small kernels, squeezed in between the resident GEMM
-        # workgroups of a second queue, cost more than they hide (36.7 ms dual, 35.9 ms as one graph with a fork/join)
-        dual = self.sched == 5 and self._dual_capable() and self._latency_bound() and self._flags_usable()
-        if dual and not self.cfg.has_y and split_for_allreduce:
-            # PVAE's side chain is the step's tail only (optimiser half, loss scalars, noise): under a gradient exchange
-            # the optimiser half cannot move there and the rest does not pay for the second graph (one-rank RCCL, cfg 1:
-            # 0.1848 -> 0.1913 split, 0.1695 -> 0.1737 captured)
-            dual = False
-        self._split_capture = bool(split_for_allreduce)
-        self._split_kind = split_for_allreduce          # False | True (two graphs) | 'overlap' | 'captured'
-        cfg = self.cfg
-        # (under a CAPTURED exchange too: the side chain then draws behind the join and sweeps its half behind the collective)
-        cap_fork = bool(dual and split_for_allreduce == 'captured' and self._cap_fork(5, 'captured', self._side_adam_layout()[0]))
-        self.noise_ahead = bool(dual and (split_for_allreduce in (False, True) or cap_fork) and self._late_ok())
+        tail = self._step_tail(split_for_allreduce)
+        self.noise_ahead = tail.noise_ahead
         self._noise_stale = True
-        if dual:
-            self._rec = 'main'
         # no garbage collection while a stream is capturing: a collected cycle may own device or pinned memory,
         # events or graphs of a retired engine, and releasing those calls HIP functions that are illegal
         # during (global-mode) capture -- the process aborts
@@ -218,24 +358,18 @@ class StepSchedule:
         # LATE -- behind the decoder heads' product, next to the HBM-bound NLL row pass, the one stretch of the main chain
         # that leaves the matrix pipes idle -- and joined behind the decoder's backward products, they win (round 6, cfg 5:
         # 31.09-31.15 -> 30.87-30.89 ms; the side chain's 0.4 ms are through long before the join)
-        self._late_fork = self.branch.on and not dual and not self._latency_bound()
+        self._late_fork = self.branch.on and not tail.dual and not self._latency_bound()
         try:
-            self._capture_main(split_for_allreduce)
-            if dual:
-                self._rec = 'side'
+            with self._recording('main', tail) if tail.dual else contextlib.nullcontext():
+                self._capture_main(split_for_allreduce)
+            if tail.dual:
                 self.sync_side_counters()
                 self.flag_side.wait_stream(torch.cuda.current_stream())
                 gs = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gs, stream=self.flag_side):
-                    self.fuse_bwd = True
-                    try:
-                        self.forward()
-                        self.backward()
-                    finally:
-                        self.fuse_bwd = False
+                with torch.cuda.graph(gs, stream=self.flag_side), self._recording('side', tail):
+                    self._launch_sequence(draw=False, optimizer=False)
                 self._side_graph = gs
         finally:
-            self._rec = 'both'
             self._late_fork = False
             if gc_was_on:
                 gc.enable()
@@ -338,8 +472,8 @@ class StepSchedule:
                 'DRVAE_SIDE_CUS' in os.environ:       # (multi-rank: split graphs need the exchange; keep the default)
             return None
         a = self.arena
-        keep = [t.clone() for t in (a.param, a.exp_avg, a.exp_avg_sq, self.step_dev, self.side_ctr, self.side_t, self.rng_ctr,
-                                    self.flags)]
+        state = (a.param, a.exp_avg, a.exp_avg_sq, self.step_dev, self.side_ctr, self.side_t, self.rng_ctr, self.flags)
+        keep = [t.clone() for t in state]
         iters = self.iters
         best = (None, float('inf'))
         for n in candidates:
@@ -358,8 +492,7 @@ class StepSchedule:
             if t < best[1]:
                 best = (n, t)
         torch.cuda.synchronize()
-        for dst, src in zip((a.param, a.exp_avg, a.exp_avg_sq, self.step_dev, self.side_ctr, self.side_t, self.rng_ctr,
-                             self.flags), keep):
+        for dst, src in zip(state, keep):
             dst.copy_(src)
         self.iters = iters
         self._noise_stale = True
@@ -414,12 +547,12 @@ class StepSchedule:
 
     @staticmethod
     def _raise_sync(words):
-        sites = [i for i, v in enumerate(words[0::2]) if v != 0]
+        sites = ', '.join('%d %s (on the %s chain)' % ((i,) + SITES[i][:2]) for i, v in enumerate(words[0::2]) if v != 0)
         raise RuntimeError('drvae_amd: a device-side chain wait timed out (main / side stream ordering; wait site(s) %s). '
                            'From that step on the loss scalars are NaN and the optimiser leaves the parameters '
                            'untouched: the state is that of the last good step -- except when the timed-out wait was the '
-                           'optimiser gate itself (site 3): that one step is applied to every parameter but the gated '
-                           'slice (the classifier head).  Restore from the last checkpoint.' % sites)
+                           'optimiser gate itself (site %d adam_gate): that one step is applied to every parameter but the gated '
+                           'slice (the classifier head).  Restore from the last checkpoint.' % (sites, SITE_INDEX['adam_gate']))
 
     def _poll_sync(self):
         """Called once per replayed step.  Every ``SYNC_POLL`` steps the sticky error words of the device-side
@@ -462,15 +595,11 @@ class StepSchedule:
                     ga.capture_end()
                     gb.capture_begin()
                 self._after_decoder_bwd = split
-                self.fuse_bwd = True
                 try:
                     ga.capture_begin()
-                    self.draw_noise(bump=False)
-                    self.forward()
-                    self.backward()
+                    self._launch_sequence(optimizer=False)
                     gb.capture_end()
                 finally:
-                    self.fuse_bwd = False
                     self._after_decoder_bwd = None
                 gc.capture_begin()
                 self.optimizer_step()
@@ -480,13 +609,7 @@ class StepSchedule:
         elif split_for_allreduce and split_for_allreduce != 'captured':
             g1, g2 = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
             with torch.cuda.graph(g1):
-                self.fuse_bwd = True
-                try:
-                    self.draw_noise(bump=False)
-                    self.forward()
-                    self.backward()
-                finally:
-                    self.fuse_bwd = False
+                self._launch_sequence(optimizer=False)
             with torch.cuda.graph(g2):
                 self.optimizer_step()
             self._graphs = [g1, g2]
