@@ -206,6 +206,7 @@ SIGNATURES = {
     'dv_mmd_identity_bwd': [_p, _p, _f, _i32, _i32, _p, _i64, _p],
     'dv_recon_finalize': [_p, _p, _i32, _i32, _p, _i32, _p, _p, _p],
     'dv_rank_metrics': [_p, _i64, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p, _p],
+    'dv_reg_metrics': [_p, _i64, _p, _i64, _p, _i32, _i32, _p, _p],
     'dv_loss_assemble': [C.POINTER(LossTerm), _i32, _p, _p, _p, _p, _i32, _p, _p],
     'dv_loss_assemble_after': [C.POINTER(Wait), C.POINTER(LossTerm), _i32, _p, _p, _p, C.POINTER(Bump), _p, _i32, _p, _p],
     'dv_axpby': [_p, _f, _p, _f, _i64, _p],

@@ -343,7 +343,9 @@ class DiagGaussianModule(GaussianLogVarMixin, nn.Module):
         h = self.nnet.features(inputs)
         mu = _run_sequential(self.encoder_mu, h)
         if self.fixed_variance is not None:
-            logvar = self.fixed_variance.to(mu.device).expand_as(mu)
+            if self.fixed_variance.device != mu.device:      # (moved once: no host-to-device copy inside a captured sequence)
+                self.fixed_variance = self.fixed_variance.to(mu.device)
+            logvar = self.fixed_variance.expand_as(mu)
         else:
             logvar = _run_sequential(self.encoder_lv, h, shift=-2.0)
         return mu, logvar

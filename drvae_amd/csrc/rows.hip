@@ -2133,6 +2133,73 @@ __global__ __launch_bounds__(1024) void recon_finalize_kernel(const float* __res
     }
 }
 
+// out[0..2] = rmse, R^2, Pearson r (float64) of a continuous target over the n selected rows x Y columns, both arrays
+// flattened (src/DGMMixin.py:181-188).  TWO passes -- the means, then the centred sums: the one-pass moment formula
+// cancels for targets clustered in (0,1).  One workgroup; every thread walks its elements in a fixed order, the waves
+// and then the 16 wave sums are added in a fixed order: two calls give the same bits.
+__global__ __launch_bounds__(1024) void reg_metrics_kernel(const float* __restrict__ pred, int64_t ldp,
+                                                           const float* __restrict__ y, int64_t ldy,
+                                                           const int32_t* __restrict__ sel, int n, int Y,
+                                                           double* __restrict__ out) {
+    __shared__ double red[4][16];
+    __shared__ double mean[2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t total = (int64_t)n * Y;
+    double sy = 0., sp = 0.;
+    for (int64_t e = threadIdx.x; e < total; e += 1024) {
+        const int r = (int)(e / Y), c = (int)(e - (int64_t)r * Y);
+        const int64_t i = sel ? sel[r] : r;
+        sy += (double)y[i * ldy + c];
+        sp += (double)pred[i * ldp + c];
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        sy += __shfl_xor(sy, off);
+        sp += __shfl_xor(sp, off);
+    }
+    if (lane == 0) {
+        red[0][wave] = sy;
+        red[1][wave] = sp;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        double t = 0.;
+        for (int w = 0; w < 16; ++w) t += red[threadIdx.x][w];
+        mean[threadIdx.x] = t / (double)total;
+    }
+    __syncthreads();
+    const double my = mean[0], mp = mean[1];
+    double v[4] = {0., 0., 0., 0.};      // sum (y-p)^2, sum yc^2, sum pc^2, sum yc pc
+    for (int64_t e = threadIdx.x; e < total; e += 1024) {
+        const int r = (int)(e / Y), c = (int)(e - (int64_t)r * Y);
+        const int64_t i = sel ? sel[r] : r;
+        const double yv = (double)y[i * ldy + c], pv = (double)pred[i * ldp + c];
+        const double d = yv - pv, yc = yv - my, pc = pv - mp;
+        v[0] += d * d;
+        v[1] += yc * yc;
+        v[2] += pc * pc;
+        v[3] += yc * pc;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        double t = v[k];
+        for (int off = 32; off >= 1; off >>= 1) t += __shfl_xor(t, off);
+        if (lane == 0) red[k][wave] = t;     // (the means were read out of ``mean`` behind the barrier above)
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t[4];
+        for (int k = 0; k < 4; ++k) {
+            t[k] = 0.;
+            for (int w = 0; w < 16; ++w) t[k] += red[k][w];
+        }
+        const double nan = __longlong_as_double(0x7ff8000000000000LL);
+        const double den = sqrt(t[1] * t[2]);
+        out[0] = total ? sqrt(t[0] / (double)total) : nan;
+        out[1] = t[1] > 0. ? 1.0 - t[0] / t[1] : nan;
+        out[2] = den > 0. ? t[3] / den : nan;
+    }
+}
+
 // counts[c][e][0..3] += { rows scoring above e, rows tied with e (e itself included), positives above, positives tied }
 // over the j-range of this workgroup; e, j index the selected rows; class c scores proba[row, c0 + c]
 constexpr int kPairJ = 512;
@@ -3189,6 +3256,13 @@ extern "C" int dv_recon_finalize(const float* rows, const int32_t* sel, int32_t 
                                  int32_t row_blocks, const float* ll, double* out, dv_stream_t stream) {
     DV_REQUIRE(n >= 0 && X >= 1 && row_blocks >= 1 && rows && cols && out);
     hipLaunchKernelGGL(recon_finalize_kernel, dim3(1), dim3(1024), 0, ST(stream), rows, sel, n, X, cols, row_blocks, ll, out);
+    DV_RETURN_LAUNCH();
+}
+
+extern "C" int dv_reg_metrics(const float* pred, int64_t ldp, const float* y, int64_t ldy, const int32_t* sel, int32_t n,
+                              int32_t Y, double* out, dv_stream_t stream) {
+    DV_REQUIRE(pred && y && out && n >= 0 && Y >= 1 && ldp >= Y && ldy >= Y);
+    hipLaunchKernelGGL(reg_metrics_kernel, dim3(1), dim3(1024), 0, ST(stream), pred, ldp, y, ldy, sel, n, Y, out);
     DV_RETURN_LAUNCH();
 }
 

@@ -185,8 +185,10 @@ class FitMixin:
         """Whole-set evaluation (src/DrVAE.py:797,821 call it on the train and on the validation set every epoch).  For
         an HBM-resident dataset it is ONE hipGraph replay and ONE device->host copy: eval-mode losses, means-only
         inference, reconstruction statistics and the prediction metrics captured once per (model, dataset) -- see
-        ``_EvalGraph``.  ``return_full_data`` (arrays for the caller), ``use_s`` models, continuous targets and host
-        datasets take the step-by-step path."""
+        ``_EvalGraph``.  That includes the regression head (``type_y='cont'``: rmse / R^2 / Pearson r from ``dv_reg_metrics``) and
+        models conditioned on the nuisance variable (``use_s``; with ``use_MMD`` for ``kernel_MMD='rbf_fourier' | 'identity'``
+        and 2 <= dim_s <= 8, the penalty as its two grouped launches).  ``return_full_data`` (arrays for the caller), host
+        datasets, ``type_rec='binary' | 'poisson'`` and the other MMD kernels take the step-by-step path."""
         g = lambda k: getattr(ds, k, None)
         ev = None if return_full_data else _EvalGraph.get(self, ds)
         if ev is not None:
@@ -406,23 +408,41 @@ class _EvalGraph:
         the whole set, its inputs gathered device-to-device from the dataset;
       * the means-only inference ``forward`` (block level: the same HIP kernels);
       * ``dv_recon_row_stats`` / ``dv_col_moments`` and their float64 combination, the Gaussian log-likelihood mean;
-      * accuracy / AUROC / AUPR by sort + scan on the device (``metrics.*_dev``: no compaction, no host decisions);
+      * accuracy / AUROC / AUPR by sort + scan on the device (``metrics.*_dev``: no compaction, no host decisions); for the
+        regression head rmse / R^2 / Pearson r of the means (``dv_reg_metrics``: one launch, two-pass float64 sums);
+      * ``use_s``: the whole set's plan carries the nuisance classes on the device (``_Plan.carry_nuisance``) and the sequence
+        feeds them from ``ds.s`` (``dv_nuisance_feed``: the loss pass's one-hot columns and class vector, and the one-hot operand
+        of the inference's encoder / decoder chains); the MMD penalty's value comes from ``dv_mmd_grouped_fwd`` -- a term with an
+        empty side counts 0 there, where ``_evaluate``'s host-list plan compares with one random row (DESIGN.md 9);
     every scalar lands in one float64 vector.  ``run()`` = set the annealing coefficient, replay, ONE copy to the host.
     The group index lists (rows with a second profile / a label) are data of the DATASET, taken once; the arrays
-    themselves are read by the replay, so a dataset edited in place is evaluated as edited."""
+    themselves -- inputs, labels, regression targets, nuisance classes -- are read by the replay, so a dataset edited in
+    place is evaluated as edited."""
 
     @staticmethod
     def get(model, ds):
+        from . import kernels as K
         x1 = getattr(ds, 'x1', None)
-        if not (torch.is_tensor(x1) and x1.is_cuda) or getattr(model, 'use_s', False) \
-                or getattr(model, 'type_y', 'discrete') != 'discrete' or getattr(model, 'type_rec', 'diag_gaussian') != 'diag_gaussian':
+        if not (torch.is_tensor(x1) and x1.is_cuda) or getattr(model, 'type_rec', 'diag_gaussian') != 'diag_gaussian':
             return None
         if next(model.parameters()).device != x1.device:
             return None
-        need = ('x1',) + (('x2', 'has_x2') if model.kind != 'vfae' else ()) + (('y', 'has_y') if model.kind != 'pvae' else ())
+        # (the decision is a function of the model's configuration and the dataset's tensors alone: every rank of a
+        # data-parallel job decides alike)
+        use_s = bool(getattr(model, 'use_s', False))
+        cont = model.kind != 'pvae' and getattr(model, 'type_y', 'discrete') != 'discrete'
+        if use_s and getattr(model, 'use_MMD', False) and not (
+                getattr(model, 'kernel_MMD', 'rbf_fourier') in K.MMD_GROUPED_KIND and 2 <= int(model.dim_s) <= K.MMD_MAX_CLASSES):
+            return None          # (the penalty's grouped launches cover these; the rest keeps the host-list path)
+        need = ('x1',) + (('x2', 'has_x2') if model.kind != 'vfae' else ()) + (('y', 'has_y') if model.kind != 'pvae' else ()) \
+            + (('s',) if use_s else ())
         parts = [getattr(ds, k, None) for k in need]
         if not all(torch.is_tensor(t) and t.device == x1.device for t in parts):
             return None          # (a host-resident label / flag array would be a pageable copy under capture)
+        if cont and not ds.y.is_floating_point():
+            return None
+        if use_s and (ds.s.is_floating_point() or ds.s.is_complex() or ds.s.dtype == torch.bool):
+            return None
         cache = model.__dict__.setdefault('_eval_graphs', {})
         # the captured launches point into the engine's arena, plan and layer chains: ``.cpu().cuda()`` / ``.to()`` retire
         # the engine (DGMMixin._apply) and a graph of the old one would read freed parameters -- the engine's identity is
@@ -433,7 +453,7 @@ class _EvalGraph:
         dp = model._dp if (getattr(model, '_dp', None) is not None and getattr(model, 'shard_evaluation', True)
                            and int(x1.shape[0]) >= 2 * model._dp[1]) else None
         sig = tuple(int(t.data_ptr()) if torch.is_tensor(t) else 0
-                    for t in (getattr(ds, k, None) for k in ('x1', 'x2', 'y', 'has_x2', 'has_y'))) + \
+                    for t in (getattr(ds, k, None) for k in ('x1', 'x2', 'y', 'has_x2', 'has_y') + (('s',) if use_s else ()))) + \
             (int(x1.shape[0]), id(eng), int(eng.arena.param.data_ptr()), dp)
         ev = cache.get(id(ds))
         if ev is None or ev.sig != sig:
@@ -454,6 +474,8 @@ class _EvalGraph:
         self.graph = None
         kind = model.kind
         dev = ds.x1.device
+        self.cont = kind != 'pvae' and getattr(model, 'type_y', 'discrete') != 'discrete'
+        self.use_s = bool(getattr(model, 'use_s', False))
         self.dp, self.full = dp, None
         if dp is not None:
             # this rank's rows as VIEWS of the dataset's tensors; the normalisers of the loss pass are the whole set's counts,
@@ -483,9 +505,13 @@ class _EvalGraph:
         # the loss plan of the whole set: built by the ordinary path (host index lists), then reused
         eng = model.engine()
         keep, keep_training, was_training = eng.plan, eng.training, model.training
-        keep_counts, keep_row0 = model.__dict__.get('_global_counts'), eng.row0
+        keep_counts, keep_row0, keep_carry = model.__dict__.get('_global_counts'), eng.row0, eng.carry_s
         try:
             model.eval()
+            # ``use_s``: the whole set's plan carries the nuisance classes on the device (``_Plan.carry_nuisance``): nothing in it
+            # depends on the set's composition of classes, ``_sequence`` feeds them from ``ds.s``.  A plan of its own key: the
+            # plan a bound ``DeviceBatcher`` replays stays in the cache (``_evict_plans`` never drops a captured step's)
+            eng.carry_s = self.use_s
             kw = dict(x1=g('x1'), s=g('s'))
             if kind != 'vfae':
                 kw.update(x2=g('x2'), has_x2=g('has_x2'))
@@ -515,7 +541,7 @@ class _EvalGraph:
                     self._finalize_full()
             self.graph = gph
         finally:
-            eng.plan, eng.training = keep, keep_training
+            eng.plan, eng.training, eng.carry_s = keep, keep_training, keep_carry
             model.train(was_training)
             if dp is not None:
                 model.__dict__.pop('_row0_override', None)
@@ -539,6 +565,23 @@ class _EvalGraph:
         if eng.cfg.has_pert:
             x2 = ds.x2.to(torch.float32)
             p.XSRC[p.B:].copy_(x2.index_select(0, self.sel) if self.sel is not None else x2)
+        n_in = int(ds.x1.shape[0])
+        if self.cont:      # the regression targets of the plan's rows (read by the replay: targets edited in place count)
+            y2 = ds.y.reshape(n_in, -1).to(torch.float32)
+            p.ylab.copy_(y2.index_select(0, self.sel) if self.sel is not None else y2)
+        if self.use_s:
+            # the nuisance classes, device to device -- the launch ``_Plan.set_s_device`` makes: one-hot columns of the stacked
+            # encoder / decoder rows and the class vector the grouped MMD penalty reads; then the same for the inference
+            # below: one_hot(s) of every row of the set, the decoder's stacked rows [z1; z2] use the same classes twice
+            s32 = ds.s.reshape(-1).to(torch.int32)
+            K.nuisance_feed(p.SOHe, p.SOHd, p.s_cls, (s32.index_select(0, self.sel) if self.sel is not None else s32).contiguous(),
+                            pair_rows=p.pair_idx if p.Np else None, L=eng.cfg.L)
+            if not hasattr(self, 'soh_d'):
+                S, reps = eng.cfg.dim_s, (2 if kind != 'vfae' else 1)
+                self.soh_e = torch.zeros(n_in, (S + 3) // 4 * 4, device=dev)[:, :S]
+                self.soh_d = torch.zeros(n_in * reps, (S + 3) // 4 * 4, device=dev)[:, :S]
+                self.s_all = torch.zeros(n_in, dtype=torch.int32, device=dev)
+            K.nuisance_feed(self.soh_e, self.soh_d, self.s_all, s32.contiguous(), L=2 if kind != 'vfae' else 1)
         eng.training = False
         eng.draw_noise()
         eng.forward()
@@ -547,7 +590,7 @@ class _EvalGraph:
         names = ['loss_' + k for k in sorted(E.LOSS_IDX, key=E.LOSS_IDX.get)]      # (all seven; ``run`` picks the model's)
         n_loss = len(names)
         if kind != 'pvae':
-            names += ['y_auroc', 'y_aupr', 'y_acc']
+            names += ['y_rmse', 'y_r2', 'y_pearr'] if self.cont else ['y_auroc', 'y_aupr', 'y_acc']
         names += ['x1_' + k for k in _NAN4]
         has_x2 = kind != 'vfae' and (len(self.x2idx) > 0 if self.dp is None else self.full_n_x2 > 0)
         if has_x2:
@@ -597,7 +640,9 @@ class _EvalGraph:
             self.full_yidx32 = torch.nonzero(full.has_y.reshape(-1).to(dev)).reshape(-1).to(torch.int32)
         blk1 = max(K.col_moment_blocks(b - a) for a, b in bounds)
         o, self.off = 0, {}
-        for name, size in (('loss', 8), ('proba', n * Y), ('pred', n if Y else 0), ('rows1', n * 6), ('ll1', n),
+        # (regression head: the ``pred`` slot carries the n x Y float means; no class probabilities, no int32 buffers)
+        for name, size in (('loss', 8), ('proba', 0 if self.cont else n * Y), ('pred', n * Y if self.cont else (n if Y else 0)),
+                           ('rows1', n * 6), ('ll1', n),
                            ('part1', world * blk1 * 3 * X), ('rows2', n * 6 if self.full_n_x2 else 0),
                            ('ll2', n if self.full_n_x2 else 0), ('part2', world * blk2 * 3 * X if self.full_n_x2 else 0)):
             self.off[name] = (o, size)
@@ -607,7 +652,9 @@ class _EvalGraph:
         f32 = lambda *shape: torch.zeros(*shape, device=dev)
         self.g_rows = {'x1': f32(n, 6), 'x2': f32(n, 6)}
         self.g_ll = {'x1': f32(n), 'x2': f32(n)}
-        if Y:
+        if Y and self.cont:
+            self.g_pred = f32(n, Y)
+        elif Y:
             self.g_proba, self.g_pred32 = f32(n, Y), torch.zeros(n, dtype=torch.int32, device=dev)
             self.g_y32 = torch.zeros(n, dtype=torch.int32, device=dev)
 
@@ -624,7 +671,9 @@ class _EvalGraph:
         lo, hi, X = self.lo, self.hi, int(ds.x1.shape[1])
         self.pack.zero_()
         self._slot('loss')[:loss_vec.numel()].copy_(loss_vec)
-        if kind != 'pvae':
+        if kind != 'pvae' and self.cont:
+            self._slot('pred').view(self.n_all, m.dim_y)[lo:hi].copy_(res['pred'])
+        elif kind != 'pvae':
             Y = m.dim_y
             self._slot('proba').view(self.n_all, Y)[lo:hi].copy_(res['proba'])
             self._slot('pred')[lo:hi].copy_(res['pred'].reshape(-1))
@@ -664,7 +713,12 @@ class _EvalGraph:
         n_loss = len(E.LOSS_IDX)
         vec[:n_loss].copy_(self._slot('loss')[:n_loss])
         o = n_loss
-        if kind != 'pvae':
+        if kind != 'pvae' and self.cont:
+            # (the targets are read by the replay: a dataset edited in place is evaluated as edited)
+            self.g_pred.copy_(self._slot('pred').view(n, m.dim_y))
+            K.reg_metrics(vec[o:o + 3], self.g_pred, full.y.reshape(n, -1).to(torch.float32), sel=self.full_yidx32)
+            o += 3
+        elif kind != 'pvae':
             Y = m.dim_y
             self.g_proba.copy_(self._slot('proba').view(n, Y))
             self.g_pred32.copy_(self._slot('pred'))
@@ -709,6 +763,9 @@ class _EvalGraph:
         m, ds = self.model, self.ds
         dev = ds.x1.device
         n_lab, Y = int(self.yidx.numel()), m.dim_y
+        if self.cont:      # regression head: out3 = [rmse, r2, pearr] of the means (src/DGMMixin.py:181-188), one launch
+            K.reg_metrics(out3, res['pred'], ds.y.reshape(int(ds.x1.shape[0]), -1).to(torch.float32), sel=self.yidx32)
+            return
         if n_lab > K.RANK_MAX_ROWS or n_lab == 0:      # (beyond the pair-counting kernel's range: the sort + scan formulation)
             y = ds.y.to(dev)
             ylab = y.reshape(-1).index_select(0, self.yidx)
@@ -762,7 +819,7 @@ class _EvalGraph:
                     self.x1p = torch.zeros(n, (X + 3) // 4 * 4, device=dev)[:, :X]
                 self.x1p.copy_(x1)
                 x1 = self.x1p
-            Q = self.c_enc.forward([x1])
+            Q = self.c_enc.forward([x1] + ([self.soh_e] if self.use_s else []))
         z1 = Q[:, :Z]
         res = OrderedDict(z1=z1, qz1=(z1, Q[:, Z:2 * Z]))
         if kind != 'vfae':
@@ -783,7 +840,7 @@ class _EvalGraph:
         # (bias, softplus + shift: ``dv_recon_rows`` / ``dv_col_moments``): 16384 x 1956 x 600 at the raw product's 126 instead of 104 TF/s
         lh = eng.L_decx[-1]
         raw = bool(X <= K.RECON_ROWS_MAX_X and self.c_dec.raw_last_ok() and lh.act1 == 'softplus')
-        PX = self.c_dec.forward([self.zd], raw_last=raw)
+        PX = self.c_dec.forward([self.zd] + ([self.soh_d] if self.use_s else []), raw_last=raw)
         res['px_bias'] = (lh.b[:X], lh.b[X:2 * X], lh.shift1) if raw else None
         res['px1'] = (PX[:n, :X], PX[:n, X:2 * X])
         if kind != 'vfae':
@@ -833,7 +890,11 @@ class _EvalGraph:
         perf = OrderedDict()
         perf['losses'] = OrderedDict((k, torch.tensor(v['loss_' + k])) for k in self.loss_keys)
         parts = []
-        if kind != 'pvae':
+        if kind != 'pvae' and self.cont:
+            for k in ('rmse', 'r2', 'pearr'):
+                perf['y_' + k] = v['y_' + k]
+            parts.append('Y: RMSE: {:.3f} R2: {:.3f} Pearson: {:.3f}'.format(perf['y_rmse'], perf['y_r2'], perf['y_pearr']))
+        elif kind != 'pvae':
             for k in ('acc', 'auroc', 'aupr'):
                 perf['y_' + k] = v['y_' + k]
             parts.append('Y: Accuracy: {:.3f}% AUROC: {:.3f} AUPR: {:.3f}'.format(perf['y_acc'] * 100., perf['y_auroc'], perf['y_aupr']))

@@ -907,6 +907,20 @@ def rank_metrics(out, counts, proba, y32, *, pred32=None, sel=None, c0=1, n_cls=
                                            int(bool(binary)), counts.data_ptr(), out.data_ptr(), _stream()), 'dv_rank_metrics')
 
 
+def reg_metrics(out3, pred, y, *, sel=None, n=None):
+    """out3 (3 float64) = rmse, R^2, Pearson r of a continuous target over the rows ``sel`` (int32; None: the first ``n``
+    rows, default all) x the Y columns of ``pred`` / ``y`` ((rows, Y) fp32, row strides free), both flattened; two-pass
+    float64 sums in a fixed order (``dv_reg_metrics``)"""
+    pred = pred.reshape(-1, 1) if pred.dim() == 1 else pred
+    y = y.reshape(-1, 1) if y.dim() == 1 else y
+    n = (sel.numel() if sel is not None else pred.shape[0]) if n is None else n
+    assert pred.dim() == 2 and y.dim() == 2 and pred.shape[1] == y.shape[1]
+    assert sel is not None or (n <= pred.shape[0] and n <= y.shape[0])
+    assert out3.dtype == torch.float64 and out3.is_cuda and out3.numel() >= 3 and out3.is_contiguous()
+    _lib.check(_lib.load().dv_reg_metrics(_f32(pred), _ld(pred), _f32(y), _ld(y), _i32(sel), n, pred.shape[1],
+                                          out3.data_ptr(), _stream()), 'dv_reg_metrics')
+
+
 def loss_assemble(loss, terms, w_elbo, w_cmpl, after=None, bump=(), halt=None, accum=None):
     """terms: list of (x, w_or_None, scale, out_index); see ``dv_loss_assemble``.  ``after`` =
     a ``Wait``: park like ``flag_wait`` inside the same launch first;

@@ -872,6 +872,16 @@ int dv_recon_finalize(const float* rows, const int32_t* sel, int32_t n, int32_t 
                       const float* ll, double* out, dv_stream_t stream);
 int dv_rank_metrics(const float* proba, int64_t ldp, const int32_t* y, const int32_t* pred, const int32_t* sel, int32_t n,
                     int32_t c0, int32_t n_cls, int32_t binary, int32_t* counts, double* out, dv_stream_t stream);
+/* dv_reg_metrics: `eval_y_prediction` for a CONTINUOUS target (src/DGMMixin.py:181-188: numpy / sklearn r2_score / scipy
+ *   pearsonr) over the n selected rows (`sel`, NULL = rows 0..n-1) x Y columns of pred / y (fp32), both flattened:
+ *     out[0] = sqrt(mean((y-p)^2))
+ *     out[1] = 1 - sum((y-p)^2) / sum((y-mean y)^2)                                    (nan: sum((y-mean y)^2) == 0)
+ *     out[2] = sum((y-mean y)(p-mean p)) / sqrt(sum((y-mean y)^2) sum((p-mean p)^2))   (nan: zero denominator)
+ *   n == 0: all three nan.  Float64 accumulation, TWO passes (means, then centred sums: no cancellation for targets
+ *   clustered in (0,1)), one workgroup, fixed summation order, no atomics: two calls give bit-equal results.  (ABI 12,
+ *   additive) */
+int dv_reg_metrics(const float* pred, int64_t ldp, const float* y, int64_t ldy, const int32_t* sel, int32_t n, int32_t Y,
+                   double* out, dv_stream_t stream);
 
 /* All loss scalars of one step in a single launch (src/DrVAE.py:611-624):
  *   loss[0..4] = 0; for each term: loss[out] += scale * sum_i w[i]*x[i]   (w == NULL: plain sum)
