@@ -18,7 +18,7 @@ class DrVAE(ELBOModel):
                  yloss_rate=1., anneal_yloss_offset=0, use_MMD=True, kernel_MMD='rbf_fourier', mmd_rate=1.,
                  kl_qz2pz2_rate=1., pertloss_rate=0.1, anneal_perturb_rate_itermax=1,
                  anneal_perturb_rate_offset=0, use_s=False, use_c=False, use_m=False, random_seed=12345,
-                 log_txt=None, weight_norm=False, device=None):
+                 log_txt=None, weight_norm=False, device=None, matmul_precision='fp32'):
         super().__init__()
         args = dict(locals())
         args.pop('self')

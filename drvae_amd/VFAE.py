@@ -13,7 +13,7 @@ class VFAE(ELBOModel):
                  batch_size=100, nonlinearity='softplus', learning_rate=0.001, optim_alg='adam', L=1,
                  weight_decay=None, dropout_rate=0., input_x_dropout=0., add_noise_var=0., yloss_rate=1.,
                  anneal_yloss_offset=0, use_MMD=True, kernel_MMD='rbf_fourier', mmd_rate=1., use_s=False,
-                 random_seed=12345, log_txt=None, weight_norm=False, device=None):
+                 random_seed=12345, log_txt=None, weight_norm=False, device=None, matmul_precision='fp32'):
         super().__init__()
         args = dict(locals())
         args.pop('self')

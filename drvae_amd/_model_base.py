@@ -23,6 +23,10 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         src/DrVAE.py:71-74) and set the hyper-parameters it hard-codes (src/DrVAE.py:79-97)."""
         device = args.pop('device', None)
         weight_norm = args.pop('weight_norm', False)
+        # 'fp32' | 'bf16x3' (opt-in): the arithmetic of the chip-filling decoder-heads products, see ``StepConfig.matmul``
+        self._matmul = args.pop('matmul_precision', 'fp32')
+        if self._matmul not in E.MATMUL_CHOICES:
+            raise ValueError('matmul_precision must be one of %s' % (E.MATMUL_CHOICES,))
         for k, v in args.items():
             setattr(self, k, v)
         self.wn = bool(weight_norm)   # reference: hard-coded False (src/DrVAE.py:79); exposed here
@@ -131,7 +135,7 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
             use_MMD=bool(getattr(self, 'use_s', False) and getattr(self, 'use_MMD', False)),
             mmd_rate=float(getattr(self, 'mmd_rate', 1.)), kernel_MMD=getattr(self, 'kernel_MMD', 'rbf_fourier'),
             prior_y=None if (getattr(self, 'prior_y', None) is None or isinstance(getattr(self, 'prior_y', None), str))
-            else tuple(float(v) for v in self.prior_y))
+            else tuple(float(v) for v in self.prior_y), matmul=self._matmul)
 
     # ---------------------------------------------------------------- inference
     @torch.no_grad()

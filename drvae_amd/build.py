@@ -8,7 +8,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 LIB = os.path.join(HERE, 'libdrvae_hip.so')
 HEADER = os.path.join(os.path.dirname(HERE), 'include', 'drvae_hip.h')
-SOURCES = ['gemm.hip', 'rows.hip', 'optim.hip', 'nuisance.hip']
+SOURCES = ['gemm.hip', 'rows.hip', 'optim.hip', 'nuisance.hip', 'gemm_x3.hip']
 SOURCE_EXT = ('.hip', '.inc', '.h')
 
 

@@ -57,6 +57,10 @@ class _Chain:
 
     def __init__(self, layers, M, device, resid_cols=0):
         self.layers, self.M, self.resid_cols = layers, M, resid_cols
+        # opt-in (``use_x3_last``, decided where the plan is built): the LAST layer's plain product (``raw_last``) and the two
+        # gradient products behind it run as split-bf16 products
+        self.x3_last = False
+        self._x3_fwd = False        # did the latest forward pass take them?
         self.out = [torch.zeros(M, _pad4(l.N), device=device)[:, :l.N] for l in layers]
         # gradient w.r.t. the pre-activation of every layer but the last (the caller owns that one)
         self.dpre = [torch.zeros(M, _pad4(l.N), device=device)[:, :l.N] for l in layers[:-1]]
@@ -77,6 +81,39 @@ class _Chain:
         l = self.layers[-1]
         return l.g is None and l.split * 2 == l.N and l.act0 == 'identity' and self.resid_cols == 0
 
+    # the last layer's raw product and its gradient pair, as launched AND as asked about at plan time (``use_x3_last``)
+    def _raw_last_call(self, x, publish=None):
+        return (self.out[-1], x, self.layers[-1].W, True, True), dict(overread=True, publish=publish, kpad=self._pad_ok(x))
+
+    def _bwd_pair_call(self, li, db, dpre, x, publish=None):
+        l, prev = self.layers[li], self.layers[li - 1]
+        return (l.dW, db, self.dpre[li - 1], dpre, x, l.W), dict(yref=self.out[li - 1], act=prev.act0, shift=prev.shift0,
+                                                               overread=True, publish=publish, npad=self._pad_ok(x),
+                                                               npad_x=True)
+
+    def use_x3_last(self, dpre_last, db_in_pass):
+        """Route the last layer's raw product, its weight gradient and its data gradient to ``dv_gemm_x3`` from now on.
+        Decides up front: raises ValueError naming the reason when one of the three descriptors is not one the split-bf16
+        kernels run (``dpre_last`` as ``backward`` will get it; ``db_in_pass``: the bias gradient comes from the producer
+        of ``dpre_last``, not from the weight-gradient product)."""
+        l, n = self.layers[-1], len(self.layers)
+        why = None
+        if not self.raw_last_ok():
+            why = 'the layer cannot run as a plain product'
+        elif n == 1:
+            why = 'the layer is the chain\'s only one (its gradient products are not a plain pair)'
+        else:
+            x = self.out[n - 2]
+            a, kw = self._raw_last_call(x)
+            why = K.x3_refusal(*a, **kw)
+            if why is None:
+                a, kw = self._bwd_pair_call(n - 1, None if db_in_pass else l.db, dpre_last, x)
+                why = K.x3_pair_refusal(*a, **kw)
+        if why is not None:
+            raise ValueError("matmul='bf16x3': the decoder-heads layer (%d x %d, %d rows) cannot run on dv_gemm_x3: %s"
+                             % (l.N, l.Kin, self.M, why))
+        self.x3_last = True
+
     def forward(self, inputs, resid=None, publish=None, heads=None, raw_last=False):
         """``publish`` = (flag, counter, add): the FIRST launch of the chain publishes on entry.
         ``raw_last``: the last layer's launch is the plain product x W^T -- bias, the second head's activation and its
@@ -85,6 +122,7 @@ class _Chain:
         with that row work fused into its epilogue (with ``nll`` the heads themselves are NOT stored: ``out``
         receives their gradients)."""
         x = list(inputs)
+        self._x3_fwd = bool(raw_last and self.x3_last and heads is None)
         for li, l in enumerate(self.layers):
             if l.g is not None:
                 K.wn_scale(l.scale, l.norm, l.W, l.g)
@@ -101,8 +139,12 @@ class _Chain:
                 return self.out[-1]
             if last and raw_last:
                 assert self.raw_last_ok() and resid is None
-                K.gemm(self.out[li], x[0], l.W, True, True, A2=x[1] if len(x) > 1 else None, overread=True,
-                       publish=publish if li == 0 else None, kpad=kpad)
+                if self._x3_fwd:
+                    a, kw = self._raw_last_call(x[0], publish if li == 0 else None)
+                    K.gemm(*a, x3=True, **kw)
+                else:
+                    K.gemm(self.out[li], x[0], l.W, True, True, A2=x[1] if len(x) > 1 else None, overread=True,
+                           publish=publish if li == 0 else None, kpad=kpad)
                 return self.out[-1]
             K.linear_fwd(self.out[li], x[0], l.W, l.b, x2=x[1] if len(x) > 1 else None, scale=l.scale, split=l.split,
                          act0=l.act0, act1=l.act1, shift0=l.shift0, shift1=l.shift1,
@@ -141,9 +183,9 @@ class _Chain:
             if l.g is None and len(srcs) == 1 and single_dst:
                 if li > 0:
                     prev = self.layers[li - 1]
-                    K.linear_bwd_pair(l.dW, db, self.dpre[li - 1], dpre, srcs[0], l.W, yref=self.out[li - 1],
-                                      act=prev.act0, shift=prev.shift0, overread=True, publish=pending_pub,
-                                      npad=self._pad_ok(srcs[0]), npad_x=True)
+                    # (the layer whose forward ran as a split-bf16 product: so do its two gradient products)
+                    a, kw = self._bwd_pair_call(li, db, dpre, srcs[0], pending_pub)
+                    K.linear_bwd_pair(*a, **kw, **(dict(x3=True) if (self._x3_fwd and li == n_layers - 1) else {}))
                     dpre = self.dpre[li - 1]
                 else:
                     dst, alpha, beta = dinputs[0][0]

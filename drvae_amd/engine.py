@@ -36,6 +36,8 @@ from .plan import LOSS_IDX, _Plan
 from .schedule import DUAL, EVAL, FORK_JOIN, StepSchedule, StepSync, _Branch
 
 
+MATMUL_CHOICES = ('fp32', 'bf16x3')
+
 
 @dataclass
 class StepConfig:
@@ -81,6 +83,14 @@ class StepConfig:
     use_MMD: bool = False
     mmd_rate: float = 1.0
     kernel_MMD: str = 'rbf_fourier'
+    # OPT-IN arithmetic of the decoder-heads layer where it takes the raw-heads route (the chip-filling products of the wide
+    # configuration): 'fp32' = fp32 MFMA like every other product (default) | 'bf16x3' = split-bf16 products, six bf16 MFMA
+    # terms per fp32 product with fp32 accumulation (``dv_gemm_x3``).  Decided once, where the plan is built
+    matmul: str = 'fp32'
+
+    def __post_init__(self):
+        if self.matmul not in MATMUL_CHOICES:
+            raise ValueError('StepConfig.matmul must be one of %s, not %r' % (MATMUL_CHOICES, self.matmul))
 
     @property
     def cont(self):
@@ -478,6 +488,11 @@ class FusedStep(StepSchedule):
         alone fill the chip with 128x128 tiles many times over (wide configuration) the plain GEMM + row pass wins"""
         return ((dpx.shape[0] + 127) // 128) * ((dpx.shape[1] + 127) // 128) < 1024
 
+    def _raw_heads_ok(self, c_decx, dpx):
+        """the raw-heads route: may the decoder's heads layer run as a plain product, finished by the NLL row pass?"""
+        return bool(self.cfg.type_rec == 'diag_gaussian' and c_decx.raw_last_ok() and c_decx.layers[-1].act1 == 'softplus'
+                    and (not self._heads_small(dpx) or T.get('raw_heads') == 2))     # (2: any size -- tests)
+
     def beta_pert(self):
         cfg = self.cfg
         if cfg.anneal_perturb_rate_itermax > 0:
@@ -657,8 +672,7 @@ class FusedStep(StepSchedule):
         else:
             # chip-filling heads in a train step: the product runs with the plain epilogue, the NLL row pass behind it
             # adds the bias and applies softplus + shift on its way (wide configuration: 10.87 -> 9.97 ms for the launch)
-            raw_ok = bool(gauss and p.c_decx.raw_last_ok() and p.c_decx.layers[-1].act1 == 'softplus'
-                          and (not self._heads_small(p.DPX) or T.get('raw_heads') == 2))     # (2: any size -- tests)
+            raw_ok = self._raw_heads_ok(p.c_decx, p.DPX)
             raw = raw_ok and self.fuse_bwd
             # an EVALUATION pass over many rows (whole-set evaluation, round 5): the heads are needed for the row terms only
             # -- plain product, finished inside the row pass (32768 x 1956 x 600: 737 -> 589 us for the product, and no

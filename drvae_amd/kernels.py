@@ -20,10 +20,11 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-def _f32(t, name='tensor'):
+def _f32(t, name='tensor', any_device=False):
+    """``any_device``: the address goes into a descriptor that is looked at, never launched (``x3_refusal``)"""
     if t is None:
         return None
-    if not (t.is_cuda and t.dtype == torch.float32):
+    if not ((t.is_cuda or any_device) and t.dtype == torch.float32):
         raise RuntimeError('drvae_amd kernels need CUDA/HIP float32 tensors (%s is %s on %s); there is no CPU '
                            'fallback' % (name, t.dtype, t.device))
     if t.dim() >= 1 and t.numel() > 0 and t.stride(-1) != 1 and t.size(-1) != 1:
@@ -84,7 +85,8 @@ def _tune_ptr():
 
 def _gemm_desc(Cm, A, B, a_kc, b_kc, *, A2=None, a_kscale=None, alpha=1.0, beta=0.0, epi=EPI_PLAIN, scale=None,
                bias=None, split=None, act0=0, act1=0, shift0=0.0, shift1=0.0, resid=None, resid_cols=0, yref=None,
-               a_colsum=None, colsum_beta=0.0, overread=False, publish=None, kpad=False, npad=False):
+               a_colsum=None, colsum_beta=0.0, overread=False, publish=None, kpad=False, npad=False, _any_device=False):
+    f32 = lambda t, name: _f32(t, name, _any_device)
     M, N = Cm.shape
     if a_kc:
         K = A.shape[1] + (A2.shape[1] if A2 is not None else 0)
@@ -98,7 +100,7 @@ def _gemm_desc(Cm, A, B, a_kc, b_kc, *, A2=None, a_kscale=None, alpha=1.0, beta=
         assert tuple(B.shape) == (K, N), (tuple(B.shape), K, N)
     d = GemmDesc()
     d.M, d.N, d.K, d.a_kcontig, d.b_kcontig = M, N, K, int(bool(a_kc)), int(bool(b_kc))
-    d.A, d.lda = _f32(A, 'A'), _ld(A)
+    d.A, d.lda = f32(A, 'A'), _ld(A)
     if kpad and a_kc and b_kc and A2 is None and (K & 3) and min(_ld(A), _ld(B)) >= ((K + 3) & ~3) \
             and not ((A.data_ptr() | B.data_ptr()) & 15) and not ((_ld(A) | _ld(B)) & 3):
         # ``kpad``: the caller guarantees that the rows of both operands are ZERO from K up to the next multiple of 4
@@ -112,17 +114,17 @@ def _gemm_desc(Cm, A, B, a_kc, b_kc, *, A2=None, a_kscale=None, alpha=1.0, beta=
         # are padded the same way: the product over the padded N writes zeros into C's pad columns (they are zero
         # anyway) and every output row ends on a 16-B store
         d.N = N = (N + 3) & ~3
-    d.A2, d.lda2, d.K1 = _f32(A2, 'A2'), _ld(A2), (A.shape[1] if A2 is not None else K)
-    d.a_kscale = _f32(a_kscale, 'a_kscale')
-    d.B, d.ldb = _f32(B, 'B'), _ld(B)
-    d.C, d.ldc = _f32(Cm, 'C'), _ld(Cm)
+    d.A2, d.lda2, d.K1 = f32(A2, 'A2'), _ld(A2), (A.shape[1] if A2 is not None else K)
+    d.a_kscale = f32(a_kscale, 'a_kscale')
+    d.B, d.ldb = f32(B, 'B'), _ld(B)
+    d.C, d.ldc = f32(Cm, 'C'), _ld(Cm)
     d.alpha, d.beta, d.epilogue = alpha, beta, epi
-    d.scale, d.bias = _f32(scale, 'scale'), _f32(bias, 'bias')
+    d.scale, d.bias = f32(scale, 'scale'), f32(bias, 'bias')
     d.split = N if split is None else split
     d.act0, d.act1, d.shift0, d.shift1 = _act(act0), _act(act1), shift0, shift1
-    d.resid, d.ldr, d.resid_cols = _f32(resid, 'resid'), _ld(resid), resid_cols
-    d.yref, d.ldy = _f32(yref, 'yref'), _ld(yref)
-    d.a_colsum, d.colsum_beta = _f32(a_colsum, 'a_colsum'), colsum_beta
+    d.resid, d.ldr, d.resid_cols = f32(resid, 'resid'), _ld(resid), resid_cols
+    d.yref, d.ldy = f32(yref, 'yref'), _ld(yref)
+    d.a_colsum, d.colsum_beta = f32(a_colsum, 'a_colsum'), colsum_beta
     d.flags = 3 if overread else 0
     if publish is not None:                 # ``Publish``: on kernel entry, see dv_flag_publish
         publish = Publish(*publish)
@@ -131,33 +133,99 @@ def _gemm_desc(Cm, A, B, a_kc, b_kc, *, A2=None, a_kscale=None, alpha=1.0, beta=
     return d
 
 
-def gemm(Cm, A, B, a_kc, b_kc, **kw):
+def _x3_refusal(d):
+    """why ``dv_gemm_x3`` does not run descriptor ``d`` (None: it does).  The verdict is the library's (``dv_gemm_x3_ok``,
+    a pure host function); this only puts a name to it."""
+    if _lib.load().dv_gemm_x3_ok(C.byref(d)):
+        return None
+    why = []
+    if d.A2:
+        why.append('a second A source (A2)')
+    if d.a_kscale:
+        why.append('a per-k scale (a_kscale)')
+    if d.epilogue not in (EPI_PLAIN, EPI_BWD):
+        why.append('epilogue %d (only DV_EPI_PLAIN and DV_EPI_BWD)' % d.epilogue)
+    if d.pub_flag:
+        why.append('a publish on entry (pub_flag)')
+    if (d.K & 3) and ((d.a_kcontig and not d.flags & 1) or (d.b_kcontig and not d.flags & 2)):
+        why.append('K = %d is no multiple of 4 and the rows of a k-contiguous operand may not be over-read' % d.K)
+    if ((d.A or 0) | (d.B or 0)) & 15 or (d.lda | d.ldb) & 3:
+        why.append('operand rows that are not 16-B aligned')
+    if not d.a_kcontig and d.b_kcontig:
+        why.append('the layout (a_kcontig, b_kcontig) = (0, 1)')
+    if d.a_colsum and (d.a_kcontig or d.b_kcontig):
+        why.append('a_colsum outside the dy^T x layout')
+    return ', '.join(why) or 'dv_gemm_x3_ok refuses the descriptor'
+
+
+def _launch_x3(descs, what):
+    """bf16x3 routing decides up front: every descriptor of the call must be one ``dv_gemm_x3`` runs -- no silent fallback"""
+    for d in descs:
+        why = _x3_refusal(d)
+        if why is not None:
+            raise RuntimeError('%s(x3=True): the split-bf16 kernels do not run this %d x %d x %d product: %s'
+                               % (what, d.M, d.N, d.K, why))
+    lib = _lib.load()
+    for d in descs:
+        _lib.check(lib.dv_gemm_x3(C.byref(d), _stream()), 'dv_gemm_x3')
+
+
+def gemm(Cm, A, B, a_kc, b_kc, x3=False, **kw):
     """C[M,N] = epilogue(alpha * Aop @ Bop) + beta*C, see ``dv_gemm`` in include/drvae_hip.h.
-    ``overread``: rows of A and B may be over-read by up to 3 floats (padded / arena buffers)."""
+    ``overread``: rows of A and B may be over-read by up to 3 floats (padded / arena buffers).
+    ``x3`` (opt-in): the product runs as a split-bf16 product (``dv_gemm_x3``; dtype bf16x3) -- raises where that entry
+    point does not take the descriptor."""
     d = _gemm_desc(Cm, A, B, a_kc, b_kc, **kw)
+    if x3:
+        return _launch_x3([d], 'gemm')
     _lib.check(_lib.load().dv_gemm(C.byref(d), _stream()), 'dv_gemm')
 
 
-def linear_bwd_pair(dW, dbias, dx, dpre, x, W, *, kscale=None, alpha=1.0, beta_x=0.0, yref=None, act=0, shift=0.0,
-                    overread=False, publish=None, npad=False, npad_x=False, klq=None):
-    """dW = dpre^T x (+ dbias) and dx = beta_x*dx + alpha*(dpre W) * act'(yref) in ONE launch when both fit
-    the fused form of ``dv_gemm_pair`` (otherwise two launches).
-    ``klq`` = dict(out, q, eps, coef, raw, kl_min, Z): the layer's input was [a sample z of the q rows | ...]: instead of
-    dx the launch writes d/d(mu | logvar) of those rows incl. their prior term into ``out`` (M, 2Z) -- the epilogue
-    DV_EPI_KLQ of include/drvae_hip.h; ``dx`` is not written (pass None)"""
-    d1 = _gemm_desc(dW, dpre, x, False, False, a_colsum=dbias, overread=overread, publish=publish, npad=npad)
+def x3_refusal(Cm, A, B, a_kc, b_kc, **kw):
+    """plan-time question: would ``gemm(..., x3=True)`` with these operands run?  None, or the reason why not.  Shapes,
+    strides and addresses only -- nothing is launched, so the operands may live on any device"""
+    return _x3_refusal(_gemm_desc(Cm, A, B, a_kc, b_kc, _any_device=True, **kw))
+
+
+def _pair_descs(dW, dbias, dx, dpre, x, W, *, kscale=None, alpha=1.0, beta_x=0.0, yref=None, act=0, shift=0.0,
+                overread=False, publish=None, npad=False, npad_x=False, klq=None, _any_device=False):
+    """the two descriptors of ``linear_bwd_pair``: dW = dpre^T x (+ dbias) | dx (or the KLQ rows)"""
+    dev = dict(_any_device=_any_device)
+    d1 = _gemm_desc(dW, dpre, x, False, False, a_colsum=dbias, overread=overread, publish=publish, npad=npad, **dev)
     if klq is not None:
         assert yref is None and kscale is None and beta_x == 0.0
         Z, out = klq['Z'], klq['out']
         assert out.shape[1] == 2 * Z and W.shape[1] >= Z and W.shape[1] <= 2 * Z
         d2 = _gemm_desc(out[:, :W.shape[1]], dpre, W, True, False, alpha=alpha, epi=EPI_KLQ, split=Z, yref=klq['q'],
-                        resid=klq['eps'], bias=klq['coef'], scale=klq['raw'], shift0=klq['kl_min'], overread=overread)
+                        resid=klq['eps'], bias=klq['coef'], scale=klq['raw'], shift0=klq['kl_min'], overread=overread, **dev)
     elif yref is None:
-        d2 = _gemm_desc(dx, dpre, W, True, False, a_kscale=kscale, alpha=alpha, beta=beta_x, overread=overread, npad=npad_x)
+        d2 = _gemm_desc(dx, dpre, W, True, False, a_kscale=kscale, alpha=alpha, beta=beta_x, overread=overread, npad=npad_x,
+                        **dev)
     else:
         d2 = _gemm_desc(dx, dpre, W, True, False, a_kscale=kscale, alpha=alpha, beta=beta_x, epi=EPI_BWD, yref=yref,
-                        act0=act, act1=act, shift0=shift, shift1=shift, overread=overread, npad=npad_x)
+                        act0=act, act1=act, shift0=shift, shift1=shift, overread=overread, npad=npad_x, **dev)
+    return d1, d2
+
+
+def linear_bwd_pair(dW, dbias, dx, dpre, x, W, x3=False, **kw):
+    """dW = dpre^T x (+ dbias) and dx = beta_x*dx + alpha*(dpre W) * act'(yref) in ONE launch when both fit
+    the fused form of ``dv_gemm_pair`` (otherwise two launches).  Keywords: kscale, alpha, beta_x, yref, act, shift,
+    overread, publish, npad, npad_x, klq (``_pair_descs``).
+    ``x3`` (opt-in): both products as split-bf16 products (``dv_gemm_x3``, two launches -- what a chip-filling pair is
+    anyway); raises where that entry point does not take one of the two descriptors.
+    ``klq`` = dict(out, q, eps, coef, raw, kl_min, Z): the layer's input was [a sample z of the q rows | ...]: instead of
+    dx the launch writes d/d(mu | logvar) of those rows incl. their prior term into ``out`` (M, 2Z) -- the epilogue
+    DV_EPI_KLQ of include/drvae_hip.h; ``dx`` is not written (pass None)"""
+    d1, d2 = _pair_descs(dW, dbias, dx, dpre, x, W, **kw)
+    if x3:
+        return _launch_x3([d1, d2], 'linear_bwd_pair')
     _lib.check(_lib.load().dv_gemm_pair(C.byref(d1), C.byref(d2), _stream()), 'dv_gemm_pair')
+
+
+def x3_pair_refusal(dW, dbias, dx, dpre, x, W, **kw):
+    """plan-time question, as ``x3_refusal``: would ``linear_bwd_pair(..., x3=True)`` with these operands run?"""
+    d1, d2 = _pair_descs(dW, dbias, dx, dpre, x, W, _any_device=True, **kw)
+    return _x3_refusal(d1) or _x3_refusal(d2)
 
 
 def linear_fwd(out, x, W, bias=None, *, x2=None, scale=None, split=None, act0=0, act1=0, shift0=0.0, shift1=0.0,

@@ -179,6 +179,11 @@ class _Plan:
         if cfg.type_rec == 'diag_gaussian' and X % 4 == 0 and Md > 0 and (T.get('nll_cs') == 2 or not eng._heads_small(self.DPX)):
             chunks, rbs = K.nll_raw_cs_shape(Md, X)
             self.NLLC, self.NLLWS = zf(Md, chunks), zf(rbs, 2 * X)
+        # opt-in split-bf16 products (``StepConfig.matmul``): exactly one layer changes arithmetic -- the decoder's heads
+        # layer where it takes the raw-heads route -- and whether it does is decided HERE, once (raises if its products are
+        # not ones ``dv_gemm_x3`` runs); every other product of the step stays fp32
+        if cfg.matmul == 'bf16x3' and Md > 0 and eng._raw_heads_ok(self.c_decx, self.DPX):
+            self.c_decx.use_x3_last(self.DPX, db_in_pass=self.NLLC is not None)
         if cfg.has_pert:
             self.c_z2F = _Chain(eng.L_z2F, L * B, dev, resid_cols=Z1)
             self.Z2F, self.D, self.DZ2F = mat(L * B, Z1), mat(L * B, Z1), mat(L * B, Z1)

@@ -220,6 +220,24 @@ int dv_gemm(const dv_gemm_desc* desc, dv_stream_t stream);
  * only need dy; otherwise exactly dv_gemm(d1) followed by dv_gemm(d2).  At most ONE of the two descriptors may
  * carry a publish (pub_flag): the launch publishes once, on entry (DV_ERR_ARG when both do). */
 int dv_gemm_pair(const dv_gemm_desc* d1, const dv_gemm_desc* d2, dv_stream_t stream);
+/* OPT-IN split-bf16 product ("dtype: bf16x3"; drvae_amd/csrc/gemm_x3.hip): the same descriptor, C = epilogue(alpha * Aop Bop)
+ * + beta * C, on the bf16 matrix pipe.  Every fp32 operand element a is split as hi = bf16_rn(a), mid = bf16_rn(a - hi),
+ * lo = bf16_rn(a - hi - mid); a product a * b is the sum of the six terms hi hi, hi mid, mid hi, hi lo, lo hi, mid mid
+ * (exact in fp32 each); accumulation is fp32, no atomics, a fixed order of summation: bitwise reproducible.  Part of that
+ * order: every output element has two fp32 accumulators -- the hi hi terms in one, the five correction terms in the other,
+ * k ascending in both -- which are added once, in front of the epilogue.  A non-finite
+ * operand element makes every output element it feeds non-finite (an inf may come out as NaN).  Nothing routes here on
+ * its own: dv_gemm and every other entry point stay fp32 MFMA.
+ * Runs: the three Linear layouts, alpha / beta, DV_EPI_PLAIN and DV_EPI_BWD, a_colsum on the dy^T x layout (a dv_colsum
+ * launch in front), any M and N, K % 4 == 0, 16-B aligned operand rows (A, B and lda, ldb multiples of 4 floats); it then
+ * never reads past the end of a row, whatever `flags` allows, and ignores `tune`.  K % 4 != 0 runs only where `flags` lets
+ * every k-contiguous operand's row ends be over-read (bit 0 for A, bit 1 for B): the 16-B chunk that straddles K is
+ * loaded whole and its elements past K count as zeros.  Everything else -- A2, a_kscale, DV_EPI_FWD, DV_EPI_KLQ, pub_flag,
+ * misaligned rows, K % 4 != 0 without that word -- returns DV_ERR_UNSUPPORTED and touches nothing; a NULL descriptor,
+ * M < 0, N < 0, K < 1, or a NULL A, B, C (yref with DV_EPI_BWD) of a non-empty product returns DV_ERR_ARG.  One launch of
+ * 128 x 128 output tiles (K tile 32, 48 KiB of LDS: three bf16 planes per operand, two workgroups per CU).  dv_gemm_x3_ok: a pure function, 1 where dv_gemm_x3 would run the descriptor, 0 otherwise. */
+int dv_gemm_x3(const dv_gemm_desc* desc, dv_stream_t stream);
+int dv_gemm_x3_ok(const dv_gemm_desc* desc);
 /* Dual-head Linear with the ROW work that consumes both heads fused into the epilogue (SURVEY.md K2+K3 /
  * K2+K5): y = x W^T with W = [W_head0 ; W_head1] (desc->split = rows of head 0, desc->N = 2*split), forward
  * layout (a_kcontig = b_kcontig = 1), epilogue DV_EPI_FWD exactly as dv_gemm (scale / bias / act0,shift0 |
