@@ -58,9 +58,8 @@ class _Chain:
     def __init__(self, layers, M, device, resid_cols=0):
         self.layers, self.M, self.resid_cols = layers, M, resid_cols
         # opt-in (``use_x3_last``, decided where the plan is built): the LAST layer's plain product (``raw_last``) and the two
-        # gradient products behind it run as split-bf16 products
+        # gradient products behind it MAY run as split-bf16 products; a pass says whether they do (``forward(x3=...)``)
         self.x3_last = False
-        self._x3_fwd = False        # did the latest forward pass take them?
         self.out = [torch.zeros(M, _pad4(l.N), device=device)[:, :l.N] for l in layers]
         # gradient w.r.t. the pre-activation of every layer but the last (the caller owns that one)
         self.dpre = [torch.zeros(M, _pad4(l.N), device=device)[:, :l.N] for l in layers[:-1]]
@@ -80,6 +79,10 @@ class _Chain:
         """may the last layer run as a plain product (no bias, no activation), finished by its consumer?"""
         l = self.layers[-1]
         return l.g is None and l.split * 2 == l.N and l.act0 == 'identity' and self.resid_cols == 0
+
+    def raw_softplus_ok(self):
+        """... by a row pass that adds the bias and applies the second head's softplus + shift (NLL rows, recon statistics)?"""
+        return bool(self.raw_last_ok() and self.layers[-1].act1 == 'softplus')
 
     # the last layer's raw product and its gradient pair, as launched AND as asked about at plan time (``use_x3_last``)
     def _raw_last_call(self, x, publish=None):
@@ -114,15 +117,16 @@ class _Chain:
                              % (l.N, l.Kin, self.M, why))
         self.x3_last = True
 
-    def forward(self, inputs, resid=None, publish=None, heads=None, raw_last=False):
+    def forward(self, inputs, resid=None, publish=None, heads=None, raw_last=False, x3=False):
         """``publish`` = (flag, counter, add): the FIRST launch of the chain publishes on entry.
         ``raw_last``: the last layer's launch is the plain product x W^T -- bias, the second head's activation and its
-        shift are left to the consumer (``K.nll_rows_fwdbwd(bias=...)``: chip-filling heads, plain GEMM epilogue).
+        shift are left to the consumer (``K.nll_rows_fwdbwd(bias=...)``: chip-filling heads, plain GEMM epilogue);
+        ``x3``: ... as a split-bf16 product (a chain that ``use_x3_last`` has accepted; ``backward(x3_last=True)`` goes with it).
         ``heads`` = dict(sample=...) | dict(nll=..., out=...): the dual-head last layer runs as ``K.linear_heads``
         with that row work fused into its epilogue (with ``nll`` the heads themselves are NOT stored: ``out``
         receives their gradients)."""
         x = list(inputs)
-        self._x3_fwd = bool(raw_last and self.x3_last and heads is None)
+        assert not x3 or (self.x3_last and raw_last and heads is None), 'x3: a raw last layer that use_x3_last accepted'
         for li, l in enumerate(self.layers):
             if l.g is not None:
                 K.wn_scale(l.scale, l.norm, l.W, l.g)
@@ -139,7 +143,7 @@ class _Chain:
                 return self.out[-1]
             if last and raw_last:
                 assert self.raw_last_ok() and resid is None
-                if self._x3_fwd:
+                if x3:
                     a, kw = self._raw_last_call(x[0], publish if li == 0 else None)
                     K.gemm(*a, x3=True, **kw)
                 else:
@@ -154,7 +158,7 @@ class _Chain:
         return self.out[-1]
 
     def backward(self, dpre_last, inputs, dinputs=None, publish_after_last=None, publish_first=None, db_last_done=False,
-                 klq=None):
+                 klq=None, x3_last=False):
         """dpre_last: gradient w.r.t. the last layer's pre-activation.  ``dinputs``: per input
         source a list of (dst, alpha, beta) destinations for its gradient (or None to skip).
         ``publish_after_last`` = (flag, counter, add):
@@ -162,9 +166,11 @@ class _Chain:
         last layer are final and its weights are no longer read); ``publish_first``: the chain's FIRST launch
         does (= everything in front of this backward pass is complete).  ``db_last_done``: the
         last layer's bias gradient has been written by the producer of ``dpre_last`` already (``kernels.nll_rows_raw_cs``).
+        ``x3_last``: the last layer's forward ran as a split-bf16 product (``forward(x3=True)``): so do its two gradient products.
         ``klq`` (see ``kernels.linear_bwd_pair``): the chain's input is a sample of q rows -- the FIRST layer's data-gradient
         launch writes d/d(mu | logvar) of those rows instead of d/d(input); returns True when the launch took it (a paired
         first layer), else the caller runs the row pass itself."""
+        assert not x3_last or self.x3_last
         dpre = dpre_last
         pending_pub = publish_first
         took_klq = False
@@ -183,9 +189,8 @@ class _Chain:
             if l.g is None and len(srcs) == 1 and single_dst:
                 if li > 0:
                     prev = self.layers[li - 1]
-                    # (the layer whose forward ran as a split-bf16 product: so do its two gradient products)
                     a, kw = self._bwd_pair_call(li, db, dpre, srcs[0], pending_pub)
-                    K.linear_bwd_pair(*a, **kw, **(dict(x3=True) if (self._x3_fwd and li == n_layers - 1) else {}))
+                    K.linear_bwd_pair(*a, **kw, **(dict(x3=True) if (x3_last and li == n_layers - 1) else {}))
                     dpre = self.dpre[li - 1]
                 else:
                     dst, alpha, beta = dinputs[0][0]

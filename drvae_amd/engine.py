@@ -33,7 +33,7 @@ from ._lib import GAUSS_LOGVAR, GAUSS_SIGMA
 from .arena import N_LOSS, ParamArena, span
 from .chain import _Chain, _Lin, _pad4
 from .plan import LOSS_IDX, _Plan
-from .schedule import DUAL, EVAL, FORK_JOIN, StepSchedule, StepSync, _Branch
+from .schedule import DUAL, EVAL, EVALUATE, FORK_JOIN, LOSS, TRAIN, StepSchedule, StepSync, _Branch, heads_route
 
 
 MATMUL_CHOICES = ('fp32', 'bf16x3')
@@ -221,7 +221,7 @@ class FusedStep(StepSchedule):
         # 0.42 ms -- the executor starts it late.)
         self.sched = T.get('sched')
         # the row work that consumes both heads of a block (the reparameterised samples; forward AND backward of
-        # the reconstruction log-likelihood) leaves the heads' own GEMM launch (dv_gemm_heads)
+        # the reconstruction log-likelihood) leaves the heads' own GEMM launch (dv_gemm_heads): where, ``heads_route`` says
         self.fuse_heads = bool(T.get('fuse_heads'))
         self._init_schedule_state()
         self.side_ctr = torch.zeros(1, dtype=torch.int32, device=self.dev)   # the side chain's own step count
@@ -482,16 +482,8 @@ class FusedStep(StepSchedule):
             self._rng_pending = n
 
     # ---------------------------------------------------------------------- forward
-    @staticmethod
-    def _heads_small(dpx):
-        """the paired-heads launch (32 x (32+32) tiles) is for the latency-bound sizes; once the decoder heads
-        alone fill the chip with 128x128 tiles many times over (wide configuration) the plain GEMM + row pass wins"""
-        return ((dpx.shape[0] + 127) // 128) * ((dpx.shape[1] + 127) // 128) < 1024
-
-    def _raw_heads_ok(self, c_decx, dpx):
-        """the raw-heads route: may the decoder's heads layer run as a plain product, finished by the NLL row pass?"""
-        return bool(self.cfg.type_rec == 'diag_gaussian' and c_decx.raw_last_ok() and c_decx.layers[-1].act1 == 'softplus'
-                    and (not self._heads_small(dpx) or T.get('raw_heads') == 2))     # (2: any size -- tests)
+    def _route(self):      # how the pass being issued runs its heads and its reconstruction rows
+        return heads_route(self, self.plan, TRAIN if self.fuse_bwd else LOSS if self.training else EVALUATE)
 
     def beta_pert(self):
         cfg = self.cfg
@@ -510,18 +502,18 @@ class FusedStep(StepSchedule):
             self.join_side()        # an evaluation forward reads parameters the side chain's tail may still be updating
         p.set_beta(self.beta_pert())
         B, Np, L, Z1 = p.B, p.Np, cfg.L, cfg.dim_z1
-        rec = self._rec
+        rec, r = self._rec, self._route()
         Z1blk = p.ZDEC[:L * B]
         if rec == 'side':           # side-chain graph: the main graph launches these; only the views are needed
             Q = p.c_enc.out[-1]
             Qmu, Qlv = Q[:, :Z1], Q[:, Z1:]
         else:
-            Qmu, Qlv = self._encoder_forward(rec)
+            Qmu, Qlv = self._encoder_forward(rec, r)
         if p.DZMMD is not None and rec != 'side':
             self._mmd_penalty()
         # ---- two independent chains from here: the classifier / fprop chain (many small launches)
         # runs on a side stream next to the decoder chain (the big GEMMs)
-        mode = self._mode()
+        mode, pub = self._mode(), None
         if mode == DUAL:
             two = cfg.has_pert                      # the decoder's first launch publishes its input final: z2Fz1 samples, else z1
             if rec == 'side' and not cfg.has_y:
@@ -533,18 +525,16 @@ class FusedStep(StepSchedule):
                 # workgroups for ~45 us slowed the main chain by 14 % (0.204 -> 0.233 ms).  The second wait has
                 # nothing left to wait for when the side chain reaches it: it rides on the KL row kernel behind it
                 K.flag_wait(*w0)
-                self._side_forward(Qmu, Qlv, Z1blk, (lambda: K.flag_wait(*w2)) if two else None,
+                self._side_forward(Qmu, Qlv, Z1blk, r, (lambda: K.flag_wait(*w2)) if two else None,
                                    mid_park=w2 if (two and not cfg.cont) else None)
                 return
             pub = self.sync.pub('z2f' if two else 'z1', self.step_dev)
             if self.L_decx[0].g is not None:             # WeightNorm: the chain's first launch is not the GEMM
                 K.flag_publish(*pub)
                 pub = None
-        else:
-            if not self._late_fork:
-                self.branch.fork()
-            pub = None
-        self._decoder_forward(pub)
+        elif not self._tail.late_fork:      # (a chip-filling step forks behind the decoder heads' product: ``_decoder_forward``)
+            self.branch.fork()
+        self._decoder_forward(r, pub)
         if mode == DUAL:
             klz2 = (self._tail.klz2_on_main or not cfg.has_y) and cfg.has_pert and Np
             P2 = p.c_z2F.out[-1] if klz2 else None
@@ -561,7 +551,7 @@ class FusedStep(StepSchedule):
                 K.kl_rows_fwd(*z2[0], **z2[1])
             return             # main-chain graph: the side chain lives in its own graph on the side stream
         with self.branch:
-            self._side_forward(Qmu, Qlv, Z1blk)
+            self._side_forward(Qmu, Qlv, Z1blk, r)
         if mode == FORK_JOIN:
             return             # train step, single fork/join: the side chain runs on into its backward
         self.branch.join()
@@ -569,7 +559,7 @@ class FusedStep(StepSchedule):
             return             # the loss scalars are assembled on the side chain of backward()
         self._loss_scalars()
 
-    def _encoder_forward(self, rec):
+    def _encoder_forward(self, rec, r):
         """inputs (explicit batch or the graph-resident feed, + the per-batch masks of a universal plan), q(z1|x1) / q(z2|x2) with
         their samples, the perturbation function q(z2Fz1|z1) with its samples; returns the heads' (mu, logvar) views"""
         cfg, p = self.cfg, self.plan
@@ -628,14 +618,13 @@ class FusedStep(StepSchedule):
         # ---- q(z1|x1), q(z2|x2): one pass of the shared encoder; the samples (src/blocks.py:170-174) -- z1
         # for every row and z2 for the pairs, drawn from q(z1|x1), not q(z2|x2) (quirk 1, src/DrVAE.py:427) --
         # leave the heads' launch itself (``fuse_heads``) or one launch of their own
-        fuse = self.fuse_heads and self._heads_small(p.DPX)
-        if fuse:
+        if r.sample_epi:
             # (... and every z1 sample is copied into the z1 columns of its fprop rows on the way out: the side
-            # chain's gather is gone)
-            fp4 = self._fprop_from_heads()
+            # chain's gather is gone; the class columns are written when the labels are: ``_Plan._refresh_onehot`` /
+            # ``dv_batch_feed``)
             Q = p.c_enc.forward(p.enc_in, heads=dict(sample=dict(
                 eps=p.E12, out=p.ZDEC[:p.o3], n_src=B, seg_ptr=p.zseg_ptr, seg_rows=p.zseg_rows,
-                out4=p.FPIN[:, :Z1] if fp4 else None, out4_ptr=p.fp_ptr_ext if fp4 else None)))
+                out4=p.FPIN[:, :Z1] if r.fprop_from_heads else None, out4_ptr=p.fp_ptr_ext if r.fprop_from_heads else None)))
             Qmu, Qlv = Q[:, :Z1], Q[:, Z1:]
         else:
             Q = p.c_enc.forward(p.enc_in)
@@ -645,7 +634,7 @@ class FusedStep(StepSchedule):
             # (dual-graph schedule) entry of this launch = the z1 samples are final: lets the side
             # chain's fprop start before the perturbation function has run
             pub1 = self.sync.pub('z1', self.step_dev) if rec == 'main' else None
-            if fuse:
+            if r.sample_epi:
                 # z2Fz1 sample, the classifier input z2Fz1 - z1, and the decoder's copy for the pairs
                 p.c_z2F.forward([Z1blk], resid=Z1blk, publish=pub1, heads=dict(sample=dict(
                     eps=p.E2F, out=p.Z2F, n_src=L * B, sub=Z1blk, out2=p.D, out3=p.ZDEC if Np else None,
@@ -656,62 +645,43 @@ class FusedStep(StepSchedule):
                               out3=p.ZDEC if Np else None, out3_idx=p.pert_out_idx if Np else None)
         return Qmu, Qlv
 
-    def _decoder_forward(self, pub=None):
-        """p(x|z): the decoder over all stacked sample rows, then the NLL over genes -- in a train step inside the heads'
-        launch, together with its gradient (``dv_gemm_heads``, NLL epilogue); ``pub``: flag published on entry of the first launch"""
+    def _decoder_forward(self, r, pub=None):
+        """p(x|z): the decoder over all stacked sample rows, then the NLL over genes by the launch ``r.nll`` names (``heads_route``:
+        in a latency-bound train step the heads' launch itself, ``dv_gemm_heads``); ``pub``: published on entry of the first launch"""
         cfg, p = self.cfg, self.plan
-        # ---- p(x|z): decoder over all stacked samples, then the NLL over genes
-        X = cfg.dim_x
-        gauss = cfg.type_rec == 'diag_gaussian'
-        self._nll_fused = bool(gauss and self.fuse_bwd and self.fuse_heads and self._heads_small(p.DPX))
-        self._nll_cs = False
-        if self._nll_fused:    # train step: the heads' launch emits d/d(mu, pre-softplus) and the row sums' partials
+        X, train = cfg.dim_x, self.fuse_bwd
+        if r.nll == 'heads':   # train step: the heads' launch emits d/d(mu, pre-softplus) and the row sums' partials
             p.c_decx.forward(p.dec_in, publish=pub, heads=dict(out=p.DPX, nll=dict(
                 x=p.XIN, xidx=p.tgt, coef=p.c_nll, part=p.NLLP)))
-            PX = None
-        else:
-            # chip-filling heads in a train step: the product runs with the plain epilogue, the NLL row pass behind it
-            # adds the bias and applies softplus + shift on its way (wide configuration: 10.87 -> 9.97 ms for the launch)
-            raw_ok = self._raw_heads_ok(p.c_decx, p.DPX)
-            raw = raw_ok and self.fuse_bwd
-            # an EVALUATION pass over many rows (whole-set evaluation, round 5): the heads are needed for the row terms only
-            # -- plain product, finished inside the row pass (32768 x 1956 x 600: 737 -> 589 us for the product, and no
-            # 256 MB of finished heads written and read back)
-            raw_eval = raw_ok and not self.fuse_bwd and not self.training
-            PX = p.c_decx.forward(p.dec_in, publish=pub, raw_last=raw or raw_eval)
-            if self._late_fork:       # (chip-filling step: the side chain starts HERE, next to the row pass below)
-                self.branch.fork()
-        if self._nll_fused:
-            raw_eval = False
-        elif not gauss:        # Bernoulli / Poisson rows (+ the gradient w.r.t. the head's pre-activation in a train step)
+            return
+        # ``raw_last``, chip-filling heads in a train step: the product runs with the plain epilogue, the NLL row pass behind it
+        # adds the bias and applies softplus + shift on its way (wide configuration: 10.87 -> 9.97 ms for the launch)
+        # ... and an EVALUATION pass over many rows (whole-set evaluation, round 5): the heads are needed for the row terms only
+        # -- plain product, finished inside the row pass (32768 x 1956 x 600: 737 -> 589 us for the product, and no
+        # 256 MB of finished heads written and read back)
+        PX = p.c_decx.forward(p.dec_in, publish=pub, raw_last=r.raw_last, x3=r.x3)
+        if self._tail.late_fork:      # (chip-filling step: the side chain starts HERE, next to the row pass below)
+            self.branch.fork()
+        lh = p.c_decx.layers[-1]
+        if r.nll == 'rec':     # Bernoulli / Poisson rows (+ the gradient w.r.t. the head's pre-activation in a train step)
             K.rec_nll_rows(p.NLL, p.XIN, PX, kind=cfg.type_rec, shift=REC_ACT[cfg.type_rec][1], xidx=p.tgt,
-                           coef=p.c_nll if self.fuse_bwd else None, dpre=p.DPX if self.fuse_bwd else None)
-        elif raw_eval and p.NLLC is not None:
-            # evaluation: the row terms from the raw heads (bias + softplus + shift applied by the pass; no gradients)
-            lh = p.c_decx.layers[-1]
-            K.nll_rows_raw_cs(p.NLLC, None, None, None, None, p.XIN, PX[:, :X], PX[:, X:], (lh.b[:X], lh.b[X:]), xidx=p.tgt,
-                              sd_shift=lh.shift1)
-            self._nll_cs = True
-        elif raw_eval:         # (gene counts that are no multiple of 4 -- 978: the wave-per-row pass)
-            lh = p.c_decx.layers[-1]
-            K.nll_rows_fwd(p.NLL, p.XIN, PX[:, :X], PX[:, X:], mode=GAUSS_SIGMA, xidx=p.tgt, bias=(lh.b[:X], lh.b[X:]),
-                           sd_shift=lh.shift1)
-        elif self.fuse_bwd and raw and p.NLLC is not None:
-            # ... and the heads' bias gradient with it (column sums of the gradients this pass writes: no second pass over them)
-            lh = p.c_decx.layers[-1]
-            K.nll_rows_raw_cs(p.NLLC, p.DPX[:, :X], p.DPX[:, X:], p.NLLWS, p.c_nll, p.XIN, PX[:, :X], PX[:, X:],
-                              (lh.b[:X], lh.b[X:]), xidx=p.tgt, sd_shift=lh.shift1)
-            K.colsum(lh.db, p.NLLWS)
-            self._nll_cs = True
-        elif self.fuse_bwd:    # train step: d/d(mu, pre-softplus) emitted in the same row pass
-            lh = p.c_decx.layers[-1]
+                           coef=p.c_nll if train else None, dpre=p.DPX if train else None)
+        elif r.nll in ('raw_cs', 'raw_cs_eval'):
+            # the row terms from the raw heads (bias + softplus + shift applied by the pass); train step: and the gradients,
+            # the heads' bias gradient with them (column sums of the gradients this pass writes: no second pass over them)
+            grads = (p.DPX[:, :X], p.DPX[:, X:], p.NLLWS, p.c_nll) if train else (None,) * 4
+            K.nll_rows_raw_cs(p.NLLC, *grads, p.XIN, PX[:, :X], PX[:, X:], (lh.b[:X], lh.b[X:]), xidx=p.tgt, sd_shift=lh.shift1)
+            if train:
+                K.colsum(lh.db, p.NLLWS)
+        elif r.nll == 'fwdbwd':        # train step: d/d(mu, pre-softplus) emitted in the same row pass
             K.nll_rows_fwdbwd(p.NLL, p.DPX[:, :X], p.DPX[:, X:], p.c_nll, p.XIN, PX[:, :X], PX[:, X:], mode=GAUSS_SIGMA,
-                              xidx=p.tgt, sd_act='softplus', sd_shift=lh.shift1 if raw else 1e-3,
-                              bias=(lh.b[:X], lh.b[X:]) if raw else None)
-        else:
-            K.nll_rows_fwd(p.NLL, p.XIN, PX[:, :X], PX[:, X:], mode=GAUSS_SIGMA, xidx=p.tgt)
+                              xidx=p.tgt, sd_act='softplus', sd_shift=lh.shift1 if r.raw_last else 1e-3,
+                              bias=(lh.b[:X], lh.b[X:]) if r.raw_last else None)
+        else:                          # 'fwd' | 'raw_eval' (gene counts that are no multiple of 4 -- 978: the wave-per-row pass)
+            raw = dict(bias=(lh.b[:X], lh.b[X:]), sd_shift=lh.shift1) if r.raw_last else {}
+            K.nll_rows_fwd(p.NLL, p.XIN, PX[:, :X], PX[:, X:], mode=GAUSS_SIGMA, xidx=p.tgt, **raw)
 
-    def _side_forward(self, Qmu, Qlv, Z1blk, mid=None, mid_park=None):
+    def _side_forward(self, Qmu, Qlv, Z1blk, r, mid=None, mid_park=None):
         """fprop first: it only needs the z1 samples, so (dual-graph schedule) it can start before
         the perturbation function has run; ``mid`` then waits for the z2Fz1 samples.  ``mid_park``
         (dual-graph schedule): that wait rides on the launch that follows it where that is a row kernel
@@ -749,18 +719,18 @@ class FusedStep(StepSchedule):
         if cfg.has_y:
             if p.Mf:
                 Z3, Y = cfg.dim_z3, cfg.dim_y
-                if not self._fprop_from_heads():
+                if not r.fprop_from_heads:
                     K.rows_gather(p.FPIN, Z1blk, p.fp_src, onehot_cls=p.fp_cls, n_classes=Y)
                 # (evaluation passes over many fprop rows -- whole-set evaluation: 24576 -- take the plain product + row pass:
                 # the 32 x (16 + 16) paired-heads tiles are the latency-bound sizes' kernel; 3.33 -> 3.27 ms per pair)
-                if self.fuse_heads and (self.fuse_bwd or p.Mf < 8192):
+                if r.z3_in_heads:
                     # the z3 sample leaves the heads' launch of q(z3|z1,y); its KL term against N(0,I) (with its
                     # own free bits) is evaluated next to the z1 term below: one launch less
                     Q3 = p.c_top.forward([p.FPIN], heads=dict(sample=dict(eps=p.E3, out=p.Z3IN[:, :Z3], n_src=p.Mf)))
                     PZ1 = p.c_dz1.forward([p.Z3IN])
                     # KLFP = max(KL(q(z1|x)||p(z1|z3,y)), kl_min) + max(KL(q(z3|.)||N(0,I)), kl_min)  (src/DrVAE.py:347,358)
-                    # -- in the train step inside the classifier-head launch below (``_fprop_tail``)
-                    if not self._fprop_tail():
+                    # -- in the train step inside the classifier-head launch below (``fprop_tail``)
+                    if not r.fprop_tail:
                         K.kl_rows_fwd(p.KLFP, p.KL1raw, Qmu, Qlv, PZ1[:, :Z1], PZ1[:, Z1:], qidx=p.fp_q,
                                       free_bits=True, kl_min=cfg.kl_min, prior=(0.0, 0.0),
                                       second=(Q3[:, :Z3], Q3[:, Z3:], p.KL3raw))
@@ -799,7 +769,7 @@ class FusedStep(StepSchedule):
                 lc = self.L_clf[0]
                 # train step: the y-marginalisation (forward and backward) rides on the classifier's launch
                 fk = None
-                if self._fprop_tail():
+                if r.fprop_tail:
                     # the fprop rows' KL terms in front of the y-marginalisation and the backward of the z1 term
                     # (with the coefficients it has just produced) behind it: same launch
                     fk = dict(Q=p.c_enc.out[-1], qidx=p.fp_q, P=p.c_dz1.out[-1], Q3=p.c_top.out[-1], Z1=Z1,
@@ -808,13 +778,11 @@ class FusedStep(StepSchedule):
                              ymarg=ym if self.fuse_bwd else None, park=mid_park if clf_park else None, fprop_kl=fk)
             else:
                 K.softmax_clamp_fwd(p.QY, p.c_clf.forward(clf_in), sigmoid1=cfg.clf_1sig)
-            if self.fuse_bwd and self.clf_small:
-                pass
-            elif self.fuse_bwd:    # train step: CFP / DQY of the backward pass come out of the same launch
+            if not self.fuse_bwd:
+                K.ymarg_fwd(p.YLrow, p.KLDrow, p.QY, p.label_r, p.fp_ptr, p.KLFP, p.log_prior)
+            elif not self.clf_small:    # train step: CFP / DQY of the backward pass come out of the same launch (clf_small: ``ymarg`` above)
                 K.ymarg_fwdbwd(p.YLrow, p.KLDrow, p.CFP, p.DQY, p.QY, p.label_r, p.fp_ptr, p.KLFP, p.log_prior,
                                p.c_kld, p.c_yl)
-            else:
-                K.ymarg_fwd(p.YLrow, p.KLDrow, p.QY, p.label_r, p.fp_ptr, p.KLFP, p.log_prior)
 
     def join_side(self):
         """Order the CURRENT stream behind everything the side chain has been given so far.  After a ``replay()`` of the
@@ -851,18 +819,6 @@ class FusedStep(StepSchedule):
         self.side_ctr.copy_(self.step_dev)
         self.side_t.copy_(self.step_dev + 1)
         self.sync.flag('tail').copy_(self.step_dev)
-
-    def _fprop_from_heads(self):
-        """the encoder heads' sample epilogue also fills the z1 columns of the fprop input (the class columns are
-        written when the labels are: ``_Plan._refresh_onehot`` / ``dv_batch_feed``)"""
-        cfg, p = self.cfg, self.plan
-        return bool(self.fuse_heads and self._heads_small(p.DPX) and cfg.has_y and not cfg.cont and p.Mf)
-
-    def _fprop_tail(self):
-        """train step: the fprop rows' KL forward and the z1 term's backward ride on the classifier-head launch
-        (``dv_fprop_kl``)"""
-        cfg, p = self.cfg, self.plan
-        return bool(self.fuse_bwd and self.fuse_heads and self.clf_small and cfg.has_y and not cfg.cont and p.Mf)
 
     def _mmd_penalty(self):
         """Model-level MMD penalty of the ``use_s`` extension (src/DrVAE.py:394-398,537-540): minus the MMD between
@@ -956,7 +912,7 @@ class FusedStep(StepSchedule):
         chain assemble the scalars (they are a leaf of the step: only the host reads them)."""
         cfg, p = self.cfg, self.plan
         L = cfg.L
-        nll = p.NLLP if self._nll_fused else (p.NLLC if self._nll_cs else p.NLL)
+        nll = getattr(p, self._route().rows)     # the buffer this pass's row launch writes
         # (per-tile / per-chunk partials: a row's sum is its term)
         rl = nll.shape[1] if nll.dim() == 2 else 1
         if p.universal:      # normalisers and group masks are per-row weights written by dv_batch_masks
@@ -999,7 +955,7 @@ class FusedStep(StepSchedule):
         Z1blk, DZ1 = p.ZDEC[:L * B], p.DZDEC[:L * B]
         # ---- side chain: y-marginalisation, fprop, classifier -> DZ1B (its share of d/dz1), DZ2F
         # (dual-graph schedule: what the side chain carries behind the join is decided in ``_step_tail``)
-        mode, t = self._mode(), self._tail
+        mode, t, r = self._mode(), self._tail, self._route()
         late, leaf = t.late, []
 
         # ---- main chain: reconstruction terms, d/d(mu, pre-softplus) straight from the per-row
@@ -1012,7 +968,7 @@ class FusedStep(StepSchedule):
             K.nll_rows_bwd(p.DPX[:, :X], p.DPX[:, X:], p.c_nll, p.XIN, PX[:, :X], PX[:, X:], mode=GAUSS_SIGMA,
                            xidx=p.tgt, sd_act='softplus', sd_shift=1e-3)
         if mode == DUAL and self._rec == 'side':
-            self._side_backward(Qmu, Qlv, Z1blk, late, leaf)
+            self._side_backward(Qmu, Qlv, Z1blk, r, late, leaf)
             self._side_graph_tail(leaf)
             return
         if mode == EVAL:
@@ -1021,7 +977,7 @@ class FusedStep(StepSchedule):
             self.branch._forked = True       # one fork/join per step: the side chain simply continues
         p.c_decx.backward(p.DPX, p.dec_in, [[(p.DZDEC, 1.0, 0.0)]] + [None] * (len(p.dec_in) - 1),
                           publish_after_last=self.sync.pub('rows', self.step_dev) if t.side_loss else None,
-                          db_last_done=bool(self.fuse_bwd and self._nll_cs))
+                          db_last_done=r.db_done, x3_last=r.x3)
         if p.DZMMD is not None:
             # model-level MMD penalty (use_s extension): its gradient w.r.t. the z1 / z2 samples was computed in
             # forward() through the block-level MMD kernels (see ``_mmd_penalty``)
@@ -1030,7 +986,7 @@ class FusedStep(StepSchedule):
             self._after_decoder_bwd()        # decoder_x gradients are final: graph split point of the overlapped exchange
         if mode != DUAL:
             with self.branch:
-                self._side_backward(Qmu, Qlv, Z1blk, late, leaf)
+                self._side_backward(Qmu, Qlv, Z1blk, r, late, leaf)
             self.branch.join()
         park = bump = None
         if t.fold_join:
@@ -1044,19 +1000,6 @@ class FusedStep(StepSchedule):
             self._loss_scalars(after=self.sync.wait('join', self.step_dev), terms_elsewhere=t.side_loss)
         elif mode == FORK_JOIN:         # (the step / Philox counters ride on this launch: two launches less in front of the optimiser)
             self._loss_scalars(bump_counters=True)
-        if t.adam_gated:      # (the optimiser's gate waits with counter + 0: the step counter is advanced before it)
-            if cfg.has_y:
-                lc, g0 = self.L_clf[0], self.arena.grad.storage_offset()
-                lo = min(lc.dW.storage_offset(), lc.db.storage_offset()) - g0
-                hi = max(lc.dW.storage_offset() + span(lc.dW), lc.db.storage_offset() + lc.db.numel()) - g0
-            else:       # (no classifier, no leaf gradient in flight: the first workgroup's elements stand in for the slice --
-                lo, hi = 0, 4       # the gate is what orders the NEXT step behind the side chain's tail, see ``_step_tail``)
-            self._adam_gate = self.sync.gate('clf_dw' if t.tail_gated else 'tail', self.step_dev, lo, hi)
-            self._adam_n = t.hs if t.side_adam else None
-        if t.cap_fork:
-            # (the sweep's first workgroup also parks on the side chain's "tail through" flag: what orders the NEXT step --
-            # its first launch reads the noise the side chain has drawn -- behind it)
-            self._adam_gate = self.sync.gate('tail', self.step_dev, 0, 4)
         if cfg.has_pert:
             P2 = p.c_z2F.out[-1]
             # everything that hangs on the z2Fz1 samples, one launch: scatter-back of the decoded
@@ -1086,7 +1029,7 @@ class FusedStep(StepSchedule):
         p.c_enc.backward(DQ, p.enc_in, None,
                          publish_first=self.sync.pub('noise', self.step_dev, 0) if t.noise_ahead else None)
 
-    def _side_backward(self, Qmu, Qlv, Z1blk, late, leaf):
+    def _side_backward(self, Qmu, Qlv, Z1blk, r, late, leaf):
         """the side chain's share of the backward pass: y-marginalisation, fprop blocks, classifier -> ``DZ1B`` (its share
         of d/dz1) and ``DZ2F``.  ``late``: the classifier's weight gradient is deferred (appended to ``leaf``: a leaf of the step
         -- only the optimiser reads it -- that runs behind the side chain's publish)"""
@@ -1130,7 +1073,7 @@ class FusedStep(StepSchedule):
                 Z3 = cfg.dim_z3
                 PZ1, Q3 = p.c_dz1.out[-1], p.c_top.out[-1]
                 # KL(q(z1|x) || p(z1|z3,y)): gradient to p (decoder_z1 heads) and, row-aligned, to q
-                if not self._fprop_tail():       # (else: left the classifier-head launch of the forward pass)
+                if not r.fprop_tail:       # (else: left the classifier-head launch of the forward pass)
                     K.kl_rows_bwd(p.DQFP[:, :Z1], p.DQFP[:, Z1:], p.DPZ1[:, :Z1], p.DPZ1[:, Z1:], p.CFP, p.KL1raw,
                                   Qmu, Qlv, PZ1[:, :Z1], PZ1[:, Z1:], qidx=p.fp_q, free_bits=True,
                                   kl_min=cfg.kl_min)
@@ -1228,11 +1171,21 @@ class FusedStep(StepSchedule):
             K.counters_add2(self.side_ctr, 1, self.side_t, 1, publish=self.sync.pub('tail', self.side_ctr))
         step = K.adamax_l2 if cfg.optim_alg == 'adamax' else K.adam_l2    # exp_avg_sq doubles as Adamax's exp_inf
         n = a.n_live                      # parameters without gradients sit behind it (untouched, like torch)
-        if self._adam_n is not None:      # dual-graph step: the side chain sweeps the rest (the decoder heads)
-            n, self._adam_n = self._adam_n, None
-        kw = {}
-        if self._adam_gate is not None:   # dual-graph step: the classifier's dW may still be in flight on the side chain
-            kw['gate'], self._adam_gate = self._adam_gate, None
+        t, kw = (self._tail if self._rec == 'main' else None), {}
+        if t and t.adam_gated:   # dual-graph step: the classifier's dW may still be in flight on the side chain
+            # (the optimiser's gate waits with counter + 0: the step counter is advanced before it)
+            if cfg.has_y:
+                lc, g0 = self.L_clf[0], a.grad.storage_offset()
+                lo = min(lc.dW.storage_offset(), lc.db.storage_offset()) - g0
+                hi = max(lc.dW.storage_offset() + span(lc.dW), lc.db.storage_offset() + lc.db.numel()) - g0
+            else:       # (no classifier, no leaf gradient in flight: the first workgroup's elements stand in for the slice --
+                lo, hi = 0, 4       # the gate is what orders the NEXT step behind the side chain's tail, see ``_step_tail``)
+            kw['gate'] = self.sync.gate('clf_dw' if t.tail_gated else 'tail', self.step_dev, lo, hi)
+            n = t.hs if t.side_adam else n      # ... and the side chain sweeps the rest (the decoder heads)
+        if t and t.cap_fork:
+            # (the sweep's first workgroup also parks on the side chain's "tail through" flag: what orders the NEXT step --
+            # its first launch reads the noise the side chain has drawn -- behind it)
+            kw['gate'] = self.sync.gate('tail', self.step_dev, 0, 4)
         step(a.param[:n], a.grad[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.step_dev, lr=cfg.learning_rate,
              weight_decay=cfg.weight_decay, gscale=gscale, halt=self.sync_err, **kw)
 

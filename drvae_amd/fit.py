@@ -839,7 +839,7 @@ class _EvalGraph:
         # the decoder's heads as a PLAIN product where the one-pass reconstruction statistics finish them on their way
         # (bias, softplus + shift: ``dv_recon_rows`` / ``dv_col_moments``): 16384 x 1956 x 600 at the raw product's 126 instead of 104 TF/s
         lh = eng.L_decx[-1]
-        raw = bool(X <= K.RECON_ROWS_MAX_X and self.c_dec.raw_last_ok() and lh.act1 == 'softplus')
+        raw = bool(X <= K.RECON_ROWS_MAX_X and self.c_dec.raw_softplus_ok())
         PX = self.c_dec.forward([self.zd] + ([self.soh_d] if self.use_s else []), raw_last=raw)
         res['px_bias'] = (lh.b[:X], lh.b[X:2 * X], lh.shift1) if raw else None
         res['px1'] = (PX[:n, :X], PX[:n, X:2 * X])

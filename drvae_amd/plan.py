@@ -7,9 +7,9 @@ import numpy as np
 import torch
 
 from . import kernels as K
-from . import tuning as T
 from .arena import N_LOSS
 from .chain import _Chain, _pad4
+from .schedule import heads_static
 
 LOSS_IDX = {'RECL': 0, 'KLD': 1, 'PERT': 2, 'YL': 3, 'MMD': 4, 'ELBO': 5, 'CMPL': 6}
 
@@ -175,15 +175,17 @@ class _Plan:
         self.NLLP = zf(Md, K.heads_tiles(X))
         # chip-filling heads (wide configuration): the NLL row pass behind the plain product also emits the heads' bias
         # gradient -- per-chunk row partials and per-row-block column sums (``kernels.nll_rows_raw_cs``)
+        # (whether they exist, and whether the heads may run raw at all: the static part of ``schedule.heads_route``)
         self.NLLC = self.NLLWS = None
-        if cfg.type_rec == 'diag_gaussian' and X % 4 == 0 and Md > 0 and (T.get('nll_cs') == 2 or not eng._heads_small(self.DPX)):
+        _, raw_ok, nll_cs = heads_static(cfg, self.c_decx, self.DPX)
+        if nll_cs:
             chunks, rbs = K.nll_raw_cs_shape(Md, X)
             self.NLLC, self.NLLWS = zf(Md, chunks), zf(rbs, 2 * X)
         # opt-in split-bf16 products (``StepConfig.matmul``): exactly one layer changes arithmetic -- the decoder's heads
         # layer where it takes the raw-heads route -- and whether it does is decided HERE, once (raises if its products are
         # not ones ``dv_gemm_x3`` runs); every other product of the step stays fp32
-        if cfg.matmul == 'bf16x3' and Md > 0 and eng._raw_heads_ok(self.c_decx, self.DPX):
-            self.c_decx.use_x3_last(self.DPX, db_in_pass=self.NLLC is not None)
+        if cfg.matmul == 'bf16x3' and Md > 0 and raw_ok:
+            self.c_decx.use_x3_last(self.DPX, db_in_pass=nll_cs)
         if cfg.has_pert:
             self.c_z2F = _Chain(eng.L_z2F, L * B, dev, resid_cols=Z1)
             self.Z2F, self.D, self.DZ2F = mat(L * B, Z1), mat(L * B, Z1), mat(L * B, Z1)

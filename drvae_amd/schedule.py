@@ -115,8 +115,74 @@ class Tail(NamedTuple):
     noise_ahead: bool = False      # the side chain draws the NEXT step's noise
     klz2_on_main: bool = False     # the pairs' KL(q(z2|x2)||p(z2|z1)) rows run on the main chain
     fold_join: bool = False        # the join rides on its first consumer (``z2f_post_bwd`` parks)
+    late_fork: bool = False        # one-graph chip-filling step: the side chain forks behind the decoder heads' product
 
-_PINNED_POOL = []             # pinned int32 buffers of retired engines (see ``_poll_sync``)
+
+# the kinds of pass ``heads_route`` tells apart: forward with its backward fused behind it (``fuse_bwd``) | forward of a
+# training-mode loss whose backward is a call of its own | evaluation forward
+TRAIN, LOSS, EVALUATE = 'train pass', 'loss pass, separate backward', 'evaluation pass'
+# the launch that writes a pass's reconstruction rows (``HeadsRoute.nll``) -> the plan buffer that receives them; the
+# table in DESIGN.md section 6 says when each is taken
+NLL_ROUTES = {'heads': 'NLLP', 'rec': 'NLL', 'raw_cs_eval': 'NLLC', 'raw_eval': 'NLL', 'raw_cs': 'NLLC', 'fwdbwd': 'NLL',
+              'fwd': 'NLL'}
+
+
+class HeadsRoute(NamedTuple):
+    """how one pass runs its dual-head layers and its reconstruction rows (``heads_route``)"""
+    sample_epi: bool           # the samples of q(z1|x) and of the perturbation function leave their heads' launches
+    fprop_from_heads: bool     # ... and the encoder's epilogue also fills the z1 columns of the fprop input
+    z3_in_heads: bool          # the q(z3|z1,y) sample leaves its heads' launch
+    fprop_tail: bool           # the fprop rows' KL forward + the z1 term's backward ride on the classifier launch (``dv_fprop_kl``)
+    nll: str                   # a key of NLL_ROUTES: the launch that writes the reconstruction rows
+    rows: str                  # ... and the plan buffer that holds them: 'NLLP' | 'NLLC' | 'NLL'
+    raw_last: bool             # the decoder's heads run as a plain product, finished by that row pass (``_Chain.forward``)
+    x3: bool                   # ... as split-bf16 products, with the gradient pair behind them
+    db_done: bool              # the heads' bias gradient is written by the row pass (``colsum``), not by the dW launch
+
+
+def heads_static(cfg, c_decx, dpx):
+    """the part of ``heads_route`` a plan's buffers follow: (small, raw heads allowed, NLLC / NLLWS exist)"""
+    # small: the paired-heads launch (32 x (32+32) tiles) is for the latency-bound sizes; once the decoder heads alone fill
+    # the chip with 128x128 tiles many times over (wide configuration) the plain product + row pass wins.  The other two are
+    # predicates of their own (the buffers do not ask for a raw-capable layer, raw heads not for 4 | genes) that meet in the
+    # ``raw_cs`` routes
+    gauss = cfg.type_rec == 'diag_gaussian'
+    small = ((dpx.shape[0] + 127) // 128) * ((dpx.shape[1] + 127) // 128) < 1024
+    raw_ok = bool(gauss and c_decx.raw_softplus_ok() and (not small or T.get('raw_heads') == 2))     # (2: any size -- tests)
+    nll_cs = bool(gauss and cfg.dim_x % 4 == 0 and dpx.shape[0] > 0 and (T.get('nll_cs') == 2 or not small))
+    return small, raw_ok, nll_cs
+
+
+def heads_route(eng, plan, kind):
+    """THE decision of how a pass of ``kind`` (TRAIN | LOSS | EVALUATE) over ``plan`` runs its heads: a ``HeadsRoute``"""
+    # a function of the configuration, the plan and the tuning switches ``fuse_heads`` / ``raw_heads`` / ``nll_cs`` alone:
+    # every reader (forward, backward, the loss scalars, either chain of a recorded step) asks it and gets the same answer
+    cfg, p, train, gauss = eng.cfg, plan, kind == TRAIN, eng.cfg.type_rec == 'diag_gaussian'
+    small, raw_ok, nll_cs = heads_static(cfg, p.c_decx, p.DPX)
+    assert nll_cs == (p.NLLC is not None), 'the tuning switches changed since the plan was built'
+    epi = bool(eng.fuse_heads and small)
+    fprop = bool(cfg.has_y and not cfg.cont and p.Mf)
+    # (an EVALUATION pass takes the raw heads too -- whole-set evaluation: the heads are needed for the row terms only; a
+    # loss pass leaves finished heads for the backward call that follows it)
+    raw_last = bool(raw_ok and not (train and epi) and kind != LOSS)
+    if gauss and train and epi:      # train step: the heads' launch emits the rows' partials and d/d(mu, pre-softplus)
+        nll = 'heads'
+    elif not gauss:                  # Bernoulli / Poisson rows
+        nll = 'rec'
+    elif raw_last and nll_cs:        # the row pass finishes the heads (+ in a train step: their bias gradient's column sums)
+        nll = 'raw_cs' if train else 'raw_cs_eval'
+    elif raw_last:                   # (gene counts that are no multiple of 4 -- 978: the wave-per-row passes, with bias)
+        nll = 'fwdbwd' if train else 'raw_eval'
+    else:
+        nll = 'fwdbwd' if train else 'fwd'
+    # (``z3_in_heads``: evaluation passes over many fprop rows -- whole-set evaluation: 24576 -- take the plain product + row pass)
+    return HeadsRoute(sample_epi=epi, fprop_from_heads=bool(epi and fprop),
+                      z3_in_heads=bool(eng.fuse_heads and (train or p.Mf < 8192)),
+                      fprop_tail=bool(train and eng.fuse_heads and fprop and eng.clf_small), nll=nll, rows=NLL_ROUTES[nll],
+                      raw_last=raw_last, x3=bool(raw_last and p.c_decx.x3_last), db_done=nll == 'raw_cs')
+
+
+_PINNED_POOL = []           # pinned int32 buffers of retired engines (see ``_poll_sync``)
 _PARTITION_STREAMS = {}      # device index -> {reserved CUs -> (main stream, side stream) | None}
 
 
@@ -182,14 +248,12 @@ class StepSchedule:
         # the step being recorded
         self._rec = 'both'                # 'both' | the dual-graph schedule's 'main' / 'side' chain (``_recording``)
         self._tail = Tail()               # ... and what its side chain carries
-        self._late_fork = False           # chip-filling step: the side chain forks behind the decoder heads' product
         self._after_decoder_bwd = None    # graph split point of the overlapped exchange
-        self._nll_fused = False           # which buffer holds this pass's reconstruction rows: NLLP ...
-        self._nll_cs = False              # ... NLLC (else NLL)
+        # (the next two count device-side EVENTS across launches -- draws not yet added to the Philox counter, a counter
+        # bump that rode on an earlier launch of the step: state by nature, unlike what ``heads_route`` / ``_step_tail``
+        # answer; untangling them is a piece of work of its own)
         self._rng_pending = 0             # Philox draw events not yet added to the counter
         self._ctr_bumped = False          # the loss-scalar launch has advanced the step / Philox counters
-        self._adam_n = None               # the main chain's share of the optimiser sweep (dual-graph step)
-        self._adam_gate = None            # ... and the flag it gates the classifier's slice on
         # replays
         self._noise_stale = True          # the noise buffer does not hold the draws of the current Philox counter
         self._flag_side = None            # the stream the side graph is launched on (``flag_side``)
@@ -232,6 +296,7 @@ class StepSchedule:
         # a wait time-out.  ``on_gpu``: what the device contributes -- a side stream on a hardware queue of its own; None:
         # ask it (CPU tests of the recorded sequence pass True)
         cfg, p = self.cfg, self.plan
+        branch_on = self.branch.on if on_gpu is None else bool(self.concurrent and cfg.has_y and on_gpu)
         # two flag-ordered graphs only for the latency-bound steps: once the decoder products alone fill the chip many
         # times over (wide configuration) the side chain's small kernels, squeezed in between the resident GEMM
         # workgroups of a second queue, cost more than they hide (36.7 ms dual, 35.9 ms as one graph with a fork/join)
@@ -240,7 +305,13 @@ class StepSchedule:
         # 0.1848 -> 0.1913 split, 0.1695 -> 0.1737 captured)
         if not (self.sched == 5 and self._dual_capable(on_gpu) and self._latency_bound() and
                 (self._flags_usable() if on_gpu is None else on_gpu) and (cfg.has_y or not split_kind)):
-            return Tail()
+            # ONE graph.  A chip-filling step (wide configuration): its side chain is 0.5 ms of small launches next to 31 ms of
+            # products that want every CU.  Forked at the start of the step they squeeze in between the resident GEMM workgroups
+            # of the other queue and cost more than they hide (round 4: 32.0 ms with the fork/join, 31.5 ms in order on one
+            # stream); forked LATE -- behind the decoder heads' product, next to the HBM-bound NLL row pass, the one stretch of
+            # the main chain that leaves the matrix pipes idle -- and joined behind the decoder's backward products, they win
+            # (round 6, cfg 5: 31.09-31.15 -> 30.87-30.89 ms; the side chain's 0.4 ms are through long before the join)
+            return Tail(late_fork=bool(branch_on and not self._latency_bound()))
         # the side chain carries the step's leaf work (classifier dW, heads' optimiser half, loss scalars) behind the join
         late_ok = bool(not cfg.cont and cfg.optim_alg == 'adam' and (self.clf_small if cfg.has_y else True))
         # (dual-graph schedule) the classifier's weight gradient is a leaf -- only the optimiser reads it --
@@ -294,7 +365,7 @@ class StepSchedule:
 
     @contextlib.contextmanager
     def _recording(self, chain, tail):
-        """the passes issued inside are the ``chain`` ('main' | 'side') of the dual-graph step decided as ``tail``"""
+        """the passes issued inside are the ``chain`` ('main' | 'side' of a dual-graph step, 'both': one graph) of the ``tail`` step"""
         self._rec, self._tail = chain, tail
         try:
             yield
@@ -352,15 +423,8 @@ class StepSchedule:
         gc.collect()
         gc_was_on = gc.isenabled()
         gc.disable()
-        # a chip-filling step (wide configuration): its side chain is 0.5 ms of small launches next to 31 ms of products that
-        # want every CU.  Forked at the start of the step they squeeze in between the resident GEMM workgroups of the other
-        # queue and cost more than they hide (round 4: 32.0 ms with the fork/join, 31.5 ms in order on one stream); forked
-        # LATE -- behind the decoder heads' product, next to the HBM-bound NLL row pass, the one stretch of the main chain
-        # that leaves the matrix pipes idle -- and joined behind the decoder's backward products, they win (round 6, cfg 5:
-        # 31.09-31.15 -> 30.87-30.89 ms; the side chain's 0.4 ms are through long before the join)
-        self._late_fork = self.branch.on and not tail.dual and not self._latency_bound()
         try:
-            with self._recording('main', tail) if tail.dual else contextlib.nullcontext():
+            with self._recording('main' if tail.dual else 'both', tail):
                 self._capture_main(split_for_allreduce)
             if tail.dual:
                 self.sync_side_counters()
@@ -370,7 +434,6 @@ class StepSchedule:
                     self._launch_sequence(draw=False, optimizer=False)
                 self._side_graph = gs
         finally:
-            self._late_fork = False
             if gc_was_on:
                 gc.enable()
         self._graph_key = self.plan.key

@@ -10,13 +10,14 @@ DRVAE_DIST_BACKEND (torch.distributed backend of the data-parallel step; default
 DRVAE_FORCE_DP=1 (the multi-rank step path over a one-rank communicator: functional check on a one-GPU box)."""
 import os
 
+# (``fuse_heads`` / ``raw_heads`` / ``nll_cs``: read in ONE place, ``schedule.heads_route`` and its static part ``heads_static``)
 DEFAULTS = {
     'sched': 5,          # 5 two graphs ordered by device flags | 3 one graph, one fork/join per step (tools/pmc_collect.sh)
-    'fuse_heads': 1,     # samples / NLL forward+backward in the epilogue of the heads' GEMM (dv_gemm_heads)
-    'raw_heads': 1,      # chip-filling decoder heads (train step) as a plain product, finished by the NLL row pass (2: at any size -- tests)
+    'fuse_heads': 1,     # samples / NLL forward+backward in the epilogue of the heads' GEMM (dv_gemm_heads); -> schedule.heads_route
+    'raw_heads': 1,      # chip-filling decoder heads (train step) as a plain product, finished by the NLL row pass (2: at any size -- tests); -> schedule.heads_route
     'tail_gate': 1,      # the side chain's tail is awaited by the NEXT step's first launch where that is a graph-resident feed (2: any first launch -- tests)
     'concurrent': 1,     # side chain at all (0: one stream)
-    'nll_cs': 1,         # chip-filling heads: their bias gradient folded into the NLL row pass (no column-sum pass of its own; 2: buffers at any size -- tests, with raw_heads=2)
+    'nll_cs': 1,         # chip-filling heads: their bias gradient folded into the NLL row pass (no column-sum pass of its own; 2: buffers at any size -- tests, with raw_heads=2); -> schedule.heads_route
     'mmd_explicit': 1,   # model-level MMD penalty (use_s extension, rbf_fourier / identity kernels) as explicit launch lists, no autograd inside the step (0: the block-level operators -- tests)
     'dp_fork': 1,        # captured gradient exchange: the side chain draws the next step's noise behind the join (as in the single-GPU step)
 }

@@ -160,3 +160,40 @@ def test_launch_count_of_the_captured_step(dev, kind, most, monkeypatch):
     torch.cuda.synchronize()
     eng.check_sync()
     assert all(np.isfinite(v) for v in eng.losses().values())
+
+
+def _raw_route_case(which):
+    if which == 'raw_cs':        # 3 gene chunks (the last one ragged), 2 row blocks of the row pass (64 + ragged)
+        spec = C.tiny_spec('drvae', dim_x=2056, h_de_x=[8], dim_z1=6)
+        return spec, M.init_params(spec, 4, as_numpy=True), M.make_batch(spec, 70, seed=3)
+    case = C.model_case('tiny_drvae')        # 13 genes: no column-sum buffers, the wave-per-row pass adds the bias
+    return case['spec'], M.init_params(case['spec'], case['param_seed'], as_numpy=True), case['batch']
+
+
+@pytest.mark.parametrize('which', ['raw_cs', 'fwdbwd_bias'])
+def test_captured_dual_step_on_the_raw_routes_replays_like_the_eager_one(dev, which):
+    """the raw-heads routes (forced at a latency-bound size, so the step IS the dual-graph one): which rows buffer the side
+    chain's graph sums is decided per recording (``schedule.heads_route``), and the captured step computes, bit for bit, what
+    four eager steps from the same state compute"""
+    from tests.test_gpu_x3 import tuned
+    spec, params, batch = _raw_route_case(which)
+    with tuned('fuse_heads=0,raw_heads=2,nll_cs=2'):
+        eng, arena = make_engine(spec, params, dev)
+        set_batch(eng, batch, dev)
+        assert (eng.plan.NLLC is not None) == (which == 'raw_cs')
+        eng.train_step()
+        eng.capture()
+        for _ in range(3):
+            eng.replay()
+        eng.check_sync()
+        assert eng._side_graph is not None, 'not the dual-graph step'
+        losses = eng.losses()
+        eng2, arena2 = make_engine(spec, params, dev)
+        set_batch(eng2, batch, dev)
+        for _ in range(4):
+            eng2.train_step()
+        torch.cuda.synchronize()
+        print('captured', losses, 'eager', eng2.losses())
+        assert all(np.isfinite(v) for v in losses.values()) and bool(torch.isfinite(arena.param).all())
+        assert eng2.losses() == losses
+        assert torch.equal(arena2.param, arena.param)

@@ -28,6 +28,7 @@ class Recorder:
         self.chain = None
         self.offset = {}                 # counter name -> bumps so far in the chain being recorded
         self.waits, self.pubs, self.launches = [], [], []
+        self.loss_terms = []             # per ``loss_assemble`` launch: (chain, the plan attribute each term's first tensor is)
         for name in kernel_ref.FUNCTIONS:
             mp.setattr(K, name, functools.partial(self._launch, name, getattr(K, name)))
 
@@ -61,8 +62,16 @@ class Recorder:
         from drvae_amd.schedule import FLAGS
         self.pubs.append((self.chain, launcher, FLAGS[self._word(flag, self.eng.flags, 1)][0], self._value(ctr, add)))
 
+    def _plan_attr(self, t):
+        names = [k for k, v in vars(self.eng.plan).items() if torch.is_tensor(v) and v.numel()
+                 and v.untyped_storage().data_ptr() == t.untyped_storage().data_ptr()]
+        assert len(names) == 1, ('a loss term that is not one buffer of the plan', names)
+        return names[0]
+
     def _launch(self, name, fn, *a, **kw):
         self.launches.append((self.chain, name))
+        if name == 'loss_assemble':
+            self.loss_terms.append((self.chain, tuple(self._plan_attr(term[0]) for term in a[1])))
         bumps = list(kw.get('bump') or ())
         if name == 'flag_publish':
             self._publish(name, *a)
@@ -84,6 +93,22 @@ class Recorder:
         for ctr, inc in bumps:           # (the counters move at the END of a launch: behind its publish and its wait)
             self.offset[self._counter(ctr)] += inc
         return fn(*a, **kw)
+
+
+def record_side_alone(spec, params, batch, noise, universal, split, mp):
+    """the side chain of the dual-graph step recorded on a FRESH engine, nothing issued in front of it"""
+    import drvae_amd.kernels as K
+    eng, _ = make_engine(spec, params)
+    eng.universal = universal
+    set_batch(eng, batch)
+    eng.set_noise(noise)
+    tail = eng._step_tail(split, on_gpu=True)
+    assert tail.dual
+    rec = Recorder(eng, K, mp)
+    with eng._recording('side', tail):
+        rec.begin('side')
+        eng._launch_sequence(draw=False, optimizer=False)
+    return rec
 
 
 @functools.lru_cache(maxsize=None)
@@ -194,3 +219,62 @@ def test_flags_nobody_waits_for_are_the_ones_the_table_declares():
                 assert {'z1', 'z2f'} <= idle, (key, idle)
             seen |= idle
     assert seen == declared
+
+
+def _side(rec):
+    return [n for c, n in rec.launches if c == 'side'], [t for c, t in rec.loss_terms if c == 'side']
+
+
+def test_the_side_chain_s_recording_does_not_depend_on_what_ran_before_it(monkeypatch):
+    """which buffer the side chain's ``loss_assemble`` sums is decided by ``heads_route`` from the plan and the kind of pass,
+    not left behind by the pass issued before it: recorded alone on a fresh engine the side chain is the one recorded behind
+    the main chain -- same launchers, same buffers summed"""
+    import drvae_amd.tuning as T
+    steps = recorded_steps(False)
+    kernel_ref.install(monkeypatch)
+    monkeypatch.setattr(T, '_VALUES', None)
+    assert steps
+    for (name, universal, split), rec in steps.items():
+        case = C.model_case(name)
+        with pytest.MonkeyPatch.context() as inner:
+            alone = record_side_alone(case['spec'], M.init_params(case['spec'], case['param_seed'], as_numpy=True),
+                                      case['batch'], case['noises'][0], universal, split, inner)
+        assert _side(alone) == _side(rec), (name, universal, split)
+        assert alone.launches == [l for l in rec.launches if l[0] == 'side']
+
+
+@pytest.mark.parametrize('kind', ['drvae', 'vfae'])
+def test_the_side_chain_sums_the_raw_row_pass_s_partials_whatever_ran_before_it(kind, monkeypatch):
+    """the same on the raw-heads route with the bias gradient in the row pass (the chip-filling step's, forced at a small
+    size): main-then-side and side alone both sum ``NLLC``"""
+    import drvae_amd.kernels as K
+    import drvae_amd.tuning as T
+    monkeypatch.setenv('DRVAE_TUNE', 'fuse_heads=0,raw_heads=2,nll_cs=2')
+    monkeypatch.setattr(T, '_VALUES', None)
+    kernel_ref.install(monkeypatch)
+    spec = C.tiny_spec(kind, dim_x=16, h_de_x=[8])
+    params, batch, noise = M.init_params(spec, 4, as_numpy=True), M.make_batch(spec, 12, seed=3), M.make_noise(spec, 12, seed=5)
+    seen = []
+    for split in SPLITS:
+        eng, _ = make_engine(spec, params)
+        set_batch(eng, batch)
+        eng.set_noise(noise)
+        tail = eng._step_tail(split, on_gpu=True)
+        assert tail.dual
+        with pytest.MonkeyPatch.context() as inner:
+            rec = Recorder(eng, K, inner)
+            with eng._recording('main', tail):
+                rec.begin('main')
+                eng._launch_sequence(allreduce=(lambda buf: None) if split == 'captured' else None)
+            with eng._recording('side', tail):
+                rec.begin('side')
+                eng._launch_sequence(draw=False, optimizer=False)
+        with pytest.MonkeyPatch.context() as inner:
+            alone = record_side_alone(spec, params, batch, noise, False, split, inner)
+        assert ('main', 'nll_rows_raw_cs') in rec.launches, split
+        assert _side(alone) == _side(rec), split
+        for chain, terms in rec.loss_terms + alone.loss_terms:
+            if terms:       # (``terms_elsewhere``: the main chain's launch only parks and bumps)
+                assert terms[0] == 'NLLC', (split, chain, terms)
+                seen.append(chain)
+    assert 'side' in seen and 'main' in seen
