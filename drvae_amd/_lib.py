@@ -145,6 +145,8 @@ SIGNATURES = {
     'dv_gemm_pair': [C.POINTER(GemmDesc), C.POINTER(GemmDesc), _p],
     'dv_gemm_x3': [C.POINTER(GemmDesc), _p],
     'dv_gemm_x3_ok': [C.POINTER(GemmDesc)],
+    'dv_gemm_split': [C.POINTER(GemmDesc), _i32, _p],
+    'dv_gemm_split_ok': [C.POINTER(GemmDesc), _i32],
     'dv_gemm_heads': [C.POINTER(GemmDesc), C.POINTER(HeadsEpi), _p],
     'dv_gemm_heads_tiles': [_i32],
     'dv_bn_fwd': [_p, _i64, _i32, _i32, _p, _p, _f, _p, _p, _p, _i64, _p, _p, _f, _i32, _p],

@@ -23,7 +23,8 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         src/DrVAE.py:71-74) and set the hyper-parameters it hard-codes (src/DrVAE.py:79-97)."""
         device = args.pop('device', None)
         weight_norm = args.pop('weight_norm', False)
-        # 'fp32' | 'bf16x3' (opt-in): the arithmetic of the chip-filling decoder-heads products, see ``StepConfig.matmul``
+        # 'fp32' | 'bf16x3' | 'bf16x2' | 'bf16x1' (opt-in): the arithmetic of the chip-filling decoder-heads products, see
+        # ``StepConfig.matmul`` ('bf16x1' is a bf16 product: label results computed with it as such)
         self._matmul = args.pop('matmul_precision', 'fp32')
         if self._matmul not in E.MATMUL_CHOICES:
             raise ValueError('matmul_precision must be one of %s' % (E.MATMUL_CHOICES,))

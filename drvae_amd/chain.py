@@ -46,6 +46,10 @@ class _Lin:
             self.scale = self.norm = self.raw = None
 
 
+# ``StepConfig.matmul`` -> bf16 parts per operand element of the split-bf16 rungs (3: ``dv_gemm_x3``; 2, 1: ``dv_gemm_split``)
+X3_PARTS = {'bf16x3': 3, 'bf16x2': 2, 'bf16x1': 1}
+
+
 class _Chain:
     """trunk layers + final layer of one block evaluated on M stacked rows, with buffers.
 
@@ -59,7 +63,9 @@ class _Chain:
         self.layers, self.M, self.resid_cols = layers, M, resid_cols
         # opt-in (``use_x3_last``, decided where the plan is built): the LAST layer's plain product (``raw_last``) and the two
         # gradient products behind it MAY run as split-bf16 products; a pass says whether they do (``forward(x3=...)``)
+        # ``x3_parts``: the rung, bf16 parts per operand (3: ``dv_gemm_x3``; 2, 1: ``dv_gemm_split``) -- remembered with it
         self.x3_last = False
+        self.x3_parts = 3
         self.out = [torch.zeros(M, _pad4(l.N), device=device)[:, :l.N] for l in layers]
         # gradient w.r.t. the pre-activation of every layer but the last (the caller owns that one)
         self.dpre = [torch.zeros(M, _pad4(l.N), device=device)[:, :l.N] for l in layers[:-1]]
@@ -94,13 +100,21 @@ class _Chain:
                                                                overread=True, publish=publish, npad=self._pad_ok(x),
                                                                npad_x=True)
 
-    def use_x3_last(self, dpre_last, db_in_pass):
-        """Route the last layer's raw product, its weight gradient and its data gradient to ``dv_gemm_x3`` from now on.
+    def _x3_kw(self):
+        """the launcher keywords of this chain's split-bf16 products: three parts are ``x3=True`` alone, as ever"""
+        return dict(x3=True) if self.x3_parts == 3 else dict(x3=True, parts=self.x3_parts)
+
+    def use_x3_last(self, dpre_last, db_in_pass, parts=3):
+        """Route the last layer's raw product, its weight gradient and its data gradient to ``dv_gemm_x3`` (``parts`` = 2, 1:
+        to ``dv_gemm_split`` with that many bf16 parts per operand, matmul 'bf16x2' / 'bf16x1') from now on.
         Decides up front: raises ValueError naming the reason when one of the three descriptors is not one the split-bf16
         kernels run (``dpre_last`` as ``backward`` will get it; ``db_in_pass``: the bias gradient comes from the producer
         of ``dpre_last``, not from the weight-gradient product)."""
         l, n = self.layers[-1], len(self.layers)
         why = None
+        if parts not in (1, 2, 3):
+            raise ValueError('use_x3_last(parts=%r): 1, 2 or 3' % (parts,))
+        pk = {} if parts == 3 else dict(parts=parts)
         if not self.raw_last_ok():
             why = 'the layer cannot run as a plain product'
         elif n == 1:
@@ -108,14 +122,14 @@ class _Chain:
         else:
             x = self.out[n - 2]
             a, kw = self._raw_last_call(x)
-            why = K.x3_refusal(*a, **kw)
+            why = K.x3_refusal(*a, **kw, **pk)
             if why is None:
                 a, kw = self._bwd_pair_call(n - 1, None if db_in_pass else l.db, dpre_last, x)
-                why = K.x3_pair_refusal(*a, **kw)
+                why = K.x3_pair_refusal(*a, **kw, **pk)
         if why is not None:
-            raise ValueError("matmul='bf16x3': the decoder-heads layer (%d x %d, %d rows) cannot run on dv_gemm_x3: %s"
-                             % (l.N, l.Kin, self.M, why))
-        self.x3_last = True
+            raise ValueError("matmul='bf16x%d': the decoder-heads layer (%d x %d, %d rows) cannot run on %s: %s"
+                             % (parts, l.N, l.Kin, self.M, 'dv_gemm_x3' if parts == 3 else 'dv_gemm_split', why))
+        self.x3_last, self.x3_parts = True, parts
 
     def forward(self, inputs, resid=None, publish=None, heads=None, raw_last=False, x3=False):
         """``publish`` = (flag, counter, add): the FIRST launch of the chain publishes on entry.
@@ -145,7 +159,7 @@ class _Chain:
                 assert self.raw_last_ok() and resid is None
                 if x3:
                     a, kw = self._raw_last_call(x[0], publish if li == 0 else None)
-                    K.gemm(*a, x3=True, **kw)
+                    K.gemm(*a, **self._x3_kw(), **kw)
                 else:
                     K.gemm(self.out[li], x[0], l.W, True, True, A2=x[1] if len(x) > 1 else None, overread=True,
                            publish=publish if li == 0 else None, kpad=kpad)
@@ -190,7 +204,7 @@ class _Chain:
                 if li > 0:
                     prev = self.layers[li - 1]
                     a, kw = self._bwd_pair_call(li, db, dpre, srcs[0], pending_pub)
-                    K.linear_bwd_pair(*a, **kw, **(dict(x3=True) if (x3_last and li == n_layers - 1) else {}))
+                    K.linear_bwd_pair(*a, **kw, **(self._x3_kw() if (x3_last and li == n_layers - 1) else {}))
                     dpre = self.dpre[li - 1]
                 else:
                     dst, alpha, beta = dinputs[0][0]

@@ -31,12 +31,14 @@ from . import kernels as K
 from . import tuning as T
 from ._lib import GAUSS_LOGVAR, GAUSS_SIGMA
 from .arena import N_LOSS, ParamArena, span
-from .chain import _Chain, _Lin, _pad4
+from .chain import X3_PARTS, _Chain, _Lin, _pad4
 from .plan import LOSS_IDX, _Plan
 from .schedule import DUAL, EVAL, EVALUATE, FORK_JOIN, LOSS, TRAIN, StepSchedule, StepSync, _Branch, heads_route
 
 
-MATMUL_CHOICES = ('fp32', 'bf16x3')
+# the precision ladder of the decoder-heads products: fp32, then the split-bf16 rungs by falling number of parts
+MATMUL_CHOICES = ('fp32',) + tuple(X3_PARTS)
+assert MATMUL_CHOICES == ('fp32', 'bf16x3', 'bf16x2', 'bf16x1')
 
 
 @dataclass
@@ -85,7 +87,10 @@ class StepConfig:
     kernel_MMD: str = 'rbf_fourier'
     # OPT-IN arithmetic of the decoder-heads layer where it takes the raw-heads route (the chip-filling products of the wide
     # configuration): 'fp32' = fp32 MFMA like every other product (default) | 'bf16x3' = split-bf16 products, six bf16 MFMA
-    # terms per fp32 product with fp32 accumulation (``dv_gemm_x3``).  Decided once, where the plan is built
+    # terms per fp32 product with fp32 accumulation (``dv_gemm_x3``) | 'bf16x2' = two bf16 parts per operand, three terms
+    # (``dv_gemm_split``; ~2^-16 of sum |a||b|: below fp32, far above bf16) | 'bf16x1' = ONE part, one term: a bf16 product
+    # of the rounded operands with fp32 accumulation (~2^-8: a different dtype, NOT held to the fp32 step's tolerances).
+    # Decided once, where the plan is built
     matmul: str = 'fp32'
 
     def __post_init__(self):

@@ -133,10 +133,13 @@ def _gemm_desc(Cm, A, B, a_kc, b_kc, *, A2=None, a_kscale=None, alpha=1.0, beta=
     return d
 
 
-def _x3_refusal(d):
-    """why ``dv_gemm_x3`` does not run descriptor ``d`` (None: it does).  The verdict is the library's (``dv_gemm_x3_ok``,
-    a pure host function); this only puts a name to it."""
-    if _lib.load().dv_gemm_x3_ok(C.byref(d)):
+def _x3_refusal(d, parts=3):
+    """why ``dv_gemm_x3`` (``parts`` < 3: ``dv_gemm_split``) does not run descriptor ``d`` (None: it does).  The verdict is
+    the library's (``dv_gemm_x3_ok`` / ``dv_gemm_split_ok``, pure host functions); this only puts a name to it."""
+    lib = _lib.load()
+    if parts not in (1, 2, 3):
+        return 'parts = %r (the split-bf16 rungs have 1, 2 or 3 parts)' % (parts,)
+    if lib.dv_gemm_x3_ok(C.byref(d)) if parts == 3 else lib.dv_gemm_split_ok(C.byref(d), parts):
         return None
     why = []
     if d.A2:
@@ -158,33 +161,40 @@ def _x3_refusal(d):
     return ', '.join(why) or 'dv_gemm_x3_ok refuses the descriptor'
 
 
-def _launch_x3(descs, what):
-    """bf16x3 routing decides up front: every descriptor of the call must be one ``dv_gemm_x3`` runs -- no silent fallback"""
+def _launch_x3(descs, what, parts=3):
+    """split-bf16 routing decides up front: every descriptor of the call must be one the rung's entry point runs
+    (``dv_gemm_x3``: three parts; ``dv_gemm_split``: two or one) -- no silent fallback"""
     for d in descs:
-        why = _x3_refusal(d)
+        why = _x3_refusal(d, parts)
         if why is not None:
-            raise RuntimeError('%s(x3=True): the split-bf16 kernels do not run this %d x %d x %d product: %s'
-                               % (what, d.M, d.N, d.K, why))
+            raise RuntimeError('%s(x3=True%s): the split-bf16 kernels do not run this %d x %d x %d product: %s'
+                               % (what, '' if parts == 3 else ', parts=%r' % (parts,), d.M, d.N, d.K, why))
     lib = _lib.load()
     for d in descs:
-        _lib.check(lib.dv_gemm_x3(C.byref(d), _stream()), 'dv_gemm_x3')
+        if parts == 3:
+            _lib.check(lib.dv_gemm_x3(C.byref(d), _stream()), 'dv_gemm_x3')
+        else:
+            _lib.check(lib.dv_gemm_split(C.byref(d), parts, _stream()), 'dv_gemm_split')
 
 
-def gemm(Cm, A, B, a_kc, b_kc, x3=False, **kw):
+def gemm(Cm, A, B, a_kc, b_kc, x3=False, parts=3, **kw):
     """C[M,N] = epilogue(alpha * Aop @ Bop) + beta*C, see ``dv_gemm`` in include/drvae_hip.h.
     ``overread``: rows of A and B may be over-read by up to 3 floats (padded / arena buffers).
     ``x3`` (opt-in): the product runs as a split-bf16 product (``dv_gemm_x3``; dtype bf16x3) -- raises where that entry
-    point does not take the descriptor."""
+    point does not take the descriptor.  ``parts`` (with ``x3``; 3 by default): 2 or 1 bf16 parts per operand, the cheaper
+    rungs of the ladder (``dv_gemm_split``; dtype bf16x2 / bf16x1 -- the latter is a bf16 product, not an fp32 one)."""
     d = _gemm_desc(Cm, A, B, a_kc, b_kc, **kw)
     if x3:
-        return _launch_x3([d], 'gemm')
+        return _launch_x3([d], 'gemm', parts)
+    if parts != 3:
+        raise ValueError('gemm(parts=%r) without x3=True: the fp32 product has no parts' % (parts,))
     _lib.check(_lib.load().dv_gemm(C.byref(d), _stream()), 'dv_gemm')
 
 
-def x3_refusal(Cm, A, B, a_kc, b_kc, **kw):
-    """plan-time question: would ``gemm(..., x3=True)`` with these operands run?  None, or the reason why not.  Shapes,
-    strides and addresses only -- nothing is launched, so the operands may live on any device"""
-    return _x3_refusal(_gemm_desc(Cm, A, B, a_kc, b_kc, _any_device=True, **kw))
+def x3_refusal(Cm, A, B, a_kc, b_kc, parts=3, **kw):
+    """plan-time question: would ``gemm(..., x3=True[, parts=...])`` with these operands run?  None, or the reason why not.
+    Shapes, strides and addresses only -- nothing is launched, so the operands may live on any device"""
+    return _x3_refusal(_gemm_desc(Cm, A, B, a_kc, b_kc, _any_device=True, **kw), parts)
 
 
 def _pair_descs(dW, dbias, dx, dpre, x, W, *, kscale=None, alpha=1.0, beta_x=0.0, yref=None, act=0, shift=0.0,
@@ -207,25 +217,27 @@ def _pair_descs(dW, dbias, dx, dpre, x, W, *, kscale=None, alpha=1.0, beta_x=0.0
     return d1, d2
 
 
-def linear_bwd_pair(dW, dbias, dx, dpre, x, W, x3=False, **kw):
+def linear_bwd_pair(dW, dbias, dx, dpre, x, W, x3=False, parts=3, **kw):
     """dW = dpre^T x (+ dbias) and dx = beta_x*dx + alpha*(dpre W) * act'(yref) in ONE launch when both fit
     the fused form of ``dv_gemm_pair`` (otherwise two launches).  Keywords: kscale, alpha, beta_x, yref, act, shift,
     overread, publish, npad, npad_x, klq (``_pair_descs``).
     ``x3`` (opt-in): both products as split-bf16 products (``dv_gemm_x3``, two launches -- what a chip-filling pair is
-    anyway); raises where that entry point does not take one of the two descriptors.
+    anyway); raises where that entry point does not take one of the two descriptors.  ``parts`` as in ``gemm``.
     ``klq`` = dict(out, q, eps, coef, raw, kl_min, Z): the layer's input was [a sample z of the q rows | ...]: instead of
     dx the launch writes d/d(mu | logvar) of those rows incl. their prior term into ``out`` (M, 2Z) -- the epilogue
     DV_EPI_KLQ of include/drvae_hip.h; ``dx`` is not written (pass None)"""
     d1, d2 = _pair_descs(dW, dbias, dx, dpre, x, W, **kw)
     if x3:
-        return _launch_x3([d1, d2], 'linear_bwd_pair')
+        return _launch_x3([d1, d2], 'linear_bwd_pair', parts)
+    if parts != 3:
+        raise ValueError('linear_bwd_pair(parts=%r) without x3=True: the fp32 products have no parts' % (parts,))
     _lib.check(_lib.load().dv_gemm_pair(C.byref(d1), C.byref(d2), _stream()), 'dv_gemm_pair')
 
 
-def x3_pair_refusal(dW, dbias, dx, dpre, x, W, **kw):
-    """plan-time question, as ``x3_refusal``: would ``linear_bwd_pair(..., x3=True)`` with these operands run?"""
+def x3_pair_refusal(dW, dbias, dx, dpre, x, W, parts=3, **kw):
+    """plan-time question, as ``x3_refusal``: would ``linear_bwd_pair(..., x3=True[, parts=...])`` with these operands run?"""
     d1, d2 = _pair_descs(dW, dbias, dx, dpre, x, W, _any_device=True, **kw)
-    return _x3_refusal(d1) or _x3_refusal(d2)
+    return _x3_refusal(d1, parts) or _x3_refusal(d2, parts)
 
 
 def linear_fwd(out, x, W, bias=None, *, x2=None, scale=None, split=None, act0=0, act1=0, shift0=0.0, shift1=0.0,

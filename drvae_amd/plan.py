@@ -8,7 +8,7 @@ import torch
 
 from . import kernels as K
 from .arena import N_LOSS
-from .chain import _Chain, _pad4
+from .chain import X3_PARTS, _Chain, _pad4
 from .schedule import heads_static
 
 LOSS_IDX = {'RECL': 0, 'KLD': 1, 'PERT': 2, 'YL': 3, 'MMD': 4, 'ELBO': 5, 'CMPL': 6}
@@ -183,9 +183,10 @@ class _Plan:
             self.NLLC, self.NLLWS = zf(Md, chunks), zf(rbs, 2 * X)
         # opt-in split-bf16 products (``StepConfig.matmul``): exactly one layer changes arithmetic -- the decoder's heads
         # layer where it takes the raw-heads route -- and whether it does is decided HERE, once (raises if its products are
-        # not ones ``dv_gemm_x3`` runs); every other product of the step stays fp32
-        if cfg.matmul == 'bf16x3' and Md > 0 and raw_ok:
-            self.c_decx.use_x3_last(self.DPX, db_in_pass=nll_cs)
+        # not ones ``dv_gemm_x3`` / ``dv_gemm_split`` runs); every other product of the step stays fp32.  The rungs differ in
+        # the number of bf16 parts per operand only ('bf16x3' | 'bf16x2' | 'bf16x1'): the chain remembers it
+        if cfg.matmul in X3_PARTS and Md > 0 and raw_ok:
+            self.c_decx.use_x3_last(self.DPX, db_in_pass=nll_cs, parts=X3_PARTS[cfg.matmul])
         if cfg.has_pert:
             self.c_z2F = _Chain(eng.L_z2F, L * B, dev, resid_cols=Z1)
             self.Z2F, self.D, self.DZ2F = mat(L * B, Z1), mat(L * B, Z1), mat(L * B, Z1)

@@ -136,7 +136,7 @@ class HeadsRoute(NamedTuple):
     nll: str                   # a key of NLL_ROUTES: the launch that writes the reconstruction rows
     rows: str                  # ... and the plan buffer that holds them: 'NLLP' | 'NLLC' | 'NLL'
     raw_last: bool             # the decoder's heads run as a plain product, finished by that row pass (``_Chain.forward``)
-    x3: bool                   # ... as split-bf16 products, with the gradient pair behind them
+    x3: bool                   # ... as split-bf16 products, with the gradient pair behind them (the rung: ``_Chain.x3_parts``)
     db_done: bool              # the heads' bias gradient is written by the row pass (``colsum``), not by the dW launch
 
 

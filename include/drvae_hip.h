@@ -238,6 +238,16 @@ int dv_gemm_pair(const dv_gemm_desc* d1, const dv_gemm_desc* d2, dv_stream_t str
  * 128 x 128 output tiles (K tile 32, 48 KiB of LDS: three bf16 planes per operand, two workgroups per CU).  dv_gemm_x3_ok: a pure function, 1 where dv_gemm_x3 would run the descriptor, 0 otherwise. */
 int dv_gemm_x3(const dv_gemm_desc* desc, dv_stream_t stream);
 int dv_gemm_x3_ok(const dv_gemm_desc* desc);
+/* The precision ladder of the split-bf16 product (OPT-IN, as dv_gemm_x3): `parts` = P bf16 parts per operand element, the
+ * FIRST P of hi, mid, lo above.  parts = 3 is dv_gemm_x3 ("dtype: bf16x3").  parts = 2 ("dtype: bf16x2"): the three terms
+ * hi hi, hi mid, mid hi (mid mid is dropped: the size of the residuals dropped already; <= (3 2^-16 + 2^-30) sum |a||b|
+ * from the exact product before accumulation), hi hi in one accumulator, the two correction terms in the other.  parts = 1
+ * ("dtype: bf16x1"): the one term hi hi in one accumulator, i.e. a bf16 product of the rounded operands with fp32
+ * accumulation (<= (2^-7 + 2^-16) sum |a||b|): NOT an fp32 product, label it.  Everything else -- what runs and what is
+ * refused, epilogues, alpha / beta, a_colsum, K tail, over-read, non-finite operands, bitwise reproducibility -- is
+ * dv_gemm_x3's.  parts outside 1..3: DV_ERR_ARG (dv_gemm_split_ok: 0). */
+int dv_gemm_split(const dv_gemm_desc* desc, int32_t parts, dv_stream_t stream);
+int dv_gemm_split_ok(const dv_gemm_desc* desc, int32_t parts);
 /* Dual-head Linear with the ROW work that consumes both heads fused into the epilogue (SURVEY.md K2+K3 /
  * K2+K5): y = x W^T with W = [W_head0 ; W_head1] (desc->split = rows of head 0, desc->N = 2*split), forward
  * layout (a_kcontig = b_kcontig = 1), epilogue DV_EPI_FWD exactly as dv_gemm (scale / bias / act0,shift0 |
