@@ -939,6 +939,43 @@ def test_reparam_bwd_seg(K, dev):
         close(dq, rq, rtol=1e-5, atol=1e-5)
 
 
+@pytest.mark.parametrize('mode', [0, 1])
+@pytest.mark.parametrize('n2', [0, 1, 40, 90])
+def test_reparam_bwd_seg_second_gradient_source(K, dev, mode, n2):
+    """dv_seg_add (``dz_add=``, VFAE's second gradient source): g[r] = dz[r] + dz_add[r] for the first n2 sample rows ==
+    the two-launch form in which dz + dz_add is formed first (bitwise: the same fp32 add), and the reference.  Segments
+    list the rows on both sides of n2, one segment is empty, one row sits in two segments; with ``extra``, beta = 1 and (in
+    log-variance mode, which it needs) the prior-KL gradient on the same launch"""
+    nq, Z, R_, F_ = 23, 100, 90, 40
+    Q = rnd(dev, nq + 5, 2 * Z, seed=1, scale=0.5)
+    sd = Q[:, Z:].abs() + 0.1 if mode == 1 else Q[:, Z:]
+    dz, eps, extra = rnd(dev, R_, Z, seed=2), rnd(dev, R_, Z, seed=3), rnd(dev, F_, 2 * Z, seed=4)
+    dz_add = strided(dev, R_, Z, 3, seed=5)[:n2]
+    edge = sorted({min(max(n2 - 1, 0), R_ - 1), min(n2, R_ - 1)})
+    gen = torch.Generator().manual_seed(6)
+    segs = [edge, [], [7, 12], [7] + edge] + [torch.randint(0, R_, (int(c),), generator=gen).tolist()
+                                               for c in torch.randint(1, 5, (nq - 4,), generator=gen)]
+    sp = torch.tensor(np.concatenate([[0], np.cumsum([len(s) for s in segs])]), dtype=torch.int32, device=dev)
+    sr = torch.tensor([r for s in segs for r in s], dtype=torch.int32, device=dev)
+    ep, er = _csr([int(v) for v in torch.randint(0, 3, (nq,), generator=torch.Generator().manual_seed(7))], F_, dev, 8)
+    kw = dict(mode=mode, extra=extra, ex_ptr=ep, ex_rows=er, beta=1.0)
+    if mode == 0:
+        raw = rnd(dev, nq, seed=10).abs() * 40
+        kw['prior'] = (rnd(dev, nq, seed=9), raw, float(raw.median()), Q[:nq, :Z])
+    summed = dz.clone()
+    summed[:n2] += dz_add
+    got, two, ref = (rnd(dev, nq, 2 * Z, seed=11) for _ in range(3))
+    K.reparam_bwd_seg(got[:, :Z], got[:, Z:], dz, eps, sd, sp, sr, dz_add=dz_add, **kw)
+    K.reparam_bwd_seg(two[:, :Z], two[:, Z:], summed, eps, sd, sp, sr, **kw)
+    R.reparam_bwd_seg(ref[:, :Z], ref[:, Z:], dz, eps, sd, sp, sr, dz_add=dz_add, **kw)
+    close(got, two, rtol=0, atol=0)
+    close(got, ref, rtol=1e-5, atol=1e-5)
+    if n2:       # ... and the second source counts: without it segment 0 (a row in front of n2) gives another result
+        bare = rnd(dev, nq, 2 * Z, seed=11)
+        K.reparam_bwd_seg(bare[:, :Z], bare[:, Z:], dz, eps, sd, sp, sr, **kw)
+        assert not torch.equal(got[0], bare[0]) and torch.equal(got[1], bare[1])
+
+
 def test_prior_kl_gradient_rides_on_the_gradient_row_launches(K, dev):
     """dv_prior_kl (round 5): the gradient of coef * max(KL(q || N(0,I)), kl_min) added by dv_reparam_bwd_seg (rows [0, B)) and
     dv_z2f_post_bwd (the pairs' q2 rows) == a dv_kl_rows_bwd(beta = 1) launch behind them"""
@@ -1112,6 +1149,36 @@ def test_batch_feed(K, dev, X, pad, Np, Mf):
     assert torch.equal(xin, rin)
 
 
+def test_batch_feed_second_onehot_copy(K, dev):
+    """dv_batch_feed_desc.onehot2: the class columns of the second fprop input -- bitwise ``onehot`` behind another leading
+    dimension, pad columns untouched; also without the first copy"""
+    N, B, Y, nb, X, Mf = 211, 50, 3, 4, 13, 41
+    x1 = rnd(dev, N, X, seed=1)
+    y32 = torch.randint(0, Y, (N,), dtype=torch.int32).to(dev)
+    table = torch.randint(0, N, (nb, B), dtype=torch.int32).to(dev)
+    has_y = (torch.arange(B) % 3 != 0).to(torch.int32).to(dev)
+    fp_i = torch.randint(0, B, (Mf,), dtype=torch.int32).to(dev)
+    fp_lab = has_y[fp_i.long()].contiguous()
+    fp_slot = torch.randint(0, Y, (Mf,), dtype=torch.int32).to(dev)
+    ctr, bs = torch.tensor([7], dtype=torch.int32, device=dev), torch.tensor([5], dtype=torch.int32, device=dev)
+    res = []
+    for mod, first in ((K, True), (R, True), (K, False)):
+        xin = torch.empty(B, X, device=dev)
+        fp_cls = torch.full((Mf,), -1, dtype=torch.int32, device=dev)
+        h1, h2 = torch.full((Mf, Y + 1), 7.0, device=dev), torch.full((Mf + 1, Y + 4), 7.0, device=dev)
+        mod.batch_feed(xin, x1, None, y32, table, nb, ctr, bs, has_y=has_y, fp_i=fp_i, fp_lab=fp_lab, fp_slot=fp_slot,
+                       fp_cls=fp_cls, onehot=h1[:, :Y] if first else None, onehot2=h2[:Mf, :Y], n_classes=Y)
+        torch.cuda.synchronize()
+        assert bool((h2[:, Y:] == 7.0).all()) and bool((h2[Mf:] == 7.0).all()) and bool((h1[:, Y:] == 7.0).all())
+        assert torch.equal(h2[:Mf, :Y], h1[:, :Y]) if first else bool((h1 == 7.0).all())
+        assert torch.equal(h2[:Mf, :Y], torch.nn.functional.one_hot(fp_cls.long(), Y).float())
+        res.append((xin, fp_cls, h2))
+    for other in res[1:]:
+        for a, b in zip(res[0], other):
+            assert torch.equal(a, b)
+    assert int(res[0][1].min()) >= 0 and len(set(res[0][1].tolist())) == Y
+
+
 @pytest.mark.parametrize('n1,n2,Z,Rr', [(6, 9, 5, 500), (75, 75, 100, 500), (300, 33, 128, 130)])
 def test_mmd_rff(K, dev, n1, n2, Z, Rr):
     from drvae_amd import ops
@@ -1281,6 +1348,67 @@ def test_batch_masks_and_labeled_slots(K, dev):
     K.loss_assemble(la, [(x2d, wrow, 0.5, 0, 7)], w_elbo, w_cmpl)
     R.loss_assemble(lb, [(x2d, wrow, 0.5, 0, 7)], w_elbo, w_cmpl)
     close(la, lb, rtol=1e-5, atol=1e-5)
+
+
+def test_batch_masks_one_slot_rows(K, dev):
+    """dv_batch_masks_desc.one_slot: rows of the plan with ONE class slot carry label = class (>= 0) instead of
+    -2 - class -- standalone and riding on the feed's launch (bit-equal), against the reference; then the y-marginalisation
+    on a plan in which exactly those rows have one fprop row"""
+    B, L, Y, nb = 37, 3, 3, 5
+    g = torch.Generator().manual_seed(0)
+    hx = (torch.rand(200, generator=g) < 0.4).to(torch.int32).to(dev)
+    hy = (torch.rand(200, generator=g) < 0.6).to(torch.int32).to(dev)
+    y = torch.randint(0, Y, (200,), generator=g).to(torch.int32).to(dev)
+    table = torch.randint(0, 200, (nb, B), generator=g).to(torch.int32).to(dev)
+    ctr, base = torch.tensor([9], dtype=torch.int32, device=dev), torch.tensor([7], dtype=torch.int32, device=dev)
+    src = table[2].long()
+    one_slot = (hy[src].bool() & (torch.arange(B, device=dev) % 2 == 0)).to(torch.int32)     # labeled for sure
+    assert 0 < int(one_slot.sum()) < int(hy[src].sum())
+    beta = torch.tensor([0.01], device=dev)
+    x1, x2 = rnd(dev, 200, 12, seed=11), rnd(dev, 200, 12, seed=12)
+    pair_rows = torch.arange(B, dtype=torch.int32, device=dev)
+    got = []
+    for how in ('kernel', 'ref', 'feed'):
+        bufs = dict(c_nll=torch.full((3 * L * B,), 9.0, device=dev), c_klz2=torch.full((L * B,), 9.0, device=dev),
+                    c_yl=torch.full((L * B,), 9.0, device=dev), w_recl=torch.full((2 * L * B,), 9.0, device=dev),
+                    w_pert=torch.full((L * B,), 9.0, device=dev), w_yl=torch.full((L * B,), 9.0, device=dev),
+                    label=torch.full((L * B + 1,), 9, dtype=torch.int32, device=dev))
+        kw = dict(n_tot=float(B), kl_rate=0.7, pert_rate=0.05, yl_rate=1.3, beta=beta, hx=hx, hy=hy, y=y, one_slot=one_slot,
+                  **bufs)
+        if how == 'feed':
+            xin = torch.zeros(2 * B, 12, device=dev)
+            K.batch_feed(xin, x1, x2, y, table, nb, ctr, base, pair_rows=pair_rows, L=L, masks=kw)
+        else:
+            (K if how == 'kernel' else R).batch_masks(B, L, table=table, n_batches=nb, ctr=ctr, base=base, **kw)
+        torch.cuda.synchronize()
+        got.append(bufs)
+    for k in got[0]:
+        assert torch.equal(got[0][k], got[2][k]), k
+        close(got[0][k].float(), got[1][k].float(), rtol=1e-6, atol=1e-9)
+    label = got[0]['label']
+    assert torch.equal(label, got[1]['label']) and int(label[L * B]) == 9
+    flag, lab, cls = (v.repeat(L) for v in (one_slot.bool(), hy[src].bool(), y[src]))
+    assert torch.equal(label[:L * B][flag], cls[flag]) and bool((label[:L * B][flag] >= 0).all())
+    assert torch.equal(label[:L * B][~flag & lab], -2 - cls[~flag & lab]) and bool((label[:L * B][~flag & ~lab] == 0).all())
+    # the plan those labels are for: one fprop row for a flagged row, Y class slots for every other
+    Rr = L * B
+    nf = torch.where(flag, 1, Y).cpu()
+    fp_ptr = torch.cat([torch.zeros(1, dtype=torch.int64), nf.cumsum(0)]).to(torch.int32).to(dev)
+    F_ = int(fp_ptr[-1])
+    qy = torch.softmax(rnd(dev, Rr, Y, seed=1), 1)
+    klfp, c_kld, c_yl = rnd(dev, F_, seed=2).abs(), rnd(dev, Rr, seed=3), got[0]['c_yl']
+    res = []
+    for Lb in (K, R):
+        o = [torch.full((Rr,), 7.0, device=dev), torch.full((Rr,), 7.0, device=dev), torch.full((F_,), 7.0, device=dev),
+             torch.full((Rr, Y), 7.0, device=dev)]
+        Lb.ymarg_fwdbwd(*o, qy, label[:Rr], fp_ptr, klfp, float(np.log(1.0 / Y)), c_kld, c_yl)
+        torch.cuda.synchronize()
+        res.append(o)
+    for a, b in zip(*res):
+        assert not bool((a == 7.0).any())
+        close(a, b, rtol=1e-5, atol=1e-6)
+    f0 = fp_ptr[:-1].long()
+    assert torch.equal(res[0][2][f0[flag]], c_kld[flag]) and torch.equal(res[0][1][flag], klfp[f0[flag]])
 
 
 def test_batch_masks_global_counts(K, dev):
