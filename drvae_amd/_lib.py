@@ -132,6 +132,14 @@ class MmdGrouped(C.Structure):   # dv_mmd_grouped_desc
                 ('cnt', _p), ('m2', _p), ('value', _p), ('dz', _p), ('ldd', _i64)]
 
 
+class MmdMasked(C.Structure):    # dv_mmd_masked_desc
+    _fields_ = [('z', _p), ('ldz', _i64), ('Z', _i32), ('kind', _i32), ('R', _i32), ('S', _i32), ('B', _i32), ('Np', _i32),
+                ('L', _i32), ('model', _i32), ('cls', _p), ('hx', _p), ('hy', _p), ('n_flags', _i32), ('table', _p),
+                ('n_batches', _i32), ('ctr', _p), ('base', _p), ('W', _p), ('b', _p), ('a', _f), ('c', _f), ('w', _f),
+                ('fac', _f), ('theta', _p), ('diff', _p), ('cnt', _p), ('members', _p), ('m2', _p), ('value', _p), ('dz', _p),
+                ('ldd', _i64)]
+
+
 class LossTerm(C.Structure):
     _fields_ = [('x', _p), ('w', _p), ('n', _i32), ('scale', _f), ('out', _i32), ('row_len', _i32)]
 
@@ -195,6 +203,8 @@ SIGNATURES = {
     'dv_nuisance_feed': [_p, _p, _i32, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _i64, _p, _i64, _p, _p],
     'dv_mmd_grouped_fwd': [C.POINTER(MmdGrouped), _p],
     'dv_mmd_grouped_bwd': [C.POINTER(MmdGrouped), _p],
+    'dv_mmd_masked_fwd': [C.POINTER(MmdMasked), _p],
+    'dv_mmd_masked_bwd': [C.POINTER(MmdMasked), _p],
     'dv_rows_gather': [_p, _i64, _p, _i32, _i32, _p, _i64, _f, _p, _i32, _p, _i64, C.POINTER(Wait), _p],
     'dv_batch_feed': [C.POINTER(BatchFeed), C.POINTER(BatchMasks), C.POINTER(Wait), _p],
     'dv_batch_masks': [C.POINTER(BatchMasks), _p, _i32, _p, _p, _i32, _i32, _p],

@@ -124,8 +124,16 @@ class DeviceBatcher:
         step gathers the classes of its batch itself (``dv_nuisance_feed``) and the MMD penalty reads class membership
         inside its two grouped launches: an epoch is ``len(self)`` replays of ONE captured step whatever the batches'
         composition of classes.  A term of the penalty with an empty side (a data group of a batch without a row of the
-        class, or with nothing else) is defined as 0 on this path.  Still refused: sampler mode with ``use_s``, and
+        class, or with nothing else) is defined as 0 on this path.  Still refused: sampler mode with ``carry_s=True``, and
         ``use_MMD`` under data parallelism.  The default keeps the host-driven routes and their refusals.
+        ``carry_s='masked'`` (sampler mode only, single process): the same for the reference's own sampler.  The step runs on
+        the batch-independent plan, which carries the classes (``set_structure_universal(carry_s=True)``), and the penalty reads
+        the batch's DATA GROUPS inside its two launches as well (``dv_mmd_masked_fwd`` / ``_bwd``): one captured step per plan
+        for every composition of groups and classes -- ``begin_epoch`` (drawn tables and ``table=``), ``draw_ahead``,
+        ``feed()``, ``rebase``, ``pair_bucket`` / ``label_bucket`` (every bucket plan carries; one shared feed) and
+        ``generator='cpu'`` included.  A term without members is 0 as well, and the z2 rows of pair slots that hold no pair get
+        a gradient of exact zeros.  Stratified batches have a fixed structure and the cheaper plan: ``'masked'`` there is a
+        ``ValueError``.  Under data parallelism ``use_s`` models on this feed are refused (``NotImplementedError``).
         ``mode='stratified'`` (default): every batch has the SAME composition (the expected counts of the four
         groups under the weights, or ``group_counts``) -- rows within a group drawn with replacement by weight;
         the step runs on the plan of exactly that structure.
@@ -182,7 +190,13 @@ class DeviceBatcher:
         self.batch_specs = None           # (bucketed) plan of every batch of the current epoch table: (pair slots, a, b)
         self._k = 0                       # (bucketed) batches handed out since begin_epoch
         self.n_switch = 0                 # (bucketed) how many times a step ran on another plan than the one before
-        self.carry_s = bool(carry_s)
+        if isinstance(carry_s, str):
+            if carry_s != 'masked':
+                raise ValueError("DeviceBatcher: carry_s is False, True or 'masked' (got %r)" % (carry_s,))
+            if mode != 'sampler':
+                raise ValueError("DeviceBatcher(carry_s='masked') is for mode='sampler': stratified batches have a fixed "
+                                 "structure, carry_s=True runs them on the cheaper plan")
+        self.carry_s = carry_s if isinstance(carry_s, str) else bool(carry_s)
         self.cpu_stream = generator == 'cpu'
         self.dp = None                   # (rank, world) under data parallelism: set by ``bind(dp=...)``
         if mode == 'sampler':
@@ -236,21 +250,27 @@ class DeviceBatcher:
             assert not engine.cfg.use_MMD, 'use_MMD: the MMD penalty is a cross-row term, it cannot be sharded over ranks'
             engine.row0 = self.rank * self.batch_size
         carry = bool(self.carry_s and engine.cfg.use_s)
-        if carry and self.mode == 'sampler':
+        if carry and self.mode == 'sampler' and self.carry_s != 'masked':
             raise NotImplementedError('DeviceBatcher(carry_s=True): the nuisance classes are carried on stratified device '
                                       'batches (a fixed batch structure); sampler mode runs on the batch-independent plan')
         if engine.cfg.use_s and not carry and (engine.cfg.use_MMD or self.mode == 'sampler'):
             raise NotImplementedError('DeviceBatcher: models conditioned on the nuisance variable (use_s extension) run on '
                                       'stratified device batches without the MMD penalty (its row lists are host knowledge); '
                                       'otherwise feed them through run_on_batch / a tuple loader')
+        if carry and self.mode == 'sampler' and self.dp is not None:
+            raise NotImplementedError("DeviceBatcher(mode='sampler', carry_s='masked') under data parallelism: models "
+                                      'conditioned on the nuisance variable run in a single process on this feed')
         if self.mode == 'sampler':
             assert counts is None, 'sampler feed: the global counts of every batch come from the shared index table (dp=...)'
             engine.universal = True
+            if carry:       # explicit batches of this engine (``set_batch``) go to the same kind of plan
+                engine.carry_s = 'masked'
             if self.pair_bucket and not engine.cfg.has_pert:
                 self.pair_bucket = None                      # (no pairs in this model: nothing to bucket)
             if self.label_bucket and not engine.cfg.has_y:
                 self.label_bucket = None
-            self._bound, self._bound_plan = sig, engine.set_structure_universal(self.batch_size, n_tot=self._n_tot())
+            self._bound, self._bound_plan = sig, engine.set_structure_universal(self.batch_size, n_tot=self._n_tot(),
+                                                                                carry_s=carry)
             return self._bound_plan
         if counts is None and self.dp is not None:      # every rank's batch has the same composition
             cfg = engine.cfg
@@ -437,11 +457,16 @@ class DeviceBatcher:
         return np.asarray([sp[0] for sp in self.batch_specs], np.int64)
 
     @property
+    def _carry(self):
+        """whether the bound engine's plans carry the nuisance classes on the device"""
+        return bool(self.carry_s and self.engine.cfg.use_s)
+
+    @property
     def _full_spec(self):
         return (self.batch_size, 0, 0)
 
     def _plan(self, spec):
-        p = self.engine.set_structure_universal(self.batch_size, spec[0], spec[1:], n_tot=self._n_tot())
+        p = self.engine.set_structure_universal(self.batch_size, spec[0], spec[1:], n_tot=self._n_tot(), carry_s=self._carry)
         self.engine.pinned_plans.add(p.key)       # (the plan cache is small and drops what is not captured)
         return p
 
@@ -540,7 +565,7 @@ class DeviceBatcher:
         """draw the next batch and write it into the bound engine's buffers (device to device)"""
         if self.mode == 'sampler' and self.bucketed:
             # explicit batches come in the order they were drawn: the plan without assumptions about the row order
-            self.engine.set_structure_universal(self.batch_size, n_tot=self._n_tot())
+            self.engine.set_structure_universal(self.batch_size, n_tot=self._n_tot(), carry_s=self._carry)
         p = self.engine.plan
         p.feed_active = False       # this batch is explicit data in XSRC, not a row of the epoch table
         idx = self.next_indices() if idx is None else idx

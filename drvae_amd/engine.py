@@ -207,7 +207,9 @@ class FusedStep(StepSchedule):
         self.universal_labeled_range = None   # ... and rows [a, b) are labeled for sure (one fprop row each)
         # ``use_s`` models: explicit batches (``set_batch``) go to plans that carry the nuisance classes on the device
         # (``_Plan.carry_nuisance``; ``s`` may then be a device tensor, no host round trip, and the MMD penalty runs as its
-        # two grouped launches) -- the plans ``DeviceBatcher(carry_s=True)`` binds.  Default: the host-list plans
+        # two grouped launches) -- the plans ``DeviceBatcher(carry_s=True)`` binds.  'masked' (set by
+        # ``DeviceBatcher(mode='sampler', carry_s='masked').bind``): the same on the universal plan when ``universal`` is on
+        # -- the penalty's data groups are device data too.  Default: the host-list plans
         self.carry_s = False
         self.plan = None
         self._plans = {}                    # plans by batch structure (a handful of signatures in practice)
@@ -297,9 +299,12 @@ class FusedStep(StepSchedule):
     # ------------------------------------------------------------------------- plan
     def universal_ok(self):
         cfg = self.cfg
-        return not cfg.cont and not (cfg.kind == 'vfae' and not cfg.semi_supervised) and not cfg.use_s
+        # (``use_s``: only with the nuisance classes AND the penalty's data groups carried as device data --
+        # ``DeviceBatcher(mode='sampler', carry_s='masked')``; otherwise such models run on structure plans)
+        return not cfg.cont and not (cfg.kind == 'vfae' and not cfg.semi_supervised) and \
+            (not cfg.use_s or self.carry_s == 'masked')
 
-    def set_structure_universal(self, n_rows, n_pair_slots=None, labeled_range=None, n_tot=None):
+    def set_structure_universal(self, n_rows, n_pair_slots=None, labeled_range=None, n_tot=None, carry_s=False):
         """Select (or build) the batch-independent plan for ``n_rows`` rows.  ``n_pair_slots`` < n_rows: only the FIRST
         so many rows of a batch have pair slots (x2 row, z2 / z2Fz1 sample rows) -- for feeds that put a batch's pairs
         first and choose the plan by the batch's number of pairs (``DeviceBatcher(mode='sampler', pair_bucket=...)``):
@@ -308,9 +313,14 @@ class FusedStep(StepSchedule):
         built for the batch's structure) instead of a row per class.  ``n_tot`` (data parallelism): the
         rows are one rank's slice of a GLOBAL batch of ``n_tot`` rows; N_pairs / N_labeled of every batch then are the
         global counts, handed over as data (``set_batch(counts=...)``, the feed's ``gcounts`` table) instead of being
-        counted over this slice by dv_batch_masks."""
+        counted over this slice by dv_batch_masks.  ``carry_s`` (required for ``use_s`` models, ignored for others): the
+        plan carries the nuisance classes on the device (``_Plan.carry_nuisance``); with ``use_MMD`` the penalty reads classes
+        AND data groups inside its two launches (``dv_mmd_masked_*``)."""
         cfg = self.cfg
-        assert self.universal_ok(), 'universal plan: discrete labels, semi-supervised models'
+        carry = bool(cfg.use_s and carry_s)
+        assert not cfg.cont and not (cfg.kind == 'vfae' and not cfg.semi_supervised), \
+            'universal plan: discrete labels, semi-supervised models'
+        assert carry or not cfg.use_s, 'universal plan of a use_s model: the nuisance classes are carried on the device (carry_s)'
         nps = n_rows if (n_pair_slots is None or not cfg.has_pert) else int(n_pair_slots)
         assert 0 <= nps <= n_rows
         lab = (0, 0) if (labeled_range is None or not cfg.has_y) else (int(labeled_range[0]), int(labeled_range[1]))
@@ -322,6 +332,8 @@ class FusedStep(StepSchedule):
             key = key + (nps,) + (lab if lab != (0, 0) else ())
         if n_tot is not None:
             key = key + (('n_tot', int(n_tot)),)
+        if carry:
+            key = key + ('carry_s',)
         if self.plan is None or self.plan.key != key:
             self.plan = self._plans.get(key)
             if self.plan is None:
@@ -332,6 +344,8 @@ class FusedStep(StepSchedule):
                                                       None if n_tot is None else (int(n_tot), 0, 0), key, universal=True)
                 if cfg.has_y:
                     self.plan.set_labels_host(np.zeros(n_rows, np.int64))      # class slots: static
+                if carry:
+                    self.plan.carry_nuisance()
                 self._evict_plans(key)
         return self.plan
 
@@ -398,7 +412,7 @@ class FusedStep(StepSchedule):
         if self.universal and self.universal_ok():
             hy = np.asarray(has_y.cpu() if torch.is_tensor(has_y) else has_y).reshape(-1)
             p = self.set_structure_universal(len(hy), self.universal_pair_slots, self.universal_labeled_range,
-                                             n_tot=None if counts is None else counts[0])
+                                             n_tot=None if counts is None else counts[0], carry_s=cfg.use_s)
             p.feed_active = False
             if counts is not None:       # this rank's slice of a global batch: the GLOBAL (N_pairs, N_labeled) are data
                 p.gcounts_dev.copy_(torch.tensor([int(counts[1]), int(counts[2])], dtype=torch.int32))
@@ -835,6 +849,22 @@ class FusedStep(StepSchedule):
         graph-safe device generator; a captured step is valid for the composition of nuisance classes it was
         captured with (``replay`` checks)."""
         cfg, p = self.cfg, self.plan
+        if p.mmd_masked is not None:
+            # ... on a universal plan: the batch's data groups are read inside the launches too, from the flags dv_batch_masks
+            # reads (the live feed's, through its table, or the explicit batch's).  Same two draws, same two launches
+            g = p.mmd_masked
+            if g['W'] is not None:
+                g['W'].normal_()
+                g['b'].uniform_()
+            fd = p.live_feed if (self.fuse_bwd and self.training) else None
+            if fd is not None:
+                g = dict(g, hx=fd.hx32 if cfg.has_pert else None, hy=fd.hy32 if cfg.has_y else None, table=fd.table,
+                         n_batches=fd.n_batches, ctr=self.step_dev, base=fd.base)
+            else:
+                g = dict(g, hx=p.hx_dev if cfg.has_pert else None, hy=p.hy_dev if cfg.has_y else None)
+            K.mmd_masked_fwd(g)
+            K.mmd_masked_bwd(g)
+            return
         if p.mmd_grouped is not None:
             # device-carried nuisance classes: ALL terms in one launch per direction, membership read from ``s_cls``; fresh
             # random features for every term from torch's graph-safe device generator (two launches), kept readable in the

@@ -844,6 +844,58 @@ def mmd_grouped_bwd(g):
     _lib.check(_lib.load().dv_mmd_grouped_bwd(C.byref(d), _stream()), 'dv_mmd_grouped_bwd')
 
 
+MMD_MASKED_MODEL = {'drvae': 0, 'pvae': 1, 'vfae': 2}       # DV_MMD_GROUPS_*: (data groups, their order)
+MMD_MASKED_GROUPS = {'drvae': 4, 'pvae': 2, 'vfae': 2}
+
+
+def mmd_masked_shapes(model, B, Np, L, S):
+    """(row lists, data groups, classes looped, terms, rows of z) of the masked penalty of a universal plan"""
+    n_lists, G, Kc = L * (2 if Np else 1), MMD_MASKED_GROUPS[model], (1 if S == 2 else S)
+    return n_lists, G, Kc, n_lists * G * Kc, L * (B + Np)
+
+
+def _mmd_masked_desc(g):
+    """``g``: the operands of the masked MMD penalty by name (``_Plan.carry_nuisance`` on a universal plan, see
+    ``dv_mmd_masked_desc``); ``hx`` / ``hy`` (and ``table`` / ``n_batches`` / ``ctr`` / ``base``) are the batch's flags"""
+    z, dz, rff, S = g['z'], g['dz'], g['kind'] == 'rbf_fourier', g['S']
+    B, Np, L = g['cls'].numel(), g['Np'], g['L']
+    n_lists, G, Kc, T, n_z = mmd_masked_shapes(g['model'], B, Np, L, S)
+    D = g['R'] if rff else z.shape[1]
+    assert z.shape[0] == n_z and dz.shape == z.shape and tuple(g['diff'].shape) == (T, D) and g['diff'].is_contiguous()
+    assert tuple(g['cnt'].shape) == (n_lists * G, S + 1) and tuple(g['members'].shape) == (n_lists * G, B)
+    assert g['cnt'].is_contiguous() and g['members'].is_contiguous() and g['m2'].numel() == T
+    if rff:
+        assert tuple(g['W'].shape) == (T, z.shape[1], g['R']) and g['W'].is_contiguous()
+        assert tuple(g['b'].shape) == (T, g['R']) and g['b'].is_contiguous()
+        assert tuple(g['theta'].shape) == (Kc * n_z, g['R']) and g['theta'].is_contiguous()
+    hx, hy, table = g.get('hx'), g.get('hy'), g.get('table')
+    flags = [f for f in (hx, hy) if f is not None]
+    assert all(f.dtype == torch.int32 and f.is_contiguous() for f in flags)
+    assert len({f.numel() for f in flags}) <= 1 and (table is not None or all(f.numel() == B for f in flags))
+    assert table is None or (tuple(table.shape) == (g['n_batches'], B) and table.is_contiguous())
+    return _lib.MmdMasked(z=_f32(z), ldz=_ld(z), Z=z.shape[1], kind=MMD_GROUPED_KIND[g['kind']], R=g['R'] if rff else 0, S=S,
+                          B=B, Np=Np, L=L, model=MMD_MASKED_MODEL[g['model']], cls=_i32(g['cls']), hx=_i32(hx), hy=_i32(hy),
+                          n_flags=flags[0].numel() if flags else 1, table=_i32(table),
+                          n_batches=g.get('n_batches', 0) if table is not None else 0,
+                          ctr=_i32(g.get('ctr')) if table is not None else None,
+                          base=_i32(g.get('base')) if table is not None else None,
+                          W=_f32(g['W']) if rff else None, b=_f32(g['b']) if rff else None, a=g['a'], c=g['c'], w=g['w'],
+                          fac=g['fac'], theta=_f32(g['theta']) if rff else None, diff=_f32(g['diff']), cnt=_i32(g['cnt']),
+                          members=_i32(g['members']), m2=_f32(g['m2']), value=_f32(g['value']), dz=_f32(dz), ldd=_ld(dz))
+
+
+def mmd_masked_fwd(g):
+    """feature-mean differences of every MMD term of a step on a universal plan, one launch (``dv_mmd_masked_fwd``)"""
+    d = _mmd_masked_desc(g)
+    _lib.check(_lib.load().dv_mmd_masked_fwd(C.byref(d), _stream()), 'dv_mmd_masked_fwd')
+
+
+def mmd_masked_bwd(g):
+    """the penalty's value and its gradient w.r.t. every sample row, one launch (``dv_mmd_masked_bwd``)"""
+    d = _mmd_masked_desc(g)
+    _lib.check(_lib.load().dv_mmd_masked_bwd(C.byref(d), _stream()), 'dv_mmd_masked_bwd')
+
+
 def rows_gather(out, src, idx=None, *, noise=None, sigma=0.0, onehot_cls=None, n_classes=0, width=None, park=None):
     n = out.shape[0]
     W = (src.shape[1] if src is not None else 0) if width is None else width

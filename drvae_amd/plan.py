@@ -256,6 +256,7 @@ class _Plan:
     # grouped launches: nothing of such a plan depends on the batch's composition of classes
     carry_s = False
     mmd_grouped = None
+    mmd_masked = None       # (universal plan) the same penalty with the batch's data groups read as data: dv_mmd_masked_*
 
     def carry_nuisance(self):
         """make this plan one that carries the nuisance classes on the device (called once, right after construction):
@@ -263,10 +264,11 @@ class _Plan:
         launches (``dv_mmd_grouped_fwd`` / ``_bwd``), from the batch STRUCTURE alone.  Term groups in the reference's
         order of data groups (src/DrVAE.py:585-608; src/PVAE.py:441-453; src/VFAE.py:421-433), per Monte-Carlo sample, on
         z1 and (pairs) z2 (src/DrVAE.py:537-540): the rows ``l B + idx_g`` / ``o2 + l Np + slot[idx_g]`` of the stacked
-        sample rows"""
+        sample rows.  On a UNIVERSAL plan the data groups of a batch are data as well: no term table, the buffers of
+        ``dv_mmd_masked_fwd`` / ``_bwd`` instead (``mmd_masked``; the batch's flags join them per step: ``FusedStep._mmd_penalty``)"""
         from .blocks import MMD_RFF_BANDWIDTH, MMD_RFF_DIM
         cfg, dev = self._cfg, self.ZDEC.device
-        assert cfg.use_s and not self.universal
+        assert cfg.use_s
         L, B, Np, Z, S = cfg.L, self.B, self.Np, cfg.dim_z1, cfg.dim_s
         i32 = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.int32, device=dev)
         zf = lambda *s: torch.zeros(*s, device=dev)
@@ -276,6 +278,20 @@ class _Plan:
             return self
         assert cfg.kernel_MMD in K.MMD_GROUPED_KIND, 'use_MMD on device-carried nuisance classes: kernel_MMD rbf_fourier | identity'
         assert 2 <= S <= K.MMD_MAX_CLASSES and B > 0
+        rff = cfg.kernel_MMD == 'rbf_fourier'
+        R = MMD_RFF_DIM if rff else 0
+        if self.universal:
+            n_lists, G, Kc, T, n_z = K.mmd_masked_shapes(cfg.kind, B, Np, L, S)
+            assert n_z == self.o3
+            self.mmd_masked = dict(
+                z=self.ZDEC[:self.o3], dz=self.DZMMD, kind=cfg.kernel_MMD, model=cfg.kind, R=R, S=S, cls=self.s_cls, Np=Np, L=L,
+                a=math.sqrt(2. / MMD_RFF_BANDWIDTH) / math.sqrt(Z), c=math.sqrt(2. / R) if rff else 1.0,
+                w=(1.0 if S == 2 else 1.0 / S) / L, fac=-cfg.mmd_rate / self.n_tot,
+                diff=zf(T, R if rff else Z), cnt=torch.zeros(n_lists * G, S + 1, dtype=torch.int32, device=dev),
+                members=torch.zeros(n_lists * G, B, dtype=torch.int32, device=dev), m2=zf(T), value=self.MMDval,
+                # fresh W ~ N(0,1), b ~ U(0,1) for every term of every step, stacked: a slot for every (list, group, class)
+                W=zf(T, Z, R) if rff else None, b=zf(T, R) if rff else None, theta=zf(Kc * n_z, R) if rff else None)
+            return self
         hx = self._hx_host
         hy = self._has_y_host.astype(bool) if cfg.has_y else np.zeros(B, bool)
         if cfg.kind == 'drvae':
@@ -299,8 +315,6 @@ class _Plan:
         n_groups, E, Kc = len(rows), ptr[-1], (1 if S == 2 else S)
         # every sample row sits in exactly one group: the backward launch WRITES every row of DZMMD, no zero fill
         assert sorted(np.concatenate(rows).tolist()) == list(range(self.o3))
-        rff = cfg.kernel_MMD == 'rbf_fourier'
-        R = MMD_RFF_DIM if rff else 0
         self.mmd_grouped = dict(
             z=self.ZDEC[:self.o3], dz=self.DZMMD, kind=cfg.kernel_MMD, R=R, S=S, cls=self.s_cls, grp_ptr=i32(ptr),
             rows=i32(np.concatenate(rows)), src=i32(np.concatenate(src)), max_rows=int(np.diff(ptr).max()),

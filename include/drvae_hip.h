@@ -880,6 +880,78 @@ typedef struct dv_mmd_grouped_desc {
 } dv_mmd_grouped_desc;
 int dv_mmd_grouped_fwd(const dv_mmd_grouped_desc* d, dv_stream_t stream);
 int dv_mmd_grouped_bwd(const dv_mmd_grouped_desc* d, dv_stream_t stream);
+/* The same penalty on a batch-independent ("universal") plan: the DATA GROUPS of the batch are data too, read inside the
+ * launches the way dv_batch_masks reads them.  One captured step serves every composition of groups and classes.
+ * Row lists.  z holds the sample rows of a universal plan with B batch rows, Np <= B pair slots (slot j belongs to batch
+ *   row j) and L Monte-Carlo samples: n_z = L (B + Np) rows.  A row list q < n_lists = L (Np > 0 ? 2 : 1) is one (sample,
+ *   latent) pair: q < L is the z1 list of sample l = q, rows l B + i of z, i < B, batch row i; q >= L is the z2 list of
+ *   sample l = q - L, rows o2 + l Np + j, j < Np, batch row j (o2 = L B).  Every row of z sits in exactly one list.
+ * Data group of batch row i.  With r = table[b, i], b = clamp(ctr[0] - base[0], 0, n_batches - 1) (table == NULL: r = i,
+ *   batch-local flags), hx = hx[r] != 0 and hy = hy[r] != 0 (hx == NULL / hy == NULL: a model without pairs / without
+ *   labels, the flag is 0; r is clamped to [0, n_flags)), the G groups of `model` in the reference's order are
+ *     DV_MMD_GROUPS_DRVAE (G = 4): [hy & ~hx, ~hy & ~hx, hy & hx, ~hy & hx]     (src/DrVAE.py:585-608)
+ *     DV_MMD_GROUPS_PVAE  (G = 2): [~hx, hx]                                    (src/PVAE.py:441-453)
+ *     DV_MMD_GROUPS_VFAE  (G = 2): [hy, ~hy]                                    (src/VFAE.py:421-433)
+ *   A z2 row exists for the pairs of the batch only: batch row j is a member of a z2 list iff hx, so a z2 list has
+ *   members in the groups of pairs only.
+ * Terms.  Term group tg = q G + g: the MEMBERS of (list q, data group g) are the list's rows whose batch row is in group
+ *   g, in ascending batch row.  For every class k < K (K = S, or 1 when S == 2) there is a term t = tg K + k; n0 / n1 are
+ *   the members with cls[batch row] == k / != k.  theta, diff, m2, value and dz are the formulas of dv_mmd_grouped_* above
+ *   with the sums over j running over the members; value sums over ALL n_lists G K terms.
+ * Layouts (T = n_lists G K terms; D = R for kind 1, Z for kind 0):
+ *   W (T, Z, R), b (T, R), diff (T, D), m2 (T)            indexed by the term
+ *   theta (K, n_z, R): theta[(k n_z + row), r] of z's row `row` (every row is a member of at most one term group)
+ *   cnt (n_lists G, S + 1): members per class, then the number of members of the term group
+ *   members (n_lists G, B): the members' batch rows, the first cnt[tg, S] entries of row tg (workspace, _fwd -> _bwd)
+ * Defined edge cases: a term without members, with an empty side (n0 == 0 or n1 == 0) or with m2 == 0 has value 0 and
+ *   gradient 0; its diff row is written as zeros.  A row of z that belongs to no term -- the z2 row of a pair slot whose
+ *   batch row is no pair in this batch -- gets dz written as exact zeros by every launch (the slot may have held a pair
+ *   in the batch before).  Rows of theta of such rows and of empty-sided terms are not written.
+ * Determinism: one writer per output element, no atomics, no zero-fill launch, fixed summation order (members in
+ *   ascending batch row, split over the same 16 row groups / 64 lanes as dv_mmd_grouped_*): two launches on the same
+ *   inputs give bit-equal results.
+ * _fwd writes members, cnt, theta (kind 1) and diff; _bwd reads them back and writes m2, value and every row of dz.
+ * Refusals: S > DV_MMD_MAX_CLASSES, Np > B, a missing operand: -1 before anything is launched.  DV_ERR_UNSUPPORTED: _bwd
+ *   when 8 rows of (R + Z) floats do not fit 60 KB of LDS (as dv_mmd_grouped_bwd), either when B ints do not. */
+#define DV_MMD_GROUPS_DRVAE 0
+#define DV_MMD_GROUPS_PVAE 1
+#define DV_MMD_GROUPS_VFAE 2
+typedef struct dv_mmd_masked_desc {
+    const float* z;
+    int64_t ldz;
+    int32_t Z;
+    int32_t kind;        /* 1 rbf_fourier, 0 identity */
+    int32_t R;
+    int32_t S;
+    int32_t B;           /* batch rows: entries of cls */
+    int32_t Np;          /* pair slots */
+    int32_t L;
+    int32_t model;       /* DV_MMD_GROUPS_* */
+    const int32_t* cls;
+    const int32_t* hx;
+    const int32_t* hy;
+    int32_t n_flags;     /* entries of hx / hy */
+    const int32_t* table;
+    int32_t n_batches;
+    const int32_t* ctr;
+    const int32_t* base;
+    const float* W;
+    const float* b;
+    float a;
+    float c;
+    float w;
+    float fac;
+    float* theta;
+    float* diff;
+    int32_t* cnt;
+    int32_t* members;
+    float* m2;
+    float* value;
+    float* dz;
+    int64_t ldd;
+} dv_mmd_masked_desc;
+int dv_mmd_masked_fwd(const dv_mmd_masked_desc* d, dv_stream_t stream);
+int dv_mmd_masked_bwd(const dv_mmd_masked_desc* d, dv_stream_t stream);
 
 /* The tail of a whole-set evaluation (round 5) in three launches instead of ~75 small library ones:
  * dv_recon_finalize: out[0..3] = rmse, variance-weighted R^2, mean per-row Pearson r, mean log-likelihood (float64) from
