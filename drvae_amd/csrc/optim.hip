@@ -24,12 +24,17 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
                                          float eps, float wd, float w1, float b2, float w2, float gscale) {
     // torch/optim/adam.py::_single_tensor_adam (2.x): grad += wd*p; m.lerp_(g, 1-b1);
     // v = v*b2 + (1-b2)*g*g; denom = sqrt(v)/sqrt(bc2) + eps; p += -(lr/bc1) * (m/denom)
-    g *= gscale;
-    if (wd != 0.f) g = g + wd * p;
-    m = m + w1 * (g - m);
-    v = v * b2 + (w2 * g) * g;
+    // Every fused multiply-add is written out and nothing else may be contracted: left to the compiler, the float4 loops
+    // fused all four (g, m, v, p) while the scalar loops -- whose g*gscale | wd*p and v*b2 | (w2*g)*g the vectoriser packs
+    // into one two-wide multiply each -- fused none of those two, so one element came out an ulp apart depending on the
+    // alignment of the view it was swept through (tests/test_gpu_optim.py, path equality).  This is the float4 loops' form.
+#pragma clang fp contract(off)
+    g = g * gscale;
+    if (wd != 0.f) g = __builtin_fmaf(wd, p, g);
+    m = __builtin_fmaf(w1, g - m, m);
+    v = __builtin_fmaf(w2 * g, g, v * b2);
     const float denom = sqrtf(v) / bc2_sqrt + eps;
-    p = p + (-step_size) * (m / denom);
+    p = __builtin_fmaf(-step_size, m / denom, p);
 }
 
 // sticky error words of the step's device-side waits: (err, ticks) pairs, see dv_wait in drvae_hip.h
@@ -101,8 +106,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     __syncthreads();
     // a chain wait has timed out (now or in an earlier step): the gradients may be built on stale data --
     // leave parameters and moments as they are (the loss scalars come out NaN, the host raises).  In the one step in
-    // which THIS launch's gate times out only the parked workgroups (the gated slice) see it: the others have swept
-    // their elements already -- that step is applied everywhere but on the gated slice, every later one nowhere
+    // which THIS launch's gate times out only the parked workgroups see it: the others have swept their elements
+    // already -- that step is applied everywhere but on the parked workgroups' elements (every span they visit, their
+    // share of the scalar tail: at least the gated slice), every later one nowhere (tests/test_gpu_optim.py)
     if (halted) return;
     const float step_size = sc[0], bc2_sqrt = sc[1];
     // (float)(1 - beta) computed in double first, as python does before the op sees it

@@ -1047,7 +1047,9 @@ int dv_adam_l2(float* p, const float* g, float* m, float* v, int64_t n, const dv
 /* same sweep, but the elements [lo, hi) are touched only after another launch chain has published `gate->flag`
  * (flag[0] >= ctr[0] + add, see dv_flag_publish): only the workgroups overlapping the range park (bounded
  * like dv_flag_wait: err[0] = 1 on time-out, err[1] += ticks parked), so gradients that are leaves of
- * the backward pass may still be in flight on the other chain when the optimiser launch starts */
+ * the backward pass may still be in flight on the other chain when the optimiser launch starts.  A parked workgroup
+ * looks at `halt` again after its wait: with gate->err among the halt words a time-out leaves the elements of the parked
+ * workgroups (at least [lo, hi)) as they are while the others have been swept; without it the time-out is only reported */
 int dv_adam_l2_gated(float* p, const float* g, float* m, float* v, int64_t n, const dv_adam_hyper* h,
                      const int32_t* step_dev, const dv_wait* gate, int64_t lo, int64_t hi, const int32_t* halt,
                      int32_t n_halt, dv_stream_t stream);
