@@ -7,7 +7,14 @@ from ._model_base import ELBOModel
 
 class DrVAE(ELBOModel):
     """p(x1,x2,z1,z2,z3,y) = p(z3)p(y)p(z1|z3,y)p(z2|z1)p(x1|z1)p(x2|z2) with posteriors
-    q(z1|x1), q(z2|x2) (shared encoder), q(y|z1,z2), q(z3|z1,y)  (arXiv:1706.08203)."""
+    q(z1|x1), q(z2|x2) (shared encoder), q(y|z1,z2), q(z3|z1,y)  (arXiv:1706.08203).
+
+    ``dropout_rate`` > 0 drops every hidden activation in front of the layer that reads it, inside the fused train step (keep
+    masks drawn on the device with the step's noise; evaluation and inference drop nothing).  Two labelled differences from
+    the block-level path and the reference, named by one warning at construction: the two heads of a block share ONE keep
+    mask (each head's marginal is the reference's, the joint is not), and a block without a hidden layer -- always
+    ``decoder_z2Fz1``, whose log-variance head alone the reference drops -- is not dropped at all.
+    ``dropout_rate`` >= 1 raises ``ValueError``."""
     kind = 'drvae'
 
     def __init__(self, dim_x, dim_s, dim_y, dim_c=1, dim_m=1, dim_h_en_z1=(50, 50), dim_h_de_z1=(50, 50),

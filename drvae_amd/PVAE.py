@@ -3,7 +3,14 @@ from ._model_base import ELBOModel
 
 
 class PVAE(ELBOModel):
-    """p(x1,x2,z1,z2) = p(z1)p(z2|z1)p(x1|z1)p(x2|z2); q(z1|x1), q(z2|x2) share one encoder."""
+    """p(x1,x2,z1,z2) = p(z1)p(z2|z1)p(x1|z1)p(x2|z2); q(z1|x1), q(z2|x2) share one encoder.
+
+    ``dropout_rate`` > 0 drops every hidden activation in front of the layer that reads it, inside the fused train step (keep
+    masks drawn on the device with the step's noise; evaluation and inference drop nothing).  Two labelled differences from
+    the block-level path and the reference, named by one warning at construction: the two heads of a block share ONE keep
+    mask (each head's marginal is the reference's, the joint is not), and a block without a hidden layer -- always
+    ``decoder_z2Fz1``, whose log-variance head alone the reference drops -- is not dropped at all.
+    ``dropout_rate`` >= 1 raises ``ValueError``."""
     kind = 'pvae'
     prior_y = None          # read by the reference ctor (src/PVAE.py:77) although PVAE has no y
 

@@ -3,7 +3,13 @@ from ._model_base import ELBOModel
 
 
 class VFAE(ELBOModel):
-    """p(x,z1,z2,y) = p(z2)p(y)p(z1|z2,y)p(x|z1); q(z1|x) q(y|z1) q(z2|z1,y)  (arXiv:1511.00830)."""
+    """p(x,z1,z2,y) = p(z2)p(y)p(z1|z2,y)p(x|z1); q(z1|x) q(y|z1) q(z2|z1,y)  (arXiv:1511.00830).
+
+    ``dropout_rate`` > 0 drops every hidden activation in front of the layer that reads it, inside the fused train step (keep
+    masks drawn on the device with the step's noise; evaluation and inference drop nothing).  Two labelled differences from
+    the block-level path and the reference, named by one warning at construction: the two heads of a block share ONE keep
+    mask (each head's marginal is the reference's, the joint is not), and a block without a hidden layer is not dropped at all.
+    ``dropout_rate`` >= 1 raises ``ValueError``."""
     kind = 'vfae'
     fit_patience = 40       # src/VFAE.py:536
 

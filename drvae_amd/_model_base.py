@@ -45,6 +45,7 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         self.nprng = np.random.RandomState(self.random_seed)
         torch.manual_seed(self.random_seed)
         self._build_blocks()
+        self._dropout_notes()
         self._create_optimizer()
         if device is None:
             device = 'cuda' if torch.cuda.is_available() else 'cpu'
@@ -75,8 +76,9 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
             raise ValueError('Invalid combination of clf_1sig and dim_y')      # src/DrVAE.py:161
         # input_x_dropout (--x-dropout) is accepted and has NO effect, exactly as in the reference: its MLP
         # computes the dropped inputs and then concatenates the ORIGINAL ones (src/blocks.py:158-161)
-        if self.dropout_rate > 0:
-            bad.append('dropout_rate > 0 (hard-coded 0. by every reference driver)')
+        # dropout_rate > 0 (hard-coded 0. by every reference driver) runs in the fused step: ``_dropout_notes``
+        if not 0. <= self.dropout_rate < 1.:
+            raise ValueError('dropout_rate must lie in [0, 1)')
         pr = getattr(self, 'prior_y', 'uniform')
         if pr is not None and not isinstance(pr, str):       # a class prior given as data (src/DrVAE.py:83-85)
             assert isinstance(pr, np.ndarray) and len(pr) == self.dim_y
@@ -116,6 +118,35 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
                'poisson': blk.PoissonDecoder}[self.type_rec]                 # src/DrVAE.py:124-129
         self.decoder_x = dec([Z1] + s_in, self.dim_h_de_x, self.dim_x, **hp)
 
+    def _dropout_notes(self):
+        """Hidden-layer dropout in the fused train step (``dropout_rate`` > 0): every hidden activation of every block is
+        dropped in front of the layer that reads it -- the reference's ``dropout{i}`` (i > 1) and the ``dropout_mu`` /
+        ``dropout_lv`` / ``dropout_sg`` / ``dropout_p`` in front of the heads.  Two LABELLED DIFFERENCES from the block-level
+        path (and the reference), named once here in a warning:
+          * shared head mask: the two heads of a block are one product over one input, so both read ONE keep mask where the
+            reference draws two independent ones -- each head's marginal is the reference's, the joint is not;
+          * a block without hidden layers is not dropped at all in the fused step (no hidden activation, no site): always
+            ``decoder_z2Fz1``, whose log-variance head alone the reference drops, and any block built with an empty hidden list."""
+        if not self.dropout_rate > 0:
+            return
+        hidden = OrderedDict(encoder_z1=self.dim_h_en_z1)
+        if self.kind in ('drvae', 'pvae'):
+            hidden['decoder_z2Fz1'] = []
+        if self.kind in ('drvae', 'vfae'):
+            hidden['encoder_y'] = self.dim_h_clf
+            hidden['encoder_z3' if self.kind == 'drvae' else 'encoder_z2'] = \
+                self.dim_h_en_z3 if self.kind == 'drvae' else self.dim_h_en_z2
+            hidden['decoder_z1'] = self.dim_h_de_z1
+        hidden['decoder_x'] = self.dim_h_de_x
+        # (one head in the fused step: the classifier -- a regression head's log-variance is fixed, its layer is not in the
+        # step's chain (``FusedStep.L_clf``) -- and a Bernoulli / Poisson decoder)
+        two_heads = [n for n, h in hidden.items() if len(h) and n != 'encoder_y' and not
+                     (n == 'decoder_x' and self.type_rec != 'diag_gaussian')]
+        undropped = [n for n, h in hidden.items() if not len(h)]
+        warnings.warn('dropout_rate=%g in the fused train step differs from the block-level path in two labelled ways: '
+                      'both heads share ONE keep mask in %s; no dropout at all (no hidden layer) in %s'
+                      % (self.dropout_rate, ', '.join(two_heads) or 'no block', ', '.join(undropped) or 'no block'))
+
     def _step_config(self):
         top = 'dim_z3' if self.kind == 'drvae' else 'dim_z2'
         return E.StepConfig(
@@ -136,7 +167,7 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
             use_MMD=bool(getattr(self, 'use_s', False) and getattr(self, 'use_MMD', False)),
             mmd_rate=float(getattr(self, 'mmd_rate', 1.)), kernel_MMD=getattr(self, 'kernel_MMD', 'rbf_fourier'),
             prior_y=None if (getattr(self, 'prior_y', None) is None or isinstance(getattr(self, 'prior_y', None), str))
-            else tuple(float(v) for v in self.prior_y), matmul=self._matmul)
+            else tuple(float(v) for v in self.prior_y), matmul=self._matmul, dropout_rate=float(self.dropout_rate))
 
     # ---------------------------------------------------------------- inference
     @torch.no_grad()

@@ -57,7 +57,13 @@ class _Chain:
     or be WHOLE row-padded buffers with zero pads (``plan.mat``): the products then run over the padded K (``kpad`` of
     ``kernels._gemm_desc``; the arena's weights are row-padded the same way).  ``backward`` likewise runs the weight
     gradient of a single-source layer and the data gradients into its own buffers (or into a destination made of whole
-    padded rows) over the padded N (``npad``): the pad columns receive the zeros they hold anyway."""
+    padded rows) over the padded N (``npad``): the pad columns receive the zeros they hold anyway.
+
+    Hidden-layer dropout (``add_dropout``): a SITE is the input of layer li >= 1, the hidden activation ``out[li - 1]``.  A
+    pass with ``drop=True`` writes ``outd[li - 1] = out[li - 1] * mask / keep`` behind the producing launch (one
+    ``K.mask_scale``) and every consumer -- the next layer's product on whichever route, its weight gradient -- reads
+    ``outd``; ``out`` stays undropped (the activation derivative is taken from it) and ``dpre[li - 1]`` is scaled in place
+    by the same mask behind the data-gradient launch.  A pass with ``drop=False`` launches nothing and reads ``out``."""
 
     def __init__(self, layers, M, device, resid_cols=0):
         self.layers, self.M, self.resid_cols = layers, M, resid_cols
@@ -69,6 +75,22 @@ class _Chain:
         self.out = [torch.zeros(M, _pad4(l.N), device=device)[:, :l.N] for l in layers]
         # gradient w.r.t. the pre-activation of every layer but the last (the caller owns that one)
         self.dpre = [torch.zeros(M, _pad4(l.N), device=device)[:, :l.N] for l in layers[:-1]]
+        # dropout sites (``add_dropout``): keep masks (views the caller owns), the dropped activations, 1 / keep
+        self.masks, self.outd, self.inv_keep = None, None, 1.0
+
+    def add_dropout(self, masks, keep):
+        """make every hidden activation of the chain a dropout site: ``masks[li]`` is the (M, N) keep mask of ``out[li]``
+        (1.0 / 0.0, filled by the caller before a ``drop=True`` pass), ``keep`` the keep probability"""
+        assert len(masks) == len(self.layers) - 1 and not self.x3_last, 'sites first, then use_x3_last'
+        assert all(m.shape == o.shape for m, o in zip(masks, self.out))
+        dev = self.out[0].device
+        self.masks, self.inv_keep = list(masks), 1.0 / keep
+        # whole-row buffers with zero pads, like ``out``: the next product runs over the padded K
+        self.outd = [torch.zeros(self.M, _pad4(l.N), device=dev)[:, :l.N] for l in self.layers[:-1]]
+
+    def _hidden(self, li, drop):
+        """what the consumers of hidden activation ``li`` read in a pass"""
+        return self.outd[li] if (drop and self.masks) else self.out[li]
 
     @staticmethod
     def _pad_ok(t):
@@ -120,26 +142,32 @@ class _Chain:
         elif n == 1:
             why = 'the layer is the chain\'s only one (its gradient products are not a plain pair)'
         else:
-            x = self.out[n - 2]
-            a, kw = self._raw_last_call(x)
-            why = K.x3_refusal(*a, **kw, **pk)
-            if why is None:
-                a, kw = self._bwd_pair_call(n - 1, None if db_in_pass else l.db, dpre_last, x)
-                why = K.x3_pair_refusal(*a, **kw, **pk)
+            # (the operand as a pass will really read it: a train pass of a chain with dropout sites reads the dropped
+            # buffer, its evaluation passes the undropped one -- both are asked about)
+            for x in ([self.outd[n - 2]] if self.masks else []) + [self.out[n - 2]]:
+                a, kw = self._raw_last_call(x)
+                why = K.x3_refusal(*a, **kw, **pk)
+                if why is None:
+                    a, kw = self._bwd_pair_call(n - 1, None if db_in_pass else l.db, dpre_last, x)
+                    why = K.x3_pair_refusal(*a, **kw, **pk)
+                if why is not None:
+                    break
         if why is not None:
             raise ValueError("matmul='bf16x%d': the decoder-heads layer (%d x %d, %d rows) cannot run on %s: %s"
                              % (parts, l.N, l.Kin, self.M, 'dv_gemm_x3' if parts == 3 else 'dv_gemm_split', why))
         self.x3_last, self.x3_parts = True, parts
 
-    def forward(self, inputs, resid=None, publish=None, heads=None, raw_last=False, x3=False):
+    def forward(self, inputs, resid=None, publish=None, heads=None, raw_last=False, x3=False, drop=False):
         """``publish`` = (flag, counter, add): the FIRST launch of the chain publishes on entry.
         ``raw_last``: the last layer's launch is the plain product x W^T -- bias, the second head's activation and its
         shift are left to the consumer (``K.nll_rows_fwdbwd(bias=...)``: chip-filling heads, plain GEMM epilogue);
         ``x3``: ... as a split-bf16 product (a chain that ``use_x3_last`` has accepted; ``backward(x3_last=True)`` goes with it).
         ``heads`` = dict(sample=...) | dict(nll=..., out=...): the dual-head last layer runs as ``K.linear_heads``
         with that row work fused into its epilogue (with ``nll`` the heads themselves are NOT stored: ``out``
-        receives their gradients)."""
+        receives their gradients).
+        ``drop``: a training pass of a chain with dropout sites (see the class docstring); else no site launches anything."""
         x = list(inputs)
+        drop = bool(drop and self.masks)
         assert not x3 or (self.x3_last and raw_last and heads is None), 'x3: a raw last layer that use_x3_last accepted'
         for li, l in enumerate(self.layers):
             if l.g is not None:
@@ -168,11 +196,15 @@ class _Chain:
                          act0=l.act0, act1=l.act1, shift0=l.shift0, shift1=l.shift1,
                          resid=resid if last else None, resid_cols=self.resid_cols if (last and resid is not None) else 0,
                          overread=True, publish=publish if (li == 0 and l.g is None) else None, kpad=kpad)
-            x = [self.out[li]]
+            if last:
+                break
+            if drop:
+                K.mask_scale(self.outd[li], self.out[li], self.masks[li], self.inv_keep)
+            x = [self._hidden(li, drop)]
         return self.out[-1]
 
     def backward(self, dpre_last, inputs, dinputs=None, publish_after_last=None, publish_first=None, db_last_done=False,
-                 klq=None, x3_last=False):
+                 klq=None, x3_last=False, drop=False):
         """dpre_last: gradient w.r.t. the last layer's pre-activation.  ``dinputs``: per input
         source a list of (dst, alpha, beta) destinations for its gradient (or None to skip).
         ``publish_after_last`` = (flag, counter, add):
@@ -183,8 +215,10 @@ class _Chain:
         ``x3_last``: the last layer's forward ran as a split-bf16 product (``forward(x3=True)``): so do its two gradient products.
         ``klq`` (see ``kernels.linear_bwd_pair``): the chain's input is a sample of q rows -- the FIRST layer's data-gradient
         launch writes d/d(mu | logvar) of those rows instead of d/d(input); returns True when the launch took it (a paired
-        first layer), else the caller runs the row pass itself."""
+        first layer), else the caller runs the row pass itself.
+        ``drop``: the forward pass ran with ``drop=True``: same masks, see the class docstring."""
         assert not x3_last or self.x3_last
+        drop = bool(drop and self.masks)
         dpre = dpre_last
         pending_pub = publish_first
         took_klq = False
@@ -192,7 +226,7 @@ class _Chain:
         for li in range(n_layers - 1, -1, -1):
             l = self.layers[li]
             db = None if (db_last_done and li == n_layers - 1) else l.db
-            srcs = list(inputs) if li == 0 else [self.out[li - 1]]
+            srcs = list(inputs) if li == 0 else [self._hidden(li - 1, drop)]
             if li == len(self.layers) - 2 and publish_after_last is not None:
                 pending_pub = publish_after_last
 
@@ -206,6 +240,10 @@ class _Chain:
                     a, kw = self._bwd_pair_call(li, db, dpre, srcs[0], pending_pub)
                     K.linear_bwd_pair(*a, **kw, **(self._x3_kw() if (x3_last and li == n_layers - 1) else {}))
                     dpre = self.dpre[li - 1]
+                    # (in place: ``dv_mask_scale`` reads and writes element i from thread i alone, so x == y is sound although its
+                    # kernel declares both ``__restrict__`` -- to be dropped there)
+                    if drop:     # (dpre . W) * act'(out) * mask / keep: the factors are elementwise and commute
+                        K.mask_scale(dpre, dpre, self.masks[li - 1], self.inv_keep)
                 else:
                     dst, alpha, beta = dinputs[0][0]
                     if klq is not None and beta == 0.0:
@@ -234,6 +272,8 @@ class _Chain:
                 K.linear_bwd_data(self.dpre[li - 1], dpre, l.W, kscale=l.scale, yref=self.out[li - 1], act=prev.act0,
                                   shift=prev.shift0, overread=True, npad=True)
                 dpre = self.dpre[li - 1]
+                if drop:
+                    K.mask_scale(dpre, dpre, self.masks[li - 1], self.inv_keep)
             elif dinputs is not None:
                 c0 = 0
                 for si, s in enumerate(srcs):

@@ -295,6 +295,70 @@ __global__ __launch_bounds__(256) void fill_normal_rows_kernel(float* __restrict
     }
 }
 
+// 10 rounds of Philox4x32 in place: the four output words of counter (c0..c3) under key (k0, k1)
+__device__ __forceinline__ void philox_words4(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0,
+                                              uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        philox_round(c0, c1, c2, c3, k0, k1);
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+
+// The noise arena of a step with hidden-layer dropout: rows [0, n_normal) of the table are the N(0,1) rows of
+// fill_normal_rows_kernel (same calls, same values); rows [n_normal, n_rows) are KEEP rows -- element (row, col) is 1.0f
+// where word col % 4 of the same Philox block (counter and key laid out as for the normals) is < keep_thr, else 0.0f:
+// an integer compare, no float uniform.  One wave per row, the row kind is wave-uniform.  (Reached through
+// dv_fill_normal_rows with n_rows < 0: the C ABI keeps its entry points.)
+__global__ __launch_bounds__(256) void fill_noise_rows_kernel(float* __restrict__ arena, const int4* __restrict__ desc,
+                                                              int n_rows, uint64_t seed, const int32_t* ctr_dev,
+                                                              dv_wait park) {
+    park_block(park);         // (the counter below is read behind the wait, as in fill_normal_rows_kernel)
+    // the trailer row behind the table: {number of keep rows at the table's END, keep_thr's bits, 0, 0} -- counted from the
+    // end, so that a caller may hand over the table from any of its rows on
+    const int4 tr = desc[n_rows];
+    // (device data the host cannot check: a count outside [0, n_rows] is clamped, never an index outside the table)
+    const int n_normal = n_rows - (tr.x < 0 ? 0 : tr.x > n_rows ? n_rows : tr.x);
+    const uint32_t keep_thr = (uint32_t)tr.y;
+    uint32_t step_lo = 0, step_hi = 0;
+    if (ctr_dev) {
+        step_lo = (uint32_t)ctr_dev[0];
+        step_hi = (uint32_t)ctr_dev[1];
+    }
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ step_hi;
+    const int lane = threadIdx.x & 63;
+    const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwave = gridDim.x * (blockDim.x >> 6);
+    for (int r = wave; r < n_rows; r += nwave) {
+        const int4 d = desc[r];
+        float* out = arena + d.x;
+        const int w = d.y, w4 = (w + 3) >> 2;
+        const bool al = ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
+        const bool keep_row = r >= n_normal;
+        for (int c = lane; c < w4; c += 64) {
+            float z[4];
+            if (keep_row) {
+                uint32_t c0 = (uint32_t)c, c1 = (uint32_t)d.w, c2 = (uint32_t)d.z, c3 = step_lo;
+                philox_words4(c0, c1, c2, c3, k0, k1);
+                z[0] = c0 < keep_thr ? 1.f : 0.f;
+                z[1] = c1 < keep_thr ? 1.f : 0.f;
+                z[2] = c2 < keep_thr ? 1.f : 0.f;
+                z[3] = c3 < keep_thr ? 1.f : 0.f;
+            } else {
+                philox_normal4((uint32_t)c, (uint32_t)d.w, (uint32_t)d.z, step_lo, k0, k1, z);
+            }
+            const int o = c << 2;
+            if (al && o + 4 <= w) {
+                *reinterpret_cast<float4*>(out + o) = make_float4(z[0], z[1], z[2], z[3]);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (o + e < w) out[o + e] = z[e];
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void fill_normal_kernel(float* __restrict__ out, int64_t n, uint64_t seed,
                                                           const int32_t* __restrict__ ctr_dev) {
     uint64_t base = 0;
@@ -483,9 +547,12 @@ extern "C" int dv_counters_add2(int32_t* c1, int32_t n1, int64_t inc1, int32_t* 
     DV_RETURN_LAUNCH();
 }
 
-extern "C" int dv_fill_normal_rows(float* arena, const int32_t* desc, int32_t n_rows, uint64_t seed,
+extern "C" int dv_fill_normal_rows(float* arena, const int32_t* desc, int32_t n_rows_in, uint64_t seed,
                                    const int32_t* ctr_dev, const dv_wait* park_in, dv_stream_t stream) {
-    DV_REQUIRE(n_rows >= 0);
+    // n_rows < 0: a table of -n_rows rows that ends in KEEP rows, followed by its trailer row (see the header)
+    const bool noise = n_rows_in < 0;
+    DV_REQUIRE(n_rows_in > INT32_MIN);
+    const int32_t n_rows = noise ? -n_rows_in : n_rows_in;
     dv_wait park = park_in ? *park_in : dv_wait{nullptr, nullptr, 0, 0, nullptr};
     DV_REQUIRE(park.flag == nullptr || (park.ctr && park.err && park.max_spins > 0));
     if (n_rows == 0) return park.flag ? DV_ERR_UNSUPPORTED : DV_OK;
@@ -493,6 +560,11 @@ extern "C" int dv_fill_normal_rows(float* arena, const int32_t* desc, int32_t n_
     int blocks = (n_rows + 3) / 4;
     if (blocks > 4096) blocks = 4096;
     if (park.flag != nullptr && blocks > 512) blocks = 512;      // a parked grid stays well below the chip's resident capacity
+    if (noise) {
+        hipLaunchKernelGGL(fill_noise_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, ST(stream), arena,
+                           reinterpret_cast<const int4*>(desc), n_rows, seed, ctr_dev, park);
+        DV_RETURN_LAUNCH();
+    }
     hipLaunchKernelGGL(fill_normal_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, ST(stream), arena,
                        reinterpret_cast<const int4*>(desc), n_rows, seed, ctr_dev, park);
     DV_RETURN_LAUNCH();

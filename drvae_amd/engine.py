@@ -92,10 +92,16 @@ class StepConfig:
     # of the rounded operands with fp32 accumulation (~2^-8: a different dtype, NOT held to the fp32 step's tolerances).
     # Decided once, where the plan is built
     matmul: str = 'fp32'
+    # hidden-layer dropout (``dropout_rate`` of the models' constructors, src/blocks.py:139-151): every hidden activation of
+    # every chain with at least two layers is a dropout SITE of a training pass (``_Chain.add_dropout``); the keep masks are
+    # drawn with the step's noise (``kernels.fill_noise_rows``).  0: no sites, the step as it ever was
+    dropout_rate: float = 0.0
 
     def __post_init__(self):
         if self.matmul not in MATMUL_CHOICES:
             raise ValueError('StepConfig.matmul must be one of %s, not %r' % (MATMUL_CHOICES, self.matmul))
+        if not 0.0 <= self.dropout_rate < 1.0:
+            raise ValueError('StepConfig.dropout_rate must lie in [0, 1), not %r' % (self.dropout_rate,))
 
     @property
     def cont(self):
@@ -334,6 +340,9 @@ class FusedStep(StepSchedule):
             key = key + (('n_tot', int(n_tot)),)
         if carry:
             key = key + ('carry_s',)
+        # nothing narrows the plan: every row may be a pair, labeled or not, counted over this slice
+        plain = nps == n_rows and lab == (0, 0) and n_tot is None and not carry
+        key = key + self._rate_key()
         if self.plan is None or self.plan.key != key:
             self.plan = self._plans.get(key)
             if self.plan is None:
@@ -342,12 +351,18 @@ class FusedStep(StepSchedule):
                 self.plan = self._plans[key] = _Plan(self, ar, ones if cfg.has_pert else zeros,
                                                       (ar >= lab[0]) & (ar < lab[1]),
                                                       None if n_tot is None else (int(n_tot), 0, 0), key, universal=True)
+                self.plan.every_row_anything = plain
                 if cfg.has_y:
                     self.plan.set_labels_host(np.zeros(n_rows, np.int64))      # class slots: static
                 if carry:
                     self.plan.carry_nuisance()
                 self._evict_plans(key)
         return self.plan
+
+    def _rate_key(self):
+        """what a plan key carries of the dropout rate: nothing at rate 0 (the keys of such plans stay what they were)"""
+        r = self.cfg.dropout_rate
+        return (('dropout', float(r)),) if r > 0 else ()
 
     def _evict_plans(self, keep):
         """keep the plan cache bounded (randomly composed minibatches rarely repeat a structure; whole-set
@@ -378,6 +393,7 @@ class FusedStep(StepSchedule):
         key = (len(rows), has_x2[rows].tobytes(), has_y[rows].tobytes(), counts, self.row0)
         if carry:
             key = key + ('carry_s',)
+        key = key + self._rate_key()
         if self.plan is None or self.plan.key != key:
             self.plan = self._plans.get(key)
             if self.plan is None:
@@ -487,18 +503,53 @@ class FusedStep(StepSchedule):
         if self._rec == 'main' and self._tail.noise_ahead:
             self._rng_pending = n         # dual-graph step: the side chain of the PREVIOUS step has drawn them
             return
-        desc = self.plan.noise_desc
+        lo = 0
         if not (self.training and self.add_noise and self.cfg.add_noise_var > 0):
             # no input noise in this pass (evaluation; ``fit(add_noise=False)``): its rows -- two thirds of the arena at
             # 978 genes -- are not drawn (whole-set evaluation of 8192 rows: 40 -> 15 us); a draw is keyed by (draw id,
             # global row), so the latent draws are the same numbers either way
-            desc = desc[self.plan.B + self.plan.Np:]
-        K.fill_normal_rows(self.plan.noise, desc, self.seed, self.rng_ctr)
+            lo = self.plan.B + self.plan.Np
+        # (an evaluation pass drops nothing: the keep rows at the table's end are not drawn either)
+        self._fill_noise(self.plan, lo, keeps=self.training)
         self._noise_stale = True          # (an eager draw: a later replay must draw for its own counter first)
         if bump:
             K.counter_add(self.rng_ctr, n)
         else:
             self._rng_pending = n
+
+    def _fill_noise(self, p, lo=0, keeps=True):
+        """the draw launch of plan ``p`` over the rows [lo, end) of its descriptor table: N(0,1) rows and, behind them, the
+        keep masks of its dropout sites (``keeps``; a plan without sites: the launch it always was)"""
+        if p.drop_sites and keeps:
+            K.fill_noise_rows(p.noise, p.noise_table[lo:], self.seed, self.rng_ctr)
+            p.masks_injected = False      # (drawn masks replace injected ones)
+        else:
+            K.fill_normal_rows(p.noise, p.noise_desc[lo:p.n_normal_rows], self.seed, self.rng_ctr)
+
+    @property
+    def _drop(self):
+        """does the pass being issued drop?  A training pass over a plan with sites; evaluation never does"""
+        return bool(self.training and self.plan.drop_sites)
+
+    def dropout_sites(self):
+        """the dropout sites of the current plan, in the order of their draws: dicts of ``chain`` (``'c_enc'`` ...), ``layer``
+        (the site is the INPUT of that layer, li >= 1), ``M``, ``N`` and ``mask``, the (M, N) keep-mask view in the noise arena"""
+        return [dict(s) for s in self.plan.drop_sites]
+
+    def set_dropout_masks(self, masks):
+        """Inject explicit keep masks (1.0 / 0.0), next to ``set_noise``: ``masks`` maps a site -- its index in
+        ``dropout_sites()`` or its (chain, layer) -- to an (M, N) array; every site must be given.  The masks HOLD: every
+        ``train_step(noise=...)`` and every forward / backward on this plan uses them and draws nothing, until something draws
+        keep rows again -- a ``train_step()`` without noise, ``draw_noise()`` in training mode, a replay of the captured step --
+        which overwrites them and ends the injection (a ``train_step(noise=...)`` after that draws fresh masks)."""
+        p = self.plan
+        index = {(s['chain'], s['layer']): i for i, s in enumerate(p.drop_sites)}
+        given = {(index[k] if not isinstance(k, (int, np.integer)) else int(k)): v for k, v in masks.items()}
+        assert sorted(given) == list(range(len(p.drop_sites))), 'set_dropout_masks: a mask for every site'
+        for i, v in given.items():
+            p.drop_sites[i]['mask'].copy_(torch.as_tensor(np.ascontiguousarray(v), dtype=torch.float32))
+        p.masks_injected = True
+        self._noise_stale = True
 
     # ---------------------------------------------------------------------- forward
     def _route(self):      # how the pass being issued runs its heads and its reconstruction rows
@@ -643,10 +694,11 @@ class FusedStep(StepSchedule):
             # ``dv_batch_feed``)
             Q = p.c_enc.forward(p.enc_in, heads=dict(sample=dict(
                 eps=p.E12, out=p.ZDEC[:p.o3], n_src=B, seg_ptr=p.zseg_ptr, seg_rows=p.zseg_rows,
-                out4=p.FPIN[:, :Z1] if r.fprop_from_heads else None, out4_ptr=p.fp_ptr_ext if r.fprop_from_heads else None)))
+                out4=p.FPIN[:, :Z1] if r.fprop_from_heads else None, out4_ptr=p.fp_ptr_ext if r.fprop_from_heads else None)),
+                drop=self._drop)
             Qmu, Qlv = Q[:, :Z1], Q[:, Z1:]
         else:
-            Q = p.c_enc.forward(p.enc_in)
+            Q = p.c_enc.forward(p.enc_in, drop=self._drop)
             Qmu, Qlv = Q[:, :Z1], Q[:, Z1:]
             K.reparam_fwd(p.ZDEC[:p.o3], Qmu, Qlv, p.E12, src_idx=p.z_src_idx)
         if cfg.has_pert:
@@ -657,9 +709,9 @@ class FusedStep(StepSchedule):
                 # z2Fz1 sample, the classifier input z2Fz1 - z1, and the decoder's copy for the pairs
                 p.c_z2F.forward([Z1blk], resid=Z1blk, publish=pub1, heads=dict(sample=dict(
                     eps=p.E2F, out=p.Z2F, n_src=L * B, sub=Z1blk, out2=p.D, out3=p.ZDEC if Np else None,
-                    out3_idx=p.pert_out_idx if Np else None)))
+                    out3_idx=p.pert_out_idx if Np else None)), drop=self._drop)
             else:
-                P2 = p.c_z2F.forward([Z1blk], resid=Z1blk, publish=pub1)
+                P2 = p.c_z2F.forward([Z1blk], resid=Z1blk, publish=pub1, drop=self._drop)
                 K.reparam_fwd(p.Z2F, P2[:, :Z1], P2[:, Z1:], p.E2F, sub=Z1blk, out2=p.D,
                               out3=p.ZDEC if Np else None, out3_idx=p.pert_out_idx if Np else None)
         return Qmu, Qlv
@@ -671,14 +723,14 @@ class FusedStep(StepSchedule):
         X, train = cfg.dim_x, self.fuse_bwd
         if r.nll == 'heads':   # train step: the heads' launch emits d/d(mu, pre-softplus) and the row sums' partials
             p.c_decx.forward(p.dec_in, publish=pub, heads=dict(out=p.DPX, nll=dict(
-                x=p.XIN, xidx=p.tgt, coef=p.c_nll, part=p.NLLP)))
+                x=p.XIN, xidx=p.tgt, coef=p.c_nll, part=p.NLLP)), drop=self._drop)
             return
         # ``raw_last``, chip-filling heads in a train step: the product runs with the plain epilogue, the NLL row pass behind it
         # adds the bias and applies softplus + shift on its way (wide configuration: 10.87 -> 9.97 ms for the launch)
         # ... and an EVALUATION pass over many rows (whole-set evaluation, round 5): the heads are needed for the row terms only
         # -- plain product, finished inside the row pass (32768 x 1956 x 600: 737 -> 589 us for the product, and no
         # 256 MB of finished heads written and read back)
-        PX = p.c_decx.forward(p.dec_in, publish=pub, raw_last=r.raw_last, x3=r.x3)
+        PX = p.c_decx.forward(p.dec_in, publish=pub, raw_last=r.raw_last, x3=r.x3, drop=self._drop)
         if self._tail.late_fork:      # (chip-filling step: the side chain starts HERE, next to the row pass below)
             self.branch.fork()
         lh = p.c_decx.layers[-1]
@@ -723,14 +775,14 @@ class FusedStep(StepSchedule):
                 clf_in = [Z1blk, p.D] if cfg.clf_z1z2 else [p.Z2F]
             else:
                 clf_in = [Z1blk]
-            QYm = p.c_clf.forward(clf_in)                         # sigmoid-constrained means
+            QYm = p.c_clf.forward(clf_in, drop=self._drop)                         # sigmoid-constrained means
             K.rows_gather(p.FPIN[:, :Z1], Z1blk, p.fp_src)
             K.ycont_fwd(p.YLrow, p.FPIN[:, Z1:], p.Z3IN[:, Z3:], QYm, p.ylab, p.has_y_i32, p.EY, Y_LOGVAR_CONT, B,
                         sqerr=cfg.kind == 'vfae')       # VFAE scores by squared error (src/VFAE.py:351)
-            Q3 = p.c_top.forward([p.FPIN])
+            Q3 = p.c_top.forward([p.FPIN], drop=self._drop)
             K.kl_rows_fwd(p.KL3, p.KL3raw, Q3[:, :Z3], Q3[:, Z3:], prior=(0.0, 0.0), free_bits=True,
                           kl_min=cfg.kl_min, eps=p.E3, zout=p.Z3IN[:, :Z3])
-            PZ1 = p.c_dz1.forward([p.Z3IN])
+            PZ1 = p.c_dz1.forward([p.Z3IN], drop=self._drop)
             K.kl_rows_fwd(p.KLDrow, p.KL1raw, Qmu, Qlv, PZ1[:, :Z1], PZ1[:, Z1:], qidx=p.fp_q, free_bits=True,
                           kl_min=cfg.kl_min, add=p.KL3)
             return
@@ -745,8 +797,8 @@ class FusedStep(StepSchedule):
                 if r.z3_in_heads:
                     # the z3 sample leaves the heads' launch of q(z3|z1,y); its KL term against N(0,I) (with its
                     # own free bits) is evaluated next to the z1 term below: one launch less
-                    Q3 = p.c_top.forward([p.FPIN], heads=dict(sample=dict(eps=p.E3, out=p.Z3IN[:, :Z3], n_src=p.Mf)))
-                    PZ1 = p.c_dz1.forward([p.Z3IN])
+                    Q3 = p.c_top.forward([p.FPIN], heads=dict(sample=dict(eps=p.E3, out=p.Z3IN[:, :Z3], n_src=p.Mf)), drop=self._drop)
+                    PZ1 = p.c_dz1.forward([p.Z3IN], drop=self._drop)
                     # KLFP = max(KL(q(z1|x)||p(z1|z3,y)), kl_min) + max(KL(q(z3|.)||N(0,I)), kl_min)  (src/DrVAE.py:347,358)
                     # -- in the train step inside the classifier-head launch below (``fprop_tail``)
                     if not r.fprop_tail:
@@ -754,11 +806,11 @@ class FusedStep(StepSchedule):
                                       free_bits=True, kl_min=cfg.kl_min, prior=(0.0, 0.0),
                                       second=(Q3[:, :Z3], Q3[:, Z3:], p.KL3raw))
                 else:
-                    Q3 = p.c_top.forward([p.FPIN])
+                    Q3 = p.c_top.forward([p.FPIN], drop=self._drop)
                     # KL(q(z3|z1,y)||N(0,I)) with free bits + the z3 sample, one row pass
                     K.kl_rows_fwd(p.KL3, p.KL3raw, Q3[:, :Z3], Q3[:, Z3:], prior=(0.0, 0.0), free_bits=True,
                                   kl_min=cfg.kl_min, eps=p.E3, zout=p.Z3IN[:, :Z3])
-                    PZ1 = p.c_dz1.forward([p.Z3IN])
+                    PZ1 = p.c_dz1.forward([p.Z3IN], drop=self._drop)
                     # KLFP = max(KL(q(z1|x)||p(z1|z3,y)), kl_min) + the z3 term   (src/DrVAE.py:347,358)
                     K.kl_rows_fwd(p.KLFP, p.KL1raw, Qmu, Qlv, PZ1[:, :Z1], PZ1[:, Z1:], qidx=p.fp_q, free_bits=True,
                                   kl_min=cfg.kl_min, add=p.KL3)
@@ -796,7 +848,7 @@ class FusedStep(StepSchedule):
                 K.smalln_fwd(p.QY, None, clf_in[0], lc.W, lc.b, clf_in[1] if len(clf_in) > 1 else None,
                              ymarg=ym if self.fuse_bwd else None, park=mid_park if clf_park else None, fprop_kl=fk)
             else:
-                K.softmax_clamp_fwd(p.QY, p.c_clf.forward(clf_in), sigmoid1=cfg.clf_1sig)
+                K.softmax_clamp_fwd(p.QY, p.c_clf.forward(clf_in, drop=self._drop), sigmoid1=cfg.clf_1sig)
             if not self.fuse_bwd:
                 K.ymarg_fwd(p.YLrow, p.KLDrow, p.QY, p.label_r, p.fp_ptr, p.KLFP, p.log_prior)
             elif not self.clf_small:    # train step: CFP / DQY of the backward pass come out of the same launch (clf_small: ``ymarg`` above)
@@ -1012,7 +1064,7 @@ class FusedStep(StepSchedule):
             self.branch._forked = True       # one fork/join per step: the side chain simply continues
         p.c_decx.backward(p.DPX, p.dec_in, [[(p.DZDEC, 1.0, 0.0)]] + [None] * (len(p.dec_in) - 1),
                           publish_after_last=self.sync.pub('rows', self.step_dev) if t.side_loss else None,
-                          db_last_done=r.db_done, x3_last=r.x3)
+                          db_last_done=r.db_done, x3_last=r.x3, drop=self._drop)
         if p.DZMMD is not None:
             # model-level MMD penalty (use_s extension): its gradient w.r.t. the z1 / z2 samples was computed in
             # forward() through the block-level MMD kernels (see ``_mmd_penalty``)
@@ -1046,7 +1098,7 @@ class FusedStep(StepSchedule):
                            p.DZ1B if cfg.has_y else None, L, B, Np, park=park,
                            prior=(p.c_klp[B:], p.KLPraw[B:]) if (cfg.kind == 'pvae' and Np) else None)
             # perturbation function: mu = z1 + z1 W^T + b, logvar head
-            p.c_z2F.backward(p.DP2, [Z1blk], [[(DZ1, 1.0, 1.0)]])
+            p.c_z2F.backward(p.DP2, [Z1blk], [[(DZ1, 1.0, 1.0)]], drop=self._drop)
         # (VFAE: the side chain's share of d/dz1 is a second source of the sample backward below, no summing launch of
         # its own.  The join stays the one-workgroup launch above: VFAE's side chain is the longer one, and 59 parked
         # workgroups polling for it slow the very chain they wait for -- cfg 4 0.164 -> 0.170 ms)
@@ -1062,7 +1114,7 @@ class FusedStep(StepSchedule):
                           # of a dv_kl_rows_bwd launch behind them (cfg 1: one launch less on the critical chain)
                           prior=(p.c_klp, p.KLPraw, cfg.kl_min, Qmu) if cfg.kind == 'pvae' else None)
         p.c_enc.backward(DQ, p.enc_in, None,
-                         publish_first=self.sync.pub('noise', self.step_dev, 0) if t.noise_ahead else None)
+                         publish_first=self.sync.pub('noise', self.step_dev, 0) if t.noise_ahead else None, drop=self._drop)
 
     def _side_backward(self, Qmu, Qlv, Z1blk, r, late, leaf):
         """the side chain's share of the backward pass: y-marginalisation, fprop blocks, classifier -> ``DZ1B`` (its share
@@ -1086,20 +1138,21 @@ class FusedStep(StepSchedule):
                         p.DZ3IN[:, Z3:], B, sqerr=cfg.kind == 'vfae')     # cfp[r] = c_kld[r]: one fprop row per row
             K.kl_rows_bwd(p.DQFP[:, :Z1], p.DQFP[:, Z1:], p.DPZ1[:, :Z1], p.DPZ1[:, Z1:], p.CFP, p.KL1raw,
                           Qmu, Qlv, PZ1[:, :Z1], PZ1[:, Z1:], qidx=p.fp_q, free_bits=True, kl_min=cfg.kl_min)
-            p.c_dz1.backward(p.DPZ1, [p.Z3IN], [[(p.DZ3IN, 1.0, 0.0)]])
+            p.c_dz1.backward(p.DPZ1, [p.Z3IN], [[(p.DZ3IN, 1.0, 0.0)]], drop=self._drop)
             K.kl_rows_bwd(p.DQ3[:, :Z3], p.DQ3[:, Z3:], None, None, p.CFP, p.KL3raw, Q3[:, :Z3], Q3[:, Z3:],
                           prior=(0.0, 0.0), free_bits=True, kl_min=cfg.kl_min, dz=p.DZ3IN[:, :Z3], eps=p.E3)
-            p.c_top.backward(p.DQ3, [p.FPIN], [[(p.DFPIN, 1.0, 0.0)]])
+            p.c_top.backward(p.DQ3, [p.FPIN], [[(p.DFPIN, 1.0, 0.0)]], drop=self._drop)
             K.rows_segment_sum(p.DZ1B, p.DFPIN, seg_ptr=p.fp_ptr, beta=0.0, width=Z1)
             # the y columns of both fprop inputs carry d/d(y sample); labeled rows: the log-likelihood
             K.ycont_bwd(p.DLOG, None, QYm, p.ylab, p.has_y_i32, Y_LOGVAR_CONT, p.c_yl, p.c_kld, p.DFPIN[:, Z1:],
                         p.DZ3IN[:, Z3:], B, sqerr=cfg.kind == 'vfae')
             if cfg.kind == 'drvae' and cfg.clf_z1z2:
-                p.c_clf.backward(p.DLOG, [Z1blk, p.D], [[(p.DZ1B, 1.0, 1.0)], [(p.DZ2F, 1.0, 0.0), (p.DZ1B, -1.0, 1.0)]])
+                p.c_clf.backward(p.DLOG, [Z1blk, p.D], [[(p.DZ1B, 1.0, 1.0)], [(p.DZ2F, 1.0, 0.0), (p.DZ1B, -1.0, 1.0)]],
+                                 drop=self._drop)
             elif cfg.kind == 'drvae':
-                p.c_clf.backward(p.DLOG, [p.Z2F], [[(p.DZ2F, 1.0, 0.0)]])
+                p.c_clf.backward(p.DLOG, [p.Z2F], [[(p.DZ2F, 1.0, 0.0)]], drop=self._drop)
             else:
-                p.c_clf.backward(p.DLOG, [Z1blk], [[(p.DZ1B, 1.0, 1.0)]])
+                p.c_clf.backward(p.DLOG, [Z1blk], [[(p.DZ1B, 1.0, 1.0)]], drop=self._drop)
         elif cfg.has_y:
             Y = cfg.dim_y
             if not self.fuse_bwd:
@@ -1117,10 +1170,10 @@ class FusedStep(StepSchedule):
                 # else a row pass behind it
                 klq = dict(out=p.DQ3, q=Q3, eps=p.E3, coef=p.CFP, raw=p.KL3raw, kl_min=cfg.kl_min, Z=Z3) \
                     if self.fuse_bwd else None
-                if not p.c_dz1.backward(p.DPZ1, [p.Z3IN], [[(p.DZ3IN, 1.0, 0.0)]], klq=klq):
+                if not p.c_dz1.backward(p.DPZ1, [p.Z3IN], [[(p.DZ3IN, 1.0, 0.0)]], klq=klq, drop=self._drop):
                     K.kl_rows_bwd(p.DQ3[:, :Z3], p.DQ3[:, Z3:], None, None, p.CFP, p.KL3raw, Q3[:, :Z3], Q3[:, Z3:],
                                   prior=(0.0, 0.0), free_bits=True, kl_min=cfg.kl_min, dz=p.DZ3IN[:, :Z3], eps=p.E3)
-                p.c_top.backward(p.DQ3, [p.FPIN], [[(p.DFPIN, 1.0, 0.0)]])
+                p.c_top.backward(p.DQ3, [p.FPIN], [[(p.DFPIN, 1.0, 0.0)]], drop=self._drop)
                 # z1 feeds one (labeled) or Y (unlabeled) fprop rows: their d/dz1 is summed per z1 row -- inside
                 # the classifier's data-gradient launch where that launch writes DZ1B anyway, else on its own
                 seg_in_clf = self.clf_small and not (cfg.kind == 'drvae' and not cfg.clf_z1z2)
@@ -1148,13 +1201,13 @@ class FusedStep(StepSchedule):
                 K.softmax_clamp_bwd(p.DLOG, p.DQY, p.QY, sigmoid1=cfg.clf_1sig)
                 if two:
                     p.c_clf.backward(p.DLOG, [Z1blk, p.D],
-                                     [[(p.DZ1B, 1.0, b1)], [(p.DZ2F, 1.0, 0.0), (p.DZ1B, -1.0, 1.0)]])
+                                     [[(p.DZ1B, 1.0, b1)], [(p.DZ2F, 1.0, 0.0), (p.DZ1B, -1.0, 1.0)]], drop=self._drop)
                 elif cfg.kind == 'drvae':
-                    p.c_clf.backward(p.DLOG, [p.Z2F], [[(p.DZ2F, 1.0, 0.0)]])
+                    p.c_clf.backward(p.DLOG, [p.Z2F], [[(p.DZ2F, 1.0, 0.0)]], drop=self._drop)
                     if not p.Mf:
                         p.DZ1B.zero_()
                 else:
-                    p.c_clf.backward(p.DLOG, [Z1blk], [[(p.DZ1B, 1.0, b1)]])
+                    p.c_clf.backward(p.DLOG, [Z1blk], [[(p.DZ1B, 1.0, b1)]], drop=self._drop)
 
     def _side_graph_tail(self, leaf):
         """(dual-graph schedule) what the side chain's graph runs behind its backward pass: publish its data gradients, the
@@ -1185,7 +1238,7 @@ class FusedStep(StepSchedule):
             # (A park of the draw launch itself instead of the wait launch was measured slower: 356
             # workgroups polling one flag, +10 us/step)
             K.flag_wait(*sync.wait('noise', ctr))
-            K.fill_normal_rows(p.noise, p.noise_desc, self.seed, self.rng_ctr)
+            self._fill_noise(p)
         # ... and now the side chain's late work is final: published by the counter launch on entry
         K.counters_add2(ctr, 1, self.side_t, 1, publish=sync.pub('tail', ctr) if (t.late or t.cap_fork) else None)
 
@@ -1231,6 +1284,11 @@ class FusedStep(StepSchedule):
         self.join_side()
         if noise is not None:
             self.set_noise(noise)
+            if self.plan.drop_sites and not self.plan.masks_injected:
+                # injected noise, no injected masks: the keep rows alone are drawn (their own draw event)
+                p = self.plan
+                K.fill_noise_rows(p.noise, p.noise_table[p.n_normal_rows:], self.seed, self.rng_ctr)
+                self._rng_pending = 1
         else:
             self.draw_noise(bump=False)
         self._launch_sequence(allreduce=allreduce, draw=False)

@@ -7,6 +7,7 @@ row-strided views (``stride(1) == 1``); the row stride is passed as the leading
 dimension.  There is no CPU path here: tensors must live on the GPU.
 """
 import ctypes as C
+import math
 import os
 from typing import Any, NamedTuple, Optional
 
@@ -1139,6 +1140,30 @@ def fill_normal_rows(arena, desc, seed, ctr_dev=None, park=None):
     assert arena.is_contiguous() and desc.dim() == 2 and desc.shape[1] == 4
     _lib.check(_lib.load().dv_fill_normal_rows(_f32(arena), _i32(desc), desc.shape[0], seed, _i32(ctr_dev), _wait(park),
                                                _stream()), 'dv_fill_normal_rows')
+
+
+def keep_threshold(dropout_rate):
+    """``keep_thr`` of the keep rows (``dv_fill_normal_rows``, n_rows < 0): floor((1 - dropout_rate) * 2^32) in double, as
+    uint32; the keep probability of a hidden unit is exactly ``keep_threshold(rate) / 2**32``"""
+    assert 0.0 <= dropout_rate < 1.0
+    return min(int(math.floor((1.0 - float(dropout_rate)) * 4294967296.0)), 0xFFFFFFFF)
+
+
+def noise_table(desc, n_normal, keep_thr):
+    """the table ``fill_noise_rows`` takes: the (R, 4) descriptor rows ``desc`` -- N(0,1) rows [0, n_normal), KEEP rows behind
+    them -- plus the trailer row {number of keep rows, keep_thr's bits, 0, 0}; any ``table[lo:]`` is such a table too"""
+    assert desc.dim() == 2 and desc.shape[1] == 4 and 0 <= n_normal <= desc.shape[0] and 0 <= keep_thr <= 0xFFFFFFFF
+    thr = keep_thr - (1 << 32) if keep_thr >= (1 << 31) else keep_thr
+    tr = torch.tensor([[desc.shape[0] - n_normal, thr, 0, 0]], dtype=torch.int32, device=desc.device)
+    return torch.cat([desc.to(torch.int32), tr])
+
+
+def fill_noise_rows(arena, table, seed, ctr_dev=None, park=None):
+    """``fill_normal_rows`` over a ``noise_table``: the same N(0,1) values in its normal rows, 1.0 / 0.0 keep masks with keep
+    probability ``keep_thr / 2**32`` in its keep rows -- ``dv_fill_normal_rows`` with n_rows < 0, a kernel of its own"""
+    assert arena.is_contiguous() and table.dim() == 2 and table.shape[1] == 4 and table.shape[0] >= 1 and table.is_contiguous()
+    _lib.check(_lib.load().dv_fill_normal_rows(_f32(arena), _i32(table), -(table.shape[0] - 1), seed, _i32(ctr_dev), _wait(park),
+                                               _stream()), 'dv_fill_normal_rows (keep rows)')
 
 
 def fill_normal(out, seed, ctr_dev=None):

@@ -107,6 +107,13 @@ class _Plan:
             sizes.append(self.Mf * Z3)
             if cfg.cont:
                 sizes.append(L * B * Y)                      # eps of the y samples (unlabeled rows use them)
+        # hidden-layer dropout (``cfg.dropout_rate`` > 0): a SITE is the input of layer li >= 1 of a chain -- a hidden
+        # activation -- on the chain's stacked rows.  Its keep mask is one more segment of the noise arena, BEHIND every
+        # segment of the normal draws (their offsets do not move), drawn by the same launch (``kernels.fill_noise_rows``)
+        grow = int(eng.row0) + np.asarray(rows, np.int64)
+        stacks = self._drop_stacks(eng, grow) if cfg.dropout_rate > 0 else []
+        n_normal = int(sum(sizes))
+        sizes = sizes + [len(g) * lay[li].N for _, lay, g, _, _ in stacks for li in range(len(lay) - 1)]
         self.noise = zf(int(sum(sizes)))
         views, o = [], 0
         for s in sizes:
@@ -124,7 +131,6 @@ class _Plan:
         # noise, then per sample l: z1, z2, z2Fz1 eps, then z3 eps per (l, class)) and by the row's position in
         # the GLOBAL minibatch (``eng.row0`` + position in this rank's shard), never by where it sits in a
         # buffer: the values do not depend on grouping, stacking or the number of ranks
-        grow = int(eng.row0) + np.asarray(rows, np.int64)
         desc, off = [], 0
 
         def seg(n_rows, width, draw, g):
@@ -145,13 +151,31 @@ class _Plan:
             seg(self.Mf, Z3, 2 + 3 * L + self.fp_l_host * Y + self.fp_slot_host, grow[self.fp_i_host])
             if cfg.cont:
                 seg(L * B, Y, 2 + 3 * L + L * Y + lB, np.tile(grow, L))
+        assert off == n_normal
+        self.n_normal_rows = int(sum(len(d) for d in desc))
+        # keep rows: draw ids one past the largest normal draw id this CONFIGURATION can hold (not this batch structure: a
+        # mask value is a function of (site, replica, global row), whatever plan and whichever rank it is drawn in), one
+        # per (site, replica of the global row within the chain's row stack)
+        self.keep = 1.0 - cfg.dropout_rate
+        self.keep_thr = K.keep_threshold(cfg.dropout_rate)
+        self.drop_sites, self.masks_injected = [], False
+        draw = 2 + 3 * L + (L * Y + L if cfg.has_y else 0)
+        for name, lay, g, rep, n_rep in stacks:
+            for li in range(len(lay) - 1):
+                N, M = lay[li].N, len(g)
+                self.drop_sites.append(dict(chain=name, layer=li + 1, M=M, N=N, mask=self.noise[off:off + M * N].view(M, N),
+                                            draw0=draw))
+                seg(M, N, draw + rep, g)
+                draw += n_rep
         assert off == self.noise.numel() and off < 2 ** 31
-        self.noise_desc = i32(np.concatenate(desc) if desc else np.zeros((0, 4)))
+        # (the rows and, behind them, the trailer row the keep rows' kernel reads: ``kernels.noise_table``)
+        self.noise_table = K.noise_table(i32(np.concatenate(desc) if desc else np.zeros((0, 4))), self.n_normal_rows, self.keep_thr)
+        self.noise_desc = self.noise_table[:-1]
         # ---- activations / gradients
         self.XIN = mat(Me, X)
         self.ZDEC, self.DZDEC = mat(Md, Z1), mat(Md, Z1)
-        self.c_enc = _Chain(eng.L_enc, Me, dev)
-        self.c_decx = _Chain(eng.L_decx, Md, dev)
+        self.c_enc = self._sited('c_enc', _Chain(eng.L_enc, Me, dev))
+        self.c_decx = self._sited('c_decx', _Chain(eng.L_decx, Md, dev))
         self.enc_in, self.dec_in = [self.XIN], [self.ZDEC]
         self.DZMMD = None
         if cfg.use_s:
@@ -197,7 +221,7 @@ class _Plan:
             self.KLP, self.KLPraw = zf(Me), zf(Me)
         if cfg.has_y:
             R, Mf = L * B, self.Mf
-            self.c_clf = _Chain(eng.L_clf, R, dev)
+            self.c_clf = self._sited('c_clf', _Chain(eng.L_clf, R, dev))
             self.QY, self.DQY, self.DLOG = zf(R, Y), zf(R, Y), zf(R, 1 if cfg.clf_1sig else Y)
             # many classifier rows (wide configuration: 4096): the single-Linear head's weight gradient splits its rows over
             # workgroups through this workspace (``kernels.smalln_bwd_weight(ws=...)``)
@@ -208,8 +232,8 @@ class _Plan:
                 torch.log(torch.tensor(cfg.prior_y, dtype=torch.float64)).float().to(dev)
             self.DZ1B = mat(R, Z1)
             self.YLrow, self.KLDrow = zf(R), zf(R)
-            self.c_top = _Chain(eng.L_top, Mf, dev)
-            self.c_dz1 = _Chain(eng.L_dz1, Mf, dev)
+            self.c_top = self._sited('c_top', _Chain(eng.L_top, Mf, dev))
+            self.c_dz1 = self._sited('c_dz1', _Chain(eng.L_dz1, Mf, dev))
             self.FPIN, self.DFPIN = mat(Mf, Z1 + Y), mat(Mf, Z1 + Y)
             self.Z3IN, self.DZ3IN = mat(Mf, Z3 + Y), mat(Mf, Z3 + Y)
             self.DQ3, self.DPZ1, self.DQFP = zf(Mf, 2 * Z3), zf(Mf, 2 * Z1), zf(Mf, 2 * Z1)
@@ -246,6 +270,30 @@ class _Plan:
         self.feed_active = False   # ... and whether it is the source of the NEXT train step: explicit data
         #                            (FusedStep.set_batch, DeviceBatcher.feed) switches it off, begin_epoch on
 
+    def _drop_stacks(self, eng, grow):
+        """the row stacks of the chains that can hold dropout sites (two layers or more; the one-layer perturbation function
+        never does): (chain, layers, global row of every stacked row, replica of that global row within the stack, number of
+        replicas the configuration allows) in a fixed order -- the L samples, the class slots, the z1 | z2 | z2Fz1 blocks of
+        the decoder are replicas: every one gets a draw id of its own"""
+        cfg, L, Y, B, Np, ph = eng.cfg, eng.cfg.L, eng.cfg.dim_y, self.B, self.Np, self.pair_host
+        lB, lN = np.repeat(np.arange(L), B), np.repeat(np.arange(L), Np)
+        out = [('c_enc', eng.L_enc, np.concatenate([grow, grow[ph]]),
+                np.concatenate([np.zeros(B, np.int64), np.ones(Np, np.int64)]), 2),
+               ('c_decx', eng.L_decx, np.concatenate([np.tile(grow, L), np.tile(grow[ph], L), np.tile(grow[ph], L)]),
+                np.concatenate([lB, L + lN, 2 * L + lN]), 3 * L)]
+        if cfg.has_y:
+            gf, rf = grow[self.fp_i_host], self.fp_l_host * Y + self.fp_slot_host
+            out += [('c_clf', eng.L_clf, np.tile(grow, L), lB, L), ('c_top', eng.L_top, gf, rf, L * Y),
+                    ('c_dz1', eng.L_dz1, gf, rf, L * Y)]
+        return out
+
+    def _sited(self, name, chain):
+        """``chain`` with the dropout sites of this plan that lie on it (none at rate 0)"""
+        masks = [s['mask'] for s in self.drop_sites if s['chain'] == name]
+        if masks:
+            chain.add_dropout(masks, self.keep)
+        return chain
+
     @property
     def live_feed(self):
         """the installed epoch feed if it is the current input source, else None (inputs come from XSRC)"""
@@ -255,6 +303,9 @@ class _Plan:
     # ``set_s_device`` or by the epoch feed's dv_nuisance_feed launch -- and the MMD penalty reads them inside its two
     # grouped launches: nothing of such a plan depends on the batch's composition of classes
     carry_s = False
+    # (universal plan) nothing narrows it -- no pair slots, no labeled range, no global counts, no carried classes: the worst-case
+    # rows of the every-row-may-be-anything plan, which ``schedule._step_tail`` schedules differently from the bucketed ones
+    every_row_anything = False
     mmd_grouped = None
     mmd_masked = None       # (universal plan) the same penalty with the batch's data groups read as data: dv_mmd_masked_*
 

@@ -350,7 +350,7 @@ class StepSchedule:
         # the side chain parks ~13 us per step behind it -- sampler feed 0.250 -> 0.248 ms with the rows on the side chain;
         # that is the every-row-may-be-anything plan: the bucketed ones are close to a structure plan's rows and keep the
         # rows on the main chain, sampler feed 0.2181 -> 0.2140 ms in a same-box A/B)
-        klz2_on_main = not cfg.cont and cfg.has_y and not (p.universal and len(p.key) <= 3)
+        klz2_on_main = not cfg.cont and cfg.has_y and not p.every_row_anything
         # the join rides on its first consumer
         # (only where the join does not wait: every workgroup of the consumer polls the flag, and a long wait -- VFAE:
         # its side chain is the longer one, 30 us/step -- slows the very chain it waits for: 0.184 -> 0.208 ms)
@@ -359,8 +359,12 @@ class StepSchedule:
         fold_join = side_loss and cfg.has_pert and (p.B * cfg.dim_z1 + 255) // 256 <= 256
         # (noise drawn ahead under a CAPTURED exchange too: the side chain then draws behind the join and sweeps its half
         # behind the collective)
+        # ... but not over a plan with dropout sites: the next step's draw is released when the encoder backward STARTS --
+        # nothing behind that point reads the arena -- and with sites the encoder backward itself reads its keep masks there.
+        # Such a step draws at its head, as under ``sched=3`` (no second arena in this round)
+        noise_ahead = bool((late or cap_fork) and not p.drop_sites)
         return Tail(dual=True, late=late, adam_gated=late and not split_kind, side_adam=side_adam, hs=hs, side_loss=side_loss,
-                    cap_fork=cap_fork, tail_gated=tail_gated, noise_ahead=late or cap_fork, klz2_on_main=klz2_on_main,
+                    cap_fork=cap_fork, tail_gated=tail_gated, noise_ahead=noise_ahead, klz2_on_main=klz2_on_main,
                     fold_join=fold_join)
 
     @contextlib.contextmanager
@@ -689,8 +693,9 @@ class StepSchedule:
         assert self._graph_mmd_sig == getattr(self.plan, 'mmd_sig', None), \
             'use_MMD: the nuisance classes of the batch changed (the penalty compares row sets): capture again'
         self.plan.set_beta(self.beta_pert())      # 0.01 on iteration 0, 1.0 afterwards (device-side coefficients)
+        self.plan.masks_injected = False          # (the captured step draws its own keep masks)
         if self.noise_ahead and self._noise_stale:        # first replay (or an eager draw since): this step's noise
-            K.fill_normal_rows(self.plan.noise, self.plan.noise_desc, self.seed, self.rng_ctr)
+            self._fill_noise(self.plan)
             self._noise_stale = False
         # the main chain's graph goes first (the host needs ~60 us per graph launch: with the side chain's graph launched first --
         # it only parks on the z1 flag -- the step's first kernels started a launch later whenever the device had run dry: after a

@@ -1098,10 +1098,21 @@ int dv_fill_normal(float* out, int64_t n, uint64_t seed, const int32_t* ctr_dev,
  * row} (int32 x 4, 16-B aligned); element (row, col) = Philox(key = seed (^ ctr_dev[1] in the high word),
  * counter = (col/4, global row, draw id, ctr_dev[0]))[col % 4] through Box-Muller.  ctr_dev counts draw
  * EVENTS (one per train step: advance it by 1), so every rank holds the same value; a rank that owns rows
- * [rB, (r+1)B) of the global minibatch draws exactly the values a single process would draw for them. */
+ * [rB, (r+1)B) of the global minibatch draws exactly the values a single process would draw for them.
+ * n_rows < 0 (hidden-layer dropout of the train step): the table has -n_rows rows and ENDS in KEEP rows; one more row
+ * behind it, the trailer {n_keep, keep_thr (the uint32's bits), 0, 0}, says how many (counted from the table's end, so the
+ * table may be handed over from any row on).  The rows in front of the keep rows are written exactly as above, bit for bit
+ * (another kernel; a call with n_rows >= 0 launches what it always did).  Element (row, col) of a keep row is 1.0f if word
+ * col % 4 of Philox4x32-10(counter = (col/4, global row, draw id, ctr_dev[0]), key = (seed_lo, seed_hi ^ ctr_dev[1])) --
+ * counter and key laid out as for the normals -- is < keep_thr (unsigned compare), else 0.0f.  keep_thr =
+ * floor((1 - dropout_rate) * 2^32) as uint32, computed by the HOST in double: the keep probability is exactly
+ * keep_thr / 2^32, no float uniform is involved (tests/philox_ref.py reproduces a mask exactly).  Same launch shape, same
+ * `park`; the counter is read behind the wait.  (A form of this entry point, not one of its own: the ABI keeps its 80.)
+ * The trailer is DEVICE memory: the host cannot validate it.  The kernel clamps n_keep to [0, -n_rows]; a wrong count or
+ * threshold inside that range draws rows of the wrong kind, it writes nothing outside the described elements.  (Before this
+ * form existed a negative n_rows was DV_ERR_ARG; INT32_MIN still is.) */
 int dv_fill_normal_rows(float* arena, const int32_t* desc, int32_t n_rows, uint64_t seed, const int32_t* ctr_dev,
                         const dv_wait* park, dv_stream_t stream);
-
 #ifdef __cplusplus
 }
 #endif
