@@ -83,7 +83,8 @@ class DeepGenerativeModelMixin:
         if active and broadcast:
             eng = self.engine()
             eng.join_side()
-            for t in (eng.arena.param, eng.arena.exp_avg, eng.arena.exp_avg_sq, eng.step_dev, eng.rng_ctr):
+            for t in (eng.arena.param, eng.arena.exp_avg, eng.arena.exp_avg_sq, eng.step_dev, eng.rng_ctr) + \
+                    ((eng.clip_rec,) if eng.clip_rec is not None else ()):
                 D.broadcast(t)
             eng.sync_side_counters()
             self.finished_training_iters = int(D.broadcast_int(self.finished_training_iters))
@@ -113,6 +114,11 @@ class DeepGenerativeModelMixin:
             self._restore_optimizer_state()
         return self._engine
 
+    def grad_clip_stats(self):
+        """dict(norm, coef, skipped_last, n_skipped) of the last train step of a model built with ``max_grad_norm``
+        (``FusedStep.clip_stats``): one small device->host copy"""
+        return self.engine().clip_stats()
+
     # ---- the nn.Parameters ALIAS the arena; anything that swaps ``prm.data`` (``.to()``, ``.cpu()``,
     # ``load_state_dict(assign=True)``) would leave the fused step training a buffer nobody reads
     def _arena_aliased(self):
@@ -129,6 +135,8 @@ class DeepGenerativeModelMixin:
         self._opt_stash = dict(exp_avg=a.exp_avg.detach().cpu().clone(), exp_avg_sq=a.exp_avg_sq.detach().cpu().clone(),
                                step=eng.step_dev.cpu().clone(), rng=eng.rng_ctr.cpu().clone(), iters=eng.iters,
                                offsets=dict(a.offsets))
+        if eng.clip_rec is not None:      # the bias corrections count step - n_skipped: the two travel together
+            self._opt_stash['n_skipped'] = int(eng.clip_rec[3])
 
     def _restore_optimizer_state(self):
         st = getattr(self, '_opt_stash', None)
@@ -140,6 +148,8 @@ class DeepGenerativeModelMixin:
         a.exp_avg_sq.copy_(st['exp_avg_sq'])
         eng.step_dev.copy_(st['step'])
         eng.rng_ctr.copy_(st['rng'])
+        if eng.clip_rec is not None:
+            eng.clip_rec[3] = int(st.get('n_skipped', 0))
         eng.sync_side_counters()
         eng.iters = st['iters']
         self._opt_stash = None

@@ -14,7 +14,12 @@ class DrVAE(ELBOModel):
     the block-level path and the reference, named by one warning at construction: the two heads of a block share ONE keep
     mask (each head's marginal is the reference's, the joint is not), and a block without a hidden layer -- always
     ``decoder_z2Fz1``, whose log-variance head alone the reference drops -- is not dropped at all.
-    ``dropout_rate`` >= 1 raises ``ValueError``."""
+    ``dropout_rate`` >= 1 raises ``ValueError``.
+    ``max_grad_norm`` (default None: off) clips the global 2-norm of the gradient inside the fused step, with the semantics of
+    ``torch.nn.utils.clip_grad_norm_`` in front of the optimiser, and guards it: a step whose gradient holds an inf or a NaN
+    is skipped -- parameters and optimiser state stay as they are, ``grad_clip_stats()['n_skipped']`` counts it, ``fit`` warns
+    once per epoch in which it happened.  ``float('inf')`` keeps the guard and clips nothing.  A clipped step gives up the
+    side chain's share of the optimiser sweep.  0, a negative number or NaN raise ``ValueError``."""
     kind = 'drvae'
 
     def __init__(self, dim_x, dim_s, dim_y, dim_c=1, dim_m=1, dim_h_en_z1=(50, 50), dim_h_de_z1=(50, 50),
@@ -25,7 +30,8 @@ class DrVAE(ELBOModel):
                  yloss_rate=1., anneal_yloss_offset=0, use_MMD=True, kernel_MMD='rbf_fourier', mmd_rate=1.,
                  kl_qz2pz2_rate=1., pertloss_rate=0.1, anneal_perturb_rate_itermax=1,
                  anneal_perturb_rate_offset=0, use_s=False, use_c=False, use_m=False, random_seed=12345,
-                 log_txt=None, weight_norm=False, device=None, matmul_precision='fp32'):
+                 log_txt=None, weight_norm=False, device=None, matmul_precision='fp32',
+                 max_grad_norm=None):
         super().__init__()
         args = dict(locals())
         args.pop('self')

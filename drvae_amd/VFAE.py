@@ -9,7 +9,12 @@ class VFAE(ELBOModel):
     masks drawn on the device with the step's noise; evaluation and inference drop nothing).  Two labelled differences from
     the block-level path and the reference, named by one warning at construction: the two heads of a block share ONE keep
     mask (each head's marginal is the reference's, the joint is not), and a block without a hidden layer is not dropped at all.
-    ``dropout_rate`` >= 1 raises ``ValueError``."""
+    ``dropout_rate`` >= 1 raises ``ValueError``.
+    ``max_grad_norm`` (default None: off) clips the global 2-norm of the gradient inside the fused step, with the semantics of
+    ``torch.nn.utils.clip_grad_norm_`` in front of the optimiser, and guards it: a step whose gradient holds an inf or a NaN
+    is skipped -- parameters and optimiser state stay as they are, ``grad_clip_stats()['n_skipped']`` counts it, ``fit`` warns
+    once per epoch in which it happened.  ``float('inf')`` keeps the guard and clips nothing.  A clipped step gives up the
+    side chain's share of the optimiser sweep.  0, a negative number or NaN raise ``ValueError``."""
     kind = 'vfae'
     fit_patience = 40       # src/VFAE.py:536
 
@@ -19,7 +24,8 @@ class VFAE(ELBOModel):
                  batch_size=100, nonlinearity='softplus', learning_rate=0.001, optim_alg='adam', L=1,
                  weight_decay=None, dropout_rate=0., input_x_dropout=0., add_noise_var=0., yloss_rate=1.,
                  anneal_yloss_offset=0, use_MMD=True, kernel_MMD='rbf_fourier', mmd_rate=1., use_s=False,
-                 random_seed=12345, log_txt=None, weight_norm=False, device=None, matmul_precision='fp32'):
+                 random_seed=12345, log_txt=None, weight_norm=False, device=None, matmul_precision='fp32',
+                 max_grad_norm=None):
         super().__init__()
         args = dict(locals())
         args.pop('self')

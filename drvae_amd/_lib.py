@@ -45,6 +45,17 @@ class AdamHyper(C.Structure):  # dv_adam_hyper
     _fields_ = [('lr', _f), ('beta1', _f), ('beta2', _f), ('eps', _f), ('weight_decay', _f), ('gscale', _f)]
 
 
+class ClipRecord(C.Structure):  # dv_clip_record
+    _fields_ = [('norm', _f), ('coef', _f), ('skip', _i32), ('n_skipped', _i32)]
+
+
+class ClipState(C.Structure):   # dv_clip_state (device memory: ``kernels.clip_state`` lays its int32 buffer out by these offsets)
+    _fields_ = [('step', _i32), ('reserved', _i32), ('max_norm', C.c_double), ('rec', ClipRecord)]
+
+
+SUMSQ_PER_BLOCK, SUMSQ_MAX_BLOCKS = 8192, 1024     # DV_SUMSQ_PER_BLOCK / DV_SUMSQ_MAX_BLOCKS (tests/test_clip_cpu.py reads the header)
+
+
 class Publish(C.Structure):    # dv_publish: "this launch has started", published on entry
     _fields_ = [('flag', _p), ('ctr', _p), ('add', _i32)]
 

@@ -28,6 +28,13 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         self._matmul = args.pop('matmul_precision', 'fp32')
         if self._matmul not in E.MATMUL_CHOICES:
             raise ValueError('matmul_precision must be one of %s' % (E.MATMUL_CHOICES,))
+        # None | a positive number | inf: global-norm gradient clipping and the non-finite guard of the fused step, see
+        # ``StepConfig.max_grad_norm``
+        self._max_grad_norm = args.pop('max_grad_norm', None)
+        if self._max_grad_norm is not None:
+            self._max_grad_norm = float(self._max_grad_norm)
+            if not self._max_grad_norm > 0.0:
+                raise ValueError('max_grad_norm must be a positive number, inf or None, not %r' % (self._max_grad_norm,))
         for k, v in args.items():
             setattr(self, k, v)
         self.wn = bool(weight_norm)   # reference: hard-coded False (src/DrVAE.py:79); exposed here
@@ -167,7 +174,8 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
             use_MMD=bool(getattr(self, 'use_s', False) and getattr(self, 'use_MMD', False)),
             mmd_rate=float(getattr(self, 'mmd_rate', 1.)), kernel_MMD=getattr(self, 'kernel_MMD', 'rbf_fourier'),
             prior_y=None if (getattr(self, 'prior_y', None) is None or isinstance(getattr(self, 'prior_y', None), str))
-            else tuple(float(v) for v in self.prior_y), matmul=self._matmul, dropout_rate=float(self.dropout_rate))
+            else tuple(float(v) for v in self.prior_y), matmul=self._matmul, dropout_rate=float(self.dropout_rate),
+            max_grad_norm=self._max_grad_norm)
 
     # ---------------------------------------------------------------- inference
     @torch.no_grad()

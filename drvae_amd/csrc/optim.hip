@@ -11,9 +11,10 @@ struct AdamC {
 };
 
 // bias corrections from the device-side step counter, in double like torch's python floats
+// (``n_skipped``: steps the non-finite guard of a clipped sweep has skipped -- they leave no trace in the corrections)
 __device__ __forceinline__ void adam_consts(float lr, float b1, float b2, const int32_t* step_dev, float* step_size,
-                                            float* bc2_sqrt) {
-    const double t = (double)step_dev[0];
+                                            float* bc2_sqrt, int n_skipped = 0) {
+    const double t = (double)(step_dev[0] - n_skipped);
     const double bc1 = 1.0 - pow((double)b1, t);
     const double bc2 = 1.0 - pow((double)b2, t);
     *step_size = (float)((double)lr / bc1);
@@ -56,11 +57,17 @@ struct AdamGate {
     int64_t lo, hi;
 };
 
+// CLIP: the sweep of a step with gradient-norm clipping (dv_adam_l2 with n_halt < 0): ``clip`` is the record the norm pass has
+// written -- skip set: nothing is touched (not sticky, no halt word involved); else gscale * coef scales the gradient and the
+// bias corrections count the steps taken.  CLIP = false is the sweep as it ever was (adam_kernel and adam_stream_kernel: the same
+// instructions but for the kernel-argument offsets; adamax_kernel: the same arithmetic, the halt loop scheduled in front of pow()).
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
-                                                   float b1, float b2, float eps, float wd, float gscale,
+                                                   float b1, float b2, float eps, float wd, float gscale_in,
                                                    const int32_t* __restrict__ step_dev, int vec4, AdamGate gate,
-                                                   const int32_t* __restrict__ halt, int n_halt) {
+                                                   const int32_t* __restrict__ halt, int n_halt,
+                                                   const dv_clip_record* __restrict__ clip) {
     __shared__ float sc[2];
     __shared__ int halted;
     // only the workgroups whose elements overlap the gated range park (typically one): a parked
@@ -81,7 +88,13 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
             seen = __hip_atomic_load(gate.flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
         }
         int h = any_halt(halt, n_halt);
-        adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1]);
+        if (CLIP) {
+            // a skipped first step has t = 0: the corrections are not evaluated, the sweep returns before it would use them
+            if (clip->skip) h = 1;
+            else adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], clip->n_skipped);
+        } else {
+            adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1]);
+        }
         if (need && seen - want < 0) {
             const long long t0 = wall_clock64();
             int k = 0;
@@ -111,6 +124,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     // share of the scalar tail: at least the gated slice), every later one nowhere (tests/test_gpu_optim.py)
     if (halted) return;
     const float step_size = sc[0], bc2_sqrt = sc[1];
+    const float gscale = CLIP ? gscale_in * clip->coef : gscale_in;      // fl32(gscale * coef): coef == 1.0f gives gscale's bits
     // (float)(1 - beta) computed in double first, as python does before the op sees it
     const float w1 = (float)(1.0 - (double)b1), w2 = (float)(1.0 - (double)b2);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
@@ -144,20 +158,29 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 // step has streamed gigabytes through the caches), 16384 workgroups.  tools/adam_probe.hip alone: 0.629 -> 0.564 ms = 5.57 -> 6.20
 // TB/s (the guide's float4-copy figure is 6.29); inside the step (behind the dW products) 0.68 -> 0.63 ms.  Ungated (the chip-filling steps have no side chain to gate on).
 typedef float adam_f4 __attribute__((ext_vector_type(4)));
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adam_stream_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                           float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
-                                                          float b1, float b2, float eps, float wd, float gscale,
+                                                          float b1, float b2, float eps, float wd, float gscale_in,
                                                           const int32_t* __restrict__ step_dev,
-                                                          const int32_t* __restrict__ halt, int n_halt) {
+                                                          const int32_t* __restrict__ halt, int n_halt,
+                                                          const dv_clip_record* __restrict__ clip) {
     __shared__ float sc[2];
     __shared__ int halted;
     if (threadIdx.x == 0) {
-        adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1]);
-        halted = any_halt(halt, n_halt);
+        if (CLIP) {       // (see adam_kernel)
+            const int skip = clip->skip;
+            if (!skip) adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], clip->n_skipped);
+            halted = any_halt(halt, n_halt) | skip;
+        } else {
+            adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1]);
+            halted = any_halt(halt, n_halt);
+        }
     }
     __syncthreads();
     if (halted) return;
     const float step_size = sc[0], bc2_sqrt = sc[1];
+    const float gscale = CLIP ? gscale_in * clip->coef : gscale_in;
     const float w1 = (float)(1.0 - (double)b1), w2 = (float)(1.0 - (double)b2);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x, n4 = n >> 2;
     const int64_t t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -193,6 +216,82 @@ __global__ __launch_bounds__(256) void adam_stream_kernel(float* __restrict__ p,
     }
     for (int64_t i = (n4 << 2) + t0; i < n; i += stride)
         adam_one(p[i], g[i], m[i], v[i], step_size, bc2_sqrt, eps, wd, w1, b2, w2, gscale);
+}
+
+// ------------------------------------------------------------------ gradient-norm clipping
+// Sum of squares of a contiguous fp32 range, in double from the square on (the square of a widened fp32 is exact in double),
+// for the global-norm clip of the optimiser sweep.  Deterministic: the elements a thread visits, the wave tree, the order of the
+// wave sums and the grid are functions of n and of the pointer's offset within 16 bytes alone -- no atomics; one double
+// partial per workgroup, summed in index order by clip_finalize_kernel.  16-B loads over the aligned body (four in flight per
+// lane), the <= 3 + 3 elements in front of and behind it by the first lanes of workgroup 0.  NT: non-temporal loads, for
+// ranges far beyond the Infinity Cache (the threshold of the streaming sweep).
+static inline int sumsq_blocks(int64_t n) { return (int)DV_SUMSQ_PARTIALS(n); }
+
+template <bool NT>
+__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ part) {
+    __shared__ double wsum[4];
+    int64_t head = (int64_t)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(g) & 15)) & 15u) >> 2);
+    if (head > n) head = n;
+    const int64_t n4 = (n - head) >> 2, tail0 = head + (n4 << 2);
+    const adam_f4* g4 = reinterpret_cast<const adam_f4*>(g + head);
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const int64_t t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    double acc = 0.0;
+    for (int64_t i = t0; i < n4; i += 4 * stride) {
+        adam_f4 x[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int64_t j = i + u * stride;
+            if (j < n4) x[u] = NT ? __builtin_nontemporal_load(g4 + j) : g4[j];
+            else x[u] = adam_f4{0.f, 0.f, 0.f, 0.f};          // (+0.0 * +0.0 added to a sum that is never -0.0: no trace)
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const double d = (double)x[u][e];
+                acc = __builtin_fma(d, d, acc);
+            }
+        }
+    }
+    if (t0 < head) {
+        const double d = (double)g[t0];
+        acc = __builtin_fma(d, d, acc);
+    }
+    if (tail0 + t0 < n) {
+        const double d = (double)g[tail0 + t0];
+        acc = __builtin_fma(d, d, acc);
+    }
+    // wave tree (64 lanes), then the four wave sums in wave order
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+}
+
+// the partials in index order -> the clip record of the step: norm = |gscale| sqrt(sumsq), coef = min(1, max_norm / (norm +
+// 1e-6)) in double, stored as fp32; a non-finite sum of squares (some gradient element is inf or NaN: finite fp32 inputs cannot
+// overflow the double sum) -> skip = 1, coef = 0 and the running count of skipped steps goes up by one
+// (max_norm is device data the host cannot check: a value that is not > 0 clips nothing)
+__global__ __launch_bounds__(256) void clip_finalize_kernel(const double* __restrict__ part, int n_part, float gscale,
+                                                            dv_clip_state* __restrict__ st) {
+    dv_clip_record* rec = &st->rec;
+    const double max_norm = st->max_norm;
+    __shared__ double sp[DV_SUMSQ_MAX_BLOCKS];
+    for (int i = threadIdx.x; i < n_part; i += blockDim.x) sp[i] = part[i];
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    double s = 0.0;
+    for (int i = 0; i < n_part; ++i) s += sp[i];
+    const int skip = !(fabs(s) <= 1.7976931348623157e308);       // inf or NaN
+    const double norm = fabs((double)gscale) * sqrt(s);
+    double coef = max_norm > 0.0 ? max_norm / (norm + 1e-6) : 1.0;
+    coef = coef < 1.0 ? coef : 1.0;
+    rec->norm = (float)norm;
+    rec->coef = skip ? 0.f : (float)coef;
+    rec->skip = skip;
+    rec->n_skipped = rec->n_skipped + skip;
 }
 
 __global__ void counter_add_kernel(int32_t* c, int n_words, int64_t inc) {
@@ -394,20 +493,33 @@ extern "C" int dv_abi_version(void) { return DV_ABI_VERSION; }
 
 // torch.optim.Adamax (2.x `_single_tensor_adamax`), the other branch of src/DGMMixin.py:37-38:
 // grad += wd*p; m.lerp_(g, 1-b1); u = max(u*b2, |g|+eps); p += -(lr/(1-b1^t)) * (m/u)
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adamax_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                      float* __restrict__ m, float* __restrict__ u, int64_t n, float lr,
-                                                     float b1, float b2, float eps, float wd, float gscale,
+                                                     float b1, float b2, float eps, float wd, float gscale_in,
                                                      const int32_t* __restrict__ step_dev,
-                                                     const int32_t* __restrict__ halt, int n_halt) {
+                                                     const int32_t* __restrict__ halt, int n_halt,
+                                                     const dv_clip_record* __restrict__ clip) {
     __shared__ float sc[2];
     __shared__ int halted;
     if (threadIdx.x == 0) {
-        adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1]);
-        halted = any_halt(halt, n_halt);
+        // (the second correction goes to a local nobody reads: a store to the shared array of a template instantiation is not
+        // dropped as dead, and the pow() behind it would stay)
+        float clr0 = 0.f, unused;
+        if (CLIP) {       // (see adam_kernel)
+            const int skip = clip->skip;
+            if (!skip) adam_consts(lr, b1, b2, step_dev, &clr0, &unused, clip->n_skipped);
+            halted = any_halt(halt, n_halt) | skip;
+        } else {
+            adam_consts(lr, b1, b2, step_dev, &clr0, &unused);
+            halted = any_halt(halt, n_halt);
+        }
+        sc[0] = clr0;
     }
     __syncthreads();
     if (halted) return;
     const float clr = sc[0];
+    const float gscale = CLIP ? gscale_in * clip->coef : gscale_in;
     const float w1 = (float)(1.0 - (double)b1);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -445,7 +557,7 @@ extern "C" const char* dv_error_string(int code) {
 
 static int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                        float eps, float weight_decay, float gscale, const int32_t* step_dev, const AdamGate& gate,
-                       const int32_t* halt, int32_t n_halt, dv_stream_t stream) {
+                       const int32_t* halt, int32_t n_halt, dv_stream_t stream, const dv_clip_record* clip = nullptr) {
     DV_REQUIRE(n >= 0 && n_halt >= 0 && (halt || n_halt == 0));
     if (n == 0) return DV_OK;
     DV_REQUIRE(p && g && m && v && step_dev);
@@ -454,21 +566,23 @@ static int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, 
     int64_t blocks = ((vec4 ? (n >> 2) : n) + 255) / 256;
     if (blocks < 1) blocks = 1;
     if (vec4 && gate.flag == nullptr && n >= (int64_t(16) << 20)) {       // far beyond the Infinity Cache: the streaming sweep
-        hipLaunchKernelGGL(adam_stream_kernel, dim3((unsigned)(blocks > 16384 ? 16384 : blocks)), dim3(256), 0, ST(stream), p, g, m, v,
-                           n, lr, beta1, beta2, eps, weight_decay, gscale, step_dev, halt, n_halt);
+        const dim3 grid((unsigned)(blocks > 16384 ? 16384 : blocks));
+        if (clip)
+            hipLaunchKernelGGL(adam_stream_kernel<true>, grid, dim3(256), 0, ST(stream), p, g, m, v, n, lr, beta1, beta2, eps,
+                               weight_decay, gscale, step_dev, halt, n_halt, clip);
+        else
+            hipLaunchKernelGGL(adam_stream_kernel<false>, grid, dim3(256), 0, ST(stream), p, g, m, v, n, lr, beta1, beta2, eps,
+                               weight_decay, gscale, step_dev, halt, n_halt, clip);
         DV_RETURN_LAUNCH();
     }
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, v, n, lr, beta1,
-                       beta2, eps, weight_decay, gscale, step_dev, vec4, gate, halt, n_halt);
+    if (clip)
+        hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, v, n, lr, beta1,
+                           beta2, eps, weight_decay, gscale, step_dev, vec4, gate, halt, n_halt, clip);
+    else
+        hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, v, n, lr, beta1,
+                           beta2, eps, weight_decay, gscale, step_dev, vec4, gate, halt, n_halt, clip);
     DV_RETURN_LAUNCH();
-}
-
-extern "C" int dv_adam_l2(float* p, const float* g, float* m, float* v, int64_t n, const dv_adam_hyper* h,
-                          const int32_t* step_dev, const int32_t* halt, int32_t n_halt, dv_stream_t stream) {
-    DV_REQUIRE(h != nullptr);
-    return adam_launch(p, g, m, v, n, h->lr, h->beta1, h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, AdamGate{},
-                       halt, n_halt, stream);
 }
 
 extern "C" int dv_adam_l2_gated(float* p, const float* g, float* m, float* v, int64_t n, const dv_adam_hyper* h,
@@ -480,16 +594,69 @@ extern "C" int dv_adam_l2_gated(float* p, const float* g, float* m, float* v, in
                        AdamGate{gate->flag, gate->ctr, gate->add, gate->err, gate->max_spins, lo, hi}, halt, n_halt, stream);
 }
 
-extern "C" int dv_adamax_l2(float* p, const float* g, float* m, float* u, int64_t n, const dv_adam_hyper* h,
-                            const int32_t* step_dev, const int32_t* halt, int32_t n_halt, dv_stream_t stream) {
+static int adamax_launch(float* p, const float* g, float* m, float* u, int64_t n, const dv_adam_hyper* h,
+                         const int32_t* step_dev, const int32_t* halt, int32_t n_halt, dv_stream_t stream,
+                         const dv_clip_record* clip) {
     DV_REQUIRE(h != nullptr && n >= 0 && n_halt >= 0 && (halt || n_halt == 0));
     if (n == 0) return DV_OK;
     DV_REQUIRE(p && g && m && u && step_dev);
     int64_t blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(adamax_kernel, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, u, n, h->lr, h->beta1,
-                       h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt);
+    if (clip)
+        hipLaunchKernelGGL(adamax_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, u, n, h->lr,
+                           h->beta1, h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt, clip);
+    else
+        hipLaunchKernelGGL(adamax_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, u, n, h->lr,
+                           h->beta1, h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt, clip);
     DV_RETURN_LAUNCH();
+}
+
+// gradient-norm clipping rides on the sweeps' own entry points (n_halt < 0, see the header): ``step_dev`` is a dv_clip_state;
+// p == NULL: the NORM PASS (sum of squares into the workspace behind the state, then the record), else the sweep reading it
+static int clip_norm_pass(const float* g, int64_t n, const dv_adam_hyper* h, dv_clip_state* st, dv_stream_t stream) {
+    DV_REQUIRE(n >= 0 && (g || n == 0) && (reinterpret_cast<uintptr_t>(g) & 3) == 0);
+    double* part = reinterpret_cast<double*>(st + 1);
+    const int blocks = sumsq_blocks(n);
+    if (n >= (int64_t(16) << 20))
+        hipLaunchKernelGGL(sumsq_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), g, n, part);
+    else
+        hipLaunchKernelGGL(sumsq_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), g, n, part);
+    hipLaunchKernelGGL(clip_finalize_kernel, dim3(1), dim3(256), 0, ST(stream), part, blocks, h->gscale, st);
+    DV_RETURN_LAUNCH();
+}
+
+static_assert(sizeof(dv_clip_state) == 32 && DV_SUMSQ_PARTIALS(1) == 1 && DV_SUMSQ_PARTIALS(int64_t(1) << 40) == DV_SUMSQ_MAX_BLOCKS,
+              "dv_clip_state / DV_SUMSQ_PARTIALS of the header");
+
+extern "C" int dv_adam_l2(float* p, const float* g, float* m, float* v, int64_t n, const dv_adam_hyper* h,
+                          const int32_t* step_dev, const int32_t* halt, int32_t n_halt, dv_stream_t stream) {
+    DV_REQUIRE(h != nullptr);
+    if (n_halt < 0) {
+        DV_REQUIRE(step_dev && (reinterpret_cast<uintptr_t>(step_dev) & 7) == 0);
+        dv_clip_state* st = reinterpret_cast<dv_clip_state*>(const_cast<int32_t*>(step_dev));
+        if (p == nullptr) {
+            DV_REQUIRE(!m && !v);
+            return clip_norm_pass(g, n, h, st, stream);
+        }
+        return adam_launch(p, g, m, v, n, h->lr, h->beta1, h->beta2, h->eps, h->weight_decay, h->gscale, &st->step, AdamGate{},
+                           halt, ~n_halt, stream, &st->rec);
+    }
+    return adam_launch(p, g, m, v, n, h->lr, h->beta1, h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, AdamGate{},
+                       halt, n_halt, stream);
+}
+
+extern "C" int dv_adamax_l2(float* p, const float* g, float* m, float* u, int64_t n, const dv_adam_hyper* h,
+                            const int32_t* step_dev, const int32_t* halt, int32_t n_halt, dv_stream_t stream) {
+    if (n_halt < 0) {
+        DV_REQUIRE(h != nullptr && step_dev && (reinterpret_cast<uintptr_t>(step_dev) & 7) == 0);
+        dv_clip_state* st = reinterpret_cast<dv_clip_state*>(const_cast<int32_t*>(step_dev));
+        if (p == nullptr) {
+            DV_REQUIRE(!m && !u);
+            return clip_norm_pass(g, n, h, st, stream);
+        }
+        return adamax_launch(p, g, m, u, n, h, &st->step, halt, ~n_halt, stream, &st->rec);
+    }
+    return adamax_launch(p, g, m, u, n, h, step_dev, halt, n_halt, stream, nullptr);
 }
 
 // Device-side ordering between two concurrently running launch chains (two root branches of one

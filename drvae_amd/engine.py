@@ -96,12 +96,24 @@ class StepConfig:
     # every chain with at least two layers is a dropout SITE of a training pass (``_Chain.add_dropout``); the keep masks are
     # drawn with the step's noise (``kernels.fill_noise_rows``).  0: no sites, the step as it ever was
     dropout_rate: float = 0.0
+    # EXTENSION (no counterpart in the reference): global-norm gradient clipping and a non-finite guard inside the step,
+    # with the semantics of ``torch.nn.utils.clip_grad_norm_(params, max_grad_norm, norm_type=2)`` in front of the optimiser:
+    # the (exchanged) gradient arena is scaled by coef = min(1, max_grad_norm / (norm + 1e-6)) on its way into the sweep, and a
+    # step whose gradient holds an inf or a NaN is SKIPPED -- parameters, moments and the bias corrections' step count stay
+    # as they are, a device counter counts it (``FusedStep.clip_stats``).  ``inf``: the guard alone.  None: nothing of this
+    # exists -- no launch, no buffer, the step as it ever was
+    max_grad_norm: Optional[float] = None
 
     def __post_init__(self):
         if self.matmul not in MATMUL_CHOICES:
             raise ValueError('StepConfig.matmul must be one of %s, not %r' % (MATMUL_CHOICES, self.matmul))
         if not 0.0 <= self.dropout_rate < 1.0:
             raise ValueError('StepConfig.dropout_rate must lie in [0, 1), not %r' % (self.dropout_rate,))
+        if self.max_grad_norm is not None:
+            self.max_grad_norm = float(self.max_grad_norm)
+            if not self.max_grad_norm > 0.0:          # (NaN fails this too)
+                raise ValueError('StepConfig.max_grad_norm must be a positive number, inf or None, not %r'
+                                 % (self.max_grad_norm,))
 
     @property
     def cont(self):
@@ -224,6 +236,14 @@ class FusedStep(StepSchedule):
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=self.dev)       # Adam step (device side)
         self.loss_sum = torch.zeros(8, device=self.dev)      # running sums of the loss scalars over train steps
         self.rng_ctr = torch.zeros(2, dtype=torch.int32, device=self.dev)        # Philox counter (device side)
+        # gradient-norm clipping (``StepConfig.max_grad_norm``): the engine's clip state (``kernels.clip_state``), device memory
+        # for its life -- the step counter becomes its first word, the record {norm, coef, skip, n_skipped} and the workspace
+        # of the norm pass are views of it; None: the feature does not exist
+        self.clip_state = self.clip_rec = self.clip_part = None
+        if cfg.max_grad_norm is not None:
+            self.clip_state = K.clip_state(self.dev, arena.n_live, cfg.max_grad_norm)
+            self.step_dev = self.clip_state[0:1]
+            self.clip_rec, self.clip_part = K.clip_record(self.clip_state), K.clip_partials(self.clip_state)
         self.seed = seed
         self.training = True
         self.fuse_bwd = False               # set by train_step/capture: forward is followed by backward
@@ -1260,6 +1280,16 @@ class FusedStep(StepSchedule):
         step = K.adamax_l2 if cfg.optim_alg == 'adamax' else K.adam_l2    # exp_avg_sq doubles as Adamax's exp_inf
         n = a.n_live                      # parameters without gradients sit behind it (untouched, like torch)
         t, kw = (self._tail if self._rec == 'main' else None), {}
+        if self.clip_rec is not None:
+            # clipped step: every gradient is final here (``_step_tail`` records no leaf work behind the join and no
+            # side-chain half of the sweep for it), behind the exchange in every exchange form.  The norm over the whole live
+            # slice -- the pad elements between parameters are zero, always (``ParamArena``) --, the record, the sweep
+            assert not (t and (t.adam_gated or t.cap_fork or t.side_adam)), 'a clipped sweep has no gated form'
+            K.clip_norm(a.grad[:n], self.clip_state, gscale=gscale, adamax=cfg.optim_alg == 'adamax')
+            step = K.adamax_l2_clip if cfg.optim_alg == 'adamax' else K.adam_l2_clip
+            step(a.param[:n], a.grad[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.clip_state,
+                 lr=cfg.learning_rate, weight_decay=cfg.weight_decay, gscale=gscale, halt=self.sync_err)
+            return
         if t and t.adam_gated:   # dual-graph step: the classifier's dW may still be in flight on the side chain
             # (the optimiser's gate waits with counter + 0: the step counter is advanced before it)
             if cfg.has_y:
@@ -1276,6 +1306,15 @@ class FusedStep(StepSchedule):
             kw['gate'] = self.sync.gate('tail', self.step_dev, 0, 4)
         step(a.param[:n], a.grad[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.step_dev, lr=cfg.learning_rate,
              weight_decay=cfg.weight_decay, gscale=gscale, halt=self.sync_err, **kw)
+
+    def clip_stats(self):
+        """dict(norm, coef, skipped_last, n_skipped) of the last clipped optimiser step as python numbers: the gradient's
+        global 2-norm (times |gscale|), the coefficient the sweep scaled it by, whether that step was skipped for a
+        non-finite gradient, and how many steps have been skipped so far.  One small device->host copy, never part of a step."""
+        if self.clip_rec is None:
+            raise RuntimeError('clip_stats: the engine was built without max_grad_norm')
+        self.join_side()
+        return K.clip_record_values(self.clip_rec)
 
     def train_step(self, noise=None, allreduce=None):
         """forward + backward (+ gradient all-reduce) + Adam + iteration count: the body of

@@ -10,6 +10,7 @@ Two ways to feed the epoch loop:
     compatibility path, one ``run_on_batch`` per tuple.
 """
 import time
+import warnings
 from collections import OrderedDict
 
 import numpy as np
@@ -348,6 +349,14 @@ class FitMixin:
                 self._log_losses(epoch, b * len(batch[0]), len(loader.dataset), b / n_b, loss)
         return float(total) / n_b
 
+    def _warn_skipped_steps(self, epoch, before):
+        """(``max_grad_norm``) one warning for an epoch in which the non-finite guard skipped steps; returns the running count"""
+        now = self.grad_clip_stats()['n_skipped']
+        if now > before:
+            warnings.warn('epoch %d: %d train step(s) skipped for a non-finite gradient (%d so far); parameters and '
+                          'optimiser state were left as they were' % (epoch, now - before, now))
+        return now
+
     def fit(self, train_loader, valid_loader, add_noise=False, verbose=False, early_stop=False,
             model_filename='best_model.pth'):
         """Train for ``self.epochs`` epochs with the reference's validation / early-stopping /
@@ -357,6 +366,7 @@ class FitMixin:
         ctl = EarlyStopping(self.epochs, early_stop, patience=self.fit_patience)
         self.w2log('Starting training at: {}'.format(time.strftime('%c')))
         epoch = 0
+        skipped = self.grad_clip_stats()['n_skipped'] if self._max_grad_norm is not None else 0
         try:
             self.add_noise = add_noise
             for epoch in range(1, self.epochs + 1):
@@ -365,6 +375,7 @@ class FitMixin:
                     train_loss = self._epoch_device(train_loader, epoch, verbose)
                 else:
                     train_loss = self._epoch_loader(train_loader, epoch, verbose)
+                skipped = self._warn_skipped_steps(epoch, skipped) if self._max_grad_norm is not None else 0
                 train_perf, train_str = self.evaluate_performance_on_dataset(train_loader.dataset)
                 self.w2log('====> Epoch: {}\tIter: {}'.format(epoch, self.finished_training_iters))
                 self.w2log('Train: sec/epoch: {:.2f}\tAvg train loss: {:9.4f}\t{}'.format(time.time() - t, train_loss,

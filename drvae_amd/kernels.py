@@ -1106,6 +1106,82 @@ def adamax_l2(p, g, m, u, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, wei
                                         _stream()), 'dv_adamax_l2')
 
 
+# gradient-norm clipping (``StepConfig.max_grad_norm``) rides on the sweeps' entry points (``n_halt`` < 0, include/drvae_hip.h).
+# The clip STATE of an engine is one int32 device buffer laid out as ``dv_clip_state`` (``_lib.ClipState``) + workspace: the
+# optimiser step (the engine's ``step_dev`` is this word), max_norm (a double), the record {norm, coef (fp32 bits), skip,
+# n_skipped}, then ``sumsq_partials(n)`` doubles
+CLIP_STATE_WORDS = C.sizeof(_lib.ClipState) // 4
+_CLIP_STEP, _CLIP_MAX_NORM, _CLIP_REC = (getattr(_lib.ClipState, f).offset // 4 for f in ('step', 'max_norm', 'rec'))
+assert _CLIP_STEP == 0 and CLIP_STATE_WORDS % 2 == 0 and _CLIP_MAX_NORM % 2 == 0
+
+
+def sumsq_partials(n):
+    """number of double partials the norm pass writes for ``n`` elements (DV_SUMSQ_PARTIALS: a function of n alone)"""
+    per, cap = _lib.SUMSQ_PER_BLOCK, _lib.SUMSQ_MAX_BLOCKS
+    return int(min(max((int(n) + per - 1) // per, 1), cap))
+
+
+def clip_state(device, n, max_norm):
+    st = torch.zeros(CLIP_STATE_WORDS + 2 * sumsq_partials(n), dtype=torch.int32, device=device)
+    clip_set_max_norm(st, max_norm)
+    return st
+
+
+def clip_set_max_norm(state, max_norm):
+    state[_CLIP_MAX_NORM:_CLIP_MAX_NORM + 2].copy_(torch.tensor([float(max_norm)], dtype=torch.float64).view(torch.int32))
+
+
+def clip_record(state):
+    """the record words {norm, coef, skip, n_skipped} of a clip state (a view)"""
+    return state[_CLIP_REC:_CLIP_REC + C.sizeof(_lib.ClipRecord) // 4]
+
+
+def clip_partials(state):
+    """the workspace of a clip state as doubles (a view)"""
+    return state[CLIP_STATE_WORDS:].view(torch.float64)
+
+
+def clip_record_values(record):
+    """dict(norm, coef, skipped_last, n_skipped) of a clip record, as python numbers (one small copy)"""
+    r = record.detach().cpu()
+    f = r.view(torch.float32)
+    return dict(norm=float(f[0]), coef=float(f[1]), skipped_last=bool(int(r[2])), n_skipped=int(r[3]))
+
+
+def _clip_halt(halt):
+    hp, hn = _halt(halt)
+    return hp, ~hn
+
+
+def clip_norm(g, state, *, gscale=1.0, adamax=False):
+    """the norm pass over the contiguous fp32 range ``g`` into ``state``: the sum of squares in double (one partial per
+    workgroup), then the record: norm = |gscale| sqrt(sumsq), coef = min(1, max_norm / (norm + 1e-6)), skip (a non-finite sum)
+    and the running count of skipped steps.  Two launches behind one call of the sweep's entry point (p = NULL)"""
+    assert g.is_contiguous() and state.numel() >= CLIP_STATE_WORDS + 2 * sumsq_partials(g.numel())
+    h = _lib.AdamHyper(gscale=gscale)
+    fn = _lib.load().dv_adamax_l2 if adamax else _lib.load().dv_adam_l2
+    _lib.check(fn(None, _f32(g), None, None, g.numel(), C.byref(h), _i32(state), None, ~0, _stream()),
+               'dv_adamax_l2 (clip norm)' if adamax else 'dv_adam_l2 (clip norm)')
+
+
+def adam_l2_clip(p, g, m, v, state, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None):
+    """``adam_l2`` reading the record of the clip state (whose first word is the step): skipped when the record says so, else
+    the gradient scaled by fl32(gscale * coef) and t = step - n_skipped.  No gated form."""
+    assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
+    hp, hn = _clip_halt(halt)
+    h = _lib.AdamHyper(lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, gscale=gscale)
+    _lib.check(_lib.load().dv_adam_l2(_f32(p), _f32(g), _f32(m), _f32(v), p.numel(), C.byref(h), _i32(state), hp, hn,
+                                      _stream()), 'dv_adam_l2 (clipped)')
+
+
+def adamax_l2_clip(p, g, m, u, state, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None):
+    assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and u.is_contiguous()
+    hp, hn = _clip_halt(halt)
+    h = _lib.AdamHyper(lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, gscale=gscale)
+    _lib.check(_lib.load().dv_adamax_l2(_f32(p), _f32(g), _f32(m), _f32(u), p.numel(), C.byref(h), _i32(state), hp, hn,
+                                        _stream()), 'dv_adamax_l2 (clipped)')
+
+
 def flag_publish(flag, ctr, add=1):
     _lib.check(_lib.load().dv_flag_publish(_i32(flag), _i32(ctr), add, _stream()), 'dv_flag_publish')
 

@@ -297,6 +297,11 @@ class StepSchedule:
         # ask it (CPU tests of the recorded sequence pass True)
         cfg, p = self.cfg, self.plan
         branch_on = self.branch.on if on_gpu is None else bool(self.concurrent and cfg.has_y and on_gpu)
+        # gradient-norm clipping (``StepConfig.max_grad_norm``): the norm launch in front of the sweep reads EVERY gradient, so
+        # nothing of the backward pass may still be in flight behind the join and the sweep has no gated or side-chain form:
+        # the single-process step is recorded the way the exchange forms record theirs.  Decided here and only here (the
+        # sweep asserts it)
+        clip = cfg.max_grad_norm is not None
         # two flag-ordered graphs only for the latency-bound steps: once the decoder products alone fill the chip many
         # times over (wide configuration) the side chain's small kernels, squeezed in between the resident GEMM
         # workgroups of a second queue, cost more than they hide (36.7 ms dual, 35.9 ms as one graph with a fork/join)
@@ -304,7 +309,7 @@ class StepSchedule:
         # the optimiser half cannot move there then and the rest does not pay for the second graph -- one-rank RCCL, cfg 1:
         # 0.1848 -> 0.1913 split, 0.1695 -> 0.1737 captured)
         if not (self.sched == 5 and self._dual_capable(on_gpu) and self._latency_bound() and
-                (self._flags_usable() if on_gpu is None else on_gpu) and (cfg.has_y or not split_kind)):
+                (self._flags_usable() if on_gpu is None else on_gpu) and (cfg.has_y or not (split_kind or clip))):
             # ONE graph.  A chip-filling step (wide configuration): its side chain is 0.5 ms of small launches next to 31 ms of
             # products that want every CU.  Forked at the start of the step they squeeze in between the resident GEMM workgroups
             # of the other queue and cost more than they hide (round 4: 32.0 ms with the fork/join, 31.5 ms in order on one
@@ -321,7 +326,9 @@ class StepSchedule:
         # two-graph split ``replay`` makes the launching stream wait for the side stream before the all-reduce, so the
         # leaf work may still move behind the join (only the optimiser half cannot: it follows the exchange); the
         # overlapped / captured exchanges keep everything in front of the join
-        late = late_ok and split_kind in (False, True)
+        # (a clipped step without an exchange: like those -- with the two-graph split the side stream is awaited in front of
+        # the exchange and the sweep is a graph of its own, nothing is in flight there)
+        late = late_ok and (split_kind is True or (split_kind is False and not clip))
         # ... and HALF of the optimiser sweep moves there too: the decoder heads (the tail of the arena, half of
         # all parameters) are final and no longer read once the heads' backward products are through -- the
         # launch after them publishes that -- so the side chain updates them next to the main chain's tail
@@ -334,7 +341,8 @@ class StepSchedule:
         # cfg 4 0.1799 -> 0.1769; the heads' half of the sweep behind the collective on the side chain's 64 CUs as well
         # (a flag published on entry of the main chain's sweep): 0.2124 / 0.1871 -- half the arena through a quarter of the
         # chip's bandwidth takes longer than the whole sweep on the rest (profiles/r06_experiments.md)
-        cap_fork = bool(split_kind == 'captured' and side_ok and late_ok and cfg.has_y and T.get('dp_fork'))
+        # (not a clipped step: this form parks the sweep's first workgroup on the side chain's flag)
+        cap_fork = bool(split_kind == 'captured' and side_ok and late_ok and cfg.has_y and T.get('dp_fork') and not clip)
         # the loss scalars (a leaf: only the host / the exchange reads them) are assembled by the side chain behind
         # the join, once the main chain has published that its reconstruction rows are final
         side_loss = side_adam or (late and split_kind is True and len(self.L_decx) > 1)
@@ -540,6 +548,8 @@ class StepSchedule:
             return None
         a = self.arena
         state = (a.param, a.exp_avg, a.exp_avg_sq, self.step_dev, self.side_ctr, self.side_t, self.rng_ctr, self.flags)
+        if self.clip_rec is not None:     # a tuning replay the guard skips counts in ``n_skipped``: it goes back with the step
+            state = state + (self.clip_rec,)
         keep = [t.clone() for t in state]
         iters = self.iters
         best = (None, float('inf'))

@@ -1057,6 +1057,39 @@ int dv_adam_l2_gated(float* p, const float* g, float* m, float* v, int64_t n, co
  * u is the exponentially weighted infinity norm; same conventions as dv_adam_l2. */
 int dv_adamax_l2(float* p, const float* g, float* m, float* u, int64_t n, const dv_adam_hyper* h,
                  const int32_t* step_dev, const int32_t* halt, int32_t n_halt, dv_stream_t stream);
+/* Global-norm gradient clipping and the non-finite guard of the optimiser sweep (EXTENSION: the reference has no
+ * counterpart; semantics of torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) in front of the optimisers above).
+ * Reached through dv_adam_l2 / dv_adamax_l2 with n_halt < 0 (the C ABI keeps its entry points): ~n_halt is the number of
+ * halt pairs, and step_dev points at a dv_clip_state in device memory, 8-byte aligned, owned by the caller and zeroed
+ * once but for max_norm: its first word is the step counter the sweep reads (bump it as ever), DV_SUMSQ_PARTIALS(n)
+ * doubles of workspace follow it.  Nothing leaves the device.
+ *   p == NULL (m, v / u NULL too): the NORM PASS over the n contiguous floats at g, two launches.  (1) one double partial
+ *       per workgroup = the sum of g[i]^2 over its elements, each element widened to double first; DV_SUMSQ_PARTIALS(n)
+ *       workgroups, a function of n alone, at most 1024.  No atomics: the value of every partial is a function of n and of
+ *       the pointer's offset within 16 bytes -- bitwise the same from run to run and from rank to rank.  Non-temporal
+ *       loads from n >= 16 Mi elements on (the streaming sweep's threshold).  g is only read.  (2) sumsq = the partials
+ *       summed in index order; norm = |h->gscale| sqrt(sumsq); coef = min(1, max_norm / (norm + 1e-6)), in double,
+ *       stored as fp32.  sumsq not finite (some g[i] is inf or NaN -- finite fp32 inputs cannot overflow the double sum):
+ *       skip = 1, coef = 0, n_skipped += 1; else skip = 0.  max_norm > 0; +inf: no clipping (coef = 1), the guard alone.
+ *   p != NULL: the sweep reading the record: skip set -> p, m, v / u are left as they are (not sticky, no halt word is
+ *       written); else the gradient is scaled by fl32(h->gscale * coef) where the plain sweep scales by h->gscale (coef ==
+ *       1.0f: the plain sweep's bits) and the bias corrections use t = step - n_skipped: a skipped step leaves no trace
+ *       in the optimiser state.  There is no gated form. */
+typedef struct dv_clip_record {
+    float norm;                     /* |gscale| * 2-norm of the gradient range of the last norm pass */
+    float coef;                     /* its clip coefficient, in [0, 1] */
+    int32_t skip;                   /* 1: that gradient held a non-finite element, the sweep reading this record does nothing */
+    int32_t n_skipped;              /* running count of such steps */
+} dv_clip_record;
+typedef struct dv_clip_state {      /* 32 bytes, then the workspace */
+    int32_t step;                   /* the 1-based optimiser step (what step_dev[0] is to the plain sweeps) */
+    int32_t reserved;
+    double max_norm;                /* the threshold, written by the caller */
+    dv_clip_record rec;
+} dv_clip_state;
+#define DV_SUMSQ_PER_BLOCK 8192     /* elements of g per workgroup of the norm pass, below the cap */
+#define DV_SUMSQ_MAX_BLOCKS 1024    /* the cap */
+#define DV_SUMSQ_PARTIALS(n) ((n) <= DV_SUMSQ_PER_BLOCK ? 1 : (n) > DV_SUMSQ_PER_BLOCK * (int64_t)(DV_SUMSQ_MAX_BLOCKS - 1) ? DV_SUMSQ_MAX_BLOCKS : ((n) + DV_SUMSQ_PER_BLOCK - 1) / DV_SUMSQ_PER_BLOCK)
 int dv_counter_add(int32_t* counter_lo_hi, int32_t n_words, int64_t inc, dv_stream_t stream);
 /* Joins folded into their consumers: dv_z2f_post_bwd, dv_reparam_bwd_seg and dv_rows_segment_sum take an optional `park`
  * (every workgroup of the launch first parks like dv_flag_wait: the first consumer of another chain's
