@@ -71,6 +71,11 @@ class Ymarg(C.Structure):      # dv_ymarg: y-marginalisation riding on the class
                 ('c_yl', _p), ('yl', _p), ('kld', _p), ('cfp', _p), ('dqy', _p), ('lddq', _i64)]
 
 
+class ClfDgrad(C.Structure):   # dv_clf_dgrad: the classifier's data gradient riding on the classifier-head launch
+    _fields_ = [('dst', _p * 2), ('ld', _i64 * 2), ('col0', _i32 * 2), ('ncol', _i32 * 2), ('alpha', _f * 2),
+                ('beta', _f * 2), ('col1', _i32 * 2), ('alpha2', _f * 2), ('n', _i32)]
+
+
 class Bump(C.Structure):       # dv_bump: up to two device counters advanced by a launch
     _fields_ = [('c', _p * 2), ('n', _i32 * 2), ('inc', _i64 * 2)]
 
@@ -122,7 +127,8 @@ class Z2F(C.Structure):          # dv_z2f_desc
                 ('lde', _i64), ('p2', _p), ('ldp2', _i64), ('q2', _p), ('ldq2', _i64), ('coef', _p), ('raw', _p),
                 ('kl_min', _f), ('dz1b', _p), ('ld_dz1b', _i64), ('dp2', _p), ('ld_dp2', _i64), ('dz1', _p),
                 ('ld_dz1', _i64), ('dq2', _p), ('ld_dq2', _i64), ('L', _i32), ('B', _i32), ('Np', _i32), ('Z', _i32),
-                ('prior_coef', _p), ('prior_raw', _p)]
+                ('prior_coef', _p), ('prior_raw', _p), ('kl_out', _p), ('raw_out', _p), ('seg_src', _p), ('ld_seg', _i64),
+                ('seg_ptr', _p), ('seg_beta', _f), ('z1_dz2f', _f)]
 
 
 class ReconRows(C.Structure):    # dv_recon_rows_desc
@@ -198,7 +204,7 @@ SIGNATURES = {
     'dv_cat_terms_fwd': [_p, _i64, _i32, _i32, _p, _p, _i64, _p, _p, _i64, _p, _p, _p],
     'dv_cat_terms_bwd': [_p, _i64, _i32, _i32, _p, _p, _i64, _p, _p, _i64, _p, _p, _i64, _f, _p],
     'dv_smalln_linear_fwd': [_p, _i64, _i32, _p, _i64, _i32, _p, _i64, _p, _i32, _i32, _p, _i64, _p, _i64,
-                             C.POINTER(Ymarg), _p, _p, _p],
+                             C.POINTER(Ymarg), _p, _p, _p, _p],
     'dv_smalln_linear_bwd_data': [_p, _i64, _p, _i64, _p, _i64, _i32, _i32, _i32, C.POINTER(_p), C.POINTER(_i64),
                                   C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_f), C.POINTER(_f), C.POINTER(_i32),
                                   C.POINTER(_f), _p, _i64, _p, _p],

@@ -220,11 +220,13 @@ __global__ void reparam_bwd_seg_kernel(const float* __restrict__ dz, int64_t ldz
 }
 
 // Backward of everything that hangs on the z2Fz1 samples (src/DrVAE.py:431-433,459-487) in one
-// pass over (row i, dim d), looping the L samples:
+// pass: one wave per batch row i, lanes over the dims d, looping the L samples:
 //   dz2F = DZ2F[(l,i)] (+ gradient of the decoded copy for pairs)
 //   DP2[(l,i)] = (dmu2 | dlv2) of p(z2|z1): reparam backward (+ KL(q(z2|x2)||p(z2|z1)) wrt p for pairs)
-//   DZ1[(l,i)] += dmu2 (residual path mu2 = z1 + ...) (+ DZ1B[(l,i)], the side chain's share)
+//   DZ1[(l,i)] += dmu2 (residual path mu2 = z1 + ...) (+ DZ1B[(l,i)] + seg_beta * its fprop rows of seg_src: the side chain's share)
 //   DQ2[jp]    = sum_l KL gradient wrt q(z2|x2)           (pairs only)
+// kl_out / raw_out set: the pairs' KL rows (what a kl_rows_fwd_kernel launch in front wrote) are formed here, from the
+// operands the gradients read anyway -- same lane mapping, same tree: same bits -- and gate the gradients
 struct Z2FArgs {
     const float* dz2f; int64_t ld_dz2f;       // (L*B, Z)
     const float* dzdec_pert; int64_t ld_pert;  // (L*Np, Z) gradient of the decoded z2Fz1 copies, or NULL
@@ -239,49 +241,256 @@ struct Z2FArgs {
     float* dq2; int64_t ld_dq2;                // (Np, 2Z) out, or NULL
     int L, B, Np, Z;
     const float* prior_coef; const float* prior_raw;   // (Np) or NULL: the prior-KL gradient of q2 rides along (dv_prior_kl)
+    float* kl_out; float* raw_out;             // (L*Np) out, or NULL: the KL rows are this launch's own
+    const float* seg_src; int64_t ld_seg; const int32_t* seg_ptr; float seg_beta;   // fprop rows' d/dz1, or NULL
+    float z1_dz2f;                             // d/dz1 also gets z1_dz2f * dz2f (classifier input [z1, z2Fz1 - z1]: -1)
 };
 
-__global__ void z2f_post_bwd_kernel(Z2FArgs a, ParkArgs park) {
+__device__ __forceinline__ float kl_term(int mode, float mq, float sq, float mp, float sp) {
+    const float dm = mq - mp;
+    if (mode == DV_GAUSS_LOGVAR) return 1.f - sp + sq - (dm * dm + expf(sq)) / expf(sp);
+    const float vq = sq * sq, vp = sp * sp;
+    return 1.f - logf(vp) + logf(vq) - (dm * dm + vq) / vp;
+}
+
+// what one (sample row r, dim d) of the block reads besides q2
+struct Z2FElem {
+    float mp, lp, gc, g, eps, z1, add;
+};
+
+// ... of it what the launch's own chain has written before the launch starts
+__device__ __forceinline__ void z2f_load_own(const Z2FArgs& a, int64_t r, int64_t kr, int d, Z2FElem& e) {
+    e.mp = a.p2[r * a.ldp2 + d];
+    e.lp = a.p2[r * a.ldp2 + a.Z + d];
+    e.g = (kr >= 0 && a.dzdec_pert) ? a.dzdec_pert[kr * a.ld_pert + d] : 0.f;
+    e.eps = a.eps[r * a.lde + d];
+    e.z1 = a.dz1[r * a.ld_dz1 + d];
+}
+
+// ... and what the chain behind the park has: d/dz2F and its share of d/dz1 from its parts,
+// add = (dz1b + seg_beta * sum of seg_src rows [t0, t1)) + z1_dz2f * dz2f
+__device__ __forceinline__ void z2f_load_side(const Z2FArgs& a, int64_t r, int d, int t0, int t1, Z2FElem& e) {
+    e.gc = a.dz2f ? a.dz2f[r * a.ld_dz2f + d] : 0.f;
+    e.g = e.gc + e.g;
+    e.add = a.dz1b ? a.dz1b[r * a.ld_dz1b + d] : 0.f;
+    if (a.seg_src != nullptr) {      // (dv_rows_segment_sum's sum, in its order)
+        float s = 0.f;
+        for (int t = t0; t < t1; ++t) s += a.seg_src[(int64_t)t * a.ld_seg + d];
+        e.add += a.seg_beta * s;
+    }
+    if (a.z1_dz2f != 0.f) e.add += a.z1_dz2f * e.gc;
+}
+
+// gradients of one (sample row, dim): stores dp2 / dz1, adds the sample's share of d/dq2 to (gq_mu, gq_lv)
+__device__ __forceinline__ void z2f_elem(const Z2FArgs& a, int64_t r, int d, bool pair, float c, float mq, float lq,
+                                         const Z2FElem& e, float& gq_mu, float& gq_lv) {
+    float dmu = e.g, dlv = e.g * e.eps * 0.5f * expf(0.5f * e.lp);
+    if (pair) {
+        const float dm = mq - e.mp, ivp = expf(-e.lp), vq = expf(lq);
+        gq_mu += c * dm * ivp;
+        gq_lv += c * (-0.5f * (1.f - vq * ivp));
+        dmu += -c * dm * ivp;
+        dlv += c * (-0.5f * (-1.f + (dm * dm + vq) * ivp));
+    }
+    a.dp2[r * a.ld_dp2 + d] = dmu;
+    a.dp2[r * a.ld_dp2 + a.Z + d] = dlv;
+    a.dz1[r * a.ld_dz1 + d] = e.z1 + (dmu + e.add);
+}
+
+__device__ __forceinline__ float z2f_gate(float cf, float rv, float kl_min) {
+    return cf * (rv > kl_min ? 1.f : (rv == kl_min ? 0.5f : 0.f));
+}
+
+// a row's state across its samples (Z <= 128: two dims per lane), and two samples' operands in registers
+struct Z2FRow {
+    int jp;
+    bool pair, own_kl, prior;
+    float cpr, mq[2], lq[2], gm[2], gl[2];
+};
+struct Z2FPair {
+    Z2FElem e[2][2];
+    int t0[2], t1[2];
+    float cf[2], rv[2];
+};
+
+__device__ __forceinline__ void z2f_row_begin(const Z2FArgs& a, int i, int lane, Z2FRow& w) {
+    w.jp = a.pair_slot ? a.pair_slot[i] : -1;
+    w.pair = w.jp >= 0;
+    w.own_kl = w.pair && a.raw_out != nullptr;
+    w.prior = w.pair && a.dq2 && a.prior_coef != nullptr;
+    w.cpr = 0.f;
+    if (w.prior)      // the prior term of q(z2|x2) row jp (what dv_kl_rows_bwd(beta = 1) added)
+        w.cpr = z2f_gate(a.prior_coef[w.jp], a.prior_raw[w.jp], a.kl_min);
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const int d = lane + 64 * c;
+        w.mq[c] = w.lq[c] = w.gm[c] = w.gl[c] = 0.f;
+        if (w.pair && d < a.Z) {
+            w.mq[c] = a.q2[(int64_t)w.jp * a.ldq2 + d];
+            w.lq[c] = a.q2[(int64_t)w.jp * a.ldq2 + a.Z + d];
+        }
+    }
+}
+
+// samples l0, l0 + 1 of row i, first half: everything that does not come from the chain behind the park -- the operands, and
+// with them the launch's own KL rows (kl_rows_fwd_kernel's lane mapping and tree: its bits), stored by lane 0
+__device__ __forceinline__ void z2f_pair_own(const Z2FArgs& a, const Z2FRow& w, int i, int l0, int lane, Z2FPair& g) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        g.t0[u] = g.t1[u] = 0;
+        g.cf[u] = g.rv[u] = 0.f;
+        if (l0 + u >= a.L) break;
+        const int64_t r = (int64_t)(l0 + u) * a.B + i, kr = w.pair ? (int64_t)(l0 + u) * a.Np + w.jp : -1;
+        if (a.seg_src != nullptr) {
+            g.t0[u] = a.seg_ptr[r];
+            g.t1[u] = a.seg_ptr[r + 1];
+        }
+        if (w.pair) g.cf[u] = a.coef[kr];
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+            if (lane + 64 * c < a.Z) z2f_load_own(a, r, kr, lane + 64 * c, g.e[u][c]);
+    }
+    if (!w.own_kl) return;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        if (l0 + u >= a.L) break;
+        float s = 0.f;
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+            if (lane + 64 * c < a.Z) s += kl_term(DV_GAUSS_LOGVAR, w.mq[c], w.lq[c], g.e[u][c].mp, g.e[u][c].lp);
+        g.rv[u] = -0.5f * dv_wave_sum_all(s);
+        if (lane == 0) {
+            const int64_t kr = (int64_t)(l0 + u) * a.Np + w.jp;
+            a.raw_out[kr] = g.rv[u];
+            a.kl_out[kr] = fmaxf(g.rv[u], a.kl_min);
+        }
+    }
+}
+
+// ... second half, behind the park: the other chain's operands, the gates, the gradients
+__device__ __forceinline__ void z2f_pair_finish(const Z2FArgs& a, Z2FRow& w, int i, int l0, int lane, Z2FPair& g) {
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        if (l0 + u >= a.L) break;
+        const int64_t r = (int64_t)(l0 + u) * a.B + i;
+        if (w.pair && !w.own_kl) g.rv[u] = a.raw[(int64_t)(l0 + u) * a.Np + w.jp];
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+            if (lane + 64 * c < a.Z) z2f_load_side(a, r, lane + 64 * c, g.t0[u], g.t1[u], g.e[u][c]);
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+        if (l0 + u >= a.L) break;
+        const int64_t r = (int64_t)(l0 + u) * a.B + i;
+        const float cg = w.pair ? z2f_gate(g.cf[u], g.rv[u], a.kl_min) : 0.f;
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+            if (lane + 64 * c < a.Z)
+                z2f_elem(a, r, lane + 64 * c, w.pair, cg, w.mq[c], w.lq[c], g.e[u][c], w.gm[c], w.gl[c]);
+    }
+}
+
+__device__ __forceinline__ void z2f_row_end(const Z2FArgs& a, Z2FRow& w, int lane) {
+    if (!(w.pair && a.dq2)) return;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const int d = lane + 64 * c;
+        if (d >= a.Z) continue;
+        if (w.prior) {
+            w.gm[c] += w.cpr * (w.mq[c] * 1.f);
+            w.gl[c] += w.cpr * (-0.5f * (1.f - expf(w.lq[c]) * 1.f));
+        }
+        a.dq2[(int64_t)w.jp * a.ld_dq2 + d] = w.gm[c];
+        a.dq2[(int64_t)w.jp * a.ld_dq2 + a.Z + d] = w.gl[c];
+    }
+}
+
+// Z <= 128.  The launch sits behind the join, on the step's critical path, and what it reads was written by other CUs: every
+// dependent trip to memory behind the park counts.  So the first two samples' own-chain operands are read, and the KL rows
+// formed, IN FRONT of the park -- in the shadow of the wait -- and one trip behind it fetches the other chain's operands
+__global__ __launch_bounds__(256) void z2f_post_bwd_kernel(Z2FArgs a, ParkArgs park) {
+    const int lane = threadIdx.x & 63;
+    int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const bool has = i < a.B;
+    Z2FRow w;
+    Z2FPair g;
+    if (has) {
+        z2f_row_begin(a, i, lane, w);
+        z2f_pair_own(a, w, i, 0, lane, g);
+    }
+    park_block(park);         // (every thread of the workgroup, with or without a row)
+    if (!has) return;
+    z2f_pair_finish(a, w, i, 0, lane, g);
+    for (int l0 = 2; l0 < a.L; l0 += 2) {
+        z2f_pair_own(a, w, i, l0, lane, g);
+        z2f_pair_finish(a, w, i, l0, lane, g);
+    }
+    z2f_row_end(a, w, lane);
+    for (i += gridDim.x * 4; i < a.B; i += gridDim.x * 4) {
+        z2f_row_begin(a, i, lane, w);
+        for (int l0 = 0; l0 < a.L; l0 += 2) {
+            z2f_pair_own(a, w, i, l0, lane, g);
+            z2f_pair_finish(a, w, i, l0, lane, g);
+        }
+        z2f_row_end(a, w, lane);
+    }
+}
+
+// Z > 128: the dims are walked twice per sample (row sum, then gradients); d/dq2 accumulates in its own element
+__global__ __launch_bounds__(256) void z2f_post_bwd_wide_kernel(Z2FArgs a, ParkArgs park) {
     park_block(park);
-    const int64_t total = (int64_t)a.B * a.Z;
-    for (int64_t e = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-        const int i = (int)(e / a.Z), d = (int)(e % a.Z);
+    const int lane = threadIdx.x & 63;
+    for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < a.B; i += gridDim.x * 4) {
         const int jp = a.pair_slot ? a.pair_slot[i] : -1;
-        float mq = 0.f, lq = 0.f, gq_mu = 0.f, gq_lv = 0.f;
-        if (jp >= 0) {
-            mq = a.q2[(int64_t)jp * a.ldq2 + d];
-            lq = a.q2[(int64_t)jp * a.ldq2 + a.Z + d];
-        }
+        const bool pair = jp >= 0;
+        const bool own_kl = pair && a.raw_out != nullptr;
+        const bool prior = pair && a.dq2 && a.prior_coef != nullptr;
+        const float cpr = prior ? z2f_gate(a.prior_coef[jp], a.prior_raw[jp], a.kl_min) : 0.f;
         for (int l = 0; l < a.L; ++l) {
-            const int64_t r = (int64_t)l * a.B + i;
-            const float mp = a.p2[r * a.ldp2 + d], lp = a.p2[r * a.ldp2 + a.Z + d];
-            float g = a.dz2f ? a.dz2f[r * a.ld_dz2f + d] : 0.f;
-            if (jp >= 0 && a.dzdec_pert) g += a.dzdec_pert[((int64_t)l * a.Np + jp) * a.ld_pert + d];
-            float dmu = g, dlv = g * a.eps[r * a.lde + d] * 0.5f * expf(0.5f * lp);
-            if (jp >= 0) {
-                const int64_t kr = (int64_t)l * a.Np + jp;
-                const float rv = a.raw[kr];
-                const float c = a.coef[kr] * (rv > a.kl_min ? 1.f : (rv == a.kl_min ? 0.5f : 0.f));
-                const float dm = mq - mp, ivp = expf(-lp), vq = expf(lq);
-                gq_mu += c * dm * ivp;
-                gq_lv += c * (-0.5f * (1.f - vq * ivp));
-                dmu += -c * dm * ivp;
-                dlv += c * (-0.5f * (-1.f + (dm * dm + vq) * ivp));
+            const int64_t r = (int64_t)l * a.B + i, kr = pair ? (int64_t)l * a.Np + jp : -1;
+            const int t0 = a.seg_src ? a.seg_ptr[r] : 0, t1 = a.seg_src ? a.seg_ptr[r + 1] : 0;
+            float rv = 0.f;
+            if (own_kl) {
+                float s = 0.f;
+                for (int d = lane; d < a.Z; d += 64)
+                    s += kl_term(DV_GAUSS_LOGVAR, a.q2[(int64_t)jp * a.ldq2 + d], a.q2[(int64_t)jp * a.ldq2 + a.Z + d],
+                                 a.p2[r * a.ldp2 + d], a.p2[r * a.ldp2 + a.Z + d]);
+                rv = -0.5f * dv_wave_sum_all(s);
+                if (lane == 0) {
+                    a.raw_out[kr] = rv;
+                    a.kl_out[kr] = fmaxf(rv, a.kl_min);
+                }
+            } else if (pair) {
+                rv = a.raw[kr];
             }
-            a.dp2[r * a.ld_dp2 + d] = dmu;
-            a.dp2[r * a.ld_dp2 + a.Z + d] = dlv;
-            float* z1 = a.dz1 + r * a.ld_dz1 + d;
-            *z1 += dmu + (a.dz1b ? a.dz1b[r * a.ld_dz1b + d] : 0.f);
-        }
-        if (jp >= 0 && a.dq2) {
-            if (a.prior_coef != nullptr) {      // + the prior term of q(z2|x2) row jp (what dv_kl_rows_bwd(beta = 1) added)
-                const float rv = a.prior_raw[jp];
-                const float c = a.prior_coef[jp] * (rv > a.kl_min ? 1.f : (rv == a.kl_min ? 0.5f : 0.f));
-                gq_mu += c * (mq * 1.f);
-                gq_lv += c * (-0.5f * (1.f - expf(lq) * 1.f));
+            const float cg = pair ? z2f_gate(a.coef[kr], rv, a.kl_min) : 0.f;
+            for (int d = lane; d < a.Z; d += 64) {
+                float mq = 0.f, lq = 0.f, gm = 0.f, gl = 0.f;
+                float* qm = nullptr;
+                if (pair) {
+                    mq = a.q2[(int64_t)jp * a.ldq2 + d];
+                    lq = a.q2[(int64_t)jp * a.ldq2 + a.Z + d];
+                    if (a.dq2) {      // (this lane's own element: the samples in front of l added to it)
+                        qm = a.dq2 + (int64_t)jp * a.ld_dq2 + d;
+                        if (l > 0) {
+                            gm = qm[0];
+                            gl = qm[a.Z];
+                        }
+                    }
+                }
+                Z2FElem e;
+                z2f_load_own(a, r, kr, d, e);
+                z2f_load_side(a, r, d, t0, t1, e);
+                z2f_elem(a, r, d, pair, cg, mq, lq, e, gm, gl);
+                if (qm != nullptr) {
+                    if (prior && l == a.L - 1) {
+                        gm += cpr * (mq * 1.f);
+                        gl += cpr * (-0.5f * (1.f - expf(lq) * 1.f));
+                    }
+                    qm[0] = gm;
+                    qm[a.Z] = gl;
+                }
             }
-            a.dq2[(int64_t)jp * a.ld_dq2 + d] = gq_mu;
-            a.dq2[(int64_t)jp * a.ld_dq2 + a.Z + d] = gq_lv;
         }
     }
 }
@@ -297,13 +506,6 @@ struct KlArgs {
     float prior_mu, prior_sd;
     int n, reps, Z, mode;
 };
-
-__device__ __forceinline__ float kl_term(int mode, float mq, float sq, float mp, float sp) {
-    const float dm = mq - mp;
-    if (mode == DV_GAUSS_LOGVAR) return 1.f - sp + sq - (dm * dm + expf(sq)) / expf(sp);
-    const float vq = sq * sq, vp = sp * sp;
-    return 1.f - logf(vp) + logf(vq) - (dm * dm + vq) / vp;
-}
 
 __global__ __launch_bounds__(256) void kl_rows_fwd_kernel(KlArgs a, int free_bits, float kl_min,
                                                           float* __restrict__ raw_out, float* __restrict__ out,
@@ -955,8 +1157,9 @@ constexpr int kMaxSmallN = 8;
 // y-marginalisation of one row right behind its class probabilities (dv_smalln_linear_fwd with a dv_ymarg argument:
 // the classifier head and the labeled / marginalised KLD assembly of src/DrVAE.py:503-534 in one launch); same
 // arithmetic as ymarg_fwdbwd_kernel below
-// (cfp_out != NULL: the coefficients written to y.cfp are also returned, slot by slot)
-__device__ __forceinline__ void ymarg_row(const dv_ymarg& y, int r, int Y, const float* q, float* cfp_out = nullptr) {
+// (cfp_out != NULL: the coefficients written to y.cfp are also returned, slot by slot; dq_out != NULL: the row of y.dqy)
+__device__ __forceinline__ void ymarg_row(const dv_ymarg& y, int r, int Y, const float* q, float* cfp_out = nullptr,
+                                          float* dq_out = nullptr) {
     const int f0 = y.fp_ptr[r], nf = y.fp_ptr[r + 1] - f0;
     const float ck = y.c_kld[r];
     float* dq = y.dqy + (int64_t)r * y.lddq;
@@ -965,7 +1168,11 @@ __device__ __forceinline__ void ymarg_row(const dv_ymarg& y, int r, int Y, const
         const int lab = nf == 1 ? lab0 : -2 - lab0;
         y.yl[r] = logf(q[lab]);
         y.kld[r] = y.klfp[nf == 1 ? f0 : f0 + lab];
-        for (int j = 0; j < Y; ++j) dq[j] = (j == lab) ? y.c_yl[r] / q[j] : 0.f;
+        for (int j = 0; j < Y; ++j) {
+            const float v = (j == lab) ? y.c_yl[r] / q[j] : 0.f;
+            dq[j] = v;
+            if (dq_out) dq_out[j] = v;
+        }
         if (nf == 1) {
             y.cfp[f0] = ck;
             if (cfp_out) cfp_out[0] = ck;
@@ -983,10 +1190,40 @@ __device__ __forceinline__ void ymarg_row(const dv_ymarg& y, int r, int Y, const
             b += -q[j] * (lp - lq);
             y.cfp[f0 + j] = ck * q[j];
             if (cfp_out) cfp_out[j] = ck * q[j];
-            dq[j] = ck * (kf + lq - lp + 1.f);
+            const float v = ck * (kf + lq - lp + 1.f);
+            dq[j] = v;
+            if (dq_out) dq_out[j] = v;
         }
         y.yl[r] = 0.f;
         y.kld[r] = a + b;
+    }
+}
+
+// d logits of row r from (d probs, probs) through clamp + softmax, see softmax_clamp_bwd_kernel
+__device__ __forceinline__ void smalln_dlogits(const float* g, const float* p, int N, float* dl) {
+    float dot = 0.f;
+    for (int j = 0; j < N; ++j) dot += (p[j] > kPMin ? g[j] : 0.f) * p[j];
+    for (int j = 0; j < N; ++j) dl[j] = p[j] * ((p[j] > kPMin ? g[j] : 0.f) - dot);
+}
+
+// the classifier's data gradient of row r right behind its y-marginalisation (dv_smalln_linear_fwd with a dv_clf_dgrad
+// argument): lane 0 holds the row's d logits (smalln_dlogits of the dqy / probs it has just stored), the wave writes the
+// destinations' columns with the arithmetic of smalln_bwd_data_kernel (no segment start)
+__device__ __forceinline__ void smalln_dgrad_row(const dv_clf_dgrad& g, int r, int N, const float* dl0,
+                                                 const float* __restrict__ W, int64_t ldw, int lane) {
+    float dl[kMaxSmallN];
+#pragma unroll
+    for (int j = 0; j < kMaxSmallN; ++j) dl[j] = j < N ? __shfl(dl0[j], 0, 64) : 0.f;
+    for (int t = 0; t < g.n; ++t) {
+        float* o = g.dst[t] + (int64_t)r * g.ld[t];
+        for (int c = lane; c < g.ncol[t]; c += 64) {
+            float s = 0.f, s2 = 0.f;
+            for (int j = 0; j < N; ++j) s += dl[j] * W[(int64_t)j * ldw + g.col0[t] + c];
+            if (g.alpha2[t] != 0.f)
+                for (int j = 0; j < N; ++j) s2 += dl[j] * W[(int64_t)j * ldw + g.col1[t] + c];
+            const float base = g.beta[t] != 0.f ? g.beta[t] * o[c] : 0.f;
+            o[c] = base + g.alpha[t] * s + g.alpha2[t] * s2;
+        }
     }
 }
 
@@ -996,7 +1233,7 @@ __global__ __launch_bounds__(256) void smalln_fwd_kernel(const float* __restrict
                                                          const float* __restrict__ bias, int M, int N,
                                                          float* __restrict__ logits, int64_t ldl,
                                                          float* __restrict__ probs, int64_t ldp, dv_ymarg ym,
-                                                         ParkArgs park, dv_fprop_kl kf) {
+                                                         ParkArgs park, dv_fprop_kl kf, dv_clf_dgrad dg) {
     park_block(park);
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1027,9 +1264,9 @@ __global__ __launch_bounds__(256) void smalln_fwd_kernel(const float* __restrict
             }
         }
     }
-    float acc[kMaxSmallN];
+    float acc[kMaxSmallN], dl[kMaxSmallN];
 #pragma unroll
-    for (int j = 0; j < kMaxSmallN; ++j) acc[j] = 0.f;
+    for (int j = 0; j < kMaxSmallN; ++j) acc[j] = dl[j] = 0.f;
     for (int k = lane; k < K1 + K2; k += 64) {
         const float x = k < K1 ? a1[(int64_t)r * lda1 + k] : a2[(int64_t)r * lda2 + (k - K1)];
 #pragma unroll
@@ -1053,9 +1290,14 @@ __global__ __launch_bounds__(256) void smalln_fwd_kernel(const float* __restrict
                 q[j] = fminf(fmaxf(expf(acc[j] - mx) / den, kPMin), kPMax);
                 probs[(int64_t)r * ldp + j] = q[j];
             }
-            if (ym.fp_ptr != nullptr) ymarg_row(ym, r, N, q, kf.mu_q != nullptr ? acc : nullptr);   // (acc: reused for cfp)
+            if (ym.fp_ptr != nullptr) {
+                float dq[kMaxSmallN];
+                ymarg_row(ym, r, N, q, kf.mu_q != nullptr ? acc : nullptr, dg.n ? dq : nullptr);   // (acc: reused for cfp)
+                if (dg.n) smalln_dlogits(dq, q, N, dl);
+            }
         }
     }
+    if (dg.n) smalln_dgrad_row(dg, r, N, dl, W, ldw, lane);
     if (kf.mu_q != nullptr) {
         // backward of the z1 term with the coefficients of the y-marginalisation (lane 0 holds them): dv_kl_rows_bwd
 #pragma unroll
@@ -1094,7 +1336,7 @@ __global__ __launch_bounds__(256) void smalln_fwd2_kernel(const float* __restric
                                                           const float* __restrict__ bias, int M, int N,
                                                           float* __restrict__ logits, int64_t ldl,
                                                           float* __restrict__ probs, int64_t ldp, dv_ymarg ym,
-                                                          ParkArgs park, dv_fprop_kl kf) {
+                                                          ParkArgs park, dv_fprop_kl kf, dv_clf_dgrad dg) {
     park_block(park);
     const int lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1166,9 +1408,9 @@ __global__ __launch_bounds__(256) void smalln_fwd2_kernel(const float* __restric
         }
     }
     // ---- the classifier and the y-marginalisation
-    float acc[kMaxSmallN];
+    float acc[kMaxSmallN], dl[kMaxSmallN];
 #pragma unroll
-    for (int j = 0; j < kMaxSmallN; ++j) acc[j] = 0.f;
+    for (int j = 0; j < kMaxSmallN; ++j) acc[j] = dl[j] = 0.f;
 #pragma unroll
     for (int c = 0; c < 4; ++c)
         if (lane + 64 * c < Kt) {
@@ -1191,8 +1433,11 @@ __global__ __launch_bounds__(256) void smalln_fwd2_kernel(const float* __restric
             q[j] = fminf(fmaxf(expf(acc[j] - mx) / den, kPMin), kPMax);
             probs[(int64_t)r * ldp + j] = q[j];
         }
-        ymarg_row(ym, r, N, q, acc);         // (acc: reused for the fprop rows' coefficients)
+        float dq[kMaxSmallN];
+        ymarg_row(ym, r, N, q, acc, dg.n ? dq : nullptr);         // (acc: reused for the fprop rows' coefficients)
+        if (dg.n) smalln_dlogits(dq, q, N, dl);
     }
+    if (dg.n) smalln_dgrad_row(dg, r, N, dl, W, ldw, lane);
     // ---- backward of the z1 term with those coefficients (lane 0 holds them), from the registers
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -1216,13 +1461,6 @@ __global__ __launch_bounds__(256) void smalln_fwd2_kernel(const float* __restric
             }
         }
     }
-}
-
-// d logits of row r from (d probs, probs) through clamp + softmax, see softmax_clamp_bwd_kernel
-__device__ __forceinline__ void smalln_dlogits(const float* g, const float* p, int N, float* dl) {
-    float dot = 0.f;
-    for (int j = 0; j < N; ++j) dot += (p[j] > kPMin ? g[j] : 0.f) * p[j];
-    for (int j = 0; j < N; ++j) dl[j] = p[j] * ((p[j] > kPMin ? g[j] : 0.f) - dot);
 }
 
 struct SmallNDst {
@@ -2662,15 +2900,22 @@ extern "C" int dv_z2f_post_bwd(const dv_z2f_desc* dsc, const dv_wait* park_in, d
     DV_REQUIRE(park.flag == nullptr || (d.L > 0 && d.B > 0 && d.Z > 0));
     // every workgroup of a parked launch polls: keep such grids far below what the chip holds resident
     // (256 CUs x 8 workgroups), or the chain that is to publish may find no slot to run in
-    if (park.flag != nullptr && grid_for((int64_t)d.B * d.Z, 256) > DV_MAX_PARKED_GRID) return DV_ERR_UNSUPPORTED;
+    if (park.flag != nullptr && grid_for(d.B, 4) > DV_MAX_PARKED_GRID) return DV_ERR_UNSUPPORTED;
     if (d.L == 0 || d.B == 0 || d.Z == 0) return DV_OK;
     DV_REQUIRE(d.eps && d.p2 && d.dp2 && d.dz1);   // dz2f == NULL: nothing flows into the z2Fz1 samples from a classifier
-    DV_REQUIRE(d.Np == 0 || (d.pair_slot && d.q2 && d.coef && d.raw));
+    DV_REQUIRE((d.kl_out == nullptr) == (d.raw_out == nullptr));
+    DV_REQUIRE(d.Np == 0 || (d.pair_slot && d.q2 && d.coef && (d.raw || d.raw_out)));
     DV_REQUIRE((d.prior_coef == nullptr) == (d.prior_raw == nullptr));
+    DV_REQUIRE((d.seg_src == nullptr) == (d.seg_ptr == nullptr));
     Z2FArgs a{d.dz2f, d.ld_dz2f, d.dzdec_pert, d.ld_pert, d.Np ? d.pair_slot : nullptr, d.eps, d.lde, d.p2, d.ldp2,
               d.q2, d.ldq2, d.coef, d.raw, d.kl_min, d.dz1b, d.ld_dz1b, d.dp2, d.ld_dp2, d.dz1, d.ld_dz1, d.dq2,
-              d.ld_dq2, d.L, d.B, d.Np, d.Z, d.Np ? d.prior_coef : nullptr, d.Np ? d.prior_raw : nullptr};
-    hipLaunchKernelGGL(z2f_post_bwd_kernel, dim3(grid_for((int64_t)d.B * d.Z, 256)), dim3(256), 0, ST(stream), a, park);
+              d.ld_dq2, d.L, d.B, d.Np, d.Z, d.Np ? d.prior_coef : nullptr, d.Np ? d.prior_raw : nullptr,
+              d.Np ? d.kl_out : nullptr, d.Np ? d.raw_out : nullptr, d.seg_src, d.ld_seg, d.seg_ptr, d.seg_beta,
+              d.dz2f ? d.z1_dz2f : 0.f};
+    if (d.Z <= 128)
+        hipLaunchKernelGGL(z2f_post_bwd_kernel, dim3(grid_for(d.B, 4)), dim3(256), 0, ST(stream), a, park);
+    else
+        hipLaunchKernelGGL(z2f_post_bwd_wide_kernel, dim3(grid_for(d.B, 4)), dim3(256), 0, ST(stream), a, park);
     DV_RETURN_LAUNCH();
 }
 
@@ -2895,7 +3140,8 @@ extern "C" int dv_cat_terms_bwd(const float* probs, int64_t ldp, int32_t M, int3
 extern "C" int dv_smalln_linear_fwd(const float* a1, int64_t lda1, int32_t K1, const float* a2, int64_t lda2,
                                     int32_t K2, const float* W, int64_t ldw, const float* bias, int32_t M, int32_t N,
                                     float* logits, int64_t ldl, float* probs, int64_t ldp, const dv_ymarg* ymarg,
-                                    const dv_wait* park_in, const dv_fprop_kl* kf_in, dv_stream_t stream) {
+                                    const dv_wait* park_in, const dv_fprop_kl* kf_in, const dv_clf_dgrad* dg_in,
+                                    dv_stream_t stream) {
     DV_REQUIRE(M >= 0 && N >= 1 && N <= kMaxSmallN && K1 >= 0 && K2 >= 0 && park_ok(park_in));
     const ParkArgs park = park_in ? *park_in : ParkArgs{};
     DV_REQUIRE(park.flag == nullptr || M > 0);
@@ -2913,14 +3159,23 @@ extern "C" int dv_smalln_linear_fwd(const float* a1, int64_t lda1, int32_t K1, c
         DV_REQUIRE(ym.fp_ptr != nullptr && kf.klfp == ym.klfp && kf.qidx && kf.mu_p && kf.mu3 && kf.raw1 && kf.raw3 &&
                    kf.dq && kf.dp && kf.Z1 >= 0 && kf.Z3 >= 0);
     }
+    dv_clf_dgrad dg{};
+    if (dg_in != nullptr && dg_in->n != 0) {
+        dg = *dg_in;
+        DV_REQUIRE(ym.fp_ptr != nullptr && dg.n >= 1 && dg.n <= 2);
+        for (int t = 0; t < dg.n; ++t) {
+            DV_REQUIRE(dg.dst[t] != nullptr && dg.ncol[t] >= 0 && dg.col0[t] >= 0 && dg.col0[t] + dg.ncol[t] <= K1 + K2);
+            DV_REQUIRE(dg.alpha2[t] == 0.f || (dg.col1[t] >= 0 && dg.col1[t] + dg.ncol[t] <= K1 + K2));
+        }
+    }
     if (kf.mu_q != nullptr && probs != nullptr && N <= 2 && K1 + K2 <= 256 && kf.Z1 <= 128 && kf.Z3 <= 128) {
         // (the train step's launch at its common shape: every operand in flight first, see smalln_fwd2_kernel)
         hipLaunchKernelGGL(smalln_fwd2_kernel, dim3((M + 3) / 4), dim3(256), 0, ST(stream), a1, lda1, K1, a2, lda2, K2, W,
-                           ldw, bias, M, N, logits, ldl, probs, ldp, ym, park, kf);
+                           ldw, bias, M, N, logits, ldl, probs, ldp, ym, park, kf, dg);
         DV_RETURN_LAUNCH();
     }
     hipLaunchKernelGGL(smalln_fwd_kernel, dim3((M + 3) / 4), dim3(256), 0, ST(stream), a1, lda1, K1, a2, lda2, K2, W,
-                       ldw, bias, M, N, logits, ldl, probs, ldp, ym, park, kf);
+                       ldw, bias, M, N, logits, ldl, probs, ldp, ym, park, kf, dg);
     DV_RETURN_LAUNCH();
 }
 

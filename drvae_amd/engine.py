@@ -626,7 +626,8 @@ class FusedStep(StepSchedule):
             self.branch.fork()
         self._decoder_forward(r, pub)
         if mode == DUAL:
-            klz2 = (self._tail.klz2_on_main or not cfg.has_y) and cfg.has_pert and Np
+            # (``fold_rows``: no launch on either chain -- ``z2f_post_bwd`` forms the rows)
+            klz2 = (self._tail.klz2_on_main or not cfg.has_y) and cfg.has_pert and Np and not self._tail.fold_rows
             P2 = p.c_z2F.out[-1] if klz2 else None
             z2 = ((p.KLZ2, p.KLZ2raw, Qmu, Qlv, P2[:, :Z1], P2[:, Z1:]),
                   dict(qidx=p.qz2_idx, pidx=p.pidx, reps=L, free_bits=True, kl_min=cfg.kl_min)) if klz2 else None
@@ -838,7 +839,7 @@ class FusedStep(StepSchedule):
         # main chain's z2Fz1 backward and the loss scalars -- in the dual-graph train step the MAIN chain computes
         # it (it has time to spare in front of the join, the side chain has not); then the wait for the z2Fz1
         # samples rides on the classifier launch
-        klz2_here = cfg.has_pert and Np and not self._tail.klz2_on_main
+        klz2_here = cfg.has_pert and Np and not self._tail.klz2_on_main and not self._tail.fold_rows
         # (a parked launch polls from every workgroup: small grids only -- the C side refuses more than 512)
         clf_park = (mid_park is not None and not klz2_here and cfg.has_y and self.clf_small
                     and (L * B + 3) // 4 <= 256)
@@ -865,8 +866,12 @@ class FusedStep(StepSchedule):
                     # (with the coefficients it has just produced) behind it: same launch
                     fk = dict(Q=p.c_enc.out[-1], qidx=p.fp_q, P=p.c_dz1.out[-1], Q3=p.c_top.out[-1], Z1=Z1,
                               Z3=cfg.dim_z3, kl_min=cfg.kl_min, raw1=p.KL1raw, raw3=p.KL3raw, dq=p.DQFP, dp=p.DPZ1)
+                # ``fold_rows``: ... and so does the classifier's data gradient, from the DQY the launch has just stored: d/dz2F
+                # whole, of d/dz1 the W[:, :Z1] part (``z2f_post_bwd`` adds the fprop rows' sum and -d/dz2F, as
+                # ``smalln_bwd_data`` did: same bits)
+                fold = dict(dgrad=[(p.DZ1C, 0, 1.0, 0.0), (p.DZ2F, Z1, 1.0, 0.0)]) if self._tail.fold_rows else {}
                 K.smalln_fwd(p.QY, None, clf_in[0], lc.W, lc.b, clf_in[1] if len(clf_in) > 1 else None,
-                             ymarg=ym if self.fuse_bwd else None, park=mid_park if clf_park else None, fprop_kl=fk)
+                             ymarg=ym if self.fuse_bwd else None, park=mid_park if clf_park else None, fprop_kl=fk, **fold)
             else:
                 K.softmax_clamp_fwd(p.QY, p.c_clf.forward(clf_in, drop=self._drop), sigmoid1=cfg.clf_1sig)
             if not self.fuse_bwd:
@@ -1112,11 +1117,15 @@ class FusedStep(StepSchedule):
             # everything that hangs on the z2Fz1 samples, one launch: scatter-back of the decoded
             # copies, reparam backward, KL(q(z2|x2)||p(z2|z1)) with free bits (src/DrVAE.py:466,482-487)
             # wrt both arguments, the residual path, and the side chain's share of d/dz1
+            # (``fold_rows``: ... and the forward of those KL rows -> KLZ2 / KLZ2raw, and the side chain's share of d/dz1 from its
+            # parts: DZ1C + the fprop rows' sum - DZ2F)
+            fold = dict(kl_out=p.KLZ2 if Np else None, seg=(p.DFPIN, p.fp_ptr, 1.0) if p.Mf else None, z1_dz2f=-1.0) \
+                if t.fold_rows else {}
             K.z2f_post_bwd(p.DP2, DZ1, DQ[B:] if Np else None, p.DZ2F if cfg.has_y else None,     # (no classifier: no gradient into the z2Fz1 samples but the decoder's)
                            p.DZDEC[p.o3:] if Np else None, p.pair_slot,
                            p.E2F, P2, Q[B:] if Np else None, p.c_klz2, p.KLZ2raw, cfg.kl_min,
-                           p.DZ1B if cfg.has_y else None, L, B, Np, park=park,
-                           prior=(p.c_klp[B:], p.KLPraw[B:]) if (cfg.kind == 'pvae' and Np) else None)
+                           (p.DZ1C if t.fold_rows else p.DZ1B) if cfg.has_y else None, L, B, Np, park=park,
+                           prior=(p.c_klp[B:], p.KLPraw[B:]) if (cfg.kind == 'pvae' and Np) else None, **fold)
             # perturbation function: mu = z1 + z1 W^T + b, logvar head
             p.c_z2F.backward(p.DP2, [Z1blk], [[(DZ1, 1.0, 1.0)]], drop=self._drop)
         # (VFAE: the side chain's share of d/dz1 is a second source of the sample backward below, no summing launch of
@@ -1206,8 +1215,9 @@ class FusedStep(StepSchedule):
             if self.clf_small:
                 lc = self.L_clf[0]
                 if two:      # input [z1, z2F - z1]: d/dz1 gets W1 - W2, d/dz2F gets W2
-                    K.smalln_bwd_data([(p.DZ1B, 0, 1.0, b1, Z1, -1.0), (p.DZ2F, Z1, 1.0, 0.0)], p.DQY, p.QY, lc.W,
-                                      seg=seg)
+                    if not self._tail.fold_rows:      # (else: left the classifier's forward launch, summed by ``z2f_post_bwd``)
+                        K.smalln_bwd_data([(p.DZ1B, 0, 1.0, b1, Z1, -1.0), (p.DZ2F, Z1, 1.0, 0.0)], p.DQY, p.QY, lc.W,
+                                          seg=seg)
                     wgrad_clf(lc.dW, lc.db, p.DQY, p.QY, Z1blk, p.D)
                 elif cfg.kind == 'drvae':
                     K.smalln_bwd_data([(p.DZ2F, 0, 1.0, 0.0)], p.DQY, p.QY, lc.W)
@@ -1251,13 +1261,18 @@ class FusedStep(StepSchedule):
                 K.adam_l2(a.param[hs:a.n_live], a.grad[hs:a.n_live], a.exp_avg[hs:a.n_live],
                           a.exp_avg_sq[hs:a.n_live], self.side_t, lr=cfg.learning_rate,
                           weight_decay=cfg.weight_decay, halt=self.sync_err)
-            self._loss_scalars()   # a leaf too; the wait above also covers the main chain's NLL rows
+            if not t.fold_rows:
+                self._loss_scalars()   # a leaf too; the wait above also covers the main chain's NLL rows
         if t.noise_ahead:
             # the next step's N(0,1) draws: every reader of this step's is through once the encoder
             # backward has started (the main chain publishes that), and the Philox counter has advanced.
             # (A park of the draw launch itself instead of the wait launch was measured slower: 356
             # workgroups polling one flag, +10 us/step)
             K.flag_wait(*sync.wait('noise', ctr))
+            if t.fold_rows:
+                # the pairs' KL rows are written by ``z2f_post_bwd``, behind the join: the loss scalars follow the wait for
+                # flag ``noise``, published behind that launch on the main chain
+                self._loss_scalars()
             self._fill_noise(p)
         # ... and now the side chain's late work is final: published by the counter launch on entry
         K.counters_add2(ctr, 1, self.side_t, 1, publish=sync.pub('tail', ctr) if (t.late or t.cap_fork) else None)

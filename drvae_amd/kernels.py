@@ -455,10 +455,14 @@ def reparam_bwd_seg(dmu, dsd, dz, eps, sd, seg_ptr, seg_rows, *, mode=GAUSS_LOGV
 
 
 def z2f_post_bwd(dp2, dz1, dq2, dz2f, dzdec_pert, pair_slot, eps, p2, q2, coef, raw, kl_min, dz1b, L, B, Np,
-                 park=None, prior=None):
+                 park=None, prior=None, kl_out=None, seg=None, z1_dz2f=0.0):
     """fused backward of the z2Fz1 sample / KL(q(z2|x2)||p(z2|z1)) / residual block, see dv_z2f_post_bwd.
     ``park`` = (flag, ctr, err[, add[, max_spins]]): the launch first parks on another chain's flag.
-    ``prior`` = (coef, raw) of the Np q2 rows: their prior-KL gradient (same kl_min) is added to dq2 (dv_prior_kl)."""
+    ``prior`` = (coef, raw) of the Np q2 rows: their prior-KL gradient (same kl_min) is added to dq2 (dv_prior_kl).
+    ``kl_out``: the launch forms the pairs' KL rows itself -- ``kl_out`` and ``raw`` are then OUTPUTS, what
+    ``kl_rows_fwd(kl_out, raw, ..., free_bits=True)`` in front of it wrote.  ``seg`` = (src, seg_ptr[, beta]): sample row r
+    also adds beta * the sum of ``src`` rows [seg_ptr[r], seg_ptr[r+1]) (their first Z columns) to dz1, and
+    ``z1_dz2f`` * dz2f[r] (a classifier on [z1, z2Fz1 - z1]: -1)."""
     Z = dp2.shape[1] // 2
     d = _lib.Z2F(dz2f=_f32(dz2f), ld_dz2f=_ld(dz2f), dzdec_pert=_f32(dzdec_pert), ld_pert=_ld(dzdec_pert),
                  pair_slot=_i32(pair_slot), eps=_f32(eps), lde=_ld(eps), p2=_f32(p2), ldp2=_ld(p2), q2=_f32(q2),
@@ -466,7 +470,15 @@ def z2f_post_bwd(dp2, dz1, dq2, dz2f, dzdec_pert, pair_slot, eps, p2, q2, coef, 
                  dp2=_f32(dp2), ld_dp2=_ld(dp2), dz1=_f32(dz1), ld_dz1=_ld(dz1), dq2=_f32(dq2), ld_dq2=_ld(dq2),
                  L=L, B=B, Np=Np, Z=Z, prior_coef=_f32(prior[0]) if prior is not None else None,
                  prior_raw=_f32(prior[1]) if prior is not None else None)
+    if kl_out is not None:
+        d.kl_out, d.raw_out, d.raw = _f32(kl_out), _f32(raw), None
+    d.z1_dz2f = z1_dz2f
+    if seg is not None:
+        d.seg_src, d.ld_seg, d.seg_ptr, d.seg_beta = _f32(seg[0]), _ld(seg[0]), _i32(seg[1]), seg[2] if len(seg) > 2 else 1.0
     _lib.check(_lib.load().dv_z2f_post_bwd(C.byref(d), _wait(park), _stream()), 'dv_z2f_post_bwd')
+
+
+z2f_post_bwd.fold_rows = True       # (this launcher takes ``kl_out`` / ``seg``: read by ``schedule._step_tail``)
 
 
 # --------------------------------------------------------------------------- KL rows
@@ -620,13 +632,15 @@ def cat_terms_bwd(dprobs, probs, *, labels=None, prior=None, c_logp=None, g_kl=N
                                             _ld(dprobs), beta, _stream()), 'dv_cat_terms_bwd')
 
 
-def smalln_fwd(probs, logits, a1, W, bias=None, a2=None, ymarg=None, park=None, fprop_kl=None):
+def smalln_fwd(probs, logits, a1, W, bias=None, a2=None, ymarg=None, park=None, fprop_kl=None, dgrad=None):
     """probs = clamp(softmax([a1|a2] W^T + b)) for N <= 8 outputs (either output may be None).
     ``ymarg`` = (yl, kld, cfp, dqy, label, fp_ptr, klfp, log_prior, c_kld, c_yl): the y-marginalisation of every row
     (the arguments of ``ymarg_fwdbwd``) rides on the same launch.  ``park`` = (flag, ctr, err[, add[, max_spins]]): every
     workgroup first parks on another chain's flag (see ``flag_wait``).  ``fprop_kl`` = dict(Q, qidx, P, Q3, Z1, Z3,
     kl_min, raw1, raw3, dq, dp) with ``ymarg``: the KL rows of the fprop rows (forward in front of the
-    y-marginalisation, the z1 term's backward behind it) ride on the same launch (``dv_fprop_kl``)."""
+    y-marginalisation, the z1 term's backward behind it) ride on the same launch (``dv_fprop_kl``).  ``dgrad`` (with
+    ``ymarg``) = up to two (dst, col0, alpha, beta[, col1, alpha2]) of ``smalln_bwd_data``: the classifier's data gradient
+    from the ``dqy`` the launch has just stored leaves it too (``dv_clf_dgrad``)."""
     M = a1.shape[0]
     N = W.shape[0]
     K1, K2 = a1.shape[1], (a2.shape[1] if a2 is not None else 0)
@@ -652,9 +666,20 @@ def smalln_fwd(probs, logits, a1, W, bias=None, a2=None, ymarg=None, park=None, 
         f.klfp, f.raw1, f.raw3 = _f32(ymarg[6]), _f32(fprop_kl['raw1']), _f32(fprop_kl['raw3'])
         f.dq, f.lddq, f.dp, f.lddp = _f32(fprop_kl['dq']), _ld(fprop_kl['dq']), _f32(fprop_kl['dp']), _ld(fprop_kl['dp'])
         kf = C.byref(f)
+    dg = None
+    if dgrad:
+        assert ymarg is not None and len(dgrad) <= 2
+        g = _lib.ClfDgrad(n=len(dgrad))
+        for t, d in enumerate(dgrad):
+            g.dst[t], g.ld[t], g.col0[t], g.ncol[t], g.alpha[t], g.beta[t] = _f32(d[0]), _ld(d[0]), d[1], d[0].shape[1], d[2], d[3]
+            g.col1[t], g.alpha2[t] = (d[4], d[5]) if len(d) > 5 else (0, 0.0)
+        dg = C.byref(g)
     _lib.check(_lib.load().dv_smalln_linear_fwd(_f32(a1), _ld(a1), K1, _f32(a2), _ld(a2), K2, _f32(W), _ld(W),
                                                 _f32(bias), M, N, _f32(logits), _ld(logits), _f32(probs),
-                                                _ld(probs), ym, _wait(park), kf, _stream()), 'dv_smalln_linear_fwd')
+                                                _ld(probs), ym, _wait(park), kf, dg, _stream()), 'dv_smalln_linear_fwd')
+
+
+smalln_fwd.fold_rows = True         # (this launcher takes ``dgrad``: read by ``schedule._step_tail``)
 
 
 def smalln_bwd_data(dsts, dprobs, probs, W, seg=None):

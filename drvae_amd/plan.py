@@ -231,6 +231,9 @@ class _Plan:
             self.log_prior = math.log(1.0 / Y) if cfg.prior_y is None else \
                 torch.log(torch.tensor(cfg.prior_y, dtype=torch.float64)).float().to(dev)
             self.DZ1B = mat(R, Z1)
+            # ``Tail.fold_rows``: d logits . W[:, :Z1], written by the classifier's FORWARD launch (``dv_clf_dgrad``); the rest of
+            # the side chain's share of d/dz1 is added where it is consumed (``z2f_post_bwd``)
+            self.DZ1C = mat(R, Z1) if (cfg.kind == 'drvae' and cfg.has_pert) else None
             self.YLrow, self.KLDrow = zf(R), zf(R)
             self.c_top = self._sited('c_top', _Chain(eng.L_top, Mf, dev))
             self.c_dz1 = self._sited('c_dz1', _Chain(eng.L_dz1, Mf, dev))

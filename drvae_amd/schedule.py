@@ -116,6 +116,8 @@ class Tail(NamedTuple):
     klz2_on_main: bool = False     # the pairs' KL(q(z2|x2)||p(z2|z1)) rows run on the main chain
     fold_join: bool = False        # the join rides on its first consumer (``z2f_post_bwd`` parks)
     late_fork: bool = False        # one-graph chip-filling step: the side chain forks behind the decoder heads' product
+    fold_rows: bool = False        # no launch for the pairs' KL rows (``z2f_post_bwd`` forms them) nor for the classifier's
+    #                                data gradient (it leaves ``smalln_fwd``; ``z2f_post_bwd`` sums the fprop rows' d/dz1)
 
 
 # the kinds of pass ``heads_route`` tells apart: forward with its backward fused behind it (``fuse_bwd``) | forward of a
@@ -364,16 +366,27 @@ class StepSchedule:
         # its side chain is the longer one, 30 us/step -- slows the very chain it waits for: 0.184 -> 0.208 ms)
         # ... and only where the parked grid is a small fraction of what the chip holds resident (256 CUs x 8
         # workgroups): a consumer grid that filled the chip would leave the side chain nowhere to run
-        fold_join = side_loss and cfg.has_pert and (p.B * cfg.dim_z1 + 255) // 256 <= 256
+        fold_join = side_loss and cfg.has_pert and (p.B * cfg.dim_z1 + 255) // 256 <= 256 and (p.B + 3) // 4 <= 256
         # (noise drawn ahead under a CAPTURED exchange too: the side chain then draws behind the join and sweeps its half
         # behind the collective)
         # ... but not over a plan with dropout sites: the next step's draw is released when the encoder backward STARTS --
         # nothing behind that point reads the arena -- and with sites the encoder backward itself reads its keep masks there.
         # Such a step draws at its head, as under ``sched=3`` (no second arena in this round)
         noise_ahead = bool((late or cap_fork) and not p.drop_sites)
+        # two launches folded into their neighbours (cfg 2: 33 -> 31 launches per step, one less on either chain): the pairs'
+        # KL rows are formed by their consumer ``z2f_post_bwd`` -- ``klz2_on_main`` then has nothing left to place, and the loss
+        # scalars, which read those rows, are assembled behind the side tail's wait for flag ``noise`` (published behind that
+        # launch on the main chain) -- and the classifier's data gradient leaves the classifier's forward launch, which has its
+        # inputs already; the fprop rows' d/dz1 is summed by ``z2f_post_bwd``.  Only the single-process dual-graph train step
+        # of a DrVAE with the single-Linear classifier on [z1, z2Fz1 - z1], and only where the installed launchers take the
+        # folded forms (the CPU stand-ins of the tests pin the launchers' signatures).  Same bits as the unfolded step; cfg 2:
+        # 0.1842 -> 0.1817 ms in alternating legs (profiles/r15_fold_rows.md)
+        fold_rows = bool(T.get('fold_rows') and not split_kind and not clip and not p.drop_sites and cfg.kind == 'drvae'
+                         and not cfg.cont and self.clf_small and cfg.clf_z1z2 and fold_join and side_loss and noise_ahead
+                         and getattr(K.z2f_post_bwd, 'fold_rows', False) and getattr(K.smalln_fwd, 'fold_rows', False))
         return Tail(dual=True, late=late, adam_gated=late and not split_kind, side_adam=side_adam, hs=hs, side_loss=side_loss,
                     cap_fork=cap_fork, tail_gated=tail_gated, noise_ahead=noise_ahead, klz2_on_main=klz2_on_main,
-                    fold_join=fold_join)
+                    fold_join=fold_join, fold_rows=fold_rows)
 
     @contextlib.contextmanager
     def _recording(self, chain, tail):

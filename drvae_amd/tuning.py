@@ -19,12 +19,13 @@ DEFAULTS = {
     'concurrent': 1,     # side chain at all (0: one stream)
     'nll_cs': 1,         # chip-filling heads: their bias gradient folded into the NLL row pass (no column-sum pass of its own; 2: buffers at any size -- tests, with raw_heads=2); -> schedule.heads_route
     'mmd_explicit': 1,   # model-level MMD penalty (use_s extension, rbf_fourier / identity kernels) as explicit launch lists, no autograd inside the step (0: the block-level operators -- tests)
+    'fold_rows': 1,      # the pairs' KL rows formed by ``z2f_post_bwd``, the classifier's data gradient by its forward launch (0: launches of their own -- tests, A/B); -> schedule._step_tail
     'dp_fork': 1,        # captured gradient exchange: the side chain draws the next step's noise behind the join (as in the single-GPU step)
 }
 
 # the values a switch accepts: the default and the ones a test or tool sets
 CHOICES = {'sched': (3, 5), 'fuse_heads': (0, 1), 'raw_heads': (1, 2), 'tail_gate': (1, 2), 'concurrent': (0, 1),
-           'nll_cs': (1, 2), 'mmd_explicit': (0, 1), 'dp_fork': (0, 1)}
+           'nll_cs': (1, 2), 'mmd_explicit': (0, 1), 'dp_fork': (0, 1), 'fold_rows': (0, 1)}
 
 
 def _parse():

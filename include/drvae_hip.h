@@ -122,6 +122,23 @@ typedef struct dv_ymarg {
     int64_t lddq;
 } dv_ymarg;
 
+/* The classifier's data gradient riding on the classifier-head launch (dv_smalln_linear_fwd with a dv_ymarg argument;
+ * train step): the wave that owns row r has stored dqy[r]; it forms the row's d logits from (dqy[r], probs[r]) as
+ * dv_smalln_linear_bwd_data does and writes, for up to two destinations t < n,
+ *   dst_t[r, c] = beta_t*dst_t[r, c] + sum_j dlogit[r,j] * (alpha_t*W[j, col0_t + c] + alpha2_t*W[j, col1_t + c]),  c < ncol_t
+ * (the arithmetic of that launch without its `seg` start: same bits).  n == 0: none */
+typedef struct dv_clf_dgrad {
+    float* dst[2];
+    int64_t ld[2];
+    int32_t col0[2];
+    int32_t ncol[2];
+    float alpha[2];
+    float beta[2];
+    int32_t col1[2];
+    float alpha2[2];
+    int32_t n;
+} dv_clf_dgrad;
+
 typedef struct dv_bump {
     int32_t* c[2];
     int32_t n[2];
@@ -369,6 +386,11 @@ int dv_reparam_bwd_seg(const float* dz, int64_t ldz, const float* eps, int64_t l
  *   dp2[r]  = (g | g*eps*0.5*exp(0.5*lv2)) + [jp >= 0] d KL(q2[jp] || p2[r]) / d p2 * coef[l*Np+jp]*mask
  *   dz1[r] += dp2[r].mu (residual mu2 = z1 + ..., src/blocks.py:357) + (dz1b ? dz1b[r] : 0)
  *   dq2[jp] = sum_l d KL / d q2 * coef*mask                      (mask = free-bits gate on raw)      */
+/* One wave per batch row i, lanes over d; with kl_out / raw_out the row sum of KL(q2[jp] || p2[r]) is formed first, with
+ * the lane mapping and the reduction tree of dv_kl_rows_fwd (same bits), and gates the gradients (weight 1/2 on raw ==
+ * kl_min); with seg_src / z1_dz2f:
+ *   dz1[r] += dp2[r].mu + (((dz1b ? dz1b[r] : 0) + seg_beta * sum_t seg_src[t]) + z1_dz2f * dz2f[r])
+ * -- with seg_beta = 1, z1_dz2f = -1 the bits of dv_smalln_linear_bwd_data's (seg + dlogit W1) - dlogit W2.             */
 /* ABI 11: the operands travel in a descriptor (28 positional arguments before); shapes in the comments */
 typedef struct dv_z2f_desc {
     const float* dz2f;       /* (L*B, Z) or NULL */
@@ -399,6 +421,14 @@ typedef struct dv_z2f_desc {
     int32_t Z;
     const float* prior_coef; /* (Np) or NULL (with prior_raw): the prior-KL gradient of q2 row jp is added to dq2[jp], */
     const float* prior_raw;  /* see dv_prior_kl (kl_min as above) */
+    /* trailing fields (ABI 12, zero = as before): the launch forms the pairs' KL rows itself, and sums fprop rows */
+    float* kl_out;           /* (L*Np) out or NULL (with raw_out): max(raw, kl_min), what dv_kl_rows_fwd(free_bits) writes */
+    float* raw_out;          /* (L*Np) out or NULL: the raw KL; when set the gate reads the launch's own sum, `raw` is unused */
+    const float* seg_src;    /* (rows, >= Z) or NULL (with seg_ptr): a second share of d/dz1, summed per sample row */
+    int64_t ld_seg;
+    const int32_t* seg_ptr;  /* (L*B + 1) row r sums seg_src rows [seg_ptr[r], seg_ptr[r+1]) in index order */
+    float seg_beta;
+    float z1_dz2f;           /* dz1[r] also gets z1_dz2f * dz2f[r]: a classifier on [z1, z2Fz1 - z1] sends -dz2f to z1 */
 } dv_z2f_desc;
 int dv_z2f_post_bwd(const dv_z2f_desc* d, const dv_wait* park, dv_stream_t stream);
 
@@ -584,7 +614,7 @@ int dv_cat_terms_bwd(const float* probs, int64_t ldp, int32_t M, int32_t Y, cons
 int dv_smalln_linear_fwd(const float* a1, int64_t lda1, int32_t K1, const float* a2, int64_t lda2, int32_t K2,
                          const float* W, int64_t ldw, const float* bias, int32_t M, int32_t N, float* logits,
                          int64_t ldl, float* probs, int64_t ldp, const dv_ymarg* ymarg, const dv_wait* park,
-                         const dv_fprop_kl* fprop_kl, dv_stream_t stream);
+                         const dv_fprop_kl* fprop_kl, const dv_clf_dgrad* dgrad, dv_stream_t stream);
 int dv_smalln_linear_bwd_data(const float* dprobs, int64_t lddp, const float* probs, int64_t ldp, const float* W,
                               int64_t ldw, int32_t M, int32_t N, int32_t n_dst, float* const* dst,
                               const int64_t* ld, const int32_t* col0, const int32_t* ncol, const float* alpha,
