@@ -244,16 +244,20 @@ SIGNATURES = {
     'dv_adam_l2': [_p, _p, _p, _p, _i64, C.POINTER(AdamHyper), _p, _p, _i32, _p],
     'dv_adam_l2_gated': [_p, _p, _p, _p, _i64, C.POINTER(AdamHyper), _p, C.POINTER(Wait), _i64, _i64, _p, _i32, _p],
     'dv_adamax_l2': [_p, _p, _p, _p, _i64, C.POINTER(AdamHyper), _p, _p, _i32, _p],
+    'dv_grad_norm_clip': [_p, _i64, _f, _p, _p],
+    'dv_adam_l2_clipped': [_p, _p, _p, _p, _i64, C.POINTER(AdamHyper), _p, _p, _i32, _p],
+    'dv_adamax_l2_clipped': [_p, _p, _p, _p, _i64, C.POINTER(AdamHyper), _p, _p, _i32, _p],
     'dv_flag_publish': [_p, _p, _i32, _p],
     'dv_flag_wait': [_p, _p, _i32, _p, _i32, C.POINTER(Publish), _p],
     'dv_counter_add': [_p, _i32, _i64, _p],
     'dv_counters_add2': [_p, _i32, _i64, _p, _i32, _i64, _p, _p],
     'dv_fill_normal': [_p, _i64, _u64, _p, _p],
     'dv_fill_normal_rows': [_p, _p, _i32, _u64, _p, _p, _p],
+    'dv_fill_noise_rows': [_p, _p, _i32, _u64, _p, _p, _p],
 }
 
 _lib = None
-ABI_VERSION = 12    # DV_ABI_VERSION of include/drvae_hip.h
+ABI_VERSION = 13    # DV_ABI_VERSION of include/drvae_hip.h
 
 
 def load():

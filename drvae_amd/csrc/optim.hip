@@ -57,7 +57,7 @@ struct AdamGate {
     int64_t lo, hi;
 };
 
-// CLIP: the sweep of a step with gradient-norm clipping (dv_adam_l2 with n_halt < 0): ``clip`` is the record the norm pass has
+// CLIP: the sweep of a step with gradient-norm clipping (dv_adam_l2_clipped / dv_adamax_l2_clipped): ``clip`` is the record the norm pass has
 // written -- skip set: nothing is touched (not sticky, no halt word involved); else gscale * coef scales the gradient and the
 // bias corrections count the steps taken.  CLIP = false is the sweep as it ever was (adam_kernel and adam_stream_kernel: the same
 // instructions but for the kernel-argument offsets; adamax_kernel: the same arithmetic, the halt loop scheduled in front of pow()).
@@ -408,8 +408,7 @@ __device__ __forceinline__ void philox_words4(uint32_t& c0, uint32_t& c1, uint32
 // The noise arena of a step with hidden-layer dropout: rows [0, n_normal) of the table are the N(0,1) rows of
 // fill_normal_rows_kernel (same calls, same values); rows [n_normal, n_rows) are KEEP rows -- element (row, col) is 1.0f
 // where word col % 4 of the same Philox block (counter and key laid out as for the normals) is < keep_thr, else 0.0f:
-// an integer compare, no float uniform.  One wave per row, the row kind is wave-uniform.  (Reached through
-// dv_fill_normal_rows with n_rows < 0: the C ABI keeps its entry points.)
+// an integer compare, no float uniform.  One wave per row, the row kind is wave-uniform.  (dv_fill_noise_rows)
 __global__ __launch_bounds__(256) void fill_noise_rows_kernel(float* __restrict__ arena, const int4* __restrict__ desc,
                                                               int n_rows, uint64_t seed, const int32_t* ctr_dev,
                                                               dv_wait park) {
@@ -555,10 +554,10 @@ extern "C" const char* dv_error_string(int code) {
     }
 }
 
-static int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
-                       float eps, float weight_decay, float gscale, const int32_t* step_dev, const AdamGate& gate,
-                       const int32_t* halt, int32_t n_halt, dv_stream_t stream, const dv_clip_record* clip = nullptr) {
-    DV_REQUIRE(n >= 0 && n_halt >= 0 && (halt || n_halt == 0));
+static int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, const dv_adam_hyper* h,
+                       const int32_t* step_dev, const AdamGate& gate, const int32_t* halt, int32_t n_halt,
+                       dv_stream_t stream, const dv_clip_record* clip) {
+    DV_REQUIRE(h != nullptr && n >= 0 && n_halt >= 0 && (halt || n_halt == 0));
     if (n == 0) return DV_OK;
     DV_REQUIRE(p && g && m && v && step_dev);
     auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
@@ -568,20 +567,20 @@ static int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, 
     if (vec4 && gate.flag == nullptr && n >= (int64_t(16) << 20)) {       // far beyond the Infinity Cache: the streaming sweep
         const dim3 grid((unsigned)(blocks > 16384 ? 16384 : blocks));
         if (clip)
-            hipLaunchKernelGGL(adam_stream_kernel<true>, grid, dim3(256), 0, ST(stream), p, g, m, v, n, lr, beta1, beta2, eps,
-                               weight_decay, gscale, step_dev, halt, n_halt, clip);
+            hipLaunchKernelGGL(adam_stream_kernel<true>, grid, dim3(256), 0, ST(stream), p, g, m, v, n, h->lr, h->beta1, h->beta2,
+                               h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt, clip);
         else
-            hipLaunchKernelGGL(adam_stream_kernel<false>, grid, dim3(256), 0, ST(stream), p, g, m, v, n, lr, beta1, beta2, eps,
-                               weight_decay, gscale, step_dev, halt, n_halt, clip);
+            hipLaunchKernelGGL(adam_stream_kernel<false>, grid, dim3(256), 0, ST(stream), p, g, m, v, n, h->lr, h->beta1, h->beta2,
+                               h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt, clip);
         DV_RETURN_LAUNCH();
     }
     if (blocks > 2048) blocks = 2048;
     if (clip)
-        hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, v, n, lr, beta1,
-                           beta2, eps, weight_decay, gscale, step_dev, vec4, gate, halt, n_halt, clip);
+        hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, v, n, h->lr, h->beta1,
+                           h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, vec4, gate, halt, n_halt, clip);
     else
-        hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, v, n, lr, beta1,
-                           beta2, eps, weight_decay, gscale, step_dev, vec4, gate, halt, n_halt, clip);
+        hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, v, n, h->lr, h->beta1,
+                           h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, vec4, gate, halt, n_halt, clip);
     DV_RETURN_LAUNCH();
 }
 
@@ -590,8 +589,8 @@ extern "C" int dv_adam_l2_gated(float* p, const float* g, float* m, float* v, in
                                 const int32_t* halt, int32_t n_halt, dv_stream_t stream) {
     DV_REQUIRE(h != nullptr && gate != nullptr);
     DV_REQUIRE(gate->flag && gate->ctr && gate->err && gate->max_spins > 0 && lo >= 0 && hi >= lo && hi <= n);
-    return adam_launch(p, g, m, v, n, h->lr, h->beta1, h->beta2, h->eps, h->weight_decay, h->gscale, step_dev,
-                       AdamGate{gate->flag, gate->ctr, gate->add, gate->err, gate->max_spins, lo, hi}, halt, n_halt, stream);
+    return adam_launch(p, g, m, v, n, h, step_dev, AdamGate{gate->flag, gate->ctr, gate->add, gate->err, gate->max_spins, lo, hi},
+                       halt, n_halt, stream, nullptr);
 }
 
 static int adamax_launch(float* p, const float* g, float* m, float* u, int64_t n, const dv_adam_hyper* h,
@@ -611,9 +610,10 @@ static int adamax_launch(float* p, const float* g, float* m, float* u, int64_t n
     DV_RETURN_LAUNCH();
 }
 
-// gradient-norm clipping rides on the sweeps' own entry points (n_halt < 0, see the header): ``step_dev`` is a dv_clip_state;
-// p == NULL: the NORM PASS (sum of squares into the workspace behind the state, then the record), else the sweep reading it
-static int clip_norm_pass(const float* g, int64_t n, const dv_adam_hyper* h, dv_clip_state* st, dv_stream_t stream) {
+// gradient-norm clipping: the NORM PASS (sum of squares into the workspace behind the state, then the record) and the two
+// sweeps reading that record; the state's first word is the step they count by
+extern "C" int dv_grad_norm_clip(const float* g, int64_t n, float gscale, dv_clip_state* st, dv_stream_t stream) {
+    DV_REQUIRE(st && (reinterpret_cast<uintptr_t>(st) & 7) == 0);
     DV_REQUIRE(n >= 0 && (g || n == 0) && (reinterpret_cast<uintptr_t>(g) & 3) == 0);
     double* part = reinterpret_cast<double*>(st + 1);
     const int blocks = sumsq_blocks(n);
@@ -621,7 +621,7 @@ static int clip_norm_pass(const float* g, int64_t n, const dv_adam_hyper* h, dv_
         hipLaunchKernelGGL(sumsq_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), g, n, part);
     else
         hipLaunchKernelGGL(sumsq_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), g, n, part);
-    hipLaunchKernelGGL(clip_finalize_kernel, dim3(1), dim3(256), 0, ST(stream), part, blocks, h->gscale, st);
+    hipLaunchKernelGGL(clip_finalize_kernel, dim3(1), dim3(256), 0, ST(stream), part, blocks, gscale, st);
     DV_RETURN_LAUNCH();
 }
 
@@ -630,33 +630,24 @@ static_assert(sizeof(dv_clip_state) == 32 && DV_SUMSQ_PARTIALS(1) == 1 && DV_SUM
 
 extern "C" int dv_adam_l2(float* p, const float* g, float* m, float* v, int64_t n, const dv_adam_hyper* h,
                           const int32_t* step_dev, const int32_t* halt, int32_t n_halt, dv_stream_t stream) {
-    DV_REQUIRE(h != nullptr);
-    if (n_halt < 0) {
-        DV_REQUIRE(step_dev && (reinterpret_cast<uintptr_t>(step_dev) & 7) == 0);
-        dv_clip_state* st = reinterpret_cast<dv_clip_state*>(const_cast<int32_t*>(step_dev));
-        if (p == nullptr) {
-            DV_REQUIRE(!m && !v);
-            return clip_norm_pass(g, n, h, st, stream);
-        }
-        return adam_launch(p, g, m, v, n, h->lr, h->beta1, h->beta2, h->eps, h->weight_decay, h->gscale, &st->step, AdamGate{},
-                           halt, ~n_halt, stream, &st->rec);
-    }
-    return adam_launch(p, g, m, v, n, h->lr, h->beta1, h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, AdamGate{},
-                       halt, n_halt, stream);
+    return adam_launch(p, g, m, v, n, h, step_dev, AdamGate{}, halt, n_halt, stream, nullptr);
+}
+
+extern "C" int dv_adam_l2_clipped(float* p, const float* g, float* m, float* v, int64_t n, const dv_adam_hyper* h,
+                                  const dv_clip_state* st, const int32_t* halt, int32_t n_halt, dv_stream_t stream) {
+    DV_REQUIRE(st && (reinterpret_cast<uintptr_t>(st) & 7) == 0);
+    return adam_launch(p, g, m, v, n, h, &st->step, AdamGate{}, halt, n_halt, stream, &st->rec);
 }
 
 extern "C" int dv_adamax_l2(float* p, const float* g, float* m, float* u, int64_t n, const dv_adam_hyper* h,
                             const int32_t* step_dev, const int32_t* halt, int32_t n_halt, dv_stream_t stream) {
-    if (n_halt < 0) {
-        DV_REQUIRE(h != nullptr && step_dev && (reinterpret_cast<uintptr_t>(step_dev) & 7) == 0);
-        dv_clip_state* st = reinterpret_cast<dv_clip_state*>(const_cast<int32_t*>(step_dev));
-        if (p == nullptr) {
-            DV_REQUIRE(!m && !u);
-            return clip_norm_pass(g, n, h, st, stream);
-        }
-        return adamax_launch(p, g, m, u, n, h, &st->step, halt, ~n_halt, stream, &st->rec);
-    }
     return adamax_launch(p, g, m, u, n, h, step_dev, halt, n_halt, stream, nullptr);
+}
+
+extern "C" int dv_adamax_l2_clipped(float* p, const float* g, float* m, float* u, int64_t n, const dv_adam_hyper* h,
+                                    const dv_clip_state* st, const int32_t* halt, int32_t n_halt, dv_stream_t stream) {
+    DV_REQUIRE(st && (reinterpret_cast<uintptr_t>(st) & 7) == 0);
+    return adamax_launch(p, g, m, u, n, h, &st->step, halt, n_halt, stream, &st->rec);
 }
 
 // Device-side ordering between two concurrently running launch chains (two root branches of one
@@ -714,12 +705,11 @@ extern "C" int dv_counters_add2(int32_t* c1, int32_t n1, int64_t inc1, int32_t* 
     DV_RETURN_LAUNCH();
 }
 
-extern "C" int dv_fill_normal_rows(float* arena, const int32_t* desc, int32_t n_rows_in, uint64_t seed,
-                                   const int32_t* ctr_dev, const dv_wait* park_in, dv_stream_t stream) {
-    // n_rows < 0: a table of -n_rows rows that ends in KEEP rows, followed by its trailer row (see the header)
-    const bool noise = n_rows_in < 0;
-    DV_REQUIRE(n_rows_in > INT32_MIN);
-    const int32_t n_rows = noise ? -n_rows_in : n_rows_in;
+// the two row-keyed fills (dv_fill_noise_rows: the table's trailer sits at row n_rows): the park's validation, the grid -- one
+// wave per row, four rows per workgroup -- and the launch
+static int fill_rows_launch(decltype(&fill_normal_rows_kernel) kernel, float* arena, const int32_t* desc, int32_t n_rows,
+                            uint64_t seed, const int32_t* ctr_dev, const dv_wait* park_in, dv_stream_t stream) {
+    DV_REQUIRE(n_rows >= 0);
     dv_wait park = park_in ? *park_in : dv_wait{nullptr, nullptr, 0, 0, nullptr};
     DV_REQUIRE(park.flag == nullptr || (park.ctr && park.err && park.max_spins > 0));
     if (n_rows == 0) return park.flag ? DV_ERR_UNSUPPORTED : DV_OK;
@@ -727,14 +717,19 @@ extern "C" int dv_fill_normal_rows(float* arena, const int32_t* desc, int32_t n_
     int blocks = (n_rows + 3) / 4;
     if (blocks > 4096) blocks = 4096;
     if (park.flag != nullptr && blocks > 512) blocks = 512;      // a parked grid stays well below the chip's resident capacity
-    if (noise) {
-        hipLaunchKernelGGL(fill_noise_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, ST(stream), arena,
-                           reinterpret_cast<const int4*>(desc), n_rows, seed, ctr_dev, park);
-        DV_RETURN_LAUNCH();
-    }
-    hipLaunchKernelGGL(fill_normal_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, ST(stream), arena,
-                       reinterpret_cast<const int4*>(desc), n_rows, seed, ctr_dev, park);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, ST(stream), arena, reinterpret_cast<const int4*>(desc),
+                       n_rows, seed, ctr_dev, park);
     DV_RETURN_LAUNCH();
+}
+
+extern "C" int dv_fill_normal_rows(float* arena, const int32_t* desc, int32_t n_rows, uint64_t seed,
+                                   const int32_t* ctr_dev, const dv_wait* park, dv_stream_t stream) {
+    return fill_rows_launch(fill_normal_rows_kernel, arena, desc, n_rows, seed, ctr_dev, park, stream);
+}
+
+extern "C" int dv_fill_noise_rows(float* arena, const int32_t* table, int32_t n_rows, uint64_t seed,
+                                  const int32_t* ctr_dev, const dv_wait* park, dv_stream_t stream) {
+    return fill_rows_launch(fill_noise_rows_kernel, arena, table, n_rows, seed, ctr_dev, park, stream);
 }
 
 extern "C" int dv_fill_normal(float* out, int64_t n, uint64_t seed, const int32_t* ctr_dev, dv_stream_t stream) {

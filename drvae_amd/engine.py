@@ -1300,7 +1300,7 @@ class FusedStep(StepSchedule):
             # side-chain half of the sweep for it), behind the exchange in every exchange form.  The norm over the whole live
             # slice -- the pad elements between parameters are zero, always (``ParamArena``) --, the record, the sweep
             assert not (t and (t.adam_gated or t.cap_fork or t.side_adam)), 'a clipped sweep has no gated form'
-            K.clip_norm(a.grad[:n], self.clip_state, gscale=gscale, adamax=cfg.optim_alg == 'adamax')
+            K.clip_norm(a.grad[:n], self.clip_state, gscale=gscale)
             step = K.adamax_l2_clip if cfg.optim_alg == 'adamax' else K.adam_l2_clip
             step(a.param[:n], a.grad[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.clip_state,
                  lr=cfg.learning_rate, weight_decay=cfg.weight_decay, gscale=gscale, halt=self.sync_err)

@@ -1131,7 +1131,7 @@ def adamax_l2(p, g, m, u, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, wei
                                         _stream()), 'dv_adamax_l2')
 
 
-# gradient-norm clipping (``StepConfig.max_grad_norm``) rides on the sweeps' entry points (``n_halt`` < 0, include/drvae_hip.h).
+# gradient-norm clipping (``StepConfig.max_grad_norm``): ``dv_grad_norm_clip`` and the ``_clipped`` sweeps of include/drvae_hip.h.
 # The clip STATE of an engine is one int32 device buffer laid out as ``dv_clip_state`` (``_lib.ClipState``) + workspace: the
 # optimiser step (the engine's ``step_dev`` is this word), max_norm (a double), the record {norm, coef (fp32 bits), skip,
 # n_skipped}, then ``sumsq_partials(n)`` doubles
@@ -1173,38 +1173,30 @@ def clip_record_values(record):
     return dict(norm=float(f[0]), coef=float(f[1]), skipped_last=bool(int(r[2])), n_skipped=int(r[3]))
 
 
-def _clip_halt(halt):
-    hp, hn = _halt(halt)
-    return hp, ~hn
-
-
-def clip_norm(g, state, *, gscale=1.0, adamax=False):
+def clip_norm(g, state, *, gscale=1.0):
     """the norm pass over the contiguous fp32 range ``g`` into ``state``: the sum of squares in double (one partial per
     workgroup), then the record: norm = |gscale| sqrt(sumsq), coef = min(1, max_norm / (norm + 1e-6)), skip (a non-finite sum)
-    and the running count of skipped steps.  Two launches behind one call of the sweep's entry point (p = NULL)"""
+    and the running count of skipped steps.  Two launches (``dv_grad_norm_clip``)"""
     assert g.is_contiguous() and state.numel() >= CLIP_STATE_WORDS + 2 * sumsq_partials(g.numel())
-    h = _lib.AdamHyper(gscale=gscale)
-    fn = _lib.load().dv_adamax_l2 if adamax else _lib.load().dv_adam_l2
-    _lib.check(fn(None, _f32(g), None, None, g.numel(), C.byref(h), _i32(state), None, ~0, _stream()),
-               'dv_adamax_l2 (clip norm)' if adamax else 'dv_adam_l2 (clip norm)')
+    _lib.check(_lib.load().dv_grad_norm_clip(_f32(g), g.numel(), gscale, _i32(state), _stream()), 'dv_grad_norm_clip')
 
 
 def adam_l2_clip(p, g, m, v, state, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None):
     """``adam_l2`` reading the record of the clip state (whose first word is the step): skipped when the record says so, else
     the gradient scaled by fl32(gscale * coef) and t = step - n_skipped.  No gated form."""
     assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
-    hp, hn = _clip_halt(halt)
+    hp, hn = _halt(halt)
     h = _lib.AdamHyper(lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, gscale=gscale)
-    _lib.check(_lib.load().dv_adam_l2(_f32(p), _f32(g), _f32(m), _f32(v), p.numel(), C.byref(h), _i32(state), hp, hn,
-                                      _stream()), 'dv_adam_l2 (clipped)')
+    _lib.check(_lib.load().dv_adam_l2_clipped(_f32(p), _f32(g), _f32(m), _f32(v), p.numel(), C.byref(h), _i32(state), hp, hn,
+                                              _stream()), 'dv_adam_l2_clipped')
 
 
 def adamax_l2_clip(p, g, m, u, state, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None):
     assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and u.is_contiguous()
-    hp, hn = _clip_halt(halt)
+    hp, hn = _halt(halt)
     h = _lib.AdamHyper(lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, gscale=gscale)
-    _lib.check(_lib.load().dv_adamax_l2(_f32(p), _f32(g), _f32(m), _f32(u), p.numel(), C.byref(h), _i32(state), hp, hn,
-                                        _stream()), 'dv_adamax_l2 (clipped)')
+    _lib.check(_lib.load().dv_adamax_l2_clipped(_f32(p), _f32(g), _f32(m), _f32(u), p.numel(), C.byref(h), _i32(state), hp, hn,
+                                                _stream()), 'dv_adamax_l2_clipped')
 
 
 def flag_publish(flag, ctr, add=1):
@@ -1244,7 +1236,7 @@ def fill_normal_rows(arena, desc, seed, ctr_dev=None, park=None):
 
 
 def keep_threshold(dropout_rate):
-    """``keep_thr`` of the keep rows (``dv_fill_normal_rows``, n_rows < 0): floor((1 - dropout_rate) * 2^32) in double, as
+    """``keep_thr`` of the keep rows (``dv_fill_noise_rows``): floor((1 - dropout_rate) * 2^32) in double, as
     uint32; the keep probability of a hidden unit is exactly ``keep_threshold(rate) / 2**32``"""
     assert 0.0 <= dropout_rate < 1.0
     return min(int(math.floor((1.0 - float(dropout_rate)) * 4294967296.0)), 0xFFFFFFFF)
@@ -1261,10 +1253,10 @@ def noise_table(desc, n_normal, keep_thr):
 
 def fill_noise_rows(arena, table, seed, ctr_dev=None, park=None):
     """``fill_normal_rows`` over a ``noise_table``: the same N(0,1) values in its normal rows, 1.0 / 0.0 keep masks with keep
-    probability ``keep_thr / 2**32`` in its keep rows -- ``dv_fill_normal_rows`` with n_rows < 0, a kernel of its own"""
+    probability ``keep_thr / 2**32`` in its keep rows -- ``dv_fill_noise_rows``, a kernel of its own"""
     assert arena.is_contiguous() and table.dim() == 2 and table.shape[1] == 4 and table.shape[0] >= 1 and table.is_contiguous()
-    _lib.check(_lib.load().dv_fill_normal_rows(_f32(arena), _i32(table), -(table.shape[0] - 1), seed, _i32(ctr_dev), _wait(park),
-                                               _stream()), 'dv_fill_normal_rows (keep rows)')
+    _lib.check(_lib.load().dv_fill_noise_rows(_f32(arena), _i32(table), table.shape[0] - 1, seed, _i32(ctr_dev), _wait(park),
+                                              _stream()), 'dv_fill_noise_rows')
 
 
 def fill_normal(out, seed, ctr_dev=None):

@@ -30,7 +30,7 @@ extern "C" {
 
 typedef void* dv_stream_t;
 
-#define DV_ABI_VERSION 12
+#define DV_ABI_VERSION 13
 
 enum { DV_OK = 0, DV_ERR_ARG = -1, DV_ERR_LAUNCH = -2, DV_ERR_UNSUPPORTED = -3 };
 
@@ -1089,22 +1089,21 @@ int dv_adamax_l2(float* p, const float* g, float* m, float* u, int64_t n, const 
                  const int32_t* step_dev, const int32_t* halt, int32_t n_halt, dv_stream_t stream);
 /* Global-norm gradient clipping and the non-finite guard of the optimiser sweep (EXTENSION: the reference has no
  * counterpart; semantics of torch.nn.utils.clip_grad_norm_(params, max_norm, norm_type=2) in front of the optimisers above).
- * Reached through dv_adam_l2 / dv_adamax_l2 with n_halt < 0 (the C ABI keeps its entry points): ~n_halt is the number of
- * halt pairs, and step_dev points at a dv_clip_state in device memory, 8-byte aligned, owned by the caller and zeroed
- * once but for max_norm: its first word is the step counter the sweep reads (bump it as ever), DV_SUMSQ_PARTIALS(n)
- * doubles of workspace follow it.  Nothing leaves the device.
- *   p == NULL (m, v / u NULL too): the NORM PASS over the n contiguous floats at g, two launches.  (1) one double partial
- *       per workgroup = the sum of g[i]^2 over its elements, each element widened to double first; DV_SUMSQ_PARTIALS(n)
- *       workgroups, a function of n alone, at most 1024.  No atomics: the value of every partial is a function of n and of
- *       the pointer's offset within 16 bytes -- bitwise the same from run to run and from rank to rank.  Non-temporal
- *       loads from n >= 16 Mi elements on (the streaming sweep's threshold).  g is only read.  (2) sumsq = the partials
- *       summed in index order; norm = |h->gscale| sqrt(sumsq); coef = min(1, max_norm / (norm + 1e-6)), in double,
+ * Three entry points around a dv_clip_state in device memory, 8-byte aligned, owned by the caller and zeroed once but for
+ * max_norm: its first word is the step counter the sweeps read (bump it as ever), DV_SUMSQ_PARTIALS(n) doubles of
+ * workspace follow it.  Nothing leaves the device.
+ *   dv_grad_norm_clip: the NORM PASS over the n contiguous floats at g (n == 0: g may be NULL), two launches.  (1) one double
+ *       partial per workgroup = the sum of g[i]^2 over its elements, each element widened to double first;
+ *       DV_SUMSQ_PARTIALS(n) workgroups, a function of n alone, at most 1024.  No atomics: the value of every partial is a
+ *       function of n and of the pointer's offset within 16 bytes -- bitwise the same from run to run and from rank to rank.
+ *       Non-temporal loads from n >= 16 Mi elements on (the streaming sweep's threshold).  g is only read.  (2) sumsq = the
+ *       partials summed in index order; norm = |gscale| sqrt(sumsq); coef = min(1, max_norm / (norm + 1e-6)), in double,
  *       stored as fp32.  sumsq not finite (some g[i] is inf or NaN -- finite fp32 inputs cannot overflow the double sum):
  *       skip = 1, coef = 0, n_skipped += 1; else skip = 0.  max_norm > 0; +inf: no clipping (coef = 1), the guard alone.
- *   p != NULL: the sweep reading the record: skip set -> p, m, v / u are left as they are (not sticky, no halt word is
- *       written); else the gradient is scaled by fl32(h->gscale * coef) where the plain sweep scales by h->gscale (coef ==
- *       1.0f: the plain sweep's bits) and the bias corrections use t = step - n_skipped: a skipped step leaves no trace
- *       in the optimiser state.  There is no gated form. */
+ *   dv_adam_l2_clipped / dv_adamax_l2_clipped: the sweeps above, counting by st->step and reading st->rec: skip set -> p, m,
+ *       v / u are left as they are (not sticky, no halt word is written); else the gradient is scaled by fl32(h->gscale *
+ *       coef) where the plain sweep scales by h->gscale (coef == 1.0f: the plain sweep's bits) and the bias corrections use
+ *       t = step - n_skipped: a skipped step leaves no trace in the optimiser state.  There is no gated form. */
 typedef struct dv_clip_record {
     float norm;                     /* |gscale| * 2-norm of the gradient range of the last norm pass */
     float coef;                     /* its clip coefficient, in [0, 1] */
@@ -1120,6 +1119,11 @@ typedef struct dv_clip_state {      /* 32 bytes, then the workspace */
 #define DV_SUMSQ_PER_BLOCK 8192     /* elements of g per workgroup of the norm pass, below the cap */
 #define DV_SUMSQ_MAX_BLOCKS 1024    /* the cap */
 #define DV_SUMSQ_PARTIALS(n) ((n) <= DV_SUMSQ_PER_BLOCK ? 1 : (n) > DV_SUMSQ_PER_BLOCK * (int64_t)(DV_SUMSQ_MAX_BLOCKS - 1) ? DV_SUMSQ_MAX_BLOCKS : ((n) + DV_SUMSQ_PER_BLOCK - 1) / DV_SUMSQ_PER_BLOCK)
+int dv_grad_norm_clip(const float* g, int64_t n, float gscale, dv_clip_state* st, dv_stream_t stream);
+int dv_adam_l2_clipped(float* p, const float* g, float* m, float* v, int64_t n, const dv_adam_hyper* h,
+                       const dv_clip_state* st, const int32_t* halt, int32_t n_halt, dv_stream_t stream);
+int dv_adamax_l2_clipped(float* p, const float* g, float* m, float* u, int64_t n, const dv_adam_hyper* h,
+                         const dv_clip_state* st, const int32_t* halt, int32_t n_halt, dv_stream_t stream);
 int dv_counter_add(int32_t* counter_lo_hi, int32_t n_words, int64_t inc, dv_stream_t stream);
 /* Joins folded into their consumers: dv_z2f_post_bwd, dv_reparam_bwd_seg and dv_rows_segment_sum take an optional `park`
  * (every workgroup of the launch first parks like dv_flag_wait: the first consumer of another chain's
@@ -1161,21 +1165,21 @@ int dv_fill_normal(float* out, int64_t n, uint64_t seed, const int32_t* ctr_dev,
  * row} (int32 x 4, 16-B aligned); element (row, col) = Philox(key = seed (^ ctr_dev[1] in the high word),
  * counter = (col/4, global row, draw id, ctr_dev[0]))[col % 4] through Box-Muller.  ctr_dev counts draw
  * EVENTS (one per train step: advance it by 1), so every rank holds the same value; a rank that owns rows
- * [rB, (r+1)B) of the global minibatch draws exactly the values a single process would draw for them.
- * n_rows < 0 (hidden-layer dropout of the train step): the table has -n_rows rows and ENDS in KEEP rows; one more row
- * behind it, the trailer {n_keep, keep_thr (the uint32's bits), 0, 0}, says how many (counted from the table's end, so the
- * table may be handed over from any row on).  The rows in front of the keep rows are written exactly as above, bit for bit
- * (another kernel; a call with n_rows >= 0 launches what it always did).  Element (row, col) of a keep row is 1.0f if word
- * col % 4 of Philox4x32-10(counter = (col/4, global row, draw id, ctr_dev[0]), key = (seed_lo, seed_hi ^ ctr_dev[1])) --
- * counter and key laid out as for the normals -- is < keep_thr (unsigned compare), else 0.0f.  keep_thr =
- * floor((1 - dropout_rate) * 2^32) as uint32, computed by the HOST in double: the keep probability is exactly
- * keep_thr / 2^32, no float uniform is involved (tests/philox_ref.py reproduces a mask exactly).  Same launch shape, same
- * `park`; the counter is read behind the wait.  (A form of this entry point, not one of its own: the ABI keeps its 80.)
- * The trailer is DEVICE memory: the host cannot validate it.  The kernel clamps n_keep to [0, -n_rows]; a wrong count or
- * threshold inside that range draws rows of the wrong kind, it writes nothing outside the described elements.  (Before this
- * form existed a negative n_rows was DV_ERR_ARG; INT32_MIN still is.) */
+ * [rB, (r+1)B) of the global minibatch draws exactly the values a single process would draw for them.  n_rows == 0: no launch. */
 int dv_fill_normal_rows(float* arena, const int32_t* desc, int32_t n_rows, uint64_t seed, const int32_t* ctr_dev,
                         const dv_wait* park, dv_stream_t stream);
+/* The noise arena of a step with hidden-layer dropout: `table` = n_rows descriptor rows as above that END in KEEP rows, and one
+ * more row behind them, the trailer {n_keep, keep_thr (the uint32's bits), 0, 0}: how many, counted from the table's end (so
+ * the table may be handed over from any row on).  The rows in front of the keep rows are written as dv_fill_normal_rows
+ * writes them, bit for bit (another kernel).  Element (row, col) of a keep row is 1.0f if word col % 4 of Philox4x32-10(counter
+ * = (col/4, global row, draw id, ctr_dev[0]), key = (seed_lo, seed_hi ^ ctr_dev[1])) -- counter and key laid out as for the
+ * normals -- is < keep_thr (unsigned compare), else 0.0f.  keep_thr = floor((1 - dropout_rate) * 2^32) as uint32, computed by
+ * the HOST in double: the keep probability is exactly keep_thr / 2^32, no float uniform is involved (tests/philox_ref.py
+ * reproduces a mask exactly).  Same launch shape, same `park`; the counter is read behind the wait.  The trailer is DEVICE
+ * memory: the host cannot validate it.  The kernel clamps n_keep to [0, n_rows]; a wrong count or threshold inside that range
+ * draws rows of the wrong kind, it writes nothing outside the described elements. */
+int dv_fill_noise_rows(float* arena, const int32_t* table, int32_t n_rows, uint64_t seed, const int32_t* ctr_dev,
+                       const dv_wait* park, dv_stream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -1,4 +1,4 @@
-"""Global-norm gradient clipping of the fused step (the norm pass of ``dv_adam_l2`` / ``dv_adamax_l2``, ``n_halt < 0``; drvae_amd/csrc/optim.hip) below
+"""Global-norm gradient clipping of the fused step (the norm pass, ``dv_grad_norm_clip``; drvae_amd/csrc/optim.hip) below
 model level: the float64 reference of the clip record, its bound, the value classes of the device test and two faulty
 emulations the CPU file (tests/test_clip_cpu.py) proves the checks against.  tests/test_gpu_clip.py holds the device to the
 same reference.  Plain numpy on the host: no device, no library.

@@ -14,7 +14,7 @@ from tests import kernel_ref
 CALLS = {'clip_norm': 0, 'adam_l2_clip': 0, 'adamax_l2_clip': 0}
 
 
-def clip_norm(g, state, *, gscale=1.0, adamax=False):
+def clip_norm(g, state, *, gscale=1.0):
     """the whole double sum goes into the first partial (one per 8192-element share would do), the partials are summed in
     index order, the record is written"""
     import drvae_amd.kernels as K

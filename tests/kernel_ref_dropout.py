@@ -33,7 +33,7 @@ def keep_rows(desc, keep_thr, seed, event):
 
 
 def fill_noise_rows(arena, table, seed, ctr_dev=None, park=None):
-    """the keep-row form of dv_fill_normal_rows as specified: ``table`` = descriptor rows + the trailer row {number of keep
+    """dv_fill_noise_rows as specified: ``table`` = descriptor rows + the trailer row {number of keep
     rows at the end, keep_thr's bits, 0, 0}; the rows in front as ``kernel_ref.fill_normal_rows``, the rest keep masks"""
     CALLS['fill_noise_rows'] += 1
     desc, tr = table[:-1], table[-1].tolist()

@@ -28,7 +28,7 @@ def lib():
 
 def test_header_declares_the_whole_abi():
     decls = _header_decls()
-    assert len(decls) >= 27
+    assert len(decls) == 84       # recorded, not budgeted: a new launch gets an entry point and this number moves
     from drvae_amd import _lib
     assert set(decls) == set(_lib.SIGNATURES), set(decls) ^ set(_lib.SIGNATURES)
     for name, n in decls.items():
@@ -39,7 +39,7 @@ def test_library_exports_every_symbol(lib):
     for name in _header_decls():
         assert hasattr(lib, name), name
     from drvae_amd import _lib
-    assert lib.dv_abi_version() == _lib.ABI_VERSION == 12
+    assert lib.dv_abi_version() == _lib.ABI_VERSION == 13
     assert 'dv_arm_park' not in _lib.SIGNATURES and not hasattr(lib, 'dv_arm_park')     # no armed (hidden) state
     assert lib.dv_error_string(0) == b'ok'
     assert lib.dv_error_string(-1) == b'invalid argument'
@@ -158,6 +158,28 @@ def test_argument_validation_without_gpu(lib):
     assert lib.dv_adam_l2(None, None, None, None, 8, None, None, None, 0, None) == -1            # no hyper-parameters
     assert lib.dv_adam_l2_gated(None, None, None, None, 8, C.byref(_lib.AdamHyper(lr=1e-3)), None, None, 0, 8, None, 0, None) == -1
     assert lib.dv_adamax_l2(None, None, None, None, 8, None, None, None, 0, None) == -1
+    # a negative halt count / row count is an error, not another form of the call
+    # Every other argument is valid and the sizes are 0, so the tested argument alone decides: the same call with it put
+    # right returns 0, still without a launch.  (a, odd: addresses that are looked at and never dereferenced)
+    hy, a, odd = C.byref(_lib.AdamHyper(lr=1e-3)), 0x1000, 0x1004
+    for fn in (lib.dv_adam_l2, lib.dv_adamax_l2):
+        assert fn(a, a, a, a, 0, hy, a, None, 0, None) == 0
+        assert fn(a, a, a, a, 0, hy, a, None, -1, None) == -1
+    # the clipped sweeps: no state, a state that is not 8-byte aligned, a negative halt count
+    for fn in (lib.dv_adam_l2_clipped, lib.dv_adamax_l2_clipped):
+        assert fn(a, a, a, a, 0, hy, a, None, 0, None) == 0
+        assert fn(a, a, a, a, 0, hy, None, None, 0, None) == -1
+        assert fn(a, a, a, a, 0, hy, odd, None, 0, None) == -1
+        assert fn(a, a, a, a, 0, hy, a, None, -1, None) == -1
+    # the norm pass launches even at n == 0, so it has no such twin: its state is the one argument that can be wrong here
+    assert lib.dv_grad_norm_clip(None, 0, 1.0, None, None) == -1
+    assert lib.dv_grad_norm_clip(None, 0, 1.0, odd, None) == -1
+    # the two fills: a negative row count (INT32_MIN, which cannot be negated, among them); rows to draw and no table
+    for fn in (lib.dv_fill_normal_rows, lib.dv_fill_noise_rows):
+        assert fn(a, a, 0, 0, None, None, None) == 0
+        assert fn(a, a, -3, 0, None, None, None) == -1
+        assert fn(a, a, -2 ** 31, 0, None, None, None) == -1
+        assert fn(a, None, 4, 0, None, None, None) == -1
     assert lib.dv_recon_rows(C.byref(_lib.ReconRows(M=4, X=8)), None) == -1          # no operands
     assert lib.dv_recon_rows(C.byref(_lib.ReconRows(M=4, X=4096)), None) == -3       # beyond the resident width
     m = _lib.BatchMasks(Np=9, n_tot=4.0)                           # more pair slots than rows

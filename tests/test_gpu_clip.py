@@ -456,7 +456,7 @@ def test_a_nan_input_skips_one_replay_and_training_goes_on(dev, name):
 
 
 # ------------------------------------------------------------------------------------------------ 7. the launch list
-CLIP_NAMES = ('dv_adam_l2 (clip norm)', 'dv_adam_l2 (clipped)', 'dv_adamax_l2 (clip norm)', 'dv_adamax_l2 (clipped)')
+CLIP_NAMES = ('dv_grad_norm_clip', 'dv_adam_l2_clipped', 'dv_adamax_l2_clipped')
 
 
 @pytest.mark.parametrize('kind', ['drvae', 'pvae', 'vfae'])

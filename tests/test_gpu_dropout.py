@@ -1,4 +1,4 @@
-"""-m gpu: hidden-layer dropout of the fused train step on the device -- the keep-row form of ``dv_fill_normal_rows`` element by element against the
+"""-m gpu: hidden-layer dropout of the fused train step on the device -- ``dv_fill_noise_rows`` element by element against the
 numpy Philox reference, one chain with device-drawn masks against float64, the model step with column-constant masks
 (tests/test_dropout_cpu.py on the device, eager and captured), finite differences, fresh masks per step, and the rate-0 step's
 launch list."""
@@ -20,7 +20,7 @@ from tests.test_dropout_cpu import (STEP_CASES, compare_step, dropped_vs_folded,
 pytestmark = pytest.mark.gpu
 
 SENTINEL = -7.25
-NOISE = 'dv_fill_normal_rows (keep rows)'        # what the keep-row form of the draw is called in the launch lists
+NOISE = 'dv_fill_noise_rows'        # the draw of a step with keep rows in the launch lists
 
 
 @pytest.fixture(scope='module')
@@ -477,8 +477,8 @@ def test_fit_with_dropout_trains_and_evaluates_undropped(dev, kind, tmp_path, mo
     perf, _ = model.evaluate_performance_on_dataset(va)
     assert all(np.isfinite(float(v)) for v in perf['losses'].values())
     assert bool(torch.isfinite(model.engine().arena.param).all())
-    assert names['eval'] and 'dv_mask_scale' not in names['eval'] and not [w for w in names['eval'] if 'keep rows' in w]
-    assert 'dv_mask_scale' in names['train'] and 'dv_fill_normal_rows (keep rows)' in names['train']
+    assert names['eval'] and 'dv_mask_scale' not in names['eval'] and NOISE not in names['eval']
+    assert 'dv_mask_scale' in names['train'] and NOISE in names['train']
 
 
 # ------------------------------------------------------------------------------------------ 6. rate 0
@@ -507,7 +507,7 @@ def _captured_launch_names(eng, monkeypatch):
 def test_rate_zero_step_launches_what_it_always_did(dev, kind, monkeypatch):
     """the captured step at the benchmark's batch shape: at rate 0 no launch of the feature appears (its count is guarded by
     tests/test_gpu_engine.py); in the one-graph schedule, where both steps draw at their head, the dropped step IS the rate-0
-    step plus one ``dv_mask_scale`` per site and pass, with the keep-row form of the draw in the draw's place"""
+    step plus one ``dv_mask_scale`` per site and pass, with ``dv_fill_noise_rows`` in the draw's place"""
     from tests.test_gpu_x3 import tuned
     spec = M.ModelSpec(kind=kind, L=1 if kind == 'pvae' else 2)
     params = M.init_params(spec, 3, as_numpy=True)

@@ -23,7 +23,7 @@ def test_abi_is_additive_and_the_descriptor_matches_the_header():
     body = re.sub(r'/\*.*?\*/', '', body, flags=re.S)
     names = [re.sub(r'.*[\s\*]', '', part.strip()) for st in body.split(';') if st.strip() for part in st.split(',')]
     assert names == [f[0] for f in _lib.MmdGrouped._fields_]
-    assert _lib.ABI_VERSION == 12 and int(re.search(r'#define DV_ABI_VERSION (\d+)', src).group(1)) == 12
+    assert _lib.ABI_VERSION == int(re.search(r'#define DV_ABI_VERSION (\d+)', src).group(1))
     for name in ('dv_nuisance_feed', 'dv_mmd_grouped_fwd', 'dv_mmd_grouped_bwd'):
         assert name in _lib.SIGNATURES
 

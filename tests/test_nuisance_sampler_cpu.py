@@ -33,12 +33,11 @@ def test_abi_grows_by_two_entry_points_and_the_descriptor_matches_the_header():
     src = _header()
     assert _struct_fields(src, 'dv_mmd_masked_desc') == [f[0] for f in _lib.MmdMasked._fields_]
     assert _struct_fields(src, 'dv_mmd_grouped_desc') == [f[0] for f in _lib.MmdGrouped._fields_]      # untouched
-    assert _lib.ABI_VERSION == 12 and int(re.search(r'#define DV_ABI_VERSION (\d+)', src).group(1)) == 12
-    assert len(_lib.SIGNATURES) == 80
+    assert _lib.ABI_VERSION == int(re.search(r'#define DV_ABI_VERSION (\d+)', src).group(1))
     for name in ('dv_mmd_masked_fwd', 'dv_mmd_masked_bwd'):
         assert len(_lib.SIGNATURES[name]) == 2
     decl = re.sub(r'/\*.*?\*/', '', src, flags=re.S)
-    assert len(set(re.findall(r'(?:int|const char\*)\s+(dv_\w+)\s*\(', decl))) == 80
+    assert set(re.findall(r'(?:int|const char\*)\s+(dv_\w+)\s*\(', decl)) == set(_lib.SIGNATURES)
     import drvae_amd.kernels as K
     for name, val in K.MMD_MASKED_MODEL.items():
         assert int(re.search(r'#define DV_MMD_GROUPS_%s (\d+)' % name.upper(), src).group(1)) == val

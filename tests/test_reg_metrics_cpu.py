@@ -2,6 +2,7 @@
 two-pass arithmetic (tests/kernel_ref_reg.py) against the reference's own numbers (the kernel itself:
 tests/test_gpu_reg_metrics.py)."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -15,7 +16,9 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 def test_entry_point_is_declared_and_the_abi_is_additive():
     from drvae_amd import _lib
     assert 'dv_reg_metrics' in _lib.SIGNATURES and len(_lib.SIGNATURES['dv_reg_metrics']) == 9
-    assert _lib.ABI_VERSION == 12
+    with open(os.path.join(os.path.dirname(os.path.dirname(GOLDEN)), 'include', 'drvae_hip.h')) as f:
+        src = f.read()
+    assert _lib.ABI_VERSION == int(re.search(r'#define DV_ABI_VERSION (\d+)', src).group(1))
 
 
 def test_entry_point_rejects_bad_arguments_without_gpu():

@@ -232,4 +232,4 @@ def test_abi_surface_without_a_device():
     assert ok(desc(64, 64, 62, 1, 1, 64, 64, 64, flags=3)) == 1 and ok(desc(64, 64, 62, 1, 1, 64, 64, 64, flags=1)) == 0
     assert ok(desc(64, 64, 62, 1, 0, 64, 64, 64, flags=1)) == 1 and ok(desc(64, 64, 62, 1, 0, 64, 64, 64, flags=2)) == 0
     assert ok(desc(64, 64, 62, 0, 0, 64, 64, 64)) == 1       # (rows along M / N: no chunk straddles K)
-    assert lib.dv_abi_version() == 12
+    assert lib.dv_abi_version() == _lib.ABI_VERSION

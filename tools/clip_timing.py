@@ -176,8 +176,8 @@ def report(results):
     lines += ['A clipped step needs every gradient final in front of the norm launch: where the switch-off step runs the',
               'classifier\'s weight gradient, the decoder heads\' half of the sweep, the loss scalars and the next step\'s draw on',
               'the side chain behind the join (`dv_adam_l2_gated` on the main chain, a second `dv_adam_l2` on the side chain), the',
-              'clipped step keeps all of it in front of the join and sweeps the whole arena once, ungated (`dv_adam_l2 (clipped)`),',
-              'behind the norm pass (`dv_adam_l2 (clip norm)`: one call, two launches -- the sum of squares and its finalisation).', '']
+              'clipped step keeps all of it in front of the join and sweeps the whole arena once, ungated (`dv_adam_l2_clipped`),',
+              'behind the norm pass (`dv_grad_norm_clip`: one call, two launches -- the sum of squares and its finalisation).', '']
     return '\n'.join(lines)
 
 

@@ -136,7 +136,7 @@ def report(results):
                      100.0 * (b - a) / a, b - a,
                      ', '.join('%s %+d' % kv for kv in r['added'].items()) or 'none'), '']
     lines += ['A plan with sites draws at the head of its step (the side chain does not draw ahead: the encoder backward reads its',
-              'masks), so the plain `dv_fill_normal_rows` leaves the list and its keep-row form joins it, next to one `dv_mask_scale` per',
+              'masks), so the plain `dv_fill_normal_rows` leaves the list and `dv_fill_noise_rows` joins it, next to one `dv_mask_scale` per',
               'site and pass.', '']
     return '\n'.join(lines)
 
