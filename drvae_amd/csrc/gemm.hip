@@ -20,6 +20,7 @@
 //   T32K: 32x32x64 tile, the 4 waves split K and reduce through LDS  (small M*N: 4x the workgroups)
 //   T128: 128x128x32 tile, 2x2 waves, 2x2 accumulators each          (wide config)
 #include "gemm_common.inc"
+#include "heads_route.h"
 
 namespace {
 
@@ -67,22 +68,27 @@ __device__ __forceinline__ float4 ld_edge(const Operand& o, int line, int pos) {
 // first of the RPT consecutive rows of a paired-heads tile that the 16- / 32-lane group `grp` of the epilogue owns.  Two
 // neighbouring groups share a 32-lane LDS access; with the reduction buffer's row stride of BN + 1 floats, rows r and
 // r + RPT put them on overlapping banks (0.11-0.22 LDS bank conflicts per access in the round-4 counters) -- half a tile
-// apart (BM / 2 rows = 16 banks) they are disjoint.  A bijection of the groups onto the tile's rows.
+// apart (BM / 2 rows = 16 banks) they are disjoint.  A bijection of the groups onto the tile's rows.  (The 16-row tile's
+// 8-lane groups, row stride 17 floats: rows r and r + 8 are 8 banks apart -- disjoint as well.)
 template <int BM, int RPT>
 __device__ __forceinline__ int heads_row0(int grp) { return (grp & 1) * (BM / 2) + (grp >> 1) * RPT; }
 
 // Epilogue of a paired-heads tile: thread -> (column c of the half tile, RPT consecutive rows); both heads of
 // an element are reduced over the KS partial sums by the same thread, pass through the DV_EPI_FWD column
 // epilogue, and feed the row work of the mode (see dv_heads_epi in drvae_hip.h).
+// A tile with fewer elements than the workgroup has threads (16 x (8 + 8) on 512: SL = 4) gives every element SL threads,
+// "slots": each forms the element's two heads (the same sums in the same order: the same bits), slot 0 stores them, and
+// slot j takes the entries j, j + SL, ... of the row's segment -- a row with up to SL sample rows is fanned out without a
+// loop.  Sample mode only.
 template <int BM, int BN, int KS, int NT>
 __device__ __forceinline__ void heads_epilogue(const dv_gemm_desc& g, const dv_heads_epi& he, const float* red, int m0,
                                                int tn, int tiles_n, int pre_s0, int pre_s1) {
-    constexpr int HB = BN / 2, RPT = BM / (NT / HB);
-    constexpr bool PRE = (KS == 8 && BN == 32);      // (segment bounds of the thread's one row loaded by the caller)
+    constexpr int HB = BN / 2, SL = NT / HB > BM ? NT / HB / BM : 1, NP = NT / SL, RPT = BM / (NP / HB);
+    constexpr bool PRE = (KS == 8 && (BN == 32 || BN == 16));      // (segment bounds of the thread's one row loaded by the caller)
     static_assert(!PRE || RPT == 1, "prefetched bounds: one row per thread");
-    static_assert((HB == 32 || HB == 16) && RPT >= 1, "half tile = 16 or 32 adjacent lanes");
-    static_assert((NT / HB) % 2 == 0 && (BM / 2) % RPT == 0, "row groups come in pairs");
-    const int tid = threadIdx.x, c = tid % HB, r0 = heads_row0<BM, RPT>(tid / HB);
+    static_assert((HB == 32 || HB == 16 || HB == 8) && RPT >= 1, "half tile = 8, 16 or 32 adjacent lanes");
+    static_assert((NP / HB) % 2 == 0 && (BM / 2) % RPT == 0 && NP * SL == NT, "row groups come in pairs");
+    const int tid = threadIdx.x, slot = tid / NP, c = tid % HB, r0 = heads_row0<BM, RPT>((tid % NP) / HB);
     const int col0 = tn * HB + c, col1 = g.split + col0;
     const bool ok = col0 < g.split && col1 < g.N;
     const int cc0 = ok ? col0 : g.split - 1, cc1 = ok ? col1 : g.N - 1;
@@ -109,7 +115,7 @@ __device__ __forceinline__ void heads_epilogue(const dv_gemm_desc& g, const dv_h
         }
         float a0 = dv_act(g.act0, v0 * g.alpha * sc0 + bi0) + g.shift0;
         if (use_res) a0 += g.resid[(int64_t)rc * g.ldr + cc0];
-        if (he.mode == DV_HEADS_NLL && g.act1 == DV_ACT_SOFTPLUS) {
+        if (SL == 1 && he.mode == DV_HEADS_NLL && g.act1 == DV_ACT_SOFTPLUS) {
             // the decoder's sigma head on hardware transcendentals (one exp, two logs, two reciprocals per element):
             //   p = pre-activation, e = exp(-|p|): softplus(p) = max(p, 0) + log1p(e), sigmoid(p) = (p >= 0 ? 1 : e) / (1 + e)
             const float pre = v1 * g.alpha * sc1 + bi1;
@@ -132,15 +138,17 @@ __device__ __forceinline__ void heads_epilogue(const dv_gemm_desc& g, const dv_h
             continue;
         }
         const float a1 = dv_act(g.act1, v1 * g.alpha * sc1 + bi1) + g.shift1;
-        if (he.mode == DV_HEADS_SAMPLE) {
+        if (SL > 1 || he.mode == DV_HEADS_SAMPLE) {
             if (ok && rok) {
-                g.C[(int64_t)row * g.ldc + col0] = a0;
-                g.C[(int64_t)row * g.ldc + col1] = a1;
+                if (slot == 0) {
+                    g.C[(int64_t)row * g.ldc + col0] = a0;
+                    g.C[(int64_t)row * g.ldc + col1] = a1;
+                }
                 if (row < he.n_src) {
                     const float std_ = expf(0.5f * a1);
                     const int s0 = he.seg_ptr ? (PRE ? pre_s0 : he.seg_ptr[row]) : row;
                     const int s1 = he.seg_ptr ? (PRE ? pre_s1 : he.seg_ptr[row + 1]) : row + 1;
-                    for (int t = s0; t < s1; ++t) {
+                    for (int t = s0 + slot; t < s1; t += SL) {
                         const int64_t s = he.seg_rows ? he.seg_rows[t] : t;
                         const float z = he.eps[s * he.lde + col0] * std_ + a0;
                         he.out[s * he.ldo + col0] = z;
@@ -905,6 +913,46 @@ __global__ __launch_bounds__(64 * KS, WPS) void gemm_heads_pipe_kernel(const dv_
     gemm_body<BM, BN, BK, 1, 1, KS, true, true, true, false, PS>(g, lc, smem, blockIdx.x, gridDim.x, &he);
 }
 
+// Paired heads, sample mode, on 16 x (8 + 8) tiles: four times the workgroups of the 32-row tile for the launches whose
+// grids leave most of the chip idle (encoder heads at cfg 2: 49 -> 182), a quarter of the matrix work per workgroup on
+// v_mfma_f32_16x16x4_f32, the K split over eight waves and its reduction order kept (heads16_loop: the same bits), and
+// an epilogue in which the idle three quarters of the workgroup take the rows' segment entries (heads_epilogue, slots).
+template <int BK, int S>
+__global__ __launch_bounds__(512, 2) void gemm_heads16_kernel(const dv_gemm_desc g, const LoadCfg lc, const dv_heads_epi he) {
+    using HG = Heads16Geom<BK, S>;
+    constexpr int BM = HG::BM, BN = HG::BN, HB = BN / 2;
+    __shared__ __attribute__((aligned(1024))) float smem[HG::SMEM_FL];
+    publish_on_entry(g);
+    const int tiles_m = (g.M + BM - 1) / BM, tiles_n = (g.split + HB - 1) / HB;
+    int tm, tn;
+    tile_of_block(blockIdx.x, gridDim.x, tiles_m, tiles_n, lc.map, tm, tn);
+    const int m0 = tm * BM;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    // (the segment bounds of the thread's row, under the K loop: see gemm_body)
+    int pre_s0 = 0, pre_s1 = 0;
+    if (he.seg_ptr != nullptr) {
+        const int prow = m0 + heads_row0<BM, 1>((tid % (HG::NT / 4)) / HB);
+        if (prow < he.n_src && prow < g.M) {
+            pre_s0 = he.seg_ptr[prow];
+            pre_s1 = he.seg_ptr[prow + 1];
+        }
+    }
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    heads16_loop<BK, S>(
+        g, smem, [&](int l) { return m0 + l < g.M ? m0 + l : g.M - 1; },
+        [&](int l) {
+            const int c = tn * HB + (l < HB ? l : l - HB);
+            return l < HB ? (c < g.split ? c : g.split - 1) : (g.split + c < g.N ? g.split + c : g.N - 1);
+        },
+        acc);
+    __syncthreads();      // (the reduction reuses the ring)
+    float* red = smem;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) red[(wave * BM + 4 * (lane >> 4) + r) * (BN + 1) + (lane & 15)] = acc[r];
+    __syncthreads();
+    heads_epilogue<BM, BN, HG::KS, HG::NT>(g, he, red, m0, tn, tiles_n, pre_s0, pre_s1);
+}
+
 template <int BM, int BN, int BK, int KS, bool A1, bool B1, bool A2, bool B2, int PS, int WPS>
 __global__ __launch_bounds__(256, WPS) void gemm_pair_pipe_kernel(const dv_gemm_desc g1, const LoadCfg lc1, const dv_gemm_desc g2,
                                                                     const LoadCfg lc2, int tiles1) {
@@ -1286,7 +1334,13 @@ extern "C" int dv_gemm_heads(const dv_gemm_desc* d, const dv_heads_epi* e, dv_st
     }
 #endif
     const bool pipe = pipe_on(g) && pipe_ok(g, lc);
-    if (tune_of(g).opt[4] == 3 || (tune_of(g).opt[4] == 0 && tiles >= dense_min_tiles(g))) {
+    // one rule (heads_route.h), a function of the 32-row tile count, K and the mode: the 16-row tile for the sample-mode
+    // launches with few tiles and a long K (dv_gemm_tune.opt[4] = 4: wherever it can run, 5: never)
+    const int route = dv_heads_route(tiles, g.K, e->mode == DV_HEADS_SAMPLE, pipe, tune_of(g).opt[4], dense_min_tiles(g));
+    if (route == DV_HEADS_ROUTE_T16) {
+        const int tiles16 = ((g.M + 15) / 16) * ((g.split + 7) / 8);
+        hipLaunchKernelGGL((gemm_heads16_kernel<128, 4>), dim3(tiles16), dim3(512), 0, static_cast<hipStream_t>(stream), g, lc, *e);
+    } else if (route == DV_HEADS_ROUTE_DENSE) {
         // chip-filling grids: four waves, half the K tile, seven workgroups per CU (see gemm_launch): 29.1 -> 26.4 us
         // for the decoder heads + NLL alone
         if (pipe)

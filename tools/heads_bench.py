@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Micro-benchmark of dv_gemm_heads against the unfused sequences it replaces (GPU box only):
-heads GEMM + reparam_fwd, heads GEMM + nll_rows_fwdbwd, at the cfg-2 shapes."""
+heads GEMM + reparam_fwd, heads GEMM + nll_rows_fwdbwd, at the cfg-2 shapes.
+
+``heads_bench.py tiles``: the three sample-mode launches of a cfg-2 step on the 32-row tile (dv_gemm_tune.opt[4] = 5) against
+the 16-row tile (opt[4] = 4), three alternating rounds each; per route the minimum and the maximum over all its replays --
+the maximum minus the minimum is the tool's spread, which a route has to win by (drvae_amd/csrc/heads_route.h)."""
 import os
 import sys
 
@@ -12,8 +16,52 @@ from drvae_amd import _lib  # noqa: E402
 from tools.gemm_bench import time_call  # noqa: E402
 
 
+def time_spread(fn, repeats=20, rounds=5):
+    """(min, max) us per call over ``rounds`` replays of a graph of ``repeats`` launches"""
+    g = torch.cuda.CUDAGraph()
+    fn()
+    torch.cuda.synchronize()
+    with torch.cuda.graph(g):
+        for _ in range(repeats):
+            fn()
+    ts = []
+    for _ in range(rounds):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        g.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        ts.append(e0.elapsed_time(e1) * 1e3 / repeats)
+    return min(ts), max(ts)
+
+
+def tiles_main():
+    dev = torch.device('cuda:0')
+    r = lambda *s: torch.randn(*s, device=dev)      # noqa: E731
+    for (M, S, Kd, tag) in [(224, 100, 800, 'enc heads + samples'), (300, 100, 100, 'z2F + sample'),
+                            (450, 100, 200, 'side chain heads + samples')]:
+        x, W, b = r(M, Kd), r(2 * S, Kd) * Kd ** -0.5, r(2 * S)
+        q = torch.empty(M, 2 * S, device=dev)
+        L = 2
+        eps, z = r(L * M, S), torch.empty(L * M, S, device=dev)
+        ptr = torch.arange(0, L * M + 1, L, dtype=torch.int32, device=dev)
+        rws = torch.arange(L * M, dtype=torch.int32, device=dev)
+        fused = lambda: K.linear_heads(q, x, W, b, sample=dict(eps=eps, out=z, n_src=M, seg_ptr=ptr, seg_rows=rws),      # noqa: E731
+                                       overread=True, split=S, shift1=-2.0)
+        res = {4: [], 5: []}
+        for _ in range(3):
+            for o in (5, 4):
+                K.gemm_set_option(4, o)
+                res[o] += list(time_spread(fused))
+        K.gemm_set_option(4, 0)
+        print('%-28s M=%d heads=2x%d K=%d: 32-row %.2f .. %.2f us | 16-row %.2f .. %.2f us'
+              % (tag, M, S, Kd, min(res[5]), max(res[5]), min(res[4]), max(res[4])), flush=True)
+
+
 def main():
     lib = _lib.load()
+    if len(sys.argv) > 1 and sys.argv[1] == 'tiles':
+        return tiles_main()
     if len(sys.argv) > 1:
         K.gemm_set_option(4, int(sys.argv[1]))     # 1: four-wave variant of the heads kernel
     dev = torch.device('cuda:0')
