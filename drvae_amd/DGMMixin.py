@@ -112,6 +112,15 @@ class DeepGenerativeModelMixin:
             self._arena = ParamArena(shapes, dev, frozen=E.frozen_params(cfg)).adopt(self)
             self._engine = E.FusedStep(cfg, self._arena, seed=self.random_seed)
             self._restore_optimizer_state()
+        else:
+            # the schedules' parameters are compiled into the engine (launch arguments of its captured steps): an attribute
+            # changed behind its back must not be ignored
+            cfg = self._engine.cfg
+            late = [(k, v, getattr(cfg, k)) for k, v in self._anneal_config().items() if v != getattr(cfg, k)]
+            if late:
+                raise RuntimeError('annealing attribute(s) changed after the fused-step engine was built: %s; set them before '
+                                   'the first step (or as constructor arguments)'
+                                   % ', '.join('%s=%r (engine: %r)' % t for t in late))
         return self._engine
 
     def grad_clip_stats(self):
@@ -297,3 +306,29 @@ class DeepGenerativeModelMixin:
 
     def load_params_from_file(self, filename):
         self.load_state_dict(torch.load(filename, map_location='cpu'))
+
+    # ``save_to_file`` is the reference's snapshot: the parameters and nothing else.  A run RESUMED from it starts its
+    # optimiser moments, its bias corrections, its noise stream and -- what the annealing schedules hang on -- its iteration
+    # count from zero, exactly as a resumed reference run does.  The two below carry the whole training state
+    def save_training_state(self, filename):
+        """parameters + optimiser moments + the step / Philox counters (+ the clipped sweep's skip count) + the iteration
+        count: a run that loads this continues bit for bit, its annealing ramps included (EXTENSION: no counterpart in the
+        reference)"""
+        eng = self.engine()
+        eng.join_side()
+        eng.iters = self.finished_training_iters
+        keep = getattr(self, '_opt_stash', None)
+        self._stash_optimizer_state()
+        opt, self._opt_stash = self._opt_stash, keep
+        torch.save(dict(state_dict=OrderedDict((k, v.detach().cpu().clone()) for k, v in self.state_dict().items()),
+                        optimizer=opt, finished_training_iters=int(self.finished_training_iters)), filename)
+
+    def load_training_state(self, filename):
+        ck = torch.load(filename, map_location='cpu', weights_only=False)
+        self.load_state_dict(ck['state_dict'])
+        eng = self.engine()
+        eng.join_side()
+        self._opt_stash = ck['optimizer']
+        self._restore_optimizer_state()
+        eng._noise_stale = True       # (noise drawn ahead for another counter: the next replay draws first)
+        self.finished_training_iters = eng.iters = int(ck['finished_training_iters'])

@@ -15,7 +15,14 @@ class PVAE(ELBOModel):
     ``torch.nn.utils.clip_grad_norm_`` in front of the optimiser, and guards it: a step whose gradient holds an inf or a NaN
     is skipped -- parameters and optimiser state stay as they are, ``grad_clip_stats()['n_skipped']`` counts it, ``fit`` warns
     once per epoch in which it happened.  ``float('inf')`` keeps the guard and clips nothing.  A clipped step gives up the
-    side chain's share of the optimiser sweep.  0, a negative number or NaN raise ``ValueError``."""
+    side chain's share of the optimiser sweep.  0, a negative number or NaN raise ``ValueError``.
+    ``anneal_kl`` / ``anneal_yloss`` / ``anneal_learning_rate`` (default off, as the reference's drivers leave them) ramp the
+    weight of ``KLD`` in the ELBO, of ``yloss_rate * YL`` in the compound loss and the learning rate over ``anneal_kl_itermax``
+    / ``anneal_yloss_itermax`` (+ ``anneal_yloss_offset``) / ``anneal_lr_itermax`` iterations inside the fused step; the
+    schedule is evaluated on the device from the step counter.  They may also be set as attributes until the first step
+    builds the engine (a later change raises).  Annealed training runs on the batch-independent plans: configurations
+    without one, and the stratified ``DeviceBatcher``, raise ``NotImplementedError``.  A switch that is on with an
+    ``itermax`` <= 0 raises ``ValueError``.  The learning-rate schedule is a labelled extension."""
     kind = 'pvae'
     prior_y = None          # read by the reference ctor (src/PVAE.py:77) although PVAE has no y
 
@@ -26,7 +33,8 @@ class PVAE(ELBOModel):
                  mmd_rate=1., kl_qz2pz2_rate=1., pertloss_rate=0.1, anneal_perturb_rate_itermax=1,
                  anneal_perturb_rate_offset=0, use_s=False, use_c=False, use_m=False, random_seed=12345,
                  log_txt=None, weight_norm=False, device=None, matmul_precision='fp32',
-                 max_grad_norm=None):
+                 max_grad_norm=None, anneal_kl=False, anneal_kl_itermax=100, anneal_yloss=False, anneal_yloss_itermax=1,
+                 anneal_learning_rate=False, anneal_lr_itermax=3000):
         super().__init__()
         args = dict(locals())
         args.pop('self')

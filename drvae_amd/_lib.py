@@ -42,7 +42,8 @@ class PriorKl(C.Structure):    # dv_prior_kl
 
 
 class AdamHyper(C.Structure):  # dv_adam_hyper
-    _fields_ = [('lr', _f), ('beta1', _f), ('beta2', _f), ('eps', _f), ('weight_decay', _f), ('gscale', _f)]
+    _fields_ = [('lr', _f), ('beta1', _f), ('beta2', _f), ('eps', _f), ('weight_decay', _f), ('gscale', _f),
+                ('lr_scale', _p)]      # (trailing: learning-rate annealing, a device scalar; NULL: the sweep as it was)
 
 
 class ClipRecord(C.Structure):  # dv_clip_record
@@ -99,7 +100,12 @@ class BatchMasks(C.Structure):   # dv_batch_masks_desc
                 ('n_tot', C.c_float), ('kl_rate', C.c_float), ('pert_rate', C.c_float), ('yl_rate', C.c_float),
                 ('beta', C.c_void_p), ('c_nll', C.c_void_p), ('c_klz2', C.c_void_p), ('c_yl', C.c_void_p),
                 ('w_recl', C.c_void_p), ('w_pert', C.c_void_p), ('w_yl', C.c_void_p), ('label', C.c_void_p),
-                ('c_klp', C.c_void_p), ('one_slot', C.c_void_p), ('gcounts', C.c_void_p)]
+                ('c_klp', C.c_void_p), ('one_slot', C.c_void_p), ('gcounts', C.c_void_p),
+                # trailing: the annealing schedules (all zero / NULL: the launch as it was)
+                ('sched_step', C.c_void_p), ('pert_itermax', C.c_int32), ('pert_offset', C.c_int32),
+                ('kl_itermax', C.c_int32), ('yl_itermax', C.c_int32), ('yl_offset', C.c_int32), ('lr_itermax', C.c_int32),
+                ('mmd_rate', C.c_float), ('sched', C.c_void_p), ('c_kld', C.c_void_p), ('w_klz2', C.c_void_p),
+                ('w_klp', C.c_void_p), ('w_elbo', C.c_void_p), ('w_cmpl', C.c_void_p)]
 
 
 class BatchFeed(C.Structure):    # dv_batch_feed_desc

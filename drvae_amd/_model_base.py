@@ -15,6 +15,12 @@ from .DGMMixin import DeepGenerativeModelMixin
 from .fit import FitMixin
 
 
+# the annealing switches every model carries (src/DrVAE.py:92-97) and their defaults; ``anneal_lr_itermax`` is the 3000 the
+# reference hard-codes (src/DGMMixin.py:101)
+ANNEAL_DEFAULTS = OrderedDict(anneal_kl=False, anneal_kl_itermax=100, anneal_yloss=False, anneal_yloss_itermax=1,
+                              anneal_learning_rate=False, anneal_lr_itermax=3000)
+
+
 class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
     kind = None             # 'drvae' | 'pvae' | 'vfae'
 
@@ -35,17 +41,22 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
             self._max_grad_norm = float(self._max_grad_norm)
             if not self._max_grad_norm > 0.0:
                 raise ValueError('max_grad_norm must be a positive number, inf or None, not %r' % (self._max_grad_norm,))
+        # annealing schedules of the fused step (``StepConfig.anneal_*``): constructor arguments here, plain attributes in
+        # the reference (src/DrVAE.py:92-97) -- both work until the engine is built (``engine``), a later change raises
+        anneal = {k: args.pop(k, d) for k, d in ANNEAL_DEFAULTS.items()}
         for k, v in args.items():
             setattr(self, k, v)
+        for k, v in anneal.items():
+            setattr(self, k, v)
+        if not hasattr(self, 'anneal_yloss_offset'):
+            self.anneal_yloss_offset = 0
+        self._anneal_config()           # (a switch that is on with itermax <= 0: ValueError)
         self.wn = bool(weight_norm)   # reference: hard-coded False (src/DrVAE.py:79); exposed here
         self.bn = False
         self.prior_mu, self.prior_sg = 0., 1.
         if self.weight_decay is None:
             self.weight_decay = 0.
         self.kl_min = 2.
-        self.anneal_learning_rate = False
-        self.anneal_kl, self.anneal_kl_itermax = False, 100
-        self.anneal_yloss, self.anneal_yloss_itermax = False, 1
         self.finished_training_iters = 0
         self.add_noise = False        # set by the caller / fit(add_noise=...) (src/DrVAE.py:769)
         self._check_supported()
@@ -154,6 +165,16 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
                       'both heads share ONE keep mask in %s; no dropout at all (no hidden layer) in %s'
                       % (self.dropout_rate, ', '.join(two_heads) or 'no block', ', '.join(undropped) or 'no block'))
 
+    def _anneal_config(self):
+        """the annealing attributes as they stand now, as ``StepConfig`` keyword arguments (checked: ValueError)"""
+        kw = {k: getattr(self, k, d) for k, d in ANNEAL_DEFAULTS.items()}
+        kw['anneal_yloss_offset'] = getattr(self, 'anneal_yloss_offset', 0)
+        for sw, mx in (('anneal_kl', 'anneal_kl_itermax'), ('anneal_yloss', 'anneal_yloss_itermax'),
+                       ('anneal_learning_rate', 'anneal_lr_itermax')):
+            if kw[sw] and not int(kw[mx]) > 0:
+                raise ValueError('%s is on: %s must be a positive number of iterations, not %r' % (sw, mx, kw[mx]))
+        return dict((k, bool(v) if k in ('anneal_kl', 'anneal_yloss', 'anneal_learning_rate') else int(v)) for k, v in kw.items())
+
     def _step_config(self):
         top = 'dim_z3' if self.kind == 'drvae' else 'dim_z2'
         return E.StepConfig(
@@ -175,7 +196,7 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
             mmd_rate=float(getattr(self, 'mmd_rate', 1.)), kernel_MMD=getattr(self, 'kernel_MMD', 'rbf_fourier'),
             prior_y=None if (getattr(self, 'prior_y', None) is None or isinstance(getattr(self, 'prior_y', None), str))
             else tuple(float(v) for v in self.prior_y), matmul=self._matmul, dropout_rate=float(self.dropout_rate),
-            max_grad_norm=self._max_grad_norm)
+            max_grad_norm=self._max_grad_norm, **self._anneal_config())
 
     # ---------------------------------------------------------------- inference
     @torch.no_grad()

@@ -12,8 +12,11 @@ struct AdamC {
 
 // bias corrections from the device-side step counter, in double like torch's python floats
 // (``n_skipped``: steps the non-finite guard of a clipped sweep has skipped -- they leave no trace in the corrections)
+// (``lr_scale``: the learning-rate annealing coefficient of the step, a device scalar -- dv_adam_hyper.lr_scale; the rate is
+// rounded to fp32 once, as the host's python float is when it is handed to a sweep; NULL or 1.0f: lr's own bits)
 __device__ __forceinline__ void adam_consts(float lr, float b1, float b2, const int32_t* step_dev, float* step_size,
-                                            float* bc2_sqrt, int n_skipped = 0) {
+                                            float* bc2_sqrt, const float* lr_scale, int n_skipped = 0) {
+    if (lr_scale != nullptr) lr = (float)((double)lr * (double)lr_scale[0]);
     const double t = (double)(step_dev[0] - n_skipped);
     const double bc1 = 1.0 - pow((double)b1, t);
     const double bc2 = 1.0 - pow((double)b2, t);
@@ -67,7 +70,8 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
                                                    float b1, float b2, float eps, float wd, float gscale_in,
                                                    const int32_t* __restrict__ step_dev, int vec4, AdamGate gate,
                                                    const int32_t* __restrict__ halt, int n_halt,
-                                                   const dv_clip_record* __restrict__ clip) {
+                                                   const dv_clip_record* __restrict__ clip,
+                                                   const float* __restrict__ lr_scale) {
     __shared__ float sc[2];
     __shared__ int halted;
     // only the workgroups whose elements overlap the gated range park (typically one): a parked
@@ -91,9 +95,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         if (CLIP) {
             // a skipped first step has t = 0: the corrections are not evaluated, the sweep returns before it would use them
             if (clip->skip) h = 1;
-            else adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], clip->n_skipped);
+            else adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], lr_scale, clip->n_skipped);
         } else {
-            adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1]);
+            adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], lr_scale);
         }
         if (need && seen - want < 0) {
             const long long t0 = wall_clock64();
@@ -164,16 +168,17 @@ __global__ __launch_bounds__(256) void adam_stream_kernel(float* __restrict__ p,
                                                           float b1, float b2, float eps, float wd, float gscale_in,
                                                           const int32_t* __restrict__ step_dev,
                                                           const int32_t* __restrict__ halt, int n_halt,
-                                                          const dv_clip_record* __restrict__ clip) {
+                                                          const dv_clip_record* __restrict__ clip,
+                                                          const float* __restrict__ lr_scale) {
     __shared__ float sc[2];
     __shared__ int halted;
     if (threadIdx.x == 0) {
         if (CLIP) {       // (see adam_kernel)
             const int skip = clip->skip;
-            if (!skip) adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], clip->n_skipped);
+            if (!skip) adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], lr_scale, clip->n_skipped);
             halted = any_halt(halt, n_halt) | skip;
         } else {
-            adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1]);
+            adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], lr_scale);
             halted = any_halt(halt, n_halt);
         }
     }
@@ -498,7 +503,8 @@ __global__ __launch_bounds__(256) void adamax_kernel(float* __restrict__ p, cons
                                                      float b1, float b2, float eps, float wd, float gscale_in,
                                                      const int32_t* __restrict__ step_dev,
                                                      const int32_t* __restrict__ halt, int n_halt,
-                                                     const dv_clip_record* __restrict__ clip) {
+                                                     const dv_clip_record* __restrict__ clip,
+                                                     const float* __restrict__ lr_scale) {
     __shared__ float sc[2];
     __shared__ int halted;
     if (threadIdx.x == 0) {
@@ -507,10 +513,10 @@ __global__ __launch_bounds__(256) void adamax_kernel(float* __restrict__ p, cons
         float clr0 = 0.f, unused;
         if (CLIP) {       // (see adam_kernel)
             const int skip = clip->skip;
-            if (!skip) adam_consts(lr, b1, b2, step_dev, &clr0, &unused, clip->n_skipped);
+            if (!skip) adam_consts(lr, b1, b2, step_dev, &clr0, &unused, lr_scale, clip->n_skipped);
             halted = any_halt(halt, n_halt) | skip;
         } else {
-            adam_consts(lr, b1, b2, step_dev, &clr0, &unused);
+            adam_consts(lr, b1, b2, step_dev, &clr0, &unused, lr_scale);
             halted = any_halt(halt, n_halt);
         }
         sc[0] = clr0;
@@ -568,19 +574,19 @@ static int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, 
         const dim3 grid((unsigned)(blocks > 16384 ? 16384 : blocks));
         if (clip)
             hipLaunchKernelGGL(adam_stream_kernel<true>, grid, dim3(256), 0, ST(stream), p, g, m, v, n, h->lr, h->beta1, h->beta2,
-                               h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt, clip);
+                               h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt, clip, h->lr_scale);
         else
             hipLaunchKernelGGL(adam_stream_kernel<false>, grid, dim3(256), 0, ST(stream), p, g, m, v, n, h->lr, h->beta1, h->beta2,
-                               h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt, clip);
+                               h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt, clip, h->lr_scale);
         DV_RETURN_LAUNCH();
     }
     if (blocks > 2048) blocks = 2048;
     if (clip)
         hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, v, n, h->lr, h->beta1,
-                           h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, vec4, gate, halt, n_halt, clip);
+                           h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, vec4, gate, halt, n_halt, clip, h->lr_scale);
     else
         hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, v, n, h->lr, h->beta1,
-                           h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, vec4, gate, halt, n_halt, clip);
+                           h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, vec4, gate, halt, n_halt, clip, h->lr_scale);
     DV_RETURN_LAUNCH();
 }
 
@@ -603,10 +609,10 @@ static int adamax_launch(float* p, const float* g, float* m, float* u, int64_t n
     if (blocks > 4096) blocks = 4096;
     if (clip)
         hipLaunchKernelGGL(adamax_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, u, n, h->lr,
-                           h->beta1, h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt, clip);
+                           h->beta1, h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt, clip, h->lr_scale);
     else
         hipLaunchKernelGGL(adamax_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, u, n, h->lr,
-                           h->beta1, h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt, clip);
+                           h->beta1, h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt, clip, h->lr_scale);
     DV_RETURN_LAUNCH();
 }
 

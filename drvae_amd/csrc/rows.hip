@@ -1844,12 +1844,52 @@ struct MaskArgs {
     float* c_klp;     // (2 B), optional: KL-to-prior rows of q(z1|x1) | q(z2|x2) (PVAE, src/PVAE.py:330-345)
     const int32_t* one_slot;   // (B), optional: rows of the plan with ONE class slot (labeled for sure): label = class
     const int32_t* gcounts;    // (n_batches, 2), optional: GLOBAL (N_pairs, N_labeled) of every batch (data parallelism)
+    // annealing schedules (the trailing fields of dv_batch_masks_desc; sched_step == NULL: none, the launch as it ever was)
+    const int32_t* sched_step; // the number of finished training iterations, a device scalar
+    int pert_itermax, pert_offset, kl_itermax, yl_itermax, yl_offset, lr_itermax;     // itermax <= 0: that schedule is off
+    float mmd_rate;
+    float* sched;     // (4) the step's record {beta_pert, beta_kl, beta_yr, lr_scale}
+    float* c_kld;     // (L B), optional: beta_kl / (L n_tot)
+    float* w_klz2;    // (L Np), optional: c_klz2 without beta_kl (the weights of the reported KLD)
+    float* w_klp;     // (B + Np), optional: c_klp without beta_kl
+    float* w_elbo;    // (3)
+    float* w_cmpl;    // (8)
 };
+
+// linear annealing coefficient of src/DGMMixin.py:77-89 in double, from the integers: the host's python expression
+// operation by operation (one division, one addition, one min), so fp32 of it is the host's value bit for bit
+__device__ __forceinline__ double anneal_coef(int it, int itermax, int offset) {
+    if (itermax <= 0) return 1.0;
+    const int d = it - offset;
+    if (d <= 0) return 0.01;
+    const double c = 0.01 + (double)d / (double)itermax;
+    return c < 1.0 ? c : 1.0;
+}
 
 __device__ __forceinline__ void batch_masks_body(const MaskArgs& a) {
     __shared__ int cnt[2];
+    __shared__ float sch[4];
     if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
     __syncthreads();
+    const bool anneal = a.sched_step != nullptr;
+    if (anneal && threadIdx.x == blockDim.x - 1) {
+        // the step's schedule record: evaluated once, by one thread, from the step counter as this (the step's first) launch
+        // reads it; plain stores -- every reader is a later launch.  (The last thread: the first two carry the counts below)
+        const int it = a.sched_step[0];
+        const double lr_c = 1.0 - anneal_coef(it, a.lr_itermax, 0);
+        sch[0] = (float)anneal_coef(it, a.pert_itermax, a.pert_offset);
+        sch[1] = (float)anneal_coef(it, a.kl_itermax, 0);
+        sch[2] = (float)anneal_coef(it, a.yl_itermax, a.yl_offset);
+        sch[3] = a.lr_itermax > 0 ? (float)(lr_c > 0.01 ? lr_c : 0.01) : 1.f;
+        for (int k = 0; k < 4; ++k) a.sched[k] = sch[k];
+        a.w_elbo[0] = 1.f;
+        a.w_elbo[1] = -sch[1];
+        a.w_elbo[2] = a.hx ? sch[0] * a.pert_rate : 0.f;
+        for (int k = 0; k < 8; ++k) a.w_cmpl[k] = 0.f;
+        a.w_cmpl[3] = a.hy ? -(sch[2] * a.yl_rate) : 0.f;
+        a.w_cmpl[4] = a.mmd_rate != 0.f ? -a.mmd_rate : 0.f;
+        a.w_cmpl[5] = -1.f;
+    }
     const int32_t* tb = nullptr;
     int b = 0;
     if (a.table) {
@@ -1873,7 +1913,8 @@ __device__ __forceinline__ void batch_masks_body(const MaskArgs& a) {
         if (nl) atomicAdd(&cnt[1], nl);
     }
     __syncthreads();
-    const float Lf = (float)a.L, beta = a.beta ? a.beta[0] : 1.f;
+    const float Lf = (float)a.L, beta = anneal ? sch[0] : (a.beta ? a.beta[0] : 1.f);
+    const float b_kl = anneal ? sch[1] : 1.f, b_yr = anneal ? sch[2] : 1.f;
     const float n_pairs = cnt[0] > 0 ? (float)cnt[0] : 1.f, n_lab = cnt[1] > 0 ? (float)cnt[1] : 1.f;
     const float c_tot = 1.f / (Lf * a.n_tot);
     const int LB = a.L * a.B, LP = a.L * a.Np;
@@ -1887,7 +1928,9 @@ __device__ __forceinline__ void batch_masks_body(const MaskArgs& a) {
             a.w_recl[LB + q] = px ? c_tot : 0.f;
             a.c_nll[LB + LP + q] = px ? -beta * a.pert_rate / (Lf * n_pairs) : 0.f;
             a.w_pert[q] = px ? 1.f / (Lf * n_pairs) : 0.f;
-            a.c_klz2[q] = px ? beta * a.kl_rate * c_tot : 0.f;
+            const float kz = px ? beta * a.kl_rate * c_tot : 0.f;
+            a.c_klz2[q] = anneal ? kz * b_kl : kz;
+            if (a.w_klz2) a.w_klz2[q] = kz;
         }
     for (int r = threadIdx.x; r < LB; r += blockDim.x) {
         const int i = r % a.B, src = tb ? tb[i] : i;
@@ -1897,16 +1940,23 @@ __device__ __forceinline__ void batch_masks_body(const MaskArgs& a) {
             a.w_recl[r] = c_tot;
         }
         if (a.hy) {
-            a.c_yl[r] = py ? -a.yl_rate / (Lf * n_lab) : 0.f;
+            const float cy = py ? -a.yl_rate / (Lf * n_lab) : 0.f;
+            a.c_yl[r] = anneal ? cy * b_yr : cy;
             a.w_yl[r] = 1.f / (Lf * n_lab);
             a.label[r] = (a.one_slot && a.one_slot[i]) ? a.y[src] : (py ? -2 - a.y[src] : 0);
         }
+        if (a.c_kld) a.c_kld[r] = b_kl * c_tot;
     }
     if (a.c_klp)
         for (int i = threadIdx.x; i < a.B; i += blockDim.x) {
             const int src = tb ? tb[i] : i;
-            a.c_klp[i] = 1.f / a.n_tot;
-            if (i < a.Np) a.c_klp[a.B + i] = (a.hx && a.hx[src] != 0) ? 1.f / a.n_tot : 0.f;
+            const float k1 = 1.f / a.n_tot, k2 = (a.hx && a.hx[src] != 0) ? 1.f / a.n_tot : 0.f;
+            a.c_klp[i] = anneal ? k1 * b_kl : k1;
+            if (i < a.Np) a.c_klp[a.B + i] = anneal ? k2 * b_kl : k2;
+            if (a.w_klp) {
+                a.w_klp[i] = k1;
+                if (i < a.Np) a.w_klp[a.B + i] = k2;
+            }
         }
 }
 
@@ -3334,14 +3384,20 @@ extern "C" int dv_rows_gather(const float* src, int64_t lds, const int32_t* idx,
 }
 
 static bool masks_ok(const dv_batch_masks_desc& m, int B) {
+    // (the schedule's outputs come with its step counter: without one none of them may be set -- a zeroed tail is "no schedule")
+    const bool sched_ok = m.sched_step ? (m.sched && m.w_elbo && m.w_cmpl && (m.w_klz2 == nullptr || m.c_klz2) &&
+                                          (m.w_klp == nullptr || m.c_klp))
+                                       : !(m.sched || m.c_kld || m.w_klz2 || m.w_klp || m.w_elbo || m.w_cmpl);
     return m.Np >= 0 && m.Np <= B && m.n_tot > 0.f && m.c_nll && m.w_recl && (m.hx == nullptr || (m.c_klz2 && m.w_pert)) &&
-           (m.hy == nullptr || (m.y && m.c_yl && m.w_yl && m.label));
+           (m.hy == nullptr || (m.y && m.c_yl && m.w_yl && m.label)) && sched_ok;
 }
 
 static MaskArgs mask_args(const dv_batch_masks_desc& m, const int32_t* table, int n_batches, const int32_t* ctr,
                           const int32_t* base, int B, int L) {
     return MaskArgs{table, n_batches, ctr, base, m.hx, m.hy, m.y, B, L, m.Np, m.n_tot, m.kl_rate, m.pert_rate, m.yl_rate,
-                    m.beta, m.c_nll, m.c_klz2, m.c_yl, m.w_recl, m.w_pert, m.w_yl, m.label, m.c_klp, m.one_slot, m.gcounts};
+                    m.beta, m.c_nll, m.c_klz2, m.c_yl, m.w_recl, m.w_pert, m.w_yl, m.label, m.c_klp, m.one_slot, m.gcounts,
+                    m.sched_step, m.pert_itermax, m.pert_offset, m.kl_itermax, m.yl_itermax, m.yl_offset, m.lr_itermax,
+                    m.mmd_rate, m.sched, m.c_kld, m.w_klz2, m.w_klp, m.w_elbo, m.w_cmpl};
 }
 
 extern "C" int dv_batch_feed(const dv_batch_feed_desc* dsc, const dv_batch_masks_desc* masks, const dv_wait* park_in,

@@ -260,11 +260,16 @@ class DeviceBatcher:
         if carry and self.mode == 'sampler' and self.dp is not None:
             raise NotImplementedError("DeviceBatcher(mode='sampler', carry_s='masked') under data parallelism: models "
                                       'conditioned on the nuisance variable run in a single process on this feed')
+        if engine.cfg.annealed and self.mode != 'sampler':
+            raise NotImplementedError("DeviceBatcher(mode='stratified') with annealing schedules (anneal_kl / anneal_yloss / "
+                                      'anneal_learning_rate): its plans have a fixed structure and host-written coefficients; '
+                                      "the schedules run on the batch-independent plan -- use DeviceBatcher(mode='sampler')")
         if self.mode == 'sampler':
             assert counts is None, 'sampler feed: the global counts of every batch come from the shared index table (dp=...)'
             engine.universal = True
             if carry:       # explicit batches of this engine (``set_batch``) go to the same kind of plan
                 engine.carry_s = 'masked'
+            engine._require_universal("DeviceBatcher(mode='sampler')")
             if self.pair_bucket and not engine.cfg.has_pert:
                 self.pair_bucket = None                      # (no pairs in this model: nothing to bucket)
             if self.label_bucket and not engine.cfg.has_y:

@@ -103,8 +103,31 @@ class StepConfig:
     # as they are, a device counter counts it (``FusedStep.clip_stats``).  ``inf``: the guard alone.  None: nothing of this
     # exists -- no launch, no buffer, the step as it ever was
     max_grad_norm: Optional[float] = None
+    # annealing schedules of the loss and of the learning rate (src/DrVAE.py:549-557,619-622; src/DGMMixin.py:100-104), off
+    # by default like the reference's drivers leave them.  With ``it`` the number of finished training iterations:
+    #   beta_kl  = anneal_coef(it, anneal_kl_itermax)                              multiplies KLD in ELBO
+    #   beta_yr  = anneal_coef(it, anneal_yloss_itermax, anneal_yloss_offset)      multiplies yloss_rate * YL in CMPL
+    #   lr_scale = max(0.01, 1 - anneal_coef(it, anneal_lr_itermax))               multiplies learning_rate (EXTENSION: the
+    #              reference writes its new rate into a COPY of the optimiser's state, so its own switch does nothing;
+    #              built here from the evident intent)
+    # Any of them on: the step trains on the batch-independent plans only, and its schedule lives on the DEVICE -- a 16-byte
+    # record {beta_pert, beta_kl, beta_yr, lr_scale} ``dv_batch_masks`` evaluates from the step counter at the head of every
+    # step (``FusedStep.sched_rec``)
+    anneal_kl: bool = False
+    anneal_kl_itermax: int = 100
+    anneal_yloss: bool = False
+    anneal_yloss_itermax: int = 1
+    anneal_yloss_offset: int = 0
+    anneal_learning_rate: bool = False
+    anneal_lr_itermax: int = 3000
 
     def __post_init__(self):
+        for sw, mx in (('anneal_kl', 'anneal_kl_itermax'), ('anneal_yloss', 'anneal_yloss_itermax'),
+                       ('anneal_learning_rate', 'anneal_lr_itermax')):
+            setattr(self, sw, bool(getattr(self, sw)))
+            if getattr(self, sw) and not int(getattr(self, mx)) > 0:
+                raise ValueError('StepConfig.%s is on: %s must be a positive number of iterations, not %r'
+                                 % (sw, mx, getattr(self, mx)))
         if self.matmul not in MATMUL_CHOICES:
             raise ValueError('StepConfig.matmul must be one of %s, not %r' % (MATMUL_CHOICES, self.matmul))
         if not 0.0 <= self.dropout_rate < 1.0:
@@ -114,6 +137,12 @@ class StepConfig:
             if not self.max_grad_norm > 0.0:          # (NaN fails this too)
                 raise ValueError('StepConfig.max_grad_norm must be a positive number, inf or None, not %r'
                                  % (self.max_grad_norm,))
+
+    @property
+    def annealed(self):
+        """is any schedule beyond the perturbation coefficient on?  (That one alone changes once, on the step from iteration 0
+        to 1 with the drivers' settings, and stays a host write: ``_Plan.set_beta``)"""
+        return bool(self.anneal_kl or (self.anneal_yloss and self.has_y) or self.anneal_learning_rate)
 
     @property
     def cont(self):
@@ -244,6 +273,10 @@ class FusedStep(StepSchedule):
             self.clip_state = K.clip_state(self.dev, arena.n_live, cfg.max_grad_norm)
             self.step_dev = self.clip_state[0:1]
             self.clip_rec, self.clip_part = K.clip_record(self.clip_state), K.clip_partials(self.clip_state)
+        # annealing schedules (``StepConfig.annealed``): the step's record {beta_pert, beta_kl, beta_yr, lr_scale}, 16 bytes of
+        # device memory for the engine's life, rewritten at the head of every step by the launch that writes the batch's
+        # masks; the sweeps read its last word.  None: no schedule, nothing of this exists
+        self.sched_rec = torch.ones(4, device=self.dev) if cfg.annealed else None
         self.seed = seed
         self.training = True
         self.fuse_bwd = False               # set by train_step/capture: forward is followed by backward
@@ -443,9 +476,20 @@ class FusedStep(StepSchedule):
             return p
         return self._set_batch(x1, x2, y, has_x2, has_y, counts)
 
+    def _require_universal(self, what):
+        """an annealed step trains on the batch-independent plans only (their per-row coefficients are rewritten on the device
+        at every step: that launch carries the schedule); a configuration that has none is refused, loudly"""
+        if self.cfg.annealed and not self.universal_ok():
+            cfg = self.cfg
+            why = "type_y='cont'" if cfg.cont else 'the supervised-only VFAE' if (cfg.kind == 'vfae' and not cfg.semi_supervised) \
+                else "use_s without DeviceBatcher(mode='sampler', carry_s='masked')"
+            raise NotImplementedError('%s: annealing schedules (anneal_kl / anneal_yloss / anneal_learning_rate) run on the '
+                                      'batch-independent plan, which %s does not have' % (what, why))
+
     def _set_batch(self, x1, x2, y, has_x2, has_y, counts=None):
         cfg = self.cfg
-        if self.universal and self.universal_ok():
+        self._require_universal('set_batch')
+        if (self.universal or cfg.annealed) and self.universal_ok():
             hy = np.asarray(has_y.cpu() if torch.is_tensor(has_y) else has_y).reshape(-1)
             p = self.set_structure_universal(len(hy), self.universal_pair_slots, self.universal_labeled_range,
                                              n_tot=None if counts is None else counts[0], carry_s=cfg.use_s)
@@ -581,6 +625,34 @@ class FusedStep(StepSchedule):
             return anneal_coef(self.iters, cfg.anneal_perturb_rate_itermax, cfg.anneal_perturb_rate_offset)
         return 1.
 
+    def betas(self):
+        """(beta_pert, beta_kl, beta_yr) of the current iteration count, as the host evaluates them (src/DrVAE.py:549-562):
+        what ``_Plan.set_beta`` writes for the passes whose coefficients are host data (every pass of an engine without
+        schedules; evaluation passes over structure plans)"""
+        cfg = self.cfg
+        kl = anneal_coef(self.iters, cfg.anneal_kl_itermax) if cfg.anneal_kl else 1.
+        yr = anneal_coef(self.iters, cfg.anneal_yloss_itermax, cfg.anneal_yloss_offset) if cfg.anneal_yloss else 1.
+        return self.beta_pert(), kl, yr
+
+    def schedule_record(self):
+        """dict(beta_pert, beta_kl, beta_yr, lr_scale) of the LAST step issued, read back from the device record (one small
+        device->host copy, never part of a step)"""
+        if self.sched_rec is None:
+            raise RuntimeError('schedule_record: the engine was built without an annealing schedule')
+        self.join_side()
+        return dict(zip(('beta_pert', 'beta_kl', 'beta_yr', 'lr_scale'), self.sched_rec.detach().cpu().tolist()))
+
+    def _anneal_args(self, p):
+        """the ``anneal`` argument of ``kernels.batch_masks`` / ``batch_feed(masks=...)`` for plan ``p``"""
+        cfg = self.cfg
+        return dict(step=self.step_dev, pert=(cfg.anneal_perturb_rate_itermax, cfg.anneal_perturb_rate_offset),
+                    kl=cfg.anneal_kl_itermax if cfg.anneal_kl else 0,
+                    yl=(cfg.anneal_yloss_itermax if cfg.anneal_yloss else 0, cfg.anneal_yloss_offset),
+                    lr=cfg.anneal_lr_itermax if cfg.anneal_learning_rate else 0,
+                    mmd_rate=cfg.mmd_rate if (cfg.use_s and cfg.use_MMD) else 0.0, sched=self.sched_rec,
+                    w_elbo=p.w_elbo, w_cmpl=p.w_cmpl, c_kld=p.c_kld if cfg.has_y else None,
+                    w_klz2=p.w_klz2 if cfg.has_pert else None, w_klp=p.w_klp if cfg.kind == 'pvae' else None)
+
     def forward(self):
         """The forward pass as a launch sequence; this function only schedules its phases: ``_encoder_forward`` (inputs,
         q(z1|x1), q(z2|x2), perturbation function, samples), then two independent chains -- ``_decoder_forward`` (the big
@@ -590,7 +662,10 @@ class FusedStep(StepSchedule):
         cfg, p = self.cfg, self.plan
         if not self.fuse_bwd and self.dev.type == 'cuda' and not torch.cuda.is_current_stream_capturing():
             self.join_side()        # an evaluation forward reads parameters the side chain's tail may still be updating
-        p.set_beta(self.beta_pert())
+        if self.fuse_bwd and cfg.annealed and not p.universal:
+            raise NotImplementedError('an annealed train step (anneal_kl / anneal_yloss / anneal_learning_rate) runs on the '
+                                      "batch-independent plan: set_batch / DeviceBatcher(mode='sampler'), not a structure plan")
+        p.set_beta(*self.betas())
         B, Np, L, Z1 = p.B, p.Np, cfg.L, cfg.dim_z1
         rec, r = self._rec, self._route()
         Z1blk = p.ZDEC[:L * B]
@@ -681,6 +756,8 @@ class FusedStep(StepSchedule):
                          c_klz2=p.c_klz2 if cfg.has_pert else None, c_yl=p.c_yl, w_pert=p.w_pert, w_yl=p.w_yl,
                          label=p.label_r if cfg.has_y else None, c_klp=p.c_klp if cfg.kind == 'pvae' else None,
                          Np=Np if cfg.has_pert else 0, one_slot=p.one_slot)
+            if p.annealed:      # ... and the step's schedule record, its betas folded into the coefficients, the ELBO / CMPL weights
+                masks['anneal'] = self._anneal_args(p)
             if fd is None:
                 K.batch_masks(B, L, **masks)
         if fd is not None:
@@ -1031,14 +1108,15 @@ class FusedStep(StepSchedule):
             terms = [(nll[:p.o3], p.w_recl[:p.o3], 1.0, 0, rl)]
             if cfg.has_pert:
                 terms.append((nll[p.o3:], p.w_pert[:L * p.Np], 1.0, 2, rl))
-                terms.append((p.KLZ2, p.c_klz2, 1.0, 1))
+                # (annealed plan: c_klz2 carries beta_kl -- the reported KLD is weighted by its copy without)
+                terms.append((p.KLZ2, p.w_klz2 if p.annealed else p.c_klz2, 1.0, 1))
         else:
             terms = [(nll[:p.o3], None, 1.0 / (L * p.n_tot), 0)]
             if cfg.has_pert and p.Np:
                 terms.append((nll[p.o3:], None, 1.0 / (L * max(1., p.n_pairs)), 2))
                 terms.append((p.KLZ2, p.c_klz2, 1.0, 1))           # beta_pert*rate/(L N) lives on the device
         if cfg.kind == 'pvae':
-            terms.append((p.KLP, p.c_klp, 1.0, 1) if p.universal else (p.KLP, None, 1.0 / p.n_tot, 1))
+            terms.append((p.KLP, p.w_klp if p.annealed else p.c_klp, 1.0, 1) if p.universal else (p.KLP, None, 1.0 / p.n_tot, 1))
         if cfg.has_y:
             terms.append((p.KLDrow, None, 1.0 / (L * p.n_tot), 1))
             terms.append((p.YLrow, p.w_yl, 1.0, 3) if p.universal else
@@ -1260,7 +1338,7 @@ class FusedStep(StepSchedule):
             if t.side_adam:
                 K.adam_l2(a.param[hs:a.n_live], a.grad[hs:a.n_live], a.exp_avg[hs:a.n_live],
                           a.exp_avg_sq[hs:a.n_live], self.side_t, lr=cfg.learning_rate,
-                          weight_decay=cfg.weight_decay, halt=self.sync_err)
+                          weight_decay=cfg.weight_decay, halt=self.sync_err, **self._lr_kw())
             if not t.fold_rows:
                 self._loss_scalars()   # a leaf too; the wait above also covers the main chain's NLL rows
         if t.noise_ahead:
@@ -1303,7 +1381,7 @@ class FusedStep(StepSchedule):
             K.clip_norm(a.grad[:n], self.clip_state, gscale=gscale)
             step = K.adamax_l2_clip if cfg.optim_alg == 'adamax' else K.adam_l2_clip
             step(a.param[:n], a.grad[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.clip_state,
-                 lr=cfg.learning_rate, weight_decay=cfg.weight_decay, gscale=gscale, halt=self.sync_err)
+                 lr=cfg.learning_rate, weight_decay=cfg.weight_decay, gscale=gscale, halt=self.sync_err, **self._lr_kw())
             return
         if t and t.adam_gated:   # dual-graph step: the classifier's dW may still be in flight on the side chain
             # (the optimiser's gate waits with counter + 0: the step counter is advanced before it)
@@ -1320,7 +1398,12 @@ class FusedStep(StepSchedule):
             # its first launch reads the noise the side chain has drawn -- behind it)
             kw['gate'] = self.sync.gate('tail', self.step_dev, 0, 4)
         step(a.param[:n], a.grad[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.step_dev, lr=cfg.learning_rate,
-             weight_decay=cfg.weight_decay, gscale=gscale, halt=self.sync_err, **kw)
+             weight_decay=cfg.weight_decay, gscale=gscale, halt=self.sync_err, **kw, **self._lr_kw())
+
+    def _lr_kw(self):
+        """learning-rate annealing: every sweep of the step (the side chain's half included) reads the rate's coefficient from
+        the step's schedule record; off: no argument at all, the call as it ever was"""
+        return dict(lr_scale=self.sched_rec[3:4]) if self.cfg.anneal_learning_rate else {}
 
     def clip_stats(self):
         """dict(norm, coef, skipped_last, n_skipped) of the last clipped optimiser step as python numbers: the gradient's

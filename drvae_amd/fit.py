@@ -890,7 +890,7 @@ class _EvalGraph:
         eng = m.engine()
         eng.join_side()
         eng.iters = m.finished_training_iters
-        self.plan.set_beta(eng.beta_pert())                 # (the annealing coefficient is data of the plan, not of the graph)
+        self.plan.set_beta(*eng.betas())                 # (the annealing coefficient is data of the plan, not of the graph)
         self.graph.replay()
         eng._noise_stale = True      # (the replay drew from the Philox counter: a train step drawn ahead re-draws, as after any eager draw)
         if self.dp is not None:      # rows sharded over the ranks: ONE sum all-reduce of the partials, then the finalising launches

@@ -933,13 +933,28 @@ def rows_gather(out, src, idx=None, *, noise=None, sigma=0.0, onehot_cls=None, n
 def _masks_desc(m, B):
     """keyword arguments of ``batch_masks`` -> dv_batch_masks_desc"""
     d = dict(hx=None, hy=None, y=None, c_klz2=None, c_yl=None, w_pert=None, w_yl=None, label=None, c_klp=None, Np=None,
-             one_slot=None, gcounts=None)
+             one_slot=None, gcounts=None, anneal=None)
     d.update(m)
     assert d['gcounts'] is None or (d['gcounts'].dtype == torch.int32 and d['gcounts'].is_contiguous())
-    return _lib.BatchMasks(_i32(d['hx']), _i32(d['hy']), _i32(d['y']), B if d['Np'] is None else d['Np'],
-                           d['n_tot'], d['kl_rate'], d['pert_rate'], d['yl_rate'], _f32(d['beta']), _f32(d['c_nll']),
-                           _f32(d['c_klz2']), _f32(d['c_yl']), _f32(d['w_recl']), _f32(d['w_pert']), _f32(d['w_yl']),
-                           _i32(d['label']), _f32(d['c_klp']), _i32(d['one_slot']), _i32(d['gcounts']))
+    md = _lib.BatchMasks(_i32(d['hx']), _i32(d['hy']), _i32(d['y']), B if d['Np'] is None else d['Np'],
+                         d['n_tot'], d['kl_rate'], d['pert_rate'], d['yl_rate'], _f32(d['beta']), _f32(d['c_nll']),
+                         _f32(d['c_klz2']), _f32(d['c_yl']), _f32(d['w_recl']), _f32(d['w_pert']), _f32(d['w_yl']),
+                         _i32(d['label']), _f32(d['c_klp']), _i32(d['one_slot']), _i32(d['gcounts']))
+    an = d['anneal']
+    if an is not None:      # the annealing schedules: the descriptor's trailing fields (left zero: the launch as it was)
+        sched, w_elbo, w_cmpl = an['sched'], an['w_elbo'], an['w_cmpl']
+        assert sched.numel() == 4 and w_elbo.numel() >= 3 and w_cmpl.numel() >= 8 and an['step'].dtype == torch.int32
+        assert all(t is None or t.is_contiguous() for t in (sched, w_elbo, w_cmpl, an.get('c_kld'), an.get('w_klz2'),
+                                                            an.get('w_klp')))
+        md.sched_step = _i32(an['step'])
+        md.pert_itermax, md.pert_offset = int(an['pert'][0]), int(an['pert'][1])
+        md.kl_itermax = int(an['kl'])
+        md.yl_itermax, md.yl_offset = int(an['yl'][0]), int(an['yl'][1])
+        md.lr_itermax = int(an['lr'])
+        md.mmd_rate = float(an.get('mmd_rate', 0.0))
+        md.sched, md.w_elbo, md.w_cmpl = _f32(sched), _f32(w_elbo), _f32(w_cmpl)
+        md.c_kld, md.w_klz2, md.w_klp = _f32(an.get('c_kld')), _f32(an.get('w_klz2')), _f32(an.get('w_klp'))
+    return md
 
 
 def batch_feed(xin, x1, x2, y32, table, n_batches, ctr, base, *, pair_rows=None, noise=None, sigma=0.0, has_y=None,
@@ -968,7 +983,10 @@ def batch_masks(B, L, *, table=None, n_batches=0, ctr=None, base=None, **masks):
     """per-batch coefficient / weight vectors of a batch-independent step plan from the batch's pair / label flags
     (``dv_batch_masks``); ``hx`` / ``hy`` / ``y``: int32 device arrays indexed by dataset row (``table`` given) or by
     batch row; ``beta``: 1-element device float; ``Np``: rows [0, Np) have pair slots (default: all B); ``gcounts``
-    (int32, (n_batches | 1, 2)): the GLOBAL (N_pairs, N_labeled) per batch under data parallelism"""
+    (int32, (n_batches | 1, 2)): the GLOBAL (N_pairs, N_labeled) per batch under data parallelism.
+    ``anneal`` (the annealing schedules, "annealing schedules" in include/drvae_hip.h): dict(step=<int32 device scalar: finished
+    iterations>, pert=(itermax, offset), kl=itermax, yl=(itermax, offset), lr=itermax -- an itermax <= 0 switches that schedule
+    off --, mmd_rate, sched=<4 floats: the record>, w_elbo, w_cmpl[, c_kld, w_klz2, w_klp]); ``beta`` is then not read"""
     md = _masks_desc(masks, B)
     _lib.check(_lib.load().dv_batch_masks(C.byref(md), _i32(table), n_batches, _i32(ctr), _i32(base), B, L, _stream()),
                'dv_batch_masks')
@@ -1106,13 +1124,22 @@ def axpby(y, x, a=1.0, b=0.0):
 
 
 # ------------------------------------------------------------------------- optimiser
+def _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale):
+    """dv_adam_hyper; ``lr_scale``: None or a 1-element fp32 device tensor the sweep multiplies the rate by (in double, one
+    rounding: learning-rate annealing)"""
+    assert lr_scale is None or (lr_scale.dtype == torch.float32 and lr_scale.numel() == 1)
+    return _lib.AdamHyper(lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, gscale=gscale,
+                          lr_scale=_f32(lr_scale))
+
+
 def adam_l2(p, g, m, v, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, gate=None,
-            halt=None):
+            halt=None, lr_scale=None):
     """``gate`` = a ``Gate``: elements [lo, hi) wait for the flag (``dv_adam_l2_gated``);
-    ``halt``: the (err, ticks) pairs of the step's waits -- any error set: nothing is updated"""
+    ``halt``: the (err, ticks) pairs of the step's waits -- any error set: nothing is updated;
+    ``lr_scale``: a device scalar the rate is multiplied by (``_hyper``; every sweep below takes it)"""
     assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
     hp, hn = _halt(halt)
-    h = _lib.AdamHyper(lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, gscale=gscale)
+    h = _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale)
     if gate is None:
         _lib.check(_lib.load().dv_adam_l2(_f32(p), _f32(g), _f32(m), _f32(v), p.numel(), C.byref(h), _i32(step_dev), hp, hn,
                                           _stream()), 'dv_adam_l2')
@@ -1123,10 +1150,11 @@ def adam_l2(p, g, m, v, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weigh
                                                 _stream()), 'dv_adam_l2_gated')
 
 
-def adamax_l2(p, g, m, u, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None):
+def adamax_l2(p, g, m, u, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None,
+              lr_scale=None):
     assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and u.is_contiguous()
     hp, hn = _halt(halt)
-    h = _lib.AdamHyper(lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, gscale=gscale)
+    h = _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale)
     _lib.check(_lib.load().dv_adamax_l2(_f32(p), _f32(g), _f32(m), _f32(u), p.numel(), C.byref(h), _i32(step_dev), hp, hn,
                                         _stream()), 'dv_adamax_l2')
 
@@ -1181,20 +1209,22 @@ def clip_norm(g, state, *, gscale=1.0):
     _lib.check(_lib.load().dv_grad_norm_clip(_f32(g), g.numel(), gscale, _i32(state), _stream()), 'dv_grad_norm_clip')
 
 
-def adam_l2_clip(p, g, m, v, state, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None):
+def adam_l2_clip(p, g, m, v, state, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None,
+                 lr_scale=None):
     """``adam_l2`` reading the record of the clip state (whose first word is the step): skipped when the record says so, else
     the gradient scaled by fl32(gscale * coef) and t = step - n_skipped.  No gated form."""
     assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
     hp, hn = _halt(halt)
-    h = _lib.AdamHyper(lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, gscale=gscale)
+    h = _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale)
     _lib.check(_lib.load().dv_adam_l2_clipped(_f32(p), _f32(g), _f32(m), _f32(v), p.numel(), C.byref(h), _i32(state), hp, hn,
                                               _stream()), 'dv_adam_l2_clipped')
 
 
-def adamax_l2_clip(p, g, m, u, state, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None):
+def adamax_l2_clip(p, g, m, u, state, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None,
+                   lr_scale=None):
     assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and u.is_contiguous()
     hp, hn = _halt(halt)
-    h = _lib.AdamHyper(lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, gscale=gscale)
+    h = _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale)
     _lib.check(_lib.load().dv_adamax_l2_clipped(_f32(p), _f32(g), _f32(m), _f32(u), p.numel(), C.byref(h), _i32(state), hp, hn,
                                                 _stream()), 'dv_adamax_l2_clipped')
 

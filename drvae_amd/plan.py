@@ -267,6 +267,13 @@ class _Plan:
                 self.c_yl = None
             # rows the feed guarantees to be labeled (one fprop row, the structure's own label path): a static flag
             self.one_slot = i32(has_y.astype(np.int32)) if (cfg.has_y and has_y.any()) else None
+            # annealing schedules (``StepConfig.annealed``): dv_batch_masks folds the step's betas into the coefficients it
+            # writes -- c_kld, a constant of every other plan, among them -- and writes w_elbo / w_cmpl; the KL coefficient
+            # vectors that double as weights of the reported KLD get copies without beta_kl
+            self.annealed = bool(cfg.annealed)
+            if self.annealed:
+                self.w_klz2 = zf(L * Np) if cfg.has_pert else None
+                self.w_klp = zf(Me) if cfg.kind == 'pvae' else None
         self._cfg = cfg
         self.x1 = self.x2 = None
         self.feed = None        # graph-resident input feed (drvae_amd.data.DeviceBatcher.begin_epoch)
@@ -306,6 +313,7 @@ class _Plan:
     # ``set_s_device`` or by the epoch feed's dv_nuisance_feed launch -- and the MMD penalty reads them inside its two
     # grouped launches: nothing of such a plan depends on the batch's composition of classes
     carry_s = False
+    annealed = False        # (universal plan of an engine with annealing schedules) the schedule is the device's: ``set_beta``
     # (universal plan) nothing narrows it -- no pair slots, no labeled range, no global counts, no carried classes: the worst-case
     # rows of the every-row-may-be-anything plan, which ``schedule._step_tail`` schedules differently from the bucketed ones
     every_row_anything = False
@@ -490,26 +498,32 @@ class _Plan:
             if not self._cfg.cont:      # ... and of the encoder_z3 input [z1 | onehot(y)] (src/DrVAE.py:341)
                 K.rows_gather(self.FPIN[:, self._cfg.dim_z1:], None, None, onehot_cls=self.fp_cls, n_classes=Y, width=0)
 
-    def set_beta(self, beta):
-        """(re)write the coefficients that depend on the perturbation annealing coefficient
-        (0.01 on the very first iteration, 1.0 afterwards with the driver settings)."""
+    def set_beta(self, beta, beta_kl=1., beta_yr=1.):
+        """(re)write the coefficients that depend on the annealing coefficients: the perturbation coefficient (0.01 on the
+        very first iteration, 1.0 afterwards with the driver settings) and -- evaluation passes of a model with annealing
+        schedules -- ``beta_kl`` / ``beta_yr`` in the ELBO / CMPL weights (src/DrVAE.py:619-622; the reported scalars stay
+        unscaled).  An ANNEALED universal plan is written by the device alone, every step (``dv_batch_masks``): nothing here"""
+        if self.annealed:
+            return
+        beta = (beta, beta_kl, beta_yr)
         if self.beta == beta:
             return
         cfg, L = self._cfg, self._cfg.L
         self.beta = beta
+        beta = beta[0]
         if self.universal:       # the per-row coefficients are rewritten every step by dv_batch_masks: it reads beta here
             self.beta_dev.fill_(beta)
-            self.w_elbo.copy_(torch.tensor([1.0, -1.0, beta * cfg.pertloss_rate if cfg.has_pert else 0.0]))
+            self.w_elbo.copy_(torch.tensor([1.0, -beta_kl, beta * cfg.pertloss_rate if cfg.has_pert else 0.0]))
         elif cfg.has_pert:
             self.c_nll[self.o3:] = -beta * cfg.pertloss_rate / (L * max(1., self.n_pairs))
             self.c_klz2.fill_(beta * cfg.kl_qz2pz2_rate / (L * self.n_tot))
-            self.w_elbo.copy_(torch.tensor([1.0, -1.0, beta * cfg.pertloss_rate]))
+            self.w_elbo.copy_(torch.tensor([1.0, -beta_kl, beta * cfg.pertloss_rate]))
         else:
-            self.w_elbo.copy_(torch.tensor([1.0, -1.0, 0.0]))
+            self.w_elbo.copy_(torch.tensor([1.0, -beta_kl, 0.0]))
         w = [0.0] * N_LOSS
         w[LOSS_IDX['ELBO']] = -1.0
         if cfg.has_y:
-            w[LOSS_IDX['YL']] = -cfg.yloss_rate
+            w[LOSS_IDX['YL']] = -beta_yr * cfg.yloss_rate
         if cfg.use_s and cfg.use_MMD:
             w[LOSS_IDX['MMD']] = -cfg.mmd_rate         # src/DrVAE.py:623-624
         self.w_cmpl.copy_(torch.tensor(w))

@@ -354,7 +354,9 @@ class StepSchedule:
         # ... where the step's first launch is the graph-resident feed (a few dozen workgroups that can park): sampler feed
         # 0.213 -> 0.2074 ms.  With the resident batch the first launch is the input gather (856 workgroups; parked with
         # 128 it is slower by itself and waits the 4 us the optimiser launch used to wait: 0.1932 -> 0.198 ms)
-        tail_gated = side_adam and (p.live_feed is not None or T.get('tail_gate') == 2)
+        # (an annealed plan without the feed: its head is ``dv_batch_masks`` as a launch of its own, which cannot park and
+        # rewrites what the tail reads -- see ``_head_behind_tail``; the tuning switch does not reach it)
+        tail_gated = side_adam and (p.live_feed is not None or (T.get('tail_gate') == 2 and not p.annealed))
         # the pairs' KL rows on the main chain (in every other schedule: on the side chain)
         # (not with the batch-independent plan: its worst-case decoder rows make the main chain the longer one again,
         # the side chain parks ~13 us per step behind it -- sampler feed 0.250 -> 0.248 ms with the rows on the side chain;
@@ -384,9 +386,33 @@ class StepSchedule:
         fold_rows = bool(T.get('fold_rows') and not split_kind and not clip and not p.drop_sites and cfg.kind == 'drvae'
                          and not cfg.cont and self.clf_small and cfg.clf_z1z2 and fold_join and side_loss and noise_ahead
                          and getattr(K.z2f_post_bwd, 'fold_rows', False) and getattr(K.smalln_fwd, 'fold_rows', False))
-        return Tail(dual=True, late=late, adam_gated=late and not split_kind, side_adam=side_adam, hs=hs, side_loss=side_loss,
-                    cap_fork=cap_fork, tail_gated=tail_gated, noise_ahead=noise_ahead, klz2_on_main=klz2_on_main,
-                    fold_join=fold_join, fold_rows=fold_rows)
+        t = Tail(dual=True, late=late, adam_gated=late and not split_kind, side_adam=side_adam, hs=hs, side_loss=side_loss,
+                 cap_fork=cap_fork, tail_gated=tail_gated, noise_ahead=noise_ahead, klz2_on_main=klz2_on_main,
+                 fold_join=fold_join, fold_rows=fold_rows)
+        # annealing schedules (``StepConfig.annealed``): step t+1's FIRST launch (``dv_batch_masks``, on its own or as the
+        # feed's extra workgroup) rewrites the schedule record and the ELBO / CMPL weights with NEW values, and step t's tail
+        # on the side chain reads them -- its half of the sweep (lr_scale), the loss scalars (w_elbo, w_cmpl, the KLD weights).
+        # No launch is added for this: the same launch has always rewritten the per-row weights those loss scalars read
+        # (w_recl, w_pert, w_yl, c_klz2: they change with every batch's composition), so every recorded form already parks
+        # the head of the next step on flag ``tail`` or behind a launch that did.  Checked here, where the tail is decided,
+        # instead of believed (DESIGN.md section 9 gives the argument form by form)
+        assert not p.annealed or self._head_behind_tail(t, split_kind), 'annealed step: the next head may overtake this tail'
+        return t
+
+    @staticmethod
+    def _head_behind_tail(t, split_kind):
+        """is the first launch of step t+1 ordered behind the LAST launch of step t's side chain (the one that publishes
+        flag ``tail``) in the dual-graph step ``t``?"""
+        if not (t.late or t.cap_fork):
+            # nothing of the side chain behind the join reads a coefficient: its tail is the publish of ``join`` and its
+            # counters, and the main chain's sweep is behind its own wait for ``join``
+            return not (t.side_adam or t.side_loss or t.noise_ahead)
+        if split_kind is True:
+            return True          # two main graphs: ``replay`` makes the launching stream wait for the side stream between them
+        if t.tail_gated:
+            return True          # the head itself parks on ``tail`` (site ``next_step``): the feed launch, masks workgroup included
+        # the sweep's gated workgroup parks on ``tail`` (site ``adam_gate``), and the head follows the whole sweep in stream order
+        return bool(t.adam_gated or t.cap_fork)
 
     @contextlib.contextmanager
     def _recording(self, chain, tail):
@@ -427,7 +453,7 @@ class StepSchedule:
             raise NotImplementedError('use_MMD: the model-level MMD penalty is a cross-row term (every row of a nuisance '
                                       'class against every other row): it cannot be sharded over ranks')
         self.training = True
-        self.plan.set_beta(self.beta_pert())
+        self.plan.set_beta(*self.betas())
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):         # warm-up on a side stream (loads code objects)
@@ -586,7 +612,7 @@ class StepSchedule:
             dst.copy_(src)
         self.iters = iters
         self._noise_stale = True
-        self.plan.set_beta(self.beta_pert())
+        self.plan.set_beta(*self.betas())
         torch.cuda.synchronize()
         self._side_cus = best[0]
         return best[0]
@@ -715,7 +741,7 @@ class StepSchedule:
         assert self._graph_feed is self.plan.live_feed, 'input source changed (epoch feed <-> explicit batch): capture again'
         assert self._graph_mmd_sig == getattr(self.plan, 'mmd_sig', None), \
             'use_MMD: the nuisance classes of the batch changed (the penalty compares row sets): capture again'
-        self.plan.set_beta(self.beta_pert())      # 0.01 on iteration 0, 1.0 afterwards (device-side coefficients)
+        self.plan.set_beta(*self.betas())      # 0.01 on iteration 0, 1.0 afterwards (device-side coefficients)
         self.plan.masks_injected = False          # (the captured step draws its own keep masks)
         if self.noise_ahead and self._noise_stale:        # first replay (or an eager draw since): this step's noise
             self._fill_noise(self.plan)

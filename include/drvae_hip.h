@@ -721,6 +721,21 @@ typedef struct dv_batch_masks_desc {
     float* c_klp;
     const int32_t* one_slot;
     const int32_t* gcounts;
+    /* annealing schedules (trailing fields; all zero / NULL: the launch as it was).  sched_step != NULL: the launch
+     * evaluates the step's schedule record from it = sched_step[0] (the number of finished training iterations, a DEVICE
+     * scalar) -- see "annealing schedules" below -- and `beta` is not read */
+    const int32_t* sched_step;
+    int32_t pert_itermax, pert_offset;
+    int32_t kl_itermax;
+    int32_t yl_itermax, yl_offset;
+    int32_t lr_itermax;
+    float mmd_rate;
+    float* sched;
+    float* c_kld;
+    float* w_klz2;
+    float* w_klp;
+    float* w_elbo;
+    float* w_cmpl;
 } dv_batch_masks_desc;
 /* ABI 11: the feed's operands as a descriptor (names as in the comment above; 37 positional arguments before) */
 typedef struct dv_batch_feed_desc {
@@ -787,6 +802,17 @@ int dv_batch_feed(const dv_batch_feed_desc* d, const dv_batch_masks_desc* masks,
  * slice of each batch, so the global counts are table data; with them the normalisers above use the global counts instead
  * of this shard's own (n_tot is then the global number of rows): summed shard gradients == the gradient of the
  * concatenated batch. */
+/* annealing schedules (sched_step != NULL; src/DrVAE.py:549-557,619-622, src/DGMMixin.py:77-104).  With it = sched_step[0] and
+ *   coef(it, max, off) = it - off > 0 ? min(1, 0.01 + (it - off) / max) : 0.01,   a schedule with itermax <= 0 is OFF (value 1),
+ * one thread evaluates, in double from the integers, and stores with one rounding each
+ *   sched[0] = beta_pert = coef(it, pert_itermax, pert_offset)      sched[1] = beta_kl = coef(it, kl_itermax, 0)
+ *   sched[2] = beta_yr   = coef(it, yl_itermax, yl_offset)          sched[3] = lr_scale = max(0.01, 1 - coef(it, lr_itermax, 0))
+ * (16 bytes the optimiser sweeps read through dv_adam_hyper.lr_scale), uses beta_pert where `beta` is read above, folds
+ * beta_kl into c_klz2, c_klp and c_kld[r] = beta_kl / (L n_tot) (L*B entries, optional), beta_yr into c_yl, and writes the
+ * weights dv_loss_assemble reads:  w_elbo = {1, -beta_kl, hx ? beta_pert pert_rate : 0},
+ *   w_cmpl = {0, 0, 0, hy ? -beta_yr yl_rate : 0, mmd_rate != 0 ? -mmd_rate : 0, -1, 0, 0}.
+ * w_klz2 / w_klp (optional, laid out as c_klz2 / c_klp): the same vectors WITHOUT beta_kl -- the weights of the reported,
+ * unscaled KLD. */
 int dv_batch_masks(const dv_batch_masks_desc* m, const int32_t* table, int32_t n_batches, const int32_t* ctr,
                    const int32_t* base, int32_t B, int32_t L, dv_stream_t stream);
 int dv_rows_segment_sum(const float* src, int64_t lds, const int32_t* seg_ptr, const int32_t* seg_rows,
@@ -1074,6 +1100,10 @@ typedef struct dv_adam_hyper {      /* ABI 11: six same-typed scalars travel by 
     float eps;
     float weight_decay;
     float gscale;
+    /* learning-rate annealing (trailing field; NULL: the sweep as it was): a DEVICE scalar, read by the one thread that
+     * evaluates the bias corrections; the sweep then runs with lr_eff = (float)((double)lr * (double)lr_scale[0]) where it
+     * uses lr (lr_scale[0] == 1.0f: the plain sweep's bits).  Every sweep below honours it, gated and clipped included */
+    const float* lr_scale;
 } dv_adam_hyper;
 int dv_adam_l2(float* p, const float* g, float* m, float* v, int64_t n, const dv_adam_hyper* h,
                const int32_t* step_dev, const int32_t* halt, int32_t n_halt, dv_stream_t stream);
