@@ -33,7 +33,7 @@ class DeepGenerativeModelMixin:
     def _create_optimizer(self):
         """Adam with coupled L2 ``weight_decay`` on every parameter (src/DGMMixin.py:31-40),
         or Adamax (src/DGMMixin.py:37-38), as one fused kernel over the arena."""
-        if self.optim_alg not in ('adam', 'adamax'):
+        if self.optim_alg not in E.OPTIM_ALGS:      # ('adamw': Adam with decoupled weight decay, an EXTENSION)
             raise ValueError('Selected unknown optimizer: ' + str(self.optim_alg))
         self.optimizer = None          # kept for attribute parity; the state lives in the arena
         self._engine = None
@@ -84,7 +84,8 @@ class DeepGenerativeModelMixin:
             eng = self.engine()
             eng.join_side()
             for t in (eng.arena.param, eng.arena.exp_avg, eng.arena.exp_avg_sq, eng.step_dev, eng.rng_ctr) + \
-                    ((eng.clip_rec,) if eng.clip_rec is not None else ()):
+                    ((eng.clip_rec,) if eng.clip_rec is not None else ()) + \
+                    ((eng.arena.avg,) if hasattr(eng.arena, 'avg') else ()):      # (replicated state, like the parameters)
                 D.broadcast(t)
             eng.sync_side_counters()
             self.finished_training_iters = int(D.broadcast_int(self.finished_training_iters))
@@ -113,12 +114,14 @@ class DeepGenerativeModelMixin:
             self._engine = E.FusedStep(cfg, self._arena, seed=self.random_seed)
             self._restore_optimizer_state()
         else:
-            # the schedules' parameters are compiled into the engine (launch arguments of its captured steps): an attribute
-            # changed behind its back must not be ignored
+            # the schedules' parameters and the average's decay are compiled into the engine (launch arguments of its captured
+            # steps): an attribute changed behind its back must not be ignored
             cfg = self._engine.cfg
             late = [(k, v, getattr(cfg, k)) for k, v in self._anneal_config().items() if v != getattr(cfg, k)]
+            if getattr(self, 'ema_decay', None) != cfg.ema_decay:     # (the average's buffer and launch arguments exist or not)
+                late.append(('ema_decay', self.ema_decay, cfg.ema_decay))
             if late:
-                raise RuntimeError('annealing attribute(s) changed after the fused-step engine was built: %s; set them before '
+                raise RuntimeError('step-configuration attribute(s) changed after the fused-step engine was built: %s; set them before '
                                    'the first step (or as constructor arguments)'
                                    % ', '.join('%s=%r (engine: %r)' % t for t in late))
         return self._engine
@@ -141,11 +144,16 @@ class DeepGenerativeModelMixin:
 
     def _stash_optimizer_state(self):
         eng, a = self._engine, self._arena
+        # (inside ``averaged_parameters()`` the two arenas hold each other's contents: a stash -- ``.to()``,
+        # ``save_training_state`` -- would carry them exchanged)
+        eng._refuse_averaged('moving or saving the training state')
         self._opt_stash = dict(exp_avg=a.exp_avg.detach().cpu().clone(), exp_avg_sq=a.exp_avg_sq.detach().cpu().clone(),
                                step=eng.step_dev.cpu().clone(), rng=eng.rng_ctr.cpu().clone(), iters=eng.iters,
                                offsets=dict(a.offsets))
         if eng.clip_rec is not None:      # the bias corrections count step - n_skipped: the two travel together
             self._opt_stash['n_skipped'] = int(eng.clip_rec[3])
+        if hasattr(a, 'avg'):             # the parameter average is optimiser state too
+            self._opt_stash['avg'] = a.avg.detach().cpu().clone()
 
     def _restore_optimizer_state(self):
         st = getattr(self, '_opt_stash', None)
@@ -159,6 +167,8 @@ class DeepGenerativeModelMixin:
         eng.rng_ctr.copy_(st['rng'])
         if eng.clip_rec is not None:
             eng.clip_rec[3] = int(st.get('n_skipped', 0))
+        if hasattr(a, 'avg') and st.get('avg') is not None:
+            a.avg.copy_(st['avg'])
         eng.sync_side_counters()
         eng.iters = st['iters']
         self._opt_stash = None
@@ -168,6 +178,7 @@ class DeepGenerativeModelMixin:
         optimiser state (Adam moments, step and Philox counters) over and rebuild the arena + engine on
         the new device at the next use.  A dtype other than fp32 is refused: the hot path is fp32."""
         if getattr(self, '_engine', None) is not None:
+            self._engine._refuse_averaged('moving the model')      # (before anything moves: the arenas hold each other's contents)
             probe = next(self.parameters())
             if fn(torch.empty(0, dtype=probe.dtype, device=probe.device)).dtype != torch.float32:
                 raise TypeError('drvae_amd: the fused train step is fp32; cast a copy of the model instead')
@@ -179,10 +190,51 @@ class DeepGenerativeModelMixin:
         return out
 
     def load_state_dict(self, state_dict, strict=True, assign=False):
+        if getattr(self, '_engine', None) is not None:
+            self._engine._refuse_averaged('load_state_dict')
         out = super().load_state_dict(state_dict, strict=strict, assign=assign)
         if assign and getattr(self, '_engine', None) is not None and not self._arena_aliased():
             self._arena.adopt(self)                # values copied into the arena, parameters aliased again
+        if getattr(self, '_engine', None) is not None:
+            self._engine.join_side()
+            self._arena.reset_avg()                # an average of the old weights must not leak into the loaded ones
+        elif getattr(self, '_opt_stash', None) is not None:
+            # (``.to()`` has retired the engine and the state waits for the next one: its average is one of the old weights)
+            self._opt_stash.pop('avg', None)
         return out
+
+    # ------------------------------------------------------------ parameter average
+    def averaged_parameters(self):
+        """Context manager: inside it the parameter arena HOLDS the exponential moving average the optimiser sweep keeps
+        (``ema_decay``), so everything that reads parameters -- ``forward``, ``run_on_batch(train_mode=False)``, the captured
+        evaluations, ``state_dict`` / ``save_to_file`` -- sees the averaged weights.  The contents are swapped, not the
+        pointers (captured graphs have the arena's addresses baked in); on exit the live parameters are back, bit for bit.
+        Training inside it raises ``RuntimeError``; so does the call on a model built without ``ema_decay``."""
+        import contextlib
+        if getattr(self, 'ema_decay', None) is None:
+            raise RuntimeError('averaged_parameters(): the model was built without ema_decay')
+        eng = self.engine()
+
+        @contextlib.contextmanager
+        def ctx():
+            eng._refuse_averaged('averaged_parameters (nested)')
+            eng.swap_average()
+            try:
+                yield self
+            finally:
+                eng.swap_average()
+        return ctx()
+
+    def averaged_state_dict(self):
+        """the reference's ``state_dict`` keys with the AVERAGED values (host copies); the live parameters are not touched"""
+        if getattr(self, 'ema_decay', None) is None:
+            raise RuntimeError('averaged_state_dict(): the model was built without ema_decay')
+        eng = self.engine()
+        eng.join_side()
+        a = self._arena
+        src = a.p if eng.averaged else a.e
+        names = dict(self.named_parameters())
+        return OrderedDict((k, (src(k) if k in names else v).detach().cpu().clone()) for k, v in self.state_dict().items())
 
     # ------------------------------------------------------- model-level MMD penalty
     def _get_mmd_criterion(self, z, sind):
@@ -261,6 +313,8 @@ class DeepGenerativeModelMixin:
             self.eval()
             return self.loss_function(noise=noise, **kwargs)
         self.train()
+        if getattr(self, '_engine', None) is not None:
+            self._engine._refuse_averaged('run_on_batch(train_mode=True)')
         eng = self._batch_to_engine(dp=True, **kwargs)
         eng.add_noise = bool(getattr(self, 'add_noise', False))
         eng.iters = self.finished_training_iters

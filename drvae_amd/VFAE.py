@@ -21,7 +21,11 @@ class VFAE(ELBOModel):
     schedule is evaluated on the device from the step counter.  They may also be set as attributes until the first step
     builds the engine (a later change raises).  Annealed training runs on the batch-independent plans: configurations
     without one, and the stratified ``DeviceBatcher``, raise ``NotImplementedError``.  A switch that is on with an
-    ``itermax`` <= 0 raises ``ValueError``.  The learning-rate schedule is a labelled extension."""
+    ``itermax`` <= 0 raises ``ValueError``.  The learning-rate schedule is a labelled extension.
+    ``ema_decay`` (default None: off; a number in (0, 1), else ``ValueError``) keeps an exponential moving average of the
+    parameters inside the optimiser sweep: ``averaged_parameters()`` evaluates with it, ``averaged_state_dict()`` returns it,
+    ``fit`` evaluates and snapshots it unless ``model.ema_eval = False``.  ``optim_alg='adamw'`` is Adam with decoupled weight
+    decay (``torch.optim.AdamW``).  Both are labelled extensions."""
     kind = 'vfae'
     fit_patience = 40       # src/VFAE.py:536
 
@@ -33,7 +37,7 @@ class VFAE(ELBOModel):
                  anneal_yloss_offset=0, use_MMD=True, kernel_MMD='rbf_fourier', mmd_rate=1., use_s=False,
                  random_seed=12345, log_txt=None, weight_norm=False, device=None, matmul_precision='fp32',
                  max_grad_norm=None, anneal_kl=False, anneal_kl_itermax=100, anneal_yloss=False, anneal_yloss_itermax=1,
-                 anneal_learning_rate=False, anneal_lr_itermax=3000):
+                 anneal_learning_rate=False, anneal_lr_itermax=3000, ema_decay=None):
         super().__init__()
         args = dict(locals())
         args.pop('self')

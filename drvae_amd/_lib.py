@@ -43,7 +43,9 @@ class PriorKl(C.Structure):    # dv_prior_kl
 
 class AdamHyper(C.Structure):  # dv_adam_hyper
     _fields_ = [('lr', _f), ('beta1', _f), ('beta2', _f), ('eps', _f), ('weight_decay', _f), ('gscale', _f),
-                ('lr_scale', _p)]      # (trailing: learning-rate annealing, a device scalar; NULL: the sweep as it was)
+                ('lr_scale', _p),      # (trailing: learning-rate annealing, a device scalar; NULL: the sweep as it was)
+                # trailing: decoupled weight decay (AdamW) and the parameter average (all zero / NULL: the sweep as it was)
+                ('decoupled', _i32), ('avg_decay', _f), ('avg', _p)]
 
 
 class ClipRecord(C.Structure):  # dv_clip_record

@@ -44,10 +44,14 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         # annealing schedules of the fused step (``StepConfig.anneal_*``): constructor arguments here, plain attributes in
         # the reference (src/DrVAE.py:92-97) -- both work until the engine is built (``engine``), a later change raises
         anneal = {k: args.pop(k, d) for k, d in ANNEAL_DEFAULTS.items()}
+        # None | a number in (0, 1): the exponential moving average of the parameters kept by the optimiser sweep, see
+        # ``StepConfig.ema_decay``; ``ema_eval``: ``fit`` evaluates and snapshots the averaged weights (default) or the live ones
+        ema_decay = E.check_ema_decay(args.pop('ema_decay', None))
         for k, v in args.items():
             setattr(self, k, v)
         for k, v in anneal.items():
             setattr(self, k, v)
+        self.ema_decay, self.ema_eval = ema_decay, True
         if not hasattr(self, 'anneal_yloss_offset'):
             self.anneal_yloss_offset = 0
         self._anneal_config()           # (a switch that is on with itermax <= 0: ValueError)
@@ -196,7 +200,7 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
             mmd_rate=float(getattr(self, 'mmd_rate', 1.)), kernel_MMD=getattr(self, 'kernel_MMD', 'rbf_fourier'),
             prior_y=None if (getattr(self, 'prior_y', None) is None or isinstance(getattr(self, 'prior_y', None), str))
             else tuple(float(v) for v in self.prior_y), matmul=self._matmul, dropout_rate=float(self.dropout_rate),
-            max_grad_norm=self._max_grad_norm, **self._anneal_config())
+            max_grad_norm=self._max_grad_norm, ema_decay=self.ema_decay, **self._anneal_config())
 
     # ---------------------------------------------------------------- inference
     @torch.no_grad()

@@ -102,6 +102,25 @@ class ParamArena:
         tail_ok = early and all(o >= first for n, o in self.offsets.items() if n.startswith('decoder_x.')) and \
             all(o < first for n, o in self.offsets.items() if not n.startswith('decoder_x.') and n not in frozen)
         self.late_end = N_LOSS + (first if tail_ok else self.n_params)
+        self._z = z
+
+    def ensure_avg(self):
+        """the parameter average (``StepConfig.ema_decay``): a sibling of ``param`` with its layout, pads and the frozen tail
+        included, allocated only when asked for and started as a copy of ``param``.  Returns True when it was created"""
+        if hasattr(self, 'avg'):
+            return False
+        self.avg = self._z(self.n_params)
+        self.reset_avg()
+        return True
+
+    def reset_avg(self):
+        """average := parameters (a fresh engine; after anything that LOADS parameters).  No-op without an average"""
+        if hasattr(self, 'avg'):
+            with torch.no_grad():
+                self.avg.copy_(self.param)
+
+    def e(self, name):
+        return self._view(self.avg, name)
 
     def numel(self, name):
         """floats the parameter occupies in the arena (rows padded to 16 B: see ``row_stride``)"""

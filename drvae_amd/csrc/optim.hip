@@ -3,6 +3,7 @@
 // All HBM-streaming: 16-B per lane, grid-stride, 7 words of traffic per parameter.
 #include "dv_common.h"
 #include <cstring>
+#include <type_traits>
 
 namespace {
 
@@ -15,8 +16,12 @@ struct AdamC {
 // (``lr_scale``: the learning-rate annealing coefficient of the step, a device scalar -- dv_adam_hyper.lr_scale; the rate is
 // rounded to fp32 once, as the host's python float is when it is handed to a sweep; NULL or 1.0f: lr's own bits)
 __device__ __forceinline__ void adam_consts(float lr, float b1, float b2, const int32_t* step_dev, float* step_size,
-                                            float* bc2_sqrt, const float* lr_scale, int n_skipped = 0) {
+                                            float* bc2_sqrt, const float* lr_scale, int n_skipped = 0,
+                                            float* decay = nullptr, float wd = 0.f) {
     if (lr_scale != nullptr) lr = (float)((double)lr * (double)lr_scale[0]);
+    // decoupled weight decay (dv_adam_hyper.decoupled): p is multiplied by fl32(1 - lr_eff wd) before the update, the product
+    // in double and rounded once like the rate itself (torch's python float 1 - lr * weight_decay handed to mul_)
+    if (decay != nullptr) *decay = (float)(1.0 - (double)lr * (double)wd);
     const double t = (double)(step_dev[0] - n_skipped);
     const double bc1 = 1.0 - pow((double)b1, t);
     const double bc2 = 1.0 - pow((double)b2, t);
@@ -24,6 +29,9 @@ __device__ __forceinline__ void adam_consts(float lr, float b1, float b2, const 
     *bc2_sqrt = (float)sqrt(bc2);
 }
 
+// DEC: decoupled weight decay (torch/optim/adamw.py, the same _single_tensor_adam): p *= 1 - lr*wd first -- ``wd`` then carries
+// that factor -- and the gradient takes no wd*p term; everything behind it is the coupled form's sequence
+template <bool DEC = false>
 __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, float step_size, float bc2_sqrt,
                                          float eps, float wd, float w1, float b2, float w2, float gscale) {
     // torch/optim/adam.py::_single_tensor_adam (2.x): grad += wd*p; m.lerp_(g, 1-b1);
@@ -33,12 +41,24 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
     // into one two-wide multiply each -- fused none of those two, so one element came out an ulp apart depending on the
     // alignment of the view it was swept through (tests/test_gpu_optim.py, path equality).  This is the float4 loops' form.
 #pragma clang fp contract(off)
-    g = g * gscale;
-    if (wd != 0.f) g = __builtin_fmaf(wd, p, g);
+    if (DEC) {
+        p = p * wd;
+        g = g * gscale;
+    } else {
+        g = g * gscale;
+        if (wd != 0.f) g = __builtin_fmaf(wd, p, g);
+    }
     m = __builtin_fmaf(w1, g - m, m);
     v = __builtin_fmaf(w2 * g, g, v * b2);
     const float denom = sqrtf(v) / bc2_sqrt + eps;
     p = __builtin_fmaf(-step_size, m / denom, p);
+}
+
+// the parameter average (dv_adam_hyper.avg): e += w (p_new - e), w = fl32(1 - avg_decay); the subtraction rounded, one fma --
+// the same form in every loop of every sweep
+__device__ __forceinline__ void avg_one(float& e, float p_new, float w) {
+#pragma clang fp contract(off)
+    e = __builtin_fmaf(w, p_new - e, e);
 }
 
 // sticky error words of the step's device-side waits: (err, ticks) pairs, see dv_wait in drvae_hip.h
@@ -64,15 +84,19 @@ struct AdamGate {
 // written -- skip set: nothing is touched (not sticky, no halt word involved); else gscale * coef scales the gradient and the
 // bias corrections count the steps taken.  CLIP = false is the sweep as it ever was (adam_kernel and adam_stream_kernel: the same
 // instructions but for the kernel-argument offsets; adamax_kernel: the same arithmetic, the halt loop scheduled in front of pow()).
-template <bool CLIP>
+// DEC: decoupled weight decay (dv_adam_hyper.decoupled; see adam_one).  AVG: the parameter average rides on the sweep
+// (dv_adam_hyper.avg: one more stream, loaded and stored like p; a sweep that returns early touches none of it).  Both false is
+// the sweep as it was: the flags are compile-time, the element loops of the plain instantiations carry no trace of them.
+template <bool CLIP, bool DEC, bool AVG>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
-                                                   float b1, float b2, float eps, float wd, float gscale_in,
+                                                   float b1, float b2, float eps, float wd_in, float gscale_in,
                                                    const int32_t* __restrict__ step_dev, int vec4, AdamGate gate,
                                                    const int32_t* __restrict__ halt, int n_halt,
                                                    const dv_clip_record* __restrict__ clip,
-                                                   const float* __restrict__ lr_scale) {
-    __shared__ float sc[2];
+                                                   const float* __restrict__ lr_scale, float* __restrict__ avg,
+                                                   float avg_decay) {
+    __shared__ float sc[DEC ? 3 : 2];
     __shared__ int halted;
     // only the workgroups whose elements overlap the gated range park (typically one): a parked
     // workgroup or two can never starve the chain that is to publish
@@ -95,9 +119,11 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         if (CLIP) {
             // a skipped first step has t = 0: the corrections are not evaluated, the sweep returns before it would use them
             if (clip->skip) h = 1;
+            else if constexpr (DEC) adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], lr_scale, clip->n_skipped, &sc[2], wd_in);
             else adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], lr_scale, clip->n_skipped);
         } else {
-            adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], lr_scale);
+            if constexpr (DEC) adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], lr_scale, 0, &sc[2], wd_in);
+            else adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], lr_scale);
         }
         if (need && seen - want < 0) {
             const long long t0 = wall_clock64();
@@ -128,9 +154,12 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
     // share of the scalar tail: at least the gated slice), every later one nowhere (tests/test_gpu_optim.py)
     if (halted) return;
     const float step_size = sc[0], bc2_sqrt = sc[1];
+    float wd = wd_in;                                                    // DEC: the factor fl32(1 - lr_eff wd) in wd's place
+    if constexpr (DEC) wd = sc[2];
     const float gscale = CLIP ? gscale_in * clip->coef : gscale_in;      // fl32(gscale * coef): coef == 1.0f gives gscale's bits
     // (float)(1 - beta) computed in double first, as python does before the op sees it
     const float w1 = (float)(1.0 - (double)b1), w2 = (float)(1.0 - (double)b2);
+    const float wa = AVG ? (float)(1.0 - (double)avg_decay) : 0.f;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     if (vec4) {
@@ -139,21 +168,34 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         const float4* g4 = reinterpret_cast<const float4*>(g);
         float4* m4 = reinterpret_cast<float4*>(m);
         float4* v4 = reinterpret_cast<float4*>(v);
+        float4* e4 = reinterpret_cast<float4*>(avg);
         for (int64_t i = t0; i < n4; i += stride) {
-            float4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i];
-            adam_one(pp.x, gg.x, mm.x, vv.x, step_size, bc2_sqrt, eps, wd, w1, b2, w2, gscale);
-            adam_one(pp.y, gg.y, mm.y, vv.y, step_size, bc2_sqrt, eps, wd, w1, b2, w2, gscale);
-            adam_one(pp.z, gg.z, mm.z, vv.z, step_size, bc2_sqrt, eps, wd, w1, b2, w2, gscale);
-            adam_one(pp.w, gg.w, mm.w, vv.w, step_size, bc2_sqrt, eps, wd, w1, b2, w2, gscale);
+            float4 pp = p4[i], gg = g4[i], mm = m4[i], vv = v4[i], ee;
+            if (AVG) ee = e4[i];
+            adam_one<DEC>(pp.x, gg.x, mm.x, vv.x, step_size, bc2_sqrt, eps, wd, w1, b2, w2, gscale);
+            adam_one<DEC>(pp.y, gg.y, mm.y, vv.y, step_size, bc2_sqrt, eps, wd, w1, b2, w2, gscale);
+            adam_one<DEC>(pp.z, gg.z, mm.z, vv.z, step_size, bc2_sqrt, eps, wd, w1, b2, w2, gscale);
+            adam_one<DEC>(pp.w, gg.w, mm.w, vv.w, step_size, bc2_sqrt, eps, wd, w1, b2, w2, gscale);
             p4[i] = pp;
             m4[i] = mm;
             v4[i] = vv;
+            if (AVG) {
+                avg_one(ee.x, pp.x, wa);
+                avg_one(ee.y, pp.y, wa);
+                avg_one(ee.z, pp.z, wa);
+                avg_one(ee.w, pp.w, wa);
+                e4[i] = ee;
+            }
         }
-        for (int64_t i = (n4 << 2) + t0; i < n; i += stride)
-            adam_one(p[i], g[i], m[i], v[i], step_size, bc2_sqrt, eps, wd, w1, b2, w2, gscale);
+        for (int64_t i = (n4 << 2) + t0; i < n; i += stride) {
+            adam_one<DEC>(p[i], g[i], m[i], v[i], step_size, bc2_sqrt, eps, wd, w1, b2, w2, gscale);
+            if (AVG) avg_one(avg[i], p[i], wa);
+        }
     } else {
-        for (int64_t i = t0; i < n; i += stride)
-            adam_one(p[i], g[i], m[i], v[i], step_size, bc2_sqrt, eps, wd, w1, b2, w2, gscale);
+        for (int64_t i = t0; i < n; i += stride) {
+            adam_one<DEC>(p[i], g[i], m[i], v[i], step_size, bc2_sqrt, eps, wd, w1, b2, w2, gscale);
+            if (AVG) avg_one(avg[i], p[i], wa);
+        }
     }
 }
 
@@ -162,39 +204,48 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
 // step has streamed gigabytes through the caches), 16384 workgroups.  tools/adam_probe.hip alone: 0.629 -> 0.564 ms = 5.57 -> 6.20
 // TB/s (the guide's float4-copy figure is 6.29); inside the step (behind the dW products) 0.68 -> 0.63 ms.  Ungated (the chip-filling steps have no side chain to gate on).
 typedef float adam_f4 __attribute__((ext_vector_type(4)));
-template <bool CLIP>
+template <bool CLIP, bool DEC, bool AVG>
 __global__ __launch_bounds__(256) void adam_stream_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                           float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
-                                                          float b1, float b2, float eps, float wd, float gscale_in,
+                                                          float b1, float b2, float eps, float wd_in, float gscale_in,
                                                           const int32_t* __restrict__ step_dev,
                                                           const int32_t* __restrict__ halt, int n_halt,
                                                           const dv_clip_record* __restrict__ clip,
-                                                          const float* __restrict__ lr_scale) {
-    __shared__ float sc[2];
+                                                          const float* __restrict__ lr_scale, float* __restrict__ avg,
+                                                          float avg_decay) {
+    __shared__ float sc[DEC ? 3 : 2];
     __shared__ int halted;
     if (threadIdx.x == 0) {
         if (CLIP) {       // (see adam_kernel)
             const int skip = clip->skip;
-            if (!skip) adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], lr_scale, clip->n_skipped);
+            if (!skip) {
+                if constexpr (DEC) adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], lr_scale, clip->n_skipped, &sc[2], wd_in);
+                else adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], lr_scale, clip->n_skipped);
+            }
             halted = any_halt(halt, n_halt) | skip;
         } else {
-            adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], lr_scale);
+            if constexpr (DEC) adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], lr_scale, 0, &sc[2], wd_in);
+            else adam_consts(lr, b1, b2, step_dev, &sc[0], &sc[1], lr_scale);
             halted = any_halt(halt, n_halt);
         }
     }
     __syncthreads();
     if (halted) return;
     const float step_size = sc[0], bc2_sqrt = sc[1];
+    float wd = wd_in;                                                    // (see adam_kernel)
+    if constexpr (DEC) wd = sc[2];
     const float gscale = CLIP ? gscale_in * clip->coef : gscale_in;
     const float w1 = (float)(1.0 - (double)b1), w2 = (float)(1.0 - (double)b2);
+    const float wa = AVG ? (float)(1.0 - (double)avg_decay) : 0.f;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x, n4 = n >> 2;
     const int64_t t0 = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
     adam_f4* p4 = reinterpret_cast<adam_f4*>(p);
     const adam_f4* g4 = reinterpret_cast<const adam_f4*>(g);
     adam_f4* m4 = reinterpret_cast<adam_f4*>(m);
     adam_f4* v4 = reinterpret_cast<adam_f4*>(v);
+    adam_f4* e4 = reinterpret_cast<adam_f4*>(avg);
     for (int64_t i = t0; i < n4; i += 2 * stride) {
-        adam_f4 pp[2], gg[2], mm[2], vv[2];
+        adam_f4 pp[2], gg[2], mm[2], vv[2], ee[2];
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             const int64_t j = i + u * stride < n4 ? i + u * stride : i;
@@ -202,25 +253,34 @@ __global__ __launch_bounds__(256) void adam_stream_kernel(float* __restrict__ p,
             gg[u] = __builtin_nontemporal_load(g4 + j);
             mm[u] = __builtin_nontemporal_load(m4 + j);
             vv[u] = __builtin_nontemporal_load(v4 + j);
+            if (AVG) ee[u] = __builtin_nontemporal_load(e4 + j);
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 float a = pp[u][e], b = mm[u][e], c = vv[u][e];
-                adam_one(a, gg[u][e], b, c, step_size, bc2_sqrt, eps, wd, w1, b2, w2, gscale);
+                adam_one<DEC>(a, gg[u][e], b, c, step_size, bc2_sqrt, eps, wd, w1, b2, w2, gscale);
                 pp[u][e] = a; mm[u][e] = b; vv[u][e] = c;
+                if (AVG) {
+                    float d = ee[u][e];
+                    avg_one(d, a, wa);
+                    ee[u][e] = d;
+                }
             }
             const int64_t j = i + u * stride;
             if (j < n4) {
                 __builtin_nontemporal_store(pp[u], p4 + j);
                 __builtin_nontemporal_store(mm[u], m4 + j);
                 __builtin_nontemporal_store(vv[u], v4 + j);
+                if (AVG) __builtin_nontemporal_store(ee[u], e4 + j);
             }
         }
     }
-    for (int64_t i = (n4 << 2) + t0; i < n; i += stride)
-        adam_one(p[i], g[i], m[i], v[i], step_size, bc2_sqrt, eps, wd, w1, b2, w2, gscale);
+    for (int64_t i = (n4 << 2) + t0; i < n; i += stride) {
+        adam_one<DEC>(p[i], g[i], m[i], v[i], step_size, bc2_sqrt, eps, wd, w1, b2, w2, gscale);
+        if (AVG) avg_one(avg[i], p[i], wa);
+    }
 }
 
 // ------------------------------------------------------------------ gradient-norm clipping
@@ -497,14 +557,16 @@ extern "C" int dv_abi_version(void) { return DV_ABI_VERSION; }
 
 // torch.optim.Adamax (2.x `_single_tensor_adamax`), the other branch of src/DGMMixin.py:37-38:
 // grad += wd*p; m.lerp_(g, 1-b1); u = max(u*b2, |g|+eps); p += -(lr/(1-b1^t)) * (m/u)
-template <bool CLIP>
+// AVG: the parameter average rides on the sweep (see adam_kernel); there is no decoupled Adamax
+template <bool CLIP, bool AVG>
 __global__ __launch_bounds__(256) void adamax_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                      float* __restrict__ m, float* __restrict__ u, int64_t n, float lr,
                                                      float b1, float b2, float eps, float wd, float gscale_in,
                                                      const int32_t* __restrict__ step_dev,
                                                      const int32_t* __restrict__ halt, int n_halt,
                                                      const dv_clip_record* __restrict__ clip,
-                                                     const float* __restrict__ lr_scale) {
+                                                     const float* __restrict__ lr_scale, float* __restrict__ avg,
+                                                     float avg_decay) {
     __shared__ float sc[2];
     __shared__ int halted;
     if (threadIdx.x == 0) {
@@ -526,6 +588,7 @@ __global__ __launch_bounds__(256) void adamax_kernel(float* __restrict__ p, cons
     const float clr = sc[0];
     const float gscale = CLIP ? gscale_in * clip->coef : gscale_in;
     const float w1 = (float)(1.0 - (double)b1);
+    const float wa = AVG ? (float)(1.0 - (double)avg_decay) : 0.f;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += stride) {
         float gg = g[i] * gscale;
@@ -535,7 +598,13 @@ __global__ __launch_bounds__(256) void adamax_kernel(float* __restrict__ p, cons
         const float uu = fmaxf(u[i] * b2, fabsf(gg) + eps);
         m[i] = mm;
         u[i] = uu;
-        p[i] = pp + (-clr) * (mm / uu);
+        const float pn = pp + (-clr) * (mm / uu);
+        p[i] = pn;
+        if (AVG) {
+            float e = avg[i];
+            avg_one(e, pn, wa);
+            avg[i] = e;
+        }
     }
 }
 
@@ -560,33 +629,57 @@ extern "C" const char* dv_error_string(int code) {
     }
 }
 
+// compile-time flags from run-time switches: f(integral_constant<bool, a>, <b>) and f(<a>, <b>, <c>)
+template <typename F>
+static void with_flags(bool a, bool b, F f) {
+    auto second = [&](auto A) {
+        if (b) f(A, std::true_type{});
+        else f(A, std::false_type{});
+    };
+    if (a) second(std::true_type{});
+    else second(std::false_type{});
+}
+
+template <typename F>
+static void with_flags(bool a, bool b, bool c, F f) {
+    with_flags(a, b, [&](auto A, auto B) {
+        if (c) f(A, B, std::true_type{});
+        else f(A, B, std::false_type{});
+    });
+}
+
+// the trailing fields of dv_adam_hyper a sweep may not be launched with (checked before any launch)
+static bool avg_ok(const dv_adam_hyper* h) {
+    if (h->avg == nullptr) return true;
+    return h->avg_decay > 0.f && h->avg_decay < 1.f && (reinterpret_cast<uintptr_t>(h->avg) & 3) == 0;
+}
+
 static int adam_launch(float* p, const float* g, float* m, float* v, int64_t n, const dv_adam_hyper* h,
                        const int32_t* step_dev, const AdamGate& gate, const int32_t* halt, int32_t n_halt,
                        dv_stream_t stream, const dv_clip_record* clip) {
     DV_REQUIRE(h != nullptr && n >= 0 && n_halt >= 0 && (halt || n_halt == 0));
+    DV_REQUIRE(avg_ok(h));
     if (n == 0) return DV_OK;
     DV_REQUIRE(p && g && m && v && step_dev);
     auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const int vec4 = al(p) && al(g) && al(m) && al(v);
+    const int vec4 = al(p) && al(g) && al(m) && al(v) && al(h->avg);      // (a NULL average is aligned)
     int64_t blocks = ((vec4 ? (n >> 2) : n) + 255) / 256;
     if (blocks < 1) blocks = 1;
     if (vec4 && gate.flag == nullptr && n >= (int64_t(16) << 20)) {       // far beyond the Infinity Cache: the streaming sweep
         const dim3 grid((unsigned)(blocks > 16384 ? 16384 : blocks));
-        if (clip)
-            hipLaunchKernelGGL(adam_stream_kernel<true>, grid, dim3(256), 0, ST(stream), p, g, m, v, n, h->lr, h->beta1, h->beta2,
-                               h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt, clip, h->lr_scale);
-        else
-            hipLaunchKernelGGL(adam_stream_kernel<false>, grid, dim3(256), 0, ST(stream), p, g, m, v, n, h->lr, h->beta1, h->beta2,
-                               h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt, clip, h->lr_scale);
+        with_flags(clip != nullptr, h->decoupled != 0, h->avg != nullptr, [&](auto C, auto D, auto A) {
+            hipLaunchKernelGGL((adam_stream_kernel<decltype(C)::value, decltype(D)::value, decltype(A)::value>), grid, dim3(256), 0,
+                               ST(stream), p, g, m, v, n, h->lr, h->beta1, h->beta2, h->eps, h->weight_decay, h->gscale, step_dev,
+                               halt, n_halt, clip, h->lr_scale, h->avg, h->avg_decay);
+        });
         DV_RETURN_LAUNCH();
     }
     if (blocks > 2048) blocks = 2048;
-    if (clip)
-        hipLaunchKernelGGL(adam_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, v, n, h->lr, h->beta1,
-                           h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, vec4, gate, halt, n_halt, clip, h->lr_scale);
-    else
-        hipLaunchKernelGGL(adam_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, v, n, h->lr, h->beta1,
-                           h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, vec4, gate, halt, n_halt, clip, h->lr_scale);
+    with_flags(clip != nullptr, h->decoupled != 0, h->avg != nullptr, [&](auto C, auto D, auto A) {
+        hipLaunchKernelGGL((adam_kernel<decltype(C)::value, decltype(D)::value, decltype(A)::value>), dim3((unsigned)blocks),
+                           dim3(256), 0, ST(stream), p, g, m, v, n, h->lr, h->beta1, h->beta2, h->eps, h->weight_decay, h->gscale,
+                           step_dev, vec4, gate, halt, n_halt, clip, h->lr_scale, h->avg, h->avg_decay);
+    });
     DV_RETURN_LAUNCH();
 }
 
@@ -603,16 +696,16 @@ static int adamax_launch(float* p, const float* g, float* m, float* u, int64_t n
                          const int32_t* step_dev, const int32_t* halt, int32_t n_halt, dv_stream_t stream,
                          const dv_clip_record* clip) {
     DV_REQUIRE(h != nullptr && n >= 0 && n_halt >= 0 && (halt || n_halt == 0));
+    DV_REQUIRE(h->decoupled == 0 && avg_ok(h));       // (torch has no decoupled Adamax: nothing to be equal to)
     if (n == 0) return DV_OK;
     DV_REQUIRE(p && g && m && u && step_dev);
     int64_t blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    if (clip)
-        hipLaunchKernelGGL(adamax_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, u, n, h->lr,
-                           h->beta1, h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt, clip, h->lr_scale);
-    else
-        hipLaunchKernelGGL(adamax_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), p, g, m, u, n, h->lr,
-                           h->beta1, h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt, clip, h->lr_scale);
+    with_flags(clip != nullptr, h->avg != nullptr, [&](auto C, auto A) {
+        hipLaunchKernelGGL((adamax_kernel<decltype(C)::value, decltype(A)::value>), dim3((unsigned)blocks), dim3(256), 0, ST(stream),
+                           p, g, m, u, n, h->lr, h->beta1, h->beta2, h->eps, h->weight_decay, h->gscale, step_dev, halt, n_halt,
+                           clip, h->lr_scale, h->avg, h->avg_decay);
+    });
     DV_RETURN_LAUNCH();
 }
 

@@ -38,6 +38,7 @@ from .schedule import DUAL, EVAL, EVALUATE, FORK_JOIN, LOSS, TRAIN, StepSchedule
 
 # the precision ladder of the decoder-heads products: fp32, then the split-bf16 rungs by falling number of parts
 MATMUL_CHOICES = ('fp32',) + tuple(X3_PARTS)
+OPTIM_ALGS = ('adam', 'adamax', 'adamw')      # 'adamw': Adam with decoupled weight decay (dv_adam_hyper.decoupled)
 assert MATMUL_CHOICES == ('fp32', 'bf16x3', 'bf16x2', 'bf16x1')
 
 
@@ -120,8 +121,16 @@ class StepConfig:
     anneal_yloss_offset: int = 0
     anneal_learning_rate: bool = False
     anneal_lr_itermax: int = 3000
+    # EXTENSION (no counterpart in the reference): the exponential moving average of the parameters, kept by the optimiser
+    # sweep itself -- e += (1 - ema_decay)(p_new - e) on every TAKEN step, one more stream of the sweep's launch
+    # (``ParamArena.avg``, ``dv_adam_hyper.avg``).  None: nothing of this exists -- no buffer, no launch
+    # argument, the step as it ever was.  ``optim_alg='adamw'`` is Adam with torch.optim.AdamW's decoupled weight decay
+    ema_decay: Optional[float] = None
 
     def __post_init__(self):
+        if self.optim_alg not in OPTIM_ALGS:
+            raise ValueError('StepConfig.optim_alg must be one of %s, not %r' % (OPTIM_ALGS, self.optim_alg))
+        self.ema_decay = check_ema_decay(self.ema_decay, 'StepConfig.ema_decay')
         for sw, mx in (('anneal_kl', 'anneal_kl_itermax'), ('anneal_yloss', 'anneal_yloss_itermax'),
                        ('anneal_learning_rate', 'anneal_lr_itermax')):
             setattr(self, sw, bool(getattr(self, sw)))
@@ -159,6 +168,16 @@ class StepConfig:
     @property
     def has_y(self):
         return self.kind in ('drvae', 'vfae')
+
+
+def check_ema_decay(d, what='ema_decay'):
+    """None or a float in (0, 1); ValueError otherwise"""
+    if d is None:
+        return None
+    d = float(d)
+    if not 0.0 < d < 1.0:               # (NaN fails this too)
+        raise ValueError('%s must be None or a number in (0, 1), not %r' % (what, d))
+    return d
 
 
 def anneal_coef(iter_num, iter_max=1000, iter_offset=0):
@@ -277,6 +296,12 @@ class FusedStep(StepSchedule):
         # device memory for the engine's life, rewritten at the head of every step by the launch that writes the batch's
         # masks; the sweeps read its last word.  None: no schedule, nothing of this exists
         self.sched_rec = torch.ones(4, device=self.dev) if cfg.annealed else None
+        # the parameter average (``StepConfig.ema_decay``): a sibling of the parameter arena, started as a copy of it, moved by
+        # every sweep of the step.  ``averaged``: the parameter arena HOLDS the averaged values (``averaged_parameters``: the
+        # contents are swapped, never the pointers -- captured graphs have the arena's addresses baked in); no train step then
+        if cfg.ema_decay is not None:
+            arena.ensure_avg()
+        self.averaged = False
         self.seed = seed
         self.training = True
         self.fuse_bwd = False               # set by train_step/capture: forward is followed by backward
@@ -974,7 +999,7 @@ class FusedStep(StepSchedule):
         cfg = self.cfg
         if cfg.has_y:
             return self.branch.on if on_gpu is None else bool(self.concurrent and on_gpu)
-        return bool(cfg.kind == 'pvae' and self.concurrent and cfg.optim_alg == 'adam')
+        return bool(cfg.kind == 'pvae' and self.concurrent and cfg.optim_alg in ('adam', 'adamw'))
 
     def _side_adam_layout(self):
         """(may the side chain sweep the decoder heads' half of the arena?, first element of that half)"""
@@ -1338,7 +1363,7 @@ class FusedStep(StepSchedule):
             if t.side_adam:
                 K.adam_l2(a.param[hs:a.n_live], a.grad[hs:a.n_live], a.exp_avg[hs:a.n_live],
                           a.exp_avg_sq[hs:a.n_live], self.side_t, lr=cfg.learning_rate,
-                          weight_decay=cfg.weight_decay, halt=self.sync_err, **self._lr_kw())
+                          weight_decay=cfg.weight_decay, halt=self.sync_err, **self._lr_kw(), **self._opt_kw(hs, a.n_live))
             if not t.fold_rows:
                 self._loss_scalars()   # a leaf too; the wait above also covers the main chain's NLL rows
         if t.noise_ahead:
@@ -1370,6 +1395,9 @@ class FusedStep(StepSchedule):
             # eager step: the side chain's counters follow, and so does the "side chain's tail is through" flag that the
             # NEXT captured step's first launch waits for (published on entry: counter + 1 = the advanced value)
             K.counters_add2(self.side_ctr, 1, self.side_t, 1, publish=self.sync.pub('tail', self.side_ctr))
+        if self.averaged:
+            raise RuntimeError('the parameter arena holds the AVERAGED parameters (averaged_parameters()): no optimiser step '
+                               'inside that context')
         step = K.adamax_l2 if cfg.optim_alg == 'adamax' else K.adam_l2    # exp_avg_sq doubles as Adamax's exp_inf
         n = a.n_live                      # parameters without gradients sit behind it (untouched, like torch)
         t, kw = (self._tail if self._rec == 'main' else None), {}
@@ -1381,7 +1409,8 @@ class FusedStep(StepSchedule):
             K.clip_norm(a.grad[:n], self.clip_state, gscale=gscale)
             step = K.adamax_l2_clip if cfg.optim_alg == 'adamax' else K.adam_l2_clip
             step(a.param[:n], a.grad[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.clip_state,
-                 lr=cfg.learning_rate, weight_decay=cfg.weight_decay, gscale=gscale, halt=self.sync_err, **self._lr_kw())
+                 lr=cfg.learning_rate, weight_decay=cfg.weight_decay, gscale=gscale, halt=self.sync_err, **self._lr_kw(),
+                 **self._opt_kw(0, n))
             return
         if t and t.adam_gated:   # dual-graph step: the classifier's dW may still be in flight on the side chain
             # (the optimiser's gate waits with counter + 0: the step counter is advanced before it)
@@ -1398,7 +1427,37 @@ class FusedStep(StepSchedule):
             # its first launch reads the noise the side chain has drawn -- behind it)
             kw['gate'] = self.sync.gate('tail', self.step_dev, 0, 4)
         step(a.param[:n], a.grad[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.step_dev, lr=cfg.learning_rate,
-             weight_decay=cfg.weight_decay, gscale=gscale, halt=self.sync_err, **kw, **self._lr_kw())
+             weight_decay=cfg.weight_decay, gscale=gscale, halt=self.sync_err, **kw, **self._lr_kw(), **self._opt_kw(0, n))
+
+    def _refuse_averaged(self, what):
+        if self.averaged:
+            raise RuntimeError('%s inside averaged_parameters(): the parameter arena holds the averaged values, a train '
+                               'step would train them' % what)
+
+    def swap_average(self):
+        """exchange the CONTENTS of the parameter arena and of the average (the whole arena: pads and the frozen tail are
+        equal in both), through the gradient arena -- dead between steps -- as scratch.  Three copies on the current stream,
+        behind the side chain; twice is the identity, bit for bit"""
+        a = self.arena
+        if not hasattr(a, 'avg'):
+            raise RuntimeError('the engine was built without ema_decay: there is no parameter average')
+        self.join_side()
+        with torch.no_grad():
+            a.grad.copy_(a.param)
+            a.param.copy_(a.avg)
+            a.avg.copy_(a.grad)
+        self.averaged = not self.averaged
+
+    def _opt_kw(self, lo, hi):
+        """AdamW and the parameter average: every sweep of the step (gated, capped fork, the side chain's half) takes the
+        decoupled switch and the slice of the average that belongs to the elements [lo, hi) it sweeps; off: no argument at all,
+        the call as it ever was"""
+        kw = {}
+        if self.cfg.optim_alg == 'adamw':
+            kw['decoupled'] = True
+        if self.cfg.ema_decay is not None:
+            kw.update(avg=self.arena.avg[lo:hi], avg_decay=self.cfg.ema_decay)
+        return kw
 
     def _lr_kw(self):
         """learning-rate annealing: every sweep of the step (the side chain's half included) reads the rate's coefficient from
@@ -1417,6 +1476,7 @@ class FusedStep(StepSchedule):
     def train_step(self, noise=None, allreduce=None):
         """forward + backward (+ gradient all-reduce) + Adam + iteration count: the body of
         ``run_on_batch(train_mode=True)`` (src/DGMMixin.py:91-126)."""
+        self._refuse_averaged('train_step')
         self.training = True
         self.join_side()
         if noise is not None:

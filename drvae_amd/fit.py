@@ -357,6 +357,14 @@ class FitMixin:
                           'optimiser state were left as they were' % (epoch, now - before, now))
         return now
 
+    def _fit_weights(self):
+        """the weights ``fit`` evaluates and snapshots: the parameter average (``averaged_parameters()``) of a model built
+        with ``ema_decay`` unless ``self.ema_eval`` is false, else the live ones (a null context: nothing happens)"""
+        import contextlib
+        if getattr(self, 'ema_decay', None) is not None and getattr(self, 'ema_eval', True):
+            return self.averaged_parameters()
+        return contextlib.nullcontext()
+
     def fit(self, train_loader, valid_loader, add_noise=False, verbose=False, early_stop=False,
             model_filename='best_model.pth'):
         """Train for ``self.epochs`` epochs with the reference's validation / early-stopping /
@@ -376,22 +384,24 @@ class FitMixin:
                 else:
                     train_loss = self._epoch_loader(train_loader, epoch, verbose)
                 skipped = self._warn_skipped_steps(epoch, skipped) if self._max_grad_norm is not None else 0
-                train_perf, train_str = self.evaluate_performance_on_dataset(train_loader.dataset)
-                self.w2log('====> Epoch: {}\tIter: {}'.format(epoch, self.finished_training_iters))
-                self.w2log('Train: sec/epoch: {:.2f}\tAvg train loss: {:9.4f}\t{}'.format(time.time() - t, train_loss,
-                                                                                     train_str))
-                t = time.time()
-                valid_perf, perf_str = self.evaluate_performance_on_dataset(valid_loader.dataset)
-                valid_loss = self._valid_objective(valid_perf)
-                self.w2log('Valid: sec/epoch: {:.2f}\tValid set loss: {:9.4f}\t{}'.format(time.time() - t, valid_loss,
-                                                                                      perf_str))
-                d = ctl.update(epoch, valid_loss)
-                self.w2log('Valid rolling mem: {}\tmean: {:.4f}\tbest: {:.4f}'.format(d['rolling'], d['rolling_mean'],
-                                                                                    d['best_before']))
-                if d['snapshot']:
-                    if self.dp_rank == 0:        # (data parallelism: the replicas are identical; one writer)
-                        self.save_to_file(model_filename)
-                    self.w2log('* Snapshotting at epoch {}'.format(epoch))
+                # (``ema_decay``: the two evaluations and the snapshot see the averaged weights unless ``ema_eval`` is off)
+                with self._fit_weights():
+                    train_perf, train_str = self.evaluate_performance_on_dataset(train_loader.dataset)
+                    self.w2log('====> Epoch: {}\tIter: {}'.format(epoch, self.finished_training_iters))
+                    self.w2log('Train: sec/epoch: {:.2f}\tAvg train loss: {:9.4f}\t{}'.format(time.time() - t, train_loss,
+                                                                                         train_str))
+                    t = time.time()
+                    valid_perf, perf_str = self.evaluate_performance_on_dataset(valid_loader.dataset)
+                    valid_loss = self._valid_objective(valid_perf)
+                    self.w2log('Valid: sec/epoch: {:.2f}\tValid set loss: {:9.4f}\t{}'.format(time.time() - t, valid_loss,
+                                                                                          perf_str))
+                    d = ctl.update(epoch, valid_loss)
+                    self.w2log('Valid rolling mem: {}\tmean: {:.4f}\tbest: {:.4f}'.format(d['rolling'], d['rolling_mean'],
+                                                                                        d['best_before']))
+                    if d['snapshot']:
+                        if self.dp_rank == 0:        # (data parallelism: the replicas are identical; one writer)
+                            self.save_to_file(model_filename)
+                        self.w2log('* Snapshotting at epoch {}'.format(epoch))
                 if d['patience_hit']:
                     self.w2log('Early stopping at: {} with train: {:.4f} valid: {:.4f} evaluate_valid_obj: {:.4f} '
                                'best_valid_obj: {:.4f}'.format(epoch, train_loss, valid_loss, d['rolling_mean'],
@@ -402,7 +412,8 @@ class FitMixin:
         except KeyboardInterrupt:
             self.w2log('KeyboardInterrupt')
             if ctl.on_interrupt() and self.dp_rank == 0:
-                self.save_to_file(model_filename)
+                with self._fit_weights():
+                    self.save_to_file(model_filename)
                 self.w2log('* Snapshotting at epoch {}'.format(epoch))
         self.w2log('Finished training at: {}'.format(time.strftime('%c')))
         self._fit_controller = ctl

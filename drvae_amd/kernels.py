@@ -1124,22 +1124,33 @@ def axpby(y, x, a=1.0, b=0.0):
 
 
 # ------------------------------------------------------------------------- optimiser
-def _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale):
+def _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale, p=None, decoupled=False, avg=None, avg_decay=None):
     """dv_adam_hyper; ``lr_scale``: None or a 1-element fp32 device tensor the sweep multiplies the rate by (in double, one
-    rounding: learning-rate annealing)"""
+    rounding: learning-rate annealing); ``decoupled``: AdamW's weight decay (p *= 1 - lr * wd, no wd * p in the gradient);
+    ``avg`` / ``avg_decay``: the parameter average riding on the sweep, laid out like ``p`` -- e += (1 - avg_decay)(p_new - e).
+    The three defaults leave the trailing fields zero: the sweep as it was"""
     assert lr_scale is None or (lr_scale.dtype == torch.float32 and lr_scale.numel() == 1)
-    return _lib.AdamHyper(lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, gscale=gscale,
-                          lr_scale=_f32(lr_scale))
+    h = _lib.AdamHyper(lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay, gscale=gscale,
+                       lr_scale=_f32(lr_scale))
+    if decoupled:
+        h.decoupled = 1
+    if avg is not None:
+        if avg_decay is None:
+            raise ValueError('an average needs its avg_decay')
+        assert avg.dtype == torch.float32 and avg.is_contiguous() and avg.numel() == p.numel() and avg.device == p.device
+        h.avg, h.avg_decay = _f32(avg), avg_decay
+    return h
 
 
 def adam_l2(p, g, m, v, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, gate=None,
-            halt=None, lr_scale=None):
+            halt=None, lr_scale=None, decoupled=False, avg=None, avg_decay=None):
     """``gate`` = a ``Gate``: elements [lo, hi) wait for the flag (``dv_adam_l2_gated``);
     ``halt``: the (err, ticks) pairs of the step's waits -- any error set: nothing is updated;
-    ``lr_scale``: a device scalar the rate is multiplied by (``_hyper``; every sweep below takes it)"""
+    ``lr_scale``: a device scalar the rate is multiplied by (``_hyper``; every sweep below takes it);
+    ``decoupled``, ``avg``, ``avg_decay``: AdamW's decay and the parameter average (``_hyper``; Adamax takes the average only)"""
     assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
     hp, hn = _halt(halt)
-    h = _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale)
+    h = _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale, p, decoupled, avg, avg_decay)
     if gate is None:
         _lib.check(_lib.load().dv_adam_l2(_f32(p), _f32(g), _f32(m), _f32(v), p.numel(), C.byref(h), _i32(step_dev), hp, hn,
                                           _stream()), 'dv_adam_l2')
@@ -1151,10 +1162,10 @@ def adam_l2(p, g, m, v, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weigh
 
 
 def adamax_l2(p, g, m, u, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None,
-              lr_scale=None):
+              lr_scale=None, decoupled=False, avg=None, avg_decay=None):
     assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and u.is_contiguous()
     hp, hn = _halt(halt)
-    h = _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale)
+    h = _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale, p, decoupled, avg, avg_decay)
     _lib.check(_lib.load().dv_adamax_l2(_f32(p), _f32(g), _f32(m), _f32(u), p.numel(), C.byref(h), _i32(step_dev), hp, hn,
                                         _stream()), 'dv_adamax_l2')
 
@@ -1210,21 +1221,21 @@ def clip_norm(g, state, *, gscale=1.0):
 
 
 def adam_l2_clip(p, g, m, v, state, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None,
-                 lr_scale=None):
+                 lr_scale=None, decoupled=False, avg=None, avg_decay=None):
     """``adam_l2`` reading the record of the clip state (whose first word is the step): skipped when the record says so, else
     the gradient scaled by fl32(gscale * coef) and t = step - n_skipped.  No gated form."""
     assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
     hp, hn = _halt(halt)
-    h = _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale)
+    h = _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale, p, decoupled, avg, avg_decay)
     _lib.check(_lib.load().dv_adam_l2_clipped(_f32(p), _f32(g), _f32(m), _f32(v), p.numel(), C.byref(h), _i32(state), hp, hn,
                                               _stream()), 'dv_adam_l2_clipped')
 
 
 def adamax_l2_clip(p, g, m, u, state, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None,
-                   lr_scale=None):
+                   lr_scale=None, decoupled=False, avg=None, avg_decay=None):
     assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and u.is_contiguous()
     hp, hn = _halt(halt)
-    h = _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale)
+    h = _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale, p, decoupled, avg, avg_decay)
     _lib.check(_lib.load().dv_adamax_l2_clipped(_f32(p), _f32(g), _f32(m), _f32(u), p.numel(), C.byref(h), _i32(state), hp, hn,
                                                 _stream()), 'dv_adamax_l2_clipped')
 

@@ -320,7 +320,7 @@ class StepSchedule:
             # (round 6, cfg 5: 31.09-31.15 -> 30.87-30.89 ms; the side chain's 0.4 ms are through long before the join)
             return Tail(late_fork=bool(branch_on and not self._latency_bound()))
         # the side chain carries the step's leaf work (classifier dW, heads' optimiser half, loss scalars) behind the join
-        late_ok = bool(not cfg.cont and cfg.optim_alg == 'adam' and (self.clf_small if cfg.has_y else True))
+        late_ok = bool(not cfg.cont and cfg.optim_alg in ('adam', 'adamw') and (self.clf_small if cfg.has_y else True))
         # (dual-graph schedule) the classifier's weight gradient is a leaf -- only the optimiser reads it --
         # and the side chain is the one the join waits for: it runs AFTER the side chain has published its
         # data gradients, and the optimiser launch gates that slice of the arena on a flag of its own
@@ -446,6 +446,7 @@ class StepSchedule:
         gradient arena can run between backward and Adam; ``split_for_allreduce='captured'`` with
         ``allreduce``: the collective is captured INTO the step's graph (RCCL supports stream capture),
         no graph boundary, no host-side launch of the exchange."""
+        self._refuse_averaged('capture')
         self._captured_allreduce = allreduce if split_for_allreduce == 'captured' else None
         assert self.plan is not None, 'set_batch first'
         self.join_side()
@@ -589,6 +590,8 @@ class StepSchedule:
         state = (a.param, a.exp_avg, a.exp_avg_sq, self.step_dev, self.side_ctr, self.side_t, self.rng_ctr, self.flags)
         if self.clip_rec is not None:     # a tuning replay the guard skips counts in ``n_skipped``: it goes back with the step
             state = state + (self.clip_rec,)
+        if hasattr(a, 'avg'):             # the tuning replays move the parameter average too: it goes back with the parameters
+            state = state + (a.avg,)
         keep = [t.clone() for t in state]
         iters = self.iters
         best = (None, float('inf'))
@@ -737,6 +740,7 @@ class StepSchedule:
 
     def replay(self, allreduce=None):
         """One captured train step.  New data is fed by copying into plan.x1 / plan.x2 in place."""
+        self._refuse_averaged('replay')
         assert self._graph_key == self.plan.key, 'batch structure changed: capture again'
         assert self._graph_feed is self.plan.live_feed, 'input source changed (epoch feed <-> explicit batch): capture again'
         assert self._graph_mmd_sig == getattr(self.plan, 'mmd_sig', None), \

@@ -1092,7 +1092,18 @@ int dv_axpby(const float* x, float a, float* y, float b, int64_t n, dv_stream_t 
  * arithmetic order of torch 2.x `_single_tensor_adam`, on a flat fp32 arena.
  * step_dev[0] (int32, device) is the 1-based step used for the bias corrections; it is
  * read, not modified (bump it with dv_counter_add so graph replays advance). gscale
- * multiplies g first (1/world_size style scaling; 1.0 for summed gradients). */
+ * multiplies g first (1/world_size style scaling; 1.0 for summed gradients).
+ * Two options ride on every sweep below through trailing fields of dv_adam_hyper (all zero / NULL: the sweep as it was):
+ *   decoupled    AdamW (torch 2.x `_single_tensor_adam` under torch.optim.AdamW): p *= (float)(1 - lr_eff * weight_decay)
+ *                first (the factor in double, rounded once; lr_eff the annealed rate), the gradient takes no wd*p term, the
+ *                moments and the update follow as ever.  The clip coefficient does not touch the decay.  Adam sweeps only:
+ *                dv_adamax_l2 / dv_adamax_l2_clipped return DV_ERR_ARG (torch has no decoupled Adamax)
+ *   avg          the exponential moving average of the parameters: after an element's new p is formed,
+ *                e = fmaf(w, p_new - e, e) with w = (float)(1.0 - (double)avg_decay); n floats laid out like p (element 0
+ *                belongs to p[0] of THIS call), loaded and stored the way p is on each path (it joins the 16-B alignment
+ *                test).  A sweep that returns early -- a halt word set, a clipped step skipped for a non-finite gradient, a
+ *                parked workgroup whose gate timed out -- touches nothing of it.  avg_decay outside (0, 1) or avg not
+ *                4-byte aligned: DV_ERR_ARG before any launch.  9 words of traffic per parameter instead of 7 */
 typedef struct dv_adam_hyper {      /* ABI 11: six same-typed scalars travel by name, not by position */
     float lr;
     float beta1;
@@ -1104,6 +1115,9 @@ typedef struct dv_adam_hyper {      /* ABI 11: six same-typed scalars travel by 
      * evaluates the bias corrections; the sweep then runs with lr_eff = (float)((double)lr * (double)lr_scale[0]) where it
      * uses lr (lr_scale[0] == 1.0f: the plain sweep's bits).  Every sweep below honours it, gated and clipped included */
     const float* lr_scale;
+    int32_t decoupled;   /* 0: coupled L2 (as ever). 1: AdamW */
+    float avg_decay;     /* d of the average; read only when avg != NULL */
+    float* avg;          /* NULL: no average. Else n floats laid out like p (element 0 = p[0] of THIS call) */
 } dv_adam_hyper;
 int dv_adam_l2(float* p, const float* g, float* m, float* v, int64_t n, const dv_adam_hyper* h,
                const int32_t* step_dev, const int32_t* halt, int32_t n_halt, dv_stream_t stream);
