@@ -155,4 +155,21 @@ __device__ __forceinline__ void publish_block0(const dv_publish& pub) {
         __hip_atomic_store(pub.flag, pub.ctr[0] + pub.add, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// an entry point's optional dv_publish: *pub = the argument, or "nothing published"; a flag without its counter is refused
+static inline int take_publish(const dv_publish* in, dv_publish* pub) {
+    *pub = in ? *in : dv_publish{nullptr, nullptr, 0};
+    return (pub->flag == nullptr || pub->ctr != nullptr) ? DV_OK : DV_ERR_ARG;
+}
+
+// a device counter of one int32 word, or of two (lo | hi of a 64-bit count), advanced by inc (one thread)
+__device__ __forceinline__ void counter_add_words(int32_t* c, int n_words, int64_t inc) {
+    if (n_words == 1) {
+        c[0] = (int32_t)(c[0] + inc);
+    } else {
+        uint64_t v = ((uint64_t)(uint32_t)c[1] << 32) | (uint32_t)c[0];
+        v += (uint64_t)inc;
+        c[0] = (int32_t)(uint32_t)v;
+        c[1] = (int32_t)(uint32_t)(v >> 32);
+    }
+}
 

@@ -361,33 +361,14 @@ __global__ __launch_bounds__(256) void clip_finalize_kernel(const double* __rest
 
 __global__ void counter_add_kernel(int32_t* c, int n_words, int64_t inc) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    if (n_words == 1) {
-        c[0] = (int32_t)(c[0] + inc);
-    } else {
-        uint64_t v = ((uint64_t)(uint32_t)c[1] << 32) | (uint32_t)c[0];
-        v += (uint64_t)inc;
-        c[0] = (int32_t)(uint32_t)v;
-        c[1] = (int32_t)(uint32_t)(v >> 32);
-    }
+    counter_add_words(c, n_words, inc);
 }
 
 __global__ void counters_add2_kernel(int32_t* c1, int n1, int64_t inc1, int32_t* c2, int n2, int64_t inc2, dv_publish pub) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     publish_block0(pub);      // (before the counters move: pub.ctr may be one of them)
-    int32_t* cs[2] = {c1, c2};
-    const int ns[2] = {n1, n2};
-    const int64_t incs[2] = {inc1, inc2};
-    for (int t = 0; t < 2; ++t) {
-        int32_t* c = cs[t];
-        if (ns[t] == 1) {
-            c[0] = (int32_t)(c[0] + incs[t]);
-        } else {
-            uint64_t v = ((uint64_t)(uint32_t)c[1] << 32) | (uint32_t)c[0];
-            v += (uint64_t)incs[t];
-            c[0] = (int32_t)(uint32_t)v;
-            c[1] = (int32_t)(uint32_t)(v >> 32);
-        }
-    }
+    counter_add_words(c1, n1, inc1);
+    counter_add_words(c2, n2, inc2);
 }
 
 // ------------------------------------------------------------------ Philox4x32-10
@@ -404,14 +385,21 @@ __device__ __forceinline__ void philox_round(uint32_t& c0, uint32_t& c1, uint32_
 
 __device__ __forceinline__ float u01(uint32_t x) { return ((float)x + 0.5f) * 2.3283064365386963e-10f; }
 
-__device__ __forceinline__ void philox_normal4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                               uint32_t k1, float (&z)[4]) {
+// 10 rounds of Philox4x32 in place: the four output words of counter (c0..c3) under key (k0, k1)
+__device__ __forceinline__ void philox_block(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0,
+                                             uint32_t k1) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         philox_round(c0, c1, c2, c3, k0, k1);
         k0 += 0x9E3779B9u;
         k1 += 0xBB67AE85u;
     }
+}
+
+// four N(0,1) values of one block: Box-Muller over its word pairs (0, 1) and (2, 3)
+__device__ __forceinline__ void philox_normal4(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                               uint32_t k1, float (&z)[4]) {
+    philox_block(c0, c1, c2, c3, k0, k1);
     const float r0 = sqrtf(-2.f * logf(u01(c0))), r1 = sqrtf(-2.f * logf(u01(c2)));
     float s0, co0, s1, co1;
     sincosf(6.283185307179586f * u01(c1), &s0, &co0);
@@ -426,11 +414,26 @@ __device__ __forceinline__ void philox_normal4(uint32_t c0, uint32_t c1, uint32_
 // Philox(key = seed ^ step_hi, counter = (col/4, global row, draw id, step_lo))[col%4], so a value depends only
 // on WHICH draw of WHICH global minibatch row of WHICH step it is -- not on how rows are grouped into
 // buffers or sharded over ranks.  desc[r] = {offset into arena (floats), width, draw id, global row};
-// one wave per row.
-__global__ __launch_bounds__(256) void fill_normal_rows_kernel(float* __restrict__ arena,
-                                                               const int4* __restrict__ desc, int n_rows,
-                                                               uint64_t seed, const int32_t* ctr_dev, dv_wait park) {
+// one wave per row.  (dv_fill_normal_rows)
+// KEEPS: the noise arena of a step with hidden-layer dropout (dv_fill_noise_rows): rows [0, n_normal) of the table are those
+// N(0,1) rows (same calls, same values); rows [n_normal, n_rows) are KEEP rows -- element (row, col) is 1.0f where word
+// col % 4 of the same Philox block (counter and key laid out as for the normals) is < keep_thr, else 0.0f: an integer
+// compare, no float uniform.  The row kind is wave-uniform.
+template <bool KEEPS>
+__global__ __launch_bounds__(256) void fill_rows_kernel(float* __restrict__ arena, const int4* __restrict__ desc,
+                                                        int n_rows, uint64_t seed, const int32_t* ctr_dev,
+                                                        dv_wait park) {
     park_block(park);         // (the counter below is read behind the wait: its advance is part of what is waited for)
+    int n_normal = n_rows;
+    uint32_t keep_thr = 0;
+    if (KEEPS) {
+        // the trailer row behind the table: {number of keep rows at the table's END, keep_thr's bits, 0, 0} -- counted from
+        // the end, so that a caller may hand over the table from any of its rows on
+        const int4 tr = desc[n_rows];
+        // (device data the host cannot check: a count outside [0, n_rows] is clamped, never an index outside the table)
+        n_normal = n_rows - (tr.x < 0 ? 0 : tr.x > n_rows ? n_rows : tr.x);
+        keep_thr = (uint32_t)tr.y;
+    }
     uint32_t step_lo = 0, step_hi = 0;
     if (ctr_dev) {
         step_lo = (uint32_t)ctr_dev[0];
@@ -444,65 +447,12 @@ __global__ __launch_bounds__(256) void fill_normal_rows_kernel(float* __restrict
         float* out = arena + d.x;
         const int w = d.y, w4 = (w + 3) >> 2;
         const bool al = ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-        for (int c = lane; c < w4; c += 64) {
-            float z[4];
-            philox_normal4((uint32_t)c, (uint32_t)d.w, (uint32_t)d.z, step_lo, k0, k1, z);
-            const int o = c << 2;
-            if (al && o + 4 <= w) {
-                *reinterpret_cast<float4*>(out + o) = make_float4(z[0], z[1], z[2], z[3]);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (o + e < w) out[o + e] = z[e];
-            }
-        }
-    }
-}
-
-// 10 rounds of Philox4x32 in place: the four output words of counter (c0..c3) under key (k0, k1)
-__device__ __forceinline__ void philox_words4(uint32_t& c0, uint32_t& c1, uint32_t& c2, uint32_t& c3, uint32_t k0,
-                                              uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(c0, c1, c2, c3, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-
-// The noise arena of a step with hidden-layer dropout: rows [0, n_normal) of the table are the N(0,1) rows of
-// fill_normal_rows_kernel (same calls, same values); rows [n_normal, n_rows) are KEEP rows -- element (row, col) is 1.0f
-// where word col % 4 of the same Philox block (counter and key laid out as for the normals) is < keep_thr, else 0.0f:
-// an integer compare, no float uniform.  One wave per row, the row kind is wave-uniform.  (dv_fill_noise_rows)
-__global__ __launch_bounds__(256) void fill_noise_rows_kernel(float* __restrict__ arena, const int4* __restrict__ desc,
-                                                              int n_rows, uint64_t seed, const int32_t* ctr_dev,
-                                                              dv_wait park) {
-    park_block(park);         // (the counter below is read behind the wait, as in fill_normal_rows_kernel)
-    // the trailer row behind the table: {number of keep rows at the table's END, keep_thr's bits, 0, 0} -- counted from the
-    // end, so that a caller may hand over the table from any of its rows on
-    const int4 tr = desc[n_rows];
-    // (device data the host cannot check: a count outside [0, n_rows] is clamped, never an index outside the table)
-    const int n_normal = n_rows - (tr.x < 0 ? 0 : tr.x > n_rows ? n_rows : tr.x);
-    const uint32_t keep_thr = (uint32_t)tr.y;
-    uint32_t step_lo = 0, step_hi = 0;
-    if (ctr_dev) {
-        step_lo = (uint32_t)ctr_dev[0];
-        step_hi = (uint32_t)ctr_dev[1];
-    }
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32) ^ step_hi;
-    const int lane = threadIdx.x & 63;
-    const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), nwave = gridDim.x * (blockDim.x >> 6);
-    for (int r = wave; r < n_rows; r += nwave) {
-        const int4 d = desc[r];
-        float* out = arena + d.x;
-        const int w = d.y, w4 = (w + 3) >> 2;
-        const bool al = ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
-        const bool keep_row = r >= n_normal;
+        const bool keep_row = KEEPS && r >= n_normal;
         for (int c = lane; c < w4; c += 64) {
             float z[4];
             if (keep_row) {
                 uint32_t c0 = (uint32_t)c, c1 = (uint32_t)d.w, c2 = (uint32_t)d.z, c3 = step_lo;
-                philox_words4(c0, c1, c2, c3, k0, k1);
+                philox_block(c0, c1, c2, c3, k0, k1);
                 z[0] = c0 < keep_thr ? 1.f : 0.f;
                 z[1] = c1 < keep_thr ? 1.f : 0.f;
                 z[2] = c2 < keep_thr ? 1.f : 0.f;
@@ -529,19 +479,8 @@ __global__ __launch_bounds__(256) void fill_normal_kernel(float* __restrict__ ou
     const int64_t n4 = (n + 3) >> 2;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
         const uint64_t ctr = base + (uint64_t)i;
-        uint32_t c0 = (uint32_t)ctr, c1 = (uint32_t)(ctr >> 32), c2 = 0u, c3 = 0u;
-        uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-        for (int r = 0; r < 10; ++r) {
-            philox_round(c0, c1, c2, c3, k0, k1);
-            k0 += 0x9E3779B9u;
-            k1 += 0xBB67AE85u;
-        }
-        const float r0 = sqrtf(-2.f * logf(u01(c0))), r1 = sqrtf(-2.f * logf(u01(c2)));
-        float s0, co0, s1, co1;
-        sincosf(6.283185307179586f * u01(c1), &s0, &co0);
-        sincosf(6.283185307179586f * u01(c3), &s1, &co1);
-        const float z[4] = {r0 * co0, r0 * s0, r1 * co1, r1 * s1};
+        float z[4];
+        philox_normal4((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), z);
         const int64_t o = i << 2;
 #pragma unroll
         for (int e = 0; e < 4; ++e)
@@ -760,7 +699,7 @@ __global__ void flag_publish_kernel(int32_t* flag, const int32_t* ctr, int add) 
 __global__ void flag_wait_kernel(int32_t* flag, const int32_t* ctr, int add, int32_t* err, int max_spins, dv_publish pub) {
     if (threadIdx.x != 0) return;
     // (pub: published on entry, like dv_flag_publish -- everything before this launch in its stream is complete)
-    if (pub.flag != nullptr) __hip_atomic_store(pub.flag, pub.ctr[0] + pub.add, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    publish_block0(pub);
     const int want = ctr[0] + add;
     const long long t0 = wall_clock64();
     int n = 0;
@@ -783,8 +722,8 @@ extern "C" int dv_flag_publish(int32_t* flag, const int32_t* ctr, int32_t add, d
 extern "C" int dv_flag_wait(int32_t* flag, const int32_t* ctr, int32_t add, int32_t* err, int32_t max_spins,
                             const dv_publish* pub_in, dv_stream_t stream) {
     DV_REQUIRE(flag && ctr && err && max_spins > 0);
-    const dv_publish pub = pub_in ? *pub_in : dv_publish{nullptr, nullptr, 0};
-    DV_REQUIRE(pub.flag == nullptr || pub.ctr != nullptr);
+    dv_publish pub;
+    if (int rc = take_publish(pub_in, &pub)) return rc;
     hipLaunchKernelGGL(flag_wait_kernel, dim3(1), dim3(64), 0, ST(stream), flag, ctr, add, err, max_spins, pub);
     DV_RETURN_LAUNCH();
 }
@@ -798,16 +737,17 @@ extern "C" int dv_counter_add(int32_t* counter_lo_hi, int32_t n_words, int64_t i
 extern "C" int dv_counters_add2(int32_t* c1, int32_t n1, int64_t inc1, int32_t* c2, int32_t n2, int64_t inc2,
                                 const dv_publish* pub_in, dv_stream_t stream) {
     DV_REQUIRE(c1 && c2 && (n1 == 1 || n1 == 2) && (n2 == 1 || n2 == 2));
-    dv_publish pub = pub_in ? *pub_in : dv_publish{nullptr, nullptr, 0};
-    DV_REQUIRE(pub.flag == nullptr || pub.ctr != nullptr);
+    dv_publish pub;
+    if (int rc = take_publish(pub_in, &pub)) return rc;
     hipLaunchKernelGGL(counters_add2_kernel, dim3(1), dim3(64), 0, ST(stream), c1, n1, inc1, c2, n2, inc2, pub);
     DV_RETURN_LAUNCH();
 }
 
 // the two row-keyed fills (dv_fill_noise_rows: the table's trailer sits at row n_rows): the park's validation, the grid -- one
 // wave per row, four rows per workgroup -- and the launch
-static int fill_rows_launch(decltype(&fill_normal_rows_kernel) kernel, float* arena, const int32_t* desc, int32_t n_rows,
-                            uint64_t seed, const int32_t* ctr_dev, const dv_wait* park_in, dv_stream_t stream) {
+template <bool KEEPS>
+static int fill_rows_launch(float* arena, const int32_t* desc, int32_t n_rows, uint64_t seed, const int32_t* ctr_dev,
+                            const dv_wait* park_in, dv_stream_t stream) {
     DV_REQUIRE(n_rows >= 0);
     dv_wait park = park_in ? *park_in : dv_wait{nullptr, nullptr, 0, 0, nullptr};
     DV_REQUIRE(park.flag == nullptr || (park.ctr && park.err && park.max_spins > 0));
@@ -816,19 +756,19 @@ static int fill_rows_launch(decltype(&fill_normal_rows_kernel) kernel, float* ar
     int blocks = (n_rows + 3) / 4;
     if (blocks > 4096) blocks = 4096;
     if (park.flag != nullptr && blocks > 512) blocks = 512;      // a parked grid stays well below the chip's resident capacity
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(256), 0, ST(stream), arena, reinterpret_cast<const int4*>(desc),
-                       n_rows, seed, ctr_dev, park);
+    hipLaunchKernelGGL(fill_rows_kernel<KEEPS>, dim3((unsigned)blocks), dim3(256), 0, ST(stream), arena,
+                       reinterpret_cast<const int4*>(desc), n_rows, seed, ctr_dev, park);
     DV_RETURN_LAUNCH();
 }
 
 extern "C" int dv_fill_normal_rows(float* arena, const int32_t* desc, int32_t n_rows, uint64_t seed,
                                    const int32_t* ctr_dev, const dv_wait* park, dv_stream_t stream) {
-    return fill_rows_launch(fill_normal_rows_kernel, arena, desc, n_rows, seed, ctr_dev, park, stream);
+    return fill_rows_launch<false>(arena, desc, n_rows, seed, ctr_dev, park, stream);
 }
 
 extern "C" int dv_fill_noise_rows(float* arena, const int32_t* table, int32_t n_rows, uint64_t seed,
                                   const int32_t* ctr_dev, const dv_wait* park, dv_stream_t stream) {
-    return fill_rows_launch(fill_noise_rows_kernel, arena, table, n_rows, seed, ctr_dev, park, stream);
+    return fill_rows_launch<true>(arena, table, n_rows, seed, ctr_dev, park, stream);
 }
 
 extern "C" int dv_fill_normal(float* out, int64_t n, uint64_t seed, const int32_t* ctr_dev, dv_stream_t stream) {

@@ -160,17 +160,28 @@ typedef dv_bump CounterBump;
 
 __device__ __forceinline__ void bump_counters(const CounterBump& bump) {
     for (int t = 0; t < 2; ++t) {
-        int32_t* c = bump.c[t];
-        if (c == nullptr) continue;
-        if (bump.n[t] == 1) {
-            c[0] = (int32_t)(c[0] + bump.inc[t]);
-        } else {
-            uint64_t v = ((uint64_t)(uint32_t)c[1] << 32) | (uint32_t)c[0];
-            v += (uint64_t)bump.inc[t];
-            c[0] = (int32_t)(uint32_t)v;
-            c[1] = (int32_t)(uint32_t)(v >> 32);
-        }
+        if (bump.c[t] != nullptr) counter_add_words(bump.c[t], bump.n[t], bump.inc[t]);
     }
+}
+
+// ---- formulas shared by the launches below: ONE definition each, whichever kernel a piece of row arithmetic was folded into
+// d max(raw, kl_min) / d raw under coefficient c: c above the free-bits floor, 0 below, c/2 on a tie (torch.max)
+__device__ __forceinline__ float free_bits_gate(float c, float rv, float kl_min) {
+    return c * (rv > kl_min ? 1.f : (rv == kl_min ? 0.5f : 0.f));
+}
+
+// d/d(mu_q, logvar_q, mu_p, logvar_p) of one element's kl_term (times -1/2) in log-variance form
+struct KlGrad {
+    float gmq, gsq, gmp, gsp;
+};
+__device__ __forceinline__ KlGrad kl_grad_logvar(float mq, float sq, float mp, float sp) {
+    const float dm = mq - mp, ivp = expf(-sp), vq = expf(sq);
+    KlGrad g;
+    g.gmq = dm * ivp;
+    g.gsq = -0.5f * (1.f - vq * ivp);
+    g.gmp = -g.gmq;
+    g.gsp = -0.5f * (-1.f + (dm * dm + vq) * ivp);
+    return g;
 }
 
 __global__ void reparam_bwd_seg_kernel(const float* __restrict__ dz, int64_t ldz, const float* __restrict__ eps,
@@ -208,8 +219,7 @@ __global__ void reparam_bwd_seg_kernel(const float* __restrict__ dz, int64_t ldz
         float vm = (beta != 0.f ? beta * *pm : 0.f) + a;
         float vs = (beta != 0.f ? beta * *ps : 0.f) + b;
         if (pk.coef != nullptr) {       // + d/d(mu, logvar) of coef * max(KL(q_i || N(0,I)), kl_min): what dv_kl_rows_bwd(beta = 1) added
-            const float rv = pk.raw[i];
-            const float c = pk.coef[i] * (rv > pk.kl_min ? 1.f : (rv == pk.kl_min ? 0.5f : 0.f));
+            const float c = free_bits_gate(pk.coef[i], pk.raw[i], pk.kl_min);
             const float mq = pk.mu[(int64_t)i * pk.ld + d], vq = expf(sd[(int64_t)i * ldq + d]);
             vm += c * (mq * 1.f);
             vs += c * (-0.5f * (1.f - vq * 1.f));
@@ -286,19 +296,17 @@ __device__ __forceinline__ void z2f_elem(const Z2FArgs& a, int64_t r, int d, boo
                                          const Z2FElem& e, float& gq_mu, float& gq_lv) {
     float dmu = e.g, dlv = e.g * e.eps * 0.5f * expf(0.5f * e.lp);
     if (pair) {
-        const float dm = mq - e.mp, ivp = expf(-e.lp), vq = expf(lq);
+        // (the means' terms keep their own association, (c dm) ivp: kl_grad_logvar's c (dm ivp) rounds differently)
+        const float dm = mq - e.mp, ivp = expf(-e.lp);
+        const KlGrad k = kl_grad_logvar(mq, lq, e.mp, e.lp);
         gq_mu += c * dm * ivp;
-        gq_lv += c * (-0.5f * (1.f - vq * ivp));
+        gq_lv += c * k.gsq;
         dmu += -c * dm * ivp;
-        dlv += c * (-0.5f * (-1.f + (dm * dm + vq) * ivp));
+        dlv += c * k.gsp;
     }
     a.dp2[r * a.ld_dp2 + d] = dmu;
     a.dp2[r * a.ld_dp2 + a.Z + d] = dlv;
     a.dz1[r * a.ld_dz1 + d] = e.z1 + (dmu + e.add);
-}
-
-__device__ __forceinline__ float z2f_gate(float cf, float rv, float kl_min) {
-    return cf * (rv > kl_min ? 1.f : (rv == kl_min ? 0.5f : 0.f));
 }
 
 // a row's state across its samples (Z <= 128: two dims per lane), and two samples' operands in registers
@@ -320,7 +328,7 @@ __device__ __forceinline__ void z2f_row_begin(const Z2FArgs& a, int i, int lane,
     w.prior = w.pair && a.dq2 && a.prior_coef != nullptr;
     w.cpr = 0.f;
     if (w.prior)      // the prior term of q(z2|x2) row jp (what dv_kl_rows_bwd(beta = 1) added)
-        w.cpr = z2f_gate(a.prior_coef[w.jp], a.prior_raw[w.jp], a.kl_min);
+        w.cpr = free_bits_gate(a.prior_coef[w.jp], a.prior_raw[w.jp], a.kl_min);
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
         const int d = lane + 64 * c;
@@ -382,7 +390,7 @@ __device__ __forceinline__ void z2f_pair_finish(const Z2FArgs& a, Z2FRow& w, int
     for (int u = 0; u < 2; ++u) {
         if (l0 + u >= a.L) break;
         const int64_t r = (int64_t)(l0 + u) * a.B + i;
-        const float cg = w.pair ? z2f_gate(g.cf[u], g.rv[u], a.kl_min) : 0.f;
+        const float cg = w.pair ? free_bits_gate(g.cf[u], g.rv[u], a.kl_min) : 0.f;
 #pragma unroll
         for (int c = 0; c < 2; ++c)
             if (lane + 64 * c < a.Z)
@@ -445,7 +453,7 @@ __global__ __launch_bounds__(256) void z2f_post_bwd_wide_kernel(Z2FArgs a, ParkA
         const bool pair = jp >= 0;
         const bool own_kl = pair && a.raw_out != nullptr;
         const bool prior = pair && a.dq2 && a.prior_coef != nullptr;
-        const float cpr = prior ? z2f_gate(a.prior_coef[jp], a.prior_raw[jp], a.kl_min) : 0.f;
+        const float cpr = prior ? free_bits_gate(a.prior_coef[jp], a.prior_raw[jp], a.kl_min) : 0.f;
         for (int l = 0; l < a.L; ++l) {
             const int64_t r = (int64_t)l * a.B + i, kr = pair ? (int64_t)l * a.Np + jp : -1;
             const int t0 = a.seg_src ? a.seg_ptr[r] : 0, t1 = a.seg_src ? a.seg_ptr[r + 1] : 0;
@@ -463,7 +471,7 @@ __global__ __launch_bounds__(256) void z2f_post_bwd_wide_kernel(Z2FArgs a, ParkA
             } else if (pair) {
                 rv = a.raw[kr];
             }
-            const float cg = pair ? z2f_gate(a.coef[kr], rv, a.kl_min) : 0.f;
+            const float cg = pair ? free_bits_gate(a.coef[kr], rv, a.kl_min) : 0.f;
             for (int d = lane; d < a.Z; d += 64) {
                 float mq = 0.f, lq = 0.f, gm = 0.f, gl = 0.f;
                 float* qm = nullptr;
@@ -507,6 +515,33 @@ struct KlArgs {
     int n, reps, Z, mode;
 };
 
+// one KL row: this lane's share of the sum of kl_term over the row's dims (operands gathered through qidx / pidx, or the
+// prior); zout != NULL: the reparameterised sample of q is written in the same pass
+__device__ __forceinline__ float kl_row_sum(const KlArgs& a, int r, int lane, const float* __restrict__ eps = nullptr,
+                                            int64_t lde = 0, float* __restrict__ zout = nullptr, int64_t ldz = 0) {
+    const int j = r % a.n;
+    const int64_t qi = a.qidx ? a.qidx[j] : j;
+    const int64_t pi = a.pidx ? a.pidx[r] : r;
+    float s = 0.f;
+    for (int d = lane; d < a.Z; d += 64) {
+        const float mq = a.mu_q[qi * a.ldq + d], sq = a.sd_q[qi * a.ldq + d];
+        const float mp = a.mu_p ? a.mu_p[pi * a.ldp + d] : a.prior_mu;
+        const float sp = a.mu_p ? a.sd_p[pi * a.ldp + d] : a.prior_sd;
+        s += kl_term(a.mode, mq, sq, mp, sp);
+        if (zout)
+            zout[(int64_t)r * ldz + d] =
+                mq + eps[(int64_t)r * lde + d] * (a.mode == DV_GAUSS_LOGVAR ? expf(0.5f * sq) : sq);
+    }
+    return s;
+}
+
+// ... and its value from the wave's sum (lane 0): raw = -sum / 2, stored where asked for, under the free-bits floor
+__device__ __forceinline__ float kl_row_finish(float sum, int free_bits, float kl_min, float* raw_out, int r) {
+    const float raw = -0.5f * sum;
+    if (raw_out) raw_out[r] = raw;
+    return free_bits ? fmaxf(raw, kl_min) : raw;
+}
+
 __global__ __launch_bounds__(256) void kl_rows_fwd_kernel(KlArgs a, int free_bits, float kl_min,
                                                           float* __restrict__ raw_out, float* __restrict__ out,
                                                           const float* __restrict__ add,
@@ -518,33 +553,15 @@ __global__ __launch_bounds__(256) void kl_rows_fwd_kernel(KlArgs a, int free_bit
     const int lane = threadIdx.x & 63;
     const int rows = a.n * a.reps;
     for (int r = blockIdx.x * 4 + (threadIdx.x >> 6); r < rows; r += gridDim.x * 4) {
-        const int j = r % a.n;
-        const int64_t qi = a.qidx ? a.qidx[j] : j;
-        const int64_t pi = a.pidx ? a.pidx[r] : r;
-        float s = 0.f, s2 = 0.f;
+        float s2 = 0.f;
         if (mu2)   // second term of the same row: KL(N(mu2, sd2) || N(prior_mu, prior_sd)), row-aligned
             for (int d = lane; d < Z2; d += 64)
                 s2 += kl_term(a.mode, mu2[(int64_t)r * ld2 + d], sd2[(int64_t)r * ld2 + d], a.prior_mu, a.prior_sd);
-        for (int d = lane; d < a.Z; d += 64) {
-            const float mq = a.mu_q[qi * a.ldq + d], sq = a.sd_q[qi * a.ldq + d];
-            const float mp = a.mu_p ? a.mu_p[pi * a.ldp + d] : a.prior_mu;
-            const float sp = a.mu_p ? a.sd_p[pi * a.ldp + d] : a.prior_sd;
-            s += kl_term(a.mode, mq, sq, mp, sp);
-            if (zout)   // fused reparameterised sample of q (same row pass)
-                zout[(int64_t)r * ldz + d] =
-                    mq + eps[(int64_t)r * lde + d] * (a.mode == DV_GAUSS_LOGVAR ? expf(0.5f * sq) : sq);
-        }
-        s = dv_wave_sum_all(s);
+        const float s = dv_wave_sum_all(kl_row_sum(a, r, lane, eps, lde, zout, ldz));
         if (mu2) s2 = dv_wave_sum_all(s2);
         if (lane == 0) {
-            const float raw = -0.5f * s;
-            if (raw_out) raw_out[r] = raw;
-            float v = (free_bits ? fmaxf(raw, kl_min) : raw) + (add ? add[r] : 0.f);
-            if (mu2) {
-                const float raw2 = -0.5f * s2;
-                if (raw2_out) raw2_out[r] = raw2;
-                v += free_bits ? fmaxf(raw2, kl_min) : raw2;
-            }
+            float v = kl_row_finish(s, free_bits, kl_min, raw_out, r) + (add ? add[r] : 0.f);
+            if (mu2) v += kl_row_finish(s2, free_bits, kl_min, raw2_out, r);
             out[r] = v;
         }
     }
@@ -571,22 +588,8 @@ __global__ __launch_bounds__(256) void kl_rows_fwd_pair_kernel(KlFwd sa, KlFwd s
     const int rows = a.n * a.reps;
     const int r = blk * 4 + (threadIdx.x >> 6);
     if (r >= rows) return;
-    const int j = r % a.n;
-    const int64_t qi = a.qidx ? a.qidx[j] : j;
-    const int64_t pi = a.pidx ? a.pidx[r] : r;
-    float sum = 0.f;
-    for (int d = lane; d < a.Z; d += 64) {
-        const float mq = a.mu_q[qi * a.ldq + d], sq = a.sd_q[qi * a.ldq + d];
-        const float mp = a.mu_p ? a.mu_p[pi * a.ldp + d] : a.prior_mu;
-        const float sp = a.mu_p ? a.sd_p[pi * a.ldp + d] : a.prior_sd;
-        sum += kl_term(a.mode, mq, sq, mp, sp);
-    }
-    sum = dv_wave_sum_all(sum);
-    if (lane == 0) {
-        const float raw = -0.5f * sum;
-        if (s.raw_out) s.raw_out[r] = raw;
-        s.out[r] = (s.free_bits ? fmaxf(raw, s.kl_min) : raw) + (s.add ? s.add[r] : 0.f);
-    }
+    const float sum = dv_wave_sum_all(kl_row_sum(a, r, lane));
+    if (lane == 0) s.out[r] = kl_row_finish(sum, s.free_bits, s.kl_min, s.raw_out, r) + (s.add ? s.add[r] : 0.f);
 }
 
 __global__ void kl_rows_bwd_kernel(KlArgs a, const float* __restrict__ coef, const float* __restrict__ raw,
@@ -602,29 +605,21 @@ __global__ void kl_rows_bwd_kernel(KlArgs a, const float* __restrict__ coef, con
         const int64_t qi = a.qidx ? a.qidx[j] : j;
         const int64_t pi = a.pidx ? a.pidx[r] : r;
         float c = coef[r];
-        if (free_bits) {   // d max(raw, kl_min)/d raw: 1 above, 0 below, 1/2 on a tie (torch.max)
-            const float rv = raw[r];
-            c *= rv > kl_min ? 1.f : (rv == kl_min ? 0.5f : 0.f);
-        }
+        if (free_bits) c = free_bits_gate(c, raw[r], kl_min);
         const float mq = a.mu_q[qi * a.ldq + d], sq = a.sd_q[qi * a.ldq + d];
         const float mp = a.mu_p ? a.mu_p[pi * a.ldp + d] : a.prior_mu;
         const float sp = a.mu_p ? a.sd_p[pi * a.ldp + d] : a.prior_sd;
-        const float dm = mq - mp;
-        float gmq, gsq, gmp, gsp;
+        KlGrad k;
         if (a.mode == DV_GAUSS_LOGVAR) {
-            const float ivp = expf(-sp), vq = expf(sq);
-            gmq = dm * ivp;
-            gsq = -0.5f * (1.f - vq * ivp);
-            gmp = -gmq;
-            gsp = -0.5f * (-1.f + (dm * dm + vq) * ivp);
+            k = kl_grad_logvar(mq, sq, mp, sp);
         } else {
-            const float vp = sp * sp;
-            gmq = dm / vp;
-            gsq = -1.f / sq + sq / vp;
-            gmp = -gmq;
-            gsp = 1.f / sp - (dm * dm + sq * sq) / (vp * sp);
+            const float dm = mq - mp, vp = sp * sp;
+            k.gmq = dm / vp;
+            k.gsq = -1.f / sq + sq / vp;
+            k.gmp = -k.gmq;
+            k.gsp = 1.f / sp - (dm * dm + sq * sq) / (vp * sp);
         }
-        float tq_mu = c * gmq, tq_sd = c * gsq;
+        float tq_mu = c * k.gmq, tq_sd = c * k.gsq;
         if (dz) {   // the sample drawn from q in the forward pass: z = mu + eps*std
             const float g = dz[(int64_t)r * ldz + d];
             tq_mu += g;
@@ -635,8 +630,8 @@ __global__ void kl_rows_bwd_kernel(KlArgs a, const float* __restrict__ coef, con
         dq_sd[oq] = (beta != 0.f ? beta * dq_sd[oq] : 0.f) + tq_sd;
         if (dp_mu) {
             const int64_t op = (int64_t)r * lddp + d;
-            dp_mu[op] = (beta != 0.f ? beta * dp_mu[op] : 0.f) + c * gmp;
-            dp_sd[op] = (beta != 0.f ? beta * dp_sd[op] : 0.f) + c * gsp;
+            dp_mu[op] = (beta != 0.f ? beta * dp_mu[op] : 0.f) + c * k.gmp;
+            dp_sd[op] = (beta != 0.f ? beta * dp_sd[op] : 0.f) + c * k.gsp;
         }
     }
 }
@@ -1065,6 +1060,28 @@ __global__ void nll_rows_bwd_kernel(const float* __restrict__ coef, const float*
 constexpr float kPMin = 1e-10f;
 constexpr float kPMax = 1.f - 1e-10f;   // == 1.0f in fp32, as in the reference's fp32 clamp
 
+// clamp(softmax) of one row from its logits a[0..Y) and their maximum mx
+__device__ __forceinline__ void softmax_clamp_row(const float* a, float mx, int Y, float* p) {
+    float den = 0.f;
+    for (int j = 0; j < Y; ++j) den += expf(a[j] - mx);
+    for (int j = 0; j < Y; ++j) p[j] = fminf(fmaxf(expf(a[j] - mx) / den, kPMin), kPMax);
+}
+
+// ... and its backward: d logits from (d probs, probs); the clamp passes the gradient only where the unclamped value lies
+// inside [1e-10, 1]
+__device__ __forceinline__ float softmax_clamp_bwd_dot(const float* g, const float* p, int Y) {
+    float dot = 0.f;
+    for (int j = 0; j < Y; ++j) dot += (p[j] > kPMin ? g[j] : 0.f) * p[j];
+    return dot;
+}
+__device__ __forceinline__ float softmax_clamp_bwd_elem(const float* g, const float* p, int j, float dot) {
+    return p[j] * ((p[j] > kPMin ? g[j] : 0.f) - dot);
+}
+__device__ __forceinline__ void softmax_clamp_bwd_row(const float* g, const float* p, int Y, float* dl) {
+    const float dot = softmax_clamp_bwd_dot(g, p, Y);
+    for (int j = 0; j < Y; ++j) dl[j] = softmax_clamp_bwd_elem(g, p, j, dot);
+}
+
 __global__ void softmax_clamp_fwd_kernel(const float* __restrict__ logits, int64_t ldl, int M, int Y, int sigmoid1,
                                          float* __restrict__ probs, int64_t ldp) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1079,9 +1096,7 @@ __global__ void softmax_clamp_fwd_kernel(const float* __restrict__ logits, int64
     }
     float mx = a[0];
     for (int j = 1; j < Y; ++j) mx = fmaxf(mx, a[j]);
-    float den = 0.f;
-    for (int j = 0; j < Y; ++j) den += expf(a[j] - mx);
-    for (int j = 0; j < Y; ++j) p[j] = fminf(fmaxf(expf(a[j] - mx) / den, kPMin), kPMax);
+    softmax_clamp_row(a, mx, Y, p);
 }
 
 __global__ void softmax_clamp_bwd_kernel(const float* __restrict__ dprobs, int64_t lddp,
@@ -1092,19 +1107,14 @@ __global__ void softmax_clamp_bwd_kernel(const float* __restrict__ dprobs, int64
     const float* g = dprobs + (int64_t)r * lddp;
     const float* p = probs + (int64_t)r * ldp;
     float* o = dlogits + (int64_t)r * ldl;
-    // clamp passes the gradient only where the unclamped value lies inside [1e-10, 1]
-    if (sigmoid1) {
+    if (sigmoid1) {      // (the clamp's pass rule of softmax_clamp_bwd_row)
         const float s = p[1], g1 = p[1] > kPMin ? g[1] : 0.f, g0 = p[0] > kPMin ? g[0] : 0.f;
         const float v = (g1 - g0) * s * (1.f - s);
         o[0] = (beta != 0.f ? beta * o[0] : 0.f) + v;
         return;
     }
-    float dot = 0.f;
-    for (int j = 0; j < Y; ++j) dot += (p[j] > kPMin ? g[j] : 0.f) * p[j];
-    for (int j = 0; j < Y; ++j) {
-        const float v = p[j] * ((p[j] > kPMin ? g[j] : 0.f) - dot);
-        o[j] = (beta != 0.f ? beta * o[j] : 0.f) + v;
-    }
+    const float dot = softmax_clamp_bwd_dot(g, p, Y);
+    for (int j = 0; j < Y; ++j) o[j] = (beta != 0.f ? beta * o[j] : 0.f) + softmax_clamp_bwd_elem(g, p, j, dot);
 }
 
 __global__ void cat_terms_fwd_kernel(const float* __restrict__ probs, int64_t ldp, int M, int Y,
@@ -1154,20 +1164,26 @@ __global__ void cat_terms_bwd_kernel(const float* __restrict__ probs, int64_t ld
 // >90 % padding, so one wavefront per row does the N dot products, the softmax and the clamp.
 constexpr int kMaxSmallN = 8;
 
-// y-marginalisation of one row right behind its class probabilities (dv_smalln_linear_fwd with a dv_ymarg argument:
-// the classifier head and the labeled / marginalised KLD assembly of src/DrVAE.py:503-534 in one launch); same
-// arithmetic as ymarg_fwdbwd_kernel below
+// y-marginalisation of one row from its class probabilities q (src/DrVAE.py:503-534): the labeled / marginalised KLD
+// assembly (FWD: yl, kld) and its backward (BWD: the fprop rows' coefficients cfp and the row of dqy).  The one definition
+// behind dv_ymarg_fwd / _bwd / _fwdbwd and the rider of the classifier head (dv_smalln_linear_fwd with a dv_ymarg).
+// A row with one fprop row is labeled; label <= -2 is a labeled row of a batch-independent ("universal") plan: all Y class
+// slots are materialised, the true class -2 - label is the one that counts (see dv_batch_masks).
 // (cfp_out != NULL: the coefficients written to y.cfp are also returned, slot by slot; dq_out != NULL: the row of y.dqy)
+template <bool FWD, bool BWD>
 __device__ __forceinline__ void ymarg_row(const dv_ymarg& y, int r, int Y, const float* q, float* cfp_out = nullptr,
                                           float* dq_out = nullptr) {
     const int f0 = y.fp_ptr[r], nf = y.fp_ptr[r + 1] - f0;
-    const float ck = y.c_kld[r];
-    float* dq = y.dqy + (int64_t)r * y.lddq;
+    const float ck = BWD ? y.c_kld[r] : 0.f;
+    float* dq = BWD ? y.dqy + (int64_t)r * y.lddq : nullptr;
     const int lab0 = y.label[r];
     if (nf == 1 || lab0 <= -2) {
         const int lab = nf == 1 ? lab0 : -2 - lab0;
-        y.yl[r] = logf(q[lab]);
-        y.kld[r] = y.klfp[nf == 1 ? f0 : f0 + lab];
+        if (FWD) {
+            y.yl[r] = logf(q[lab]);
+            y.kld[r] = y.klfp[nf == 1 ? f0 : f0 + lab];
+        }
+        if (!BWD) return;
         for (int j = 0; j < Y; ++j) {
             const float v = (j == lab) ? y.c_yl[r] / q[j] : 0.f;
             dq[j] = v;
@@ -1186,28 +1202,27 @@ __device__ __forceinline__ void ymarg_row(const dv_ymarg& y, int r, int Y, const
         float a = 0.f, b = 0.f;
         for (int j = 0; j < Y; ++j) {
             const float lp = y.log_prior_v ? y.log_prior_v[j] : y.log_prior, lq = logf(q[j]), kf = y.klfp[f0 + j];
-            a += q[j] * kf;
-            b += -q[j] * (lp - lq);
-            y.cfp[f0 + j] = ck * q[j];
-            if (cfp_out) cfp_out[j] = ck * q[j];
-            const float v = ck * (kf + lq - lp + 1.f);
-            dq[j] = v;
-            if (dq_out) dq_out[j] = v;
+            if (FWD) {
+                a += q[j] * kf;
+                b += -q[j] * (lp - lq);
+            }
+            if (BWD) {
+                y.cfp[f0 + j] = ck * q[j];
+                if (cfp_out) cfp_out[j] = ck * q[j];
+                const float v = ck * (kf + lq - lp + 1.f);
+                dq[j] = v;
+                if (dq_out) dq_out[j] = v;
+            }
         }
-        y.yl[r] = 0.f;
-        y.kld[r] = a + b;
+        if (FWD) {
+            y.yl[r] = 0.f;
+            y.kld[r] = a + b;
+        }
     }
 }
 
-// d logits of row r from (d probs, probs) through clamp + softmax, see softmax_clamp_bwd_kernel
-__device__ __forceinline__ void smalln_dlogits(const float* g, const float* p, int N, float* dl) {
-    float dot = 0.f;
-    for (int j = 0; j < N; ++j) dot += (p[j] > kPMin ? g[j] : 0.f) * p[j];
-    for (int j = 0; j < N; ++j) dl[j] = p[j] * ((p[j] > kPMin ? g[j] : 0.f) - dot);
-}
-
 // the classifier's data gradient of row r right behind its y-marginalisation (dv_smalln_linear_fwd with a dv_clf_dgrad
-// argument): lane 0 holds the row's d logits (smalln_dlogits of the dqy / probs it has just stored), the wave writes the
+// argument): lane 0 holds the row's d logits (softmax_clamp_bwd_row of the dqy / probs it has just stored), the wave writes the
 // destinations' columns with the arithmetic of smalln_bwd_data_kernel (no segment start)
 __device__ __forceinline__ void smalln_dgrad_row(const dv_clf_dgrad& g, int r, int N, const float* dl0,
                                                  const float* __restrict__ W, int64_t ldw, int lane) {
@@ -1225,6 +1240,56 @@ __device__ __forceinline__ void smalln_dgrad_row(const dv_clf_dgrad& g, int r, i
             o[c] = base + g.alpha[t] * s + g.alpha2[t] * s2;
         }
     }
+}
+
+// the pieces the two classifier-head kernels below share (their load schedules differ, their arithmetic does not)
+// one fprop row t from this lane's shares (s1, s3) of its two KL sums: raw1 / raw3 / klfp stored by lane 0; returns raw1,
+// the gate of the z1 term's backward
+__device__ __forceinline__ float fprop_kl_row(const dv_fprop_kl& kf, int t, float s1, float s3, int lane) {
+    s1 = dv_wave_sum_all(s1);
+    s3 = dv_wave_sum_all(s3);
+    const float raw1 = -0.5f * s1;
+    if (lane == 0) {
+        kf.raw1[t] = raw1;
+        kf.raw3[t] = -0.5f * s3;
+        kf.klfp[t] = fmaxf(raw1, kf.kl_min) + fmaxf(-0.5f * s3, kf.kl_min);
+    }
+    return raw1;
+}
+
+// lane 0 of row r behind the wave sums acc[0..N): bias, the logits' store, clamp(softmax) and its store, then the riders --
+// the y-marginalisation (cfp: acc is reused for the fprop rows' coefficients) and the row's d logits dl for the data gradient.
+// ALL: the launch is known to carry probs, a dv_ymarg and a dv_fprop_kl (smalln_fwd2_kernel's dispatch); else they are looked at
+template <bool ALL>
+__device__ __forceinline__ void smalln_row_tail(const float* bias, int r, int N, float* acc, float* logits, int64_t ldl,
+                                                float* probs, int64_t ldp, const dv_ymarg& ym, bool cfp, bool dgrad,
+                                                float* dl) {
+    float mx = -3.4e38f;
+    for (int j = 0; j < N; ++j) {
+        acc[j] += bias ? bias[j] : 0.f;
+        if (logits) logits[(int64_t)r * ldl + j] = acc[j];
+        mx = fmaxf(mx, acc[j]);
+    }
+    if (!ALL && !probs) return;
+    float q[kMaxSmallN];
+    softmax_clamp_row(acc, mx, N, q);
+    for (int j = 0; j < N; ++j) probs[(int64_t)r * ldp + j] = q[j];
+    if (!ALL && ym.fp_ptr == nullptr) return;
+    float dq[kMaxSmallN];
+    ymarg_row<true, true>(ym, r, N, q, (ALL || cfp) ? acc : nullptr, dgrad ? dq : nullptr);
+    if (dgrad) softmax_clamp_bwd_row(dq, q, N, dl);
+}
+
+// backward of fprop row t's z1 term, element d, under the gated coefficient c of the y-marginalisation: dv_kl_rows_bwd's values
+__device__ __forceinline__ void fprop_kl_bwd_elem(const dv_fprop_kl& kf, int t, int d, float c, float mq, float sq, float mp,
+                                                  float sp) {
+    const KlGrad k = kl_grad_logvar(mq, sq, mp, sp);
+    float* dq = kf.dq + (int64_t)t * kf.lddq;
+    float* dp = kf.dp + (int64_t)t * kf.lddp;
+    dq[d] = c * k.gmq;
+    dq[kf.Z1 + d] = c * k.gsq;
+    dp[d] = c * k.gmp;
+    dp[kf.Z1 + d] = c * k.gsp;
 }
 
 __global__ __launch_bounds__(256) void smalln_fwd_kernel(const float* __restrict__ a1, int64_t lda1, int K1,
@@ -1254,14 +1319,7 @@ __global__ __launch_bounds__(256) void smalln_fwd_kernel(const float* __restrict
             float s1 = 0.f, s3 = 0.f;
             for (int d = lane; d < kf.Z1; d += 64) s1 += kl_term(DV_GAUSS_LOGVAR, q[d], q[kf.Z1 + d], pp[d], pp[kf.Z1 + d]);
             for (int d = lane; d < kf.Z3; d += 64) s3 += kl_term(DV_GAUSS_LOGVAR, q3[d], q3[kf.Z3 + d], 0.f, 0.f);
-            s1 = dv_wave_sum_all(s1);
-            s3 = dv_wave_sum_all(s3);
-            raw1[u] = -0.5f * s1;
-            if (lane == 0) {
-                kf.raw1[t] = raw1[u];
-                kf.raw3[t] = -0.5f * s3;
-                kf.klfp[t] = fmaxf(raw1[u], kf.kl_min) + fmaxf(-0.5f * s3, kf.kl_min);
-            }
+            raw1[u] = fprop_kl_row(kf, t, s1, s3, lane);
         }
     }
     float acc[kMaxSmallN], dl[kMaxSmallN];
@@ -1275,28 +1333,7 @@ __global__ __launch_bounds__(256) void smalln_fwd_kernel(const float* __restrict
     }
 #pragma unroll
     for (int j = 0; j < kMaxSmallN; ++j) acc[j] = dv_wave_sum_all(acc[j]);
-    if (lane == 0) {
-        float mx = -3.4e38f;
-        for (int j = 0; j < N; ++j) {
-            acc[j] += bias ? bias[j] : 0.f;
-            if (logits) logits[(int64_t)r * ldl + j] = acc[j];
-            mx = fmaxf(mx, acc[j]);
-        }
-        if (probs) {
-            float den = 0.f;
-            for (int j = 0; j < N; ++j) den += expf(acc[j] - mx);
-            float q[kMaxSmallN];
-            for (int j = 0; j < N; ++j) {
-                q[j] = fminf(fmaxf(expf(acc[j] - mx) / den, kPMin), kPMax);
-                probs[(int64_t)r * ldp + j] = q[j];
-            }
-            if (ym.fp_ptr != nullptr) {
-                float dq[kMaxSmallN];
-                ymarg_row(ym, r, N, q, kf.mu_q != nullptr ? acc : nullptr, dg.n ? dq : nullptr);   // (acc: reused for cfp)
-                if (dg.n) smalln_dlogits(dq, q, N, dl);
-            }
-        }
-    }
+    if (lane == 0) smalln_row_tail<false>(bias, r, N, acc, logits, ldl, probs, ldp, ym, kf.mu_q != nullptr, dg.n != 0, dl);
     if (dg.n) smalln_dgrad_row(dg, r, N, dl, W, ldw, lane);
     if (kf.mu_q != nullptr) {
         // backward of the z1 term with the coefficients of the y-marginalisation (lane 0 holds them): dv_kl_rows_bwd
@@ -1304,21 +1341,10 @@ __global__ __launch_bounds__(256) void smalln_fwd_kernel(const float* __restrict
         for (int u = 0; u < kMaxSmallN; ++u) {
             if (u >= nf) break;
             const int t = f0 + u;
-            float c = __shfl(acc[u], 0, 64);
-            c *= raw1[u] > kf.kl_min ? 1.f : (raw1[u] == kf.kl_min ? 0.5f : 0.f);
+            const float c = free_bits_gate(__shfl(acc[u], 0, 64), raw1[u], kf.kl_min);
             const float* q = kf.mu_q + (int64_t)kf.qidx[t] * kf.ldq;
             const float* pp = kf.mu_p + (int64_t)t * kf.ldp;
-            float* dq = kf.dq + (int64_t)t * kf.lddq;
-            float* dp = kf.dp + (int64_t)t * kf.lddp;
-            for (int d = lane; d < kf.Z1; d += 64) {
-                const float mq = q[d], sq = q[kf.Z1 + d], mp = pp[d], sp = pp[kf.Z1 + d];
-                const float dm = mq - mp, ivp = expf(-sp), vq = expf(sq);
-                const float gmq = dm * ivp, gsq = -0.5f * (1.f - vq * ivp);
-                dq[d] = c * gmq;
-                dq[kf.Z1 + d] = c * gsq;
-                dp[d] = c * -gmq;
-                dp[kf.Z1 + d] = c * (-0.5f * (-1.f + (dm * dm + vq) * ivp));
-            }
+            for (int d = lane; d < kf.Z1; d += 64) fprop_kl_bwd_elem(kf, t, d, c, q[d], q[kf.Z1 + d], pp[d], pp[kf.Z1 + d]);
         }
     }
 }
@@ -1397,15 +1423,7 @@ __global__ __launch_bounds__(256) void smalln_fwd2_kernel(const float* __restric
         for (int c = 0; c < 2; ++c) {
             if (lane + 64 * c < Z3) s3 += kl_term(DV_GAUSS_LOGVAR, tm[u][c], tl[u][c], 0.f, 0.f);
         }
-        s1 = dv_wave_sum_all(s1);
-        s3 = dv_wave_sum_all(s3);
-        raw1[u] = -0.5f * s1;
-        if (lane == 0) {
-            const int t = f0 + u;
-            kf.raw1[t] = raw1[u];
-            kf.raw3[t] = -0.5f * s3;
-            kf.klfp[t] = fmaxf(raw1[u], kf.kl_min) + fmaxf(-0.5f * s3, kf.kl_min);
-        }
+        raw1[u] = fprop_kl_row(kf, f0 + u, s1, s3, lane);
     }
     // ---- the classifier and the y-marginalisation
     float acc[kMaxSmallN], dl[kMaxSmallN];
@@ -1419,47 +1437,17 @@ __global__ __launch_bounds__(256) void smalln_fwd2_kernel(const float* __restric
         }
     acc[0] = dv_wave_sum_all(acc[0]);
     acc[1] = dv_wave_sum_all(acc[1]);
-    if (lane == 0) {
-        float mx = -3.4e38f;
-        for (int j = 0; j < N; ++j) {
-            acc[j] += bias ? bias[j] : 0.f;
-            if (logits) logits[(int64_t)r * ldl + j] = acc[j];
-            mx = fmaxf(mx, acc[j]);
-        }
-        float den = 0.f;
-        for (int j = 0; j < N; ++j) den += expf(acc[j] - mx);
-        float q[kMaxSmallN];
-        for (int j = 0; j < N; ++j) {
-            q[j] = fminf(fmaxf(expf(acc[j] - mx) / den, kPMin), kPMax);
-            probs[(int64_t)r * ldp + j] = q[j];
-        }
-        float dq[kMaxSmallN];
-        ymarg_row(ym, r, N, q, acc, dg.n ? dq : nullptr);         // (acc: reused for the fprop rows' coefficients)
-        if (dg.n) smalln_dlogits(dq, q, N, dl);
-    }
+    if (lane == 0) smalln_row_tail<true>(bias, r, N, acc, logits, ldl, probs, ldp, ym, true, dg.n != 0, dl);
     if (dg.n) smalln_dgrad_row(dg, r, N, dl, W, ldw, lane);
     // ---- backward of the z1 term with those coefficients (lane 0 holds them), from the registers
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         if (u >= nf) break;
         const int t = f0 + u;
-        float c = __shfl(acc[u], 0, 64);
-        c *= raw1[u] > kf.kl_min ? 1.f : (raw1[u] == kf.kl_min ? 0.5f : 0.f);
-        float* dq = kf.dq + (int64_t)t * kf.lddq;
-        float* dp = kf.dp + (int64_t)t * kf.lddp;
+        const float c = free_bits_gate(__shfl(acc[u], 0, 64), raw1[u], kf.kl_min);
 #pragma unroll
-        for (int cc = 0; cc < 2; ++cc) {
-            const int d = lane + 64 * cc;
-            if (d < Z1) {
-                const float mq = qm[u][cc], sq = ql[u][cc], mp = pm[u][cc], sp = pl[u][cc];
-                const float dm = mq - mp, ivp = expf(-sp), vq = expf(sq);
-                const float gmq = dm * ivp, gsq = -0.5f * (1.f - vq * ivp);
-                dq[d] = c * gmq;
-                dq[Z1 + d] = c * gsq;
-                dp[d] = c * -gmq;
-                dp[Z1 + d] = c * (-0.5f * (-1.f + (dm * dm + vq) * ivp));
-            }
-        }
+        for (int cc = 0; cc < 2; ++cc)
+            if (lane + 64 * cc < Z1) fprop_kl_bwd_elem(kf, t, lane + 64 * cc, c, qm[u][cc], ql[u][cc], pm[u][cc], pl[u][cc]);
     }
 }
 
@@ -1492,7 +1480,7 @@ __global__ void smalln_bwd_data_kernel(const float* __restrict__ dprobs, int64_t
         }
         float dl[kMaxSmallN];
         if (from_probs) {
-            smalln_dlogits(dprobs + (int64_t)r * lddp, probs + (int64_t)r * ldp, N, dl);
+            softmax_clamp_bwd_row(dprobs + (int64_t)r * lddp, probs + (int64_t)r * ldp, N, dl);
         } else {
             for (int j = 0; j < N; ++j) dl[j] = dprobs[(int64_t)r * lddp + j];
         }
@@ -1549,7 +1537,7 @@ __global__ __launch_bounds__(1024) void smalln_bwd_weight_kernel(const float* __
                 const int r = r0 + u * kSnRG, rc = r < m1 ? r : m1 - 1;
                 x[u] = r < m1 ? (k == KT ? 1.f : xs[(int64_t)rc * ldx]) : 0.f;
                 if (from_probs) {
-                    smalln_dlogits(dprobs + (int64_t)rc * lddp, probs + (int64_t)rc * ldp, N, dl[u]);
+                    softmax_clamp_bwd_row(dprobs + (int64_t)rc * lddp, probs + (int64_t)rc * ldp, N, dl[u]);
                 } else {
                     for (int j = 0; j < N; ++j) dl[u][j] = dprobs[(int64_t)rc * lddp + j];
                 }
@@ -1594,102 +1582,13 @@ __global__ __launch_bounds__(256) void smalln_wgrad_reduce_kernel(const float* _
 }
 
 // ------------------------------------------------------------- y-marginalisation
-__global__ void ymarg_fwd_kernel(const float* __restrict__ qy, int64_t ldq, const int32_t* __restrict__ label,
-                                 const int32_t* __restrict__ fp_ptr, const float* __restrict__ klfp,
-                                 float log_prior, const float* __restrict__ log_prior_v, int R, int Y,
-                                 float* __restrict__ yl, float* __restrict__ kld) {
+// one thread per row of ymarg_row: forward (dv_ymarg_fwd), backward (dv_ymarg_bwd), or both in one pass (dv_ymarg_fwdbwd: the
+// train step, whose coefficients are known); y carries the operands and outputs of the directions asked for
+template <bool FWD, bool BWD>
+__global__ void ymarg_kernel(const float* __restrict__ qy, int64_t ldq, dv_ymarg y, int R, int Y) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= R) return;
-    const float* q = qy + (int64_t)r * ldq;
-    const int f0 = fp_ptr[r], nf = fp_ptr[r + 1] - f0;
-    if (nf == 1) {
-        yl[r] = logf(q[label[r]]);
-        kld[r] = klfp[f0];
-    } else if (label[r] <= -2) {
-        // labeled row of a batch-independent ("universal") plan: all Y class slots are materialised, the
-        // true class c = -2 - label[r] is the one that counts (see dv_batch_masks)
-        const int lab = -2 - label[r];
-        yl[r] = logf(q[lab]);
-        kld[r] = klfp[f0 + lab];
-    } else {
-        float a = 0.f, b = 0.f;
-        for (int j = 0; j < Y; ++j) {
-            a += q[j] * klfp[f0 + j];
-            b += -q[j] * ((log_prior_v ? log_prior_v[j] : log_prior) - logf(q[j]));
-        }
-        yl[r] = 0.f;
-        kld[r] = a + b;
-    }
-}
-
-__global__ void ymarg_bwd_kernel(const float* __restrict__ qy, int64_t ldq, const int32_t* __restrict__ label,
-                                 const int32_t* __restrict__ fp_ptr, const float* __restrict__ klfp,
-                                 float log_prior, const float* __restrict__ log_prior_v,
-                                 const float* __restrict__ c_kld, const float* __restrict__ c_yl, int R, int Y,
-                                 float* __restrict__ cfp, float* __restrict__ dqy, int64_t lddq) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= R) return;
-    const float* q = qy + (int64_t)r * ldq;
-    float* dq = dqy + (int64_t)r * lddq;
-    const int f0 = fp_ptr[r], nf = fp_ptr[r + 1] - f0;
-    const float ck = c_kld[r];
-    if (nf == 1) {
-        const int lab = label[r];
-        for (int j = 0; j < Y; ++j) dq[j] = (j == lab) ? c_yl[r] / q[j] : 0.f;
-        cfp[f0] = ck;
-    } else if (label[r] <= -2) {
-        const int lab = -2 - label[r];
-        for (int j = 0; j < Y; ++j) {
-            dq[j] = (j == lab) ? c_yl[r] / q[j] : 0.f;
-            cfp[f0 + j] = (j == lab) ? ck : 0.f;
-        }
-    } else {
-        for (int j = 0; j < Y; ++j) {
-            cfp[f0 + j] = ck * q[j];
-            dq[j] = ck * (klfp[f0 + j] + logf(q[j]) - (log_prior_v ? log_prior_v[j] : log_prior) + 1.f);
-        }
-    }
-}
-
-// forward and backward of the y-marginalisation in one pass (train step: the coefficients are known)
-__global__ void ymarg_fwdbwd_kernel(const float* __restrict__ qy, int64_t ldq, const int32_t* __restrict__ label,
-                                    const int32_t* __restrict__ fp_ptr, const float* __restrict__ klfp,
-                                    float log_prior, const float* __restrict__ log_prior_v,
-                                    const float* __restrict__ c_kld, const float* __restrict__ c_yl, int R, int Y,
-                                    float* __restrict__ yl, float* __restrict__ kld, float* __restrict__ cfp,
-                                    float* __restrict__ dqy, int64_t lddq) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= R) return;
-    const float* q = qy + (int64_t)r * ldq;
-    float* dq = dqy + (int64_t)r * lddq;
-    const int f0 = fp_ptr[r], nf = fp_ptr[r + 1] - f0;
-    const float ck = c_kld[r];
-    if (nf == 1) {
-        const int lab = label[r];
-        yl[r] = logf(q[lab]);
-        kld[r] = klfp[f0];
-        for (int j = 0; j < Y; ++j) dq[j] = (j == lab) ? c_yl[r] / q[j] : 0.f;
-        cfp[f0] = ck;
-    } else if (label[r] <= -2) {
-        const int lab = -2 - label[r];
-        yl[r] = logf(q[lab]);
-        kld[r] = klfp[f0 + lab];
-        for (int j = 0; j < Y; ++j) {
-            dq[j] = (j == lab) ? c_yl[r] / q[j] : 0.f;
-            cfp[f0 + j] = (j == lab) ? ck : 0.f;
-        }
-    } else {
-        float a = 0.f, b = 0.f;
-        for (int j = 0; j < Y; ++j) {
-            const float lp = log_prior_v ? log_prior_v[j] : log_prior, lq = logf(q[j]), kf = klfp[f0 + j];
-            a += q[j] * kf;
-            b += -q[j] * (lp - lq);
-            cfp[f0 + j] = ck * q[j];
-            dq[j] = ck * (kf + lq - lp + 1.f);
-        }
-        yl[r] = 0.f;
-        kld[r] = a + b;
-    }
+    ymarg_row<FWD, BWD>(y, r, Y, qy + (int64_t)r * ldq);
 }
 
 // ------------------------------------------------ regression head (type_y = 'cont')
@@ -2853,6 +2752,18 @@ static bool bump_ok(const dv_bump* b) {
     return b == nullptr || ((!b->c[0] || b->n[0] == 1 || b->n[0] == 2) && (!b->c[1] || b->n[1] == 1 || b->n[1] == 2));
 }
 
+// an entry point's optional dv_wait, for its launch of `grid` workgroups (0: it launches nothing): *park = the wait, or none.
+// DV_ERR_ARG: a malformed wait, or one without a launch to ride on.  DV_ERR_UNSUPPORTED: every workgroup of a parked launch
+// polls -- such grids stay far below what the chip holds resident (256 CUs x 8 workgroups), or the chain that is to publish
+// may find no slot to run in
+static int take_park(const dv_wait* in, int64_t grid, ParkArgs* park) {
+    DV_REQUIRE(park_ok(in));
+    *park = in ? *in : ParkArgs{};
+    if (park->flag == nullptr) return DV_OK;
+    DV_REQUIRE(grid > 0);
+    return grid > DV_MAX_PARKED_GRID ? DV_ERR_UNSUPPORTED : DV_OK;
+}
+
 extern "C" int dv_colsum(const float* X, int64_t ldx, int32_t M, int32_t N, float* out, float beta,
                          dv_stream_t stream) {
     DV_REQUIRE(M >= 0 && N >= 0);
@@ -2924,15 +2835,15 @@ extern "C" int dv_reparam_bwd_seg(const float* dz, int64_t ldz, const float* eps
                                   const int32_t* ex_rows, float* dmu, float* dsd, int64_t lddq, float beta,
                                   const dv_bump* bump_in, const dv_seg_add* add, const dv_wait* park_in,
                                   const dv_prior_kl* prior, dv_stream_t stream) {
-    DV_REQUIRE(bump_ok(bump_in) && park_ok(park_in));
+    DV_REQUIRE(bump_ok(bump_in));
     DV_REQUIRE(prior == nullptr || prior->coef == nullptr || (prior->raw && prior->mu && mode == DV_GAUSS_LOGVAR));
     const dv_prior_kl pk = prior ? *prior : dv_prior_kl{};
     const CounterBump bump = bump_in ? *bump_in : CounterBump{};
-    const ParkArgs park = park_in ? *park_in : ParkArgs{};
     DV_REQUIRE(nq >= 0 && Z >= 0);
-    DV_REQUIRE(!(bump.c[0] || bump.c[1] || park.flag) || (nq > 0 && Z > 0));      // a bump / a wait needs a launch to ride on
+    DV_REQUIRE(!(bump.c[0] || bump.c[1]) || (nq > 0 && Z > 0));      // a bump (like a wait) needs a launch to ride on
     DV_REQUIRE(add == nullptr || add->n == 0 || (add->dz && add->n > 0));
-    if (park.flag != nullptr && grid_for((int64_t)nq * Z, 256) > DV_MAX_PARKED_GRID) return DV_ERR_UNSUPPORTED;
+    ParkArgs park;
+    if (int rc = take_park(park_in, nq > 0 && Z > 0 ? grid_for((int64_t)nq * Z, 256) : 0, &park)) return rc;
     if (nq == 0 || Z == 0) return DV_OK;
     DV_REQUIRE(dz && eps && sd && seg_ptr && seg_rows && dmu && dsd);
     DV_REQUIRE(extra == nullptr || (ex_ptr && ex_rows));
@@ -2943,14 +2854,11 @@ extern "C" int dv_reparam_bwd_seg(const float* dz, int64_t ldz, const float* eps
 }
 
 extern "C" int dv_z2f_post_bwd(const dv_z2f_desc* dsc, const dv_wait* park_in, dv_stream_t stream) {
-    DV_REQUIRE(dsc != nullptr && park_ok(park_in));
+    DV_REQUIRE(dsc != nullptr);
     const dv_z2f_desc& d = *dsc;
-    const ParkArgs park = park_in ? *park_in : ParkArgs{};
     DV_REQUIRE(d.L >= 0 && d.B >= 0 && d.Np >= 0 && d.Z >= 0);
-    DV_REQUIRE(park.flag == nullptr || (d.L > 0 && d.B > 0 && d.Z > 0));
-    // every workgroup of a parked launch polls: keep such grids far below what the chip holds resident
-    // (256 CUs x 8 workgroups), or the chain that is to publish may find no slot to run in
-    if (park.flag != nullptr && grid_for(d.B, 4) > DV_MAX_PARKED_GRID) return DV_ERR_UNSUPPORTED;
+    ParkArgs park;
+    if (int rc = take_park(park_in, d.L > 0 && d.B > 0 && d.Z > 0 ? grid_for(d.B, 4) : 0, &park)) return rc;
     if (d.L == 0 || d.B == 0 || d.Z == 0) return DV_OK;
     DV_REQUIRE(d.eps && d.p2 && d.dp2 && d.dz1);   // dz2f == NULL: nothing flows into the z2Fz1 samples from a classifier
     DV_REQUIRE((d.kl_out == nullptr) == (d.raw_out == nullptr));
@@ -2972,11 +2880,10 @@ extern "C" int dv_z2f_post_bwd(const dv_z2f_desc* dsc, const dv_wait* park_in, d
 extern "C" int dv_kl_rows_fwd(const dv_kl_rows_desc* dsc, const dv_wait* park_in, dv_stream_t stream) {
     DV_REQUIRE(dsc != nullptr);
     const dv_kl_rows_desc& d = *dsc;
-    DV_REQUIRE(d.n >= 0 && d.reps >= 0 && d.Z >= 0 && park_ok(park_in));
+    DV_REQUIRE(d.n >= 0 && d.reps >= 0 && d.Z >= 0);
     DV_REQUIRE((d.mu2 == nullptr) == (d.sd2 == nullptr) && (d.mu2 == nullptr || d.Z2 >= 0));
-    const ParkArgs park = park_in ? *park_in : ParkArgs{};
-    DV_REQUIRE(park.flag == nullptr || (d.n > 0 && d.reps > 0));
-    if (park.flag != nullptr && grid_for((int64_t)d.n * d.reps, 4) > DV_MAX_PARKED_GRID) return DV_ERR_UNSUPPORTED;
+    ParkArgs park;
+    if (int rc = take_park(park_in, d.n > 0 && d.reps > 0 ? grid_for((int64_t)d.n * d.reps, 4) : 0, &park)) return rc;
     if (d.n == 0 || d.reps == 0) return DV_OK;
     DV_REQUIRE(d.mu_q && d.sd_q && d.out);
     DV_REQUIRE((d.mu_p == nullptr) == (d.sd_p == nullptr));
@@ -3192,10 +3099,9 @@ extern "C" int dv_smalln_linear_fwd(const float* a1, int64_t lda1, int32_t K1, c
                                     float* logits, int64_t ldl, float* probs, int64_t ldp, const dv_ymarg* ymarg,
                                     const dv_wait* park_in, const dv_fprop_kl* kf_in, const dv_clf_dgrad* dg_in,
                                     dv_stream_t stream) {
-    DV_REQUIRE(M >= 0 && N >= 1 && N <= kMaxSmallN && K1 >= 0 && K2 >= 0 && park_ok(park_in));
-    const ParkArgs park = park_in ? *park_in : ParkArgs{};
-    DV_REQUIRE(park.flag == nullptr || M > 0);
-    if (park.flag != nullptr && (M + 3) / 4 > DV_MAX_PARKED_GRID) return DV_ERR_UNSUPPORTED;
+    DV_REQUIRE(M >= 0 && N >= 1 && N <= kMaxSmallN && K1 >= 0 && K2 >= 0);
+    ParkArgs park;
+    if (int rc = take_park(park_in, (M + 3) / 4, &park)) return rc;
     if (M == 0) return DV_OK;
     DV_REQUIRE(a1 && W && (a2 || K2 == 0) && (logits || probs));
     dv_ymarg ym{};
@@ -3270,8 +3176,8 @@ extern "C" int dv_smalln_linear_bwd_weight(const float* dprobs, int64_t lddp, co
                                            dv_stream_t stream) {
     DV_REQUIRE(M >= 0 && N >= 1 && N <= kMaxSmallN && K1 >= 0 && K2 >= 0);
     DV_REQUIRE(dprobs && a1 && dW && (a2 || K2 == 0) && ws_splits >= 0 && (ws || ws_splits <= 1));
-    dv_publish pub = pub_in ? *pub_in : dv_publish{nullptr, nullptr, 0};
-    DV_REQUIRE(pub.flag == nullptr || pub.ctr != nullptr);
+    dv_publish pub;
+    if (int rc = take_publish(pub_in, &pub)) return rc;
     const int col_blocks = (K1 + K2 + 1 + kSnCols - 1) / kSnCols;
     // rows split over workgroups only where a column block's workgroup would walk many rows (>= 1024) on a mostly idle
     // chip; the caller's workspace holds ws_splits x N x (K1 + K2 + 1) floats
@@ -3289,39 +3195,38 @@ extern "C" int dv_smalln_linear_bwd_weight(const float* dprobs, int64_t lddp, co
     DV_RETURN_LAUNCH();
 }
 
+template <bool FWD, bool BWD>
+static int ymarg_launch(const float* qy, int64_t ldq, const dv_ymarg& y, int32_t R, int32_t Y, dv_stream_t stream) {
+    DV_REQUIRE(R >= 0 && Y >= 1);
+    if (R == 0) return DV_OK;
+    DV_REQUIRE(qy && y.label && y.fp_ptr && y.klfp);
+    DV_REQUIRE(!FWD || (y.yl && y.kld));
+    DV_REQUIRE(!BWD || (y.c_kld && y.c_yl && y.cfp && y.dqy));
+    hipLaunchKernelGGL((ymarg_kernel<FWD, BWD>), dim3((R + 255) / 256), dim3(256), 0, ST(stream), qy, ldq, y, R, Y);
+    DV_RETURN_LAUNCH();
+}
+
 extern "C" int dv_ymarg_fwd(const float* qy, int64_t ldq, const int32_t* label, const int32_t* fp_ptr,
                             const float* klfp, float log_prior, const float* log_prior_v, int32_t R, int32_t Y,
                             float* yl, float* kld, dv_stream_t stream) {
-    DV_REQUIRE(R >= 0 && Y >= 1);
-    if (R == 0) return DV_OK;
-    DV_REQUIRE(qy && label && fp_ptr && klfp && yl && kld);
-    hipLaunchKernelGGL(ymarg_fwd_kernel, dim3((R + 255) / 256), dim3(256), 0, ST(stream), qy, ldq, label, fp_ptr,
-                       klfp, log_prior, log_prior_v, R, Y, yl, kld);
-    DV_RETURN_LAUNCH();
+    return ymarg_launch<true, false>(qy, ldq, dv_ymarg{label, fp_ptr, klfp, log_prior, log_prior_v, nullptr, nullptr, yl, kld,
+                                                       nullptr, nullptr, 0}, R, Y, stream);
 }
 
 extern "C" int dv_ymarg_fwdbwd(const float* qy, int64_t ldq, const int32_t* label, const int32_t* fp_ptr,
                                const float* klfp, float log_prior, const float* log_prior_v, const float* c_kld,
                                const float* c_yl, int32_t R, int32_t Y, float* yl, float* kld, float* cfp,
                                float* dqy, int64_t lddq, dv_stream_t stream) {
-    DV_REQUIRE(R >= 0 && Y >= 1);
-    if (R == 0) return DV_OK;
-    DV_REQUIRE(qy && label && fp_ptr && klfp && c_kld && c_yl && yl && kld && cfp && dqy);
-    hipLaunchKernelGGL(ymarg_fwdbwd_kernel, dim3((R + 255) / 256), dim3(256), 0, ST(stream), qy, ldq, label, fp_ptr,
-                       klfp, log_prior, log_prior_v, c_kld, c_yl, R, Y, yl, kld, cfp, dqy, lddq);
-    DV_RETURN_LAUNCH();
+    return ymarg_launch<true, true>(qy, ldq, dv_ymarg{label, fp_ptr, klfp, log_prior, log_prior_v, c_kld, c_yl, yl, kld, cfp,
+                                                      dqy, lddq}, R, Y, stream);
 }
 
 extern "C" int dv_ymarg_bwd(const float* qy, int64_t ldq, const int32_t* label, const int32_t* fp_ptr,
                             const float* klfp, float log_prior, const float* log_prior_v, const float* c_kld,
                             const float* c_yl, int32_t R, int32_t Y, float* cfp, float* dqy, int64_t lddq,
                             dv_stream_t stream) {
-    DV_REQUIRE(R >= 0 && Y >= 1);
-    if (R == 0) return DV_OK;
-    DV_REQUIRE(qy && label && fp_ptr && klfp && c_kld && c_yl && cfp && dqy);
-    hipLaunchKernelGGL(ymarg_bwd_kernel, dim3((R + 255) / 256), dim3(256), 0, ST(stream), qy, ldq, label, fp_ptr,
-                       klfp, log_prior, log_prior_v, c_kld, c_yl, R, Y, cfp, dqy, lddq);
-    DV_RETURN_LAUNCH();
+    return ymarg_launch<false, true>(qy, ldq, dv_ymarg{label, fp_ptr, klfp, log_prior, log_prior_v, c_kld, c_yl, nullptr,
+                                                       nullptr, cfp, dqy, lddq}, R, Y, stream);
 }
 
 extern "C" int dv_ycont_fwd(const float* mu, int64_t ldm, const float* ylab, const int32_t* has_y, const float* eps,
@@ -3369,10 +3274,10 @@ extern "C" int dv_mmd_rff_bwd(const float* th, int64_t ld, int32_t n, int32_t R,
 extern "C" int dv_rows_gather(const float* src, int64_t lds, const int32_t* idx, int32_t n, int32_t W,
                               const float* noise, int64_t ldn, float sigma, const int32_t* onehot_cls, int32_t Y,
                               float* out, int64_t ldo, const dv_wait* park_in, dv_stream_t stream) {
-    DV_REQUIRE(n >= 0 && W >= 0 && Y >= 0 && park_ok(park_in));
-    const ParkArgs park = park_in ? *park_in : ParkArgs{};
+    DV_REQUIRE(n >= 0 && W >= 0 && Y >= 0);
     const int64_t total = (int64_t)n * (W + (onehot_cls ? Y : 0));
-    DV_REQUIRE(park.flag == nullptr || total > 0);
+    ParkArgs park;
+    if (int rc = take_park(park_in, total > 0 ? grid_for(total, 256, 128) : 0, &park)) return rc;      // (128: see below)
     if (n == 0) return DV_OK;
     DV_REQUIRE(out && (src || W == 0));
     if (total == 0) return DV_OK;
@@ -3402,9 +3307,8 @@ static MaskArgs mask_args(const dv_batch_masks_desc& m, const int32_t* table, in
 
 extern "C" int dv_batch_feed(const dv_batch_feed_desc* dsc, const dv_batch_masks_desc* masks, const dv_wait* park_in,
                              dv_stream_t stream) {
-    DV_REQUIRE(dsc != nullptr && park_ok(park_in));
+    DV_REQUIRE(dsc != nullptr && park_ok(park_in));      // (a malformed wait is refused even where B == 0 launches nothing)
     const dv_batch_feed_desc& d = *dsc;
-    const ParkArgs park = park_in ? *park_in : ParkArgs{};
     const int B = d.B, Np = d.Np, L = d.L, Mf = d.Mf;
     DV_REQUIRE(B >= 0 && Np >= 0 && d.X >= 0 && d.n_batches >= 1 && L >= 1 && Mf >= 0 && d.Y >= 0 && d.Yc >= 0);
     DV_REQUIRE(!d.ylab || (d.yf && d.Yc >= 1));
@@ -3424,7 +3328,8 @@ extern "C" int dv_batch_feed(const dv_batch_feed_desc* dsc, const dv_batch_masks
         ma = mask_args(*masks, d.table, d.n_batches, d.ctr, d.base, B, L);
     }
     const int feed_blocks = row_blocks + lab_blocks;
-    if (park.flag != nullptr && feed_blocks + 1 > DV_MAX_PARKED_GRID) return DV_ERR_UNSUPPORTED;
+    ParkArgs park;
+    if (int rc = take_park(park_in, feed_blocks + 1, &park)) return rc;
     hipLaunchKernelGGL(batch_feed_kernel, dim3(feed_blocks + (masks ? 1 : 0)), dim3(256), 0, ST(stream), d.x1, d.ld1, d.x2,
                        d.ld2, d.y, d.table, d.n_batches, d.ctr, d.base, B, d.pair_rows, Np, d.X, d.noise, d.ldn, d.sigma,
                        d.xin, d.ldo, d.has_y, L, d.label_r, d.fp_i, d.fp_lab, d.fp_slot, Mf, d.fp_cls, d.onehot, d.ldh,
@@ -3445,11 +3350,9 @@ extern "C" int dv_batch_masks(const dv_batch_masks_desc* m, const int32_t* table
 extern "C" int dv_rows_segment_sum(const float* src, int64_t lds, const int32_t* seg_ptr, const int32_t* seg_rows,
                                    const float* w, int32_t n, int32_t W, const int32_t* dst_idx, float* dst,
                                    int64_t ldd, float beta, const dv_wait* park_in, dv_stream_t stream) {
-    DV_REQUIRE(park_ok(park_in));
-    const ParkArgs park = park_in ? *park_in : ParkArgs{};
     DV_REQUIRE(n >= 0 && W >= 0);
-    DV_REQUIRE(park.flag == nullptr || (n > 0 && W > 0));
-    if (park.flag != nullptr && grid_for((int64_t)n * W, 256) > DV_MAX_PARKED_GRID) return DV_ERR_UNSUPPORTED;
+    ParkArgs park;
+    if (int rc = take_park(park_in, n > 0 && W > 0 ? grid_for((int64_t)n * W, 256) : 0, &park)) return rc;
     if (n == 0 || W == 0) return DV_OK;
     DV_REQUIRE(src && dst);
     hipLaunchKernelGGL(rows_segment_sum_kernel, dim3(grid_for((int64_t)n * W, 256)), dim3(256), 0, ST(stream), src,
@@ -3642,8 +3545,9 @@ extern "C" int dv_loss_assemble_after(const dv_wait* wait, const dv_loss_term* t
                                       const int32_t* halt, int32_t n_halt, float* accum, dv_stream_t stream) {
     DV_REQUIRE(n_halt >= 0 && (halt || n_halt == 0));
     DV_REQUIRE(n_terms >= 0 && n_terms <= DV_MAX_LOSS_TERMS && (terms || n_terms == 0));
-    const dv_wait w = wait ? *wait : dv_wait{};
-    DV_REQUIRE(w_elbo && w_cmpl && loss && (!w.flag || (w.ctr && w.err && w.max_spins > 0)));     // flag == NULL: no wait
+    ParkArgs w;       // flag == NULL: no wait
+    if (int rc = take_park(wait, 1, &w)) return rc;
+    DV_REQUIRE(w_elbo && w_cmpl && loss);
     const CounterBump bump = bump_in ? *bump_in : CounterBump{};
     for (int i = 0; i < 2; ++i) DV_REQUIRE(!bump.c[i] || bump.n[i] == 1 || bump.n[i] == 2);
     LossTerms lt;

@@ -1346,7 +1346,7 @@ class FusedStep(StepSchedule):
         """(dual-graph schedule) what the side chain's graph runs behind its backward pass: publish its data gradients, the
         deferred leaf launches, the decoder heads' half of the optimiser sweep, the loss scalars, the NEXT step's noise, its
         own counters"""
-        cfg, p, t, sync, ctr = self.cfg, self.plan, self._tail, self.sync, self.side_ctr
+        p, t, sync, ctr = self.plan, self._tail, self.sync, self.side_ctr
         # DZ1B / DZ2F / every side gradient is final (the join): published on entry of the first leaf launch behind them
         # (the classifier's weight gradient) where there is one, else by a launch of its own
         if leaf:
@@ -1356,14 +1356,11 @@ class FusedStep(StepSchedule):
         else:
             K.flag_publish(*sync.pub('join', ctr))
         if t.side_loss:
-            a, hs = self.arena, t.hs
             # (entry of this launch = the deferred leaf launches, i.e. the classifier's weight gradient, are through:
             # flag ``clf_dw``, what the main chain's optimiser launch gates its classifier slice on)
             K.flag_wait(*sync.wait('rows', ctr), publish=sync.pub('clf_dw', ctr) if t.tail_gated else None)
             if t.side_adam:
-                K.adam_l2(a.param[hs:a.n_live], a.grad[hs:a.n_live], a.exp_avg[hs:a.n_live],
-                          a.exp_avg_sq[hs:a.n_live], self.side_t, lr=cfg.learning_rate,
-                          weight_decay=cfg.weight_decay, halt=self.sync_err, **self._lr_kw(), **self._opt_kw(hs, a.n_live))
+                self._sweep(t.hs, self.arena.n_live, step=self.side_t)
             if not t.fold_rows:
                 self._loss_scalars()   # a leaf too; the wait above also covers the main chain's NLL rows
         if t.noise_ahead:
@@ -1398,19 +1395,15 @@ class FusedStep(StepSchedule):
         if self.averaged:
             raise RuntimeError('the parameter arena holds the AVERAGED parameters (averaged_parameters()): no optimiser step '
                                'inside that context')
-        step = K.adamax_l2 if cfg.optim_alg == 'adamax' else K.adam_l2    # exp_avg_sq doubles as Adamax's exp_inf
         n = a.n_live                      # parameters without gradients sit behind it (untouched, like torch)
-        t, kw = (self._tail if self._rec == 'main' else None), {}
+        t, gate = (self._tail if self._rec == 'main' else None), None
         if self.clip_rec is not None:
             # clipped step: every gradient is final here (``_step_tail`` records no leaf work behind the join and no
             # side-chain half of the sweep for it), behind the exchange in every exchange form.  The norm over the whole live
             # slice -- the pad elements between parameters are zero, always (``ParamArena``) --, the record, the sweep
             assert not (t and (t.adam_gated or t.cap_fork or t.side_adam)), 'a clipped sweep has no gated form'
             K.clip_norm(a.grad[:n], self.clip_state, gscale=gscale)
-            step = K.adamax_l2_clip if cfg.optim_alg == 'adamax' else K.adam_l2_clip
-            step(a.param[:n], a.grad[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.clip_state,
-                 lr=cfg.learning_rate, weight_decay=cfg.weight_decay, gscale=gscale, halt=self.sync_err, **self._lr_kw(),
-                 **self._opt_kw(0, n))
+            self._sweep(0, n, gscale=gscale)
             return
         if t and t.adam_gated:   # dual-graph step: the classifier's dW may still be in flight on the side chain
             # (the optimiser's gate waits with counter + 0: the step counter is advanced before it)
@@ -1420,14 +1413,41 @@ class FusedStep(StepSchedule):
                 hi = max(lc.dW.storage_offset() + span(lc.dW), lc.db.storage_offset() + lc.db.numel()) - g0
             else:       # (no classifier, no leaf gradient in flight: the first workgroup's elements stand in for the slice --
                 lo, hi = 0, 4       # the gate is what orders the NEXT step behind the side chain's tail, see ``_step_tail``)
-            kw['gate'] = self.sync.gate('clf_dw' if t.tail_gated else 'tail', self.step_dev, lo, hi)
+            gate = self.sync.gate('clf_dw' if t.tail_gated else 'tail', self.step_dev, lo, hi)
             n = t.hs if t.side_adam else n      # ... and the side chain sweeps the rest (the decoder heads)
         if t and t.cap_fork:
             # (the sweep's first workgroup also parks on the side chain's "tail through" flag: what orders the NEXT step --
             # its first launch reads the noise the side chain has drawn -- behind it)
-            kw['gate'] = self.sync.gate('tail', self.step_dev, 0, 4)
-        step(a.param[:n], a.grad[:n], a.exp_avg[:n], a.exp_avg_sq[:n], self.step_dev, lr=cfg.learning_rate,
-             weight_decay=cfg.weight_decay, gscale=gscale, halt=self.sync_err, **kw, **self._lr_kw(), **self._opt_kw(0, n))
+            gate = self.sync.gate('tail', self.step_dev, 0, 4)
+        self._sweep(0, n, gscale=gscale, gate=gate)
+
+    def _sweep(self, lo, hi, *, gscale=None, gate=None, step=None):
+        """the optimiser sweep over the elements [lo, hi) of the arena -- every sweep of the step, the gated one, the capped
+        fork's and the side chain's half included: Adam or Adamax by ``cfg.optim_alg`` (exp_avg_sq doubles as Adamax's exp_inf),
+        the clipped form where the engine clips (it counts by the clip state's first word), else by ``step`` (default: the
+        step counter; the side chain has its own).  What is switched off is no argument at all, the call as it ever was:
+        the rate's annealing coefficient from the step's schedule record, AdamW's decoupled switch, the slice of the
+        parameter average that belongs to the elements, the gate, the gradient's scale (the side chain's half runs only in
+        steps without an exchange: it has none)"""
+        cfg, a = self.cfg, self.arena
+        name = ('adamax_l2' if cfg.optim_alg == 'adamax' else 'adam_l2') + ('_clip' if self.clip_rec is not None else '')
+        if self.clip_rec is not None:
+            step = self.clip_state
+        elif step is None:
+            step = self.step_dev
+        kw = {}
+        if gscale is not None:
+            kw['gscale'] = gscale
+        if gate is not None:
+            kw['gate'] = gate
+        if cfg.anneal_learning_rate:
+            kw['lr_scale'] = self.sched_rec[3:4]
+        if cfg.optim_alg == 'adamw':
+            kw['decoupled'] = True
+        if cfg.ema_decay is not None:
+            kw.update(avg=a.avg[lo:hi], avg_decay=cfg.ema_decay)
+        getattr(K, name)(a.param[lo:hi], a.grad[lo:hi], a.exp_avg[lo:hi], a.exp_avg_sq[lo:hi], step, lr=cfg.learning_rate,
+                         weight_decay=cfg.weight_decay, halt=self.sync_err, **kw)
 
     def _refuse_averaged(self, what):
         if self.averaged:
@@ -1447,22 +1467,6 @@ class FusedStep(StepSchedule):
             a.param.copy_(a.avg)
             a.avg.copy_(a.grad)
         self.averaged = not self.averaged
-
-    def _opt_kw(self, lo, hi):
-        """AdamW and the parameter average: every sweep of the step (gated, capped fork, the side chain's half) takes the
-        decoupled switch and the slice of the average that belongs to the elements [lo, hi) it sweeps; off: no argument at all,
-        the call as it ever was"""
-        kw = {}
-        if self.cfg.optim_alg == 'adamw':
-            kw['decoupled'] = True
-        if self.cfg.ema_decay is not None:
-            kw.update(avg=self.arena.avg[lo:hi], avg_decay=self.cfg.ema_decay)
-        return kw
-
-    def _lr_kw(self):
-        """learning-rate annealing: every sweep of the step (the side chain's half included) reads the rate's coefficient from
-        the step's schedule record; off: no argument at all, the call as it ever was"""
-        return dict(lr_scale=self.sched_rec[3:4]) if self.cfg.anneal_learning_rate else {}
 
     def clip_stats(self):
         """dict(norm, coef, skipped_last, n_skipped) of the last clipped optimiser step as python numbers: the gradient's

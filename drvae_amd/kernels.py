@@ -1142,32 +1142,34 @@ def _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale, p=None, decoup
     return h
 
 
-def adam_l2(p, g, m, v, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, gate=None,
-            halt=None, lr_scale=None, decoupled=False, avg=None, avg_decay=None):
-    """``gate`` = a ``Gate``: elements [lo, hi) wait for the flag (``dv_adam_l2_gated``);
+def _sweep(symbol, p, g, m, v, step_or_state, *, gate=None, halt=None, **hyper):
+    """one optimiser sweep through entry point ``symbol`` -- what the four public wrappers are: they differ in the symbol and in
+    whether the int32 tensor behind the moments is the step counter or a clip state (its first word is the step).
+    ``gate`` = a ``Gate``: elements [lo, hi) wait for the flag (the symbol's ``_gated`` form);
     ``halt``: the (err, ticks) pairs of the step's waits -- any error set: nothing is updated;
-    ``lr_scale``: a device scalar the rate is multiplied by (``_hyper``; every sweep below takes it);
-    ``decoupled``, ``avg``, ``avg_decay``: AdamW's decay and the parameter average (``_hyper``; Adamax takes the average only)"""
+    ``hyper``: ``_hyper``'s arguments -- ``lr_scale``: a device scalar the rate is multiplied by; ``decoupled``, ``avg``,
+    ``avg_decay``: AdamW's decay and the parameter average (Adamax takes the average only)"""
     assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
     hp, hn = _halt(halt)
-    h = _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale, p, decoupled, avg, avg_decay)
-    if gate is None:
-        _lib.check(_lib.load().dv_adam_l2(_f32(p), _f32(g), _f32(m), _f32(v), p.numel(), C.byref(h), _i32(step_dev), hp, hn,
-                                          _stream()), 'dv_adam_l2')
-    else:
-        gate = Gate(*gate)
-        _lib.check(_lib.load().dv_adam_l2_gated(_f32(p), _f32(g), _f32(m), _f32(v), p.numel(), C.byref(h), _i32(step_dev),
-                                                _wait(Wait(gate.flag, gate.ctr, gate.err, gate.add)), gate.lo, gate.hi, hp, hn,
-                                                _stream()), 'dv_adam_l2_gated')
+    h = _hyper(p=p, **hyper)
+    args = (_f32(p), _f32(g), _f32(m), _f32(v), p.numel(), C.byref(h), _i32(step_or_state))
+    if gate is not None:
+        gate, symbol = Gate(*gate), symbol + '_gated'
+        args += (_wait(Wait(gate.flag, gate.ctr, gate.err, gate.add)), gate.lo, gate.hi)
+    _lib.check(getattr(_lib.load(), symbol)(*args, hp, hn, _stream()), symbol)
+
+
+def adam_l2(p, g, m, v, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, gate=None,
+            halt=None, lr_scale=None, decoupled=False, avg=None, avg_decay=None):
+    """torch.optim.Adam with coupled L2 (AdamW: ``decoupled``) over the flat range; ``gate``: ``dv_adam_l2_gated`` (``_sweep``)"""
+    _sweep('dv_adam_l2', p, g, m, v, step_dev, gate=gate, halt=halt, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
+           weight_decay=weight_decay, gscale=gscale, lr_scale=lr_scale, decoupled=decoupled, avg=avg, avg_decay=avg_decay)
 
 
 def adamax_l2(p, g, m, u, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None,
               lr_scale=None, decoupled=False, avg=None, avg_decay=None):
-    assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and u.is_contiguous()
-    hp, hn = _halt(halt)
-    h = _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale, p, decoupled, avg, avg_decay)
-    _lib.check(_lib.load().dv_adamax_l2(_f32(p), _f32(g), _f32(m), _f32(u), p.numel(), C.byref(h), _i32(step_dev), hp, hn,
-                                        _stream()), 'dv_adamax_l2')
+    _sweep('dv_adamax_l2', p, g, m, u, step_dev, halt=halt, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
+           weight_decay=weight_decay, gscale=gscale, lr_scale=lr_scale, decoupled=decoupled, avg=avg, avg_decay=avg_decay)
 
 
 # gradient-norm clipping (``StepConfig.max_grad_norm``): ``dv_grad_norm_clip`` and the ``_clipped`` sweeps of include/drvae_hip.h.
@@ -1224,20 +1226,14 @@ def adam_l2_clip(p, g, m, v, state, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, wei
                  lr_scale=None, decoupled=False, avg=None, avg_decay=None):
     """``adam_l2`` reading the record of the clip state (whose first word is the step): skipped when the record says so, else
     the gradient scaled by fl32(gscale * coef) and t = step - n_skipped.  No gated form."""
-    assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and v.is_contiguous()
-    hp, hn = _halt(halt)
-    h = _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale, p, decoupled, avg, avg_decay)
-    _lib.check(_lib.load().dv_adam_l2_clipped(_f32(p), _f32(g), _f32(m), _f32(v), p.numel(), C.byref(h), _i32(state), hp, hn,
-                                              _stream()), 'dv_adam_l2_clipped')
+    _sweep('dv_adam_l2_clipped', p, g, m, v, state, halt=halt, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
+           weight_decay=weight_decay, gscale=gscale, lr_scale=lr_scale, decoupled=decoupled, avg=avg, avg_decay=avg_decay)
 
 
 def adamax_l2_clip(p, g, m, u, state, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None,
                    lr_scale=None, decoupled=False, avg=None, avg_decay=None):
-    assert p.is_contiguous() and g.is_contiguous() and m.is_contiguous() and u.is_contiguous()
-    hp, hn = _halt(halt)
-    h = _hyper(lr, beta1, beta2, eps, weight_decay, gscale, lr_scale, p, decoupled, avg, avg_decay)
-    _lib.check(_lib.load().dv_adamax_l2_clipped(_f32(p), _f32(g), _f32(m), _f32(u), p.numel(), C.byref(h), _i32(state), hp, hn,
-                                                _stream()), 'dv_adamax_l2_clipped')
+    _sweep('dv_adamax_l2_clipped', p, g, m, u, state, halt=halt, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
+           weight_decay=weight_decay, gscale=gscale, lr_scale=lr_scale, decoupled=decoupled, avg=avg, avg_decay=avg_decay)
 
 
 def flag_publish(flag, ctr, add=1):

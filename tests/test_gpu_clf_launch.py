@@ -144,7 +144,7 @@ def test_riders_left_out(K, dev, table, case):
 # ------------------------------------------------------------------ the softmax backward of the weight / data gradients
 @pytest.mark.parametrize('case', L.EDGE_CASES[2:], ids=[L.case_id(c) for c in L.EDGE_CASES[2:]])
 def test_smalln_backward_at_the_clamp(K, dev, case):
-    """smalln_dlogits inside dv_smalln_linear_bwd_data / _bwd_weight on stored probabilities on both sides of the 1e-10
+    """softmax_clamp_bwd_row inside dv_smalln_linear_bwd_data / _bwd_weight on stored probabilities on both sides of the 1e-10
     clamp, against float64 P * (g_masked - <g_masked, P>).  W = I: the data gradient IS d logits (a sum with one non-zero
     product is exact); the weight gradient is its product with the logit grid, a row sum over M"""
     M, Y = case['shape'][:2]

@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
 """Kernel sequence of ONE replayed whole-set evaluation from a rocprofv3 --kernel-trace CSV of tools/eval_bench.py:
 eval_timeline.py <..._kernel_trace.csv> [train|valid]  -- a pass starts at its Philox draw
-(fill_normal_rows_kernel)."""
+(fill_rows_kernel; fill_normal_rows_kernel in traces of older builds)."""
 import csv
 import sys
 
 rows = list(csv.DictReader(open(sys.argv[1])))
 rows.sort(key=lambda r: int(r['Start_Timestamp']))
 which = sys.argv[2] if len(sys.argv) > 2 else 'valid'
-starts = [i for i, r in enumerate(rows) if 'fill_normal_rows' in r['Kernel_Name']]
+starts = [i for i, r in enumerate(rows) if 'fill_rows_kernel' in r['Kernel_Name'] or 'fill_normal_rows' in r['Kernel_Name']]
 # tools/eval_bench.py: per dataset 2 eager passes (plan building, warm-up) + (2 + reps) replays, train set first
 half = len(starts) // 2
 k = half - 1 if which == 'train' else len(starts) - 2

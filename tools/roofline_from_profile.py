@@ -87,7 +87,7 @@ def main():
     ap.add_argument('prefix', help='e.g. profiles/r02_cfg2')
     ap.add_argument('--out', default=None)
     ap.add_argument('--commit', default=None, help='commit the profile was collected at (recorded in the JSON)')
-    ap.add_argument('--step-kernel', default='fill_normal_rows_kernel',
+    ap.add_argument('--step-kernel', default='fill_rows_kernel',
                     help='a kernel launched exactly once per train step (counts the profiled steps)')
     args = ap.parse_args()
     pre = args.prefix
