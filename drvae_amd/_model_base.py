@@ -74,10 +74,11 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         self.to(device)
 
     def _check_supported(self):
-        if self.type_rec not in ('diag_gaussian', 'binary', 'poisson'):
-            raise ValueError("type_rec must be 'diag_gaussian', 'binary' or 'poisson'")      # src/DrVAE.py:124-131
+        if self.type_rec not in ('diag_gaussian', 'binary', 'poisson', 'nb'):
+            raise ValueError("type_rec must be 'diag_gaussian', 'binary', 'poisson' or 'nb'")      # src/DrVAE.py:124-131
         # 'binary' / 'poisson' point at blk.BernoulliDecoder / blk.PoissonDecoder, which the reference's blocks.py
-        # does not define (its constructor raises AttributeError there): built here as labelled EXTENSIONS
+        # does not define (its constructor raises AttributeError there): built here as labelled EXTENSIONS; 'nb' (the
+        # negative binomial for overdispersed counts, blk.NegativeBinomialDecoder) is an extension the reference never names
         bad = []
         # use_s=True is an EXTENSION here: the reference crashes on it (torch.cat([z, s_raw]) of a float and an
         # integer tensor, src/DrVAE.py:438), so it is built from the evident intent -- one_hot(s) appended to the
@@ -137,7 +138,7 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
             setattr(self, 'encoder_z3' if self.kind == 'drvae' else 'encoder_z2', top)
             self.decoder_z1 = blk.DiagGaussianModule([top_z, self.dim_y], self.dim_h_de_z1, Z1, **hp)
         dec = {'diag_gaussian': blk.DiagGaussianSigmaModule, 'binary': blk.BernoulliDecoder,
-               'poisson': blk.PoissonDecoder}[self.type_rec]                 # src/DrVAE.py:124-129
+               'poisson': blk.PoissonDecoder, 'nb': blk.NegativeBinomialDecoder}[self.type_rec]      # src/DrVAE.py:124-129
         self.decoder_x = dec([Z1] + s_in, self.dim_h_de_x, self.dim_x, **hp)
 
     def _dropout_notes(self):
@@ -161,9 +162,9 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
             hidden['decoder_z1'] = self.dim_h_de_z1
         hidden['decoder_x'] = self.dim_h_de_x
         # (one head in the fused step: the classifier -- a regression head's log-variance is fixed, its layer is not in the
-        # step's chain (``FusedStep.L_clf``) -- and a Bernoulli / Poisson decoder)
+        # step's chain (``FusedStep.L_clf``) -- and a Bernoulli / Poisson decoder; the negative binomial has two)
         two_heads = [n for n, h in hidden.items() if len(h) and n != 'encoder_y' and not
-                     (n == 'decoder_x' and self.type_rec != 'diag_gaussian')]
+                     (n == 'decoder_x' and self.type_rec not in ('diag_gaussian', 'nb'))]
         undropped = [n for n, h in hidden.items() if not len(h)]
         warnings.warn('dropout_rate=%g in the fused train step differs from the block-level path in two labelled ways: '
                       'both heads share ONE keep mask in %s; no dropout at all (no hidden layer) in %s'

@@ -20,7 +20,8 @@ import torch
 N_LOSS = 8   # RECL KLD PERT YL MMD ELBO CMPL + 1 spare, parked in FRONT of the gradients
 
 _HEAD_PAIRS = (('encoder_mu.linear_mu', 'encoder_lv.linear_lv'),
-               ('encoder_mu.linear_mu', 'encoder_sg.linear_sg'))
+               ('encoder_mu.linear_mu', 'encoder_sg.linear_sg'),
+               ('decoder_m.linear_m', 'decoder_t.linear_t'))      # (the negative-binomial decoder's mean | theta)
 
 
 def _fusion_groups(names, frozen=()):

@@ -473,6 +473,59 @@ class PoissonDecoder(_SingleHeadDecoder):
         return torch.poisson(rate)
 
 
+class NegativeBinomialDecoder(nn.Module):
+    """EXTENSION (``type_rec='nb'``; no counterpart in the reference): the data decoder for overdispersed counts, a negative
+    binomial with mean ``mu`` and inverse dispersion ``theta`` (Var = mu + mu^2 / theta; theta -> inf is the Poisson decoder).
+    MLP trunk ``nnet`` + two Linear heads over it, like ``DiagGaussianSigmaModule``: inputs -> (mu, theta) with
+    ``mu = softplus(decoder_m.linear_m(h)) + 1e-6`` (the Poisson decoder's rate, same shift) and
+    ``theta = softplus(decoder_t.linear_t(h)) + 1e-3`` (the sigma head's activation and shift).
+
+        log p(x | mu, theta) = lgamma(x + theta) - lgamma(theta) - lgamma(x + 1)
+                               + theta log(theta / (theta + mu)) + x log(mu / (theta + mu))
+
+    The fused step forms these rows and both heads' gradients in ``dv_rec_nll_rows`` (kind ``DV_REC_NEGBIN``); the methods
+    here are the block-level path in torch: the two log ratios through ``log1p``, the lgamma pair subtracted in float64."""
+    MU_SHIFT, THETA_SHIFT = 1e-6, 1e-3
+
+    def __init__(self, input_dims, hidden_dims, reconstruction_dim, nonlin='softplus', weight_norm=False,
+                 batch_norm=False, dropout_rate=0., input_dropout_rates=None):
+        super().__init__()
+        self.nnet = MLP(input_dims=input_dims, hidden_dims=hidden_dims, nonlin=nonlin, weight_norm=weight_norm,
+                        batch_norm=batch_norm, dropout_rate=dropout_rate, input_dropout_rates=input_dropout_rates)
+        self.reconstruction_dim = reconstruction_dim
+        make = lyr.WeightNormLinear if weight_norm else nn.Linear
+        width = _trunk_width(input_dims, hidden_dims)
+        # (mean head first, then theta: the parameter-init RNG stream and the arena's head pair follow this order)
+        for head, lin in (('decoder_m', 'linear_m'), ('decoder_t', 'linear_t')):
+            mods = OrderedDict()
+            if dropout_rate > 0.:
+                mods['dropout'] = Dropout(p=dropout_rate)
+            mods[lin] = make(width, reconstruction_dim)
+            setattr(self, head, nn.Sequential(mods))
+
+    def _head_out(self, seq, lin, h, shift):
+        if hasattr(seq, 'dropout'):
+            h = [seq.dropout(h[0] if len(h) == 1 else torch.cat(h, 1))]
+        return _apply_linear(getattr(seq, lin), h, act='softplus', shift=shift)
+
+    def forward(self, inputs):
+        h = self.nnet.features(inputs)
+        return (self._head_out(self.decoder_m, 'linear_m', h, self.MU_SHIFT),
+                self._head_out(self.decoder_t, 'linear_t', h, self.THETA_SHIFT))
+
+    def logp_perx(self, x, mu, theta):
+        t64 = theta.double()
+        lg = (torch.lgamma(x.double() + t64) - torch.lgamma(t64)).to(theta.dtype)
+        return (lg - torch.lgamma(x + 1.) - theta * torch.log1p(mu / theta) - x * torch.log1p(theta / mu)).sum(1)
+
+    def logp(self, x, mu, theta):
+        return torch.sum(self.logp_perx(x, mu, theta))
+
+    def sample(self, mu, theta):
+        """Gamma-Poisson: rate ~ Gamma(shape = theta, mean = mu), x ~ Poisson(rate)"""
+        return torch.poisson(torch._standard_gamma(theta) * (mu / theta))
+
+
 class CategoricalDecoder(nn.Module):
     """inputs -> [clamped class probabilities] (a 1-element list), plus the categorical
     log-likelihood / KL / entropy helpers (src/blocks.py:419-486)."""

@@ -1023,6 +1023,111 @@ __global__ __launch_bounds__(256) void rec_nll_rows_kernel(int kind, float shift
     }
 }
 
+// Negative-binomial reconstruction rows (type_rec = 'nb': labelled extension, no counterpart in the reference): mean m > 0,
+// inverse dispersion t > 0 (Var = m + m^2 / t), count x >= 0.
+//   log p = [lgamma(x+t) - lgamma(t)] - lgamma(x+1) + t log(t/(t+m)) + x log(m/(t+m))
+//   d/dm  = x/m - (x+t)/(t+m) = (x - m) / (m (1 + m/t));   d/dt = [psi(x+t) - psi(t)] + log(t/(t+m)) + (m - x)/(t+m)
+// Every cancelling pair is formed as a difference, never as two large values subtracted:
+//   * the lgamma and digamma pairs: n = min(x, steps that lift t to >= 8) recurrence steps (log of the product of t + k,
+//     sum of 1 / (t + k): at most 8, and ALL of x when x is that small), then for the d = x - n steps left, from b = t + n >= 8
+//     to a = b + d, the difference of the asymptotic series with the leading logs combined:
+//       lgamma(a) - lgamma(b) = d log a + ((b - 1/2) log1p(d/b) - d) + (s(a) - s(b)),  s(z) = 1/12z - 1/360z^3 + 1/1260z^5
+//       psi(a) - psi(b)       = log1p(d/b) + d/(2ab) + d(a+b)/(12 a^2 b^2) + (q(a) - q(b)),  q(z) = 1/120z^4 - 1/252z^6
+//     (the series' next terms at z = 8: 3e-10 and 2e-10 absolute).  x = 0: n = d = 0, both pairs are exactly 0.
+//   * log(t/(t+m)) = -log1p(m/t) and log(m/(t+m)) = -log1p(t/m): exact in the Poisson limit (t log(t/(t+m)) -> -m) and
+//     in its mirror (t << m).
+// g_m / g_t: the gradients w.r.t. the heads' pre-activations (softplus slope from the stored outputs, as rec_term does).
+__device__ __forceinline__ float nb_term(float shift, float x, float m, float t, float& g_m, float& g_t) {
+    const float n8 = t < 8.f ? ceilf(8.f - t) : 0.f;
+    const float n = fminf(x, n8), d = x - n;
+    float prod = 1.f, rsum = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float tk = t + (float)k;
+        if ((float)k < n) {
+            prod *= tk;
+            rsum += 1.f / tk;
+        }
+    }
+    float lg = n > 0.f ? logf(prod) : 0.f, ps = rsum;
+    if (d > 0.f) {
+        const float b = t + n, a = b + d;
+        const float ra = 1.f / a, rb = 1.f / b, ra2 = ra * ra, rb2 = rb * rb;
+        const float l1 = log1pf(d * rb);
+        const float sa = ra * (1.f / 12.f - ra2 * (1.f / 360.f - ra2 * (1.f / 1260.f)));
+        const float sb = rb * (1.f / 12.f - rb2 * (1.f / 360.f - rb2 * (1.f / 1260.f)));
+        lg += d * logf(a) + (fmaf(b - 0.5f, l1, -d) + (sa - sb));
+        const float qa = ra2 * ra2 * (1.f / 120.f - ra2 * (1.f / 252.f));
+        const float qb = rb2 * rb2 * (1.f / 120.f - rb2 * (1.f / 252.f));
+        ps += l1 + d * ra * rb * (0.5f + (a + b) * ra * rb * (1.f / 12.f)) + (qa - qb);
+    }
+    const float lt = -log1pf(m / t), lm = -log1pf(t / m);
+    const float tm = t + m;
+    g_m = (x - m) / (m * (1.f + m / t)) * dv_softplus_slope_from_y(m - shift);
+    g_t = (ps + lt + (m - x) / tm) * dv_softplus_slope_from_y(t - DV_NB_THETA_SHIFT);
+    return (lg - lgammaf(x + 1.f)) + (t * lt + x * lm);
+}
+
+// one workgroup per row, like rec_nll_rows_kernel; VEC (X % 4 == 0, 16-byte aligned rows: the dispatcher checks): four
+// genes per thread on 16-byte loads and stores, else one gene per thread
+template <bool VEC>
+__global__ __launch_bounds__(256) void nb_nll_rows_kernel(float shift, const float* __restrict__ coef,
+                                                          const float* __restrict__ x, int64_t ldx,
+                                                          const int32_t* __restrict__ xidx, const float* __restrict__ v,
+                                                          int64_t ldv, int M, int X, float* __restrict__ out,
+                                                          float* __restrict__ dpre, int64_t ldd) {
+    __shared__ float part[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int r = blockIdx.x; r < M; r += gridDim.x) {
+        const float* xr = x + (int64_t)(xidx ? xidx[r] : r) * ldx;
+        const float* vr = v + (int64_t)r * ldv;
+        float* dr = coef ? dpre + (int64_t)r * ldd : nullptr;
+        const float c = coef ? coef[r] : 0.f;
+        float acc = 0.f;
+        if constexpr (VEC) {
+            for (int q = threadIdx.x; q < (X >> 2); q += 256) {
+                const float4 xv = reinterpret_cast<const float4*>(xr)[q];
+                const float4 mv = reinterpret_cast<const float4*>(vr)[q];
+                const float4 tv = reinterpret_cast<const float4*>(vr + X)[q];
+                float4 gm = make_float4(0.f, 0.f, 0.f, 0.f), gt = gm;
+                // ONE copy of the term's code, walked four times (j is uniform: scalar selects); four inlined copies
+                // interleave their branches' saved masks and run out of scalar registers
+#pragma unroll 1
+                for (int j = 0; j < 4; ++j) {
+                    const float xj = j == 0 ? xv.x : j == 1 ? xv.y : j == 2 ? xv.z : xv.w;
+                    const float mj = j == 0 ? mv.x : j == 1 ? mv.y : j == 2 ? mv.z : mv.w;
+                    const float tj = j == 0 ? tv.x : j == 1 ? tv.y : j == 2 ? tv.z : tv.w;
+                    float a, b;
+                    acc += nb_term(shift, xj, mj, tj, a, b);
+                    if (coef) {      // (inside the branch: a pass without gradients does not pay for them)
+                        a *= c, b *= c;
+                        gm.x = j == 0 ? a : gm.x, gm.y = j == 1 ? a : gm.y, gm.z = j == 2 ? a : gm.z, gm.w = j == 3 ? a : gm.w;
+                        gt.x = j == 0 ? b : gt.x, gt.y = j == 1 ? b : gt.y, gt.z = j == 2 ? b : gt.z, gt.w = j == 3 ? b : gt.w;
+                    }
+                }
+                if (coef) {
+                    reinterpret_cast<float4*>(dr)[q] = gm;
+                    reinterpret_cast<float4*>(dr + X)[q] = gt;
+                }
+            }
+        } else {
+            for (int g = threadIdx.x; g < X; g += 256) {
+                float gm, gt;
+                acc += nb_term(shift, xr[g], vr[g], vr[X + g], gm, gt);
+                if (coef) {
+                    dr[g] = c * gm;
+                    dr[X + g] = c * gt;
+                }
+            }
+        }
+        acc = dv_wave_sum_all(acc);
+        if (lane == 0) part[wave] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) out[r] = (part[0] + part[1]) + (part[2] + part[3]);
+        __syncthreads();
+    }
+}
+
 __global__ void nll_rows_bwd_kernel(const float* __restrict__ coef, const float* __restrict__ x, int64_t ldx,
                                     const int32_t* __restrict__ xidx, const float* __restrict__ mu,
                                     const float* __restrict__ sd, int64_t ldp, int M, int X, int mode, int sd_act,
@@ -3024,9 +3129,22 @@ extern "C" int dv_nll_raw_cs_row_blocks(int32_t M) { return M <= 0 ? 0 : (M + kN
 extern "C" int dv_rec_nll_rows(int32_t kind, float shift, const float* coef, const float* x, int64_t ldx,
                                const int32_t* xidx, const float* v, int64_t ldv, int32_t M, int32_t X, float* out,
                                float* dpre, int64_t ldd, dv_stream_t stream) {
-    DV_REQUIRE(M >= 0 && X >= 1 && (kind == DV_REC_BERNOULLI || kind == DV_REC_POISSON));
+    DV_REQUIRE(M >= 0 && X >= 1 && (kind == DV_REC_BERNOULLI || kind == DV_REC_POISSON || kind == DV_REC_NEGBIN));
     if (M == 0) return DV_OK;
     DV_REQUIRE(x && v && out && (coef == nullptr || dpre != nullptr));
+    if (kind == DV_REC_NEGBIN) {      // v = [mu | theta], dpre = [d/da_m | d/da_t]: 2X columns each, a kernel of its own
+        DV_REQUIRE(ldv >= 2 * (int64_t)X && (coef == nullptr || ldd >= 2 * (int64_t)X));
+        auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+        const bool vec = X % 4 == 0 && a16(x) && a16(v) && ldx % 4 == 0 && ldv % 4 == 0 &&
+                         (coef == nullptr || (a16(dpre) && ldd % 4 == 0));
+        if (vec)
+            hipLaunchKernelGGL(nb_nll_rows_kernel<true>, dim3(grid_for(M, 1, 4096)), dim3(256), 0, ST(stream), shift, coef,
+                               x, ldx, xidx, v, ldv, M, X, out, dpre, ldd);
+        else
+            hipLaunchKernelGGL(nb_nll_rows_kernel<false>, dim3(grid_for(M, 1, 4096)), dim3(256), 0, ST(stream), shift,
+                               coef, x, ldx, xidx, v, ldv, M, X, out, dpre, ldd);
+        DV_RETURN_LAUNCH();
+    }
     hipLaunchKernelGGL(rec_nll_rows_kernel, dim3(grid_for(M, 1, 4096)), dim3(256), 0, ST(stream), kind, shift, coef, x,
                        ldx, xidx, v, ldv, M, X, out, dpre, ldd);
     DV_RETURN_LAUNCH();

@@ -79,7 +79,8 @@ class StepConfig:
     # penalty between the nuisance classes' latent samples (src/DrVAE.py:394-398,537-540,616,623-624)
     # type of p(x|z): 'diag_gaussian' (the only one the reference can build) | 'binary' | 'poisson' -- the Bernoulli /
     # Poisson decoders src/DrVAE.py:124-129 names and blocks.py never defines: one Linear head, log-likelihood rows
-    # by dv_rec_nll_rows (EXTENSION)
+    # by dv_rec_nll_rows (EXTENSION) | 'nb': the negative binomial for overdispersed counts (EXTENSION, no counterpart in
+    # the reference) -- two softplus heads [mu | theta] over one trunk, rows and both heads' gradients by the same launch
     type_rec: str = 'diag_gaussian'
     use_s: bool = False
     dim_s: int = 2
@@ -228,6 +229,10 @@ def param_shapes(cfg):
         gauss('decoder_z1', Z3 + Y, cfg.h_de_z1, Z1)
     if cfg.type_rec == 'diag_gaussian':
         gauss('decoder_x', Z1 + S, cfg.h_de_x, X, second='sg')
+    elif cfg.type_rec == 'nb':
+        n = trunk('decoder_x.nnet', Z1 + S, cfg.h_de_x)
+        for q in NB_HEADS:
+            lin(q, n, X)
     else:
         n = trunk('decoder_x.nnet', Z1 + S, cfg.h_de_x)
         lin(REC_HEAD[cfg.type_rec], n, X)
@@ -235,7 +240,12 @@ def param_shapes(cfg):
 
 
 REC_HEAD = {'binary': 'decoder_x.decoder_p.linear_p', 'poisson': 'decoder_x.decoder_r.linear_r'}
-REC_ACT = {'binary': ('sigmoid', 0.0), 'poisson': ('softplus', 1e-6)}
+# (head's activation, shift of its first -- or only -- head: the ``shift`` argument of ``dv_rec_nll_rows``)
+REC_ACT = {'binary': ('sigmoid', 0.0), 'poisson': ('softplus', 1e-6), 'nb': ('softplus', 1e-6)}
+# the negative-binomial decoder's two heads over one trunk, mean then inverse dispersion (``blocks.NegativeBinomialDecoder``);
+# theta's shift is the sigma head's (``DV_NB_THETA_SHIFT``)
+NB_HEADS = ('decoder_x.decoder_m.linear_m', 'decoder_x.decoder_t.linear_t')
+NB_THETA_SHIFT = 1e-3
 Y_LOGVAR_CONT = math.log(0.05 ** 2)      # fixed variance of the regression head (src/DrVAE.py:168)
 
 
@@ -352,14 +362,20 @@ class FusedStep(StepSchedule):
         self.L_enc = self._gauss('encoder_z1', len(cfg.h_en_z1), 'lv', shift_second=-2.0)
         if cfg.type_rec == 'diag_gaussian':
             self.L_decx = self._gauss('decoder_x', len(cfg.h_de_x), 'sg', 'softplus', 1e-3)
-        else:       # Bernoulli / Poisson decoder: trunk + ONE head (probabilities / rates)
+        else:       # Bernoulli / Poisson decoder: trunk + ONE head (probabilities / rates); negative binomial: two
             layers = []
             for i in range(1, len(cfg.h_de_x) + 1):
                 q = 'decoder_x.nnet.model.linear%d' % i
                 layers.append(_Lin(a, q + '.weight', q + '.bias', q + '.g' if wn else None, act=cfg.nonlin))
-            q = REC_HEAD[cfg.type_rec]
             act, shift = REC_ACT[cfg.type_rec]
-            layers.append(_Lin(a, q + '.weight', q + '.bias', q + '.g' if wn else None, act=act, shift0=shift))
+            if cfg.type_rec == 'nb':      # negative binomial: TWO heads, [mu | theta], both softplus + their own shift
+                q, s = NB_HEADS
+                layers.append(_Lin(a, q + '.weight', q + '.bias', q + '.g' if wn else None,
+                                   second=(s + '.weight', s + '.bias', s + '.g' if wn else None),
+                                   act=act, shift0=shift, act1='softplus', shift1=NB_THETA_SHIFT))
+            else:
+                q = REC_HEAD[cfg.type_rec]
+                layers.append(_Lin(a, q + '.weight', q + '.bias', q + '.g' if wn else None, act=act, shift0=shift))
             self.L_decx = layers
         if cfg.has_pert:
             p = 'decoder_z2Fz1.'
@@ -857,7 +873,7 @@ class FusedStep(StepSchedule):
         if self._tail.late_fork:      # (chip-filling step: the side chain starts HERE, next to the row pass below)
             self.branch.fork()
         lh = p.c_decx.layers[-1]
-        if r.nll == 'rec':     # Bernoulli / Poisson rows (+ the gradient w.r.t. the head's pre-activation in a train step)
+        if r.nll == 'rec':     # Bernoulli / Poisson / negative-binomial rows (+ the gradient w.r.t. the head's pre-activation in a train step)
             K.rec_nll_rows(p.NLL, p.XIN, PX, kind=cfg.type_rec, shift=REC_ACT[cfg.type_rec][1], xidx=p.tgt,
                            coef=p.c_nll if train else None, dpre=p.DPX if train else None)
         elif r.nll in ('raw_cs', 'raw_cs_eval'):

@@ -189,7 +189,8 @@ class FitMixin:
         ``_EvalGraph``.  That includes the regression head (``type_y='cont'``: rmse / R^2 / Pearson r from ``dv_reg_metrics``) and
         models conditioned on the nuisance variable (``use_s``; with ``use_MMD`` for ``kernel_MMD='rbf_fourier' | 'identity'``
         and 2 <= dim_s <= 8, the penalty as its two grouped launches).  ``return_full_data`` (arrays for the caller), host
-        datasets, ``type_rec='binary' | 'poisson'`` and the other MMD kernels take the step-by-step path."""
+        datasets, ``type_rec='binary' | 'poisson' | 'nb'`` and the other MMD kernels take the step-by-step path (``'nb'``:
+        ``x1_rec`` / ``x2_pert`` are the means, ``px1`` = (mu, theta), and the reported ``ll`` is the negative binomial's)."""
         g = lambda k: getattr(ds, k, None)
         ev = None if return_full_data else _EvalGraph.get(self, ds)
         if ev is not None:

@@ -588,8 +588,13 @@ def nll_rows_raw_cs(out_part, dmu, dsd, ws, coef, x, mu, sd, bias, *, xidx=None,
 
 def rec_nll_rows(out, x, v, *, kind, shift=0.0, xidx=None, coef=None, dpre=None):
     """log-likelihood rows of the Bernoulli ('binary') / Poisson decoders from the head's post-activation output
-    ``v``; with ``coef`` also the gradient w.r.t. the head's pre-activation (``dv_rec_nll_rows``)"""
+    ``v``; with ``coef`` also the gradient w.r.t. the head's pre-activation (``dv_rec_nll_rows``).  ``kind='nb'`` (negative
+    binomial): ``v`` = [mu | theta] and ``dpre`` = [d/da_m | d/da_t], 2X columns each; ``shift`` is the mean's, theta's is
+    ``DV_NB_THETA_SHIFT``"""
     M, X = v.shape
+    if kind == 'nb':
+        X = x.shape[1]
+        assert v.shape[1] == 2 * X and (dpre is None or tuple(dpre.shape) == (M, 2 * X))
     _lib.check(_lib.load().dv_rec_nll_rows(_lib.REC_KIND[kind], shift, _f32(coef), _f32(x), _ld(x), _i32(xidx), _f32(v),
                                            _ld(v), M, X, _f32(out), _f32(dpre), _ld(dpre), _stream()), 'dv_rec_nll_rows')
 

@@ -525,8 +525,18 @@ int dv_gauss_nll_rows_bwd(const float* coef, const float* x, int64_t ldx, const 
  * (probability = sigmoid(a), or rate = softplus(a) + shift); x row = xidx ? xidx[r] : r.
  *   out[r] = sum_g log p(x[.,g] | v[r,g]);  coef != NULL: dpre[r,g] = coef[r] * d log p / d a  (a = pre-activation)
  *   BERNOULLI: pc = clamp(v, 1e-10, 1 - 1e-10); log p = x log pc + (1-x) log(1-pc); d/da = x - v inside the clamp, else 0
- *   POISSON  : log p = x log v - v - lgamma(x+1);  d/da = (x/v - 1) (1 - exp(-(v - shift))) */
-enum { DV_REC_BERNOULLI = 0, DV_REC_POISSON = 1 };
+ *   POISSON  : log p = x log v - v - lgamma(x+1);  d/da = (x/v - 1) (1 - exp(-(v - shift)))
+ * EXTENSION (`type_rec='nb'`, no counterpart in the reference): NEGBIN, the negative binomial with mean mu > 0 and inverse
+ * dispersion theta > 0 (Var = mu + mu^2 / theta), two heads over one trunk.  v row r = [mu | theta], 2X columns
+ * (ldv >= 2X), mu = softplus(a_m) + shift, theta = softplus(a_t) + DV_NB_THETA_SHIFT; dpre row r =
+ * coef[r] * [d/da_m | d/da_t], 2X columns (ldd >= 2X); x counts >= 0 (exact in fp32 up to 2^24):
+ *   log p    = [lgamma(x+theta) - lgamma(theta)] - lgamma(x+1) + theta log(theta/(theta+mu)) + x log(mu/(theta+mu))
+ *   d/dmu    = x/mu - (x+theta)/(theta+mu);   d/dtheta = [psi(x+theta) - psi(theta)] + log(theta/(theta+mu)) + (mu-x)/(theta+mu)
+ *   d/da_*   = d/d(mu, theta) * (1 - exp(-(v - its shift)))
+ * The lgamma / digamma pairs and the two log ratios are formed as differences (recurrence + asymptotic series, log1p),
+ * never as two large values subtracted: the x = 0 pair is exactly 0, and theta -> inf is the Poisson term. */
+enum { DV_REC_BERNOULLI = 0, DV_REC_POISSON = 1, DV_REC_NEGBIN = 2 };
+#define DV_NB_THETA_SHIFT 1e-3f     /* the shift of the NEGBIN theta head (that of the Gaussian decoder's sigma head) */
 int dv_rec_nll_rows(int32_t kind, float shift, const float* coef, const float* x, int64_t ldx, const int32_t* xidx,
                     const float* v, int64_t ldv, int32_t M, int32_t X, float* out, float* dpre, int64_t ldd,
                     dv_stream_t stream);
