@@ -118,6 +118,7 @@ class DeepGenerativeModelMixin:
             # steps): an attribute changed behind its back must not be ignored
             cfg = self._engine.cfg
             late = [(k, v, getattr(cfg, k)) for k, v in self._anneal_config().items() if v != getattr(cfg, k)]
+            late += [(k, v, getattr(cfg, k)) for k, v in self._counts_config().items() if v != getattr(cfg, k)]
             if getattr(self, 'ema_decay', None) != cfg.ema_decay:     # (the average's buffer and launch arguments exist or not)
                 late.append(('ema_decay', self.ema_decay, cfg.ema_decay))
             if late:

@@ -26,7 +26,12 @@ class PVAE(ELBOModel):
     ``ema_decay`` (default None: off; a number in (0, 1), else ``ValueError``) keeps an exponential moving average of the
     parameters inside the optimiser sweep: ``averaged_parameters()`` evaluates with it, ``averaged_state_dict()`` returns it,
     ``fit`` evaluates and snapshots it unless ``model.ema_eval = False``.  ``optim_alg='adamw'`` is Adam with decoupled weight
-    decay (``torch.optim.AdamW``).  Both are labelled extensions."""
+    decay (``torch.optim.AdamW``).  Both are labelled extensions.
+    ``x_transform`` (default None | 'log1p') and ``library_size`` (default False) are the raw-count inputs of the count decoders
+    (``type_rec='poisson'`` / ``'nb'``; anything else, or another ``x_transform``, raises ``ValueError``; x >= 0, checked once
+    per dataset by ``fit`` / ``DeviceBatcher.bind``): the encoder reads log1p(x) while the likelihood keeps the raw counts
+    without training noise, and every decoder mean of a row is multiplied by the row's observed size factor
+    max(sum_g x_g, 1) / dim_x.  Attributes until the engine is built, like the schedules.  Labelled extensions."""
     kind = 'pvae'
     prior_y = None          # read by the reference ctor (src/PVAE.py:77) although PVAE has no y
 
@@ -38,7 +43,8 @@ class PVAE(ELBOModel):
                  anneal_perturb_rate_offset=0, use_s=False, use_c=False, use_m=False, random_seed=12345,
                  log_txt=None, weight_norm=False, device=None, matmul_precision='fp32',
                  max_grad_norm=None, anneal_kl=False, anneal_kl_itermax=100, anneal_yloss=False, anneal_yloss_itermax=1,
-                 anneal_learning_rate=False, anneal_lr_itermax=3000, ema_decay=None):
+                 anneal_learning_rate=False, anneal_lr_itermax=3000, ema_decay=None,
+                 x_transform=None, library_size=False):
         super().__init__()
         args = dict(locals())
         args.pop('self')

@@ -25,7 +25,12 @@ class VFAE(ELBOModel):
     ``ema_decay`` (default None: off; a number in (0, 1), else ``ValueError``) keeps an exponential moving average of the
     parameters inside the optimiser sweep: ``averaged_parameters()`` evaluates with it, ``averaged_state_dict()`` returns it,
     ``fit`` evaluates and snapshots it unless ``model.ema_eval = False``.  ``optim_alg='adamw'`` is Adam with decoupled weight
-    decay (``torch.optim.AdamW``).  Both are labelled extensions."""
+    decay (``torch.optim.AdamW``).  Both are labelled extensions.
+    ``x_transform`` (default None | 'log1p') and ``library_size`` (default False) are the raw-count inputs of the count decoders
+    (``type_rec='poisson'`` / ``'nb'``; anything else, or another ``x_transform``, raises ``ValueError``; x >= 0, checked once
+    per dataset by ``fit`` / ``DeviceBatcher.bind``): the encoder reads log1p(x) while the likelihood keeps the raw counts
+    without training noise, and every decoder mean of a row is multiplied by the row's observed size factor
+    max(sum_g x_g, 1) / dim_x.  Attributes until the engine is built, like the schedules.  Labelled extensions."""
     kind = 'vfae'
     fit_patience = 40       # src/VFAE.py:536
 
@@ -37,7 +42,8 @@ class VFAE(ELBOModel):
                  anneal_yloss_offset=0, use_MMD=True, kernel_MMD='rbf_fourier', mmd_rate=1., use_s=False,
                  random_seed=12345, log_txt=None, weight_norm=False, device=None, matmul_precision='fp32',
                  max_grad_norm=None, anneal_kl=False, anneal_kl_itermax=100, anneal_yloss=False, anneal_yloss_itermax=1,
-                 anneal_learning_rate=False, anneal_lr_itermax=3000, ema_decay=None):
+                 anneal_learning_rate=False, anneal_lr_itermax=3000, ema_decay=None,
+                 x_transform=None, library_size=False):
         super().__init__()
         args = dict(locals())
         args.pop('self')

@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, 'libdrvae_hip.so')
 ACT = {'identity': 0, 'elu': 1, 'softplus': 2, 'sigmoid': 3, 'tanh': 4, 'relu': 5, 'leaky_relu': 6, 'selu': 7,
        'softsign': 8, 'cos': 9}
 GAUSS_LOGVAR, GAUSS_SIGMA = 0, 1
-REC_KIND = {'binary': 0, 'poisson': 1, 'nb': 2}
+REC_KIND = {'binary': 0, 'poisson': 1, 'nb': 2, 'poisson_lib': 3, 'nb_lib': 4}
 EPI_PLAIN, EPI_FWD, EPI_BWD, EPI_KLQ = 0, 1, 2, 3
 
 _f, _i32, _i64, _u64, _p = C.c_float, C.c_int32, C.c_int64, C.c_uint64, C.c_void_p
@@ -115,7 +115,9 @@ class BatchFeed(C.Structure):    # dv_batch_feed_desc
                 ('ctr', _p), ('base', _p), ('B', _i32), ('pair_rows', _p), ('Np', _i32), ('X', _i32), ('noise', _p),
                 ('ldn', _i64), ('sigma', _f), ('xin', _p), ('ldo', _i64), ('has_y', _p), ('L', _i32), ('label_r', _p),
                 ('fp_i', _p), ('fp_lab', _p), ('fp_slot', _p), ('Mf', _i32), ('fp_cls', _p), ('onehot', _p),
-                ('ldh', _i64), ('Y', _i32), ('yf', _p), ('ylab', _p), ('Yc', _i32), ('onehot2', _p), ('ldh2', _i64)]
+                ('ldh', _i64), ('Y', _i32), ('yf', _p), ('ylab', _p), ('Yc', _i32), ('onehot2', _p), ('ldh2', _i64),
+                # trailing: the split form (raw-count inputs; xt NULL: the launch as it was)
+                ('xt', _p), ('ldt', _i64), ('transform', _i32)]
 
 
 class KlRows(C.Structure):       # dv_kl_rows_desc

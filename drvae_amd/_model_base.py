@@ -47,11 +47,16 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         # None | a number in (0, 1): the exponential moving average of the parameters kept by the optimiser sweep, see
         # ``StepConfig.ema_decay``; ``ema_eval``: ``fit`` evaluates and snapshots the averaged weights (default) or the live ones
         ema_decay = E.check_ema_decay(args.pop('ema_decay', None))
+        # raw-count inputs (EXTENSIONS, count decoders only; ``StepConfig.x_transform`` / ``library_size``): the encoder reads
+        # log1p(x) while the likelihood keeps the raw counts; every decoder mean is scaled by the row's observed size factor
+        x_transform, library_size = args.pop('x_transform', None), args.pop('library_size', False)
         for k, v in args.items():
             setattr(self, k, v)
         for k, v in anneal.items():
             setattr(self, k, v)
         self.ema_decay, self.ema_eval = ema_decay, True
+        self.x_transform, self.library_size = x_transform, library_size
+        self._counts_config()           # (a bad value, or a switch on a decoder that is no count decoder: ValueError)
         if not hasattr(self, 'anneal_yloss_offset'):
             self.anneal_yloss_offset = 0
         self._anneal_config()           # (a switch that is on with itermax <= 0: ValueError)
@@ -180,6 +185,25 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
                 raise ValueError('%s is on: %s must be a positive number of iterations, not %r' % (sw, mx, kw[mx]))
         return dict((k, bool(v) if k in ('anneal_kl', 'anneal_yloss', 'anneal_learning_rate') else int(v)) for k, v in kw.items())
 
+    def _counts_config(self):
+        """the raw-count switches as they stand now, as ``StepConfig`` keyword arguments (checked: ValueError)"""
+        return E.check_counts_config(getattr(self, 'x_transform', None), getattr(self, 'library_size', False), self.type_rec)
+
+    def size_factor(self, x):
+        """the observed size factor of every row of ``x``, (rows,): max(sum_g x_g, 1) / dim_x -- what ``library_size=True``
+        multiplies the decoder means of a row by (``dv_rec_nll_rows``, the ``_LIB`` kinds)"""
+        return torch.clamp(x.sum(dim=1), min=1.0) / float(self.dim_x)
+
+    def _enc_x(self, x):
+        """the encoder's view of the rows ``x``: T(x), T = log1p with ``x_transform='log1p'``"""
+        return torch.log1p(x) if getattr(self, 'x_transform', None) == 'log1p' else x
+
+    def _scaled(self, px, x):
+        """decoder output ``px`` with its mean multiplied by the size factor of the rows ``x`` (``library_size``; else as it is)"""
+        if not getattr(self, 'library_size', False):
+            return px
+        return (px[0] * self.size_factor(x)[:, None],) + tuple(px[1:])
+
     def _step_config(self):
         top = 'dim_z3' if self.kind == 'drvae' else 'dim_z2'
         return E.StepConfig(
@@ -201,17 +225,21 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
             mmd_rate=float(getattr(self, 'mmd_rate', 1.)), kernel_MMD=getattr(self, 'kernel_MMD', 'rbf_fourier'),
             prior_y=None if (getattr(self, 'prior_y', None) is None or isinstance(getattr(self, 'prior_y', None), str))
             else tuple(float(v) for v in self.prior_y), matmul=self._matmul, dropout_rate=float(self.dropout_rate),
-            max_grad_norm=self._max_grad_norm, ema_decay=self.ema_decay, **self._anneal_config())
+            max_grad_norm=self._max_grad_norm, ema_decay=self.ema_decay, **self._counts_config(), **self._anneal_config())
 
     # ---------------------------------------------------------------- inference
     @torch.no_grad()
     def forward(self, x1, s=[]):
         """Inference with the posterior MEANS (no sampling): src/DrVAE.py:253-311,
-        src/PVAE.py:203-246, src/VFAE.py:178-215."""
+        src/PVAE.py:203-246, src/VFAE.py:178-215.
+
+        Raw-count switches (EXTENSIONS): the encoder reads T(x1) (``x_transform``); with ``library_size`` the means
+        ``px1[0]`` / ``x1_rec`` and ``px2[0]`` / ``x2_pert`` are multiplied by the size factor of ``x1`` -- the depth of the
+        perturbed profile is unknown at prediction time, so the prediction is made at the depth of the profile it starts from."""
         self.eval()
         x1 = x1.to(next(self.parameters()).device, torch.float32)
         cond = self._s_inputs(s, x1)
-        qz1 = self.encoder_z1([x1] + cond)
+        qz1 = self.encoder_z1([self._enc_x(x1)] + cond)
         z1 = qz1[0]
         res = OrderedDict(z1=z1, qz1=qz1)
         if self.kind in ('drvae', 'pvae'):
@@ -225,10 +253,10 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
                 clf_in = [z1]
             qy = self.encoder_y(clf_in)
             res.update(**self._pred_proba(qy))
-        px1 = self.decoder_x([z1] + cond)
+        px1 = self._scaled(self.decoder_x([z1] + cond), x1)
         res.update(px1=px1, x1_rec=px1[0])
         if self.kind in ('drvae', 'pvae'):
-            px2 = self.decoder_x([z2] + cond)
+            px2 = self._scaled(self.decoder_x([z2] + cond), x1)
             res.update(px2=px2, x2_pert=px2[0])
         return res
 
@@ -241,22 +269,23 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
     @torch.no_grad()
     def forward_w_pert_identity(self, x1, x2, s=[]):
         """Inference assuming the perturbation function is the identity
-        (src/DrVAE.py:185-251, src/PVAE.py:155-201)."""
+        (src/DrVAE.py:185-251, src/PVAE.py:155-201).  ``library_size``: ``px2`` / ``x2_pert`` (predicted from x1) carry x1's
+        size factor, ``px2_rec`` / ``x2_rec`` (reconstructed from x2) x2's own."""
         if self.kind == 'vfae':
             raise AttributeError('VFAE has no perturbation path')
         self.eval()
         dev = next(self.parameters()).device
         x1, x2 = x1.to(dev, torch.float32), x2.to(dev, torch.float32)
         cond = self._s_inputs(s, x1)
-        qz1 = self.encoder_z1([x1] + cond)
+        qz1 = self.encoder_z1([self._enc_x(x1)] + cond)
         z1 = qz1[0]
         res = OrderedDict(z1=z1, qz1=qz1)
         if self.kind == 'drvae':
             qy = self.encoder_y([z1, z1 - z1] if self.clf_z1z2 else [z1])
             res.update(**self._pred_proba(qy))
-        px2 = self.decoder_x([z1] + cond)
-        qz2 = self.encoder_z1([x2] + cond)
-        px2_rec = self.decoder_x([qz2[0]] + cond)
+        px2 = self._scaled(self.decoder_x([z1] + cond), x1)
+        qz2 = self.encoder_z1([self._enc_x(x2)] + cond)
+        px2_rec = self._scaled(self.decoder_x([qz2[0]] + cond), x2)
         res.update(px2=px2, x2_pert=px2[0], z2=qz2[0], qz2=qz2, px2_rec=px2_rec, x2_rec=px2_rec[0])
         return res
 

@@ -458,6 +458,11 @@ class BernoulliDecoder(_SingleHeadDecoder):
         return (ps > 0.5).to(ps.dtype)
 
 
+def _size_scaled(mean, size):
+    """``mean`` (rows, genes) times the per-row size factors ``size`` (rows,); None: as it is"""
+    return mean if size is None else mean * torch.as_tensor(size, dtype=mean.dtype, device=mean.device).reshape(-1, 1)
+
+
 class PoissonDecoder(_SingleHeadDecoder):
     """EXTENSION (``type_rec='poisson'``, src/DrVAE.py:128-129; absent from the reference's blocks.py):
     inputs -> [softplus(linear_r(h)) + 1e-6]; log p(x|.) = sum x log rate - rate - lgamma(x+1)."""
@@ -466,11 +471,13 @@ class PoissonDecoder(_SingleHeadDecoder):
     def forward(self, inputs):
         return [self._head_out(inputs)]
 
-    def logp_perx(self, x, rate):
+    def logp_perx(self, x, rate, size=None):
+        """``size`` (rows,): the rows' size factors -- the rate is size * rate (``library_size`` models)"""
+        rate = _size_scaled(rate, size)
         return (x * torch.log(rate) - rate - torch.lgamma(x + 1.)).sum(1)
 
-    def sample(self, rate):
-        return torch.poisson(rate)
+    def sample(self, rate, size=None):
+        return torch.poisson(_size_scaled(rate, size))
 
 
 class NegativeBinomialDecoder(nn.Module):
@@ -513,7 +520,9 @@ class NegativeBinomialDecoder(nn.Module):
         return (self._head_out(self.decoder_m, 'linear_m', h, self.MU_SHIFT),
                 self._head_out(self.decoder_t, 'linear_t', h, self.THETA_SHIFT))
 
-    def logp_perx(self, x, mu, theta):
+    def logp_perx(self, x, mu, theta, size=None):
+        """``size`` (rows,): the rows' size factors -- the mean is size * mu, theta as it is (``library_size`` models)"""
+        mu = _size_scaled(mu, size)
         t64 = theta.double()
         lg = (torch.lgamma(x.double() + t64) - torch.lgamma(t64)).to(theta.dtype)
         return (lg - torch.lgamma(x + 1.) - theta * torch.log1p(mu / theta) - x * torch.log1p(theta / mu)).sum(1)
@@ -521,8 +530,9 @@ class NegativeBinomialDecoder(nn.Module):
     def logp(self, x, mu, theta):
         return torch.sum(self.logp_perx(x, mu, theta))
 
-    def sample(self, mu, theta):
-        """Gamma-Poisson: rate ~ Gamma(shape = theta, mean = mu), x ~ Poisson(rate)"""
+    def sample(self, mu, theta, size=None):
+        """Gamma-Poisson: rate ~ Gamma(shape = theta, mean = mu), x ~ Poisson(rate); ``size``: as in ``logp_perx``"""
+        mu = _size_scaled(mu, size)
         return torch.poisson(torch._standard_gamma(theta) * (mu / theta))
 
 

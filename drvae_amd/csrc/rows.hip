@@ -986,17 +986,45 @@ __global__ __launch_bounds__(256) void nll_rows_raw_cs_kernel(NllCsArgs a) {
 //   Bernoulli: pc = clamp(v, 1e-10, 1 - 1e-10) (the clamp of src/blocks.py:463 applied to this decoder's probabilities);
 //              log p = x log pc + (1-x) log(1-pc);  d/da = x - v inside the clamp, 0 outside
 //   Poisson  : log p = x log v - v - lgamma(x+1);   d/da = (x/v - 1) * sigmoid(a), sigmoid(a) = -expm1(-(v - shift))
-__device__ __forceinline__ float rec_term(int kind, float shift, float xv, float v, float& g) {
+//   library-scaled (LIB, DV_REC_POISSON_LIB): the rate is m = s v with the row's size factor s; d/da = (x/v - s) * sigmoid(a)
+//              (x/m * s = x/v: the slope is the UNSCALED head's).  !LIB: s is not read, the term as it ever was
+template <bool LIB>
+__device__ __forceinline__ float rec_term(int kind, float shift, float s, float xv, float v, float& g) {
     if (kind == DV_REC_BERNOULLI) {
         const float lo = 1e-10f, hi = (float)(1.0 - 1e-10);
         const float pc = fminf(fmaxf(v, lo), hi);
         g = (v > lo && v < hi) ? xv - v : 0.f;
         return xv * logf(pc) + (1.f - xv) * logf(1.f - pc);
     }
-    g = (xv / v - 1.f) * dv_softplus_slope_from_y(v - shift);
-    return xv * logf(v) - v - lgammaf(xv + 1.f);
+    const float m = LIB ? s * v : v;
+    g = (xv / v - (LIB ? s : 1.f)) * dv_softplus_slope_from_y(v - shift);
+    return xv * logf(m) - m - lgammaf(xv + 1.f);
 }
 
+// The observed size factor of a target row (library-scaled kinds): s = max(sum_g x_g, 1) / X, by the whole workgroup in a
+// fixed order -- per-thread partials in index order, the wave sum, then the four waves as (p0 + p1) + (p2 + p3), like the
+// row sums below.  (Integer counts with a total below 2^24 sum exactly in fp32 in ANY order: s is then one correctly
+// rounded quotient.)  VEC: 16-byte loads.  Every thread returns s; `part` is free again on return
+template <bool VEC>
+__device__ __forceinline__ float row_size_factor(const float* __restrict__ xr, int X, float* part) {
+    float acc = 0.f;
+    if constexpr (VEC) {
+        for (int q = threadIdx.x; q < (X >> 2); q += 256) {
+            const float4 xv = reinterpret_cast<const float4*>(xr)[q];
+            acc += xv.x, acc += xv.y, acc += xv.z, acc += xv.w;
+        }
+    } else {
+        for (int g = threadIdx.x; g < X; g += 256) acc += xr[g];
+    }
+    acc = dv_wave_sum_all(acc);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    const float tot = (part[0] + part[1]) + (part[2] + part[3]);
+    __syncthreads();
+    return fmaxf(tot, 1.f) / (float)X;
+}
+
+template <bool LIB>
 __global__ __launch_bounds__(256) void rec_nll_rows_kernel(int kind, float shift, const float* __restrict__ coef,
                                                            const float* __restrict__ x, int64_t ldx,
                                                            const int32_t* __restrict__ xidx,
@@ -1009,10 +1037,12 @@ __global__ __launch_bounds__(256) void rec_nll_rows_kernel(int kind, float shift
         const float* xr = x + (int64_t)(xidx ? xidx[r] : r) * ldx;
         const float* vr = v + (int64_t)r * ldv;
         const float c = coef ? coef[r] : 0.f;
+        float sz = 1.f;
+        if constexpr (LIB) sz = row_size_factor<false>(xr, X, part);      // (the term loop's read of the row: from cache)
         float acc = 0.f;
         for (int g = threadIdx.x; g < X; g += 256) {
             float gr;
-            acc += rec_term(kind, shift, xr[g], vr[g], gr);
+            acc += rec_term<LIB>(kind, shift, sz, xr[g], vr[g], gr);
             if (coef) dpre[(int64_t)r * ldd + g] = c * gr;
         }
         acc = dv_wave_sum_all(acc);
@@ -1037,7 +1067,12 @@ __global__ __launch_bounds__(256) void rec_nll_rows_kernel(int kind, float shift
 //   * log(t/(t+m)) = -log1p(m/t) and log(m/(t+m)) = -log1p(t/m): exact in the Poisson limit (t log(t/(t+m)) -> -m) and
 //     in its mirror (t << m).
 // g_m / g_t: the gradients w.r.t. the heads' pre-activations (softplus slope from the stored outputs, as rec_term does).
-__device__ __forceinline__ float nb_term(float shift, float x, float m, float t, float& g_m, float& g_t) {
+// LIB (DV_REC_NEGBIN_LIB): the mean is m = s v with the row's size factor s and the mean head's output v; the slope of
+// g_m comes from the UNSCALED head, d/da_m = d/dm * s * slope = (x - m) / (v (1 + m/t)) * slope(v - shift); theta and g_t as
+// they are, at m.  !LIB: s is not read and m = v, the term as it ever was
+template <bool LIB>
+__device__ __forceinline__ float nb_term(float shift, float s, float x, float v, float t, float& g_m, float& g_t) {
+    const float m = LIB ? s * v : v;
     const float n8 = t < 8.f ? ceilf(8.f - t) : 0.f;
     const float n = fminf(x, n8), d = x - n;
     float prod = 1.f, rsum = 0.f;
@@ -1063,14 +1098,14 @@ __device__ __forceinline__ float nb_term(float shift, float x, float m, float t,
     }
     const float lt = -log1pf(m / t), lm = -log1pf(t / m);
     const float tm = t + m;
-    g_m = (x - m) / (m * (1.f + m / t)) * dv_softplus_slope_from_y(m - shift);
+    g_m = (x - m) / (v * (1.f + m / t)) * dv_softplus_slope_from_y(v - shift);
     g_t = (ps + lt + (m - x) / tm) * dv_softplus_slope_from_y(t - DV_NB_THETA_SHIFT);
     return (lg - lgammaf(x + 1.f)) + (t * lt + x * lm);
 }
 
 // one workgroup per row, like rec_nll_rows_kernel; VEC (X % 4 == 0, 16-byte aligned rows: the dispatcher checks): four
 // genes per thread on 16-byte loads and stores, else one gene per thread
-template <bool VEC>
+template <bool VEC, bool LIB>
 __global__ __launch_bounds__(256) void nb_nll_rows_kernel(float shift, const float* __restrict__ coef,
                                                           const float* __restrict__ x, int64_t ldx,
                                                           const int32_t* __restrict__ xidx, const float* __restrict__ v,
@@ -1083,6 +1118,8 @@ __global__ __launch_bounds__(256) void nb_nll_rows_kernel(float shift, const flo
         const float* vr = v + (int64_t)r * ldv;
         float* dr = coef ? dpre + (int64_t)r * ldd : nullptr;
         const float c = coef ? coef[r] : 0.f;
+        float sz = 1.f;
+        if constexpr (LIB) sz = row_size_factor<VEC>(xr, X, part);      // (the term loops' read of the row: from cache)
         float acc = 0.f;
         if constexpr (VEC) {
             for (int q = threadIdx.x; q < (X >> 2); q += 256) {
@@ -1098,7 +1135,7 @@ __global__ __launch_bounds__(256) void nb_nll_rows_kernel(float shift, const flo
                     const float mj = j == 0 ? mv.x : j == 1 ? mv.y : j == 2 ? mv.z : mv.w;
                     const float tj = j == 0 ? tv.x : j == 1 ? tv.y : j == 2 ? tv.z : tv.w;
                     float a, b;
-                    acc += nb_term(shift, xj, mj, tj, a, b);
+                    acc += nb_term<LIB>(shift, sz, xj, mj, tj, a, b);
                     if (coef) {      // (inside the branch: a pass without gradients does not pay for them)
                         a *= c, b *= c;
                         gm.x = j == 0 ? a : gm.x, gm.y = j == 1 ? a : gm.y, gm.z = j == 2 ? a : gm.z, gm.w = j == 3 ? a : gm.w;
@@ -1113,7 +1150,7 @@ __global__ __launch_bounds__(256) void nb_nll_rows_kernel(float shift, const flo
         } else {
             for (int g = threadIdx.x; g < X; g += 256) {
                 float gm, gt;
-                acc += nb_term(shift, xr[g], vr[g], vr[X + g], gm, gt);
+                acc += nb_term<LIB>(shift, sz, xr[g], vr[g], vr[X + g], gm, gt);
                 if (coef) {
                     dr[g] = c * gm;
                     dr[X + g] = c * gt;
@@ -1970,6 +2007,12 @@ __global__ __launch_bounds__(1024) void batch_masks_kernel(MaskArgs a) { batch_m
 // the HBM-resident dataset straight into the step's input rows ([x1 rows ; x2 rows of the pairs],
 // + training noise), and the label-dependent index buffers of the step are refreshed, in ONE
 // launch whose arguments never change -- so the whole epoch is replays of one captured graph.
+// SPLIT (dv_batch_feed_desc.xt given: raw-count inputs): the wave that owns row r also writes the RAW row to xt[r,:] -- the
+// reconstruction target, without noise -- and the encoder's row becomes T(x) + sigma*noise, T = log1p with `transform` == 1.
+// A compile-time variant: the default launch keeps its instruction stream (it heads the step's critical path)
+__device__ __forceinline__ float feed_T(int transform, float x) { return transform ? log1pf(x) : x; }
+
+template <bool SPLIT>
 __global__ __launch_bounds__(256) void batch_feed_kernel(
     const float* __restrict__ x1, int64_t ld1, const float* __restrict__ x2, int64_t ld2,
     const int32_t* __restrict__ y, const int32_t* __restrict__ table, int n_batches,
@@ -1979,7 +2022,7 @@ __global__ __launch_bounds__(256) void batch_feed_kernel(
     const int32_t* __restrict__ fp_lab, const int32_t* __restrict__ fp_slot, int Mf, int32_t* __restrict__ fp_cls,
     float* __restrict__ onehot, int64_t ldh, int Y, int row_blocks, int vec4, const float* __restrict__ yf,
     float* __restrict__ ylab, int Yc, float* __restrict__ onehot2, int64_t ldh2, int mask_block, MaskArgs masks,
-    ParkArgs park) {
+    ParkArgs park, float* __restrict__ xt, int64_t ldt, int transform) {
     park_block(park);
     if ((int)blockIdx.x == mask_block) {        // (batch-independent plan: the batch's masks ride on this launch)
         batch_masks_body(masks);
@@ -1995,6 +2038,8 @@ __global__ __launch_bounds__(256) void batch_feed_kernel(
         const float* src = r < B ? x1 + (int64_t)tb[r] * ld1 : x2 + (int64_t)tb[pair_rows[r - B]] * ld2;
         const float* nz = noise ? noise + (int64_t)r * ldn : nullptr;
         float* dst = xin + (int64_t)r * ldo;
+        float* raw = nullptr;
+        if constexpr (SPLIT) raw = xt + (int64_t)r * ldt;
         if (vec4) {
             // (a wave per row: four 16-B groups per lane in flight at a time -- a 978-gene row is ONE round trip of loads,
             // not four load -> store iterations; this launch is the head of the step's critical path)
@@ -2010,12 +2055,31 @@ __global__ __launch_bounds__(256) void batch_feed_kernel(
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int q = q0 + lane + 64 * u;
+                    if constexpr (SPLIT) {
+                        if (q < X4) reinterpret_cast<float4*>(raw)[q] = v[u];
+                        v[u] = make_float4(feed_T(transform, v[u].x), feed_T(transform, v[u].y), feed_T(transform, v[u].z),
+                                           feed_T(transform, v[u].w));
+                    }
                     if (q < X4)
                         reinterpret_cast<float4*>(dst)[q] = make_float4(fmaf(sigma, e[u].x, v[u].x), fmaf(sigma, e[u].y, v[u].y),
                                                                         fmaf(sigma, e[u].z, v[u].z), fmaf(sigma, e[u].w, v[u].w));
                 }
             }
-            for (int g = (X & ~3) + lane; g < X; g += 64) dst[g] = nz ? fmaf(sigma, nz[g], src[g]) : src[g];
+            if constexpr (SPLIT) {
+                for (int g = (X & ~3) + lane; g < X; g += 64) {
+                    const float xv = src[g], tv = feed_T(transform, xv);
+                    raw[g] = xv;
+                    dst[g] = nz ? fmaf(sigma, nz[g], tv) : tv;
+                }
+            } else {
+                for (int g = (X & ~3) + lane; g < X; g += 64) dst[g] = nz ? fmaf(sigma, nz[g], src[g]) : src[g];
+            }
+        } else if constexpr (SPLIT) {
+            for (int g = lane; g < X; g += 64) {
+                const float xv = src[g], tv = feed_T(transform, xv);
+                raw[g] = xv;
+                dst[g] = nz ? fmaf(sigma, nz[g], tv) : tv;
+            }
         } else {
             for (int g = lane; g < X; g += 64) dst[g] = nz ? fmaf(sigma, nz[g], src[g]) : src[g];
         }
@@ -3126,27 +3190,43 @@ extern "C" int dv_gauss_nll_rows_raw_cs(const dv_nll_raw_cs_desc* dsc, dv_stream
 extern "C" int dv_nll_raw_cs_chunks(int32_t X) { return X < 4 ? 0 : ((X >> 2) + 255) / 256; }
 extern "C" int dv_nll_raw_cs_row_blocks(int32_t M) { return M <= 0 ? 0 : (M + kNllCsRows - 1) / kNllCsRows; }
 
+template <bool LIB>
+static void launch_rec_nll_rows(bool nb, bool vec, int kind, float shift, const float* coef, const float* x, int64_t ldx,
+                                const int32_t* xidx, const float* v, int64_t ldv, int M, int X, float* out, float* dpre,
+                                int64_t ldd, dv_stream_t stream) {
+    const dim3 grid(grid_for(M, 1, 4096)), block(256);
+    if (!nb)
+        hipLaunchKernelGGL(rec_nll_rows_kernel<LIB>, grid, block, 0, ST(stream), kind, shift, coef, x, ldx, xidx, v, ldv, M,
+                           X, out, dpre, ldd);
+    else if (vec)
+        hipLaunchKernelGGL((nb_nll_rows_kernel<true, LIB>), grid, block, 0, ST(stream), shift, coef, x, ldx, xidx, v, ldv,
+                           M, X, out, dpre, ldd);
+    else
+        hipLaunchKernelGGL((nb_nll_rows_kernel<false, LIB>), grid, block, 0, ST(stream), shift, coef, x, ldx, xidx, v, ldv,
+                           M, X, out, dpre, ldd);
+}
+
 extern "C" int dv_rec_nll_rows(int32_t kind, float shift, const float* coef, const float* x, int64_t ldx,
                                const int32_t* xidx, const float* v, int64_t ldv, int32_t M, int32_t X, float* out,
                                float* dpre, int64_t ldd, dv_stream_t stream) {
-    DV_REQUIRE(M >= 0 && X >= 1 && (kind == DV_REC_BERNOULLI || kind == DV_REC_POISSON || kind == DV_REC_NEGBIN));
+    DV_REQUIRE(M >= 0 && X >= 1 && kind >= DV_REC_BERNOULLI && kind <= DV_REC_NEGBIN_LIB);
     if (M == 0) return DV_OK;
     DV_REQUIRE(x && v && out && (coef == nullptr || dpre != nullptr));
-    if (kind == DV_REC_NEGBIN) {      // v = [mu | theta], dpre = [d/da_m | d/da_t]: 2X columns each, a kernel of its own
+    // the library-scaled kinds: the unscaled kind's kernel, compiled with the size-factor sweep in front of its term loop
+    const bool lib = kind == DV_REC_POISSON_LIB || kind == DV_REC_NEGBIN_LIB;
+    const bool nb = kind == DV_REC_NEGBIN || kind == DV_REC_NEGBIN_LIB;
+    bool vec = false;
+    if (nb) {      // v = [mu | theta], dpre = [d/da_m | d/da_t]: 2X columns each, a kernel of its own
         DV_REQUIRE(ldv >= 2 * (int64_t)X && (coef == nullptr || ldd >= 2 * (int64_t)X));
         auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-        const bool vec = X % 4 == 0 && a16(x) && a16(v) && ldx % 4 == 0 && ldv % 4 == 0 &&
-                         (coef == nullptr || (a16(dpre) && ldd % 4 == 0));
-        if (vec)
-            hipLaunchKernelGGL(nb_nll_rows_kernel<true>, dim3(grid_for(M, 1, 4096)), dim3(256), 0, ST(stream), shift, coef,
-                               x, ldx, xidx, v, ldv, M, X, out, dpre, ldd);
-        else
-            hipLaunchKernelGGL(nb_nll_rows_kernel<false>, dim3(grid_for(M, 1, 4096)), dim3(256), 0, ST(stream), shift,
-                               coef, x, ldx, xidx, v, ldv, M, X, out, dpre, ldd);
-        DV_RETURN_LAUNCH();
+        vec = X % 4 == 0 && a16(x) && a16(v) && ldx % 4 == 0 && ldv % 4 == 0 &&
+              (coef == nullptr || (a16(dpre) && ldd % 4 == 0));
     }
-    hipLaunchKernelGGL(rec_nll_rows_kernel, dim3(grid_for(M, 1, 4096)), dim3(256), 0, ST(stream), kind, shift, coef, x,
-                       ldx, xidx, v, ldv, M, X, out, dpre, ldd);
+    const int k = kind == DV_REC_POISSON_LIB ? DV_REC_POISSON : kind;
+    if (lib)
+        launch_rec_nll_rows<true>(nb, vec, k, shift, coef, x, ldx, xidx, v, ldv, M, X, out, dpre, ldd, stream);
+    else
+        launch_rec_nll_rows<false>(nb, vec, k, shift, coef, x, ldx, xidx, v, ldv, M, X, out, dpre, ldd, stream);
     DV_RETURN_LAUNCH();
 }
 
@@ -3434,12 +3514,16 @@ extern "C" int dv_batch_feed(const dv_batch_feed_desc* dsc, const dv_batch_masks
     DV_REQUIRE(d.x1 && d.table && d.ctr && d.base && d.xin && (Np == 0 || (d.x2 && d.pair_rows)));
     DV_REQUIRE(!d.label_r || (d.y && d.has_y));
     DV_REQUIRE(!d.fp_cls || Mf == 0 || (d.y && d.fp_i && d.fp_lab && d.fp_slot));
+    // split form (raw-count inputs): targets to xt, encoder rows T(x) + sigma*noise to xin
+    DV_REQUIRE((d.transform == 0 || d.transform == 1) && (d.transform == 0 || d.xt != nullptr));
+    DV_REQUIRE(d.xt == nullptr || (aligned16(d.xt) && d.ldt >= d.X));
     const int row_blocks = (B + Np + 3) / 4;
     int nlab = (d.label_r ? L * B : 0) > (d.fp_cls ? Mf : 0) ? (d.label_r ? L * B : 0) : (d.fp_cls ? Mf : 0);
     if (d.ylab && B * d.Yc > nlab) nlab = B * d.Yc;
     const int lab_blocks = (nlab + 255) / 256;
     const bool v4 = aligned16(d.x1) && (Np == 0 || aligned16(d.x2)) && aligned16(d.xin) && (!d.noise || aligned16(d.noise)) &&
-                    d.ld1 % 4 == 0 && (Np == 0 || d.ld2 % 4 == 0) && d.ldo % 4 == 0 && (!d.noise || d.ldn % 4 == 0);
+                    d.ld1 % 4 == 0 && (Np == 0 || d.ld2 % 4 == 0) && d.ldo % 4 == 0 && (!d.noise || d.ldn % 4 == 0) &&
+                    (!d.xt || d.ldt % 4 == 0);
     MaskArgs ma{};
     if (masks) {
         DV_REQUIRE(masks_ok(*masks, B));
@@ -3448,11 +3532,18 @@ extern "C" int dv_batch_feed(const dv_batch_feed_desc* dsc, const dv_batch_masks
     const int feed_blocks = row_blocks + lab_blocks;
     ParkArgs park;
     if (int rc = take_park(park_in, feed_blocks + 1, &park)) return rc;
-    hipLaunchKernelGGL(batch_feed_kernel, dim3(feed_blocks + (masks ? 1 : 0)), dim3(256), 0, ST(stream), d.x1, d.ld1, d.x2,
-                       d.ld2, d.y, d.table, d.n_batches, d.ctr, d.base, B, d.pair_rows, Np, d.X, d.noise, d.ldn, d.sigma,
-                       d.xin, d.ldo, d.has_y, L, d.label_r, d.fp_i, d.fp_lab, d.fp_slot, Mf, d.fp_cls, d.onehot, d.ldh,
-                       d.Y, row_blocks, v4 ? 1 : 0, d.yf, d.ylab, d.Yc, d.onehot2, d.ldh2, masks ? feed_blocks : -1, ma,
-                       park);
+    const dim3 grid(feed_blocks + (masks ? 1 : 0)), block(256);
+    const int mask_block = masks ? feed_blocks : -1;
+    // (ONE list of the common arguments: the two variants differ in the three of the descriptor's tail)
+#define DV_FEED_ARGS                                                                                                       \
+    d.x1, d.ld1, d.x2, d.ld2, d.y, d.table, d.n_batches, d.ctr, d.base, B, d.pair_rows, Np, d.X, d.noise, d.ldn, d.sigma,  \
+        d.xin, d.ldo, d.has_y, L, d.label_r, d.fp_i, d.fp_lab, d.fp_slot, Mf, d.fp_cls, d.onehot, d.ldh, d.Y, row_blocks,  \
+        v4 ? 1 : 0, d.yf, d.ylab, d.Yc, d.onehot2, d.ldh2, mask_block, ma, park
+    if (d.xt)
+        hipLaunchKernelGGL(batch_feed_kernel<true>, grid, block, 0, ST(stream), DV_FEED_ARGS, d.xt, d.ldt, d.transform);
+    else
+        hipLaunchKernelGGL(batch_feed_kernel<false>, grid, block, 0, ST(stream), DV_FEED_ARGS, nullptr, 0, 0);
+#undef DV_FEED_ARGS
     DV_RETURN_LAUNCH();
 }
 

@@ -112,6 +112,24 @@ def compute_balanced_weights(labels, unlabeled_data_ratio=None, unlabeled_token=
 _GROUPS = ((1, 0), (0, 0), (1, 1), (0, 1))      # (has_y, has_x2) in the reference's order ls, us, lp, up
 
 
+def require_counts(ds, what):
+    """the precondition of the raw-count switches (``x_transform`` / ``library_size``): every entry of the dataset's ``x1`` /
+    ``x2`` is >= 0.  One reduction per dataset (remembered on it), outside any step; ValueError otherwise"""
+    if getattr(ds, '_counts_checked', False):
+        return
+    for name in ('x1', 'x2'):
+        x = getattr(ds, name, None)
+        if x is None or not len(x):
+            continue
+        lo = float(torch.as_tensor(x).min())
+        if not lo >= 0.0:      # (NaN fails this too)
+            raise ValueError('%s: x_transform / library_size need count data, x >= 0; the minimum of %s is %r' % (what, name, lo))
+    try:
+        ds._counts_checked = True
+    except AttributeError:
+        pass
+
+
 class DeviceBatcher:
     """Stratified, weighted, with-replacement minibatches drawn ON the device and written
     straight into the fused step's input buffers (see the module docstring)."""
@@ -243,6 +261,8 @@ class DeviceBatcher:
             if dp is not None:
                 engine.row0 = dp[0] * self.batch_size
             return engine.plan          # (every epoch of ``fit`` binds: nothing to rebuild)
+        if engine.cfg.split_x:      # raw-count inputs: log1p and the size factor want x >= 0 (checked once per dataset, here)
+            require_counts(self.dataset, 'DeviceBatcher.bind')
         self.engine = engine
         self.dp = dp
         assert self.dp is None or 0 <= self.dp[0] < self.dp[1]

@@ -14,6 +14,7 @@ Restructuring relative to the reference (arithmetic identical):
 
 Row layout (B rows, Np pairs, L samples):
   XIN  [B + Np]            noisy x1 rows, then noisy x2 rows of the pairs    (src/DrVAE.py:404-418)
+  XT   [B + Np]            (raw-count inputs only) the RAW rows: the reconstruction targets, XIN then holds T(x) + noise
   Q    [B + Np, 2 Z1]      (mu | logvar) of q(z1|x1) and q(z2|x2)            (shared encoder, src/DrVAE.py:418)
   ZDEC [L B + 2 L Np, Z1]  z1 samples | z2 samples (from qz1: src/DrVAE.py:427) | z2Fz1 samples of pairs
   fprop rows               per (l, row): 1 row if labeled else Y rows        (src/DrVAE.py:503-526)
@@ -127,8 +128,18 @@ class StepConfig:
     # (``ParamArena.avg``, ``dv_adam_hyper.avg``).  None: nothing of this exists -- no buffer, no launch
     # argument, the step as it ever was.  ``optim_alg='adamw'`` is Adam with torch.optim.AdamW's decoupled weight decay
     ema_decay: Optional[float] = None
+    # EXTENSIONS (no counterpart in the reference) for RAW COUNTS, count decoders ('poisson' / 'nb') only; x >= 0:
+    #   x_transform='log1p': the encoder reads log1p(x) + sigma * eps; the reconstruction target stays the raw row x, no noise
+    #   library_size=True  : every decoder mean of a row is multiplied by the observed size factor of its target row,
+    #                        s = max(sum_g x_g, 1) / dim_x -- mu = s * (softplus(a_m) + 1e-6); the NB's theta is untouched
+    # Either on: SPLIT MODE -- the plan holds the raw target rows in a buffer of their own (``_Plan.XT``), the input launch is
+    # ``dv_batch_feed`` in its split form on every path.  Both off: nothing of this exists, the step as it ever was
+    x_transform: Optional[str] = None
+    library_size: bool = False
 
     def __post_init__(self):
+        check_counts_config(self.x_transform, self.library_size, self.type_rec, 'StepConfig.')
+        self.library_size = bool(self.library_size)
         if self.optim_alg not in OPTIM_ALGS:
             raise ValueError('StepConfig.optim_alg must be one of %s, not %r' % (OPTIM_ALGS, self.optim_alg))
         self.ema_decay = check_ema_decay(self.ema_decay, 'StepConfig.ema_decay')
@@ -155,6 +166,11 @@ class StepConfig:
         return bool(self.anneal_kl or (self.anneal_yloss and self.has_y) or self.anneal_learning_rate)
 
     @property
+    def split_x(self):
+        """are the encoder's rows and the reconstruction targets two buffers?  (raw-count inputs)"""
+        return bool(self.x_transform is not None or self.library_size)
+
+    @property
     def cont(self):
         return self.type_y == 'cont'
 
@@ -169,6 +185,22 @@ class StepConfig:
     @property
     def has_y(self):
         return self.kind in ('drvae', 'vfae')
+
+
+X_TRANSFORMS = (None, 'log1p')
+COUNT_DECODERS = ('poisson', 'nb')
+
+
+def check_counts_config(x_transform, library_size, type_rec, prefix=''):
+    """the raw-count switches as ``StepConfig`` keyword arguments; ValueError for an unknown ``x_transform`` and for either
+    switch on a decoder that is no count decoder"""
+    if x_transform not in X_TRANSFORMS:
+        raise ValueError("%sx_transform must be None or 'log1p', not %r" % (prefix, x_transform))
+    on = [n for n, v in (('x_transform', x_transform is not None), ('library_size', bool(library_size))) if v]
+    if on and type_rec not in COUNT_DECODERS:
+        raise ValueError("%s%s is for the count decoders (type_rec='poisson' / 'nb'), not type_rec=%r"
+                         % (prefix, ' / '.join(on), type_rec))
+    return dict(x_transform=x_transform, library_size=bool(library_size))
 
 
 def check_ema_decay(d, what='ema_decay'):
@@ -807,6 +839,7 @@ class FusedStep(StepSchedule):
             # (universal plan: dv_batch_masks has the labels; its rows with ONE fprop row get their class columns here)
             lab = cfg.has_y and not cfg.cont and (not p.universal or p.one_slot is not None)
             K.batch_feed(p.XIN, fd.x1, fd.x2, fd.y32, fd.table, fd.n_batches, self.step_dev, fd.base, park=start_park,
+                         **self._split_args(p),
                          pair_rows=p.pair_idx if Np else None, noise=p.EX if sigma else None, sigma=sigma,
                          has_y=p.has_y_i32 if (lab and not p.universal) else None, L=L,
                          label_r=p.label_r if (lab and not p.universal) else None,
@@ -822,6 +855,13 @@ class FusedStep(StepSchedule):
                 assert p.carry_s and getattr(fd, 's32', None) is not None, 'use_s: this feed does not carry the nuisance classes'
                 K.nuisance_feed(p.SOHe, p.SOHd, p.s_cls, fd.s32, table=fd.table, n_batches=fd.n_batches, ctr=self.step_dev,
                                 base=fd.base, pair_rows=p.pair_idx if Np else None, L=L)
+        elif cfg.split_x:
+            # raw-count inputs, explicit batch: the SAME launch as the graph-resident feed (targets to XT, encoder rows to XIN)
+            # over the plan's own one-batch identity table and zero counters -- x1 = XSRC[:B], x2 = XSRC[B:]; no label
+            # outputs, the masks stay with ``dv_batch_masks`` above.  Host-fed and feed steps agree bit for bit
+            K.batch_feed(p.XIN, p.XSRC[:B], p.XSRC[B:], None, p.id_table, 1, p.id_zero, p.id_zero, park=start_park,
+                         pair_rows=p.pair_idx if Np else None, noise=p.EX if sigma else None, sigma=sigma, L=L,
+                         **self._split_args(p))
         else:
             K.rows_gather(p.XIN, p.XSRC, p.xin_idx, noise=p.EX if sigma else None, sigma=sigma, park=start_park)
         # ---- q(z1|x1), q(z2|x2): one pass of the shared encoder; the samples (src/blocks.py:170-174) -- z1
@@ -855,6 +895,14 @@ class FusedStep(StepSchedule):
                               out3=p.ZDEC if Np else None, out3_idx=p.pert_out_idx if Np else None)
         return Qmu, Qlv
 
+    def _lib_kw(self):
+        """``library=True`` for the reconstruction rows of a ``library_size`` model; no keyword otherwise (the call as it was)"""
+        return dict(library=True) if self.cfg.library_size else {}
+
+    def _split_args(self, p):
+        """the split-form keywords of ``kernels.batch_feed`` for plan ``p`` (raw-count inputs); none with both switches off"""
+        return dict(xt=p.XT, transform=self.cfg.x_transform) if self.cfg.split_x else {}
+
     def _decoder_forward(self, r, pub=None):
         """p(x|z): the decoder over all stacked sample rows, then the NLL over genes by the launch ``r.nll`` names (``heads_route``:
         in a latency-bound train step the heads' launch itself, ``dv_gemm_heads``); ``pub``: published on entry of the first launch"""
@@ -874,8 +922,8 @@ class FusedStep(StepSchedule):
             self.branch.fork()
         lh = p.c_decx.layers[-1]
         if r.nll == 'rec':     # Bernoulli / Poisson / negative-binomial rows (+ the gradient w.r.t. the head's pre-activation in a train step)
-            K.rec_nll_rows(p.NLL, p.XIN, PX, kind=cfg.type_rec, shift=REC_ACT[cfg.type_rec][1], xidx=p.tgt,
-                           coef=p.c_nll if train else None, dpre=p.DPX if train else None)
+            K.rec_nll_rows(p.NLL, p.XT if cfg.split_x else p.XIN, PX, kind=cfg.type_rec, shift=REC_ACT[cfg.type_rec][1],
+                           xidx=p.tgt, coef=p.c_nll if train else None, dpre=p.DPX if train else None, **self._lib_kw())
         elif r.nll in ('raw_cs', 'raw_cs_eval'):
             # the row terms from the raw heads (bias + softplus + shift applied by the pass); train step: and the gradients,
             # the heads' bias gradient with them (column sums of the gradients this pass writes: no second pass over them)
@@ -1193,8 +1241,8 @@ class FusedStep(StepSchedule):
         # coefficients, then back through the decoder (the three big GEMMs)
         PX = p.c_decx.out[-1]
         if not self.fuse_bwd and cfg.type_rec != 'diag_gaussian':
-            K.rec_nll_rows(p.NLL, p.XIN, PX, kind=cfg.type_rec, shift=REC_ACT[cfg.type_rec][1], xidx=p.tgt, coef=p.c_nll,
-                           dpre=p.DPX)
+            K.rec_nll_rows(p.NLL, p.XT if cfg.split_x else p.XIN, PX, kind=cfg.type_rec, shift=REC_ACT[cfg.type_rec][1],
+                           xidx=p.tgt, coef=p.c_nll, dpre=p.DPX, **self._lib_kw())
         elif not self.fuse_bwd:
             K.nll_rows_bwd(p.DPX[:, :X], p.DPX[:, X:], p.c_nll, p.XIN, PX[:, :X], PX[:, X:], mode=GAUSS_SIGMA,
                            xidx=p.tgt, sd_act='softplus', sd_shift=1e-3)

@@ -370,7 +370,11 @@ class FitMixin:
             model_filename='best_model.pth'):
         """Train for ``self.epochs`` epochs with the reference's validation / early-stopping /
         snapshot protocol (signature and log lines of src/DrVAE.py:743)."""
-        from .data import DeviceBatcher
+        from .data import DeviceBatcher, require_counts
+        if getattr(self, 'x_transform', None) is not None or getattr(self, 'library_size', False):
+            for ld in (train_loader, valid_loader):      # raw-count inputs: x >= 0, checked once, outside the step
+                if getattr(ld, 'dataset', None) is not None:
+                    require_counts(ld.dataset, 'fit')
         np.set_printoptions(precision=4)
         ctl = EarlyStopping(self.epochs, early_stop, patience=self.fit_patience)
         self.w2log('Starting training at: {}'.format(time.strftime('%c')))

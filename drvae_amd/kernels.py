@@ -586,13 +586,18 @@ def nll_rows_raw_cs(out_part, dmu, dsd, ws, coef, x, mu, sd, bias, *, xidx=None,
     _lib.check(_lib.load().dv_gauss_nll_rows_raw_cs(C.byref(d), _stream()), 'dv_gauss_nll_rows_raw_cs')
 
 
-def rec_nll_rows(out, x, v, *, kind, shift=0.0, xidx=None, coef=None, dpre=None):
+def rec_nll_rows(out, x, v, *, kind, shift=0.0, xidx=None, coef=None, dpre=None, library=False):
     """log-likelihood rows of the Bernoulli ('binary') / Poisson decoders from the head's post-activation output
     ``v``; with ``coef`` also the gradient w.r.t. the head's pre-activation (``dv_rec_nll_rows``).  ``kind='nb'`` (negative
     binomial): ``v`` = [mu | theta] and ``dpre`` = [d/da_m | d/da_t], 2X columns each; ``shift`` is the mean's, theta's is
-    ``DV_NB_THETA_SHIFT``"""
+    ``DV_NB_THETA_SHIFT``.  ``library`` ('poisson' / 'nb' only): the library-scaled kind -- the mean of row r is
+    s * v with s = max(sum_g x[xidx[r], g], 1) / X, the size factor the kernel forms from the target row it reads"""
     M, X = v.shape
-    if kind == 'nb':
+    if library:
+        if kind not in ('poisson', 'nb'):
+            raise ValueError("rec_nll_rows: library= is for kind 'poisson' / 'nb', not %r" % (kind,))
+        kind = kind + '_lib'
+    if kind in ('nb', 'nb_lib'):
         X = x.shape[1]
         assert v.shape[1] == 2 * X and (dpre is None or tuple(dpre.shape) == (M, 2 * X))
     _lib.check(_lib.load().dv_rec_nll_rows(_lib.REC_KIND[kind], shift, _f32(coef), _f32(x), _ld(x), _i32(xidx), _f32(v),
@@ -962,11 +967,15 @@ def _masks_desc(m, B):
     return md
 
 
+FEED_TRANSFORM = {None: 0, 'log1p': 1}      # dv_batch_feed_desc.transform
+
+
 def batch_feed(xin, x1, x2, y32, table, n_batches, ctr, base, *, pair_rows=None, noise=None, sigma=0.0, has_y=None,
                L=1, label_r=None, fp_i=None, fp_lab=None, fp_slot=None, fp_cls=None, onehot=None, n_classes=0, yf=None,
-               ylab=None, onehot2=None, masks=None, park=None):
+               ylab=None, onehot2=None, masks=None, park=None, xt=None, transform=None):
     """graph-resident minibatch feed: see dv_batch_feed in include/drvae_hip.h; ``masks``: keyword arguments of
-    ``batch_masks`` (minus table / ctr / base / B / L): the batch's masks written by the same launch"""
+    ``batch_masks`` (minus table / ctr / base / B / L): the batch's masks written by the same launch.  ``xt`` (split form,
+    raw-count inputs): the raw rows go to ``xt`` and ``xin`` gets T(x) + sigma * noise, T = log1p with ``transform='log1p'``"""
     B = table.shape[1]
     md = _masks_desc(masks, B) if masks is not None else None
     assert masks is None or masks.get('gcounts') is None or masks['gcounts'].shape[0] == n_batches
@@ -980,6 +989,9 @@ def batch_feed(xin, x1, x2, y32, table, n_batches, ctr, base, *, pair_rows=None,
                        fp_lab=_i32(fp_lab), fp_slot=_i32(fp_slot), Mf=Mf, fp_cls=_i32(fp_cls), onehot=_f32(onehot),
                        ldh=_ld(onehot), Y=n_classes, yf=_f32(yf), ylab=_f32(ylab),
                        Yc=ylab.shape[1] if ylab is not None else 0, onehot2=_f32(onehot2), ldh2=_ld(onehot2))
+    if xt is not None or transform is not None:
+        assert xt is None or tuple(xt.shape) == tuple(xin.shape)
+        d.xt, d.ldt, d.transform = _f32(xt), _ld(xt), FEED_TRANSFORM[transform]
     _lib.check(_lib.load().dv_batch_feed(C.byref(d), C.byref(md) if md is not None else None, _wait(park), _stream()),
                'dv_batch_feed')
 

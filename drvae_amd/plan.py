@@ -173,6 +173,13 @@ class _Plan:
         self.noise_desc = self.noise_table[:-1]
         # ---- activations / gradients
         self.XIN = mat(Me, X)
+        if cfg.split_x:
+            # raw-count inputs (``StepConfig.x_transform`` / ``library_size``): XIN holds the encoder's rows, XT the RAW target
+            # rows every reconstruction term reads (same shape, same ``tgt``); an explicit batch goes through the feed's launch
+            # too, over a one-batch identity table and zero counters of the plan's own
+            self.XT = mat(Me, X)
+            self.id_table = i32(np.arange(B)[None, :])
+            self.id_zero = i32(np.zeros(1))
         self.ZDEC, self.DZDEC = mat(Md, Z1), mat(Md, Z1)
         self.c_enc = self._sited('c_enc', _Chain(eng.L_enc, Me, dev))
         self.c_decx = self._sited('c_decx', _Chain(eng.L_decx, Md, dev))

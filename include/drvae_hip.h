@@ -534,8 +534,18 @@ int dv_gauss_nll_rows_bwd(const float* coef, const float* x, int64_t ldx, const 
  *   d/dmu    = x/mu - (x+theta)/(theta+mu);   d/dtheta = [psi(x+theta) - psi(theta)] + log(theta/(theta+mu)) + (mu-x)/(theta+mu)
  *   d/da_*   = d/d(mu, theta) * (1 - exp(-(v - its shift)))
  * The lgamma / digamma pairs and the two log ratios are formed as differences (recurrence + asymptotic series, log1p),
- * never as two large values subtracted: the x = 0 pair is exactly 0, and theta -> inf is the Poisson term. */
-enum { DV_REC_BERNOULLI = 0, DV_REC_POISSON = 1, DV_REC_NEGBIN = 2 };
+ * never as two large values subtracted: the x = 0 pair is exactly 0, and theta -> inf is the Poisson term.
+ * EXTENSION (`library_size=True`): POISSON_LIB / NEGBIN_LIB, the same rows with every mean of row r multiplied by the observed
+ * size factor of its target row, s = max(sum_g x[xrow,g], 1) / X; v still holds the UNSCALED heads, m = s v:
+ *   POISSON_LIB: log p = x log m - m - lgamma(x+1);  d/da = (x/v - s) (1 - exp(-(v - shift)))
+ *   NEGBIN_LIB : log p as NEGBIN at m;  d/da_m = (x - m) / (v (1 + m/theta)) (1 - exp(-(v - shift)))  (the slope is the
+ *                unscaled head's);  d/da_t as NEGBIN, at m; theta is not scaled
+ * Same signature, same layouts.  The workgroup that owns row r forms s itself in a first sweep over the target row (fixed
+ * order: per-thread partials in index order, the wave sum, the four waves as (p0 + p1) + (p2 + p3)); the term loop's second
+ * read of the row comes from cache.  For integer counts with a row total below 2^24 every partial sum is exact in fp32 in
+ * any order, so s is ONE correctly rounded quotient on every path; a row whose total is X (s = 1) gives the unscaled
+ * kind's output bit for bit. */
+enum { DV_REC_BERNOULLI = 0, DV_REC_POISSON = 1, DV_REC_NEGBIN = 2, DV_REC_POISSON_LIB = 3, DV_REC_NEGBIN_LIB = 4 };
 #define DV_NB_THETA_SHIFT 1e-3f     /* the shift of the NEGBIN theta head (that of the Gaussian decoder's sigma head) */
 int dv_rec_nll_rows(int32_t kind, float shift, const float* coef, const float* x, int64_t ldx, const int32_t* xidx,
                     const float* v, int64_t ldv, int32_t M, int32_t X, float* out, float* dpre, int64_t ldd,
@@ -712,6 +722,14 @@ int dv_rows_gather(const float* src, int64_t lds, const int32_t* idx, int32_t n,
  * constant and the launch can live inside the captured train-step graph. */
 /* `masks` (optional): the per-batch masks of a batch-independent plan (dv_batch_masks below, same table / ctr / base /
  * B / L) written by one more workgroup of this launch instead of a launch of their own. */
+/* split form (raw-count inputs; `xt` != NULL, trailing fields of the descriptor): the wave that owns row r also writes the
+ * RAW row to xt[r,:] (ldt >= X) -- the reconstruction target, without noise -- and xin[r,:] = T(x) + sigma*noise[r] as one
+ * fmaf, T = log1p with `transform` == 1 (0: identity).  A compile-time variant of the kernel; with xt == NULL the launch is
+ * what it was.  DV_ERR_ARG: `transform` outside {0, 1}, `transform` != 0 without xt, xt not 16-byte aligned.  The step's
+ * explicit-batch path runs this form too, over a one-batch identity table with ctr = base = a zero word, x1 / x2 = the two
+ * halves of the plan's source rows and no label outputs (y, has_y, label_r, fp_* all NULL: the argument checks never
+ * required them without label outputs, so none had to be relaxed), so host-fed and graph-resident steps form their inputs
+ * with one kernel and agree bit for bit. */
 /* `park` (optional): the launch first parks like dv_flag_wait -- the first launch of a step waiting for the previous
  * step's other launch chain (DV_ERR_UNSUPPORTED for grids above DV_MAX_PARKED_GRID workgroups). */
 typedef struct dv_batch_masks_desc {
@@ -783,6 +801,10 @@ typedef struct dv_batch_feed_desc {
     int32_t Yc;
     float* onehot2;
     int64_t ldh2;
+    /* split form (trailing fields; xt == NULL: the launch as it was) -- see "split form" above */
+    float* xt;
+    int64_t ldt;
+    int32_t transform;
 } dv_batch_feed_desc;
 int dv_batch_feed(const dv_batch_feed_desc* d, const dv_batch_masks_desc* masks, const dv_wait* park,
                   dv_stream_t stream);
