@@ -21,6 +21,7 @@
 //   T128: 128x128x32 tile, 2x2 waves, 2x2 accumulators each          (wide config)
 #include "gemm_common.inc"
 #include "heads_route.h"
+#include "ring_route.h"
 
 namespace {
 
@@ -1021,6 +1022,15 @@ int launch_kpipe(const dv_gemm_desc& g_in, const LoadCfg& lc, hipStream_t st) {
     DV_RETURN_LAUNCH();
 }
 
+// the latency-bound 32 x 32 x 64 launches on a ring of `depth` slots (ring_route.h): the same kernel, the same bits.  The
+// register budget follows what LDS leaves room for: a four-wave workgroup with three / four slots fits a CU three / two times
+template <int KS>
+int launch_kpipe_ring(int depth, const dv_gemm_desc& g, const LoadCfg& lc, hipStream_t st) {
+    if (depth == 4) return launch_kpipe<32, 32, 64, KS, 4, 2>(g, lc, st);
+    if (depth == 3) return launch_kpipe<32, 32, 64, KS, 3, KS == 8 ? 2 : 3>(g, lc, st);
+    return launch_kpipe<32, 32, 64, KS, 2, KS == 8 ? 2 : 4>(g, lc, st);
+}
+
 }  // namespace
 
 // which tilings this build of the library carries (tests / tuning: dv_gemm_tune.tiling); the lab tilings exist in the
@@ -1225,8 +1235,11 @@ static int gemm_launch(const dv_gemm_desc& g_in, const LoadCfg& lc, int tiling, 
     // each of the three on the hand-pipelined LDS-DMA loop where the operands allow it (pipe_ok; dv_gemm_set_option(3, -1): never)
     const bool pipe = pipe_on(g) && pipe_ok(g, lc);
     if (tiles32 >= dense_min_tiles(g)) return pipe ? launch_kpipe<32, 32, 32, 4, 2, DV_DENSE_WG>(g, lc, st) : launch_cfg<32, 32, 32, 1, 1, 4>(g, lc, st);
-    if (g.a_kcontig && tune_of(g).opt[7] == 0) return pipe ? launch_kpipe<32, 32, 64, 8, 2, 2>(g, lc, st) : launch_cfg<32, 32, 64, 1, 1, 8>(g, lc, st);
-    return pipe ? launch_kpipe<32, 32, 64, 4, 2, 4>(g, lc, st) : launch_cfg<32, 32, 64, 1, 1, 4>(g, lc, st);
+    // (the ring's depth: one rule, ring_route.h; dv_gemm_tune.opt[7] = 2 / 3 force four / three slots, 4 forbids them)
+    const int opt7 = tune_of(g).opt[7];
+    const int depth = dv_ring_depth(DV_RING_FAMILY_GEMM, tiles32, g.K, g.a_kcontig, g.b_kcontig, opt7);
+    if (g.a_kcontig && opt7 != DV_RING_OPT_FOUR_WAVE) return pipe ? launch_kpipe_ring<8>(depth, g, lc, st) : launch_cfg<32, 32, 64, 1, 1, 8>(g, lc, st);
+    return pipe ? launch_kpipe_ring<4>(depth, g, lc, st) : launch_cfg<32, 32, 64, 1, 1, 4>(g, lc, st);
 }
 
 // A chip-filling product on the 128x256 tiling whose N is no multiple of 256: the ragged last column of tiles costs
@@ -1350,8 +1363,16 @@ extern "C" int dv_gemm_heads(const dv_gemm_desc* d, const dv_heads_epi* e, dv_st
             hipLaunchKernelGGL((gemm_heads_kernel<32, 32, 32, 4>), dim3(tiles), dim3(256), 0,
                                static_cast<hipStream_t>(stream), g, lc, *e);
     } else if (pipe) {
-        hipLaunchKernelGGL((gemm_heads_pipe_kernel<32, 32, 64, 8, 2, 2>), dim3(tiles), dim3(512), 0,
-                           static_cast<hipStream_t>(stream), g, lc, *e);
+        const int depth = dv_ring_depth(DV_RING_FAMILY_HEADS, tiles, g.K, 1, 1, tune_of(g).opt[7]);
+        if (depth == 4)
+            hipLaunchKernelGGL((gemm_heads_pipe_kernel<32, 32, 64, 8, 4, 2>), dim3(tiles), dim3(512), 0,
+                               static_cast<hipStream_t>(stream), g, lc, *e);
+        else if (depth == 3)
+            hipLaunchKernelGGL((gemm_heads_pipe_kernel<32, 32, 64, 8, 3, 2>), dim3(tiles), dim3(512), 0,
+                               static_cast<hipStream_t>(stream), g, lc, *e);
+        else
+            hipLaunchKernelGGL((gemm_heads_pipe_kernel<32, 32, 64, 8, 2, 2>), dim3(tiles), dim3(512), 0,
+                               static_cast<hipStream_t>(stream), g, lc, *e);
     } else {  // default: the 32x32 tiling's eight-wave K split, B lines = 16 + 16 rows of the two heads
         hipLaunchKernelGGL((gemm_heads_kernel<32, 32, 64, 8>), dim3(tiles), dim3(512), lds_pad(g, 32, tiles),
                            static_cast<hipStream_t>(stream), g, lc, *e);
@@ -1418,10 +1439,18 @@ extern "C" int dv_gemm_pair(const dv_gemm_desc* d1, const dv_gemm_desc* d2, dv_s
         first.pub_ctr = d2->pub_ctr;
         first.pub_add = d2->pub_add;
     }
-    if (pipe)
-        hipLaunchKernelGGL((gemm_pair_pipe_kernel<32, 32, 64, 4, false, false, true, false, 2, 4>), dim3(tiles1 + tiles2),
-                           dim3(256), 0, st, first, lc1, e2, lc2, tiles1);
-    else
+    if (pipe) {
+        const int depth = dv_ring_depth(DV_RING_FAMILY_PAIR, tiles1 + tiles2, e1.K > e2.K ? e1.K : e2.K, 0, 0, tune_of(*d1).opt[7]);
+        if (depth == 4)
+            hipLaunchKernelGGL((gemm_pair_pipe_kernel<32, 32, 64, 4, false, false, true, false, 4, 2>), dim3(tiles1 + tiles2),
+                               dim3(256), 0, st, first, lc1, e2, lc2, tiles1);
+        else if (depth == 3)
+            hipLaunchKernelGGL((gemm_pair_pipe_kernel<32, 32, 64, 4, false, false, true, false, 3, 3>), dim3(tiles1 + tiles2),
+                               dim3(256), 0, st, first, lc1, e2, lc2, tiles1);
+        else
+            hipLaunchKernelGGL((gemm_pair_pipe_kernel<32, 32, 64, 4, false, false, true, false, 2, 4>), dim3(tiles1 + tiles2),
+                               dim3(256), 0, st, first, lc1, e2, lc2, tiles1);
+    } else
         hipLaunchKernelGGL((gemm_pair_kernel<32, 32, 64, 1, 1, 4, false, false, true, false>), dim3(tiles1 + tiles2),
                            dim3(256), 0, st, first, lc1, e2, lc2, tiles1);
     DV_RETURN_LAUNCH();

@@ -183,7 +183,10 @@ typedef struct dv_bump {
  * long K runs on 16 x (8 + 8) tiles, the same bits (csrc/heads_route.h) --, 3 = the seven-per-CU kernel at any size, 4 = the
  * 16-row tile wherever it can run (sample mode, operands fit for the LDS-DMA ring; otherwise as 0), 5 = never the 16-row
  * tile; opt[5] > 0 (opt-in, tuning): the 128x256 tiling's second resident workgroup of a CU starts that many percent of an estimated half tile late under a plain epilogue; opt[6] = -1: a chip-filling plain product with a ragged last column of
- * 128x256 tiles is NOT split into [full tiles | narrow rest] (dv_gemm: two launches where that saves a tile per CU); opt[7] = 1: four-wave K split for the k-contiguous layouts; opt[8]: tiles of
+ * 128x256 tiles is NOT split into [full tiles | narrow rest] (dv_gemm: two launches where that saves a tile per CU); opt[7]: the latency-bound 32x32x64 launches (dv_gemm, dv_gemm_heads, the fused dv_gemm_pair): 0 = the LDS-DMA ring's depth by rule --
+ * three slots of one 64-deep K tile for long reductions on grids of at most 192 workgroups, otherwise two; every depth stores the same
+ * bits (csrc/ring_route.h) --, 1 = four-wave K split for the k-contiguous layouts (ring of two), 2 = four ring slots wherever these
+ * kernels run, 3 = three slots, 4 = never a deeper ring (two slots everywhere); opt[8]: tiles of
  * 32x32 from which the seven-per-CU tiling runs; opt[9] = 1: chip-filling dW || dX as two launches */
 typedef struct dv_gemm_tune {
     int32_t tiling;
