@@ -478,9 +478,6 @@ def z2f_post_bwd(dp2, dz1, dq2, dz2f, dzdec_pert, pair_slot, eps, p2, q2, coef, 
     _lib.check(_lib.load().dv_z2f_post_bwd(C.byref(d), _wait(park), _stream()), 'dv_z2f_post_bwd')
 
 
-z2f_post_bwd.fold_rows = True       # (this launcher takes ``kl_out`` / ``seg``: read by ``schedule._step_tail``)
-
-
 # --------------------------------------------------------------------------- KL rows
 def _kl_desc(out, raw, mu_q, sd_q, mu_p=None, sd_p=None, *, prior=(0.0, 0.0), mode=GAUSS_LOGVAR, qidx=None, pidx=None,
              reps=1, free_bits=False, kl_min=0.0, add=None):
@@ -687,9 +684,6 @@ def smalln_fwd(probs, logits, a1, W, bias=None, a2=None, ymarg=None, park=None, 
     _lib.check(_lib.load().dv_smalln_linear_fwd(_f32(a1), _ld(a1), K1, _f32(a2), _ld(a2), K2, _f32(W), _ld(W),
                                                 _f32(bias), M, N, _f32(logits), _ld(logits), _f32(probs),
                                                 _ld(probs), ym, _wait(park), kf, dg, _stream()), 'dv_smalln_linear_fwd')
-
-
-smalln_fwd.fold_rows = True         # (this launcher takes ``dgrad``: read by ``schedule._step_tail``)
 
 
 def smalln_bwd_data(dsts, dprobs, probs, W, seg=None):

@@ -380,12 +380,10 @@ class StepSchedule:
         # scalars, which read those rows, are assembled behind the side tail's wait for flag ``noise`` (published behind that
         # launch on the main chain) -- and the classifier's data gradient leaves the classifier's forward launch, which has its
         # inputs already; the fprop rows' d/dz1 is summed by ``z2f_post_bwd``.  Only the single-process dual-graph train step
-        # of a DrVAE with the single-Linear classifier on [z1, z2Fz1 - z1], and only where the installed launchers take the
-        # folded forms (the CPU stand-ins of the tests pin the launchers' signatures).  Same bits as the unfolded step; cfg 2:
+        # of a DrVAE with the single-Linear classifier on [z1, z2Fz1 - z1].  Same bits as the unfolded step; cfg 2:
         # 0.1842 -> 0.1817 ms in alternating legs (profiles/r15_fold_rows.md)
         fold_rows = bool(T.get('fold_rows') and not split_kind and not clip and not p.drop_sites and cfg.kind == 'drvae'
-                         and not cfg.cont and self.clf_small and cfg.clf_z1z2 and fold_join and side_loss and noise_ahead
-                         and getattr(K.z2f_post_bwd, 'fold_rows', False) and getattr(K.smalln_fwd, 'fold_rows', False))
+                         and not cfg.cont and self.clf_small and cfg.clf_z1z2 and fold_join and side_loss and noise_ahead)
         t = Tail(dual=True, late=late, adam_gated=late and not split_kind, side_adam=side_adam, hs=hs, side_loss=side_loss,
                  cap_fork=cap_fork, tail_gated=tail_gated, noise_ahead=noise_ahead, klz2_on_main=klz2_on_main,
                  fold_join=fold_join, fold_rows=fold_rows)

@@ -116,7 +116,7 @@ def z2f_alloc(case, o, dev=None):
 
 
 def z2f_launch(mod, case, o, out, fold_kl=True, raw_in=None):
-    """the launch through ``mod`` (drvae_amd.kernels, tests.kernel_ref_fold or a faulty emulation).  ``fold_kl`` False:
+    """the launch through ``mod`` (drvae_amd.kernels, tests.kernel_ref or a faulty emulation).  ``fold_kl`` False:
     the KL rows are an input (``raw_in``), the old form of the same launcher"""
     Z, L, B, Np = case['shape']
     v = {k: b[1] for k, b in out.items()}
@@ -253,28 +253,26 @@ def z2f_verify(case, host, raises=True, site=''):
 def kl_rows_separate(mod, case, o, dev=None):
     """(kl, raw) of the separate launch ``mod.kl_rows_fwd`` on the case's operands: what the folded launch must equal bit
     for bit"""
-    from tests import kernel_ref_fold as F
     Z, L, B, Np = case['shape']
     kl, raw = torch.zeros(L * Np, device=dev), torch.zeros(L * Np, device=dev)
     q2, p2 = o['q2'][:Np], o['p2']
-    mod.kl_rows_fwd(kl, raw, q2[:, :Z], q2[:, Z:], p2[:, :Z], p2[:, Z:], pidx=F.pair_rows(o['slot'], L, B, Np).to(torch.int32),
+    mod.kl_rows_fwd(kl, raw, q2[:, :Z], q2[:, Z:], p2[:, :Z], p2[:, Z:], pidx=kernel_ref.pair_rows(o['slot'], L, B, Np).to(torch.int32),
                     reps=L, free_bits=True, kl_min=case['kl_min'])
     return kl, raw
 
 
 class FaultyZ2F:
-    """the folded launch on the host in fp32 -- ``kernel_ref_fold.z2f_post_bwd`` -- with ONE defect (None: bitwise that)"""
+    """the folded launch on the host in fp32 -- ``kernel_ref.z2f_post_bwd`` -- with ONE defect (None: bitwise that)"""
 
     def __init__(self, fault=None):
         self.fault = fault
 
     def z2f_post_bwd(self, dp2, dz1, dq2, dz2f, dzdec_pert, pair_slot, eps, p2, q2, coef, raw, kl_min, dz1b, L, B, Np,
                      park=None, prior=None, kl_out=None, seg=None, z1_dz2f=0.0):
-        from tests import kernel_ref_fold as F
         fault = self.fault
         Z = dp2.shape[1] // 2
         if kl_out is not None and Np:
-            pidx = F.pair_rows(pair_slot, L, B, Np)
+            pidx = kernel_ref.pair_rows(pair_slot, L, B, Np)
             if fault == 'sum_in_another_order':     # the dims summed back to front, in fp32
                 mq, lq = q2[:, :Z].repeat(L, 1), q2[:, Z:2 * Z].repeat(L, 1)
                 mp, lp = p2[pidx, :Z], p2[pidx, Z:2 * Z]

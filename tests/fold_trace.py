@@ -128,13 +128,13 @@ def step(eng, tail, functions, run=True):
     return rec
 
 
-def default_trace(name, universal, install=kernel_ref.install):
-    """the recorded (not run) default dual-graph step of a case on the stand-ins of ``install``"""
+def default_trace(name, universal):
+    """the recorded (not run) dual-graph step of a case on the stand-ins, as ``DRVAE_TUNE`` has it"""
     import pytest
     import drvae_amd.tuning as T
     with pytest.MonkeyPatch.context() as mp:
         mp.setattr(T, '_VALUES', None)
-        eng, _, case = make(name, universal, install, mp)
+        eng, _, case = make(name, universal, kernel_ref.install, mp)
         eng.set_noise(case['noises'][0])
         tail = eng._step_tail(False, on_gpu=True)
         assert tail.dual
@@ -143,6 +143,7 @@ def default_trace(name, universal, install=kernel_ref.install):
 
 
 if __name__ == '__main__':
+    os.environ['DRVAE_TUNE'] = 'fold_rows=0'        # the golden trace is the UNFOLDED step
     out = {'%s/%s' % (n, 'universal' if u else 'structure'): default_trace(n, u) for n, u in CASES}
     with open(GOLDEN, 'w') as f:
         json.dump(out, f, separators=(',', ':'), sort_keys=True)

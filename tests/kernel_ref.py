@@ -1,5 +1,6 @@
-"""Plain-PyTorch fp32 reference of every launcher in ``drvae_amd.kernels`` (same names,
-same signatures, writes into the same output tensors; works on CPU or GPU tensors).
+"""Plain-PyTorch reference of every launcher in ``drvae_amd.kernels`` that reaches the library (same names, same
+signatures with every keyword of today, writes into the same output tensors; works on CPU or GPU tensors) -- ONE module:
+``FUNCTIONS`` names them all, ``tests/test_engine_cpu.py`` holds the list to the launchers' signatures.
 
 Two uses, both test-only:
   * ``-m gpu`` tests run each HIP kernel next to its reference here;
@@ -7,6 +8,12 @@ Two uses, both test-only:
     ``install``) to check the host-side orchestration (autograd wrappers, the fused
     step engine's hand-written backward, data-parallel sharding) against the oracle
     without a GPU.  The product never imports this module.
+
+The arithmetic is fp32 in the launchers' own operation order, except where a launcher is SPECIFIED in float64 with one
+rounding, and the stand-in states that specification: the negative-binomial and library-size rows (``tests/nb_ref.py``,
+``tests/counts_ref.py``), the noise (``tests/philox_ref.py``), the split-bf16 products (``tests/x3_ref.py``), the schedule
+record, the rate / decay / average factors of the sweeps and the clip record.  ``CALLS`` counts what the step tests ask
+about (reset by ``install``); ``FAULT`` makes one stand-in wrong on purpose.
 """
 import math
 
@@ -16,9 +23,16 @@ import torch
 import torch.nn.functional as F
 
 from drvae_amd._lib import ACT, EPI_BWD, EPI_FWD, EPI_PLAIN, GAUSS_LOGVAR, GAUSS_SIGMA  # noqa: F401
+from tests import counts_ref, nb_ref, philox_ref, x3_ref
 
 LOG_2PI = 1.8378770664093453
 _ACT_NAME = {v: k for k, v in ACT.items()}
+
+CALLS = dict.fromkeys(['batch_masks', 'batch_feed', 'lr_scaled_sweeps', 'decoupled_sweeps', 'averaged_sweeps', 'clip_norm',
+                       'adam_l2_clip', 'adamax_l2_clip', 'split_feed', 'plain_feed', 'lib_rows', 'plain_rows',
+                       'fill_noise_rows', 'mask_scale', 'z2f_post_bwd', 'smalln_fwd', 'folded_kl', 'folded_dgrad', 'nb',
+                       'other'], 0)
+FAULT = {'name': None}          # tests only: 'moved_on_skipped_step' makes the averaged sweeps wrong on purpose
 
 
 def _name(a):
@@ -102,12 +116,33 @@ def _widen(t, cols):
     return torch.as_strided(t, (t.shape[0], cols), (_ldr(t), 1), t.storage_offset())
 
 
-def gemm(Cm, A, B, a_kc, b_kc, *, A2=None, a_kscale=None, alpha=1.0, beta=0.0, epi=EPI_PLAIN, scale=None,
+RUNG_TERMS = {3: x3_ref.TERMS, 2: ((0, 0), (0, 1), (1, 0)), 1: ((0, 0),)}     # bf16 part products of a split-bf16 rung
+
+
+def routed_product(Cm, A, B, a_kc, b_kc, parts, *, a_colsum=None, colsum_beta=0.0, **kw):
+    """one product routed with ``x3=True``: the rung's contract (``x3_ref.matmul`` with its terms: float64 sums, rounded to
+    fp32 once), its epilogue by the fp32 stand-in (through an exact product with the identity)"""
+    Aop, Bop = (A if a_kc else A.t()), (B.t() if b_kc else B)
+    prod = x3_ref.matmul(Aop.contiguous(), Bop.contiguous(), RUNG_TERMS[parts]).float()
+    gemm(Cm, prod, torch.eye(Cm.shape[1]), True, False, **kw)
+    if a_colsum is not None:
+        _acc(a_colsum, Aop.sum(1), colsum_beta)
+
+
+def gemm(Cm, A, B, a_kc, b_kc, x3=False, parts=3, *, A2=None, a_kscale=None, alpha=1.0, beta=0.0, epi=EPI_PLAIN, scale=None,
          bias=None, split=None, act0=0, act1=0, shift0=0.0, shift1=0.0, resid=None, resid_cols=0, yref=None,
          a_colsum=None, colsum_beta=0.0, overread=False, publish=None, kpad=False, npad=False):
     """mirrors ``kernels._gemm_desc`` INCLUDING its padded forms (round 5, advisor): with ``kpad`` the product runs over
     K rounded up to 4 and so reads the operands' pad columns; with ``npad`` it runs over N rounded up and WRITES C's pad
-    columns -- a pad that is not zero shows up in the CPU suite exactly as it would on the device"""
+    columns -- a pad that is not zero shows up in the CPU suite exactly as it would on the device.  ``x3``: the product is
+    ``routed_product`` (no second source, no per-k scale, and its pads are not run over)"""
+    if x3:
+        assert A2 is None and a_kscale is None
+        return routed_product(Cm, A, B, a_kc, b_kc, parts, alpha=alpha, beta=beta, epi=epi, scale=scale, bias=bias,
+                              split=split, act0=act0, act1=act1, shift0=shift0, shift1=shift1, resid=resid,
+                              resid_cols=resid_cols, yref=yref, a_colsum=a_colsum, colsum_beta=colsum_beta, publish=publish)
+    if parts != 3:
+        raise ValueError('gemm(parts=%r) without x3=True: the fp32 product has no parts' % (parts,))
     if publish is not None:
         flag_publish(publish[0], publish[1], publish[2])
     M, N = Cm.shape
@@ -202,8 +237,49 @@ def linear_bwd_weight(dW, dpre, x, *, beta=0.0, dbias=None, overread=False, npad
     gemm(dW, dpre, x, False, False, beta=beta, a_colsum=dbias, colsum_beta=beta, npad=npad)
 
 
-def linear_bwd_pair(dW, dbias, dx, dpre, x, W, *, kscale=None, alpha=1.0, beta_x=0.0, yref=None, act=0, shift=0.0,
-                    overread=False, publish=None, npad=False, npad_x=False, klq=None):
+def bn_fwd(y, x, w, b, mean, rstd, running_mean, running_var, eps=1e-5, momentum=0.1, training=True):
+    """dv_bn_fwd: nn.BatchNorm1d(affine=True) over the rows of x; ``mean`` / ``rstd`` keep what ``bn_bwd`` needs"""
+    M = x.shape[0]
+    if training:
+        mu, var = x.mean(0), x.var(0, unbiased=False)
+        if running_mean is not None:
+            running_mean.mul_(1 - momentum).add_(momentum * mu)
+            running_var.mul_(1 - momentum).add_(momentum * var * (M / max(M - 1, 1)))
+    else:
+        mu, var = running_mean, running_var
+    mean.copy_(mu)
+    rstd.copy_(torch.rsqrt(var + eps))
+    y.copy_((x - mean) * rstd * w + b)
+
+
+def bn_bwd(dx, dw, db, dy, x, mean, rstd, w, training=True):
+    """dv_bn_bwd; dx, dw, db optional"""
+    M = x.shape[0]
+    xhat = (x - mean) * rstd
+    sw, sb = (dy * xhat).sum(0), dy.sum(0)
+    if dw is not None:
+        dw.copy_(sw)
+    if db is not None:
+        db.copy_(sb)
+    if dx is not None:
+        dx.copy_(w * rstd * (dy - sb / M - xhat * sw / M) if training else dy * w * rstd)
+
+
+def mask_scale(y, x, mask, scale):
+    """dv_mask_scale: y = x * mask * scale in fp32, in that order (y may be x)"""
+    CALLS['mask_scale'] += 1
+    y.copy_(x * mask * torch.tensor(scale, dtype=x.dtype, device=x.device))
+
+
+def linear_bwd_pair(dW, dbias, dx, dpre, x, W, x3=False, parts=3, *, kscale=None, alpha=1.0, beta_x=0.0, yref=None, act=0,
+                    shift=0.0, overread=False, publish=None, npad=False, npad_x=False, klq=None):
+    if x3:                     # both products routed (``routed_product``)
+        assert kscale is None and beta_x == 0.0 and klq is None
+        routed_product(dW, dpre, x, False, False, parts, a_colsum=dbias, publish=publish)
+        e = {} if yref is None else dict(epi=EPI_BWD, yref=yref, act0=act, act1=act, shift0=shift, shift1=shift)
+        return routed_product(dx, dpre, W, True, False, parts, alpha=alpha, **e)
+    if parts != 3:
+        raise ValueError('linear_bwd_pair(parts=%r) without x3=True: the fp32 products have no parts' % (parts,))
     if publish is not None:
         flag_publish(publish[0], publish[1], publish[2])
     linear_bwd_weight(dW, dpre, x, dbias=dbias, npad=npad)
@@ -313,12 +389,34 @@ def reparam_bwd_seg(dmu, dsd, dz, eps, sd, seg_ptr, seg_rows, *, mode=GAUSS_LOGV
         dsd[:nq] += gs
 
 
+def pair_rows(pair_slot, L, B, Np):
+    """p row l*B + i of every KL row l*Np + jp (pair_slot[i] == jp): the ``pidx`` of the separate launch"""
+    slot = pair_slot.long()
+    i_of = torch.empty(Np, dtype=torch.long, device=slot.device)
+    i_of[slot[slot >= 0]] = torch.arange(B, device=slot.device)[slot >= 0]
+    return (torch.arange(L, device=slot.device)[:, None] * B + i_of[None, :]).reshape(-1)
+
+
 def z2f_post_bwd(dp2, dz1, dq2, dz2f, dzdec_pert, pair_slot, eps, p2, q2, coef, raw, kl_min, dz1b, L, B, Np,
-                 park=None, prior=None):
+                 park=None, prior=None, kl_out=None, seg=None, z1_dz2f=0.0):
+    """the folded forms (``Tail.fold_rows``) as the unfolded sequences they replace: ``kl_out``: the pairs' KL rows are
+    formed here first; ``seg`` / ``z1_dz2f``: the fprop rows' d/dz1 and the classifier's share join ``dz1b``"""
+    CALLS['z2f_post_bwd'] += 1
     if park is not None:
         flag_wait(park[0], park[1], park[2], park[3] if len(park) > 3 else 1)                  # single-threaded stand-in: the producer has run already
     Z = dp2.shape[1] // 2
     dev = dp2.device
+    if kl_out is not None and Np:
+        CALLS['folded_kl'] += 1
+        kl_rows_fwd(kl_out, raw, q2[:, :Z], q2[:, Z:2 * Z], p2[:, :Z], p2[:, Z:2 * Z], pidx=pair_rows(pair_slot, L, B, Np),
+                    reps=L, free_bits=True, kl_min=kl_min)
+    if seg is not None:
+        s = torch.zeros(L * B, Z, device=dev)
+        rows_segment_sum(s, seg[0], seg_ptr=seg[1], beta=0.0, width=Z)
+        s = s * (seg[2] if len(seg) > 2 else 1.0)
+        dz1b = s if dz1b is None else dz1b + s
+    if z1_dz2f != 0.0 and dz2f is not None:
+        dz1b = z1_dz2f * dz2f if dz1b is None else dz1b + z1_dz2f * dz2f
     if dz2f is None:
         dz2f = torch.zeros(L * B, Z, device=dev)
     slot = pair_slot.long() if (pair_slot is not None and Np) else torch.full((B,), -1, dtype=torch.long, device=dev)
@@ -461,8 +559,35 @@ def nll_rows_bwd(dmu, dsd, coef, x, mu, sd, *, mode=GAUSS_SIGMA, xidx=None, sd_a
         _acc(dx, -c * gm, beta)
 
 
-def rec_nll_rows(out, x, v, *, kind, shift=0.0, xidx=None, coef=None, dpre=None):
+def rec_nll_rows(out, x, v, *, kind, shift=0.0, xidx=None, coef=None, dpre=None, library=False):
+    """``kind='nb'`` (``v`` = [mu | theta], ``dpre`` = [d/da_m | d/da_t]) and ``library=True`` (the mean scaled by the size
+    factor the kernel forms, an fp32 quotient) state the header's formulas: float64 on the fp32 values handed in, rounded
+    once (``tests/nb_ref.py``, ``tests/counts_ref.py``)"""
     xs = x[xidx.long()] if xidx is not None else x
+    X = x.shape[1]
+    CALLS['lib_rows' if library else 'plain_rows'] += 1
+    if library:
+        assert kind in ('poisson', 'nb')
+        ref = counts_ref.reference(kind, xs, v[:, :X], v[:, X:] if kind == 'nb' else None, coef=coef, shift=shift)
+        out.copy_(ref['rows'].to(out.dtype))
+        if coef is not None:
+            dpre[:, :X] = ref['gm'].to(dpre.dtype)
+            if kind == 'nb':
+                dpre[:, X:] = ref['gt'].to(dpre.dtype)
+        return
+    CALLS['nb' if kind == 'nb' else 'other'] += 1
+    if kind == 'nb':
+        assert v.shape[1] == 2 * X
+        xs, mu, th = xs.double(), v[:, :X].double(), v[:, X:].double()
+        out.copy_(nb_ref.logp64(xs, mu, th).sum(1).to(out.dtype))
+        if coef is not None:
+            gm, gt, _, _ = nb_ref.grads64(xs, mu, th)
+            sm = -torch.expm1(-(mu - nb_ref.ref64.f32(shift)))
+            st = -torch.expm1(-(th - nb_ref.ref64.f32(nb_ref.THETA_SHIFT)))
+            c = coef.double()[:, None]
+            dpre[:, :X] = (c * gm * sm).to(dpre.dtype)
+            dpre[:, X:] = (c * gt * st).to(dpre.dtype)
+        return
     if kind == 'binary':
         lo, hi = 1e-10, float(np.float32(1.0 - 1e-10))
         pc = v.clamp(lo, hi)
@@ -546,7 +671,17 @@ def _dlogits(dprobs, probs):
     return probs * (g - (g * probs).sum(1, keepdim=True))
 
 
-def smalln_fwd(probs, logits, a1, W, bias=None, a2=None, ymarg=None, park=None, fprop_kl=None):
+def smalln_fwd(probs, logits, a1, W, bias=None, a2=None, ymarg=None, park=None, fprop_kl=None, dgrad=None):
+    """``dgrad`` (the folded form, ``Tail.fold_rows``): the classifier's data gradient leaves the launch too"""
+    CALLS['smalln_fwd'] += 1
+    _smalln_fwd(probs, logits, a1, W, bias, a2, ymarg, park, fprop_kl)
+    if dgrad:
+        CALLS['folded_dgrad'] += 1
+        assert ymarg is not None and len(dgrad) <= 2
+        smalln_bwd_data(list(dgrad), ymarg[3], probs, W)
+
+
+def _smalln_fwd(probs, logits, a1, W, bias=None, a2=None, ymarg=None, park=None, fprop_kl=None):
     if park is not None:
         flag_wait(*park)
     if ymarg is not None:
@@ -557,7 +692,7 @@ def smalln_fwd(probs, logits, a1, W, bias=None, a2=None, ymarg=None, park=None, 
             kl_rows_fwd(klfp, f['raw1'], f['Q'][:, :Z1], f['Q'][:, Z1:], f['P'][:, :Z1], f['P'][:, Z1:], qidx=f['qidx'],
                         free_bits=True, kl_min=f['kl_min'], prior=(0.0, 0.0),
                         second=(f['Q3'][:, :Z3], f['Q3'][:, Z3:], f['raw3']))
-        smalln_fwd(probs, logits, a1, W, bias, a2)
+        _smalln_fwd(probs, logits, a1, W, bias, a2)
         ymarg_fwdbwd(yl, kld, cfp, dqy, probs, label, fp_ptr, klfp, log_prior, c_kld, c_yl)
         if f is not None:
             kl_rows_bwd(f['dq'][:, :Z1], f['dq'][:, Z1:], f['dp'][:, :Z1], f['dp'][:, Z1:], cfp, f['raw1'],
@@ -686,6 +821,138 @@ def mmd_identity_bwd(dx, diff, gout, coef):
     dx.copy_((coef * gout.reshape(-1)[0] * diff)[None, :].expand_as(dx))
 
 
+def nuisance_feed(sohe, sohd, cls, s32, *, table=None, n_batches=0, ctr=None, base=None, pair_rows=None, L=1):
+    B, S = cls.numel(), sohe.shape[1]
+    if table is not None:
+        b = min(max(int(ctr[0]) - int(base[0]), 0), n_batches - 1)
+        c = s32[table[b].long()]
+    else:
+        c = s32.reshape(-1)
+    c = c.to(torch.int32)
+    cp = c[pair_rows.long()] if (pair_rows is not None and pair_rows.numel()) else c[:0]
+    cls.copy_(c)
+    sohe.copy_(F.one_hot(torch.cat([c, cp]).long(), S).to(sohe.dtype))
+    sohd.copy_(F.one_hot(torch.cat([c.repeat(L), cp.repeat(L), cp.repeat(L)]).long(), S).to(sohd.dtype))
+
+
+def _grouped_terms(g, count):
+    """(term, class k, theta rows, rows of z, class of every row) of every term of the grouped penalty (``_Plan``'s table);
+    ``count`` (the forward launch): ``cnt`` is written on the way"""
+    Kc, E = (1 if g['S'] == 2 else g['S']), g['rows'].numel()
+    ptr = g['grp_ptr'].tolist()
+    for tg in range(len(ptr) - 1):
+        e = slice(ptr[tg], ptr[tg + 1])
+        rows = g['rows'][e].long()
+        c = g['cls'][g['src'][e].long()]
+        for k in range(Kc):
+            if count:
+                g['cnt'][tg, k] = int((c == k).sum())
+                if g['S'] == 2:
+                    g['cnt'][tg, 1] = c.numel() - int((c == k).sum())
+            yield tg * Kc + k, k, slice(k * E + e.start, k * E + e.stop), rows, c
+
+
+_MASKED_GROUPS = {'drvae': 4, 'pvae': 2, 'vfae': 2}
+
+
+def _masked_terms(g, count):
+    """the same of the masked penalty (a batch-independent plan: data groups and classes read as data); ``count``:
+    ``members`` and ``cnt`` are written on the way"""
+    cls, S = g['cls'], g['S']
+    B, Np, L, model, n_z = cls.numel(), g['Np'], g['L'], g['model'], g['z'].shape[0]
+    table = g.get('table')
+    if table is not None:
+        b = min(max(int(g['ctr'][0]) - int(g['base'][0]), 0), g['n_batches'] - 1)
+        r = table[b].long()
+    else:
+        r = torch.arange(B, device=cls.device)
+    zero = torch.zeros(B, dtype=torch.bool, device=cls.device)
+    hx = g['hx'][r] != 0 if g.get('hx') is not None else zero
+    hy = g['hy'][r] != 0 if g.get('hy') is not None else zero
+    if model == 'drvae':
+        grp = torch.where(hx, torch.where(hy, 2, 3), torch.where(hy, 0, 1))
+    elif model == 'pvae':
+        grp = hx.long()
+    else:
+        grp = 1 - hy.long()
+    G, Kc = _MASKED_GROUPS[model], (1 if S == 2 else S)
+    lists = [(l * B, B, False) for l in range(L)] + ([(L * B + l * Np, Np, True) for l in range(L)] if Np else [])
+    for q, (z0, n, z2) in enumerate(lists):
+        for gi in range(G):
+            m = grp[:n] == gi
+            if z2:
+                m = m & hx[:n]
+            mem = torch.nonzero(m).reshape(-1)
+            tg, c = q * G + gi, cls[mem]
+            if count:
+                g['members'][tg, :mem.numel()] = mem.to(torch.int32)
+                for k in range(S):
+                    g['cnt'][tg, k] = int((c == k).sum())
+                g['cnt'][tg, S] = mem.numel()
+            for k in range(Kc):
+                yield tg * Kc + k, k, k * n_z + z0 + mem, z0 + mem, c
+
+
+def _mmd_fwd(g, terms, zero_theta):
+    z, rff = g['z'], g['kind'] == 'rbf_fourier'
+    for t, k, th_rows, rows, c in terms:
+        n0 = int((c == k).sum())
+        n1 = c.numel() - n0
+        if n0 == 0 or n1 == 0:
+            g['diff'][t].zero_()
+            if rff and zero_theta:
+                g['theta'][th_rows].zero_()
+            continue
+        u = torch.where(c == k, torch.full_like(c, 1, dtype=z.dtype) / n0, torch.full_like(c, -1, dtype=z.dtype) / n1)
+        if rff:
+            th = g['a'] * (z[rows] @ g['W'][t]) + 2 * math.pi * g['b'][t]
+            g['theta'][th_rows] = th
+            g['diff'][t] = g['c'] * (u[:, None] * torch.cos(th)).sum(0)
+        else:
+            g['diff'][t] = (u[:, None] * z[rows]).sum(0)
+
+
+def _mmd_bwd(g, terms):
+    z, rff = g['z'], g['kind'] == 'rbf_fourier'
+    dz = torch.zeros_like(g['dz'])
+    val = z.new_zeros(())
+    for t, k, th_rows, rows, c in terms:
+        diff = g['diff'][t]
+        m2 = (diff * diff).sum()
+        g['m2'][t] = m2
+        n0 = int((c == k).sum())
+        n1 = c.numel() - n0
+        if float(m2) <= 0.0 or n0 == 0 or n1 == 0:
+            continue
+        val = val - g['w'] * torch.sqrt(m2)
+        coef = -g['fac'] * g['w'] / torch.sqrt(m2)
+        u = torch.where(c == k, torch.full_like(c, 1, dtype=z.dtype) / n0, torch.full_like(c, -1, dtype=z.dtype) / n1)
+        if rff:
+            G = -diff[None, :] * torch.sin(g['theta'][th_rows])
+            dz[rows] += (coef * g['c'] * g['a']) * u[:, None] * (G @ g['W'][t].t())
+        else:
+            dz[rows] += coef * u[:, None] * diff[None, :]
+    g['dz'].copy_(dz)
+    g['value'].copy_(val.reshape(1))
+
+
+def mmd_grouped_fwd(g):
+    _mmd_fwd(g, _grouped_terms(g, True), zero_theta=True)       # (a term with an empty side leaves zeros in its theta rows)
+
+
+def mmd_grouped_bwd(g):
+    _mmd_bwd(g, _grouped_terms(g, False))
+
+
+def mmd_masked_fwd(g):
+    g['cnt'].zero_()
+    _mmd_fwd(g, _masked_terms(g, True), zero_theta=False)
+
+
+def mmd_masked_bwd(g):
+    _mmd_bwd(g, _masked_terms(g, False))
+
+
 def _mix(G, kind, gammas, sa, sb):
     """the kernel mixture on a Gram matrix and its derivative w.r.t. G (poly) / the squared distance (rbf): dv_mmd_mix_*"""
     gam = [float(g) for g in gammas]
@@ -729,21 +996,29 @@ def rows_gather(out, src, idx=None, *, noise=None, sigma=0.0, onehot_cls=None, n
 
 def batch_feed(xin, x1, x2, y32, table, n_batches, ctr, base, *, pair_rows=None, noise=None, sigma=0.0, has_y=None,
                L=1, label_r=None, fp_i=None, fp_lab=None, fp_slot=None, fp_cls=None, onehot=None, n_classes=0, yf=None,
-               ylab=None, onehot2=None, masks=None, park=None):
+               ylab=None, onehot2=None, masks=None, park=None, xt=None, transform=None):
+    """``xt`` (the split form, raw-count inputs): the gathered rows go to ``xt`` and ``xin`` = T(xt) + sigma * noise"""
+    CALLS['batch_feed'] += 1
+    CALLS['plain_feed' if xt is None else 'split_feed'] += 1
+    assert transform is None if xt is None else (transform in (None, 'log1p') and tuple(xt.shape) == tuple(xin.shape))
+    rows = xin if xt is None else xt
     if park is not None:
         flag_wait(park[0], park[1], park[2], park[3] if len(park) > 3 else 1)
     if masks is not None:
-        batch_masks(table.shape[1], L, table=table, n_batches=n_batches, ctr=ctr, base=base, **masks)
+        _batch_masks(table.shape[1], L, table=table, n_batches=n_batches, ctr=ctr, base=base, **masks)
     if ylab is not None:
         bb = min(max(int(ctr[0]) - int(base[0]), 0), n_batches - 1)
         ylab.copy_(yf.reshape(-1, ylab.shape[1])[table[bb].long()])
     b = min(max(int(ctr[0]) - int(base[0]), 0), n_batches - 1)
     tb = table[b].long()
     B = tb.numel()
-    xin[:B] = x1[tb]
+    rows[:B] = x1[tb]
     if pair_rows is not None and pair_rows.numel():
-        xin[B:] = x2[tb[pair_rows.long()]]
-    if noise is not None:
+        rows[B:] = x2[tb[pair_rows.long()]]
+    if xt is not None:
+        t = torch.log1p(xt) if transform == 'log1p' else xt
+        xin.copy_(t + sigma * noise if noise is not None else t)
+    elif noise is not None:
         xin += sigma * noise
     if label_r is not None:
         label_r.copy_(torch.where(has_y.bool(), y32[tb], torch.zeros_like(y32[tb])).repeat(L))
@@ -849,6 +1124,35 @@ def _halted(halt):
     return halt is not None and bool((halt.reshape(-1)[0::2] != 0).any())
 
 
+def reg_metrics64(pred, y, sel=None, n=None):
+    """numpy float64 restatement of ``dv_reg_metrics`` (include/drvae_hip.h): the regression metrics of a continuous target
+    in the kernel's TWO-PASS arithmetic -- the means first, then the centred sums -- with its defined edge cases.
+    -> float64 array [rmse, r2, pearr] over the rows ``sel`` (None: the first ``n`` rows, default all) x all columns of
+    ``pred`` / ``y`` ((rows, Y) or (rows,)), flattened"""
+    pred = np.asarray(pred, np.float64).reshape(len(pred), -1)
+    y = np.asarray(y, np.float64).reshape(len(y), -1)
+    if sel is not None:
+        sel = np.asarray(sel, np.int64)
+        pred, y = pred[sel], y[sel]
+    elif n is not None:
+        pred, y = pred[:n], y[:n]
+    p, t = pred.reshape(-1), y.reshape(-1)
+    nan = float('nan')
+    if t.size == 0:
+        return np.array([nan, nan, nan])
+    my, mp = t.sum() / t.size, p.sum() / p.size          # pass 1
+    d, yc, pc = t - p, t - my, p - mp                    # pass 2
+    sse, syy, spp, syp = (d * d).sum(), (yc * yc).sum(), (pc * pc).sum(), (yc * pc).sum()
+    den = np.sqrt(syy * spp)
+    return np.array([np.sqrt(sse / t.size), 1.0 - sse / syy if syy > 0 else nan, syp / den if den > 0 else nan])
+
+
+def reg_metrics(out3, pred, y, *, sel=None, n=None):
+    """the launcher's form of ``reg_metrics64``: tensors in, ``out3`` (3 float64) written"""
+    v = reg_metrics64(pred.detach().cpu().numpy(), y.detach().cpu().numpy(), None if sel is None else sel.cpu().numpy(), n)
+    out3[:3] = torch.from_numpy(v).to(out3.device)
+
+
 def loss_assemble(loss, terms, w_elbo, w_cmpl, after=None, bump=(), halt=None, accum=None):
     if after is not None:
         flag_wait(after[0], after[1], after[2], after[3], after[4])
@@ -876,33 +1180,110 @@ def axpby(y, x, a=1.0, b=0.0):
     y.copy_(a * x + (b * y if b != 0.0 else 0))
 
 
-def adam_l2(p, g, m, v, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, gate=None,
-            halt=None):
+def lr_effective(lr, lr_scale):
+    """the rate a sweep with ``lr_scale`` runs at: (float)((double)lr * (double)lr_scale[0]) of the fp32 ``lr`` it is handed"""
+    return float(np.float32(np.float64(np.float32(lr)) * np.float64(np.float32(float(lr_scale.reshape(-1)[0])))))
+
+
+def _sweep(adamax, p, g, m, v, step_dev, state, *, lr, beta1, beta2, eps, weight_decay, gscale, gate=None, halt=None,
+           lr_scale=None, decoupled=False, avg=None, avg_decay=None):
+    """the one body of the four sweeps.  ``state`` (the ``_clip`` forms): the clip state, whose first word is the step.  A
+    sweep is TAKEN unless a halt word is set (behind the gate's wait, where there is one) or the clip record says skip; a
+    sweep that is not taken touches nothing, the average included.  Clipping: the gradient scaled by fl32(gscale * coef),
+    t = step - n_skipped.  ``lr_scale``: ``lr_effective``.  Decoupled decay: p *= fl32(1 - lr_eff wd) first (the factor in
+    double from the fp32 rate the sweep runs at), then the sweep at weight_decay = 0.  The average: e += fl32(1 - avg_decay)
+    (p_new - e) behind the sweep."""
+    if decoupled and adamax:
+        raise RuntimeError('drvae_amd: dv_adamax_l2 failed: invalid argument (-1)')       # (as ``_lib.check`` raises)
+    if avg is not None:
+        if avg_decay is None:
+            raise ValueError('an average needs its avg_decay')
+        if not 0.0 < float(np.float32(avg_decay)) < 1.0:
+            raise RuntimeError('drvae_amd: dv_adam_l2 failed: invalid argument (-1)')
+        assert avg.shape == p.shape
+    if state is not None:
+        import drvae_amd.kernels as K
+        CALLS['adamax_l2_clip' if adamax else 'adam_l2_clip'] += 1
+        clip, step_dev = K.clip_record(state), state[0:1]
+    CALLS['lr_scaled_sweeps'] += lr_scale is not None
+    CALLS['decoupled_sweeps'] += bool(decoupled)
+    CALLS['averaged_sweeps'] += avg is not None
     if gate is not None:
         flag_wait(gate[0], gate[1], gate[3], gate[2])
-    if _halted(halt):
-        return
-    t = int(step_dev.reshape(-1)[0])
-    gg = g * gscale
-    if weight_decay != 0.0:
-        gg = gg + weight_decay * p
-    m.lerp_(gg, 1 - beta1)
-    v.mul_(beta2).addcmul_(gg, gg, value=1 - beta2)
-    bc1, bc2 = 1 - beta1 ** t, 1 - beta2 ** t
-    denom = (v.sqrt() / math.sqrt(bc2)).add_(eps)
-    p.addcdiv_(m, denom, value=-(lr / bc1))
+    taken = not _halted(halt) and not (state is not None and int(clip[2]))
+    if taken:
+        t = int(step_dev.reshape(-1)[0])
+        if state is not None:
+            gscale = float(np.float32(gscale) * np.float32(float(clip.view(torch.float32)[1])))
+            t -= int(clip[3])
+        if lr_scale is not None:
+            lr = lr_effective(lr, lr_scale)
+        if decoupled:
+            p.mul_(float(np.float32(1.0 - np.float64(np.float32(lr)) * np.float64(np.float32(weight_decay)))))
+            weight_decay = 0.0
+        gg = g * gscale
+        if weight_decay != 0.0:
+            gg = gg + weight_decay * p
+        m.lerp_(gg, 1 - beta1)
+        if adamax:
+            torch.maximum(v.mul_(beta2), gg.abs().add_(eps), out=v)
+            p.addcdiv_(m, v, value=-(lr / (1 - beta1 ** t)))
+        else:
+            v.mul_(beta2).addcmul_(gg, gg, value=1 - beta2)
+            bc1, bc2 = 1 - beta1 ** t, 1 - beta2 ** t
+            denom = (v.sqrt() / math.sqrt(bc2)).add_(eps)
+            p.addcdiv_(m, denom, value=-(lr / bc1))
+    if avg is not None and (taken or FAULT['name'] == 'moved_on_skipped_step'):
+        avg.add_((p - avg) * float(np.float32(1.0 - np.float64(np.float32(avg_decay)))))
 
 
-def adamax_l2(p, g, m, u, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None):
-    if _halted(halt):
-        return
-    t = int(step_dev.reshape(-1)[0])
-    gg = g * gscale
-    if weight_decay != 0.0:
-        gg = gg + weight_decay * p
-    m.lerp_(gg, 1 - beta1)
-    torch.maximum(u.mul_(beta2), gg.abs().add_(eps), out=u)
-    p.addcdiv_(m, u, value=-(lr / (1 - beta1 ** t)))
+def adam_l2(p, g, m, v, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, gate=None,
+            halt=None, lr_scale=None, decoupled=False, avg=None, avg_decay=None):
+    _sweep(False, p, g, m, v, step_dev, None, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay,
+           gscale=gscale, gate=gate, halt=halt, lr_scale=lr_scale, decoupled=decoupled, avg=avg, avg_decay=avg_decay)
+
+
+def adamax_l2(p, g, m, u, step_dev, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None,
+              lr_scale=None, decoupled=False, avg=None, avg_decay=None):
+    _sweep(True, p, g, m, u, step_dev, None, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay,
+           gscale=gscale, halt=halt, lr_scale=lr_scale, decoupled=decoupled, avg=avg, avg_decay=avg_decay)
+
+
+def adam_l2_clip(p, g, m, v, state, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None,
+                 lr_scale=None, decoupled=False, avg=None, avg_decay=None):
+    _sweep(False, p, g, m, v, None, state, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay,
+           gscale=gscale, halt=halt, lr_scale=lr_scale, decoupled=decoupled, avg=avg, avg_decay=avg_decay)
+
+
+def adamax_l2_clip(p, g, m, u, state, *, lr, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0, gscale=1.0, halt=None,
+                   lr_scale=None, decoupled=False, avg=None, avg_decay=None):
+    _sweep(True, p, g, m, u, None, state, lr=lr, beta1=beta1, beta2=beta2, eps=eps, weight_decay=weight_decay,
+           gscale=gscale, halt=halt, lr_scale=lr_scale, decoupled=decoupled, avg=avg, avg_decay=avg_decay)
+
+
+def clip_norm(g, state, *, gscale=1.0):
+    """dv_grad_norm_clip on the clip state of ``kernels.clip_state`` (word 0 the step, max_norm a double, the record {norm,
+    coef (fp32 bits), skip, n_skipped}, then the workspace): the whole double sum goes into the first partial (one per
+    8192-element share would do), the partials are summed in index order, the record is written"""
+    import drvae_amd.kernels as K
+    CALLS['clip_norm'] += 1
+    part, rec = K.clip_partials(state), K.clip_record(state)
+    n_part = K.sumsq_partials(g.numel())
+    assert part.numel() >= n_part
+    max_norm = float(state[K._CLIP_MAX_NORM:K._CLIP_MAX_NORM + 2].view(torch.float64)[0])
+    assert max_norm > 0
+    part.zero_()
+    part[0] = (g.reshape(-1).double() ** 2).sum()
+    s = 0.0
+    for v in part[:n_part].tolist():        # index order
+        s = s + v
+    skip = not math.isfinite(s)
+    norm = abs(float(np.float32(gscale))) * math.sqrt(s) if s == s else float('nan')
+    coef = 0.0 if skip else min(1.0, max_norm / (norm + 1e-6))
+    f = rec.view(torch.float32)
+    f[0], f[1] = float(np.float32(norm)), float(np.float32(coef))
+    rec[2] = int(skip)
+    rec[3] += int(skip)
 
 
 def flag_publish(flag, ctr, add=1):
@@ -934,9 +1315,93 @@ def counter_add(counter, inc=1):
         counter[1] = hi - (1 << 32) if hi >= (1 << 31) else hi
 
 
-def batch_masks(B, L, *, n_tot, kl_rate, pert_rate, yl_rate, beta, c_nll, w_recl, hx=None, hy=None, y=None, c_klz2=None,
-                c_yl=None, w_pert=None, w_yl=None, label=None, c_klp=None, table=None, n_batches=0, ctr=None, base=None,
-                Np=None, one_slot=None, gcounts=None):
+def _coef64(it, itermax, offset):
+    if itermax <= 0:
+        return 1.0
+    d = it - offset
+    if d <= 0:
+        return 0.01
+    return min(1.0, 0.01 + float(d) / float(itermax))
+
+
+def record(it, pert, kl, yl, lr):
+    """the schedule record {beta_pert, beta_kl, beta_yr, lr_scale} as ``dv_batch_masks`` evaluates it: in double from the
+    integer step counter and the integer schedule parameters, one rounding to fp32 per coefficient.  ``pert`` / ``yl`` =
+    (itermax, offset), ``kl`` / ``lr`` = itermax; an itermax <= 0 switches that schedule off (value 1)"""
+    lr_s = max(0.01, 1.0 - _coef64(it, lr, 0)) if lr > 0 else 1.0
+    return np.array([np.float32(_coef64(it, pert[0], pert[1])), np.float32(_coef64(it, kl, 0)),
+                     np.float32(_coef64(it, yl[0], yl[1])), np.float32(lr_s)], np.float32)
+
+
+def _coef32(it, itermax, offset):
+    f = np.float32
+    if itermax <= 0:
+        return f(1.0)
+    d = it - offset
+    if d <= 0:
+        return f(0.01)
+    return min(f(1.0), f(f(0.01) + f(f(d) / f(itermax))))
+
+
+def record_fp32(it, pert, kl, yl, lr):
+    """FAULTY on purpose: the same record with every operation rounded to fp32 (what a kernel evaluating the schedule in
+    single precision would store)"""
+    f = np.float32
+    lr_s = max(f(0.01), f(f(1.0) - _coef32(it, lr, 0))) if lr > 0 else f(1.0)
+    return np.array([_coef32(it, pert[0], pert[1]), _coef32(it, kl, 0), _coef32(it, yl[0], yl[1]), lr_s], np.float32)
+
+
+def _apply_schedule(B, L, an, m, rec):
+    """what the annealed launch does behind the plain masks: the record, beta_kl / beta_yr folded into the coefficients, the
+    copies without beta_kl, the ELBO / CMPL weights (fp32 arithmetic on the fp32 record, like the kernel)"""
+    dev = m['c_nll'].device
+    r = torch.from_numpy(rec).to(dev)
+    an['sched'].copy_(r)
+    b_kl, b_yr = r[1], r[2]
+    if m.get('c_klz2') is not None and m.get('hx') is not None:
+        if an.get('w_klz2') is not None:
+            an['w_klz2'].copy_(m['c_klz2'])
+        m['c_klz2'].mul_(b_kl)
+    if m.get('c_klp') is not None:
+        if an.get('w_klp') is not None:
+            an['w_klp'].copy_(m['c_klp'])
+        m['c_klp'].mul_(b_kl)
+    if m.get('hy') is not None:
+        m['c_yl'].mul_(b_yr)
+    if an.get('c_kld') is not None:
+        c_tot = torch.tensor(1.0, dtype=torch.float32) / (torch.tensor(float(L), dtype=torch.float32) * torch.tensor(m['n_tot'], dtype=torch.float32))
+        an['c_kld'][:L * B] = (b_kl.cpu() * c_tot).to(dev)
+    has_pert, has_y = m.get('hx') is not None, m.get('hy') is not None
+    f = lambda v: torch.tensor(v, dtype=torch.float32)
+    an['w_elbo'][:3] = torch.stack([f(1.0), -r[1].cpu(), r[0].cpu() * f(m['pert_rate']) if has_pert else f(0.0)]).to(dev)
+    w = torch.zeros(8)
+    w[3] = -(r[2].cpu() * f(m['yl_rate'])) if has_y else 0.0
+    mmd = float(an.get('mmd_rate', 0.0))
+    w[4] = -float(np.float32(mmd)) if mmd != 0.0 else 0.0
+    w[5] = -1.0
+    an['w_cmpl'][:8] = w.to(dev)
+
+
+def batch_masks(B, L, **masks):
+    CALLS['batch_masks'] += 1
+    _batch_masks(B, L, **masks)
+
+
+def _batch_masks(B, L, *, anneal=None, **m):
+    """``anneal`` (the annealing schedules): the launch evaluates its OWN beta_pert -- ``beta`` is not read -- and applies
+    the schedule behind the plain masks"""
+    if anneal is None:
+        return _plain_masks(B, L, **m)
+    rec = record(int(anneal['step'].reshape(-1)[0]), anneal['pert'], anneal['kl'], anneal['yl'], anneal['lr'])
+    if m.get('gcounts') is not None:      # (an explicit batch's one pair of global counts: ``_plain_masks`` indexes rows)
+        m = dict(m, gcounts=m['gcounts'].reshape(-1, 2))
+    _plain_masks(B, L, **dict(m, beta=torch.from_numpy(rec[0:1].copy()).to(m['c_nll'].device)))
+    _apply_schedule(B, L, anneal, m, rec)
+
+
+def _plain_masks(B, L, *, n_tot, kl_rate, pert_rate, yl_rate, beta, c_nll, w_recl, hx=None, hy=None, y=None, c_klz2=None,
+                 c_yl=None, w_pert=None, w_yl=None, label=None, c_klp=None, table=None, n_batches=0, ctr=None, base=None,
+                 Np=None, one_slot=None, gcounts=None):
     Np = B if Np is None else Np
     gc = None
     if gcounts is not None:       # data parallelism: the GLOBAL (N_pairs, N_labeled) of the batch are table data
@@ -980,16 +1445,53 @@ def _event(ctr_dev):
 def fill_normal_rows(arena, desc, seed, ctr_dev=None, park=None):
     """dv_fill_normal_rows as specified (tests/philox_ref.py, float32 of its float64 value): the device's numbers up to
     the fp32 rounding of its Box-Muller transform"""
-    from tests import philox_ref
     if park is not None:
         flag_wait(*park)
     offsets, z, _, _ = philox_ref.rows_table(desc.cpu().numpy(), seed, _event(ctr_dev))
     arena.view(-1)[torch.from_numpy(offsets).to(arena.device)] = torch.from_numpy(z.astype(np.float32)).to(arena.device)
 
 
+def keep_rows(desc, keep_thr, seed, event):
+    """(offsets, mask) flat over every element the KEEP rows ``desc`` (n x {offset, width, draw id, global row}) describe:
+    mask = 1.0 where word col % 4 of Philox4x32-10(counter = (col // 4, global row, draw id, event_lo),
+    key = (seed_lo, seed_hi ^ event_hi)) is < keep_thr, else 0.0 (integer Philox words against the threshold: no float
+    uniform, so a conforming kernel writes exactly these masks)"""
+    desc = np.asarray(desc, dtype=np.int64).reshape(-1, 4)
+    s_lo, s_hi = philox_ref._split(seed)
+    e_lo, e_hi = philox_ref._split(event)
+    offs, vals = [], []
+    for w in np.unique(desc[:, 1]):
+        if w <= 0:
+            continue
+        d = desc[desc[:, 1] == w]
+        blk = np.arange((int(w) + 3) // 4, dtype=np.uint64).reshape(1, -1)
+        words = philox_ref.philox4x32_10(blk, d[:, 3].reshape(-1, 1), d[:, 2].reshape(-1, 1), e_lo, s_lo, s_hi ^ e_hi)
+        words = np.stack(words, -1).reshape(len(d), -1)[:, :int(w)]              # (rows, width): word col % 4 of block col // 4
+        offs.append((d[:, 0][:, None] + np.arange(int(w))[None, :]).reshape(-1))
+        vals.append((words.astype(np.uint64) < np.uint64(keep_thr)).astype(np.float32).reshape(-1))
+    if not offs:
+        return np.zeros(0, np.int64), np.zeros(0, np.float32)
+    return np.concatenate(offs), np.concatenate(vals)
+
+
+def fill_noise_rows(arena, table, seed, ctr_dev=None, park=None):
+    """dv_fill_noise_rows as specified: ``table`` = descriptor rows + the trailer row {number of keep
+    rows at the end, keep_thr's bits, 0, 0}; the rows in front as ``fill_normal_rows``, the rest keep masks"""
+    CALLS['fill_noise_rows'] += 1
+    desc, tr = table[:-1], table[-1].tolist()
+    n_normal, keep_thr = desc.shape[0] - tr[0], tr[1] & 0xFFFFFFFF
+    assert 0 <= n_normal <= desc.shape[0] and tr[2] == tr[3] == 0
+    if park is not None:
+        flag_wait(*park)
+    d = desc.cpu().numpy()
+    if n_normal:
+        fill_normal_rows(arena, desc[:n_normal], seed, ctr_dev)
+    offs, vals = keep_rows(d[n_normal:], keep_thr, seed, _event(ctr_dev))
+    arena.view(-1)[torch.from_numpy(offs).to(arena.device)] = torch.from_numpy(vals).to(arena.device)
+
+
 def fill_normal(out, seed, ctr_dev=None):
     """dv_fill_normal as specified (tests/philox_ref.py, float32 of its float64 value)"""
-    from tests import philox_ref
     z = philox_ref.flat(out.numel(), seed, _event(ctr_dev))[0]
     out.copy_(torch.from_numpy(z.astype(np.float32)).view(out.shape).to(out.device))
 
@@ -1018,16 +1520,29 @@ def nll_rows_raw_cs(out_part, dmu, dsd, ws, coef, x, mu, sd, bias, *, xidx=None,
             ws[b, X:2 * X] = dsd[b * 64:(b + 1) * 64].sum(0)
 
 
-FUNCTIONS = ['mmd_identity_fwd', 'mmd_identity_bwd', 'mmd_mix_fwd', 'mmd_mix_bwd', 'mmd_mix_combine', 'smalln_ws_numel', 'col_moment_blocks', 'recon_finalize', 'rank_metrics', 'nll_raw_cs_shape', 'nll_rows_raw_cs', 'rec_nll_rows', 'batch_masks', 'fill_normal_rows', 'linear_heads', 'heads_tiles', 'adamax_l2', 'batch_feed', 'mmd_rff_fwd', 'mmd_rff_bwd', 'counters_add2', 'ycont_fwd', 'ycont_bwd', 'flag_publish', 'flag_wait', 'gemm', 'linear_fwd', 'linear_bwd_data', 'linear_bwd_weight', 'linear_bwd_pair', 'colsum', 'act_bwd_', 'wn_scale', 'wn_bwd',
-             'reparam_fwd', 'reparam_bwd', 'reparam_bwd_seg', 'z2f_post_bwd', 'kl_rows_fwd', 'kl_rows_fwd_pair', 'kl_rows_bwd', 'nll_rows_fwd', 'nll_rows_bwd', 'nll_rows_fwdbwd',
-             'softmax_clamp_fwd', 'softmax_clamp_bwd', 'cat_terms_fwd', 'cat_terms_bwd', 'smalln_fwd', 'smalln_bwd_data',
-             'smalln_bwd_weight', 'ymarg_fwd', 'ymarg_bwd', 'ymarg_fwdbwd',
-             'rows_gather', 'rows_segment_sum', 'weighted_sum', 'recon_row_stats', 'recon_rows', 'col_moments', 'loss_assemble', 'axpby', 'adam_l2', 'counter_add', 'fill_normal']
+# the host-side helpers of ``drvae_amd.kernels`` (``clip_state``, ``noise_table``, ``x3_refusal``, ...) are plain python and
+# are used as they are
+FUNCTIONS = sorted(
+    'gemm linear_fwd heads_tiles linear_heads linear_bwd_data linear_bwd_weight linear_bwd_pair bn_fwd bn_bwd mask_scale '
+    'colsum act_bwd_ wn_scale wn_bwd reparam_fwd reparam_bwd reparam_bwd_seg z2f_post_bwd kl_rows_fwd kl_rows_fwd_pair '
+    'kl_rows_bwd nll_rows_fwd nll_rows_bwd nll_rows_fwdbwd nll_raw_cs_shape nll_rows_raw_cs rec_nll_rows softmax_clamp_fwd '
+    'softmax_clamp_bwd cat_terms_fwd cat_terms_bwd smalln_fwd smalln_bwd_data smalln_ws_numel smalln_bwd_weight ymarg_fwd '
+    'ymarg_bwd ymarg_fwdbwd ycont_fwd ycont_bwd mmd_rff_fwd mmd_rff_bwd mmd_identity_fwd mmd_identity_bwd mmd_mix_fwd '
+    'mmd_mix_bwd mmd_mix_combine nuisance_feed mmd_grouped_fwd mmd_grouped_bwd mmd_masked_fwd mmd_masked_bwd rows_gather '
+    'batch_feed batch_masks rows_segment_sum weighted_sum recon_row_stats recon_rows col_moments col_moment_blocks '
+    'recon_finalize rank_metrics reg_metrics loss_assemble axpby adam_l2 adamax_l2 clip_norm adam_l2_clip adamax_l2_clip '
+    'flag_publish flag_wait counter_add counters_add2 fill_normal_rows fill_noise_rows fill_normal'.split())
 
 
 def install(monkeypatch):
-    """Replace the HIP launchers by these references for one CPU test (pytest monkeypatch)."""
+    """Replace the HIP launchers by these references for one CPU test (pytest monkeypatch); resets ``CALLS`` and ``FAULT``."""
     import drvae_amd.kernels as K
     me = globals()
     for name in FUNCTIONS:
         monkeypatch.setattr(K, name, me[name])
+    for name in CALLS:
+        CALLS[name] = 0
+    FAULT['name'] = None
+
+
+assert nb_ref.MU_SHIFT == 1e-6

@@ -2,7 +2,7 @@
 record's values against the float64 formula (and a faulty emulation the check must catch), construction and refusals, the
 annealed step against ``tests/anneal_ref.py`` on the three models, the schedules-off step bit for bit, resuming, data
 parallelism and the dual-graph ordering -- with the HIP launchers replaced by their plain-PyTorch references
-(tests/kernel_ref.py, tests/kernel_ref_clip.py, tests/kernel_ref_anneal.py).  The kernels themselves are checked on the GPU
+(tests/kernel_ref.py).  The kernels themselves are checked on the GPU
 (tests/test_gpu_anneal.py)."""
 import dataclasses
 import os
@@ -16,8 +16,6 @@ import torch.multiprocessing as mp
 from oracle import models_ref as M
 from tests import anneal_ref as R
 from tests import kernel_ref
-from tests import kernel_ref_anneal as KA
-from tests import kernel_ref_clip as KC
 
 # ramps of 3 iterations, crossed and saturated within the 6 steps of a test; the y-loss ramp with and without an offset
 SCHEDULES = {
@@ -99,7 +97,7 @@ def _reference_records():
 
 
 def test_stand_in_record_equals_fp32_of_the_float64_formula():
-    want, got = _reference_records(), _records(KA.record)
+    want, got = _reference_records(), _records(kernel_ref.record)
     assert set(want) == set(got) and len(want) == sum(m + o + 3 for m, o in GRID)
     for key in want:
         assert got[key].dtype == np.float32 and got[key].tobytes() == want[key].tobytes(), (key, got[key], want[key])
@@ -109,7 +107,7 @@ def test_stand_in_record_equals_fp32_of_the_float64_formula():
 
 
 def test_record_check_catches_an_fp32_evaluation():
-    want, bad = _reference_records(), _records(KA.record_fp32)
+    want, bad = _reference_records(), _records(kernel_ref.record_fp32)
     off = [k for k in want if bad[k].tobytes() != want[k].tobytes()]
     print('fp32-evaluated schedule: %d of %d records differ from fp32(float64 formula), e.g. %s' % (len(off), len(want), off[:3]))
     assert off, 'the faulty emulation went unnoticed'
@@ -120,7 +118,7 @@ def test_record_check_catches_an_fp32_evaluation():
 
 
 def test_off_switches_leave_ones_in_the_record():
-    r = KA.record(5, (0, 0), 0, (0, 7), 0)
+    r = kernel_ref.record(5, (0, 0), 0, (0, 7), 0)
     assert r.tobytes() == np.ones(4, np.float32).tobytes()
 
 
@@ -174,7 +172,7 @@ def _model_batch(model, n=8, seed=1):
 
 
 def test_configurations_without_a_universal_plan_are_refused(monkeypatch):
-    KA.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     from drvae_amd.VFAE import VFAE
     sup = VFAE(dim_x=13, dim_s=1, dim_y=2, dim_h_en_z1=[7], dim_h_de_z1=[6], dim_h_en_z2=[6], dim_h_de_x=[8], dim_h_clf=[],
                dim_z1=5, dim_z2=4, type_rec='diag_gaussian', nonlinearity='elu', semi_supervised=False, use_MMD=False,
@@ -196,7 +194,7 @@ def test_configurations_without_a_universal_plan_are_refused(monkeypatch):
 
 
 def test_the_stratified_feed_is_refused_and_points_at_the_sampler(monkeypatch):
-    KA.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     from drvae_amd import data as D
     from tests.test_fit import _tiny_dataset
     ds = _tiny_dataset('drvae', 32, 1)
@@ -211,7 +209,7 @@ def test_the_stratified_feed_is_refused_and_points_at_the_sampler(monkeypatch):
 
 
 def test_a_structure_plan_cannot_run_an_annealed_train_step(monkeypatch):
-    KA.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec, batch, noises = case('drvae')
     eng, _ = make_engine(spec, M.init_params(spec, 1, as_numpy=True), SCHEDULES['kl'])
     eng.set_structure(batch['has_x2'], batch['has_y'])
@@ -221,7 +219,7 @@ def test_a_structure_plan_cannot_run_an_annealed_train_step(monkeypatch):
 
 # ------------------------------------------------------------------------------------------------ 3. after the engine exists
 def test_attribute_idiom_works_until_the_engine_is_built_then_raises(monkeypatch):
-    KA.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     model = tiny_model('drvae')
     model.anneal_kl, model.anneal_kl_itermax = True, 3            # the reference's idiom (src/DrVAE.py:92-97 are attributes)
     kw = _model_batch(model)
@@ -255,7 +253,7 @@ STEP_CASES = [(kind, name) for kind in ('drvae', 'pvae', 'vfae') for name in SCH
 
 @pytest.mark.parametrize('kind,name', STEP_CASES)
 def test_annealed_step_against_the_reference(kind, name, monkeypatch):
-    KA.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec, batch, noises = case(kind)
     sched = SCHEDULES[name]
     got, prm, eng = run_engine(spec, sched, batch, noises[:N_STEPS])
@@ -269,13 +267,13 @@ def test_annealed_step_against_the_reference(kind, name, monkeypatch):
     # the record the last step ran with, bit for bit
     rec = R.record32(N_STEPS - 1, sched, spec.anneal_perturb_rate_itermax, spec.anneal_perturb_rate_offset)
     assert eng.sched_rec.numpy().tobytes() == rec.tobytes()
-    assert KA.CALLS['lr_scaled_sweeps'] == (N_STEPS if sched['anneal_learning_rate'] else 0)
+    assert kernel_ref.CALLS['lr_scaled_sweeps'] == (N_STEPS if sched['anneal_learning_rate'] else 0)
 
 
 def test_bucketed_universal_plans_anneal_too(monkeypatch):
     """the plans of the bucketed sampler feed (pair slots for the first rows only, a labeled range with one fprop row): the
     schedule rides on their masks launch as on the plain universal plan's"""
-    KA.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec = R.small_spec('drvae')
     batch = M.make_batch(spec, 8, seed=3)
     fl = {'a': (1, 0), 'b': (0, 0), 'c': (1, 1), 'd': (0, 1)}        # (labeled, pair); pairs first, labeled rows one run
@@ -298,11 +296,11 @@ def test_bucketed_universal_plans_anneal_too(monkeypatch):
 
 def test_clipped_annealed_step_against_the_reference(monkeypatch):
     """a threshold no gradient reaches: the clipped sweeps honour lr_scale and the step is the unclipped one's"""
-    KA.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec, batch, noises = case('drvae')
     got, prm, eng = run_engine(spec, SCHEDULES['all'], batch, noises[:N_STEPS], max_grad_norm=1e6)
     want, wprm = run_reference(spec, SCHEDULES['all'], batch, noises[:N_STEPS])
-    assert KC.CALLS['adam_l2_clip'] == N_STEPS and KA.CALLS['lr_scaled_sweeps'] == N_STEPS
+    assert kernel_ref.CALLS['adam_l2_clip'] == N_STEPS and kernel_ref.CALLS['lr_scaled_sweeps'] == N_STEPS
     for step in range(N_STEPS):
         for k, v in got[step].items():
             np.testing.assert_allclose(v, want[step][k], err_msg='step %d %s' % (step, k), **LOSS_TOL)
@@ -311,7 +309,7 @@ def test_clipped_annealed_step_against_the_reference(monkeypatch):
 
 
 def test_adamax_annealed_learning_rate_against_the_reference(monkeypatch):
-    KA.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec, batch, noises = case('drvae', optim_alg='adamax')
     got, prm, _ = run_engine(spec, SCHEDULES['lr'], batch, noises[:N_STEPS])
     want, wprm = run_reference(spec, SCHEDULES['lr'], batch, noises[:N_STEPS])
@@ -325,7 +323,7 @@ def test_adamax_annealed_learning_rate_against_the_reference(monkeypatch):
 def test_reported_scalars_stay_unscaled_in_training_and_evaluation(monkeypatch):
     """RECL / KLD / PERT / YL are the oracle's own (unannealed) scalars; ELBO / CMPL carry the betas -- in an evaluation
     pass mid-ramp too (the reference's loss_function applies them there), on the universal plan and on a structure plan"""
-    KA.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec, batch, noises = case('drvae')
     sched = SCHEDULES['all']
     eng, arena = make_engine(spec, M.init_params(spec, 9, as_numpy=True), sched)
@@ -361,7 +359,7 @@ def test_reported_scalars_stay_unscaled_in_training_and_evaluation(monkeypatch):
 def test_kl_warm_up_is_far_from_the_unannealed_run(monkeypatch):
     """the check the parent commit fails: with anneal_kl on, steps 0-2 (beta_kl = 0.01, 0.343, 0.677) are nowhere near a
     run with beta_kl = 1 -- the silently ignored switch of the code before this feature"""
-    KA.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec, batch, noises = case('drvae')
     on, _, _ = run_engine(spec, SCHEDULES['kl'], batch, noises[:3])
     off, _, _ = run_engine(spec, None, batch, noises[:3])
@@ -379,7 +377,7 @@ def test_the_reference_idiom_trains_with_the_ramp_not_with_beta_one(monkeypatch)
     """``model.anneal_kl = True`` after construction, the way the reference's users flip it: the model's losses over steps
     0-2 are the annealed reference's -- before this feature they were the unannealed ones, silently (this comparison fails
     there by value, not by a refused argument)"""
-    KA.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec = M.ModelSpec(kind='drvae', dim_x=13, dim_y=2, dim_z1=5, dim_z3=4, h_en_z1=[7], h_de_z1=[6], h_en_z3=[6], h_de_x=[8],
                        h_clf=[], L=2, learning_rate=5e-3, weight_decay=0.01, add_noise_var=0.01, pertloss_rate=0.05)
     model = tiny_model('drvae')
@@ -417,7 +415,7 @@ def _launch_log(mp_ctx, names):
 def test_schedules_off_is_the_step_as_it_was(kind, universal, monkeypatch):
     """the launch list (names and keyword names), the plan keys, the buffers and every bit of the result: an engine built
     without the arguments == one built with every switch spelled out as off (whatever their itermax)"""
-    KA.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec, batch, noises = case(kind)
     params = M.init_params(spec, 9, as_numpy=True)
     off = R.settings(anneal_kl_itermax=3, anneal_yloss_itermax=3, anneal_yloss_offset=2, anneal_lr_itermax=3)
@@ -427,7 +425,7 @@ def test_schedules_off_is_the_step_as_it_was(kind, universal, monkeypatch):
         eng.universal = universal
         set_batch(eng, batch)
         with pytest.MonkeyPatch.context() as mpc:
-            log = _launch_log(mpc, sorted(set(kernel_ref.FUNCTIONS + KC.FUNCTIONS + KA.FUNCTIONS) - {'smalln_ws_numel',
+            log = _launch_log(mpc, sorted(set(kernel_ref.FUNCTIONS) - {'smalln_ws_numel',
                               'col_moment_blocks', 'nll_raw_cs_shape', 'heads_tiles'}))
             for noise in noises[:3]:
                 eng.train_step(noise)
@@ -447,7 +445,7 @@ def test_schedules_off_is_the_step_as_it_was(kind, universal, monkeypatch):
 def test_training_state_round_trip_continues_the_ramps_bitwise(monkeypatch, tmp_path):
     """``save_to_file`` is the reference's snapshot -- parameters only: a run resumed from it restarts its ramps (shown).
     ``save_training_state`` at step 2 into a fresh model: step 3 equals the uninterrupted run's, bit for bit"""
-    KA.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     kw = dict(anneal_kl=True, anneal_kl_itermax=3, anneal_yloss=True, anneal_yloss_itermax=3, anneal_learning_rate=True,
               anneal_lr_itermax=3)
     spec_noise = M.ModelSpec(kind='drvae', dim_x=13, dim_y=2, dim_z1=5, dim_z3=4, L=2)
@@ -505,9 +503,8 @@ def _dp_worker(rank, world, port, q):
                           LOCAL_RANK=str(rank))
         torch.set_num_threads(1)
         import drvae_amd.kernels as K
-        for mod in (kernel_ref, KC, KA):
-            for name in mod.FUNCTIONS:
-                setattr(K, name, getattr(mod, name))
+        for name in kernel_ref.FUNCTIONS:
+            setattr(K, name, getattr(kernel_ref, name))
         from drvae_amd import dist as D
         D.init_from_env(backend='gloo')
         spec, batch, noises = case('drvae')
@@ -524,7 +521,7 @@ def _dp_worker(rank, world, port, q):
 
 
 def test_two_ranks_equal_one_rank_with_every_schedule_on(monkeypatch):
-    KA.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec, batch, noises = case('drvae')
     single = _dp_steps(spec, batch, noises[:N_STEPS], None, None)
     ctx = mp.get_context('spawn')
@@ -551,7 +548,7 @@ def test_every_recorded_form_orders_the_next_head_behind_the_tail(monkeypatch):
     """cfg-2 shape (150 rows): whichever way the annealed step is recorded, the next step's first launch -- which rewrites
     the record and the ELBO / CMPL weights -- is ordered behind this step's tail (``_head_behind_tail``, asserted inside
     ``_step_tail``); the single-process form keeps its side-chain sweep and loss scalars, i.e. there IS something to order"""
-    KA.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     from drvae_amd.schedule import StepSchedule, Tail
     spec = M.ModelSpec(kind='drvae')
     params = M.init_params(spec, 3, as_numpy=True)
@@ -579,7 +576,7 @@ def test_dual_graph_annealed_steps_equal_eager_steps_bitwise(monkeypatch):
     engine's, bit for bit, and no wait finds its flag unpublished"""
     from tests import fold_trace as FT
     import drvae_amd.tuning as T
-    KA.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     # (the unfolded forms on either side: the CPU stand-ins of the folded launches agree with them to rounding only --
     # tests/test_fold_rows_cpu.py --, the device's bit for bit -- tests/test_gpu_anneal.py runs the folded step)
     monkeypatch.setenv('DRVAE_TUNE', 'fold_rows=0')
@@ -591,7 +588,7 @@ def test_dual_graph_annealed_steps_equal_eager_steps_bitwise(monkeypatch):
     for e in (eager, dual):
         set_batch(e, batch)
         e.training = True
-    functions = sorted(set(kernel_ref.FUNCTIONS + KC.FUNCTIONS + KA.FUNCTIONS))
+    functions = sorted(set(kernel_ref.FUNCTIONS))
     for step in range(N_STEPS):
         eager.train_step()
         tail = dual._step_tail(False, on_gpu=True)

@@ -2,7 +2,7 @@
 references of tests/avg_ref.py against their own bounds and the faulty emulations, construction and refusals, the step with
 both switches off, AdamW against ``torch.optim.AdamW`` in float64, the average against its float64 recurrence, the
 ``averaged_parameters()`` context, ``fit``, resuming, data parallelism and the dual-graph schedule -- with the HIP launchers
-replaced by their plain-PyTorch references (tests/kernel_ref_avg.py on top of the earlier stand-ins).  The kernels themselves
+replaced by their plain-PyTorch references (tests/kernel_ref.py).  The kernels themselves
 are checked on the GPU (tests/test_gpu_avg.py)."""
 import os
 
@@ -14,9 +14,6 @@ import torch.multiprocessing as mp
 from oracle import models_ref as M
 from tests import avg_ref as AR
 from tests import kernel_ref
-from tests import kernel_ref_anneal as KA
-from tests import kernel_ref_avg as KV
-from tests import kernel_ref_clip as KC
 from tests import optim_ref as R
 from tests.test_anneal_cpu import _free_port, _launch_log, _model_batch, tiny_model
 from tests.test_anneal_cpu import case as small_case
@@ -111,7 +108,7 @@ def test_models_construct_with_the_new_switches(kind):
 
 
 def test_adamax_launcher_refuses_decoupled_decay_and_a_bad_average(monkeypatch):
-    KV.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     import drvae_amd.kernels as K
     p, g, m, u = (torch.ones(8) for _ in range(4))
     step = torch.ones(1, dtype=torch.int32)
@@ -167,7 +164,7 @@ def test_the_library_validates_the_trailing_fields_before_any_launch():
 
 
 def test_a_late_change_of_ema_decay_raises(monkeypatch):
-    KV.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     model = tiny_model('drvae')
     model.ema_decay = 0.5                  # the attribute idiom works until the engine is built
     assert hasattr(model.engine().arena, 'avg')
@@ -187,10 +184,10 @@ def test_switches_off_is_the_step_as_it_was(name, monkeypatch):
     """the launch list with every launch's keyword names, and every bit of the result: the extended stand-ins with the
     switches off == the wrapped stand-ins (which know neither keyword); no average is allocated"""
     case, spec, params = case_of(name)
-    functions = sorted(set(kernel_ref.FUNCTIONS + KC.FUNCTIONS + KA.FUNCTIONS) - {'smalln_ws_numel', 'col_moment_blocks',
+    functions = sorted(set(kernel_ref.FUNCTIONS) - {'smalln_ws_numel', 'col_moment_blocks',
                                                                                    'nll_raw_cs_shape', 'heads_tiles'})
     out = {}
-    for tag, install, kw in (('parent', KA.install, {}), ('off', KV.install, dict(ema_decay=None))):
+    for tag, install, kw in (('parent', kernel_ref.install, {}), ('off', kernel_ref.install, dict(ema_decay=None))):
         with pytest.MonkeyPatch.context() as outer:
             install(outer)
             eng, arena = make_engine(spec, params, **kw)
@@ -206,7 +203,7 @@ def test_switches_off_is_the_step_as_it_was(name, monkeypatch):
     assert not any({'avg', 'avg_decay', 'decoupled'} & set(kw) for _, kw in b[0])
     for x, y in zip(a[1:], b[1:]):
         assert torch.equal(x, y)
-    assert KV.CALLS == {'decoupled_sweeps': 0, 'averaged_sweeps': 0}
+    assert kernel_ref.CALLS['decoupled_sweeps'] == 0 and kernel_ref.CALLS['averaged_sweeps'] == 0
 
 
 # ------------------------------------------------------------------------------------------------ 4. AdamW against torch
@@ -234,9 +231,9 @@ class AdamW64:
         if self.max_norm is not None:
             torch.nn.utils.clip_grad_norm_(list(self.p.values()), self.max_norm, norm_type=2)
         if self.lr_itermax:
-            scale = float(KA.record(self.iters, (0, 0), 0, (0, 0), self.lr_itermax)[3])
+            scale = float(kernel_ref.record(self.iters, (0, 0), 0, (0, 0), self.lr_itermax)[3])
             for grp in self.opt.param_groups:
-                grp['lr'] = KA.lr_effective(self.cfg.learning_rate, torch.tensor([scale]))
+                grp['lr'] = kernel_ref.lr_effective(self.cfg.learning_rate, torch.tensor([scale]))
         self.opt.step()
         self.iters += 1
 
@@ -250,7 +247,7 @@ class AdamW64:
 @pytest.mark.parametrize('clip', [False, True], ids=['unclipped', 'clipped'])
 @pytest.mark.parametrize('name', MODEL_CASES)
 def test_adamw_steps_against_torch_in_float64(name, clip, anneal, monkeypatch):
-    KV.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     case, spec, params = case_of(name)
     kw = dict(optim_alg='adamw')
     if anneal:
@@ -271,7 +268,7 @@ def test_adamw_steps_against_torch_in_float64(name, clip, anneal, monkeypatch):
         eng.train_step(noise)
         ref.step(case['batch'], noise)
         compare_state(arena, ref, '%s step %d' % (name, i))
-    assert KV.CALLS['decoupled_sweeps'] >= len(noises)
+    assert kernel_ref.CALLS['decoupled_sweeps'] >= len(noises)
     # ... and the coupled form is NOT within that tolerance of it (weight_decay is 0.05 in these cases): the check sees the switch
     coupled, carena = make_engine(spec, params, max_grad_norm=thr, **dict(kw, optim_alg='adam'))
     if anneal:
@@ -286,7 +283,7 @@ def test_adamw_steps_against_torch_in_float64(name, clip, anneal, monkeypatch):
 # ------------------------------------------------------------------------------------------------ 5. the average
 @pytest.mark.parametrize('name', MODEL_CASES + ['tiny_drvae_adamax'])
 def test_average_equals_the_float64_recurrence_over_the_trajectory(name, monkeypatch):
-    KV.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     case, spec, params = case_of(name)
     eng, arena = make_engine(spec, params, ema_decay=D)
     assert torch.equal(arena.avg, arena.param)                 # starts as the initial parameters
@@ -312,12 +309,12 @@ def test_average_equals_the_float64_recurrence_over_the_trajectory(name, monkeyp
     assert torch.equal(arena.avg[n:], arena.param[n:])
     for pad in arena.pads(arena.avg):
         assert not pad.any()
-    assert KV.CALLS['averaged_sweeps'] == len(noises)
+    assert kernel_ref.CALLS['averaged_sweeps'] == len(noises)
 
 
 @pytest.mark.parametrize('name', ['tiny_drvae', 'tiny_drvae_adamax'])
 def test_a_skipped_step_leaves_the_average_alone(name, monkeypatch):
-    KV.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     case, spec, params = case_of(name)
     eng, arena = make_engine(spec, params, max_grad_norm=1e6, ema_decay=D)
     set_batch(eng, case['batch'])
@@ -331,14 +328,14 @@ def test_a_skipped_step_leaves_the_average_alone(name, monkeypatch):
     assert eng.clip_stats()['skipped_last']
     assert torch.equal(arena.avg, before)
     # the faulty stand-in that moves it anyway is seen by the same comparison
-    KV.FAULT['name'] = 'moved_on_skipped_step'
+    kernel_ref.FAULT['name'] = 'moved_on_skipped_step'
     eng.train_step(case['noises'][1])
     assert eng.clip_stats()['skipped_last'] and not torch.equal(arena.avg, before)
 
 
 # ------------------------------------------------------------------------------------------------ 6. the context
 def test_averaged_parameters_context(monkeypatch, tmp_path):
-    KV.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     model = tiny_model('drvae', ema_decay=D)
     batch = _model_batch(model)
     spec_noise = M.ModelSpec(kind='drvae', dim_x=13, dim_y=2, dim_z1=5, dim_z3=4, L=2)
@@ -411,7 +408,7 @@ def _fit_once(monkeypatch, tmp_path, tag, **kw):
 
 def test_fit_evaluates_and_snapshots_the_average(monkeypatch, tmp_path):
     import re
-    KV.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     runs = {}
     for tag, kw, ema_eval in (('off', {}, True), ('avg', dict(ema_decay=D), True), ('live', dict(ema_decay=D), False)):
         model, logs, fn, seen, (tr, va, _loader) = _fit_once(monkeypatch, tmp_path, tag, **kw)
@@ -443,7 +440,7 @@ def test_fit_evaluates_and_snapshots_the_average(monkeypatch, tmp_path):
 
 # ------------------------------------------------------------------------------------------------ 8. resume
 def test_training_state_round_trip_carries_the_average_bitwise(monkeypatch, tmp_path):
-    KV.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     kw = dict(ema_decay=D, optim_alg='adamw')
     spec_noise = M.ModelSpec(kind='drvae', dim_x=13, dim_y=2, dim_z1=5, dim_z3=4, L=2)
     noises = [M.make_noise(spec_noise, 8, seed=70 + i) for i in range(3)]
@@ -472,7 +469,7 @@ def test_training_state_round_trip_carries_the_average_bitwise(monkeypatch, tmp_
 def test_a_pending_stash_does_not_leak_the_old_average_into_loaded_weights(monkeypatch):
     """``.to()`` retires the engine and stashes the state; parameters loaded before the next engine is built must not meet
     the stashed average of the OLD weights.  Inside ``averaged_parameters()`` the state is neither moved nor saved"""
-    KV.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     model = tiny_model('drvae', ema_decay=D)
     batch = _model_batch(model)
     spec_noise = M.ModelSpec(kind='drvae', dim_x=13, dim_y=2, dim_z1=5, dim_z3=4, L=2)
@@ -516,9 +513,8 @@ def _dp_worker(rank, world, port, q):
                           LOCAL_RANK=str(rank))
         torch.set_num_threads(1)
         import drvae_amd.kernels as K
-        for mod in (kernel_ref, KC, KA, KV):
-            for name in mod.FUNCTIONS:
-                setattr(K, name, getattr(mod, name))
+        for name in kernel_ref.FUNCTIONS:
+            setattr(K, name, getattr(kernel_ref, name))
         from drvae_amd import dist as DD
         DD.init_from_env(backend='gloo')
         spec, batch, noises = small_case('drvae')
@@ -535,7 +531,7 @@ def _dp_worker(rank, world, port, q):
 
 
 def test_two_ranks_keep_bit_identical_averages_equal_to_one_rank(monkeypatch):
-    KV.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec, batch, noises = small_case('drvae')
     single = _dp_steps(spec, batch, noises[:N_STEPS], None, None)
     ctx = mp.get_context('spawn')
@@ -558,7 +554,7 @@ def test_two_ranks_keep_bit_identical_averages_equal_to_one_rank(monkeypatch):
 
 
 def test_the_broadcast_of_data_parallelism_carries_the_average(monkeypatch):
-    KV.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     from drvae_amd import dist as DD
     sent = []
     monkeypatch.setattr(DD, 'broadcast', lambda t: sent.append(t.data_ptr()))
@@ -581,7 +577,7 @@ def test_dual_graph_schedule_sweeps_the_average_on_both_halves(monkeypatch):
     from tests import fold_trace as FT
     import drvae_amd.kernels as K
     import drvae_amd.tuning as T
-    KV.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     monkeypatch.setenv('DRVAE_TUNE', 'fold_rows=0')
     monkeypatch.setattr(T, '_VALUES', None)
     spec, batch, _ = small_case('drvae')
@@ -598,7 +594,7 @@ def test_dual_graph_schedule_sweeps_the_average_on_both_halves(monkeypatch):
     calls = []
     real = K.adam_l2
     monkeypatch.setattr(K, 'adam_l2', lambda *a, **k: (calls.append((a[0], k)), real(*a, **k))[1])
-    functions = sorted(set(kernel_ref.FUNCTIONS + KC.FUNCTIONS + KA.FUNCTIONS + KV.FUNCTIONS))
+    functions = sorted(set(kernel_ref.FUNCTIONS))
     for step in range(N_STEPS):
         eager.train_step()
         tail = dual._step_tail(False, on_gpu=True)

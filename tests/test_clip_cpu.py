@@ -1,7 +1,7 @@
 """CPU: gradient-norm clipping and the non-finite guard of the fused train step -- the reference's checks against faulty
 emulations, construction, the schedule decision, the clipped step against torch's clip + optimiser in float64, the skipped
 step and the optimiser-state round trip -- with the HIP launchers replaced by their plain-PyTorch references
-(tests/kernel_ref.py, tests/kernel_ref_clip.py).  The kernels themselves are checked on the GPU (tests/test_gpu_clip.py)."""
+(tests/kernel_ref.py).  The kernels themselves are checked on the GPU (tests/test_gpu_clip.py)."""
 import dataclasses
 import math
 
@@ -11,7 +11,7 @@ import torch
 
 from oracle import models_ref as M
 from tests import clip_ref as R
-from tests import kernel_ref_clip as KC
+from tests import kernel_ref
 from tests.golden import cases as C
 from tests.test_dropout_cpu import set_batch, tiny_model
 
@@ -134,7 +134,7 @@ def test_reference_bound_catches_a_missing_epsilon():
 
 def test_stand_in_record_matches_the_reference(monkeypatch):
     import drvae_amd.kernels as K
-    KC.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     for cls in R.CLASSES:
         for n in (1, 5, 4099):
             g = R.values(cls, n)
@@ -176,8 +176,7 @@ def _launch_log(monkeypatch_ctx, names):
 
 @pytest.mark.parametrize('name', ['tiny_drvae', 'tiny_pvae', 'tiny_vfae', 'tiny_drvae_adamax'])
 def test_switch_off_launches_what_it_always_did(name, monkeypatch):
-    from tests import kernel_ref
-    KC.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     case, spec, params = case_of(name)
     lists = {}
     for tag, kw in (('absent', None), ('none', dict(max_grad_norm=None)), ('set', dict(max_grad_norm=0.5))):
@@ -188,7 +187,7 @@ def test_switch_off_launches_what_it_always_did(name, monkeypatch):
             eng, _ = make_engine(spec, params, **kw)
         set_batch(eng, case['batch'])
         with pytest.MonkeyPatch.context() as mp:
-            log = _launch_log(mp, kernel_ref.FUNCTIONS + KC.FUNCTIONS)
+            log = _launch_log(mp, kernel_ref.FUNCTIONS)
             eng.train_step(case['noises'][0])
         lists[tag] = log
         assert (eng.clip_rec is None) == (tag != 'set') and (eng.clip_part is None) == (tag != 'set')
@@ -202,7 +201,7 @@ def test_switch_off_launches_what_it_always_did(name, monkeypatch):
 def test_a_clipped_step_keeps_nothing_behind_the_join(monkeypatch):
     """cfg-2 shape (the default DrVAE configuration, 150 rows): the unclipped single-process step runs the classifier's weight
     gradient and the decoder heads' half of the sweep behind the join; the clipped one is recorded like an exchange form"""
-    KC.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec = M.ModelSpec(kind='drvae')
     params = M.init_params(spec, 3, as_numpy=True)
     batch = M.make_batch(spec, 150, seed=5)
@@ -240,7 +239,7 @@ def test_a_clipped_step_keeps_nothing_behind_the_join(monkeypatch):
 # ------------------------------------------------------------------------------------------------ 4. the clipped step
 @pytest.mark.parametrize('name', STEP_CASES)
 def test_clipped_step_against_torch_in_float64(name, monkeypatch):
-    KC.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     case, spec, params = case_of(name)
     noise = case['noises'][0]
     plain, parena = make_engine(spec, params)
@@ -270,7 +269,7 @@ def test_clipped_step_against_torch_in_float64(name, monkeypatch):
 
 @pytest.mark.parametrize('name', ['tiny_drvae', 'tiny_drvae_wn', 'tiny_drvae_adamax'])
 def test_threshold_above_the_norm_changes_no_bit(name, monkeypatch):
-    KC.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     case, spec, params = case_of(name)
     states = []
     for kw in ({}, dict(max_grad_norm=1e6), dict(max_grad_norm=float('inf'))):
@@ -289,7 +288,7 @@ def test_threshold_above_the_norm_changes_no_bit(name, monkeypatch):
 @pytest.mark.parametrize('bad', [float('inf'), float('nan')], ids=['inf', 'nan'])
 @pytest.mark.parametrize('name', ['tiny_drvae', 'tiny_drvae_adamax'])
 def test_a_non_finite_gradient_skips_the_step_and_leaves_no_trace(name, bad, monkeypatch):
-    KC.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     case, spec, params = case_of(name)
     noises = case['noises']
     eng, arena = make_engine(spec, params, max_grad_norm=float('inf'))
@@ -317,7 +316,7 @@ def test_a_non_finite_gradient_skips_the_step_and_leaves_no_trace(name, bad, mon
 
 
 def test_a_skipped_first_step_divides_by_nothing(monkeypatch):
-    KC.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     case, spec, params = case_of('tiny_drvae')
     eng, arena = make_engine(spec, params, max_grad_norm=1.0)
     set_batch(eng, case['batch'])
@@ -331,7 +330,7 @@ def test_a_skipped_first_step_divides_by_nothing(monkeypatch):
 
 # ------------------------------------------------------------------------------------------------ 6. the state travels
 def test_stash_and_restore_keep_the_skip_count(monkeypatch):
-    KC.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     model = tiny_model('drvae', max_grad_norm=3.0)
     eng = model.engine()
     eng.clip_rec[3] = 5

@@ -12,8 +12,6 @@ import torch.nn.functional as F
 from oracle import models_ref as M
 from tests import counts_ref as CR
 from tests import kernel_ref
-from tests import kernel_ref_counts as KC
-from tests import kernel_ref_nb as KN
 from tests import nb_ref as R
 from tests import ref64
 from tests.golden import cases as C
@@ -181,7 +179,7 @@ def test_switches_off_is_the_step_as_it_was(kind, type_rec):
     noises = [M.make_noise(spec, 16, seed=10 + i) for i in range(3)]
     names = sorted(set(kernel_ref.FUNCTIONS) - {'smalln_ws_numel', 'col_moment_blocks', 'nll_raw_cs_shape', 'heads_tiles'})
     out = {}
-    for tag, install in (('before', KN.install), ('after', KC.install)):
+    for tag, install in (('before', kernel_ref.install), ('after', kernel_ref.install)):
         with pytest.MonkeyPatch.context() as mp:
             install(mp)
             eng, arena = make_engine(spec, params, type_rec=type_rec)
@@ -199,7 +197,7 @@ def test_switches_off_is_the_step_as_it_was(kind, type_rec):
     assert not [n for n, _ in b[0] if n == 'batch_feed'] and [n for n, _ in b[0] if n == 'rows_gather']
     rec = [kw for n, kw in b[0] if n == 'rec_nll_rows']
     assert len(rec) == 3 and all(kw == ['coef', 'dpre', 'kind', 'shift', 'xidx'] for kw in rec)
-    assert KC.CALLS['split_feed'] == 0 and KC.CALLS['lib_rows'] == 0 and KC.CALLS['plain_rows'] == 3
+    assert kernel_ref.CALLS['split_feed'] == 0 and kernel_ref.CALLS['lib_rows'] == 0 and kernel_ref.CALLS['plain_rows'] == 3
 
 
 # ----------------------------------------------------------------------- 5. the fused step on the stand-ins
@@ -271,11 +269,11 @@ def run_against_reference(kind, variant, sw, dev='cpu', tol=((2e-5, 2e-6), (3e-4
 @pytest.mark.parametrize('variant,sw', CASES)
 @pytest.mark.parametrize('kind', ['drvae', 'pvae', 'vfae'])
 def test_fused_step_matches_the_float64_model_reference(kind, variant, sw, monkeypatch):
-    KC.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     run_against_reference(kind, variant, sw)
     lib = bool(SWITCHES[sw].get('library_size'))
-    assert KC.CALLS['split_feed'] > 0 and KC.CALLS['plain_feed'] == 0
-    assert (KC.CALLS['lib_rows'] > 0) == lib and (KC.CALLS['plain_rows'] > 0) == (not lib)
+    assert kernel_ref.CALLS['split_feed'] > 0 and kernel_ref.CALLS['plain_feed'] == 0
+    assert (kernel_ref.CALLS['lib_rows'] > 0) == lib and (kernel_ref.CALLS['plain_rows'] > 0) == (not lib)
 
 
 def _counts_dataset(kind, n, seed, dev='cpu', decades=2.0, lo=0.0):
@@ -342,20 +340,16 @@ def host_fed_equals_feed(kind, dev, extra=None, steps=3, captured=False, use_s=F
 @pytest.mark.parametrize('kind,use_s', [('drvae', False), ('pvae', False), ('vfae', False), ('vfae', True)])
 def test_host_fed_step_equals_feed_step_bit_for_bit(kind, use_s, monkeypatch):
     """(the sampler feed binds the batch-independent plan: every case here runs on it)"""
-    KC.install(monkeypatch)
-    if use_s:
-        from tests import kernel_ref_nuisance_masked as KM
-        KM.install(monkeypatch)
-        KC.install_over(monkeypatch)
+    kernel_ref.install(monkeypatch)
     host_fed_equals_feed(kind, 'cpu', use_s=use_s)
-    assert KC.CALLS['split_feed'] >= 6 and KC.CALLS['plain_feed'] == 0
+    assert kernel_ref.CALLS['split_feed'] >= 6 and kernel_ref.CALLS['plain_feed'] == 0
 
 
 @pytest.mark.parametrize('kind', ['drvae', 'vfae'])
 def test_two_shards_sum_to_the_whole_batch(kind, monkeypatch):
     """row-sharded data parallelism needs nothing new (transform and size factor are row-local): two engines on rows [0, 8) and
     [8, 16) with the global counts and their rows of the noise hold loss scalars and gradients that SUM to the whole batch's"""
-    KC.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec, batch = _case(kind)
     ref = R.ModelRef(spec, seed=9)
     noise = M.make_noise(spec, 16, seed=4)
@@ -375,7 +369,7 @@ def test_two_shards_sum_to_the_whole_batch(kind, monkeypatch):
         return arena.xchg.clone().double().numpy()
     whole, parts = xchg(0, 16), xchg(0, 8) + xchg(8, 16)
     np.testing.assert_allclose(parts, whole, rtol=2e-5, atol=2e-6 * np.abs(whole).max())
-    assert np.abs(whole).max() > 1 and KC.CALLS['lib_rows'] > 0
+    assert np.abs(whole).max() > 1 and kernel_ref.CALLS['lib_rows'] > 0
 
 
 COMBINED = dict(dropout_rate=0.25, max_grad_norm=1.0, anneal_kl=True, anneal_kl_itermax=10, ema_decay=0.9)
@@ -417,21 +411,21 @@ def combined_against_reference(dev='cpu', tol=((2e-5, 2e-6), None, (1e-4, 2e-5))
 
 
 def test_combined_riders_match_the_float64_model_reference(monkeypatch):
-    KC.install(monkeypatch, riders=True)
+    kernel_ref.install(monkeypatch)
     combined_against_reference()
-    assert KC.CALLS['split_feed'] > 0 and KC.CALLS['lib_rows'] > 0
+    assert kernel_ref.CALLS['split_feed'] > 0 and kernel_ref.CALLS['lib_rows'] > 0
 
 
 def test_combined_riders_host_fed_equals_feed(monkeypatch):
     """dropout, clipping, KL annealing and the parameter average together with both switches: both pieces are row-local, so
     the riders need nothing new -- the host-fed and the feed step stay bit-identical and finite"""
-    KC.install(monkeypatch, riders=True)
+    kernel_ref.install(monkeypatch)
     host_fed_equals_feed('drvae', 'cpu', extra=COMBINED)
 
 
 # ----------------------------------------------------------------------------------------------- 6. inference
 def test_inference_scales_by_the_right_rows_factor(monkeypatch):
-    KC.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     ds = _counts_dataset('drvae', 16, 3)
     m = tiny_model('drvae', type_rec='nb', x_transform='log1p', library_size=True)
     plain = tiny_model('drvae', type_rec='nb')

@@ -1,6 +1,6 @@
 """CPU, world_size 2 over gloo: the data-parallel train step of a negative-binomial model with the raw-count switches
 (``x_transform='log1p'``, ``library_size=True``: both row-local) reproduces the single-process step on the concatenated batch --
-the pattern of ``tests/test_dp_gloo.py``, with the stand-ins of ``tests/kernel_ref_counts.py``."""
+the pattern of ``tests/test_dp_gloo.py``, with the stand-ins of ``tests/kernel_ref.py``."""
 import os
 
 import numpy as np
@@ -18,11 +18,8 @@ SW = dict(type_rec='nb', x_transform='log1p', library_size=True)
 def _install_refs():
     import drvae_amd.kernels as K
     from tests import kernel_ref as R
-    from tests import kernel_ref_counts as KC
     for name in R.FUNCTIONS:
         setattr(K, name, getattr(R, name))
-    KC.INNER['feed'] = R.batch_feed
-    K.batch_feed, K.rec_nll_rows = KC.batch_feed, KC.rec_nll_rows
 
 
 def _case(kind):
@@ -82,11 +79,11 @@ def _worker(rank, world, port, kind, q):
 
 @pytest.mark.parametrize('kind', ['drvae', 'pvae', 'vfae'])
 def test_two_ranks_equal_one_rank_with_the_count_switches(kind, monkeypatch):
-    from tests import kernel_ref_counts as KC
-    KC.install(monkeypatch)
+    from tests import kernel_ref
+    kernel_ref.install(monkeypatch)
     spec, batch, noises, params = _case(kind)
     single = _run_steps(spec, params, batch, noises, None, None)
-    assert KC.CALLS['split_feed'] > 0 and KC.CALLS['lib_rows'] > 0 and np.isfinite(single[1]).all()
+    assert kernel_ref.CALLS['split_feed'] > 0 and kernel_ref.CALLS['lib_rows'] > 0 and np.isfinite(single[1]).all()
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
     port = _free_port()

@@ -1,6 +1,6 @@
 """CPU: hidden-layer dropout in the fused train step -- sites, masks, descriptor rows, the chain's dropped operands and the
-schedule decision -- with the HIP launchers replaced by their plain-PyTorch references (tests/kernel_ref.py,
-tests/kernel_ref_dropout.py).  The kernels themselves and the device masks are checked on the GPU (tests/test_gpu_dropout.py)."""
+schedule decision -- with the HIP launchers replaced by their plain-PyTorch references (tests/kernel_ref.py).
+The kernels themselves and the device masks are checked on the GPU (tests/test_gpu_dropout.py)."""
 import warnings
 
 import numpy as np
@@ -8,7 +8,7 @@ import pytest
 import torch
 
 from oracle import models_ref as M
-from tests import kernel_ref_dropout as KD
+from tests import kernel_ref
 from tests.golden import cases as C
 
 CHAIN_LAYERS = {'c_enc': 'L_enc', 'c_decx': 'L_decx', 'c_clf': 'L_clf', 'c_top': 'L_top', 'c_dz1': 'L_dz1'}
@@ -166,7 +166,7 @@ def test_models_construct_with_dropout_and_warn_once(kind):
 # ------------------------------------------------------------------------------------------------ 2. rate 0
 @pytest.mark.parametrize('name', ['tiny_drvae', 'tiny_pvae', 'tiny_vfae'])
 def test_rate_zero_is_untouched(name, monkeypatch):
-    KD.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     case = C.model_case(name)
     spec, params = case['spec'], M.init_params(case['spec'], case['param_seed'], as_numpy=True)
     eng, _ = make_engine(spec, params)
@@ -190,9 +190,9 @@ def test_rate_zero_is_untouched(name, monkeypatch):
     eng.training = False
     eng.draw_noise()
     eng.forward()
-    assert KD.CALLS == {'fill_noise_rows': 0, 'mask_scale': 0}
+    assert kernel_ref.CALLS['fill_noise_rows'] == 0 and kernel_ref.CALLS['mask_scale'] == 0
     drp.train_step()
-    assert KD.CALLS['fill_noise_rows'] == 1 and KD.CALLS['mask_scale'] == 2 * len(q.drop_sites)
+    assert kernel_ref.CALLS['fill_noise_rows'] == 1 and kernel_ref.CALLS['mask_scale'] == 2 * len(q.drop_sites)
 
 
 # ------------------------------------------------------------------------------------------------ 3. column-constant masks
@@ -202,10 +202,10 @@ def test_rate_zero_is_untouched(name, monkeypatch):
 def test_column_constant_masks_reduce_to_the_undropped_step(name, keep, fused, monkeypatch):
     """a mask that is the same in every row is a diagonal scaling of the next layer's weight: losses and every gradient of
     the dropped step equal those of a rate-0 engine with W' = W diag(m / keep) behind each site (dW = dW' diag(m / keep))"""
-    KD.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     eng, ref, arena, rarena = dropped_vs_folded(name, keep, fused)
-    assert KD.CALLS['fill_noise_rows'] == 0, 'injected noise and injected masks: nothing is drawn'
-    assert KD.CALLS['mask_scale'] == 2 * len(eng.dropout_sites())
+    assert kernel_ref.CALLS['fill_noise_rows'] == 0, 'injected noise and injected masks: nothing is drawn'
+    assert kernel_ref.CALLS['mask_scale'] == 2 * len(eng.dropout_sites())
     compare_step(eng, ref, arena, rarena, '%s keep %.1f' % (name, keep))
 
 
@@ -227,7 +227,7 @@ def _row_keys(p, row0):
 
 def test_masks_are_keyed_by_global_row(monkeypatch):
     """two plans over the two halves of a batch (``row0`` = 0 and k) draw, row for row, the masks of the single plan"""
-    KD.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec = C.tiny_spec('drvae', dim_y=3, h_clf=[3], h_de_x=[8, 5])
     params = M.init_params(spec, 3, as_numpy=True)
     batch = M.make_batch(spec, 12, seed=4)
@@ -281,7 +281,7 @@ def test_masks_are_keyed_by_global_row(monkeypatch):
 # ------------------------------------------------------------------------------------------------ 5. evaluation
 @pytest.mark.parametrize('name', ['tiny_drvae', 'tiny_vfae', 'tiny_pvae'])
 def test_evaluation_drops_nothing(name, monkeypatch):
-    KD.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     case = C.model_case(name)
     spec, params = case['spec'], M.init_params(case['spec'], case['param_seed'], as_numpy=True)
     out = []
@@ -294,7 +294,7 @@ def test_evaluation_drops_nothing(name, monkeypatch):
         out.append(eng.losses())
         eng.draw_noise()              # an evaluation draw skips the keep rows as it skips the input noise
         eng.forward()
-    assert KD.CALLS == {'fill_noise_rows': 0, 'mask_scale': 0}
+    assert kernel_ref.CALLS['fill_noise_rows'] == 0 and kernel_ref.CALLS['mask_scale'] == 0
     assert list(out[0].values()) == list(out[1].values())          # bit-equal
 
 
@@ -304,7 +304,7 @@ def test_a_plan_with_sites_never_draws_ahead(name, monkeypatch):
     """the side chain's draw-ahead is released when the encoder backward starts; with sites that backward reads its masks:
     every tail the schedule builds for such a plan has ``noise_ahead`` off, and the recorded step draws at its head"""
     import drvae_amd.kernels as K
-    KD.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     case = C.model_case(name)
     spec, params = case['spec'], M.init_params(case['spec'], case['param_seed'], as_numpy=True)
     ahead = {}

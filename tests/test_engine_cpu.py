@@ -462,3 +462,35 @@ def test_chain_refuses_padded_products_over_column_slices(monkeypatch):
     assert _Chain._pad_ok(wide[:, :8])                            # a multiple of 4: nothing to pad
     assert not _Chain._pad_ok(wide[:, :10])                       # a slice with live neighbours
     assert not _Chain._pad_ok(torch.zeros(6, 12)[:, 1:11])
+
+
+# functions of ``drvae_amd.kernels`` that never reach the library or only ask it a host question (plain python on plain
+# arguments): they need no stand-in, the CPU tests call them as they are
+HOST_ONLY = {'gemm_force_tiling', 'gemm_set_option', 'x3_refusal', 'x3_pair_refusal', 'keep_threshold', 'noise_table',
+             'clip_state', 'clip_set_max_norm', 'clip_record', 'clip_partials', 'clip_record_values', 'sumsq_partials',
+             'mmd_masked_shapes'}
+
+
+def test_the_stand_ins_cover_every_launcher_with_its_present_signature():
+    """``tests/kernel_ref.py`` stays complete: every public launcher has a stand-in in ``FUNCTIONS`` with the same positional
+    parameters, and every keyword the launcher takes binds to it (a launcher that forwards ``**kw`` is held to the keywords of
+    the function it forwards them to)"""
+    import inspect
+    import drvae_amd.kernels as K
+    launchers = {n: f for n, f in vars(K).items()
+                 if inspect.isfunction(f) and f.__module__ == K.__name__ and not n.startswith('_')}
+    assert HOST_ONLY <= set(launchers)
+    assert sorted(set(launchers) - HOST_ONLY - set(kernel_ref.FUNCTIONS)) == [], 'launchers without a stand-in'
+    assert sorted(set(kernel_ref.FUNCTIONS) - set(launchers)) == [], 'stand-ins of no launcher'
+    assert len(set(kernel_ref.FUNCTIONS)) == len(kernel_ref.FUNCTIONS)
+    forwards = {'gemm': K._gemm_desc, 'linear_bwd_pair': K._pair_descs}
+    P = inspect.Parameter
+    positional = lambda sig: [p.name for p in sig.parameters.values() if p.kind in (P.POSITIONAL_ONLY, P.POSITIONAL_OR_KEYWORD)]
+    for name in kernel_ref.FUNCTIONS:
+        want, got = inspect.signature(launchers[name]), inspect.signature(getattr(kernel_ref, name))
+        assert positional(got) == positional(want), name
+        keywords = [p.name for p in want.parameters.values() if p.kind == P.KEYWORD_ONLY]
+        if name in forwards:
+            keywords += [p.name for p in inspect.signature(forwards[name]).parameters.values()
+                         if p.kind == P.KEYWORD_ONLY and not p.name.startswith('_')]
+        got.bind_partial(**dict.fromkeys(positional(want) + keywords))

@@ -1,8 +1,8 @@
 """CPU: ``Tail.fold_rows`` -- the pairs' KL rows formed by ``z2f_post_bwd``, the classifier's data gradient by its forward
 launch.  (1) the checks of ``tests/fold_rows_ref.py`` hold the fp32 stand-ins of the folded launches and catch faulty
-emulations of them; (2) on the stand-ins of ``tests/kernel_ref_fold.py`` the folded dual-graph step, RUN in an order its
+emulations of them; (2) on the stand-ins of ``tests/kernel_ref.py`` the folded dual-graph step, RUN in an order its
 device flags allow, leaves what the unfolded step leaves; its recorded chains pass the checks of the FLAGS / SITES table;
-(3) with ``fold_rows=0``, or on the plain stand-ins of ``tests/kernel_ref.py``, the recorded step is the one recorded in
+(3) with ``fold_rows=0`` the recorded step is the one recorded in
 front of this schedule, argument for argument (``tests/golden/fold_rows_trace.json``)."""
 import json
 
@@ -13,7 +13,7 @@ import torch
 from tests import clf_launch_ref as CL
 from tests import fold_rows_ref as R
 from tests import fold_trace as FT
-from tests import kernel_ref, kernel_ref_fold
+from tests import kernel_ref
 
 
 # ------------------------------------------------------------------------------------------- (1) the checks
@@ -28,7 +28,7 @@ def _tied(case):
     """the case with kl_min at a raw value the stand-in computes: above, below and a tie"""
     if not case['shape'][3]:
         return case
-    _, host = _run(kernel_ref_fold, case)
+    _, host = _run(kernel_ref, case)
     tied = R.with_tie(case, host['raw'][1])
     raw = host['raw'][1]
     assert (raw == tied['kl_min']).any() and (raw > tied['kl_min']).any()
@@ -48,7 +48,7 @@ def _kl_bits(case, o, host):
 @pytest.mark.parametrize('case', R.Z2F_CASES, ids=lambda c: c['name'])
 def test_the_stand_in_of_the_folded_launch_passes_every_check(case):
     for c in (case, _tied(case)):
-        o, host = _run(kernel_ref_fold, c)
+        o, host = _run(kernel_ref, c)
         worst = R.z2f_verify(c, host, site=c['name'])
         assert max(worst.values()) <= 1.0 and _kl_bits(c, o, host) == 0.0
         # ... and the faultless emulation is bitwise the stand-in
@@ -85,7 +85,7 @@ def test_the_classifier_rider_s_stand_in_is_within_the_float64_bound(shape):
     d0, d1 = torch.randn(M, K1), torch.randn(M, K2)
     old = [d0.clone(), d1.clone()]
     dsts = [(d0, 0, 1.0, 0.5, K1, -1.0), (d1, K1, 1.0, 0.0)]
-    kernel_ref_fold.smalln_fwd(v['probs'], v['logits'], o['a1'], o['W'], o['bias'], o['a2'], ymarg=ym, fprop_kl=kf, dgrad=dsts)
+    kernel_ref.smalln_fwd(v['probs'], v['logits'], o['a1'], o['W'], o['bias'], o['a2'], ymarg=ym, fprop_kl=kf, dgrad=dsts)
     for (dst, *_), (ref, bnd) in zip(dsts, R.dgrad_reference(v['dqy'], v['probs'], o['W'], dsts, old)):
         assert float(R.excess(dst, ref, bnd).max()) <= 1.0
     # ... and a rider that forgets the second column block is not
@@ -109,7 +109,7 @@ def _tail(eng, monkeypatch, fold):
 
 
 def _three_steps(name, universal, fold, monkeypatch):
-    eng, arena, case = FT.make(name, universal, kernel_ref_fold.install, monkeypatch)
+    eng, arena, case = FT.make(name, universal, kernel_ref.install, monkeypatch)
     tail = _tail(eng, monkeypatch, fold)
     assert tail.dual and tail.fold_rows == fold
     losses, recs = [], []
@@ -123,9 +123,9 @@ def _three_steps(name, universal, fold, monkeypatch):
 @pytest.mark.parametrize('name,universal', [('tiny_drvae', False), ('tiny_drvae', True), ('tiny_drvae_prior', False)])
 def test_the_folded_step_leaves_what_the_unfolded_step_leaves(name, universal, monkeypatch):
     _, p1, l1, r1 = _three_steps(name, universal, True, monkeypatch)
-    assert kernel_ref_fold.CALLS['folded_kl'] == 3 and kernel_ref_fold.CALLS['folded_dgrad'] == 3
+    assert kernel_ref.CALLS['folded_kl'] == 3 and kernel_ref.CALLS['folded_dgrad'] == 3
     _, p0, l0, r0 = _three_steps(name, universal, False, monkeypatch)
-    assert kernel_ref_fold.CALLS['folded_kl'] == 0 and kernel_ref_fold.CALLS['folded_dgrad'] == 0
+    assert kernel_ref.CALLS['folded_kl'] == 0 and kernel_ref.CALLS['folded_dgrad'] == 0
     for a, b in zip(l1, l0):
         assert a.keys() == b.keys()
         for k in a:
@@ -144,7 +144,7 @@ def test_the_folded_chains_pass_the_checks_of_the_flag_table(universal, monkeypa
     import drvae_amd.kernels as K
     from drvae_amd.schedule import FLAGS, SITES
     from tests.test_step_sync import OTHER, Recorder
-    eng, _, case = FT.make('tiny_drvae', universal, kernel_ref_fold.install, monkeypatch)
+    eng, _, case = FT.make('tiny_drvae', universal, kernel_ref.install, monkeypatch)
     eng.set_noise(case['noises'][0])
     tail = _tail(eng, monkeypatch, True)
     assert tail.fold_rows
@@ -184,15 +184,9 @@ def golden():
 
 
 @pytest.mark.parametrize('name,universal', FT.CASES)
-def test_the_default_step_on_the_plain_stand_ins_is_the_recorded_one(name, universal, golden):
-    """the stand-ins of ``kernel_ref`` do not carry the folded forms: nothing folds, no new keyword reaches a launcher"""
-    assert FT.default_trace(name, universal) == golden['%s/%s' % (name, 'universal' if universal else 'structure')]
-
-
-@pytest.mark.parametrize('name,universal', FT.CASES)
 def test_fold_rows_0_records_the_old_sequence(name, universal, golden, monkeypatch):
     monkeypatch.setenv('DRVAE_TUNE', 'fold_rows=0')
-    got = FT.default_trace(name, universal, install=kernel_ref_fold.install)
+    got = FT.default_trace(name, universal)
     assert got == golden['%s/%s' % (name, 'universal' if universal else 'structure')]
 
 
@@ -205,12 +199,12 @@ def test_only_the_schedules_the_fold_is_for_take_it(monkeypatch):
     from tests.test_dropout_cpu import make_engine as drop_engine
     from tests.test_engine_cpu import set_batch
     from oracle import models_ref as M
-    kernel_ref_fold.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     monkeypatch.delenv('DRVAE_TUNE', raising=False)
     monkeypatch.setattr(T, '_VALUES', None)
     seen = {}
     for name in C.SMALL_MODEL_CASES:
-        eng, _, case = FT.make(name, False, kernel_ref_fold.install, monkeypatch)
+        eng, _, case = FT.make(name, False, kernel_ref.install, monkeypatch)
         for split in (False, True, 'captured', 'overlap'):
             t = eng._step_tail(split, on_gpu=True)
             cfg = eng.cfg

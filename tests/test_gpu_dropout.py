@@ -11,7 +11,7 @@ import torch
 
 from oracle import models_ref as M
 from tests import gemm_contract as G
-from tests import kernel_ref_dropout as KD
+from tests import kernel_ref
 from tests import ref64
 from tests.golden import cases as C
 from tests.ref64 import U
@@ -85,7 +85,7 @@ def test_fill_noise_rows_matches_the_reference_exactly(K, dev, n_rows, n_normal)
                 nmask[o:o + w] = True
             assert np.array_equal(g[nmask].view(np.int32), want_n.cpu().numpy()[nmask].view(np.int32))
             # the keep rows: the reference mask element for element, exactly 0.0 or 1.0
-            offs, vals = KD.keep_rows(d[nn:], thr, seed, ev)
+            offs, vals = kernel_ref.keep_rows(d[nn:], thr, seed, ev)
             assert len(offs) == int(d[nn:, 1].sum())
             assert np.array_equal(g[offs], vals) and set(np.unique(g[offs])) <= {0.0, 1.0}
             if rate == TINY_RATE and len(offs) > 1000:
@@ -106,7 +106,7 @@ def test_fill_noise_rows_keeps_the_stated_fraction(K, dev):
         z = (float(got.double().mean()) - keep) / math.sqrt(keep * (1 - keep) / n)
         print('rate %.1f: kept fraction %+.2f sigma from keep_thr / 2^32' % (rate, z))
         assert abs(z) <= 4.0
-        offs, vals = KD.keep_rows(d, thr, 1234, 0)
+        offs, vals = kernel_ref.keep_rows(d, thr, 1234, 0)
         assert np.array_equal(got.cpu().numpy()[offs], vals)
 
 

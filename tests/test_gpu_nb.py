@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from oracle import models_ref as M
-from tests import kernel_ref_nb as KN
+from tests import kernel_ref
 from tests import nb_ref as R
 from tests import ref64
 from tests.golden import cases as C
@@ -130,7 +130,7 @@ def test_shapes_gather_and_memory_contract(K, dev, X):
     ref64.check('d/da_t', first[1][:Mr, X:2 * X], ref['gt'], ref['gt_bound'])
     # the CPU stand-in
     o_ref, d_ref = torch.zeros(Mr), torch.zeros(Mr, 2 * X)
-    KN.rec_nll_rows(o_ref, xs, torch.cat([mu, th], 1), kind='nb', shift=R.MU_SHIFT, xidx=xi, coef=coef, dpre=d_ref)
+    kernel_ref.rec_nll_rows(o_ref, xs, torch.cat([mu, th], 1), kind='nb', shift=R.MU_SHIFT, xidx=xi, coef=coef, dpre=d_ref)
     np.testing.assert_allclose(first[0][:Mr].numpy(), o_ref.numpy(), rtol=2e-5, atol=1e-3)
     np.testing.assert_allclose(first[1][:Mr, :2 * X].numpy(), d_ref.numpy(), rtol=2e-4, atol=1e-5)
     # second call: the same bits

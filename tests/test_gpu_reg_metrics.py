@@ -1,4 +1,4 @@
-"""-m gpu: ``dv_reg_metrics`` against the float64 restatement of its two-pass arithmetic (tests/kernel_ref_reg.py).
+"""-m gpu: ``dv_reg_metrics`` against the float64 restatement of its two-pass arithmetic (``reg_metrics64`` of tests/kernel_ref.py).
 
 Tolerance 1e-9 * max(1, |v|): the inputs are fp32, exact in float64, and only the ORDER of at most 2^17 float64 additions
 differs between the kernel and numpy (n u ~ 1e-11); two orders of margin keep the test independent of the reduction tree."""
@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import kernel_ref_reg as KR
+from tests import kernel_ref
 from tests.golden import cases as C
 
 pytestmark = pytest.mark.gpu
@@ -35,7 +35,7 @@ def K():
 def test_reference_generated_case(K, dev):
     c = C.y_metric_cases()['Ycont']
     got = _run(K, torch.from_numpy(c['pred']).cuda(), torch.from_numpy(np.asarray(c['ylab'], np.float32)).cuda())
-    _close(got, KR.reg_metrics(c['pred'], np.asarray(c['ylab'], np.float32)))
+    _close(got, kernel_ref.reg_metrics64(c['pred'], np.asarray(c['ylab'], np.float32)))
     G = np.load(C.__file__.replace('cases.py', 'fit.npz'))
     for i, k in enumerate(('rmse', 'r2', 'pearr')):
         assert got[i] == pytest.approx(float(G['Ycont/' + k]), rel=1e-6)
@@ -52,7 +52,7 @@ def test_random_against_fp64(K, dev, n, Y, with_sel):
     sel = rs.permutation(M)[:n].astype(np.int32) if with_sel else None
     got = _run(K, torch.from_numpy(p).cuda(), torch.from_numpy(y).cuda(),
                sel=torch.from_numpy(sel).cuda() if with_sel else None)
-    _close(got, KR.reg_metrics(p, y, sel=sel))
+    _close(got, kernel_ref.reg_metrics64(p, y, sel=sel))
 
 
 @pytest.mark.parametrize('Y', [1, 3])
@@ -66,9 +66,9 @@ def test_row_strides(K, dev, Y):
     pv, yv = tp[:, 2:2 + Y], ty[:, :Y]
     assert not pv.is_contiguous() and not yv.is_contiguous()
     sel = rs.permutation(n)[:333].astype(np.int32)
-    _close(_run(K, pv, yv), KR.reg_metrics(wide_p[:, 2:2 + Y], wide_y[:, :Y]))
-    _close(_run(K, pv, yv, sel=torch.from_numpy(sel).cuda()), KR.reg_metrics(wide_p[:, 2:2 + Y], wide_y[:, :Y], sel=sel))
-    _close(_run(K, pv, yv, n=17), KR.reg_metrics(wide_p[:, 2:2 + Y], wide_y[:, :Y], n=17))
+    _close(_run(K, pv, yv), kernel_ref.reg_metrics64(wide_p[:, 2:2 + Y], wide_y[:, :Y]))
+    _close(_run(K, pv, yv, sel=torch.from_numpy(sel).cuda()), kernel_ref.reg_metrics64(wide_p[:, 2:2 + Y], wide_y[:, :Y], sel=sel))
+    _close(_run(K, pv, yv, n=17), kernel_ref.reg_metrics64(wide_p[:, 2:2 + Y], wide_y[:, :Y], n=17))
 
 
 @pytest.mark.parametrize('n', [4097, 32768])
@@ -77,7 +77,7 @@ def test_targets_in_a_narrow_band(K, dev, n):
     rs = np.random.RandomState(8)
     y = (0.5 + 1e-3 * (2 * rs.rand(n, 1) - 1)).astype(np.float32)
     p = (y + 3e-4 * rs.standard_normal((n, 1))).astype(np.float32)
-    want = KR.reg_metrics(p, y)
+    want = kernel_ref.reg_metrics64(p, y)
     assert 0.5 < want[2] < 1.0 and np.isfinite(want[1])
     _close(_run(K, torch.from_numpy(p).cuda(), torch.from_numpy(y).cuda()), want)
 
@@ -90,10 +90,10 @@ def test_edge_cases(K, dev):
     const = torch.full((n, Y), 0.3, device='cuda')
     v = _run(K, p, const)                       # constant target: no variance to explain, no correlation
     assert np.isfinite(v[0]) and np.isnan(v[1]) and np.isnan(v[2])
-    _close(v, KR.reg_metrics(p.cpu().numpy(), const.cpu().numpy()))
+    _close(v, kernel_ref.reg_metrics64(p.cpu().numpy(), const.cpu().numpy()))
     v = _run(K, const, y)                       # constant prediction: r2 finite (<= 0), no correlation
     assert np.isfinite(v[0]) and np.isfinite(v[1]) and np.isnan(v[2])
-    _close(v, KR.reg_metrics(const.cpu().numpy(), y.cpu().numpy()))
+    _close(v, kernel_ref.reg_metrics64(const.cpu().numpy(), y.cpu().numpy()))
     assert np.isnan(_run(K, p, y, n=0)).all()
     assert np.isnan(_run(K, p, y, sel=torch.zeros(0, dtype=torch.int32, device='cuda'))).all()
 
@@ -119,4 +119,4 @@ def test_capturable(K, dev):
         K.reg_metrics(out, p, y)
     y.mul_(0.5)
     g.replay()
-    _close(out.cpu().numpy(), KR.reg_metrics(p.cpu().numpy(), y.cpu().numpy()))
+    _close(out.cpu().numpy(), kernel_ref.reg_metrics64(p.cpu().numpy(), y.cpu().numpy()))

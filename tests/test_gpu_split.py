@@ -256,35 +256,15 @@ def count_split(monkeypatch):
 
 
 def install_contract(monkeypatch, seen):
-    """CPU stand-ins over tests/kernel_ref.py that know ``x3=`` / ``parts=``: a routed product is evaluated by the contract's
-    emulation (``x3_ref.matmul`` with the rung's terms: float64 sums, rounded to fp32 once), its epilogue by the fp32
-    stand-in (through an exact product with the identity)"""
-    import drvae_amd.kernels as K
+    """the CPU stand-ins, whose routed products follow the rung's contract (``kernel_ref.routed_product``), with the ``parts``
+    of every routed product noted in ``seen``"""
     kernel_ref.install(monkeypatch)
+    routed = kernel_ref.routed_product
 
-    def routed(Cm, A, B, a_kc, b_kc, parts, *, a_colsum=None, colsum_beta=0.0, overread=False, kpad=False, npad=False, **kw):
+    def noting(Cm, A, B, a_kc, b_kc, parts, **kw):
         seen.append(parts)
-        Aop, Bop = (A if a_kc else A.t()), (B.t() if b_kc else B)
-        prod = x3_ref.matmul(Aop.contiguous(), Bop.contiguous(), TERMS[parts]).float()
-        kernel_ref.gemm(Cm, prod, torch.eye(Cm.shape[1]), True, False, **kw)
-        if a_colsum is not None:
-            kernel_ref._acc(a_colsum, Aop.sum(1), colsum_beta)
-
-    def gemm(Cm, A, B, a_kc, b_kc, x3=False, parts=3, **kw):
-        if not x3:
-            return kernel_ref.gemm(Cm, A, B, a_kc, b_kc, **kw)
         return routed(Cm, A, B, a_kc, b_kc, parts, **kw)
-
-    def linear_bwd_pair(dW, dbias, dx, dpre, x, W, x3=False, parts=3, **kw):
-        if not x3:
-            return kernel_ref.linear_bwd_pair(dW, dbias, dx, dpre, x, W, **kw)
-        assert not (set(kw) - {'yref', 'act', 'shift', 'overread', 'publish', 'npad', 'npad_x', 'alpha'}), kw
-        routed(dW, dpre, x, False, False, parts, a_colsum=dbias, publish=kw.get('publish'))
-        e = {} if kw.get('yref') is None else dict(epi=K.EPI_BWD, yref=kw['yref'], act0=kw.get('act', 0), act1=kw.get('act', 0),
-                                                   shift0=kw.get('shift', 0.0), shift1=kw.get('shift', 0.0))
-        routed(dx, dpre, W, True, False, parts, alpha=kw.get('alpha', 1.0), **e)
-    monkeypatch.setattr(K, 'gemm', gemm)
-    monkeypatch.setattr(K, 'linear_bwd_pair', linear_bwd_pair)
+    monkeypatch.setattr(kernel_ref, 'routed_product', noting)
 
 
 def contract_step_on_cpu(case, mm):

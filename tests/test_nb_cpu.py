@@ -9,7 +9,6 @@ import torch
 
 from oracle import models_ref as M
 from tests import kernel_ref
-from tests import kernel_ref_nb as KN
 from tests import nb_ref as R
 from tests import ref64
 from tests.golden import cases as C
@@ -178,7 +177,7 @@ VARIANTS = ['plain', 'weight_norm', 'use_s', 'universal']
 def test_fused_step_matches_the_float64_model_reference(kind, variant, monkeypatch):
     """losses and gradients of a train-mode pass, then three Adam steps at 16 rows: the tolerances of
     ``tests/test_engine_cpu.py::test_bernoulli_poisson_decoders_match_oracle``"""
-    KN.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     if variant == 'use_s':
         spec, batch = _use_s_case(kind)
     else:
@@ -215,7 +214,7 @@ def test_fused_step_matches_the_float64_model_reference(kind, variant, monkeypat
             close(v, float(want[k].detach()), 2e-5, 2e-6)
     for k, prm in ref.params().items():
         close(arena.p(k), prm, 1e-4, 2e-5)
-    assert KN.CALLS['nb'] > 0 and KN.CALLS['other'] == 0
+    assert kernel_ref.CALLS['nb'] > 0 and kernel_ref.CALLS['other'] == 0
 
 
 @pytest.mark.parametrize('kind', ['drvae', 'vfae'])
@@ -223,7 +222,7 @@ def test_two_shards_sum_to_the_whole_batch(kind, monkeypatch):
     """data parallelism needs nothing new: two engines on rows [0, 8) and [8, 16) with the global counts and their rows of the
     noise hold loss scalars and gradients that SUM to the whole batch's (what the all-reduce forms); fp32 sums of 8 + 8
     against 16 terms, compared in float64"""
-    KN.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec, batch = _case(kind)
     ref = R.ModelRef(spec, seed=9)
     noise = M.make_noise(spec, 16, seed=4)
@@ -269,7 +268,7 @@ def test_other_decoders_record_the_launches_they_did(kind, type_rec, monkeypatch
     noises = [M.make_noise(spec, 16, seed=10 + i) for i in range(3)]
     names = sorted(set(kernel_ref.FUNCTIONS) - {'smalln_ws_numel', 'col_moment_blocks', 'nll_raw_cs_shape', 'heads_tiles'})
     out = {}
-    for tag, install in (('before', kernel_ref.install), ('after', KN.install)):
+    for tag, install in (('before', kernel_ref.install), ('after', kernel_ref.install)):
         with pytest.MonkeyPatch.context() as mp_install:
             install(mp_install)
             from tests.test_engine_cpu import make_engine as plain_engine, set_batch as plain_batch
@@ -295,4 +294,4 @@ def test_other_decoders_record_the_launches_they_did(kind, type_rec, monkeypatch
     else:
         assert len(rec) == 3 and all(kw == ['coef', 'dpre', 'kind', 'shift', 'xidx'] for kw in rec)
         assert all(k == type_rec and shp[1] == spec.dim_x for k, shp in a[1]) and a[5][1] == spec.dim_x
-    assert KN.CALLS['nb'] == 0
+    assert kernel_ref.CALLS['nb'] == 0

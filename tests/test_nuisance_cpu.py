@@ -9,7 +9,7 @@ import pytest
 import torch
 
 from oracle import models_ref as M
-from tests import kernel_ref_nuisance as KN
+from tests import kernel_ref
 from tests import nuisance_cases as NC
 from tests.test_engine_cpu import make_engine
 
@@ -68,8 +68,8 @@ def test_standins_follow_the_fp64_formulas(kind, S):
     rs = np.random.RandomState(3 + S)
     g = _random_case(rs, kind, S, 5, [6, 9, 4])
     g['cls'][g['src'][6:15].long()] = 1          # the second group: one class only -- an empty side
-    KN.mmd_grouped_fwd(g)
-    KN.mmd_grouped_bwd(g)
+    kernel_ref.mmd_grouped_fwd(g)
+    kernel_ref.mmd_grouped_bwd(g)
     n = lambda t: None if t is None else t.numpy()
     diff, m2, value, dz, theta, cnt = NC.mmd_ref(n(g['z']), n(g['cls']), n(g['grp_ptr']), n(g['rows']), n(g['src']), S, kind,
                                                  g['w'], g['fac'], n(g['W']), n(g['b']), g['a'], g['c'])
@@ -97,7 +97,7 @@ def _engines(kind, dim_s, use_mmd, dev='cpu'):
 def test_epoch_feed_with_nuisance_classes_equals_host_fed_steps_cpu(kind, dim_s, use_mmd, monkeypatch):
     """CPU twin of the GPU epoch test: an epoch through ``begin_epoch(table=...)`` on the plan that carries the classes
     (eager steps that gather through the live feed) against a second engine fed the same rows and classes from the host"""
-    KN.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec, big, ds, bat, fed, a1, host, a0 = _engines(kind, dim_s, use_mmd)
     tab = NC.epoch_table(big, dim_s, 6)
     NC.assert_every_side_filled(kind, big, tab, dim_s, bat.has_x2 * (kind != 'vfae'), bat.has_y * (kind != 'pvae'))
@@ -127,7 +127,7 @@ def test_epoch_feed_with_nuisance_classes_equals_host_fed_steps_cpu(kind, dim_s,
 
 def test_explicit_batches_feed_the_same_class_vector_cpu(monkeypatch):
     """``DeviceBatcher.feed()`` and ``set_batch`` with a device ``s`` on the plan that carries the classes == the epoch feed"""
-    KN.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec, big, ds, bat, fed, a1, twin, a0 = _engines('drvae', 3, True)
     tab = NC.epoch_table(big, 3, 4, vary=True)
     bat.bind(fed)
@@ -152,7 +152,7 @@ def test_explicit_batches_feed_the_same_class_vector_cpu(monkeypatch):
 
 
 def test_what_is_still_refused(monkeypatch):
-    KN.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     from drvae_amd import data as D
     for use_mmd in (False, True):
         over = dict(use_MMD=True, kernel_MMD='identity') if use_mmd else {}

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from oracle import models_ref as M
-from tests import kernel_ref_nuisance_masked as KM
+from tests import kernel_ref
 from tests import nuisance_cases as NC
 from tests import nuisance_masked_cases as MC
 from tests.test_engine_cpu import make_engine
@@ -99,8 +99,8 @@ def _ref(g, flags, b=1):
 def test_standins_follow_the_fp64_reference(model, S, kind, table):
     rs = np.random.RandomState(7 + S)
     g, flags = _case(rs, model, S, kind, table=table)
-    KM.mmd_masked_fwd(g)
-    KM.mmd_masked_bwd(g)
+    kernel_ref.mmd_masked_fwd(g)
+    kernel_ref.mmd_masked_bwd(g)
     (fx, fy), ref = _ref(g, flags)
     assert np.array_equal(g['cnt'].numpy(), ref['cnt'])
     for tg, mem in enumerate(ref['members']):
@@ -166,7 +166,7 @@ def test_epoch_of_varying_batches_through_one_plan_equals_host_fed_steps_cpu(kin
     """an epoch of tables whose composition of data groups AND classes differs from batch to batch, through ONE plan
     (eager steps that gather through the live feed), against a second engine fed per batch from the host (structure plans,
     host row lists)"""
-    KM.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec, big, ds, bat, fed, a1, host, a0 = _engines(kind, dim_s, use_mmd)
     tab = MC.varied_table(kind, big, dim_s, 6)
     MC.assert_cells_filled_and_counts_differ(kind, big, tab, dim_s)
@@ -192,7 +192,7 @@ def test_epoch_of_varying_batches_through_one_plan_equals_host_fed_steps_cpu(kin
 def test_explicit_batches_and_buckets_feed_the_same_plan_kind_cpu(monkeypatch):
     """``feed()``, ``set_batch`` with a device ``s`` and the bucketed feed: every plan carries, the classes arrive through
     ``set_s_device`` / the shared feed, and the steps equal those of the unbucketed epoch feed"""
-    KM.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec, big, ds, bat, fed, a1, twin, a0 = _engines('drvae', 3, True)
     tab = MC.varied_table('drvae', big, 3, 4, seed=2)
     bat.bind(fed)
@@ -230,7 +230,7 @@ def test_explicit_batches_and_buckets_feed_the_same_plan_kind_cpu(monkeypatch):
 
 def test_cpu_generator_and_draw_ahead(monkeypatch):
     """``generator='cpu'`` (the reference's stream) and ``draw_ahead`` / ``rebase`` work with the masked carry"""
-    KM.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     from drvae_amd import data as D
     spec, big, ds = NC.dataset('vfae', 2, 'cpu', use_MMD=True, kernel_MMD='identity')
     eng, _ = make_engine(spec, M.init_params(spec, 3, as_numpy=True))
@@ -258,7 +258,7 @@ def test_cpu_generator_and_draw_ahead(monkeypatch):
 
 
 def test_what_is_refused_and_what_stays(monkeypatch):
-    KM.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     from drvae_amd import data as D
     spec, big, ds = NC.dataset('drvae', 2, 'cpu', use_MMD=True, kernel_MMD='identity')
     w = torch.ones(400)

@@ -1,5 +1,5 @@
 """CPU: ``dv_reg_metrics`` -- the C-ABI declaration, its argument checks without a GPU, and the float64 restatement of its
-two-pass arithmetic (tests/kernel_ref_reg.py) against the reference's own numbers (the kernel itself:
+two-pass arithmetic (``reg_metrics64`` of tests/kernel_ref.py) against the reference's own numbers (the kernel itself:
 tests/test_gpu_reg_metrics.py)."""
 import os
 import re
@@ -7,7 +7,7 @@ import re
 import numpy as np
 import pytest
 
-from tests import kernel_ref_reg as KR
+from tests import kernel_ref
 from tests.golden import cases as C
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
@@ -38,7 +38,7 @@ def test_entry_point_rejects_bad_arguments_without_gpu():
 def test_two_pass_reference_reproduces_the_reference_generated_metrics():
     c = C.y_metric_cases()['Ycont']
     G = np.load(os.path.join(GOLDEN, 'fit.npz'))
-    got = KR.reg_metrics(c['pred'], c['ylab'])
+    got = kernel_ref.reg_metrics64(c['pred'], c['ylab'])
     for i, k in enumerate(('rmse', 'r2', 'pearr')):
         assert got[i] == pytest.approx(float(G['Ycont/' + k]), rel=1e-6)
 
@@ -47,16 +47,16 @@ def test_two_pass_reference_edge_cases_and_selection():
     rs = np.random.RandomState(0)
     y, p = rs.rand(20, 3).astype(np.float32), rs.rand(20, 3).astype(np.float32)
     sel = np.array([3, 1, 17, 4])
-    np.testing.assert_array_equal(KR.reg_metrics(p, y, sel=sel), KR.reg_metrics(p[sel], y[sel]))
-    np.testing.assert_array_equal(KR.reg_metrics(p, y, n=5), KR.reg_metrics(p[:5], y[:5]))
-    assert np.isnan(KR.reg_metrics(p, y, n=0)).all()
+    np.testing.assert_array_equal(kernel_ref.reg_metrics64(p, y, sel=sel), kernel_ref.reg_metrics64(p[sel], y[sel]))
+    np.testing.assert_array_equal(kernel_ref.reg_metrics64(p, y, n=5), kernel_ref.reg_metrics64(p[:5], y[:5]))
+    assert np.isnan(kernel_ref.reg_metrics64(p, y, n=0)).all()
     const = np.full_like(y, 0.3)
-    v = KR.reg_metrics(p, const)
+    v = kernel_ref.reg_metrics64(p, const)
     assert np.isfinite(v[0]) and np.isnan(v[1]) and np.isnan(v[2])
-    v = KR.reg_metrics(const, y)
+    v = kernel_ref.reg_metrics64(const, y)
     assert np.isfinite(v[0]) and np.isfinite(v[1]) and np.isnan(v[2])
     # against the host function the step-by-step evaluation uses
     import torch
     from drvae_amd import metrics as MET
     h = MET.eval_y_regression(torch.from_numpy(p), torch.from_numpy(y))
-    np.testing.assert_allclose(KR.reg_metrics(p, y), [h['rmse'], h['r2'], h['pearr']], rtol=1e-12)
+    np.testing.assert_allclose(kernel_ref.reg_metrics64(p, y), [h['rmse'], h['r2'], h['pearr']], rtol=1e-12)

@@ -74,9 +74,9 @@ def test_truncation_bounds(Kdim):
 
 # ------------------------------------------------------------------------------------------------ routing
 def install_with_parts(monkeypatch, seen):
-    """stand-ins that know ``x3=`` and ``parts=``: note every PRODUCT a launcher call stands for with the keywords it was
-    routed by (None: not routed; else the ``parts`` keyword, 'absent' when the call did not pass one) and run the fp32
-    stand-in (the routing is what is tested here)"""
+    """spies over the CPU stand-ins: note every PRODUCT a launcher call stands for with the keywords it was routed by
+    (None: not routed; else the ``parts`` keyword, 'absent' when the call did not pass one) and run the fp32 stand-in
+    whatever they say (the routing is what is tested here)"""
     import drvae_amd.kernels as K
     kernel_ref.install(monkeypatch)
 

@@ -2,7 +2,9 @@
 the step -- the main chain with its optimiser launch, then the side chain -- are issued on CPU tensors the way
 ``capture()`` issues them into their two graphs (stand-in launchers of tests/kernel_ref.py, a recorder around them), for
 every small model case, every exchange form, a structure plan and a universal plan, with and without the explicit-batch tail
-gate (``DRVAE_TUNE=tail_gate=2``).  What is asserted comes from the trace and from the protocol table of
+gate (``DRVAE_TUNE=tail_gate=2``).  The schedule recorded is the UNFOLDED one (``fold_rows=0``: the product's path under
+clipping, dropout sites, the other models and every exchange form; the folded chains pass the same statements in
+``tests/test_fold_rows_cpu.py``).  What is asserted comes from the trace and from the protocol table of
 ``drvae_amd/schedule.py`` (FLAGS / SITES) alone."""
 import functools
 
@@ -119,8 +121,7 @@ def recorded_steps(tail_gate):
     out = {}
     with pytest.MonkeyPatch.context() as mp:
         kernel_ref.install(mp)
-        if tail_gate:
-            mp.setenv('DRVAE_TUNE', 'tail_gate=2')
+        mp.setenv('DRVAE_TUNE', 'fold_rows=0,tail_gate=2' if tail_gate else 'fold_rows=0')
         mp.setattr(T, '_VALUES', None)       # (re-read the switches now, and again after this block)
         for name in C.SMALL_MODEL_CASES:
             case = C.model_case(name)
@@ -232,6 +233,7 @@ def test_the_side_chain_s_recording_does_not_depend_on_what_ran_before_it(monkey
     import drvae_amd.tuning as T
     steps = recorded_steps(False)
     kernel_ref.install(monkeypatch)
+    monkeypatch.setenv('DRVAE_TUNE', 'fold_rows=0')
     monkeypatch.setattr(T, '_VALUES', None)
     assert steps
     for (name, universal, split), rec in steps.items():
@@ -249,7 +251,7 @@ def test_the_side_chain_sums_the_raw_row_pass_s_partials_whatever_ran_before_it(
     size): main-then-side and side alone both sum ``NLLC``"""
     import drvae_amd.kernels as K
     import drvae_amd.tuning as T
-    monkeypatch.setenv('DRVAE_TUNE', 'fuse_heads=0,raw_heads=2,nll_cs=2')
+    monkeypatch.setenv('DRVAE_TUNE', 'fuse_heads=0,raw_heads=2,nll_cs=2,fold_rows=0')
     monkeypatch.setattr(T, '_VALUES', None)
     kernel_ref.install(monkeypatch)
     spec = C.tiny_spec(kind, dim_x=16, h_de_x=[8])

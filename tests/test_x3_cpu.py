@@ -81,8 +81,8 @@ def make_engine(spec, params, **cfg_over):
 
 
 def install_with_x3(monkeypatch, seen):
-    """the CPU stand-ins of tests/kernel_ref.py do not know the ``x3=`` keyword: these do, note every PRODUCT a launcher
-    call stands for together with its flag, and run the fp32 stand-in (the routing is what is tested here)"""
+    """spies over the CPU stand-ins: note every PRODUCT a launcher call stands for together with its ``x3=`` flag, and run
+    the fp32 stand-in whatever the flag says (the routing is what is tested here)"""
     import drvae_amd.kernels as K
     kernel_ref.install(monkeypatch)
 
