@@ -143,7 +143,12 @@ class Z2F(C.Structure):          # dv_z2f_desc
 
 class ReconRows(C.Structure):    # dv_recon_rows_desc
     _fields_ = [('x', _p), ('ldx', _i64), ('mu', _p), ('sd', _p), ('ldp', _i64), ('bias_mu', _p), ('bias_sd', _p),
-                ('sd_shift', _f), ('M', _i32), ('X', _i32), ('rows', _p), ('ll', _p)]
+                ('sd_shift', _f), ('M', _i32), ('X', _i32), ('rows', _p), ('ll', _p),
+                # (the count kinds, ABI 13's trailing fields; all zero = the Gaussian pass as it was)
+                ('kind', _i32), ('ldt', _i64), ('size_x', _p), ('size_ld', _i64), ('rec_out', _p), ('rec_ld', _i64)]
+
+
+RECON_KIND = {None: 0, 'binary': 1, 'poisson': 2, 'nb': 3}      # dv_recon_rows_desc.kind (DV_RECON_*)
 
 
 class NllRawCs(C.Structure):     # dv_nll_raw_cs_desc

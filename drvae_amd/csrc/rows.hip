@@ -2323,6 +2323,138 @@ __global__ __launch_bounds__(256) void recon_rows_kernel(RcArgs a) {
     }
 }
 
+// The COUNT kinds of dv_recon_rows (type_rec = 'binary' / 'poisson' / 'nb'): the six row statistics between the target row
+// x and the finished mean r, the kind's log-likelihood row at that mean (rec_term / nb_term above: the one definition of each
+// formula, their gradient outputs dead code here) and, optionally, the stored mean -- one workgroup per row like
+// rec_nll_rows_kernel / nb_nll_rows_kernel, any X.  v / t: the POST-activation heads (mean | theta).  LIB: r = s v with the
+// size factor s of the row xs[i,:] (row_size_factor; xs = the target itself, or ANOTHER matrix: the prediction of x2 is made
+// at x1's depth); !LIB: r = v, xs is not read.  Walk 1 forms sum x, sum r, sum (x-r)^2 and the term sum (and stores r), walk
+// 2 -- over the cache-hot row -- the centred sums at the means of walk 1, as recon_row_stats_kernel does (counts reach the
+// thousands: raw moments would cancel).  The r of the statistics is ONE rounded product (__fmul_rn: never contracted into its
+// consumers), so both walks and the stored mean see the same number.  The term forms its own m = s * v inside rec_term /
+// nb_term, a plain product the compiler may contract into a neighbour (x log m - s v as one fma): inside the count of
+// roundings the row kernels are held to, not necessarily the bits of r.  ro may alias v: every element is read and written by the same
+// lane, and walk 2 reads r back from ro when there is one (v holds r then).  Per-thread partials in index order, the wave
+// sum, the four waves as (p0 + p1) + (p2 + p3): no atomics, equal bits on every launch.
+// VEC (X % 4 == 0, 16-byte aligned rows: the dispatcher checks): 16-byte loads and stores; the term walked one gene at a
+// time (#pragma unroll 1: see nb_nll_rows_kernel -- four inlined copies of nb_term run out of scalar registers)
+struct RcCountArgs {
+    const float* x; int64_t ldx; const float* v; int64_t ldv; const float* t; int64_t ldt;
+    const float* xs; int64_t ldxs; float* ro; int64_t ldo;
+    int M, X;
+    float* rows; float* ll;
+};
+
+template <int KIND, bool LIB>
+__device__ __forceinline__ float rc_count_term(float s, float x, float v, float t, float& r) {
+    r = LIB ? __fmul_rn(s, v) : v;
+    if constexpr (KIND == DV_REC_NEGBIN) {
+        float gm, gt;
+        return nb_term<LIB>(0.f, s, x, v, t, gm, gt);
+    } else {
+        float g;
+        return rec_term<LIB>(KIND, 0.f, s, x, v, g);
+    }
+}
+
+template <int KIND, bool LIB, bool VEC>
+__global__ __launch_bounds__(256) void recon_rows_count_kernel(RcCountArgs a) {
+    __shared__ float part[4][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int X = a.X;
+    constexpr bool NB = KIND == DV_REC_NEGBIN;
+    {       // (grid = M workgroups, no row loop: the scalar registers of a loop's bookkeeping are the ones nb_term runs out of)
+        const int i = blockIdx.x;
+        const float* xr = a.x + (int64_t)i * a.ldx;
+        const float* vr = a.v + (int64_t)i * a.ldv;
+        const float* tr = NB ? a.t + (int64_t)i * a.ldt : nullptr;
+        float* ro = a.ro ? a.ro + (int64_t)i * a.ldo : nullptr;
+        float sz = 1.f;
+        if constexpr (LIB) sz = row_size_factor<VEC>(a.xs + (int64_t)i * a.ldxs, X, &part[0][0]);
+        float sx = 0.f, sr = 0.f, sse = 0.f, sl = 0.f;
+        if constexpr (VEC) {
+            for (int q = threadIdx.x; q < (X >> 2); q += 256) {
+                const float4 xv = reinterpret_cast<const float4*>(xr)[q];
+                const float4 mv = reinterpret_cast<const float4*>(vr)[q];
+                float4 tv = make_float4(1.f, 1.f, 1.f, 1.f), rv = make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (NB) tv = reinterpret_cast<const float4*>(tr)[q];
+#pragma unroll 1
+                for (int j = 0; j < 4; ++j) {
+                    const float xj = j == 0 ? xv.x : j == 1 ? xv.y : j == 2 ? xv.z : xv.w;
+                    const float mj = j == 0 ? mv.x : j == 1 ? mv.y : j == 2 ? mv.z : mv.w;
+                    const float tj = j == 0 ? tv.x : j == 1 ? tv.y : j == 2 ? tv.z : tv.w;
+                    float r;
+                    sl += rc_count_term<KIND, LIB>(sz, xj, mj, tj, r);
+                    sx += xj;
+                    sr += r;
+                    sse += (xj - r) * (xj - r);
+                    rv.x = j == 0 ? r : rv.x, rv.y = j == 1 ? r : rv.y, rv.z = j == 2 ? r : rv.z, rv.w = j == 3 ? r : rv.w;
+                }
+                if (ro) reinterpret_cast<float4*>(ro)[q] = rv;
+            }
+        } else {
+            for (int g = threadIdx.x; g < X; g += 256) {
+                const float xg = xr[g];
+                float r;
+                sl += rc_count_term<KIND, LIB>(sz, xg, vr[g], NB ? tr[g] : 1.f, r);
+                sx += xg;
+                sr += r;
+                sse += (xg - r) * (xg - r);
+                if (ro) ro[g] = r;
+            }
+        }
+        sx = dv_wave_sum_all(sx);
+        sr = dv_wave_sum_all(sr);
+        sse = dv_wave_sum_all(sse);
+        sl = dv_wave_sum_all(sl);
+        if (lane == 0) part[0][wave] = sx, part[1][wave] = sr, part[2][wave] = sse, part[3][wave] = sl;
+        __syncthreads();
+        const float mx = ((part[0][0] + part[0][1]) + (part[0][2] + part[0][3])) / X;
+        const float mr = ((part[1][0] + part[1][1]) + (part[1][2] + part[1][3])) / X;
+        const float tse = (part[2][0] + part[2][1]) + (part[2][2] + part[2][3]);
+        const float tl = (part[3][0] + part[3][1]) + (part[3][2] + part[3][3]);
+        __syncthreads();
+        // walk 2: the centred sums.  r as walk 1 formed it: read back where it was stored (v may hold it by now), else the
+        // same one product again
+        float cxx = 0.f, crr = 0.f, cxr = 0.f;
+        const float* rr = ro ? ro : vr;
+        const bool scale = LIB && !ro;
+        if constexpr (VEC) {
+            for (int q = threadIdx.x; q < (X >> 2); q += 256) {
+                const float4 xv = reinterpret_cast<const float4*>(xr)[q];
+                float4 rv = reinterpret_cast<const float4*>(rr)[q];
+                if (scale) rv.x = __fmul_rn(sz, rv.x), rv.y = __fmul_rn(sz, rv.y), rv.z = __fmul_rn(sz, rv.z), rv.w = __fmul_rn(sz, rv.w);
+                const float p0 = xv.x - mx, p1 = xv.y - mx, p2 = xv.z - mx, p3 = xv.w - mx;
+                const float q0 = rv.x - mr, q1 = rv.y - mr, q2 = rv.z - mr, q3 = rv.w - mr;
+                cxx += p0 * p0, cxx += p1 * p1, cxx += p2 * p2, cxx += p3 * p3;
+                crr += q0 * q0, crr += q1 * q1, crr += q2 * q2, crr += q3 * q3;
+                cxr += p0 * q0, cxr += p1 * q1, cxr += p2 * q2, cxr += p3 * q3;
+            }
+        } else {
+            for (int g = threadIdx.x; g < X; g += 256) {
+                const float r = scale ? __fmul_rn(sz, rr[g]) : rr[g];
+                const float p = xr[g] - mx, q = r - mr;
+                cxx += p * p;
+                crr += q * q;
+                cxr += p * q;
+            }
+        }
+        cxx = dv_wave_sum_all(cxx);
+        crr = dv_wave_sum_all(crr);
+        cxr = dv_wave_sum_all(cxr);
+        if (lane == 0) part[0][wave] = cxx, part[1][wave] = crr, part[2][wave] = cxr;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            float* o = a.rows + (int64_t)i * 6;
+            o[0] = tse; o[1] = mx; o[2] = mr;
+            o[3] = (part[0][0] + part[0][1]) + (part[0][2] + part[0][3]);
+            o[4] = (part[1][0] + part[1][1]) + (part[1][2] + part[1][3]);
+            o[5] = (part[2][0] + part[2][1]) + (part[2][2] + part[2][3]);
+            if (a.ll) a.ll[i] = tl;
+        }
+    }
+}
+
 // ------------------------------------------------------------------ kernel-mixture MMD (src/blocks.py:29-38,59-76; round 5)
 // mmd_objective(kernel = 'rbf' | 'poly'): mean_ij k(a_i, b_j) with k = 1/nb sum_b f(., gamma_b) over three Gram products
 // (x1 x1^T, x2 x2^T, x1 x2^T: dv_gemm).  The element-wise mixture, its mean and its derivative were library element-wise
@@ -3598,10 +3730,47 @@ extern "C" int dv_col_moments(const float* x, int64_t ldx, const float* r, int64
     DV_RETURN_LAUNCH();
 }
 
+template <int KIND, bool LIB>
+static void launch_recon_rows_count(bool vec, const RcCountArgs& a, dv_stream_t stream) {
+    const dim3 grid(a.M), block(256);
+    if (vec) hipLaunchKernelGGL((recon_rows_count_kernel<KIND, LIB, true>), grid, block, 0, ST(stream), a);
+    else hipLaunchKernelGGL((recon_rows_count_kernel<KIND, LIB, false>), grid, block, 0, ST(stream), a);
+}
+
+// the count kinds of dv_recon_rows (d.kind != DV_RECON_GAUSS): every refusal before any launch
+static int recon_rows_count(const dv_recon_rows_desc& d, dv_stream_t stream) {
+    DV_REQUIRE(d.kind == DV_RECON_BERNOULLI || d.kind == DV_RECON_POISSON || d.kind == DV_RECON_NEGBIN);
+    const bool nb = d.kind == DV_RECON_NEGBIN, lib = d.size_x != nullptr;
+    DV_REQUIRE(d.bias_mu == nullptr && d.bias_sd == nullptr);      // (count heads leave their launch finished)
+    DV_REQUIRE(!(lib && d.kind == DV_RECON_BERNOULLI));             // (probabilities have no depth)
+    DV_REQUIRE(!nb || d.ldt >= (int64_t)d.X);                       // (theta has a row stride of its own)
+    DV_REQUIRE(d.rec_out == nullptr || lib);                        // (without a size source the mean IS the head: no copy)
+    if (d.M == 0) return DV_OK;
+    DV_REQUIRE(d.x && d.mu && d.rows && (!nb || d.sd));
+    DV_REQUIRE(d.ldx >= d.X && d.ldp >= d.X && (!lib || d.size_ld >= d.X) && (!d.rec_out || d.rec_ld >= d.X));
+    auto a16 = [](const void* p, int64_t ld) { return p == nullptr || ((reinterpret_cast<uintptr_t>(p) & 15) == 0 && ld % 4 == 0); };
+    const bool vec = d.X % 4 == 0 && a16(d.x, d.ldx) && a16(d.mu, d.ldp) && (!nb || a16(d.sd, d.ldt)) &&
+                     a16(d.size_x, d.size_ld) && a16(d.rec_out, d.rec_ld);
+    RcCountArgs a{d.x, d.ldx, d.mu, d.ldp, nb ? d.sd : nullptr, d.ldt, d.size_x, d.size_ld, d.rec_out, d.rec_ld,
+                  d.M, d.X, d.rows, d.ll};
+    if (nb) {
+        if (lib) launch_recon_rows_count<DV_REC_NEGBIN, true>(vec, a, stream);
+        else launch_recon_rows_count<DV_REC_NEGBIN, false>(vec, a, stream);
+    } else if (d.kind == DV_RECON_POISSON) {
+        if (lib) launch_recon_rows_count<DV_REC_POISSON, true>(vec, a, stream);
+        else launch_recon_rows_count<DV_REC_POISSON, false>(vec, a, stream);
+    } else {
+        launch_recon_rows_count<DV_REC_BERNOULLI, false>(vec, a, stream);
+    }
+    DV_RETURN_LAUNCH();
+}
+
 extern "C" int dv_recon_rows(const dv_recon_rows_desc* dsc, dv_stream_t stream) {
     DV_REQUIRE(dsc != nullptr);
     const dv_recon_rows_desc& d = *dsc;
     DV_REQUIRE(d.M >= 0 && d.X >= 1);
+    if (d.kind != DV_RECON_GAUSS) return recon_rows_count(d, stream);
+    DV_REQUIRE(d.size_x == nullptr && d.rec_out == nullptr);       // (the count kinds' operands)
     if (d.X > DV_RECON_ROWS_MAX_X) return DV_ERR_UNSUPPORTED;
     if (d.M == 0) return DV_OK;
     DV_REQUIRE(d.x && d.mu && d.sd && d.rows);

@@ -188,9 +188,11 @@ class FitMixin:
         inference, reconstruction statistics and the prediction metrics captured once per (model, dataset) -- see
         ``_EvalGraph``.  That includes the regression head (``type_y='cont'``: rmse / R^2 / Pearson r from ``dv_reg_metrics``) and
         models conditioned on the nuisance variable (``use_s``; with ``use_MMD`` for ``kernel_MMD='rbf_fourier' | 'identity'``
-        and 2 <= dim_s <= 8, the penalty as its two grouped launches).  ``return_full_data`` (arrays for the caller), host
-        datasets, ``type_rec='binary' | 'poisson' | 'nb'`` and the other MMD kernels take the step-by-step path (``'nb'``:
-        ``x1_rec`` / ``x2_pert`` are the means, ``px1`` = (mu, theta), and the reported ``ll`` is the negative binomial's)."""
+        and 2 <= dim_s <= 8, the penalty as its two grouped launches) and the count decoders (``type_rec='binary' | 'poisson' |
+        'nb'``, with ``x_transform`` / ``library_size``: ``dv_recon_rows``' count kinds -- row statistics at the scaled mean and the
+        count log-likelihood in one pass; the reported ``ll`` is the negative binomial's for ``'nb'`` and nan for the other two,
+        as on the step-by-step path).  ``return_full_data`` (arrays for the caller), host datasets and the other MMD kernels take
+        the step-by-step path (``'nb'``: ``x1_rec`` / ``x2_pert`` are the means, ``px1`` = (mu, theta))."""
         g = lambda k: getattr(ds, k, None)
         ev = None if return_full_data else _EvalGraph.get(self, ds)
         if ev is not None:
@@ -434,7 +436,10 @@ class _EvalGraph:
       * the evaluation-mode loss scalars of the fused step's forward (Philox draws from the device counter) on a plan of
         the whole set, its inputs gathered device-to-device from the dataset;
       * the means-only inference ``forward`` (block level: the same HIP kernels);
-      * ``dv_recon_row_stats`` / ``dv_col_moments`` and their float64 combination, the Gaussian log-likelihood mean;
+      * ``dv_recon_row_stats`` / ``dv_col_moments`` and their float64 combination, the Gaussian log-likelihood mean; for the
+        count decoders (``type_rec='binary' | 'poisson' | 'nb'``) the decoder's FINISHED heads and ``dv_recon_rows``' count kinds:
+        statistics at the mean scaled by x1's size factor (``library_size``; for the x2 targets too), the negative binomial's
+        log-likelihood rows, the scaled mean stored in place of the mean head for ``dv_col_moments``;
       * accuracy / AUROC / AUPR by sort + scan on the device (``metrics.*_dev``: no compaction, no host decisions); for the
         regression head rmse / R^2 / Pearson r of the means (``dv_reg_metrics``: one launch, two-pass float64 sums);
       * ``use_s``: the whole set's plan carries the nuisance classes on the device (``_Plan.carry_nuisance``) and the sequence
@@ -450,7 +455,7 @@ class _EvalGraph:
     def get(model, ds):
         from . import kernels as K
         x1 = getattr(ds, 'x1', None)
-        if not (torch.is_tensor(x1) and x1.is_cuda) or getattr(model, 'type_rec', 'diag_gaussian') != 'diag_gaussian':
+        if not (torch.is_tensor(x1) and x1.is_cuda):
             return None
         if next(model.parameters()).device != x1.device:
             return None
@@ -503,6 +508,8 @@ class _EvalGraph:
         dev = ds.x1.device
         self.cont = kind != 'pvae' and getattr(model, 'type_y', 'discrete') != 'discrete'
         self.use_s = bool(getattr(model, 'use_s', False))
+        # the count decoders ('binary' / 'poisson' / 'nb'): finished heads, ``dv_recon_rows``' count kinds (``_rows_pass``)
+        self.rec_kind = None if model.type_rec == 'diag_gaussian' else model.type_rec
         self.dp, self.full = dp, None
         if dp is not None:
             # this rank's rows as VIEWS of the dataset's tensors; the normalisers of the loss pass are the whole set's counts,
@@ -558,14 +565,25 @@ class _EvalGraph:
             torch.cuda.synchronize()
             gph = torch.cuda.CUDAGraph()
             eng.join_side()
-            with torch.cuda.graph(gph):
-                self.names, self.vec, self.loss_keys = self._sequence()
-            if dp is not None:
-                self._finalize_full()                           # (warm-up)
-                torch.cuda.synchronize()
-                self.graph_final = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph_final):
-                    self._finalize_full()
+            # no garbage collection while a stream is capturing, as in ``FusedStep.capture``: a collected cycle may own the
+            # graph of a retired model's evaluation (``_EvalGraph`` <-> model), and destroying a graph during a capture
+            # aborts the process
+            import gc
+            gc.collect()
+            gc_was_on = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.graph(gph):
+                    self.names, self.vec, self.loss_keys = self._sequence()
+                if dp is not None:
+                    self._finalize_full()                           # (warm-up)
+                    torch.cuda.synchronize()
+                    self.graph_final = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(self.graph_final):
+                        self._finalize_full()
+            finally:
+                if gc_was_on:
+                    gc.enable()
             self.graph = gph
         finally:
             eng.plan, eng.training, eng.carry_s = keep, keep_training, keep_carry
@@ -635,10 +653,10 @@ class _EvalGraph:
         if kind != 'pvae':
             self._y_metrics(res, vec[o:o + 3])
             o += 3
-        self._recon(ds.x1, res['px1'][0], res['px1'][1], None, vec[o:o + 4], 'x1', res['px_bias'])
+        self._recon(ds.x1, res['px1'], None, vec[o:o + 4], 'x1', res['px_bias'])
         o += 4
         if has_x2:
-            self._recon(ds.x2, res['px2'][0], res['px2'][1], self.x2idx32, vec[o:o + 4], 'x2', res['px_bias'])
+            self._recon(ds.x2, res['px2'], self.x2idx32, vec[o:o + 4], 'x2', res['px_bias'])
         return names, vec, list(losses)
 
     # ------------------------------------------------------------ rows sharded over ranks (data parallelism, round 6)
@@ -692,7 +710,6 @@ class _EvalGraph:
     def _sequence_partial(self, res, loss_vec):
         """this rank's share of the evaluation's partials into the exchange buffer (captured; no finalising launch)"""
         from . import kernels as K
-        from ._lib import GAUSS_SIGMA
         m, ds, kind = self.model, self.ds, self.model.kind
         rank, world = self.dp
         lo, hi, X = self.lo, self.hi, int(ds.x1.shape[1])
@@ -716,16 +733,11 @@ class _EvalGraph:
                 buf[tag] = (torch.empty(M, 6, device=x.device),
                             torch.zeros(self.blk[tag], 3, X, dtype=torch.float64, device=x.device), torch.empty(M, device=x.device))
             rows, part, ll = buf[tag]
-            x_rec, x_std = res[key][0], res[key][1]
-            if X <= K.RECON_ROWS_MAX_X:
-                K.recon_rows(rows, ll, x, x_rec, x_std, bias=bias[:2] if bias is not None else None,
-                             sd_shift=bias[2] if bias is not None else 0.0)
-            else:
-                K.recon_row_stats(rows, x, x_rec)
-                K.nll_rows_fwd(ll, x, x_rec, x_std, mode=GAUSS_SIGMA)
+            x_rec, ll = self._rows_pass(rows, ll, x, res[key], bias)
             t = '1' if tag == 'x1' else '2'
             self._slot('rows' + t).view(self.n_all, 6)[lo:hi].copy_(rows)
-            self._slot('ll' + t)[lo:hi].copy_(ll)
+            if ll is not None:      # ('binary' / 'poisson': no reported log-likelihood, the slot stays zero and is not read)
+                self._slot('ll' + t)[lo:hi].copy_(ll)
             if n_sel > 0:
                 nb = K.col_moment_blocks(n_sel)
                 K.col_moments(None, x, x_rec, sel=sel, part=part[:nb], r_bias=bias[0] if bias is not None else None)
@@ -759,7 +771,7 @@ class _EvalGraph:
             self.g_ll[tag].copy_(self._slot('ll' + t))
             part = self._slot('part' + t).view(-1, 3, X)
             K.recon_finalize(vec[o:o + 4], self.g_rows[tag], part, X, sel=sel, n=int(sel.numel()) if sel is not None else n,
-                             ll=self.g_ll[tag])
+                             ll=self.g_ll[tag] if self.rec_kind in (None, 'nb') else None)
             o += 4
 
     def _rank_metrics(self, proba, y32, pred32, yidx32, out3, n_rows):
@@ -836,10 +848,13 @@ class _EvalGraph:
         if self.sel is None:
             # q(z1|x1) of every row has just been computed by the loss pass (``_sequence`` runs it first): evaluation mode adds
             # no input noise, its encoder input rows [0, n) ARE x1 in dataset order, same layer chain, same kernels -- the
-            # first n rows of its heads' buffer are this product (8192 rows: 15 GFLOP not computed twice)
+            # first n rows of its heads' buffer are this product (8192 rows: 15 GFLOP not computed twice).  The raw-count
+            # switches change nothing here: ``_sequence`` clears ``eng.training`` before the pass, so ``_encoder_forward``
+            # takes sigma = 0 and hands the split feed ``noise=None`` -- its encoder rows are T(x1) exactly (log1p(x1) with
+            # ``x_transform='log1p'``), what ``forward`` feeds the encoder
             Q = self.plan.c_enc.out[-1][:n]
         else:
-            x1 = ds.x1.to(torch.float32)
+            x1 = m._enc_x(ds.x1.to(torch.float32))      # (``x_transform='log1p'``: the encoder reads log1p(x1))
             if X % 4:
                 # rows padded to 16 B (zero pads): the first layer's product then runs on the LDS-DMA kernels (``_Chain``)
                 if not hasattr(self, 'x1p'):
@@ -865,39 +880,60 @@ class _EvalGraph:
         self.zd[:n].copy_(z1)
         # the decoder's heads as a PLAIN product where the one-pass reconstruction statistics finish them on their way
         # (bias, softplus + shift: ``dv_recon_rows`` / ``dv_col_moments``): 16384 x 1956 x 600 at the raw product's 126 instead of 104 TF/s
+        # The count decoders' heads leave their launch FINISHED (probability / rate / [mean | theta]: ``raw_last_ok`` is false
+        # for them); ``px1`` / ``px2`` are 1-tuples for 'binary' / 'poisson' and (mu, theta) for 'nb' -- UNSCALED: the size
+        # factor of a ``library_size`` model is applied by the row pass (``_rows_pass``)
         lh = eng.L_decx[-1]
-        raw = bool(X <= K.RECON_ROWS_MAX_X and self.c_dec.raw_softplus_ok())
+        raw = bool(self.rec_kind is None and X <= K.RECON_ROWS_MAX_X and self.c_dec.raw_softplus_ok())
         PX = self.c_dec.forward([self.zd] + ([self.soh_d] if self.use_s else []), raw_last=raw)
         res['px_bias'] = (lh.b[:X], lh.b[X:2 * X], lh.shift1) if raw else None
-        res['px1'] = (PX[:n, :X], PX[:n, X:2 * X])
+        two = self.rec_kind in (None, 'nb')
+        res['px1'] = (PX[:n, :X], PX[:n, X:2 * X]) if two else (PX[:n, :X],)
         if kind != 'vfae':
-            res['px2'] = (PX[n:, :X], PX[n:, X:2 * X])
+            res['px2'] = (PX[n:, :X], PX[n:, X:2 * X]) if two else (PX[n:, :X],)
         return res
 
-    def _recon(self, x, x_rec, x_std, sel, out4, tag, bias=None):
+    def _rows_pass(self, rows, ll, x, px, bias):
+        """row statistics (+ log-likelihood rows) of the target rows ``x`` against the heads ``px`` -> (the reconstruction
+        ``dv_col_moments`` reads, the log-likelihood rows ``dv_recon_finalize`` reads or None).  Gaussian decoder: one pass up
+        to 1024 genes, else the two separate ones.  Count decoders: ``dv_recon_rows``' count kinds at any width; with
+        ``library_size`` the mean is scaled by the size factor of the SAME rows of ``x1`` -- for the x2 targets too,
+        as ``forward`` does it -- and stored in place of the mean head, where ``dv_col_moments`` finds it.  'binary' /
+        'poisson' report no log-likelihood (``_evaluate`` passes no second head: nan), 'nb' the negative binomial's."""
+        from . import kernels as K
+        from ._lib import GAUSS_SIGMA
+        if self.rec_kind is not None:
+            nb = self.rec_kind == 'nb'
+            size = self.ds.x1.to(torch.float32) if getattr(self.model, 'library_size', False) else None
+            K.recon_rows(rows, ll if nb else None, x, px[0], px[1] if nb else None, kind=self.rec_kind, size_from=size,
+                         rec_out=px[0] if size is not None else None)
+            return px[0], (ll if nb else None)
+        if x.shape[1] <= K.RECON_ROWS_MAX_X:
+            K.recon_rows(rows, ll, x, px[0], px[1], bias=bias[:2] if bias is not None else None,
+                         sd_shift=bias[2] if bias is not None else 0.0)
+        else:
+            K.recon_row_stats(rows, x, px[0])
+            K.nll_rows_fwd(ll, x, px[0], px[1], mode=GAUSS_SIGMA)
+        return px[0], ll
+
+    def _recon(self, x, px, sel, out4, tag, bias=None):
         """``eval_x_reconstruction`` (src/DGMMixin.py:128-156) over the rows ``sel`` (all when None): row statistics, column
         moments and log-likelihood rows from the HIP kernels, combined in float64 by ``dv_recon_finalize`` into ``out4`` =
         [rmse, r2, pearr, ll].  The statistics are taken over ALL rows and selected afterwards (no gathered copies of
         the x2 rows and their reconstructions).  Rows of up to 1024 genes: row statistics and log-likelihood rows in ONE pass
-        (``dv_recon_rows``); ``bias`` = (bias_mu, bias_sd, shift): the heads are raw products, finished by the passes."""
+        (``dv_recon_rows``); ``bias`` = (bias_mu, bias_sd, shift): the heads are raw products, finished by the passes.
+        ``px``: the heads of these rows (``_rows_pass``: the count decoders' route)."""
         from . import kernels as K
-        from ._lib import GAUSS_SIGMA
         x = x.to(torch.float32)
         M, X = x.shape
         n = int(sel.numel()) if sel is not None else M
-        one_pass = X <= K.RECON_ROWS_MAX_X
-        assert bias is None or one_pass
+        assert bias is None or X <= K.RECON_ROWS_MAX_X
         buf = self.__dict__.setdefault('_recon_bufs', {})
         if tag not in buf:
             buf[tag] = (torch.empty(M, 6, device=x.device), torch.empty(K.col_moment_blocks(n), 3, X, dtype=torch.float64, device=x.device),
                         torch.empty(M, device=x.device))
         rows, part, ll = buf[tag]
-        if one_pass:
-            K.recon_rows(rows, ll, x, x_rec, x_std, bias=bias[:2] if bias is not None else None,
-                         sd_shift=bias[2] if bias is not None else 0.0)
-        else:
-            K.recon_row_stats(rows, x, x_rec)
-            K.nll_rows_fwd(ll, x, x_rec, x_std, mode=GAUSS_SIGMA)
+        x_rec, ll = self._rows_pass(rows, ll, x, px, bias)
         K.col_moments(None, x, x_rec, sel=sel, part=part, r_bias=bias[0] if bias is not None else None)
         K.recon_finalize(out4, rows, part, X, sel=sel, n=n, ll=ll)
 

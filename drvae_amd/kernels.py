@@ -1057,11 +1057,35 @@ def col_moment_blocks(M):
 RECON_ROWS_MAX_X = 1024
 
 
-def recon_rows(rows, ll, x, mu, sd, *, bias=None, sd_shift=1e-3):
+def recon_rows(rows, ll, x, mu, sd, *, bias=None, sd_shift=1e-3, **count):
     """row statistics (M, 6) and log-likelihood rows (M; may be None) of a reconstruction in ONE pass over (x, mu, sd),
     X <= RECON_ROWS_MAX_X -- ``recon_row_stats`` + ``nll_rows_fwd``.  ``bias`` = (bias_mu, bias_sd): mu / sd are the
-    heads' raw products, finished on the way."""
+    heads' raw products, finished on the way.
+
+    The count decoders, keyword-only: ``kind=None | 'binary' | 'poisson' | 'nb'``, ``size_from=None``, ``rec_out=None`` (taken
+    as ``**count`` so that the Gaussian pass's own signature stays the one its CPU stand-in ``tests/kernel_ref.py`` states; the
+    stand-in of these three is ``tests/eval_counts_ref.py``; any other keyword is a TypeError).  ``kind`` other than None: any
+    X.  ``mu`` is the mean head's finished output, ``sd`` the theta head for 'nb' and None otherwise.  ``size_from`` (M, X;
+    'poisson' / 'nb'): the statistics and the log-likelihood are taken at r = s * mu, s the size factor of ``size_from``'s rows
+    (the target itself or another matrix); ``rec_out`` (M, X; with ``size_from`` only, may be ``mu`` itself) receives r."""
+    kind, size_from, rec_out = count.pop('kind', None), count.pop('size_from', None), count.pop('rec_out', None)
+    if count:
+        raise TypeError('recon_rows() got an unexpected keyword argument %r' % sorted(count)[0])
     M, X = x.shape
+    if kind is not None:
+        assert kind in ('binary', 'poisson', 'nb') and bias is None
+        assert tuple(mu.shape) == (M, X) and rows.is_contiguous() and tuple(rows.shape) == (M, 6)
+        assert (sd is not None and tuple(sd.shape) == (M, X)) if kind == 'nb' else sd is None
+        assert size_from is None or tuple(size_from.shape) == (M, X)
+        assert rec_out is None or tuple(rec_out.shape) == (M, X)
+        assert ll is None or (ll.is_contiguous() and ll.numel() == M)
+        d = _lib.ReconRows(x=_f32(x), ldx=_ld(x), mu=_f32(mu), sd=_f32(sd), ldp=_ld(mu), M=M, X=X, rows=_f32(rows),
+                           ll=_f32(ll), kind=_lib.RECON_KIND[kind], ldt=_ld(sd) if sd is not None else 0,
+                           size_x=_f32(size_from), size_ld=_ld(size_from) if size_from is not None else 0,
+                           rec_out=_f32(rec_out), rec_ld=_ld(rec_out) if rec_out is not None else 0)
+        _lib.check(_lib.load().dv_recon_rows(C.byref(d), _stream()), 'dv_recon_rows')
+        return
+    assert size_from is None and rec_out is None, 'size_from / rec_out: the count kinds'
     assert tuple(mu.shape) == (M, X) and tuple(sd.shape) == (M, X) and _ld(mu) == _ld(sd)
     assert rows.is_contiguous() and tuple(rows.shape) == (M, 6)
     d = _lib.ReconRows(x=_f32(x), ldx=_ld(x), mu=_f32(mu), sd=_f32(sd), ldp=_ld(mu),

@@ -875,8 +875,29 @@ int dv_col_moments(const float* x, int64_t ldx, const float* r, int64_t ldr, int
  * row in registers.  Same outputs: rows (M, 6), ll (M, optional) -- bitwise those of dv_recon_row_stats on the dword path
  * (odd X or unaligned rows); rows of even width are read with 8-B loads (a lane owns column pairs: another summation order).  bias_mu / bias_sd (both or neither): mu / sd are the heads' RAW products and are finished on the way
  * (mu + bias_mu, softplus(sd + bias_sd) + sd_shift).  X beyond the limit: DV_ERR_UNSUPPORTED (callers take the two
- * separate passes). */
+ * separate passes).
+ *
+ * The COUNT kinds (trailing fields, ABI 13; all zero / NULL = DV_RECON_GAUSS: the launch above, bit for bit, with its
+ * refusals).  kind = DV_RECON_BERNOULLI / _POISSON / _NEGBIN: the whole-set evaluation of the count decoders in one pass
+ * per row, ANY X (a workgroup walks a row; 16-byte loads when X % 4 == 0 and every operand's rows are 16-byte aligned):
+ *   heads  mu (ldp) = the mean head's POST-activation output, as dv_rec_nll_rows reads it (probability | rate | NB mean);
+ *          NEGBIN: sd (row stride ldt >= X, its own) = the theta head; else sd is not read.  bias_mu / bias_sd / sd_shift:
+ *          NULL / unread (the count heads leave their launch finished)
+ *   mean   r = mu without a size source; with size_x (row stride size_ld): r = s * mu, s = max(sum_g size_x[i,g], 1) / X,
+ *          ONE rounded product.  size_x may be x itself or another matrix (the prediction of x2 is made at x1's depth);
+ *          theta is never scaled
+ *   rows   (M, 6): the six statistics of dv_recon_row_stats between x and r -- the centred sums from a second walk over
+ *          the row at the means of the first (never from raw moments)
+ *   ll     (M, optional): sum_g log p(x | r), the terms of dv_rec_nll_rows (kinds DV_REC_BERNOULLI / _POISSON[_LIB] /
+ *          _NEGBIN[_LIB]: the same device functions)
+ *   rec_out (row stride rec_ld, optional, WITH a size source only): the finished mean r, for dv_col_moments; may alias
+ *          mu (every element is read and written by the same lane).  Without a size source r IS mu: nothing to store,
+ *          DV_ERR_ARG
+ * No atomics, fixed summation order: equal bits on every launch.  DV_ERR_ARG before any launch: kind outside the four,
+ * a size source with BERNOULLI, bias_mu / bias_sd with a count kind, NEGBIN with ldt < X, rec_out without a size source,
+ * a row stride below X, a missing operand (M > 0); size_x / rec_out with DV_RECON_GAUSS. */
 #define DV_RECON_ROWS_MAX_X 1024
+enum { DV_RECON_GAUSS = 0, DV_RECON_BERNOULLI = 1, DV_RECON_POISSON = 2, DV_RECON_NEGBIN = 3 };
 typedef struct dv_recon_rows_desc {
     const float* x;
     int64_t ldx;
@@ -890,6 +911,12 @@ typedef struct dv_recon_rows_desc {
     int32_t X;
     float* rows;
     float* ll;
+    int32_t kind;
+    int64_t ldt;
+    const float* size_x;
+    int64_t size_ld;
+    float* rec_out;
+    int64_t rec_ld;
 } dv_recon_rows_desc;
 int dv_recon_rows(const dv_recon_rows_desc* d, dv_stream_t stream);
 
