@@ -976,6 +976,7 @@ def mmd_mix_bwd(W, rs, G, kind, gammas, gout, coef, sa=None, sb=None):
 
 
 def mmd_mix_combine(out4, p11, p12, p22, c11, c12, c22):
+    c11, c12, c22 = (float(np.float32(c)) for c in (c11, c12, c22))       # (the launch receives the counts as fp32)
     m11, m12, m22 = p11.double().sum() / c11, p12.double().sum() / c12, p22.double().sum() / c22
     out4.copy_(torch.stack([m11 - 2.0 * m12 + m22, m11, m12, m22]).float())
 
