@@ -325,12 +325,13 @@ class DeepGenerativeModelMixin:
 
     # ---------------------------------------------------------------- evaluation
     @torch.no_grad()
-    def eval_x_reconstruction(self, x, x_rec, x_rec_logvar=None):
+    def eval_x_reconstruction(self, x, x_rec, x_rec_logvar=None, x_rec_logit=None):
         """RMSE, variance-weighted R^2, mean per-row Pearson r and mean log-likelihood of a
         reconstruction (src/DGMMixin.py:128-156).  The O(rows x genes) reductions run in two HIP
         kernels; the final combination of the (rows x 6) / (3 x genes) partials is done in float64
         on the host, like the reference's numpy/scipy/sklearn code.  ``x_rec_logvar`` is what the
-        reference passes as third argument of ``decoder_x.logp_perx``: the decoder's std."""
+        reference passes as third argument of ``decoder_x.logp_perx``: the decoder's std.  ``x_rec_logit`` (``type_rec='zinb'``
+        alone): the dropout logits, its fourth; the statistics stay those of the negative-binomial mean ``x_rec``."""
         from . import kernels as K
         dev = next(self.parameters()).device
         x = x.to(dev, torch.float32).contiguous()
@@ -349,7 +350,8 @@ class DeepGenerativeModelMixin:
         with np.errstate(divide='ignore', invalid='ignore'):
             out['pearr'] = float((r[:, 5] / np.sqrt(r[:, 3] * r[:, 4])).mean())
         if x_rec_logvar is not None:
-            out['ll'] = float(self.decoder_x.logp_perx(x, x_rec, x_rec_logvar.to(dev, torch.float32)).mean())
+            more = () if x_rec_logit is None else (x_rec_logit.to(dev, torch.float32),)
+            out['ll'] = float(self.decoder_x.logp_perx(x, x_rec, x_rec_logvar.to(dev, torch.float32), *more).mean())
         else:
             out['ll'] = float('nan')
         return out

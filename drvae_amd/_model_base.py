@@ -79,11 +79,12 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         self.to(device)
 
     def _check_supported(self):
-        if self.type_rec not in ('diag_gaussian', 'binary', 'poisson', 'nb'):
-            raise ValueError("type_rec must be 'diag_gaussian', 'binary', 'poisson' or 'nb'")      # src/DrVAE.py:124-131
+        if self.type_rec not in ('diag_gaussian', 'binary', 'poisson', 'nb', 'zinb'):
+            raise ValueError("type_rec must be 'diag_gaussian', 'binary', 'poisson', 'nb' or 'zinb'")      # src/DrVAE.py:124-131
         # 'binary' / 'poisson' point at blk.BernoulliDecoder / blk.PoissonDecoder, which the reference's blocks.py
         # does not define (its constructor raises AttributeError there): built here as labelled EXTENSIONS; 'nb' (the
-        # negative binomial for overdispersed counts, blk.NegativeBinomialDecoder) is an extension the reference never names
+        # negative binomial for overdispersed counts, blk.NegativeBinomialDecoder) and 'zinb' (its zero-inflated form,
+        # blk.ZeroInflatedNegativeBinomialDecoder) are extensions the reference never names
         bad = []
         # use_s=True is an EXTENSION here: the reference crashes on it (torch.cat([z, s_raw]) of a float and an
         # integer tensor, src/DrVAE.py:438), so it is built from the evident intent -- one_hot(s) appended to the
@@ -143,7 +144,8 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
             setattr(self, 'encoder_z3' if self.kind == 'drvae' else 'encoder_z2', top)
             self.decoder_z1 = blk.DiagGaussianModule([top_z, self.dim_y], self.dim_h_de_z1, Z1, **hp)
         dec = {'diag_gaussian': blk.DiagGaussianSigmaModule, 'binary': blk.BernoulliDecoder,
-               'poisson': blk.PoissonDecoder, 'nb': blk.NegativeBinomialDecoder}[self.type_rec]      # src/DrVAE.py:124-129
+               'poisson': blk.PoissonDecoder, 'nb': blk.NegativeBinomialDecoder,
+               'zinb': blk.ZeroInflatedNegativeBinomialDecoder}[self.type_rec]      # src/DrVAE.py:124-129
         self.decoder_x = dec([Z1] + s_in, self.dim_h_de_x, self.dim_x, **hp)
 
     def _dropout_notes(self):
@@ -167,13 +169,15 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
             hidden['decoder_z1'] = self.dim_h_de_z1
         hidden['decoder_x'] = self.dim_h_de_x
         # (one head in the fused step: the classifier -- a regression head's log-variance is fixed, its layer is not in the
-        # step's chain (``FusedStep.L_clf``) -- and a Bernoulli / Poisson decoder; the negative binomial has two)
+        # step's chain (``FusedStep.L_clf``) -- and a Bernoulli / Poisson decoder; the negative binomial has two, its
+        # zero-inflated form three: all of them read the one mask)
         two_heads = [n for n, h in hidden.items() if len(h) and n != 'encoder_y' and not
-                     (n == 'decoder_x' and self.type_rec not in ('diag_gaussian', 'nb'))]
+                     (n == 'decoder_x' and self.type_rec not in ('diag_gaussian', 'nb', 'zinb'))]
         undropped = [n for n, h in hidden.items() if not len(h)]
+        three = ' (all three heads of the zero-inflated decoder_x)' if self.type_rec == 'zinb' and 'decoder_x' in two_heads else ''
         warnings.warn('dropout_rate=%g in the fused train step differs from the block-level path in two labelled ways: '
-                      'both heads share ONE keep mask in %s; no dropout at all (no hidden layer) in %s'
-                      % (self.dropout_rate, ', '.join(two_heads) or 'no block', ', '.join(undropped) or 'no block'))
+                      'both heads share ONE keep mask in %s%s; no dropout at all (no hidden layer) in %s'
+                      % (self.dropout_rate, ', '.join(two_heads) or 'no block', three, ', '.join(undropped) or 'no block'))
 
     def _anneal_config(self):
         """the annealing attributes as they stand now, as ``StepConfig`` keyword arguments (checked: ValueError)"""
@@ -235,7 +239,10 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
 
         Raw-count switches (EXTENSIONS): the encoder reads T(x1) (``x_transform``); with ``library_size`` the means
         ``px1[0]`` / ``x1_rec`` and ``px2[0]`` / ``x2_pert`` are multiplied by the size factor of ``x1`` -- the depth of the
-        perturbed profile is unknown at prediction time, so the prediction is made at the depth of the profile it starts from."""
+        perturbed profile is unknown at prediction time, so the prediction is made at the depth of the profile it starts from.
+
+        ``type_rec='zinb'``: ``px1`` = (mu, theta, dropout logit); ``x1_rec`` / ``x2_pert`` are the negative-binomial MEAN (scaled
+        under ``library_size``) -- the denoised expression, NOT the mixture's mean (1 - pi) mu."""
         self.eval()
         x1 = x1.to(next(self.parameters()).device, torch.float32)
         cond = self._s_inputs(s, x1)

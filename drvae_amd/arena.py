@@ -21,7 +21,8 @@ N_LOSS = 8   # RECL KLD PERT YL MMD ELBO CMPL + 1 spare, parked in FRONT of the 
 
 _HEAD_PAIRS = (('encoder_mu.linear_mu', 'encoder_lv.linear_lv'),
                ('encoder_mu.linear_mu', 'encoder_sg.linear_sg'),
-               ('decoder_m.linear_m', 'decoder_t.linear_t'))      # (the negative-binomial decoder's mean | theta)
+               ('decoder_m.linear_m', 'decoder_t.linear_t'),      # (the negative-binomial decoder's mean | theta)
+               ('decoder_m.linear_m', 'decoder_d.linear_d'))      # (zero-inflated: mean | theta | dropout logit, a triple)
 
 
 def _fusion_groups(names, frozen=()):
@@ -154,16 +155,19 @@ class ParamArena:
     def g(self, name):
         return self._view(self.grad, name)
 
-    def fused(self, buf, first, second):
-        """(N1+N2, ...) view covering two adjacent parameters (the two heads of a block)."""
-        o = self.offsets[first]
-        assert self.offsets[second] == o + self.numel(first), (first, second)
-        s1, s2 = self.shapes[first], self.shapes[second]
-        assert s1[1:] == s2[1:]
-        shape = (s1[0] + s2[0],) + s1[1:]
+    def fused(self, buf, first, *others):
+        """(N1+N2[+N3], ...) view covering adjacent parameters (the two heads of a block; the zero-inflated decoder's three)."""
+        o = end = self.offsets[first]
+        s1 = self.shapes[first]
+        rows = 0
+        for n in (first,) + others:
+            assert self.offsets[n] == end and self.shapes[n][1:] == s1[1:], (first, n)
+            end += self.numel(n)
+            rows += self.shapes[n][0]
+        shape = (rows,) + s1[1:]
         if len(s1) == 2 and row_stride(s1) != s1[1]:
-            return buf[o:o + self.numel(first) + self.numel(second)].view(shape[0], row_stride(s1))[:, :s1[1]]
-        return buf[o:o + self.numel(first) + self.numel(second)].view(shape)
+            return buf[o:end].view(shape[0], row_stride(s1))[:, :s1[1]]
+        return buf[o:end].view(shape)
 
     def adopt(self, module):
         """Make every parameter of ``module`` an alias of the arena (values are copied in;

@@ -17,11 +17,22 @@ def _whole_rows(t):
 
 
 class _Lin:
-    """One Linear layer (or two fused heads) bound to arena views."""
+    """One Linear layer (or two fused heads) bound to arena views.  ``third`` (with ``second``; the zero-inflated decoder's
+    dropout-logit head): one more head behind the pair, identity activation -- ``W`` / ``b`` / ``g`` and their gradients are the
+    fused (3 split, K) views, which is all the backward products need; the forward runs the pair as it runs any pair and the
+    third head as one more plain Linear from the same input (``_Chain.forward``)."""
 
     def __init__(self, arena, wname, bname, gname=None, second=None, act='identity', act1=None, shift0=0.0,
-                 shift1=0.0):
-        if second is None:
+                 shift1=0.0, third=None):
+        self.tri = third is not None
+        if self.tri:
+            names = list(zip((wname, bname, gname), second, third))
+            self.W, self.dW = arena.fused(arena.param, *names[0]), arena.fused(arena.grad, *names[0])
+            self.b, self.db = arena.fused(arena.param, *names[1]), arena.fused(arena.grad, *names[1])
+            self.g = arena.fused(arena.param, *names[2]) if all(names[2]) else None
+            self.dg = arena.fused(arena.grad, *names[2]) if all(names[2]) else None
+            self.split = arena.shapes[wname][0]
+        elif second is None:
             self.W, self.dW = arena.p(wname), arena.g(wname)
             self.b, self.db = arena.p(bname), arena.g(bname)
             self.g = arena.p(gname) if gname else None
@@ -192,6 +203,17 @@ class _Chain:
                     K.gemm(self.out[li], x[0], l.W, True, True, A2=x[1] if len(x) > 1 else None, overread=True,
                            publish=publish if li == 0 else None, kpad=kpad)
                 return self.out[-1]
+            if last and l.tri:
+                # three heads (zero-inflated decoder): the pair exactly as a two-head layer runs, into columns [0, 2 split),
+                # and the identity head as one more plain Linear from the same input into columns [2 split, 3 split)
+                assert resid is None
+                n2, x2 = 2 * l.split, x[1] if len(x) > 1 else None
+                sc = (None, None) if l.scale is None else (l.scale[:n2], l.scale[n2:])
+                K.linear_fwd(self.out[li][:, :n2], x[0], l.W[:n2], l.b[:n2], x2=x2, scale=sc[0], split=l.split, act0=l.act0,
+                             act1=l.act1, shift0=l.shift0, shift1=l.shift1, overread=True,
+                             publish=publish if (li == 0 and l.g is None) else None, kpad=kpad)
+                K.linear_fwd(self.out[li][:, n2:], x[0], l.W[n2:], l.b[n2:], x2=x2, scale=sc[1], overread=True, kpad=kpad)
+                break
             K.linear_fwd(self.out[li], x[0], l.W, l.b, x2=x[1] if len(x) > 1 else None, scale=l.scale, split=l.split,
                          act0=l.act0, act1=l.act1, shift0=l.shift0, shift1=l.shift1,
                          resid=resid if last else None, resid_cols=self.resid_cols if (last and resid is not None) else 0,

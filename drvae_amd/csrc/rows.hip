@@ -1165,6 +1165,104 @@ __global__ __launch_bounds__(256) void nb_nll_rows_kernel(float shift, const flo
     }
 }
 
+// Zero-inflated negative-binomial reconstruction rows (type_rec = 'zinb': labelled extension, no counterpart in the
+// reference): a third head, the dropout logit a (identity activation), pi = sigmoid(a), over the NB term at (m, t):
+//   x > 0:  log p = -softplus(a) + logNB(x)              d/da = -pi;   d/da_m, d/da_t: the NB term's
+//   x = 0:  log p = log(pi + (1 - pi) e^{L0}),  L0 = logNB(0) = -t log1p(m/t) (nb_term returns exactly that: its pairs are 0)
+//           with rho = sigmoid(L0 - a), the NB component's responsibility for the zero:
+//           d/da = (1 - rho) (1 - pi) (1 - e^{L0});      d/da_m, d/da_t: rho times the NB term's
+// The x = 0 term never adds a vanishing addend to 1: with q = 1 - pi = sigmoid(-a) and z = q (-expm1(L0)) in [0, 1),
+//   z <= 1/2: log1p(-z);   else max(u, w) + log1p(exp(-|a - L0|)),  u = -softplus(-a), w = -softplus(a) + L0  (u - w = a - L0)
+// and its logit gradient is a product of non-negative factors, never sigmoid(a - L0) - sigmoid(a).  Both sigmoid pairs come
+// from ONE exp(-|.|): (1, e) / (1 + e), no 1 - sigmoid.  LIB / shift / s / v: nb_term's, untouched (theta and the logit are
+// never scaled)
+template <bool LIB>
+__device__ __forceinline__ float zinb_term(float shift, float s, float x, float v, float t, float a, float& g_m, float& g_t,
+                                           float& g_d) {
+    const float L = nb_term<LIB>(shift, s, x, v, t, g_m, g_t);
+    const float e = expf(-fabsf(a)), r = 1.f / (1.f + e), l = log1pf(e);
+    const float pi = a >= 0.f ? r : e * r, q = a >= 0.f ? e * r : r;
+    const float sp = fmaxf(a, 0.f) + l;            // softplus(a); softplus(-a) = sp - a exactly as max(-a, 0) + l
+    if (x > 0.f) {
+        g_d = -pi;
+        return L - sp;
+    }
+    const float em = -expm1f(L), z = q * em;
+    const float d = L - a, ed = expf(-fabsf(d)), rd = 1.f / (1.f + ed);
+    const float rho = d >= 0.f ? rd : ed * rd, nrho = d >= 0.f ? ed * rd : rd;
+    g_m *= rho, g_t *= rho;
+    g_d = nrho * z;
+    if (z <= 0.5f) return log1pf(-z);
+    const float u = -(fmaxf(-a, 0.f) + l), w = L - sp;
+    return fmaxf(u, w) + log1pf(ed);
+}
+
+// one workgroup per row, the NB kernel's shape: v row = [mu | theta | logit], dpre row = [d/da_m | d/da_t | d/da_d], 3X columns
+// each; VEC as there (the dispatcher checks), the same fixed summation order, the same one-copy walk of the quad
+template <bool VEC, bool LIB>
+__global__ __launch_bounds__(256) void zinb_nll_rows_kernel(float shift, const float* __restrict__ coef,
+                                                            const float* __restrict__ x, int64_t ldx,
+                                                            const int32_t* __restrict__ xidx, const float* __restrict__ v,
+                                                            int64_t ldv, int M, int X, float* __restrict__ out,
+                                                            float* __restrict__ dpre, int64_t ldd) {
+    __shared__ float part[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int r = blockIdx.x; r < M; r += gridDim.x) {
+        const float* xr = x + (int64_t)(xidx ? xidx[r] : r) * ldx;
+        const float* vr = v + (int64_t)r * ldv;
+        float* dr = coef ? dpre + (int64_t)r * ldd : nullptr;
+        const float c = coef ? coef[r] : 0.f;
+        float sz = 1.f;
+        if constexpr (LIB) sz = row_size_factor<VEC>(xr, X, part);      // (the term loops' read of the row: from cache)
+        float acc = 0.f;
+        if constexpr (VEC) {
+            for (int q = threadIdx.x; q < (X >> 2); q += 256) {
+                const float4 xv = reinterpret_cast<const float4*>(xr)[q];
+                const float4 mv = reinterpret_cast<const float4*>(vr)[q];
+                const float4 tv = reinterpret_cast<const float4*>(vr + X)[q];
+                const float4 av = reinterpret_cast<const float4*>(vr + 2 * (int64_t)X)[q];
+                float4 gm = make_float4(0.f, 0.f, 0.f, 0.f), gt = gm, gd = gm;
+                // (ONE copy of the term's code, walked four times: see nb_nll_rows_kernel)
+#pragma unroll 1
+                for (int j = 0; j < 4; ++j) {
+                    const float xj = j == 0 ? xv.x : j == 1 ? xv.y : j == 2 ? xv.z : xv.w;
+                    const float mj = j == 0 ? mv.x : j == 1 ? mv.y : j == 2 ? mv.z : mv.w;
+                    const float tj = j == 0 ? tv.x : j == 1 ? tv.y : j == 2 ? tv.z : tv.w;
+                    const float aj = j == 0 ? av.x : j == 1 ? av.y : j == 2 ? av.z : av.w;
+                    float a, b, e;
+                    acc += zinb_term<LIB>(shift, sz, xj, mj, tj, aj, a, b, e);
+                    if (coef) {
+                        a *= c, b *= c, e *= c;
+                        gm.x = j == 0 ? a : gm.x, gm.y = j == 1 ? a : gm.y, gm.z = j == 2 ? a : gm.z, gm.w = j == 3 ? a : gm.w;
+                        gt.x = j == 0 ? b : gt.x, gt.y = j == 1 ? b : gt.y, gt.z = j == 2 ? b : gt.z, gt.w = j == 3 ? b : gt.w;
+                        gd.x = j == 0 ? e : gd.x, gd.y = j == 1 ? e : gd.y, gd.z = j == 2 ? e : gd.z, gd.w = j == 3 ? e : gd.w;
+                    }
+                }
+                if (coef) {
+                    reinterpret_cast<float4*>(dr)[q] = gm;
+                    reinterpret_cast<float4*>(dr + X)[q] = gt;
+                    reinterpret_cast<float4*>(dr + 2 * (int64_t)X)[q] = gd;
+                }
+            }
+        } else {
+            for (int g = threadIdx.x; g < X; g += 256) {
+                float gm, gt, gd;
+                acc += zinb_term<LIB>(shift, sz, xr[g], vr[g], vr[X + g], vr[2 * (int64_t)X + g], gm, gt, gd);
+                if (coef) {
+                    dr[g] = c * gm;
+                    dr[X + g] = c * gt;
+                    dr[2 * (int64_t)X + g] = c * gd;
+                }
+            }
+        }
+        acc = dv_wave_sum_all(acc);
+        if (lane == 0) part[wave] = acc;
+        __syncthreads();
+        if (threadIdx.x == 0) out[r] = (part[0] + part[1]) + (part[2] + part[3]);
+        __syncthreads();
+    }
+}
+
 __global__ void nll_rows_bwd_kernel(const float* __restrict__ coef, const float* __restrict__ x, int64_t ldx,
                                     const int32_t* __restrict__ xidx, const float* __restrict__ mu,
                                     const float* __restrict__ sd, int64_t ldp, int M, int X, int mode, int sd_act,
@@ -3338,21 +3436,43 @@ static void launch_rec_nll_rows(bool nb, bool vec, int kind, float shift, const 
                            M, X, out, dpre, ldd);
 }
 
+template <bool LIB>
+static void launch_zinb_nll_rows(bool vec, float shift, const float* coef, const float* x, int64_t ldx, const int32_t* xidx,
+                                 const float* v, int64_t ldv, int M, int X, float* out, float* dpre, int64_t ldd,
+                                 dv_stream_t stream) {
+    const dim3 grid(grid_for(M, 1, 4096)), block(256);
+    if (vec)
+        hipLaunchKernelGGL((zinb_nll_rows_kernel<true, LIB>), grid, block, 0, ST(stream), shift, coef, x, ldx, xidx, v, ldv,
+                           M, X, out, dpre, ldd);
+    else
+        hipLaunchKernelGGL((zinb_nll_rows_kernel<false, LIB>), grid, block, 0, ST(stream), shift, coef, x, ldx, xidx, v,
+                           ldv, M, X, out, dpre, ldd);
+}
+
 extern "C" int dv_rec_nll_rows(int32_t kind, float shift, const float* coef, const float* x, int64_t ldx,
                                const int32_t* xidx, const float* v, int64_t ldv, int32_t M, int32_t X, float* out,
                                float* dpre, int64_t ldd, dv_stream_t stream) {
-    DV_REQUIRE(M >= 0 && X >= 1 && kind >= DV_REC_BERNOULLI && kind <= DV_REC_NEGBIN_LIB);
+    DV_REQUIRE(M >= 0 && X >= 1 && kind >= DV_REC_BERNOULLI && kind <= DV_REC_ZINB_LIB);
     if (M == 0) return DV_OK;
     DV_REQUIRE(x && v && out && (coef == nullptr || dpre != nullptr));
     // the library-scaled kinds: the unscaled kind's kernel, compiled with the size-factor sweep in front of its term loop
-    const bool lib = kind == DV_REC_POISSON_LIB || kind == DV_REC_NEGBIN_LIB;
+    const bool lib = kind == DV_REC_POISSON_LIB || kind == DV_REC_NEGBIN_LIB || kind == DV_REC_ZINB_LIB;
     const bool nb = kind == DV_REC_NEGBIN || kind == DV_REC_NEGBIN_LIB;
+    const bool zinb = kind == DV_REC_ZINB || kind == DV_REC_ZINB_LIB;
     bool vec = false;
-    if (nb) {      // v = [mu | theta], dpre = [d/da_m | d/da_t]: 2X columns each, a kernel of its own
-        DV_REQUIRE(ldv >= 2 * (int64_t)X && (coef == nullptr || ldd >= 2 * (int64_t)X));
+    if (nb || zinb) {      // v = [mu | theta (| logit)], dpre = [d/da_m | d/da_t (| d/da_d)]: 2X (3X) columns each, kernels of their own
+        const int64_t w = (nb ? 2 : 3) * (int64_t)X;
+        DV_REQUIRE(ldv >= w && (coef == nullptr || ldd >= w));
         auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
         vec = X % 4 == 0 && a16(x) && a16(v) && ldx % 4 == 0 && ldv % 4 == 0 &&
               (coef == nullptr || (a16(dpre) && ldd % 4 == 0));
+    }
+    if (zinb) {
+        if (lib)
+            launch_zinb_nll_rows<true>(vec, shift, coef, x, ldx, xidx, v, ldv, M, X, out, dpre, ldd, stream);
+        else
+            launch_zinb_nll_rows<false>(vec, shift, coef, x, ldx, xidx, v, ldv, M, X, out, dpre, ldd, stream);
+        DV_RETURN_LAUNCH();
     }
     const int k = kind == DV_REC_POISSON_LIB ? DV_REC_POISSON : kind;
     if (lib)

@@ -81,7 +81,8 @@ class StepConfig:
     # type of p(x|z): 'diag_gaussian' (the only one the reference can build) | 'binary' | 'poisson' -- the Bernoulli /
     # Poisson decoders src/DrVAE.py:124-129 names and blocks.py never defines: one Linear head, log-likelihood rows
     # by dv_rec_nll_rows (EXTENSION) | 'nb': the negative binomial for overdispersed counts (EXTENSION, no counterpart in
-    # the reference) -- two softplus heads [mu | theta] over one trunk, rows and both heads' gradients by the same launch
+    # the reference) -- two softplus heads [mu | theta] over one trunk, rows and both heads' gradients by the same launch |
+    # 'zinb': the zero-inflated negative binomial (EXTENSION) -- a third head, the dropout logit (identity), behind those two
     type_rec: str = 'diag_gaussian'
     use_s: bool = False
     dim_s: int = 2
@@ -128,10 +129,10 @@ class StepConfig:
     # (``ParamArena.avg``, ``dv_adam_hyper.avg``).  None: nothing of this exists -- no buffer, no launch
     # argument, the step as it ever was.  ``optim_alg='adamw'`` is Adam with torch.optim.AdamW's decoupled weight decay
     ema_decay: Optional[float] = None
-    # EXTENSIONS (no counterpart in the reference) for RAW COUNTS, count decoders ('poisson' / 'nb') only; x >= 0:
+    # EXTENSIONS (no counterpart in the reference) for RAW COUNTS, count decoders ('poisson' / 'nb' / 'zinb') only; x >= 0:
     #   x_transform='log1p': the encoder reads log1p(x) + sigma * eps; the reconstruction target stays the raw row x, no noise
     #   library_size=True  : every decoder mean of a row is multiplied by the observed size factor of its target row,
-    #                        s = max(sum_g x_g, 1) / dim_x -- mu = s * (softplus(a_m) + 1e-6); the NB's theta is untouched
+    #                        s = max(sum_g x_g, 1) / dim_x -- mu = s * (softplus(a_m) + 1e-6); theta and the dropout logit are untouched
     # Either on: SPLIT MODE -- the plan holds the raw target rows in a buffer of their own (``_Plan.XT``), the input launch is
     # ``dv_batch_feed`` in its split form on every path.  Both off: nothing of this exists, the step as it ever was
     x_transform: Optional[str] = None
@@ -188,7 +189,7 @@ class StepConfig:
 
 
 X_TRANSFORMS = (None, 'log1p')
-COUNT_DECODERS = ('poisson', 'nb')
+COUNT_DECODERS = ('poisson', 'nb', 'zinb')
 
 
 def check_counts_config(x_transform, library_size, type_rec, prefix=''):
@@ -198,7 +199,7 @@ def check_counts_config(x_transform, library_size, type_rec, prefix=''):
         raise ValueError("%sx_transform must be None or 'log1p', not %r" % (prefix, x_transform))
     on = [n for n, v in (('x_transform', x_transform is not None), ('library_size', bool(library_size))) if v]
     if on and type_rec not in COUNT_DECODERS:
-        raise ValueError("%s%s is for the count decoders (type_rec='poisson' / 'nb'), not type_rec=%r"
+        raise ValueError("%s%s is for the count decoders (type_rec='poisson' / 'nb' / 'zinb'), not type_rec=%r"
                          % (prefix, ' / '.join(on), type_rec))
     return dict(x_transform=x_transform, library_size=bool(library_size))
 
@@ -261,9 +262,9 @@ def param_shapes(cfg):
         gauss('decoder_z1', Z3 + Y, cfg.h_de_z1, Z1)
     if cfg.type_rec == 'diag_gaussian':
         gauss('decoder_x', Z1 + S, cfg.h_de_x, X, second='sg')
-    elif cfg.type_rec == 'nb':
+    elif cfg.type_rec in ('nb', 'zinb'):
         n = trunk('decoder_x.nnet', Z1 + S, cfg.h_de_x)
-        for q in NB_HEADS:
+        for q in NB_HEADS + ((ZINB_LOGIT_HEAD,) if cfg.type_rec == 'zinb' else ()):
             lin(q, n, X)
     else:
         n = trunk('decoder_x.nnet', Z1 + S, cfg.h_de_x)
@@ -273,11 +274,13 @@ def param_shapes(cfg):
 
 REC_HEAD = {'binary': 'decoder_x.decoder_p.linear_p', 'poisson': 'decoder_x.decoder_r.linear_r'}
 # (head's activation, shift of its first -- or only -- head: the ``shift`` argument of ``dv_rec_nll_rows``)
-REC_ACT = {'binary': ('sigmoid', 0.0), 'poisson': ('softplus', 1e-6), 'nb': ('softplus', 1e-6)}
+REC_ACT = {'binary': ('sigmoid', 0.0), 'poisson': ('softplus', 1e-6), 'nb': ('softplus', 1e-6), 'zinb': ('softplus', 1e-6)}
 # the negative-binomial decoder's two heads over one trunk, mean then inverse dispersion (``blocks.NegativeBinomialDecoder``);
 # theta's shift is the sigma head's (``DV_NB_THETA_SHIFT``)
 NB_HEADS = ('decoder_x.decoder_m.linear_m', 'decoder_x.decoder_t.linear_t')
 NB_THETA_SHIFT = 1e-3
+# the zero-inflated decoder's third head behind those two: the dropout logit, identity (``blocks.ZeroInflatedNegativeBinomialDecoder``)
+ZINB_LOGIT_HEAD = 'decoder_x.decoder_d.linear_d'
 Y_LOGVAR_CONT = math.log(0.05 ** 2)      # fixed variance of the regression head (src/DrVAE.py:168)
 
 
@@ -400,11 +403,13 @@ class FusedStep(StepSchedule):
                 q = 'decoder_x.nnet.model.linear%d' % i
                 layers.append(_Lin(a, q + '.weight', q + '.bias', q + '.g' if wn else None, act=cfg.nonlin))
             act, shift = REC_ACT[cfg.type_rec]
-            if cfg.type_rec == 'nb':      # negative binomial: TWO heads, [mu | theta], both softplus + their own shift
+            if cfg.type_rec in ('nb', 'zinb'):      # negative binomial: TWO heads, [mu | theta], both softplus + their own shift
                 q, s = NB_HEADS
-                layers.append(_Lin(a, q + '.weight', q + '.bias', q + '.g' if wn else None,
-                                   second=(s + '.weight', s + '.bias', s + '.g' if wn else None),
-                                   act=act, shift0=shift, act1='softplus', shift1=NB_THETA_SHIFT))
+                names = lambda h: (h + '.weight', h + '.bias', h + '.g' if wn else None)
+                # (zero-inflated: the dropout logit behind them, back to back in the arena -- ``_Lin(third=...)``)
+                tri = dict(third=names(ZINB_LOGIT_HEAD)) if cfg.type_rec == 'zinb' else {}
+                layers.append(_Lin(a, *names(q), second=names(s), act=act, shift0=shift, act1='softplus',
+                                   shift1=NB_THETA_SHIFT, **tri))
             else:
                 q = REC_HEAD[cfg.type_rec]
                 layers.append(_Lin(a, q + '.weight', q + '.bias', q + '.g' if wn else None, act=act, shift0=shift))
@@ -921,7 +926,7 @@ class FusedStep(StepSchedule):
         if self._tail.late_fork:      # (chip-filling step: the side chain starts HERE, next to the row pass below)
             self.branch.fork()
         lh = p.c_decx.layers[-1]
-        if r.nll == 'rec':     # Bernoulli / Poisson / negative-binomial rows (+ the gradient w.r.t. the head's pre-activation in a train step)
+        if r.nll == 'rec':     # Bernoulli / Poisson / (zero-inflated) negative-binomial rows (+ the gradient w.r.t. the head's pre-activation in a train step)
             K.rec_nll_rows(p.NLL, p.XT if cfg.split_x else p.XIN, PX, kind=cfg.type_rec, shift=REC_ACT[cfg.type_rec][1],
                            xidx=p.tgt, coef=p.c_nll if train else None, dpre=p.DPX if train else None, **self._lib_kw())
         elif r.nll in ('raw_cs', 'raw_cs_eval'):

@@ -131,7 +131,7 @@ class FitMixin:
             x2idx = torch.nonzero(has_x2.reshape(-1)).reshape(-1)
             if len(x2idx) > 0:
                 x2p = x2[x2idx]
-                rp = self.eval_x_reconstruction(x2p, *[t_[x2idx] for t_ in res['px2'][:2]])
+                rp = self.eval_x_reconstruction(x2p, *[t_[x2idx] for t_ in res['px2'][:3]])
                 for k, v in rp.items():
                     perf['x2_' + k] = v
                 parts.append('X2: ' + _REC.format(perf['x2_rmse'], perf['x2_r2'], perf['x2_pearr']))
@@ -163,7 +163,7 @@ class FitMixin:
         if len(x2idx) > 0:
             x2p = x2[x2idx]
             for tag, key in (('x2_wI_', 'px2'), ('x2_rec_', 'px2_rec')):
-                rp = self.eval_x_reconstruction(x2p, *[t_[x2idx] for t_ in res2[key][:2]])
+                rp = self.eval_x_reconstruction(x2p, *[t_[x2idx] for t_ in res2[key][:3]])
                 for k, v in rp.items():
                     perf[tag + k] = v
             q1, q2 = res2['z1'][x2idx].double(), res2['z2'][x2idx].double()
@@ -192,7 +192,10 @@ class FitMixin:
         'nb'``, with ``x_transform`` / ``library_size``: ``dv_recon_rows``' count kinds -- row statistics at the scaled mean and the
         count log-likelihood in one pass; the reported ``ll`` is the negative binomial's for ``'nb'`` and nan for the other two,
         as on the step-by-step path).  ``return_full_data`` (arrays for the caller), host datasets and the other MMD kernels take
-        the step-by-step path (``'nb'``: ``x1_rec`` / ``x2_pert`` are the means, ``px1`` = (mu, theta))."""
+        the step-by-step path (``'nb'``: ``x1_rec`` / ``x2_pert`` are the means, ``px1`` = (mu, theta)).  So does
+        ``type_rec='zinb'`` on every dataset (``_EvalGraph.get`` declines it up front: ``dv_recon_rows`` has no zero-inflated
+        kind): ``x1_rec`` / ``x2_pert`` are the negative-binomial means, ``px1`` = (mu, theta, dropout logit), and the reported
+        ``ll`` is the zero-inflated log-likelihood."""
         g = lambda k: getattr(ds, k, None)
         ev = None if return_full_data else _EvalGraph.get(self, ds)
         if ev is not None:
@@ -459,6 +462,8 @@ class _EvalGraph:
             return None
         if next(model.parameters()).device != x1.device:
             return None
+        if model.type_rec == 'zinb':
+            return None          # (no zero-inflated kind of ``dv_recon_rows``: step by step, decided up front -- no warning)
         # (the decision is a function of the model's configuration and the dataset's tensors alone: every rank of a
         # data-parallel job decides alike)
         use_s = bool(getattr(model, 'use_s', False))

@@ -587,16 +587,18 @@ def rec_nll_rows(out, x, v, *, kind, shift=0.0, xidx=None, coef=None, dpre=None,
     """log-likelihood rows of the Bernoulli ('binary') / Poisson decoders from the head's post-activation output
     ``v``; with ``coef`` also the gradient w.r.t. the head's pre-activation (``dv_rec_nll_rows``).  ``kind='nb'`` (negative
     binomial): ``v`` = [mu | theta] and ``dpre`` = [d/da_m | d/da_t], 2X columns each; ``shift`` is the mean's, theta's is
-    ``DV_NB_THETA_SHIFT``.  ``library`` ('poisson' / 'nb' only): the library-scaled kind -- the mean of row r is
-    s * v with s = max(sum_g x[xidx[r], g], 1) / X, the size factor the kernel forms from the target row it reads"""
+    ``DV_NB_THETA_SHIFT``.  ``kind='zinb'`` (zero-inflated negative binomial): ``v`` = [mu | theta | dropout logit] (the
+    logit RAW) and ``dpre`` = [d/da_m | d/da_t | d/da_d], 3X columns each.  ``library`` ('poisson' / 'nb' / 'zinb' only): the
+    library-scaled kind -- the mean of row r is s * v with s = max(sum_g x[xidx[r], g], 1) / X, the size factor the kernel
+    forms from the target row it reads"""
     M, X = v.shape
     if library:
-        if kind not in ('poisson', 'nb'):
-            raise ValueError("rec_nll_rows: library= is for kind 'poisson' / 'nb', not %r" % (kind,))
+        if kind not in ('poisson', 'nb', 'zinb'):
+            raise ValueError("rec_nll_rows: library= is for kind 'poisson' / 'nb' / 'zinb', not %r" % (kind,))
         kind = kind + '_lib'
-    if kind in ('nb', 'nb_lib'):
-        X = x.shape[1]
-        assert v.shape[1] == 2 * X and (dpre is None or tuple(dpre.shape) == (M, 2 * X))
+    if kind in ('nb', 'nb_lib', 'zinb', 'zinb_lib'):
+        X, w = x.shape[1], 2 if kind in ('nb', 'nb_lib') else 3
+        assert v.shape[1] == w * X and (dpre is None or tuple(dpre.shape) == (M, w * X))
     _lib.check(_lib.load().dv_rec_nll_rows(_lib.REC_KIND[kind], shift, _f32(coef), _f32(x), _ld(x), _i32(xidx), _f32(v),
                                            _ld(v), M, X, _f32(out), _f32(dpre), _ld(dpre), _stream()), 'dv_rec_nll_rows')
 

@@ -169,7 +169,7 @@ def heads_route(eng, plan, kind):
     raw_last = bool(raw_ok and not (train and epi) and kind != LOSS)
     if gauss and train and epi:      # train step: the heads' launch emits the rows' partials and d/d(mu, pre-softplus)
         nll = 'heads'
-    elif not gauss:                  # Bernoulli / Poisson / negative-binomial rows, at every size (``dv_rec_nll_rows``)
+    elif not gauss:                  # Bernoulli / Poisson / (zero-inflated) negative-binomial rows, at every size (``dv_rec_nll_rows``)
         nll = 'rec'
     elif raw_last and nll_cs:        # the row pass finishes the heads (+ in a train step: their bias gradient's column sums)
         nll = 'raw_cs' if train else 'raw_cs_eval'

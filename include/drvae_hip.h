@@ -547,8 +547,20 @@ int dv_gauss_nll_rows_bwd(const float* coef, const float* x, int64_t ldx, const 
  * order: per-thread partials in index order, the wave sum, the four waves as (p0 + p1) + (p2 + p3)); the term loop's second
  * read of the row comes from cache.  For integer counts with a row total below 2^24 every partial sum is exact in fp32 in
  * any order, so s is ONE correctly rounded quotient on every path; a row whose total is X (s = 1) gives the unscaled
- * kind's output bit for bit. */
-enum { DV_REC_BERNOULLI = 0, DV_REC_POISSON = 1, DV_REC_NEGBIN = 2, DV_REC_POISSON_LIB = 3, DV_REC_NEGBIN_LIB = 4 };
+ * kind's output bit for bit.
+ * EXTENSION (`type_rec='zinb'`, no counterpart in the reference): ZINB / ZINB_LIB, the zero-inflated negative binomial -- a
+ * third head, the dropout logit a_d (identity activation), pi = sigmoid(a_d), over the NEGBIN (NEGBIN_LIB) term logNB:
+ * v row r = [mu | theta | a_d], 3X columns (ldv >= 3X), the first two blocks as NEGBIN reads them, the third the RAW logit;
+ * dpre row r = coef[r] * [d/da_m | d/da_t | d/da_d], 3X columns (ldd >= 3X).  With L0 = logNB(0) = -theta log1p(m/theta) and
+ * rho = sigmoid(L0 - a_d), the NB component's responsibility for a zero:
+ *   x > 0: log p = -softplus(a_d) + logNB(x);        d/da_d = -pi;  d/da_m, d/da_t as NEGBIN
+ *   x = 0: log p = log(pi + (1 - pi) e^{L0});         d/da_d = (1 - rho) (1 - pi) (1 - e^{L0});  d/da_m, d/da_t = rho * NEGBIN's
+ * The x = 0 term never adds a vanishing addend to 1: with z = (1 - pi)(-expm1(L0)) it is log1p(-z) for z <= 1/2, else
+ * max(u, w) + log1p(exp(-|a_d - L0|)) with u = -softplus(-a_d), w = -softplus(a_d) + L0; its logit gradient is a product of
+ * non-negative factors, never a difference of two sigmoids.  theta and the logit are never scaled (ZINB_LIB: m = s mu, the
+ * slope of d/da_m the unscaled head's).  Same signature; refusals and the 16-byte / one-gene-per-thread paths as NEGBIN. */
+enum { DV_REC_BERNOULLI = 0, DV_REC_POISSON = 1, DV_REC_NEGBIN = 2, DV_REC_POISSON_LIB = 3, DV_REC_NEGBIN_LIB = 4,
+       DV_REC_ZINB = 5, DV_REC_ZINB_LIB = 6 };
 #define DV_NB_THETA_SHIFT 1e-3f     /* the shift of the NEGBIN theta head (that of the Gaussian decoder's sigma head) */
 int dv_rec_nll_rows(int32_t kind, float shift, const float* coef, const float* x, int64_t ldx, const int32_t* xidx,
                     const float* v, int64_t ldv, int32_t M, int32_t X, float* out, float* dpre, int64_t ldd,

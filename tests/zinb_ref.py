@@ -1,0 +1,292 @@
+"""Float64 reference of the zero-inflated negative-binomial reconstruction rows (``dv_rec_nll_rows``, kinds ``DV_REC_ZINB`` /
+``DV_REC_ZINB_LIB``; ``type_rec='zinb'``), the bound the kernel is held to, fp32 emulations -- a careful one and five faulty
+ones the bound catches --, a model-level float64 reference, a CPU stand-in of the launcher and a zero-inflated batch
+generator.  Test-only; builds on ``tests/nb_ref.py`` and ``tests/counts_ref.py``.
+
+With a = the dropout logit (third head, identity), pi = sigmoid(a), q = 1 - pi = sigmoid(-a), logNB the negative-binomial term
+at (m, theta) (m = mu, or s mu under ``library_size``), L0 = logNB(0) = -theta log1p(m / theta), rho = sigmoid(L0 - a):
+
+    x > 0:  log p = -softplus(a) + logNB(x)         d/da = -pi                       d/da_m, d/da_t = NB's
+    x = 0:  log p = log(pi + q e^{L0})              d/da = (1 - rho) q (1 - e^{L0})  d/da_m, d/da_t = rho * NB's
+
+The float64 reference forms the x = 0 term without cancellation, like the kernel: z = q (-expm1(L0)); log1p(-z) for z <= 1/2,
+else max(u, w) + log1p(exp(-|a - L0|)) with u = -softplus(-a), w = -softplus(a) + L0.
+
+The bound, componentwise in ``nb_ref``'s style (U = 2^-24; roundings counted by its rule -- a transcendental 3, a sum, product
+or quotient 1):
+
+* x > 0, C_SP = 8 on softplus(a) plus NB's bound: softplus = max(a, 0) + log1p(exp(-|a|)): exp 3, log1p 3, the sum 1, and the
+  subtraction from logNB 1 (its share of |logNB| is the one rounding ``nb_ref`` counts 31 of and grants 32).
+* x = 0, C0 = 25 on |log p| plus rho times NB's bound of the x = 0 term (L0 carries the NB term's error, the mixture passes it
+  on with slope d log p / d L0 = rho <= 1).  The mixture step at exact L0:
+  z <= 1/2: q = e / (1 + e) or 1 / (1 + e): 5; -expm1(L0): 3; their product: 1 -- 9 relative roundings of z, which log1p(-z)
+  passes on with the factor z / ((1 - z) |log1p(-z)|) <= 1 / (1 - z) <= 2: 18; log1p itself 3: 21.
+  z > 1/2 (then a < 0, L0 < -log 2, |log p| >= log 2): u carries 7 roundings of softplus(-a), w 7 of softplus(a) <= log 2 <= |w| and
+  the sum with L0: 8; |max(u, w)| <= |log p| + log 2 <= 2 |log p|: 16.  The second addend: a - L0 (one rounding, U |d|), exp (3):
+  absolute U (|d| + 3) e^{-|d|} <= 3.4 U, through log1p' <= 1, plus log1p's own 3 U log 2: <= 5.5 U <= 8 U |log p|.  The sum: 1.  25.
+* d/da at x > 0, C_GD = 8: exp 3, 1 + e, the reciprocal, the product, times coef: 7.
+* d/da at x = 0, C_GD0 = 18 on |g|: 1 - rho (exp 3, sum, reciprocal, product: 6), q (6), -expm1 (3), two products, times coef: 18.
+  Two terms no count of roundings covers, both inherent to an exponential of a computed difference d = L0 - a:
+    - the ONE rounding of d moves exp(-|d|) by U |d| relative: (1 - rho) by rho |d| U, rho by (1 - rho) |d| U;
+    - L0's own error e0 (NB's bound of the x = 0 term) moves g = (1 - rho) q (1 - e^{L0}) by
+      rho (|g| + |c| (1 - rho) P) e0, P = e^{log p} (d(1 - rho)/dL0 = -rho (1 - rho); (1 - rho) q e^{L0} = (1 - rho) rho P),
+      and rho by rho (1 - rho) e0.
+* d/da_m, d/da_t at x = 0: rho times NB's bounds, plus C_RHO = 8 on |g| (rho: 6, the product: 1), plus the two terms above:
+  (1 - rho) (U |d| + e0) |g|.
+* every factor that is an exponential can underflow: fp32 flushes below 2^-126 where float64 still holds 1e-300.  Each
+  gradient carries the floor TINY = 2^-126 times the magnitude of what the underflowing factor multiplies, and TINY itself:
+  the product's own result may be flushed (rho = 1e-30 times a gradient of 1e-16 is 1e-46 in float64 and 0 in fp32).
+
+Under ``library_size`` the NB pieces and bounds are ``counts_ref.reference``'s (m = fl(s v), the slope of d/da_m the unscaled
+head's); theta and the logit are never scaled."""
+import contextlib
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+from tests import counts_ref as CR
+from tests import nb_ref as R
+from tests import ref64
+from tests.ref64 import U, f64, row_sum_bound
+
+MU_SHIFT, THETA_SHIFT = R.MU_SHIFT, R.THETA_SHIFT
+C_SP, C0, C_GD, C_GD0, C_RHO = 8, 25, 8, 18, 8
+TINY = 2.0 ** -126
+LOGITS = (-30.0, -8.0, -1.0, 0.0, 1.0, 8.0, 30.0)
+
+
+# --------------------------------------------------------------------------------------------- float64 terms
+def zero_term(a, L0):
+    """log(sigmoid(a) + sigmoid(-a) e^{L0}) without cancellation (the two-branch form), differentiable"""
+    z = torch.sigmoid(-a) * -torch.expm1(L0)
+    near = torch.log1p(-torch.clamp(z, max=0.5))
+    far = torch.maximum(-F.softplus(-a), -F.softplus(a) + L0) + torch.log1p(torch.exp(-(a - L0).abs()))
+    return torch.where(z <= 0.5, near, far)
+
+
+def logp64(x, m, theta, a):
+    """log p per element at the (scaled) mean ``m``, float64, differentiable"""
+    nb = R.logp64(x, m, theta)
+    return torch.where(x > 0, nb - F.softplus(a), zero_term(a, torch.where(x > 0, torch.zeros_like(nb), nb)))
+
+
+def reference(x, v_mu, v_theta, logit, coef=None, shift=MU_SHIFT, library=False, s=None):
+    """everything the kernel tests compare with, from the exact fp32 values the kernel received (``x``: the target row of every
+    decoder row, gathered): ll, rows, rows_bound and with ``coef`` gm / gt / gd with gm_bound / gt_bound / gd_bound; ``nb``: the
+    negative-binomial reference underneath; ``s`` (library): fp32 size factors per row, default those of the rows of ``x``"""
+    X = x.shape[1]
+    nb = CR.reference('nb', x, v_mu, v_theta, coef=coef, shift=shift, s=s) if library else \
+        R.reference(x, v_mu, v_theta, coef=coef, shift=shift)
+    nb_ll_bound = nb['ll_bound'] if library else ref64.bound(R.C_ROW, nb['comps'])
+    xx, a = f64(x), f64(logit)
+    pos = xx > 0
+    L0 = torch.where(pos, torch.zeros_like(a), nb['ll'])
+    sp = F.softplus(a)
+    zt = zero_term(a, L0)
+    d = L0 - a
+    rho, nrho = torch.sigmoid(d), torch.sigmoid(-d)
+    out = dict(nb=nb, rho=rho, pos=pos)
+    out['ll'] = torch.where(pos, nb['ll'] - sp, zt)
+    out['ll_bound'] = torch.where(pos, nb_ll_bound + C_SP * U * sp, C0 * U * zt.abs() + rho * nb_ll_bound)
+    comps = torch.where(pos, nb['comps'] + sp, zt.abs())
+    out['comps'] = comps
+    out['rows'] = out['ll'].sum(1)
+    out['rows_bound'] = out['ll_bound'].sum(1) + row_sum_bound(comps, X)
+    if coef is not None:
+        c = f64(coef)[:, None].abs()
+        pi, q = torch.sigmoid(a), torch.sigmoid(-a)
+        em = -torch.expm1(L0)
+        gd0 = f64(coef)[:, None] * nrho * q * em
+        out['gd'] = torch.where(pos, -f64(coef)[:, None] * pi, gd0)
+        e0 = nb_ll_bound
+        out['gd_bound'] = torch.where(pos, C_GD * U * c * pi,
+                                      C_GD0 * U * gd0.abs() + rho * d.abs() * U * gd0.abs()
+                                      + rho * (gd0.abs() + c * nrho * torch.exp(zt)) * e0) + TINY * (c + 1)
+        for k in ('gm', 'gt'):
+            g0 = rho * nb[k]
+            out[k] = torch.where(pos, nb[k], g0)
+            out[k + '_bound'] = torch.where(pos, nb[k + '_bound'],
+                                            rho * nb[k + '_bound'] + C_RHO * U * g0.abs() + nrho * (U * d.abs() + e0) * g0.abs()
+                                            + TINY * (nb[k].abs() + 1))
+    return out
+
+
+def grads_autograd(x, a_m, a_t, a_d, s=None, shift=MU_SHIFT):
+    """d sum log p / d(a_m, a_t, a_d) by float64 autograd through the heads (the cross-check of the closed forms)"""
+    am, at, ad = (t.clone().requires_grad_(True) for t in (a_m, a_t, a_d))
+    m = F.softplus(am) + shift
+    if s is not None:
+        m = s[:, None] * m
+    logp64(x, m, F.softplus(at) + ref64.f32(THETA_SHIFT), ad).sum().backward()
+    return am.grad, at.grad, ad.grad
+
+
+# ------------------------------------------------------------------------------------------------ the grid
+def edge_grid(X=256):
+    """``nb_ref.edge_grid`` crossed with the logits, each block twice: as it is and with every count set to 0 -- more than half
+    of the elements are zeros.  It holds mu = 1e-6 with theta = 1e6 (L0 ~ -1e-6: the addend that vanishes next to 1) and
+    mu = 1e4 with logit -30 (both addends tiny).  Returns fp32 (x, mu, theta, logit) and the row coefficients"""
+    x, mu, th, coef = R.edge_grid(X)
+    xs, ms, ts, ls, cs = [], [], [], [], []
+    for l in LOGITS:
+        for zero in (False, True):
+            xs.append(torch.zeros_like(x) if zero else x)
+            ms.append(mu), ts.append(th), cs.append(coef)
+            ls.append(torch.full_like(x, l))
+    return torch.cat(xs), torch.cat(ms), torch.cat(ts), torch.cat(ls), torch.cat(cs)
+
+
+# ------------------------------------------------------------------------------------------ fp32 emulations
+def emulate_fp32(x, mu, theta, logit, shift=MU_SHIFT, s=None, zero='careful', dlogit='careful', rho_in_gt=True, slope='head'):
+    """the row formula in numpy float32, operation by operation: (log p, d/da_m, d/da_t, d/da_d) per element; ``s``: fp32 size
+    factors per row (the library kind).  'careful' is the kernel's construction on top of ``nb_ref`` / ``counts_ref``'s careful
+    negative-binomial emulation.  FAULTY on purpose:
+      zero='naive'          log(pi + (1 - pi) exp(L0))
+      zero='softplus_pair'  softplus(L0 - a) - softplus(-a)
+      dlogit='sigdiff'      the x = 0 logit gradient as sigmoid(a - L0) - sigmoid(a)
+      rho_in_gt=False       rho left out of d/da_t at zeros
+      slope='scaled'        (library) the slope of d/da_m taken from the scaled mean"""
+    f = np.float32
+    x, a = R._f(x), R._f(logit)
+    with np.errstate(all='ignore'):
+        if s is None:
+            L, gm, gt = R.emulate_fp32(x, mu, theta, shift=shift)
+        else:
+            L, gm, gt = CR.emulate_fp32(x, mu, theta, s, shift=shift, slope=slope)
+        sp_ = lambda v: (np.maximum(v, f(0)) + np.log1p(np.exp(-np.abs(v)))).astype(f)
+        e = np.exp(-np.abs(a))
+        r = f(1) / (f(1) + e)
+        pi, q = np.where(a >= 0, r, e * r).astype(f), np.where(a >= 0, e * r, r).astype(f)
+        sp = sp_(a)
+        em = -np.expm1(L)
+        z = q * em
+        d = L - a
+        ed = np.exp(-np.abs(d))
+        rd = f(1) / (f(1) + ed)
+        rho, nrho = np.where(d >= 0, rd, ed * rd).astype(f), np.where(d >= 0, ed * rd, rd).astype(f)
+        u, w = -sp_(-a), L - sp
+        zt = np.where(z <= f(0.5), np.log1p(-np.minimum(z, f(0.5))), np.maximum(u, w) + np.log1p(ed)).astype(f)
+        if zero == 'naive':
+            p1 = f(1) / (f(1) + np.exp(-a))
+            zt = np.log(p1 + (f(1) - p1) * np.exp(L)).astype(f)
+        elif zero == 'softplus_pair':
+            zt = (sp_(L - a) - sp_(-a)).astype(f)
+        gd0 = nrho * z
+        if dlogit == 'sigdiff':
+            gd0 = (f(1) / (f(1) + np.exp(-(a - L))) - f(1) / (f(1) + np.exp(-a))).astype(f)
+        pos = x > 0
+        ll = np.where(pos, L - sp, zt).astype(f)
+        gmz = np.where(pos, gm, gm * rho).astype(f)
+        gtz = np.where(pos, gt, gt * rho if rho_in_gt else gt).astype(f)
+        gd = np.where(pos, -pi, gd0).astype(f)
+    return ll, gmz, gtz, gd
+
+
+# ------------------------------------------------------------------------------------ the launcher's stand-in
+def rec_nll_rows(out, x, v, *, kind, shift=0.0, xidx=None, coef=None, dpre=None, library=False):
+    """CPU stand-in of ``kernels.rec_nll_rows``: ``kind='zinb'`` (``v`` = [mu | theta | logit], ``dpre`` 3X wide; with
+    ``library=True`` the scaled kind) from the float64 reference, rounded once; every other kind is ``tests/kernel_ref``'s.
+    Installed OVER ``kernel_ref.install`` (``install``)"""
+    from tests import kernel_ref
+    if kind != 'zinb':
+        return kernel_ref.rec_nll_rows(out, x, v, kind=kind, shift=shift, xidx=xidx, coef=coef, dpre=dpre, library=library)
+    CALLS['zinb_lib' if library else 'zinb'] += 1
+    xs = x[xidx.long()] if xidx is not None else x
+    X = x.shape[1]
+    assert v.shape[1] == 3 * X and (dpre is None or dpre.shape[1] == 3 * X)
+    ref = reference(xs, v[:, :X], v[:, X:2 * X], v[:, 2 * X:], coef=coef, shift=shift, library=library)
+    out.copy_(ref['rows'].to(out.dtype))
+    if coef is not None:
+        for i, k in enumerate(('gm', 'gt', 'gd')):
+            dpre[:, i * X:(i + 1) * X] = ref[k].to(dpre.dtype)
+
+
+CALLS = {'zinb': 0, 'zinb_lib': 0}
+
+
+def install(monkeypatch):
+    """``kernel_ref.install``, then this module's ``rec_nll_rows`` over it"""
+    from tests import kernel_ref
+    import drvae_amd.kernels as K
+    kernel_ref.install(monkeypatch)
+    monkeypatch.setattr(K, 'rec_nll_rows', rec_nll_rows)
+    for k in CALLS:
+        CALLS[k] = 0
+
+
+# ------------------------------------------------------------------------------- model-level float64 reference
+LOGIT_HEAD = 'decoder_x.decoder_d.linear_d'
+
+
+class ModelRef(CR.RidersRef):
+    """``counts_ref.RidersRef`` (the negative-binomial model with the count switches and the step's riders, all off by default)
+    with the third head: its parameters are appended to the oracle's (behind the decoder's two heads, where ``param_shapes``
+    puts them), the decoder returns (mu, theta, logit) and the row log-likelihood is the zero-inflated one at the size-scaled
+    mean -- two more run-time substitutions inside the contexts of ``nb_ref`` / ``counts_ref`` (nothing under oracle/ changes)"""
+
+    def __init__(self, spec, seed=9, **kw):
+        from oracle import models_ref as M
+        super().__init__(spec, seed, **kw)
+        m = 'decoder_x.encoder_mu.linear_mu'
+        rs = np.random.RandomState(seed + 77)
+        w = self.init32[m + '.weight']
+        self.init32[LOGIT_HEAD + '.weight'] = (rs.standard_normal(w.shape) * w.std()).astype(np.float32)
+        self.init32[LOGIT_HEAD + '.bias'] = (0.1 * rs.standard_normal(w.shape[0])).astype(np.float32)
+        if spec.weight_norm:
+            self.init32[LOGIT_HEAD + '.g'] = self.init32[m + '.g'].copy()
+        params = type(self.init32)((k, torch.tensor(v.astype(np.float64), requires_grad=True)) for k, v in self.init32.items())
+        self.tr = M.RefTrainer(spec, params)
+        self.avg = {k: v.detach().clone() for k, v in self.tr.params.items()}
+
+    @contextlib.contextmanager
+    def context(self):
+        from oracle import blocks_ref as B
+        with super().context():
+            heads2, rows2 = B.diag_gaussian_sigma, B.logp_sigma_rows
+            lib = self.sw['library_size']
+
+            def heads3(inputs, p, prefix, n_hidden, nonlin, constrain_means=False):
+                mu, theta = heads2(inputs, p, prefix, n_hidden, nonlin)
+                h = B.mlp(inputs, p, prefix + '.nnet', n_hidden, nonlin)
+                return mu, theta, B.linear(h, p, LOGIT_HEAD)
+
+            def rows3(x, mu, theta, logit):
+                m = mu * CR.size_factor64(x)[:, None] if lib else mu
+                return logp64(x, m, theta, logit).sum(1)
+            B.diag_gaussian_sigma, B.logp_sigma_rows = heads3, rows3
+            try:
+                yield
+            finally:
+                B.diag_gaussian_sigma, B.logp_sigma_rows = heads2, rows2
+
+    def plain_loss(self, batch, noise, training=True):
+        """loss scalars without the riders' recombination (all riders off: the same numbers)"""
+        return self.loss(batch, noise, training)
+
+
+# --------------------------------------------------------------------------------------- zero-inflated data
+def zi_counts(n, X=13, seed=0, theta=2.0, depth=6.0):
+    """(x, y): zero-inflated Gamma-Poisson counts -- NB(theta) around gene means depth * (1 .. 4) (a class shifts every third
+    gene), each entry then zeroed with its GENE's structural-zero probability, spread evenly over 0.1 .. 0.6"""
+    rs = np.random.RandomState(seed)
+    y = rs.randint(0, 2, n)
+    mean = depth * (1.0 + (np.arange(X) % 4))[None, :] * np.where((np.arange(X) % 3 == 0)[None, :], 1.0 + 0.8 * y[:, None], 1.0)
+    x = rs.poisson(rs.gamma(theta, mean / theta))
+    pi = np.linspace(0.1, 0.6, X)[None, :]
+    x = np.where(rs.rand(n, X) < pi, 0, x)
+    return x.astype(np.float32), y.astype(np.int64)
+
+
+def zi_dataset(kind, n, seed, dev='cpu', **kw):
+    """a dataset of ``zi_counts`` for model ``kind``: every third row has a second profile (1.3 times the means), three in
+    four rows a label"""
+    from drvae_amd import data as D
+    x1, y = zi_counts(n, seed=seed, **kw)
+    x2, _ = zi_counts(n, seed=seed + 500, depth=1.3 * kw.get('depth', 6.0), **{k: v for k, v in kw.items() if k != 'depth'})
+    hx = (np.arange(n) % 3 == 0).astype(np.int64)
+    hy = (np.arange(n) % 4 != 1).astype(np.int64)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    if kind == 'vfae':
+        return D.VFAEDataset(t(x1), t(np.zeros(n, np.int64)), t(y), t(hy))
+    return D.DrVAEDataset(t(x1), t(x2 * hx[:, None].astype(np.float32)), t(np.zeros(n, np.int64)), t(y), t(hx), t(hy))
