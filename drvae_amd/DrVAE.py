@@ -31,9 +31,10 @@ class DrVAE(ELBOModel):
     parameters inside the optimiser sweep: ``averaged_parameters()`` evaluates with it, ``averaged_state_dict()`` returns it,
     ``fit`` evaluates and snapshots it unless ``model.ema_eval = False``.  ``optim_alg='adamw'`` is Adam with decoupled weight
     decay (``torch.optim.AdamW``).  Both are labelled extensions.
-    ``x_transform`` (default None | 'log1p') and ``library_size`` (default False) are the raw-count inputs of the count decoders
+    ``x_transform`` (default None | 'log1p' | 'log1p_norm') and ``library_size`` (default False) are the raw-count inputs of the count decoders
     (``type_rec='poisson'`` / ``'nb'`` / ``'zinb'``; anything else, or another ``x_transform``, raises ``ValueError``; x >= 0, checked once
-    per dataset by ``fit`` / ``DeviceBatcher.bind``): the encoder reads log1p(x) while the likelihood keeps the raw counts
+    per dataset by ``fit`` / ``DeviceBatcher.bind``): the encoder reads log1p(x) (``'log1p_norm'``: the depth-normalised
+    log1p(x / s), s the row's own size factor below) while the likelihood keeps the raw counts
     without training noise, and every decoder mean of a row is multiplied by the row's observed size factor
     max(sum_g x_g, 1) / dim_x.  Attributes until the engine is built, like the schedules.  Labelled extensions."""
     kind = 'drvae'

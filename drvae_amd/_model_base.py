@@ -199,14 +199,34 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         return torch.clamp(x.sum(dim=1), min=1.0) / float(self.dim_x)
 
     def _enc_x(self, x):
-        """the encoder's view of the rows ``x``: T(x), T = log1p with ``x_transform='log1p'``"""
-        return torch.log1p(x) if getattr(self, 'x_transform', None) == 'log1p' else x
+        """the encoder's view of the rows ``x``: T(x), T = log1p with ``x_transform='log1p'``, log1p(x / s) with
+        ``'log1p_norm'`` -- s the rows' own observed size factors (``size_factor``), as the feed launch forms them"""
+        tr = getattr(self, 'x_transform', None)
+        if tr == 'log1p_norm':
+            return torch.log1p(x / self.size_factor(x)[:, None])
+        return torch.log1p(x) if tr == 'log1p' else x
 
-    def _scaled(self, px, x):
-        """decoder output ``px`` with its mean multiplied by the size factor of the rows ``x`` (``library_size``; else as it is)"""
+    def _scaled(self, px, x, size_factor=None):
+        """decoder output ``px`` with its mean multiplied by the size factor of the rows ``x`` (``library_size``; else as it is),
+        or by ``size_factor`` where one is given (``_chosen_size``); theta and the dropout logit are never scaled"""
         if not getattr(self, 'library_size', False):
             return px
-        return (px[0] * self.size_factor(x)[:, None],) + tuple(px[1:])
+        sz = self.size_factor(x) if size_factor is None else size_factor
+        return (px[0] * sz[:, None],) + tuple(px[1:])
+
+    def _chosen_size(self, size_factor, x):
+        """the ``size_factor=`` keyword of inference as a (rows,) tensor next to ``x`` (None stays None: the observed factors);
+        ValueError on a model without ``library_size=True``, whose means carry no size factor at all"""
+        if size_factor is None:
+            return None
+        if not getattr(self, 'library_size', False):
+            raise ValueError('size_factor= scales the decoder means of a library_size=True model; this model has library_size=False')
+        sz = torch.as_tensor(size_factor, dtype=torch.float32, device=x.device)
+        if sz.dim() == 0:
+            return sz.expand(x.shape[0])
+        if tuple(sz.shape) != (x.shape[0],):
+            raise ValueError('size_factor must be a number or a (rows,) tensor, not shape %r for %d rows' % (tuple(sz.shape), x.shape[0]))
+        return sz
 
     def _step_config(self):
         top = 'dim_z3' if self.kind == 'drvae' else 'dim_z2'
@@ -233,19 +253,23 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
 
     # ---------------------------------------------------------------- inference
     @torch.no_grad()
-    def forward(self, x1, s=[]):
+    def forward(self, x1, s=[], size_factor=None):
         """Inference with the posterior MEANS (no sampling): src/DrVAE.py:253-311,
         src/PVAE.py:203-246, src/VFAE.py:178-215.
 
         Raw-count switches (EXTENSIONS): the encoder reads T(x1) (``x_transform``); with ``library_size`` the means
         ``px1[0]`` / ``x1_rec`` and ``px2[0]`` / ``x2_pert`` are multiplied by the size factor of ``x1`` -- the depth of the
         perturbed profile is unknown at prediction time, so the prediction is made at the depth of the profile it starts from.
+        ``size_factor`` (a number or a (rows,) tensor; ``library_size`` models only, ValueError otherwise) scales those means by
+        the given value INSTEAD: the decoder's output at a chosen depth -- ``size_factor=1.0`` is the denoised expression at a
+        common depth of ``dim_x`` counts per cell.  None: the observed factors.  theta and the dropout logit are never scaled.
 
         ``type_rec='zinb'``: ``px1`` = (mu, theta, dropout logit); ``x1_rec`` / ``x2_pert`` are the negative-binomial MEAN (scaled
         under ``library_size``) -- the denoised expression, NOT the mixture's mean (1 - pi) mu."""
         self.eval()
         x1 = x1.to(next(self.parameters()).device, torch.float32)
         cond = self._s_inputs(s, x1)
+        size = self._chosen_size(size_factor, x1)
         qz1 = self.encoder_z1([self._enc_x(x1)] + cond)
         z1 = qz1[0]
         res = OrderedDict(z1=z1, qz1=qz1)
@@ -260,10 +284,10 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
                 clf_in = [z1]
             qy = self.encoder_y(clf_in)
             res.update(**self._pred_proba(qy))
-        px1 = self._scaled(self.decoder_x([z1] + cond), x1)
+        px1 = self._scaled(self.decoder_x([z1] + cond), x1, size)
         res.update(px1=px1, x1_rec=px1[0])
         if self.kind in ('drvae', 'pvae'):
-            px2 = self._scaled(self.decoder_x([z2] + cond), x1)
+            px2 = self._scaled(self.decoder_x([z2] + cond), x1, size)
             res.update(px2=px2, x2_pert=px2[0])
         return res
 
@@ -274,25 +298,26 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         return [blk.one_hot(torch.as_tensor(s).to(like.device), self.dim_s)]
 
     @torch.no_grad()
-    def forward_w_pert_identity(self, x1, x2, s=[]):
+    def forward_w_pert_identity(self, x1, x2, s=[], size_factor=None):
         """Inference assuming the perturbation function is the identity
         (src/DrVAE.py:185-251, src/PVAE.py:155-201).  ``library_size``: ``px2`` / ``x2_pert`` (predicted from x1) carry x1's
-        size factor, ``px2_rec`` / ``x2_rec`` (reconstructed from x2) x2's own."""
+        size factor, ``px2_rec`` / ``x2_rec`` (reconstructed from x2) x2's own; ``size_factor`` (see ``forward``) replaces both."""
         if self.kind == 'vfae':
             raise AttributeError('VFAE has no perturbation path')
         self.eval()
         dev = next(self.parameters()).device
         x1, x2 = x1.to(dev, torch.float32), x2.to(dev, torch.float32)
         cond = self._s_inputs(s, x1)
+        size = self._chosen_size(size_factor, x1)
         qz1 = self.encoder_z1([self._enc_x(x1)] + cond)
         z1 = qz1[0]
         res = OrderedDict(z1=z1, qz1=qz1)
         if self.kind == 'drvae':
             qy = self.encoder_y([z1, z1 - z1] if self.clf_z1z2 else [z1])
             res.update(**self._pred_proba(qy))
-        px2 = self._scaled(self.decoder_x([z1] + cond), x1)
+        px2 = self._scaled(self.decoder_x([z1] + cond), x1, size)
         qz2 = self.encoder_z1([self._enc_x(x2)] + cond)
-        px2_rec = self._scaled(self.decoder_x([qz2[0]] + cond), x2)
+        px2_rec = self._scaled(self.decoder_x([qz2[0]] + cond), x2, size)
         res.update(px2=px2, x2_pert=px2[0], z2=qz2[0], qz2=qz2, px2_rec=px2_rec, x2_rec=px2_rec[0])
         return res
 

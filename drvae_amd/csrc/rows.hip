@@ -2108,9 +2108,29 @@ __global__ __launch_bounds__(1024) void batch_masks_kernel(MaskArgs a) { batch_m
 // SPLIT (dv_batch_feed_desc.xt given: raw-count inputs): the wave that owns row r also writes the RAW row to xt[r,:] -- the
 // reconstruction target, without noise -- and the encoder's row becomes T(x) + sigma*noise, T = log1p with `transform` == 1.
 // A compile-time variant: the default launch keeps its instruction stream (it heads the step's critical path)
+// NORM (`transform` == 3, 'log1p_norm'; a compile-time variant of SPLIT): T(x) = log1p(x / s) with the row's observed size
+// factor s = max(sum_g x_g, 1) / X.  The wave sums its SOURCE row first (never xin: the sum is taken before the noise) --
+// lane partials in index order, then dv_wave_sum_all, one fixed order on every path -- and divides every element by s (a
+// true division: one rounding).  A row of up to 1024 columns already sits in the lane's four 16-byte groups and is summed
+// from registers; a wider row is walked twice, the second walk from cache.  Integer counts with a row total below 2^24
+// sum exactly in fp32 in ANY order: s is then the ONE correctly rounded quotient that row_size_factor forms in the row
+// kernels.  Non-integer input: not guaranteed bit-equal to the decoder's s (the two sums run in different orders)
 __device__ __forceinline__ float feed_T(int transform, float x) { return transform ? log1pf(x) : x; }
+__device__ __forceinline__ float feed_Tn(float x, float s) { return log1pf(x / s); }
+__device__ __forceinline__ float feed_size(float acc, int X) { return fmaxf(dv_wave_sum_all(acc), 1.f) / (float)X; }
 
-template <bool SPLIT>
+// the lane's partial of a row's sum: 16-byte groups q = lane, lane + 64, ... below X4, then scalars from g0 on
+__device__ __forceinline__ float feed_row_partial(const float* __restrict__ src, int X4, int g0, int X, int lane) {
+    float acc = 0.f;
+    for (int q = lane; q < X4; q += 64) {
+        const float4 xv = reinterpret_cast<const float4*>(src)[q];
+        acc += xv.x, acc += xv.y, acc += xv.z, acc += xv.w;
+    }
+    for (int g = g0 + lane; g < X; g += 64) acc += src[g];
+    return acc;
+}
+
+template <bool SPLIT, bool NORM>
 __global__ __launch_bounds__(256) void batch_feed_kernel(
     const float* __restrict__ x1, int64_t ld1, const float* __restrict__ x2, int64_t ld2,
     const int32_t* __restrict__ y, const int32_t* __restrict__ table, int n_batches,
@@ -2121,6 +2141,7 @@ __global__ __launch_bounds__(256) void batch_feed_kernel(
     float* __restrict__ onehot, int64_t ldh, int Y, int row_blocks, int vec4, const float* __restrict__ yf,
     float* __restrict__ ylab, int Yc, float* __restrict__ onehot2, int64_t ldh2, int mask_block, MaskArgs masks,
     ParkArgs park, float* __restrict__ xt, int64_t ldt, int transform) {
+    static_assert(SPLIT || !NORM, "the normalised feed is a variant of the split feed");
     park_block(park);
     if ((int)blockIdx.x == mask_block) {        // (batch-independent plan: the batch's masks ride on this launch)
         batch_masks_body(masks);
@@ -2142,6 +2163,10 @@ __global__ __launch_bounds__(256) void batch_feed_kernel(
             // (a wave per row: four 16-B groups per lane in flight at a time -- a 978-gene row is ONE round trip of loads,
             // not four load -> store iterations; this launch is the head of the step's critical path)
             const int X4 = X >> 2;
+            float sz = 1.f;
+            if constexpr (NORM) {       // (a row wider than one outer iteration, or narrower than one group: summed by a walk)
+                if (X4 > 256 || X4 == 0) sz = feed_size(feed_row_partial(src, X4, X & ~3, X, lane), X);
+            }
             for (int q0 = 0; q0 < X4; q0 += 256) {
                 float4 v[4], e[4];
 #pragma unroll
@@ -2150,13 +2175,27 @@ __global__ __launch_bounds__(256) void batch_feed_kernel(
                     v[u] = reinterpret_cast<const float4*>(src)[qc];
                     e[u] = nz ? reinterpret_cast<const float4*>(nz)[qc] : make_float4(0.f, 0.f, 0.f, 0.f);
                 }
+                if constexpr (NORM) {
+                    if (X4 <= 256) {        // (the whole row is in registers: this is the only iteration)
+                        float acc = 0.f;
+#pragma unroll
+                        for (int u = 0; u < 4; ++u)
+                            if (lane + 64 * u < X4) acc += v[u].x, acc += v[u].y, acc += v[u].z, acc += v[u].w;
+                        for (int g = (X & ~3) + lane; g < X; g += 64) acc += src[g];
+                        sz = feed_size(acc, X);
+                    }
+                }
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     const int q = q0 + lane + 64 * u;
                     if constexpr (SPLIT) {
                         if (q < X4) reinterpret_cast<float4*>(raw)[q] = v[u];
-                        v[u] = make_float4(feed_T(transform, v[u].x), feed_T(transform, v[u].y), feed_T(transform, v[u].z),
-                                           feed_T(transform, v[u].w));
+                        if constexpr (NORM)
+                            v[u] = make_float4(feed_Tn(v[u].x, sz), feed_Tn(v[u].y, sz), feed_Tn(v[u].z, sz),
+                                               feed_Tn(v[u].w, sz));
+                        else
+                            v[u] = make_float4(feed_T(transform, v[u].x), feed_T(transform, v[u].y), feed_T(transform, v[u].z),
+                                               feed_T(transform, v[u].w));
                     }
                     if (q < X4)
                         reinterpret_cast<float4*>(dst)[q] = make_float4(fmaf(sigma, e[u].x, v[u].x), fmaf(sigma, e[u].y, v[u].y),
@@ -2165,7 +2204,7 @@ __global__ __launch_bounds__(256) void batch_feed_kernel(
             }
             if constexpr (SPLIT) {
                 for (int g = (X & ~3) + lane; g < X; g += 64) {
-                    const float xv = src[g], tv = feed_T(transform, xv);
+                    const float xv = src[g], tv = NORM ? feed_Tn(xv, sz) : feed_T(transform, xv);
                     raw[g] = xv;
                     dst[g] = nz ? fmaf(sigma, nz[g], tv) : tv;
                 }
@@ -2173,8 +2212,10 @@ __global__ __launch_bounds__(256) void batch_feed_kernel(
                 for (int g = (X & ~3) + lane; g < X; g += 64) dst[g] = nz ? fmaf(sigma, nz[g], src[g]) : src[g];
             }
         } else if constexpr (SPLIT) {
+            float sz = 1.f;
+            if constexpr (NORM) sz = feed_size(feed_row_partial(src, 0, 0, X, lane), X);
             for (int g = lane; g < X; g += 64) {
-                const float xv = src[g], tv = feed_T(transform, xv);
+                const float xv = src[g], tv = NORM ? feed_Tn(xv, sz) : feed_T(transform, xv);
                 raw[g] = xv;
                 dst[g] = nz ? fmaf(sigma, nz[g], tv) : tv;
             }
@@ -3767,7 +3808,8 @@ extern "C" int dv_batch_feed(const dv_batch_feed_desc* dsc, const dv_batch_masks
     DV_REQUIRE(!d.label_r || (d.y && d.has_y));
     DV_REQUIRE(!d.fp_cls || Mf == 0 || (d.y && d.fp_i && d.fp_lab && d.fp_slot));
     // split form (raw-count inputs): targets to xt, encoder rows T(x) + sigma*noise to xin
-    DV_REQUIRE((d.transform == 0 || d.transform == 1) && (d.transform == 0 || d.xt != nullptr));
+    // (`transform`: 0 none, 1 log1p, 3 log1p_norm -- the row's own size factor divides it first; 2 is no code)
+    DV_REQUIRE((d.transform == 0 || d.transform == 1 || d.transform == 3) && (d.transform == 0 || d.xt != nullptr));
     DV_REQUIRE(d.xt == nullptr || (aligned16(d.xt) && d.ldt >= d.X));
     const int row_blocks = (B + Np + 3) / 4;
     int nlab = (d.label_r ? L * B : 0) > (d.fp_cls ? Mf : 0) ? (d.label_r ? L * B : 0) : (d.fp_cls ? Mf : 0);
@@ -3791,10 +3833,12 @@ extern "C" int dv_batch_feed(const dv_batch_feed_desc* dsc, const dv_batch_masks
     d.x1, d.ld1, d.x2, d.ld2, d.y, d.table, d.n_batches, d.ctr, d.base, B, d.pair_rows, Np, d.X, d.noise, d.ldn, d.sigma,  \
         d.xin, d.ldo, d.has_y, L, d.label_r, d.fp_i, d.fp_lab, d.fp_slot, Mf, d.fp_cls, d.onehot, d.ldh, d.Y, row_blocks,  \
         v4 ? 1 : 0, d.yf, d.ylab, d.Yc, d.onehot2, d.ldh2, mask_block, ma, park
-    if (d.xt)
-        hipLaunchKernelGGL(batch_feed_kernel<true>, grid, block, 0, ST(stream), DV_FEED_ARGS, d.xt, d.ldt, d.transform);
+    if (d.xt && d.transform == 3)
+        hipLaunchKernelGGL((batch_feed_kernel<true, true>), grid, block, 0, ST(stream), DV_FEED_ARGS, d.xt, d.ldt, d.transform);
+    else if (d.xt)
+        hipLaunchKernelGGL((batch_feed_kernel<true, false>), grid, block, 0, ST(stream), DV_FEED_ARGS, d.xt, d.ldt, d.transform);
     else
-        hipLaunchKernelGGL(batch_feed_kernel<false>, grid, block, 0, ST(stream), DV_FEED_ARGS, nullptr, 0, 0);
+        hipLaunchKernelGGL((batch_feed_kernel<false, false>), grid, block, 0, ST(stream), DV_FEED_ARGS, nullptr, 0, 0);
 #undef DV_FEED_ARGS
     DV_RETURN_LAUNCH();
 }

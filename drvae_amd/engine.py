@@ -131,6 +131,8 @@ class StepConfig:
     ema_decay: Optional[float] = None
     # EXTENSIONS (no counterpart in the reference) for RAW COUNTS, count decoders ('poisson' / 'nb' / 'zinb') only; x >= 0:
     #   x_transform='log1p': the encoder reads log1p(x) + sigma * eps; the reconstruction target stays the raw row x, no noise
+    #   x_transform='log1p_norm': the encoder reads log1p(x / s) + sigma * eps, s the size factor below of that same source
+    #                        row (the x2 rows of pairs: x2's own), summed by the feed launch; targets as with 'log1p'
     #   library_size=True  : every decoder mean of a row is multiplied by the observed size factor of its target row,
     #                        s = max(sum_g x_g, 1) / dim_x -- mu = s * (softplus(a_m) + 1e-6); theta and the dropout logit are untouched
     # Either on: SPLIT MODE -- the plan holds the raw target rows in a buffer of their own (``_Plan.XT``), the input launch is
@@ -188,7 +190,7 @@ class StepConfig:
         return self.kind in ('drvae', 'vfae')
 
 
-X_TRANSFORMS = (None, 'log1p')
+X_TRANSFORMS = (None, 'log1p', 'log1p_norm')
 COUNT_DECODERS = ('poisson', 'nb', 'zinb')
 
 
@@ -196,7 +198,7 @@ def check_counts_config(x_transform, library_size, type_rec, prefix=''):
     """the raw-count switches as ``StepConfig`` keyword arguments; ValueError for an unknown ``x_transform`` and for either
     switch on a decoder that is no count decoder"""
     if x_transform not in X_TRANSFORMS:
-        raise ValueError("%sx_transform must be None or 'log1p', not %r" % (prefix, x_transform))
+        raise ValueError("%sx_transform must be None, 'log1p' or 'log1p_norm', not %r" % (prefix, x_transform))
     on = [n for n, v in (('x_transform', x_transform is not None), ('library_size', bool(library_size))) if v]
     if on and type_rec not in COUNT_DECODERS:
         raise ValueError("%s%s is for the count decoders (type_rec='poisson' / 'nb' / 'zinb'), not type_rec=%r"

@@ -963,7 +963,7 @@ def _masks_desc(m, B):
     return md
 
 
-FEED_TRANSFORM = {None: 0, 'log1p': 1}      # dv_batch_feed_desc.transform
+FEED_TRANSFORM = {None: 0, 'log1p': 1, 'log1p_norm': 3}      # dv_batch_feed_desc.transform (2 is no code: refused)
 
 
 def batch_feed(xin, x1, x2, y32, table, n_batches, ctr, base, *, pair_rows=None, noise=None, sigma=0.0, has_y=None,
@@ -971,7 +971,8 @@ def batch_feed(xin, x1, x2, y32, table, n_batches, ctr, base, *, pair_rows=None,
                ylab=None, onehot2=None, masks=None, park=None, xt=None, transform=None):
     """graph-resident minibatch feed: see dv_batch_feed in include/drvae_hip.h; ``masks``: keyword arguments of
     ``batch_masks`` (minus table / ctr / base / B / L): the batch's masks written by the same launch.  ``xt`` (split form,
-    raw-count inputs): the raw rows go to ``xt`` and ``xin`` gets T(x) + sigma * noise, T = log1p with ``transform='log1p'``"""
+    raw-count inputs): the raw rows go to ``xt`` and ``xin`` gets T(x) + sigma * noise, T = log1p with ``transform='log1p'``,
+    log1p(x / s) with ``'log1p_norm'`` -- s = max(sum_g x_g, 1) / X of the same source row, summed by the launch itself"""
     B = table.shape[1]
     md = _masks_desc(masks, B) if masks is not None else None
     assert masks is None or masks.get('gcounts') is None or masks['gcounts'].shape[0] == n_batches

@@ -740,11 +740,17 @@ int dv_rows_gather(const float* src, int64_t lds, const int32_t* idx, int32_t n,
 /* split form (raw-count inputs; `xt` != NULL, trailing fields of the descriptor): the wave that owns row r also writes the
  * RAW row to xt[r,:] (ldt >= X) -- the reconstruction target, without noise -- and xin[r,:] = T(x) + sigma*noise[r] as one
  * fmaf, T = log1p with `transform` == 1 (0: identity).  A compile-time variant of the kernel; with xt == NULL the launch is
- * what it was.  DV_ERR_ARG: `transform` outside {0, 1}, `transform` != 0 without xt, xt not 16-byte aligned.  The step's
- * explicit-batch path runs this form too, over a one-batch identity table with ctr = base = a zero word, x1 / x2 = the two
- * halves of the plan's source rows and no label outputs (y, has_y, label_r, fp_* all NULL: the argument checks never
- * required them without label outputs, so none had to be relaxed), so host-fed and graph-resident steps form their inputs
- * with one kernel and agree bit for bit. */
+ * what it was.  `transform` == 3 (`x_transform='log1p_norm'`, a compile-time variant of the split form): T(x) = log1p(x / s)
+ * with s = max(sum_g x[g], 1) / X of that same SOURCE row (the x2 rows of the pairs: x2's own total), summed by the row's wave
+ * in front of the transform -- lane partials in index order, then the wave sum, one fixed order -- before and without the noise;
+ * x / s is a true division (one rounding).  A row whose total is X (s = 1) gives the bits of code 1, an all-zero row T = 0.
+ * For integer counts with a row total below 2^24 the sum is exact in any order, so s is the ONE correctly rounded quotient
+ * that dv_rec_nll_rows' _LIB kinds form; for non-integer input s is not guaranteed bit-equal to the decoder's s.  Code 2 is
+ * no transform and stays refused.  DV_ERR_ARG, before any launch: `transform` outside {0, 1, 3}, `transform` != 0 without
+ * xt, xt not 16-byte aligned.  The step's explicit-batch path runs this form too, over a one-batch identity table with
+ * ctr = base = a zero word, x1 / x2 = the two halves of the plan's source rows and no label outputs (y, has_y, label_r,
+ * fp_* all NULL: the argument checks never required them without label outputs, so none had to be relaxed), so host-fed
+ * and graph-resident steps form their inputs with one kernel and agree bit for bit. */
 /* `park` (optional): the launch first parks like dv_flag_wait -- the first launch of a step waiting for the previous
  * step's other launch chain (DV_ERR_UNSUPPORTED for grids above DV_MAX_PARKED_GRID workgroups). */
 typedef struct dv_batch_masks_desc {
