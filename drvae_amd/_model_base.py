@@ -79,8 +79,9 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         self.to(device)
 
     def _check_supported(self):
-        if self.type_rec not in ('diag_gaussian', 'binary', 'poisson', 'nb', 'zinb'):
-            raise ValueError("type_rec must be 'diag_gaussian', 'binary', 'poisson', 'nb' or 'zinb'")      # src/DrVAE.py:124-131
+        if self.type_rec not in E.REC_FAMILIES:      # src/DrVAE.py:124-131
+            names = [repr(k) for k in E.REC_FAMILIES]
+            raise ValueError('type_rec must be %s or %s' % (', '.join(names[:-1]), names[-1]))
         # 'binary' / 'poisson' point at blk.BernoulliDecoder / blk.PoissonDecoder, which the reference's blocks.py
         # does not define (its constructor raises AttributeError there): built here as labelled EXTENSIONS; 'nb' (the
         # negative binomial for overdispersed counts, blk.NegativeBinomialDecoder) and 'zinb' (its zero-inflated form,
@@ -171,10 +172,10 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         # (one head in the fused step: the classifier -- a regression head's log-variance is fixed, its layer is not in the
         # step's chain (``FusedStep.L_clf``) -- and a Bernoulli / Poisson decoder; the negative binomial has two, its
         # zero-inflated form three: all of them read the one mask)
-        two_heads = [n for n, h in hidden.items() if len(h) and n != 'encoder_y' and not
-                     (n == 'decoder_x' and self.type_rec not in ('diag_gaussian', 'nb', 'zinb'))]
+        x_heads = len(E.REC_FAMILIES[self.type_rec].heads)
+        two_heads = [n for n, h in hidden.items() if len(h) and n != 'encoder_y' and not (n == 'decoder_x' and x_heads == 1)]
         undropped = [n for n, h in hidden.items() if not len(h)]
-        three = ' (all three heads of the zero-inflated decoder_x)' if self.type_rec == 'zinb' and 'decoder_x' in two_heads else ''
+        three = ' (all three heads of the zero-inflated decoder_x)' if x_heads == 3 and 'decoder_x' in two_heads else ''
         warnings.warn('dropout_rate=%g in the fused train step differs from the block-level path in two labelled ways: '
                       'both heads share ONE keep mask in %s%s; no dropout at all (no hidden layer) in %s'
                       % (self.dropout_rate, ', '.join(two_heads) or 'no block', three, ', '.join(undropped) or 'no block'))

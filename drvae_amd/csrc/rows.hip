@@ -1024,35 +1024,6 @@ __device__ __forceinline__ float row_size_factor(const float* __restrict__ xr, i
     return fmaxf(tot, 1.f) / (float)X;
 }
 
-template <bool LIB>
-__global__ __launch_bounds__(256) void rec_nll_rows_kernel(int kind, float shift, const float* __restrict__ coef,
-                                                           const float* __restrict__ x, int64_t ldx,
-                                                           const int32_t* __restrict__ xidx,
-                                                           const float* __restrict__ v, int64_t ldv, int M, int X,
-                                                           float* __restrict__ out, float* __restrict__ dpre,
-                                                           int64_t ldd) {
-    __shared__ float part[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int r = blockIdx.x; r < M; r += gridDim.x) {
-        const float* xr = x + (int64_t)(xidx ? xidx[r] : r) * ldx;
-        const float* vr = v + (int64_t)r * ldv;
-        const float c = coef ? coef[r] : 0.f;
-        float sz = 1.f;
-        if constexpr (LIB) sz = row_size_factor<false>(xr, X, part);      // (the term loop's read of the row: from cache)
-        float acc = 0.f;
-        for (int g = threadIdx.x; g < X; g += 256) {
-            float gr;
-            acc += rec_term<LIB>(kind, shift, sz, xr[g], vr[g], gr);
-            if (coef) dpre[(int64_t)r * ldd + g] = c * gr;
-        }
-        acc = dv_wave_sum_all(acc);
-        if (lane == 0) part[wave] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) out[r] = (part[0] + part[1]) + (part[2] + part[3]);
-        __syncthreads();
-    }
-}
-
 // Negative-binomial reconstruction rows (type_rec = 'nb': labelled extension, no counterpart in the reference): mean m > 0,
 // inverse dispersion t > 0 (Var = m + m^2 / t), count x >= 0.
 //   log p = [lgamma(x+t) - lgamma(t)] - lgamma(x+1) + t log(t/(t+m)) + x log(m/(t+m))
@@ -1103,68 +1074,6 @@ __device__ __forceinline__ float nb_term(float shift, float s, float x, float v,
     return (lg - lgammaf(x + 1.f)) + (t * lt + x * lm);
 }
 
-// one workgroup per row, like rec_nll_rows_kernel; VEC (X % 4 == 0, 16-byte aligned rows: the dispatcher checks): four
-// genes per thread on 16-byte loads and stores, else one gene per thread
-template <bool VEC, bool LIB>
-__global__ __launch_bounds__(256) void nb_nll_rows_kernel(float shift, const float* __restrict__ coef,
-                                                          const float* __restrict__ x, int64_t ldx,
-                                                          const int32_t* __restrict__ xidx, const float* __restrict__ v,
-                                                          int64_t ldv, int M, int X, float* __restrict__ out,
-                                                          float* __restrict__ dpre, int64_t ldd) {
-    __shared__ float part[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int r = blockIdx.x; r < M; r += gridDim.x) {
-        const float* xr = x + (int64_t)(xidx ? xidx[r] : r) * ldx;
-        const float* vr = v + (int64_t)r * ldv;
-        float* dr = coef ? dpre + (int64_t)r * ldd : nullptr;
-        const float c = coef ? coef[r] : 0.f;
-        float sz = 1.f;
-        if constexpr (LIB) sz = row_size_factor<VEC>(xr, X, part);      // (the term loops' read of the row: from cache)
-        float acc = 0.f;
-        if constexpr (VEC) {
-            for (int q = threadIdx.x; q < (X >> 2); q += 256) {
-                const float4 xv = reinterpret_cast<const float4*>(xr)[q];
-                const float4 mv = reinterpret_cast<const float4*>(vr)[q];
-                const float4 tv = reinterpret_cast<const float4*>(vr + X)[q];
-                float4 gm = make_float4(0.f, 0.f, 0.f, 0.f), gt = gm;
-                // ONE copy of the term's code, walked four times (j is uniform: scalar selects); four inlined copies
-                // interleave their branches' saved masks and run out of scalar registers
-#pragma unroll 1
-                for (int j = 0; j < 4; ++j) {
-                    const float xj = j == 0 ? xv.x : j == 1 ? xv.y : j == 2 ? xv.z : xv.w;
-                    const float mj = j == 0 ? mv.x : j == 1 ? mv.y : j == 2 ? mv.z : mv.w;
-                    const float tj = j == 0 ? tv.x : j == 1 ? tv.y : j == 2 ? tv.z : tv.w;
-                    float a, b;
-                    acc += nb_term<LIB>(shift, sz, xj, mj, tj, a, b);
-                    if (coef) {      // (inside the branch: a pass without gradients does not pay for them)
-                        a *= c, b *= c;
-                        gm.x = j == 0 ? a : gm.x, gm.y = j == 1 ? a : gm.y, gm.z = j == 2 ? a : gm.z, gm.w = j == 3 ? a : gm.w;
-                        gt.x = j == 0 ? b : gt.x, gt.y = j == 1 ? b : gt.y, gt.z = j == 2 ? b : gt.z, gt.w = j == 3 ? b : gt.w;
-                    }
-                }
-                if (coef) {
-                    reinterpret_cast<float4*>(dr)[q] = gm;
-                    reinterpret_cast<float4*>(dr + X)[q] = gt;
-                }
-            }
-        } else {
-            for (int g = threadIdx.x; g < X; g += 256) {
-                float gm, gt;
-                acc += nb_term<LIB>(shift, sz, xr[g], vr[g], vr[X + g], gm, gt);
-                if (coef) {
-                    dr[g] = c * gm;
-                    dr[X + g] = c * gt;
-                }
-            }
-        }
-        acc = dv_wave_sum_all(acc);
-        if (lane == 0) part[wave] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) out[r] = (part[0] + part[1]) + (part[2] + part[3]);
-        __syncthreads();
-    }
-}
-
 // Zero-inflated negative-binomial reconstruction rows (type_rec = 'zinb': labelled extension, no counterpart in the
 // reference): a third head, the dropout logit a (identity activation), pi = sigmoid(a), over the NB term at (m, t):
 //   x > 0:  log p = -softplus(a) + logNB(x)              d/da = -pi;   d/da_m, d/da_t: the NB term's
@@ -1197,61 +1106,102 @@ __device__ __forceinline__ float zinb_term(float shift, float s, float x, float 
     return fmaxf(u, w) + log1pf(ed);
 }
 
-// one workgroup per row, the NB kernel's shape: v row = [mu | theta | logit], dpre row = [d/da_m | d/da_t | d/da_d], 3X columns
-// each; VEC as there (the dispatcher checks), the same fixed summation order, the same one-copy walk of the quad
-template <bool VEC, bool LIB>
-__global__ __launch_bounds__(256) void zinb_nll_rows_kernel(float shift, const float* __restrict__ coef,
-                                                            const float* __restrict__ x, int64_t ldx,
-                                                            const int32_t* __restrict__ xidx, const float* __restrict__ v,
-                                                            int64_t ldv, int M, int X, float* __restrict__ out,
-                                                            float* __restrict__ dpre, int64_t ldd) {
+// lane j of a 16-byte quad, read and written (j is uniform in the walks that use them: scalar selects).  quad_at as a chain of
+// flat selects: written as one nested conditional inside a function, the compiler turns it into branches on j
+__device__ __forceinline__ float quad_at(float4 v, int j) {
+    float r = v.w;
+    r = j == 2 ? v.z : r, r = j == 1 ? v.y : r, r = j == 0 ? v.x : r;
+    return r;
+}
+__device__ __forceinline__ void quad_put(float4& v, int j, float a) {
+    v.x = j == 0 ? a : v.x, v.y = j == 1 ? a : v.y, v.z = j == 2 ? a : v.z, v.w = j == 3 ? a : v.w;
+}
+
+// the term of a family by its number of heads: h = the heads' outputs at one gene, g = the gradients w.r.t. their
+// pre-activations (rec_term / nb_term / zinb_term: the one definition of each formula).  zinb_term scales two of its gradients
+// after the fact; handed the array's elements it compiles to packed pairs and one more vector register in the scalar walk
+// (72 -> 73 with LIB: a wave less per SIMD), so it writes scalars that are copied out
+template <int HEADS, bool LIB>
+__device__ __forceinline__ float count_term(int kind, float shift, float s, float x, const float (&h)[HEADS],
+                                            float (&g)[HEADS]) {
+    static_assert(HEADS >= 1 && HEADS <= 3);
+    if constexpr (HEADS == 1) return rec_term<LIB>(kind, shift, s, x, h[0], g[0]);
+    else if constexpr (HEADS == 2) return nb_term<LIB>(shift, s, x, h[0], h[1], g[0], g[1]);
+    else {
+        float a, b, d;
+        const float r = zinb_term<LIB>(shift, s, x, h[0], h[1], h[2], a, b, d);
+        g[0] = a, g[1] = b, g[2] = d;
+        return r;
+    }
+}
+
+// The training-side count rows (dv_rec_nll_rows), one workgroup per row: out[r] = sum_g log p(x[xidx[r], g] | heads), with
+// coef != NULL also dpre = coef[r] * the gradients w.r.t. the heads' pre-activations.  A row of v holds the HEADS
+// post-activation heads back to back, X columns each, and a row of dpre their gradients in the same order:
+//   HEADS = 1 (Bernoulli / Poisson, the runtime `kind`): v = [p] or [rate]              dpre = [d/da]
+//   HEADS = 2 (negative binomial; `kind` is not read)  : v = [mu | theta]               dpre = [d/da_m | d/da_t]
+//   HEADS = 3 (zero-inflated; `kind` is not read)      : v = [mu | theta | RAW logit]   dpre = [d/da_m | d/da_t | d/da_d]
+// LIB: the row's size factor first (row_size_factor; the term loops' read of the row then comes from cache).  VEC (X % 4
+// == 0, 16-byte aligned rows: the dispatcher checks; HEADS >= 2 only): four genes per thread on 16-byte loads and stores,
+// else one gene per thread.  Per-thread partials in index order, the wave sum, the four waves as (p0 + p1) + (p2 + p3)
+template <int HEADS, bool VEC, bool LIB>
+__global__ __launch_bounds__(256) void count_nll_rows_kernel(int kind, float shift, const float* __restrict__ coef,
+                                                             const float* __restrict__ x, int64_t ldx,
+                                                             const int32_t* __restrict__ xidx,
+                                                             const float* __restrict__ v, int64_t ldv, int M, int X,
+                                                             float* __restrict__ out, float* __restrict__ dpre,
+                                                             int64_t ldd) {
+    static_assert(HEADS > 1 || !VEC, "the one-head kinds have no 16-byte walk");
     __shared__ float part[4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int r = blockIdx.x; r < M; r += gridDim.x) {
         const float* xr = x + (int64_t)(xidx ? xidx[r] : r) * ldx;
         const float* vr = v + (int64_t)r * ldv;
-        float* dr = coef ? dpre + (int64_t)r * ldd : nullptr;
+        // the gradient row's address: hoisted for two and three heads (formed at the stores, the scalar library-scaled walk of
+        // three heads takes 74 VGPRs, not 72: a wave less per SIMD); for one head formed at the store, which spares the
+        // gradient-free pass its scalar arithmetic and branch per row
+        float* dr = HEADS > 1 && coef ? dpre + (int64_t)r * ldd : nullptr;
         const float c = coef ? coef[r] : 0.f;
         float sz = 1.f;
-        if constexpr (LIB) sz = row_size_factor<VEC>(xr, X, part);      // (the term loops' read of the row: from cache)
+        if constexpr (LIB) sz = row_size_factor<VEC>(xr, X, part);
         float acc = 0.f;
         if constexpr (VEC) {
             for (int q = threadIdx.x; q < (X >> 2); q += 256) {
                 const float4 xv = reinterpret_cast<const float4*>(xr)[q];
-                const float4 mv = reinterpret_cast<const float4*>(vr)[q];
-                const float4 tv = reinterpret_cast<const float4*>(vr + X)[q];
-                const float4 av = reinterpret_cast<const float4*>(vr + 2 * (int64_t)X)[q];
-                float4 gm = make_float4(0.f, 0.f, 0.f, 0.f), gt = gm, gd = gm;
-                // (ONE copy of the term's code, walked four times: see nb_nll_rows_kernel)
+                float4 hv[HEADS], gv[HEADS];
+#pragma unroll
+                for (int k = 0; k < HEADS; ++k) {
+                    hv[k] = reinterpret_cast<const float4*>(vr + k * (int64_t)X)[q];
+                    gv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+                // ONE copy of the term's code, walked four times (j is uniform: scalar selects); four inlined copies
+                // interleave their branches' saved masks and run out of scalar registers
 #pragma unroll 1
                 for (int j = 0; j < 4; ++j) {
-                    const float xj = j == 0 ? xv.x : j == 1 ? xv.y : j == 2 ? xv.z : xv.w;
-                    const float mj = j == 0 ? mv.x : j == 1 ? mv.y : j == 2 ? mv.z : mv.w;
-                    const float tj = j == 0 ? tv.x : j == 1 ? tv.y : j == 2 ? tv.z : tv.w;
-                    const float aj = j == 0 ? av.x : j == 1 ? av.y : j == 2 ? av.z : av.w;
-                    float a, b, e;
-                    acc += zinb_term<LIB>(shift, sz, xj, mj, tj, aj, a, b, e);
-                    if (coef) {
-                        a *= c, b *= c, e *= c;
-                        gm.x = j == 0 ? a : gm.x, gm.y = j == 1 ? a : gm.y, gm.z = j == 2 ? a : gm.z, gm.w = j == 3 ? a : gm.w;
-                        gt.x = j == 0 ? b : gt.x, gt.y = j == 1 ? b : gt.y, gt.z = j == 2 ? b : gt.z, gt.w = j == 3 ? b : gt.w;
-                        gd.x = j == 0 ? e : gd.x, gd.y = j == 1 ? e : gd.y, gd.z = j == 2 ? e : gd.z, gd.w = j == 3 ? e : gd.w;
+                    float h[HEADS], g[HEADS];
+#pragma unroll
+                    for (int k = 0; k < HEADS; ++k) h[k] = quad_at(hv[k], j);
+                    acc += count_term<HEADS, LIB>(kind, shift, sz, quad_at(xv, j), h, g);
+                    if (coef) {      // (inside the branch: a pass without gradients does not pay for them)
+#pragma unroll
+                        for (int k = 0; k < HEADS; ++k) quad_put(gv[k], j, c * g[k]);
                     }
                 }
                 if (coef) {
-                    reinterpret_cast<float4*>(dr)[q] = gm;
-                    reinterpret_cast<float4*>(dr + X)[q] = gt;
-                    reinterpret_cast<float4*>(dr + 2 * (int64_t)X)[q] = gd;
+#pragma unroll
+                    for (int k = 0; k < HEADS; ++k) reinterpret_cast<float4*>(dr + k * (int64_t)X)[q] = gv[k];
                 }
             }
         } else {
-            for (int g = threadIdx.x; g < X; g += 256) {
-                float gm, gt, gd;
-                acc += zinb_term<LIB>(shift, sz, xr[g], vr[g], vr[X + g], vr[2 * (int64_t)X + g], gm, gt, gd);
+            for (int i = threadIdx.x; i < X; i += 256) {
+                float h[HEADS], g[HEADS];
+#pragma unroll
+                for (int k = 0; k < HEADS; ++k) h[k] = vr[k * (int64_t)X + i];
+                acc += count_term<HEADS, LIB>(kind, shift, sz, xr[i], h, g);
                 if (coef) {
-                    dr[g] = c * gm;
-                    dr[X + g] = c * gt;
-                    dr[2 * (int64_t)X + g] = c * gd;
+                    float* d = HEADS > 1 ? dr : dpre + (int64_t)r * ldd;
+#pragma unroll
+                    for (int k = 0; k < HEADS; ++k) d[k * (int64_t)X + i] = c * g[k];
                 }
             }
         }
@@ -2465,7 +2415,7 @@ __global__ __launch_bounds__(256) void recon_rows_kernel(RcArgs a) {
 // The COUNT kinds of dv_recon_rows (type_rec = 'binary' / 'poisson' / 'nb'): the six row statistics between the target row
 // x and the finished mean r, the kind's log-likelihood row at that mean (rec_term / nb_term above: the one definition of each
 // formula, their gradient outputs dead code here) and, optionally, the stored mean -- one workgroup per row like
-// rec_nll_rows_kernel / nb_nll_rows_kernel, any X.  v / t: the POST-activation heads (mean | theta).  LIB: r = s v with the
+// count_nll_rows_kernel, any X.  v / t: the POST-activation heads (mean | theta).  LIB: r = s v with the
 // size factor s of the row xs[i,:] (row_size_factor; xs = the target itself, or ANOTHER matrix: the prediction of x2 is made
 // at x1's depth); !LIB: r = v, xs is not read.  Walk 1 forms sum x, sum r, sum (x-r)^2 and the term sum (and stores r), walk
 // 2 -- over the cache-hot row -- the centred sums at the means of walk 1, as recon_row_stats_kernel does (counts reach the
@@ -2476,7 +2426,7 @@ __global__ __launch_bounds__(256) void recon_rows_kernel(RcArgs a) {
 // lane, and walk 2 reads r back from ro when there is one (v holds r then).  Per-thread partials in index order, the wave
 // sum, the four waves as (p0 + p1) + (p2 + p3): no atomics, equal bits on every launch.
 // VEC (X % 4 == 0, 16-byte aligned rows: the dispatcher checks): 16-byte loads and stores; the term walked one gene at a
-// time (#pragma unroll 1: see nb_nll_rows_kernel -- four inlined copies of nb_term run out of scalar registers)
+// time (#pragma unroll 1: see count_nll_rows_kernel -- four inlined copies of nb_term run out of scalar registers)
 struct RcCountArgs {
     const float* x; int64_t ldx; const float* v; int64_t ldv; const float* t; int64_t ldt;
     const float* xs; int64_t ldxs; float* ro; int64_t ldo;
@@ -2519,15 +2469,13 @@ __global__ __launch_bounds__(256) void recon_rows_count_kernel(RcCountArgs a) {
                 if constexpr (NB) tv = reinterpret_cast<const float4*>(tr)[q];
 #pragma unroll 1
                 for (int j = 0; j < 4; ++j) {
-                    const float xj = j == 0 ? xv.x : j == 1 ? xv.y : j == 2 ? xv.z : xv.w;
-                    const float mj = j == 0 ? mv.x : j == 1 ? mv.y : j == 2 ? mv.z : mv.w;
-                    const float tj = j == 0 ? tv.x : j == 1 ? tv.y : j == 2 ? tv.z : tv.w;
+                    const float xj = quad_at(xv, j), mj = quad_at(mv, j), tj = quad_at(tv, j);
                     float r;
                     sl += rc_count_term<KIND, LIB>(sz, xj, mj, tj, r);
                     sx += xj;
                     sr += r;
                     sse += (xj - r) * (xj - r);
-                    rv.x = j == 0 ? r : rv.x, rv.y = j == 1 ? r : rv.y, rv.z = j == 2 ? r : rv.z, rv.w = j == 3 ? r : rv.w;
+                    quad_put(rv, j, r);
                 }
                 if (ro) reinterpret_cast<float4*>(ro)[q] = rv;
             }
@@ -3461,33 +3409,20 @@ extern "C" int dv_gauss_nll_rows_raw_cs(const dv_nll_raw_cs_desc* dsc, dv_stream
 extern "C" int dv_nll_raw_cs_chunks(int32_t X) { return X < 4 ? 0 : ((X >> 2) + 255) / 256; }
 extern "C" int dv_nll_raw_cs_row_blocks(int32_t M) { return M <= 0 ? 0 : (M + kNllCsRows - 1) / kNllCsRows; }
 
-template <bool LIB>
-static void launch_rec_nll_rows(bool nb, bool vec, int kind, float shift, const float* coef, const float* x, int64_t ldx,
-                                const int32_t* xidx, const float* v, int64_t ldv, int M, int X, float* out, float* dpre,
-                                int64_t ldd, dv_stream_t stream) {
+template <int HEADS, bool LIB>
+static void launch_count_nll_rows(bool vec, int kind, float shift, const float* coef, const float* x, int64_t ldx,
+                                  const int32_t* xidx, const float* v, int64_t ldv, int M, int X, float* out, float* dpre,
+                                  int64_t ldd, dv_stream_t stream) {
     const dim3 grid(grid_for(M, 1, 4096)), block(256);
-    if (!nb)
-        hipLaunchKernelGGL(rec_nll_rows_kernel<LIB>, grid, block, 0, ST(stream), kind, shift, coef, x, ldx, xidx, v, ldv, M,
-                           X, out, dpre, ldd);
-    else if (vec)
-        hipLaunchKernelGGL((nb_nll_rows_kernel<true, LIB>), grid, block, 0, ST(stream), shift, coef, x, ldx, xidx, v, ldv,
-                           M, X, out, dpre, ldd);
-    else
-        hipLaunchKernelGGL((nb_nll_rows_kernel<false, LIB>), grid, block, 0, ST(stream), shift, coef, x, ldx, xidx, v, ldv,
-                           M, X, out, dpre, ldd);
-}
-
-template <bool LIB>
-static void launch_zinb_nll_rows(bool vec, float shift, const float* coef, const float* x, int64_t ldx, const int32_t* xidx,
-                                 const float* v, int64_t ldv, int M, int X, float* out, float* dpre, int64_t ldd,
-                                 dv_stream_t stream) {
-    const dim3 grid(grid_for(M, 1, 4096)), block(256);
-    if (vec)
-        hipLaunchKernelGGL((zinb_nll_rows_kernel<true, LIB>), grid, block, 0, ST(stream), shift, coef, x, ldx, xidx, v, ldv,
-                           M, X, out, dpre, ldd);
-    else
-        hipLaunchKernelGGL((zinb_nll_rows_kernel<false, LIB>), grid, block, 0, ST(stream), shift, coef, x, ldx, xidx, v,
-                           ldv, M, X, out, dpre, ldd);
+    if constexpr (HEADS > 1) {
+        if (vec) {
+            hipLaunchKernelGGL((count_nll_rows_kernel<HEADS, true, LIB>), grid, block, 0, ST(stream), kind, shift, coef, x,
+                               ldx, xidx, v, ldv, M, X, out, dpre, ldd);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((count_nll_rows_kernel<HEADS, false, LIB>), grid, block, 0, ST(stream), kind, shift, coef, x, ldx,
+                       xidx, v, ldv, M, X, out, dpre, ldd);
 }
 
 extern "C" int dv_rec_nll_rows(int32_t kind, float shift, const float* coef, const float* x, int64_t ldx,
@@ -3498,28 +3433,22 @@ extern "C" int dv_rec_nll_rows(int32_t kind, float shift, const float* coef, con
     DV_REQUIRE(x && v && out && (coef == nullptr || dpre != nullptr));
     // the library-scaled kinds: the unscaled kind's kernel, compiled with the size-factor sweep in front of its term loop
     const bool lib = kind == DV_REC_POISSON_LIB || kind == DV_REC_NEGBIN_LIB || kind == DV_REC_ZINB_LIB;
-    const bool nb = kind == DV_REC_NEGBIN || kind == DV_REC_NEGBIN_LIB;
-    const bool zinb = kind == DV_REC_ZINB || kind == DV_REC_ZINB_LIB;
+    const int heads = kind == DV_REC_NEGBIN || kind == DV_REC_NEGBIN_LIB ? 2
+                      : kind == DV_REC_ZINB || kind == DV_REC_ZINB_LIB ? 3 : 1;
     bool vec = false;
-    if (nb || zinb) {      // v = [mu | theta (| logit)], dpre = [d/da_m | d/da_t (| d/da_d)]: 2X (3X) columns each, kernels of their own
-        const int64_t w = (nb ? 2 : 3) * (int64_t)X;
+    if (heads > 1) {      // v and dpre: `heads` blocks of X columns each
+        const int64_t w = heads * (int64_t)X;
         DV_REQUIRE(ldv >= w && (coef == nullptr || ldd >= w));
         auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
         vec = X % 4 == 0 && a16(x) && a16(v) && ldx % 4 == 0 && ldv % 4 == 0 &&
               (coef == nullptr || (a16(dpre) && ldd % 4 == 0));
     }
-    if (zinb) {
-        if (lib)
-            launch_zinb_nll_rows<true>(vec, shift, coef, x, ldx, xidx, v, ldv, M, X, out, dpre, ldd, stream);
-        else
-            launch_zinb_nll_rows<false>(vec, shift, coef, x, ldx, xidx, v, ldv, M, X, out, dpre, ldd, stream);
-        DV_RETURN_LAUNCH();
-    }
-    const int k = kind == DV_REC_POISSON_LIB ? DV_REC_POISSON : kind;
-    if (lib)
-        launch_rec_nll_rows<true>(nb, vec, k, shift, coef, x, ldx, xidx, v, ldv, M, X, out, dpre, ldd, stream);
-    else
-        launch_rec_nll_rows<false>(nb, vec, k, shift, coef, x, ldx, xidx, v, ldv, M, X, out, dpre, ldd, stream);
+    const int k = kind == DV_REC_POISSON_LIB ? DV_REC_POISSON : kind;      // (read by the one-head kernels only)
+    static constexpr decltype(&launch_count_nll_rows<1, false>) launch[3][2] = {
+        {launch_count_nll_rows<1, false>, launch_count_nll_rows<1, true>},
+        {launch_count_nll_rows<2, false>, launch_count_nll_rows<2, true>},
+        {launch_count_nll_rows<3, false>, launch_count_nll_rows<3, true>}};
+    launch[heads - 1][lib](vec, k, shift, coef, x, ldx, xidx, v, ldv, M, X, out, dpre, ldd, stream);
     DV_RETURN_LAUNCH();
 }
 

@@ -23,14 +23,14 @@ import math
 import os
 from collections import OrderedDict
 from dataclasses import dataclass, field
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import kernels as K
 from . import tuning as T
-from ._lib import GAUSS_LOGVAR, GAUSS_SIGMA
+from ._lib import GAUSS_LOGVAR, GAUSS_SIGMA, REC_KIND, RECON_KIND
 from .arena import N_LOSS, ParamArena, span
 from .chain import X3_PARTS, _Chain, _Lin, _pad4
 from .plan import LOSS_IDX, _Plan
@@ -169,6 +169,11 @@ class StepConfig:
         return bool(self.anneal_kl or (self.anneal_yloss and self.has_y) or self.anneal_learning_rate)
 
     @property
+    def rec(self):
+        """the reconstruction family of ``type_rec`` (``REC_FAMILIES``)"""
+        return REC_FAMILIES[self.type_rec]
+
+    @property
     def split_x(self):
         """are the encoder's rows and the reconstruction targets two buffers?  (raw-count inputs)"""
         return bool(self.x_transform is not None or self.library_size)
@@ -191,7 +196,44 @@ class StepConfig:
 
 
 X_TRANSFORMS = (None, 'log1p', 'log1p_norm')
-COUNT_DECODERS = ('poisson', 'nb', 'zinb')
+NB_THETA_SHIFT = 1e-3       # the inverse-dispersion head's shift: the sigma head's (``DV_NB_THETA_SHIFT``)
+
+
+class RecHead(NamedTuple):
+    prefix: str             # state_dict prefix of the head's Linear
+    act: str                # its activation and the shift behind it
+    shift: float
+
+
+class RecFamily(NamedTuple):
+    """what a ``type_rec`` is, in one place.  'binary' / 'poisson': the Bernoulli / Poisson decoders src/DrVAE.py:124-129 names
+    (EXTENSION); 'nb' / 'zinb': the negative binomial and its zero-inflated form (EXTENSIONS, no counterpart in
+    the reference; ``blocks.NegativeBinomialDecoder`` / ``ZeroInflatedNegativeBinomialDecoder``)"""
+    heads: Tuple[RecHead, ...]          # over one trunk, in arena order: the head columns of ``_Plan.DPX`` and of the row launch;
+    #                                     heads[0].shift is the ``shift`` argument of ``dv_rec_nll_rows``
+    counts: bool                        # a count decoder: takes ``x_transform`` / ``library_size``
+    rows_kind: Optional[int]            # kind of ``dv_rec_nll_rows`` (None: the Gaussian rows have entry points of their own)
+    rows_kind_lib: Optional[int]        # its library-scaled kind (None: the family has none)
+    recon_kind: Optional[int]           # kind of ``dv_recon_rows`` (None: it has none -- whole-set evaluation declines the model)
+    eval_ll: bool                       # does that evaluation report a log-likelihood?
+
+
+# the negative binomial's two heads, mean then inverse dispersion: both softplus + their own shift
+_NB_HEADS = (RecHead('decoder_x.decoder_m.linear_m', 'softplus', 1e-6),
+             RecHead('decoder_x.decoder_t.linear_t', 'softplus', NB_THETA_SHIFT))
+REC_FAMILIES = {
+    'diag_gaussian': RecFamily((RecHead('decoder_x.encoder_mu.linear_mu', 'identity', 0.0),
+                                RecHead('decoder_x.encoder_sg.linear_sg', 'softplus', 1e-3)),
+                               False, None, None, RECON_KIND[None], True),
+    'binary': RecFamily((RecHead('decoder_x.decoder_p.linear_p', 'sigmoid', 0.0),), False, REC_KIND['binary'], None,
+                        RECON_KIND['binary'], False),
+    'poisson': RecFamily((RecHead('decoder_x.decoder_r.linear_r', 'softplus', 1e-6),), True, REC_KIND['poisson'],
+                         REC_KIND['poisson_lib'], RECON_KIND['poisson'], False),
+    'nb': RecFamily(_NB_HEADS, True, REC_KIND['nb'], REC_KIND['nb_lib'], RECON_KIND['nb'], True),
+    # the dropout logit (identity) behind those two, back to back in the arena -- ``_Lin(third=...)``
+    'zinb': RecFamily(_NB_HEADS + (RecHead('decoder_x.decoder_d.linear_d', 'identity', 0.0),), True,
+                      REC_KIND['zinb'], REC_KIND['zinb_lib'], None, False),
+}
 
 
 def check_counts_config(x_transform, library_size, type_rec, prefix=''):
@@ -200,9 +242,9 @@ def check_counts_config(x_transform, library_size, type_rec, prefix=''):
     if x_transform not in X_TRANSFORMS:
         raise ValueError("%sx_transform must be None, 'log1p' or 'log1p_norm', not %r" % (prefix, x_transform))
     on = [n for n, v in (('x_transform', x_transform is not None), ('library_size', bool(library_size))) if v]
-    if on and type_rec not in COUNT_DECODERS:
-        raise ValueError("%s%s is for the count decoders (type_rec='poisson' / 'nb' / 'zinb'), not type_rec=%r"
-                         % (prefix, ' / '.join(on), type_rec))
+    if on and not (type_rec in REC_FAMILIES and REC_FAMILIES[type_rec].counts):
+        raise ValueError("%s%s is for the count decoders (type_rec=%s), not type_rec=%r"
+                         % (prefix, ' / '.join(on), ' / '.join(repr(k) for k, f in REC_FAMILIES.items() if f.counts), type_rec))
     return dict(x_transform=x_transform, library_size=bool(library_size))
 
 
@@ -262,27 +304,12 @@ def param_shapes(cfg):
             lin('encoder_y.decoder_p.linear_p', n, 1 if cfg.clf_1sig else Y)
         gauss(cfg.top_name, Z1 + Y, cfg.h_en_z3, Z3)
         gauss('decoder_z1', Z3 + Y, cfg.h_de_z1, Z1)
-    if cfg.type_rec == 'diag_gaussian':
-        gauss('decoder_x', Z1 + S, cfg.h_de_x, X, second='sg')
-    elif cfg.type_rec in ('nb', 'zinb'):
-        n = trunk('decoder_x.nnet', Z1 + S, cfg.h_de_x)
-        for q in NB_HEADS + ((ZINB_LOGIT_HEAD,) if cfg.type_rec == 'zinb' else ()):
-            lin(q, n, X)
-    else:
-        n = trunk('decoder_x.nnet', Z1 + S, cfg.h_de_x)
-        lin(REC_HEAD[cfg.type_rec], n, X)
+    n = trunk('decoder_x.nnet', Z1 + S, cfg.h_de_x)
+    for h in cfg.rec.heads:
+        lin(h.prefix, n, X)
     return out
 
 
-REC_HEAD = {'binary': 'decoder_x.decoder_p.linear_p', 'poisson': 'decoder_x.decoder_r.linear_r'}
-# (head's activation, shift of its first -- or only -- head: the ``shift`` argument of ``dv_rec_nll_rows``)
-REC_ACT = {'binary': ('sigmoid', 0.0), 'poisson': ('softplus', 1e-6), 'nb': ('softplus', 1e-6), 'zinb': ('softplus', 1e-6)}
-# the negative-binomial decoder's two heads over one trunk, mean then inverse dispersion (``blocks.NegativeBinomialDecoder``);
-# theta's shift is the sigma head's (``DV_NB_THETA_SHIFT``)
-NB_HEADS = ('decoder_x.decoder_m.linear_m', 'decoder_x.decoder_t.linear_t')
-NB_THETA_SHIFT = 1e-3
-# the zero-inflated decoder's third head behind those two: the dropout logit, identity (``blocks.ZeroInflatedNegativeBinomialDecoder``)
-ZINB_LOGIT_HEAD = 'decoder_x.decoder_d.linear_d'
 Y_LOGVAR_CONT = math.log(0.05 ** 2)      # fixed variance of the regression head (src/DrVAE.py:168)
 
 
@@ -397,25 +424,17 @@ class FusedStep(StepSchedule):
         cfg, a = self.cfg, self.arena
         wn = cfg.weight_norm
         self.L_enc = self._gauss('encoder_z1', len(cfg.h_en_z1), 'lv', shift_second=-2.0)
-        if cfg.type_rec == 'diag_gaussian':
-            self.L_decx = self._gauss('decoder_x', len(cfg.h_de_x), 'sg', 'softplus', 1e-3)
-        else:       # Bernoulli / Poisson decoder: trunk + ONE head (probabilities / rates); negative binomial: two
-            layers = []
-            for i in range(1, len(cfg.h_de_x) + 1):
-                q = 'decoder_x.nnet.model.linear%d' % i
-                layers.append(_Lin(a, q + '.weight', q + '.bias', q + '.g' if wn else None, act=cfg.nonlin))
-            act, shift = REC_ACT[cfg.type_rec]
-            if cfg.type_rec in ('nb', 'zinb'):      # negative binomial: TWO heads, [mu | theta], both softplus + their own shift
-                q, s = NB_HEADS
-                names = lambda h: (h + '.weight', h + '.bias', h + '.g' if wn else None)
-                # (zero-inflated: the dropout logit behind them, back to back in the arena -- ``_Lin(third=...)``)
-                tri = dict(third=names(ZINB_LOGIT_HEAD)) if cfg.type_rec == 'zinb' else {}
-                layers.append(_Lin(a, *names(q), second=names(s), act=act, shift0=shift, act1='softplus',
-                                   shift1=NB_THETA_SHIFT, **tri))
-            else:
-                q = REC_HEAD[cfg.type_rec]
-                layers.append(_Lin(a, q + '.weight', q + '.bias', q + '.g' if wn else None, act=act, shift0=shift))
-            self.L_decx = layers
+        # the data decoder: trunk + the family's heads as ONE layer (one, a pair, or a pair with a third -- identity -- behind it)
+        names = lambda q: (q + '.weight', q + '.bias', q + '.g' if wn else None)
+        heads = cfg.rec.heads
+        kw = dict(act=heads[0].act, shift0=heads[0].shift)
+        if len(heads) > 1:
+            kw.update(second=names(heads[1].prefix), act1=heads[1].act, shift1=heads[1].shift)
+        if len(heads) > 2:
+            assert heads[2].act == 'identity'
+            kw.update(third=names(heads[2].prefix))
+        self.L_decx = [_Lin(a, *names('decoder_x.nnet.model.linear%d' % i), act=cfg.nonlin)
+                       for i in range(1, len(cfg.h_de_x) + 1)] + [_Lin(a, *names(heads[0].prefix), **kw)]
         if cfg.has_pert:
             p = 'decoder_z2Fz1.'
             self.L_z2F = [_Lin(a, p + 'W_mu', p + 'bias_mu', None,
@@ -929,7 +948,7 @@ class FusedStep(StepSchedule):
             self.branch.fork()
         lh = p.c_decx.layers[-1]
         if r.nll == 'rec':     # Bernoulli / Poisson / (zero-inflated) negative-binomial rows (+ the gradient w.r.t. the head's pre-activation in a train step)
-            K.rec_nll_rows(p.NLL, p.XT if cfg.split_x else p.XIN, PX, kind=cfg.type_rec, shift=REC_ACT[cfg.type_rec][1],
+            K.rec_nll_rows(p.NLL, p.XT if cfg.split_x else p.XIN, PX, kind=cfg.type_rec, shift=cfg.rec.heads[0].shift,
                            xidx=p.tgt, coef=p.c_nll if train else None, dpre=p.DPX if train else None, **self._lib_kw())
         elif r.nll in ('raw_cs', 'raw_cs_eval'):
             # the row terms from the raw heads (bias + softplus + shift applied by the pass); train step: and the gradients,
@@ -1248,7 +1267,7 @@ class FusedStep(StepSchedule):
         # coefficients, then back through the decoder (the three big GEMMs)
         PX = p.c_decx.out[-1]
         if not self.fuse_bwd and cfg.type_rec != 'diag_gaussian':
-            K.rec_nll_rows(p.NLL, p.XT if cfg.split_x else p.XIN, PX, kind=cfg.type_rec, shift=REC_ACT[cfg.type_rec][1],
+            K.rec_nll_rows(p.NLL, p.XT if cfg.split_x else p.XIN, PX, kind=cfg.type_rec, shift=cfg.rec.heads[0].shift,
                            xidx=p.tgt, coef=p.c_nll, dpre=p.DPX, **self._lib_kw())
         elif not self.fuse_bwd:
             K.nll_rows_bwd(p.DPX[:, :X], p.DPX[:, X:], p.c_nll, p.XIN, PX[:, :X], PX[:, X:], mode=GAUSS_SIGMA,

@@ -462,8 +462,8 @@ class _EvalGraph:
             return None
         if next(model.parameters()).device != x1.device:
             return None
-        if model.type_rec == 'zinb':
-            return None          # (no zero-inflated kind of ``dv_recon_rows``: step by step, decided up front -- no warning)
+        if E.REC_FAMILIES[model.type_rec].recon_kind is None:
+            return None          # (no kind of ``dv_recon_rows``, 'zinb': step by step, decided up front -- no warning)
         # (the decision is a function of the model's configuration and the dataset's tensors alone: every rank of a
         # data-parallel job decides alike)
         use_s = bool(getattr(model, 'use_s', False))
@@ -514,7 +514,8 @@ class _EvalGraph:
         self.cont = kind != 'pvae' and getattr(model, 'type_y', 'discrete') != 'discrete'
         self.use_s = bool(getattr(model, 'use_s', False))
         # the count decoders ('binary' / 'poisson' / 'nb'): finished heads, ``dv_recon_rows``' count kinds (``_rows_pass``)
-        self.rec_kind = None if model.type_rec == 'diag_gaussian' else model.type_rec
+        self.fam = E.REC_FAMILIES[model.type_rec]
+        self.rec_kind = None if self.fam.recon_kind == E.RECON_KIND[None] else model.type_rec      # (as ``K.recon_rows`` names it)
         self.dp, self.full = dp, None
         if dp is not None:
             # this rank's rows as VIEWS of the dataset's tensors; the normalisers of the loss pass are the whole set's counts,
@@ -776,7 +777,7 @@ class _EvalGraph:
             self.g_ll[tag].copy_(self._slot('ll' + t))
             part = self._slot('part' + t).view(-1, 3, X)
             K.recon_finalize(vec[o:o + 4], self.g_rows[tag], part, X, sel=sel, n=int(sel.numel()) if sel is not None else n,
-                             ll=self.g_ll[tag] if self.rec_kind in (None, 'nb') else None)
+                             ll=self.g_ll[tag] if self.fam.eval_ll else None)
             o += 4
 
     def _rank_metrics(self, proba, y32, pred32, yidx32, out3, n_rows):
@@ -892,7 +893,7 @@ class _EvalGraph:
         raw = bool(self.rec_kind is None and X <= K.RECON_ROWS_MAX_X and self.c_dec.raw_softplus_ok())
         PX = self.c_dec.forward([self.zd] + ([self.soh_d] if self.use_s else []), raw_last=raw)
         res['px_bias'] = (lh.b[:X], lh.b[X:2 * X], lh.shift1) if raw else None
-        two = self.rec_kind in (None, 'nb')
+        two = len(self.fam.heads) == 2
         res['px1'] = (PX[:n, :X], PX[:n, X:2 * X]) if two else (PX[:n, :X],)
         if kind != 'vfae':
             res['px2'] = (PX[n:, :X], PX[n:, X:2 * X]) if two else (PX[n:, :X],)
@@ -908,11 +909,11 @@ class _EvalGraph:
         from . import kernels as K
         from ._lib import GAUSS_SIGMA
         if self.rec_kind is not None:
-            nb = self.rec_kind == 'nb'
+            ll = ll if self.fam.eval_ll else None
             size = self.ds.x1.to(torch.float32) if getattr(self.model, 'library_size', False) else None
-            K.recon_rows(rows, ll if nb else None, x, px[0], px[1] if nb else None, kind=self.rec_kind, size_from=size,
+            K.recon_rows(rows, ll, x, px[0], px[1] if len(px) > 1 else None, kind=self.rec_kind, size_from=size,
                          rec_out=px[0] if size is not None else None)
-            return px[0], (ll if nb else None)
+            return px[0], ll
         if x.shape[1] <= K.RECON_ROWS_MAX_X:
             K.recon_rows(rows, ll, x, px[0], px[1], bias=bias[:2] if bias is not None else None,
                          sd_shift=bias[2] if bias is not None else 0.0)

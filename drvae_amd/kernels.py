@@ -591,15 +591,16 @@ def rec_nll_rows(out, x, v, *, kind, shift=0.0, xidx=None, coef=None, dpre=None,
     logit RAW) and ``dpre`` = [d/da_m | d/da_t | d/da_d], 3X columns each.  ``library`` ('poisson' / 'nb' / 'zinb' only): the
     library-scaled kind -- the mean of row r is s * v with s = max(sum_g x[xidx[r], g], 1) / X, the size factor the kernel
     forms from the target row it reads"""
+    from .engine import REC_FAMILIES          # (the engine imports this module: looked up at call time)
+    fam = REC_FAMILIES[kind]
+    code = fam.rows_kind_lib if library else fam.rows_kind
+    if library and code is None:
+        raise ValueError("rec_nll_rows: library= is for kind 'poisson' / 'nb' / 'zinb', not %r" % (kind,))
     M, X = v.shape
-    if library:
-        if kind not in ('poisson', 'nb', 'zinb'):
-            raise ValueError("rec_nll_rows: library= is for kind 'poisson' / 'nb' / 'zinb', not %r" % (kind,))
-        kind = kind + '_lib'
-    if kind in ('nb', 'nb_lib', 'zinb', 'zinb_lib'):
-        X, w = x.shape[1], 2 if kind in ('nb', 'nb_lib') else 3
+    if len(fam.heads) > 1:
+        X, w = x.shape[1], len(fam.heads)
         assert v.shape[1] == w * X and (dpre is None or tuple(dpre.shape) == (M, w * X))
-    _lib.check(_lib.load().dv_rec_nll_rows(_lib.REC_KIND[kind], shift, _f32(coef), _f32(x), _ld(x), _i32(xidx), _f32(v),
+    _lib.check(_lib.load().dv_rec_nll_rows(code, shift, _f32(coef), _f32(x), _ld(x), _i32(xidx), _f32(v),
                                            _ld(v), M, X, _f32(out), _f32(dpre), _ld(dpre), _stream()), 'dv_rec_nll_rows')
 
 
@@ -1060,20 +1061,14 @@ def col_moment_blocks(M):
 RECON_ROWS_MAX_X = 1024
 
 
-def recon_rows(rows, ll, x, mu, sd, *, bias=None, sd_shift=1e-3, **count):
+def recon_rows(rows, ll, x, mu, sd, *, bias=None, sd_shift=1e-3, kind=None, size_from=None, rec_out=None):
     """row statistics (M, 6) and log-likelihood rows (M; may be None) of a reconstruction in ONE pass over (x, mu, sd),
     X <= RECON_ROWS_MAX_X -- ``recon_row_stats`` + ``nll_rows_fwd``.  ``bias`` = (bias_mu, bias_sd): mu / sd are the
     heads' raw products, finished on the way.
 
-    The count decoders, keyword-only: ``kind=None | 'binary' | 'poisson' | 'nb'``, ``size_from=None``, ``rec_out=None`` (taken
-    as ``**count`` so that the Gaussian pass's own signature stays the one its CPU stand-in ``tests/kernel_ref.py`` states; the
-    stand-in of these three is ``tests/eval_counts_ref.py``; any other keyword is a TypeError).  ``kind`` other than None: any
-    X.  ``mu`` is the mean head's finished output, ``sd`` the theta head for 'nb' and None otherwise.  ``size_from`` (M, X;
+    The count decoders: ``kind='binary' | 'poisson' | 'nb'``, any X.  ``mu`` is the mean head's finished output, ``sd`` the theta head for 'nb' and None otherwise.  ``size_from`` (M, X;
     'poisson' / 'nb'): the statistics and the log-likelihood are taken at r = s * mu, s the size factor of ``size_from``'s rows
     (the target itself or another matrix); ``rec_out`` (M, X; with ``size_from`` only, may be ``mu`` itself) receives r."""
-    kind, size_from, rec_out = count.pop('kind', None), count.pop('size_from', None), count.pop('rec_out', None)
-    if count:
-        raise TypeError('recon_rows() got an unexpected keyword argument %r' % sorted(count)[0])
     M, X = x.shape
     if kind is not None:
         assert kind in ('binary', 'poisson', 'nb') and bias is None

@@ -199,7 +199,7 @@ class _Plan:
                 self.DZMMD = zf(self.o3, Z1)
                 self.MMDval = zf(1)
         self.DQ = zf(Me, 2 * Z1)
-        self.DPX = mat(Md, {'diag_gaussian': 2, 'nb': 2, 'zinb': 3}.get(cfg.type_rec, 1) * X)      # (two heads | three | one)
+        self.DPX = mat(Md, len(cfg.rec.heads) * X)
         self.NLL = zf(Md)
         # per-tile partial sums of the reconstruction rows when they come out of the decoder-heads launch itself
         # (dv_gemm_heads, DV_HEADS_NLL): row r's log-likelihood = NLLP[r].sum()

@@ -1,6 +1,6 @@
 """Float64 reference of the depth-normalised encoder feed (``x_transform='log1p_norm'``: ``dv_batch_feed`` with ``xt`` and
-``transform`` == 3), the bound it is held to, fp32 emulations -- a careful one and five faulty ones the bound catches --, the
-CPU stand-in of the new transform and a model-level float64 reference of one step.  Test-only; builds on
+``transform`` == 3), the bound it is held to, fp32 emulations -- a careful one and five faulty ones the bound catches -- and
+a model-level float64 reference of one step (the feed's CPU stand-in: ``tests/kernel_ref.py``).  Test-only; builds on
 ``tests/counts_ref.py``.
 
 The feed.  ``xt`` is the source row, bit for bit.  The encoder's row is fmaf(sigma, eps, log1p(x / s)) with
@@ -82,36 +82,6 @@ def edge_rows(X=16):
     tot = x.astype(np.float64).sum(1)
     assert tot[2] == X and tot[3] == 1e7 + 1 and tot[4] == 2 ** 24 - 1 and tot.max() < 2 ** 24
     return x
-
-
-# ---------------------------------------------------------------------------------------------- the stand-in
-CALLS = {'norm_feed': 0}
-
-
-def batch_feed(*a, noise=None, sigma=0.0, xt=None, transform=None, **k):
-    """``kernels.batch_feed`` on the CPU: ``tests/kernel_ref``'s stand-in, with ``transform='log1p_norm'`` formed here behind its
-    split feed without a transform (which gathers the raw rows into ``xt``): xin = log1p(xt / s) + sigma * noise, s in fp32
-    from the gathered row itself.  Installed OVER ``kernel_ref.install`` (``install``)"""
-    from tests import kernel_ref
-    if transform != 'log1p_norm':
-        return kernel_ref.batch_feed(*a, noise=noise, sigma=sigma, xt=xt, transform=transform, **k)
-    assert xt is not None
-    CALLS['norm_feed'] += 1
-    kernel_ref.batch_feed(*a, noise=None, sigma=0.0, xt=xt, transform=None, **k)
-    xin = a[0]
-    s = torch.clamp(xt.sum(1), min=1.0) / float(xt.shape[1])
-    t = torch.log1p(xt / s[:, None])
-    xin.copy_(t + sigma * noise if noise is not None else t)
-
-
-def install(monkeypatch):
-    """``kernel_ref.install``, then this module's ``batch_feed`` over it"""
-    from tests import kernel_ref
-    import drvae_amd.kernels as K
-    kernel_ref.install(monkeypatch)
-    monkeypatch.setattr(K, 'batch_feed', batch_feed)
-    for k in CALLS:
-        CALLS[k] = 0
 
 
 # ------------------------------------------------------------------------------- model-level float64 reference

@@ -1,7 +1,7 @@
 """Float64 reference of the count kinds of ``dv_recon_rows`` (``kernels.recon_rows(kind='binary' | 'poisson' | 'nb',
 size_from=..., rec_out=...)``: the whole-set evaluation of the count decoders), the bounds its outputs are held to, an fp32
-emulation -- a careful one and five faulty ones the bounds catch --, the CPU stand-in of the new keywords (on top of
-``tests/kernel_ref.py``) and a float64 evaluation of the reported metrics.  Test-only.
+emulation -- a careful one and five faulty ones the bounds catch -- and a float64 evaluation of the reported metrics (the
+launcher's CPU stand-in: ``tests/kernel_ref.py``).  Test-only.
 
 What the launch forms, per target row x[i,:], from the POST-activation heads v (and theta for 'nb'):
 
@@ -197,32 +197,6 @@ def case(kind, M, X, seed=0, scaled=False, other=False, counts='mixed'):
         assert float(np.asarray(size, np.float64).sum(1).max()) < 2 ** 24
     t = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a))
     return t(x), t(mu), t(theta), t(size)
-
-
-# ------------------------------------------------------------------------------------------- the CPU stand-in
-def recon_rows(rows, ll, x, mu, sd, *, bias=None, sd_shift=1e-3, kind=None, size_from=None, rec_out=None):
-    """``kernel_ref.recon_rows`` plus the count keywords: the header's formulas in float64 on the fp32 values handed in,
-    rounded once (the refusals of the launcher / the entry point as assertions)"""
-    from tests import kernel_ref
-    if kind is None:
-        assert size_from is None and rec_out is None
-        return kernel_ref.recon_rows(rows, ll, x, mu, sd, bias=bias, sd_shift=sd_shift)
-    assert kind in KINDS and bias is None and (sd is not None) == (kind == 'nb')
-    assert not (kind == 'binary' and size_from is not None) and (rec_out is None or size_from is not None)
-    ref = reference(kind, x, mu, sd, size_from)
-    rows.copy_(ref['rows'].to(rows.dtype))
-    if ll is not None:
-        ll.copy_(ref['ll'].to(ll.dtype))
-    if rec_out is not None:
-        rec_out.copy_(ref['rec'].to(rec_out.dtype))
-
-
-def install(monkeypatch):
-    """``kernel_ref.install`` with ``recon_rows`` replaced by the stand-in above"""
-    from tests import kernel_ref
-    import drvae_amd.kernels as K
-    kernel_ref.install(monkeypatch)
-    monkeypatch.setattr(K, 'recon_rows', recon_rows)
 
 
 # -------------------------------------------------------------------------- the reported metrics, in float64

@@ -10,8 +10,9 @@ Two uses, both test-only:
     without a GPU.  The product never imports this module.
 
 The arithmetic is fp32 in the launchers' own operation order, except where a launcher is SPECIFIED in float64 with one
-rounding, and the stand-in states that specification: the negative-binomial and library-size rows (``tests/nb_ref.py``,
-``tests/counts_ref.py``), the noise (``tests/philox_ref.py``), the split-bf16 products (``tests/x3_ref.py``), the schedule
+rounding, and the stand-in states that specification: the negative-binomial, zero-inflated and library-size rows
+(``tests/nb_ref.py``, ``tests/zinb_ref.py``, ``tests/counts_ref.py``), the count kinds of ``recon_rows``
+(``tests/eval_counts_ref.py``), the noise (``tests/philox_ref.py``), the split-bf16 products (``tests/x3_ref.py``), the schedule
 record, the rate / decay / average factors of the sweeps and the clip record.  ``CALLS`` counts what the step tests ask
 about (reset by ``install``); ``FAULT`` makes one stand-in wrong on purpose.
 """
@@ -23,7 +24,7 @@ import torch
 import torch.nn.functional as F
 
 from drvae_amd._lib import ACT, EPI_BWD, EPI_FWD, EPI_PLAIN, GAUSS_LOGVAR, GAUSS_SIGMA  # noqa: F401
-from tests import counts_ref, nb_ref, philox_ref, x3_ref
+from tests import counts_ref, eval_counts_ref, nb_ref, philox_ref, x3_ref, zinb_ref
 
 LOG_2PI = 1.8378770664093453
 _ACT_NAME = {v: k for k, v in ACT.items()}
@@ -31,7 +32,7 @@ _ACT_NAME = {v: k for k, v in ACT.items()}
 CALLS = dict.fromkeys(['batch_masks', 'batch_feed', 'lr_scaled_sweeps', 'decoupled_sweeps', 'averaged_sweeps', 'clip_norm',
                        'adam_l2_clip', 'adamax_l2_clip', 'split_feed', 'plain_feed', 'lib_rows', 'plain_rows',
                        'fill_noise_rows', 'mask_scale', 'z2f_post_bwd', 'smalln_fwd', 'folded_kl', 'folded_dgrad', 'nb',
-                       'other'], 0)
+                       'other', 'zinb', 'zinb_lib', 'norm_feed'], 0)
 FAULT = {'name': None}          # tests only: 'moved_on_skipped_step' makes the averaged sweeps wrong on purpose
 
 
@@ -562,9 +563,19 @@ def nll_rows_bwd(dmu, dsd, coef, x, mu, sd, *, mode=GAUSS_SIGMA, xidx=None, sd_a
 def rec_nll_rows(out, x, v, *, kind, shift=0.0, xidx=None, coef=None, dpre=None, library=False):
     """``kind='nb'`` (``v`` = [mu | theta], ``dpre`` = [d/da_m | d/da_t]) and ``library=True`` (the mean scaled by the size
     factor the kernel forms, an fp32 quotient) state the header's formulas: float64 on the fp32 values handed in, rounded
-    once (``tests/nb_ref.py``, ``tests/counts_ref.py``)"""
+    once (``tests/nb_ref.py``, ``tests/counts_ref.py``); so does ``kind='zinb'`` (``v`` = [mu | theta | logit], ``dpre`` 3X wide;
+    ``tests/zinb_ref.py``), counted on its own"""
     xs = x[xidx.long()] if xidx is not None else x
     X = x.shape[1]
+    if kind == 'zinb':
+        CALLS['zinb_lib' if library else 'zinb'] += 1
+        assert v.shape[1] == 3 * X and (dpre is None or dpre.shape[1] == 3 * X)
+        ref = zinb_ref.reference(xs, v[:, :X], v[:, X:2 * X], v[:, 2 * X:], coef=coef, shift=shift, library=library)
+        out.copy_(ref['rows'].to(out.dtype))
+        if coef is not None:
+            for i, k in enumerate(('gm', 'gt', 'gd')):
+                dpre[:, i * X:(i + 1) * X] = ref[k].to(dpre.dtype)
+        return
     CALLS['lib_rows' if library else 'plain_rows'] += 1
     if library:
         assert kind in ('poisson', 'nb')
@@ -998,10 +1009,13 @@ def rows_gather(out, src, idx=None, *, noise=None, sigma=0.0, onehot_cls=None, n
 def batch_feed(xin, x1, x2, y32, table, n_batches, ctr, base, *, pair_rows=None, noise=None, sigma=0.0, has_y=None,
                L=1, label_r=None, fp_i=None, fp_lab=None, fp_slot=None, fp_cls=None, onehot=None, n_classes=0, yf=None,
                ylab=None, onehot2=None, masks=None, park=None, xt=None, transform=None):
-    """``xt`` (the split form, raw-count inputs): the gathered rows go to ``xt`` and ``xin`` = T(xt) + sigma * noise"""
+    """``xt`` (the split form, raw-count inputs): the gathered rows go to ``xt`` and ``xin`` = T(xt) + sigma * noise;
+    ``transform='log1p_norm'``: T = log1p(xt / s), s in fp32 from the gathered row itself"""
     CALLS['batch_feed'] += 1
     CALLS['plain_feed' if xt is None else 'split_feed'] += 1
-    assert transform is None if xt is None else (transform in (None, 'log1p') and tuple(xt.shape) == tuple(xin.shape))
+    CALLS['norm_feed'] += transform == 'log1p_norm'
+    assert transform is None if xt is None else (transform in (None, 'log1p', 'log1p_norm') and
+                                                 tuple(xt.shape) == tuple(xin.shape))
     rows = xin if xt is None else xt
     if park is not None:
         flag_wait(park[0], park[1], park[2], park[3] if len(park) > 3 else 1)
@@ -1017,7 +1031,10 @@ def batch_feed(xin, x1, x2, y32, table, n_batches, ctr, base, *, pair_rows=None,
     if pair_rows is not None and pair_rows.numel():
         rows[B:] = x2[tb[pair_rows.long()]]
     if xt is not None:
-        t = torch.log1p(xt) if transform == 'log1p' else xt
+        if transform == 'log1p_norm':
+            t = torch.log1p(xt / (torch.clamp(xt.sum(1), min=1.0) / float(xt.shape[1]))[:, None])
+        else:
+            t = torch.log1p(xt) if transform == 'log1p' else xt
         xin.copy_(t + sigma * noise if noise is not None else t)
     elif noise is not None:
         xin += sigma * noise
@@ -1088,7 +1105,20 @@ def col_moments(out, x, r, sel=None, part=None, r_bias=None):
 RECON_ROWS_MAX_X = 1024
 
 
-def recon_rows(rows, ll, x, mu, sd, *, bias=None, sd_shift=1e-3):
+def recon_rows(rows, ll, x, mu, sd, *, bias=None, sd_shift=1e-3, kind=None, size_from=None, rec_out=None):
+    """the count kinds (``kind`` / ``size_from`` / ``rec_out``): the header's formulas in float64 on the fp32 values handed in,
+    rounded once (``tests/eval_counts_ref.py``; the refusals of the launcher / the entry point as assertions)"""
+    if kind is not None:
+        assert kind in eval_counts_ref.KINDS and bias is None and (sd is not None) == (kind == 'nb')
+        assert not (kind == 'binary' and size_from is not None) and (rec_out is None or size_from is not None)
+        ref = eval_counts_ref.reference(kind, x, mu, sd, size_from)
+        rows.copy_(ref['rows'].to(rows.dtype))
+        if ll is not None:
+            ll.copy_(ref['ll'].to(ll.dtype))
+        if rec_out is not None:
+            rec_out.copy_(ref['rec'].to(rec_out.dtype))
+        return
+    assert size_from is None and rec_out is None
     if bias is not None:          # raw heads: finished here
         mu = mu + bias[0]
         sd = F.softplus(sd + bias[1]) + sd_shift

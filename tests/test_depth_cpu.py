@@ -165,9 +165,9 @@ def run_against_reference(kind, variant, lib, dev='cpu', tol=((2e-5, 2e-6), (3e-
 @pytest.mark.parametrize('variant,lib', CASES)
 @pytest.mark.parametrize('kind', ['drvae', 'pvae', 'vfae'])
 def test_fused_step_matches_the_float64_model_reference(kind, variant, lib, monkeypatch):
-    DR.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     run_against_reference(kind, variant, lib)
-    assert DR.CALLS['norm_feed'] > 0 and kernel_ref.CALLS['plain_feed'] == 0
+    assert kernel_ref.CALLS['norm_feed'] > 0 and kernel_ref.CALLS['plain_feed'] == 0
     assert (kernel_ref.CALLS['lib_rows'] > 0) == lib and (kernel_ref.CALLS['plain_rows'] > 0) == (not lib)
 
 
@@ -218,9 +218,9 @@ def host_fed_equals_feed(kind, dev, extra=None, steps=3, captured=False, use_s=F
 @pytest.mark.parametrize('kind,use_s,lib', [('drvae', False, True), ('pvae', False, False), ('vfae', False, True), ('vfae', True, True)])
 def test_host_fed_step_equals_feed_step_bit_for_bit(kind, use_s, lib, monkeypatch):
     """(the sampler feed binds the batch-independent plan: every case here runs on it)"""
-    DR.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     host_fed_equals_feed(kind, 'cpu', use_s=use_s, library_size=lib)
-    assert DR.CALLS['norm_feed'] >= 6 and kernel_ref.CALLS['plain_feed'] == 0
+    assert kernel_ref.CALLS['norm_feed'] >= 6 and kernel_ref.CALLS['plain_feed'] == 0
 
 
 def combined_against_reference(dev='cpu', tol=((2e-5, 2e-6), None, (1e-4, 2e-5)), steps=3):
@@ -258,18 +258,18 @@ def combined_against_reference(dev='cpu', tol=((2e-5, 2e-6), None, (1e-4, 2e-5))
 
 
 def test_combined_riders_match_the_float64_model_reference(monkeypatch):
-    DR.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     combined_against_reference()
-    assert DR.CALLS['norm_feed'] > 0 and kernel_ref.CALLS['lib_rows'] > 0
+    assert kernel_ref.CALLS['norm_feed'] > 0 and kernel_ref.CALLS['lib_rows'] > 0
 
 
 def test_combined_riders_host_fed_equals_feed(monkeypatch):
-    DR.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     host_fed_equals_feed('drvae', 'cpu', extra=COMBINED)
 
 
 def test_adamw_step_host_fed_equals_feed(monkeypatch):
-    DR.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     host_fed_equals_feed('pvae', 'cpu', extra=dict(optim_alg='adamw', ema_decay=0.9))
 
 
@@ -414,13 +414,13 @@ def test_fit_and_evaluation_on_the_stand_ins(monkeypatch, tmp_path):
     """``fit`` with the normalised feed and ``library_size`` through host loaders (``DeviceBatcher``'s epoch mode needs a device:
     ``tests/test_gpu_depth.py``): finite losses, the evaluation's likelihood at the scaled mean, z1 free of depth afterwards"""
     from tests.test_fit import _loader
-    DR.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     tr, va = _counts_dataset('drvae', 48, 1), _counts_dataset('drvae', 16, 2)
     model = tiny_model('drvae', type_rec='nb', x_transform=NORM, library_size=True, epochs=2)
     model.w2log = lambda *a: None
     model.fit(_loader(tr, 16), _loader(va, 8), add_noise=True, verbose=False, early_stop=False,
               model_filename=str(tmp_path / 'm.pth'))
-    assert model.finished_training_iters == 2 * 3 and DR.CALLS['norm_feed'] > 0
+    assert model.finished_training_iters == 2 * 3 and kernel_ref.CALLS['norm_feed'] > 0
     perf, _ = model.evaluate_performance_on_dataset(va)
     assert all(np.isfinite(float(v)) for v in perf['losses'].values())
     res = model.forward(va.x1)

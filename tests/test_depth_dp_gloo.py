@@ -1,7 +1,6 @@
 """CPU, world_size 2 over gloo: the data-parallel train step of a negative-binomial model with the depth-normalised encoder
 input (``x_transform='log1p_norm'``, ``library_size=True``: the row's own total is row-local) reproduces the single-process step
-on the concatenated batch -- ``tests/test_counts_dp_gloo.py`` with the stand-in of ``tests/depth_ref.py`` over
-``tests/kernel_ref.py``'s."""
+on the concatenated batch -- ``tests/test_counts_dp_gloo.py`` with the normalised feed."""
 import os
 
 import numpy as np
@@ -18,11 +17,9 @@ SW = dict(type_rec='nb', x_transform='log1p_norm', library_size=True)
 
 def _install_refs():
     import drvae_amd.kernels as K
-    from tests import depth_ref as DR
     from tests import kernel_ref as R
     for name in R.FUNCTIONS:
         setattr(K, name, getattr(R, name))
-    K.batch_feed = DR.batch_feed
 
 
 def _run_steps(spec, params, batch, noises, counts, allreduce, lo=None, hi=None):
@@ -62,12 +59,11 @@ def _worker(rank, world, port, kind, q):
 
 @pytest.mark.parametrize('kind', ['drvae', 'vfae'])
 def test_two_ranks_equal_one_rank_with_the_normalised_feed(kind, monkeypatch):
-    from tests import depth_ref as DR
     from tests import kernel_ref
-    DR.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec, batch, noises, params = _case(kind)
     single = _run_steps(spec, params, batch, noises, None, None)
-    assert DR.CALLS['norm_feed'] > 0 and kernel_ref.CALLS['lib_rows'] > 0 and np.isfinite(single[1]).all()
+    assert kernel_ref.CALLS['norm_feed'] > 0 and kernel_ref.CALLS['lib_rows'] > 0 and np.isfinite(single[1]).all()
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
     port = _free_port()

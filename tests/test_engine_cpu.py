@@ -474,7 +474,8 @@ HOST_ONLY = {'gemm_force_tiling', 'gemm_set_option', 'x3_refusal', 'x3_pair_refu
 def test_the_stand_ins_cover_every_launcher_with_its_present_signature():
     """``tests/kernel_ref.py`` stays complete: every public launcher has a stand-in in ``FUNCTIONS`` with the same positional
     parameters, and every keyword the launcher takes binds to it (a launcher that forwards ``**kw`` is held to the keywords of
-    the function it forwards them to)"""
+    the function it forwards them to, and has to be listed in ``forwards``: keywords popped by hand are keywords this test
+    cannot see)"""
     import inspect
     import drvae_amd.kernels as K
     launchers = {n: f for n, f in vars(K).items()
@@ -483,13 +484,17 @@ def test_the_stand_ins_cover_every_launcher_with_its_present_signature():
     assert sorted(set(launchers) - HOST_ONLY - set(kernel_ref.FUNCTIONS)) == [], 'launchers without a stand-in'
     assert sorted(set(kernel_ref.FUNCTIONS) - set(launchers)) == [], 'stand-ins of no launcher'
     assert len(set(kernel_ref.FUNCTIONS)) == len(kernel_ref.FUNCTIONS)
-    forwards = {'gemm': K._gemm_desc, 'linear_bwd_pair': K._pair_descs}
+    # (``batch_masks`` hands its keywords on as ONE dict: ``_masks_desc`` names none to bind)
+    forwards = {'gemm': K._gemm_desc, 'linear_bwd_pair': K._pair_descs, 'batch_masks': K._masks_desc}
     P = inspect.Parameter
     positional = lambda sig: [p.name for p in sig.parameters.values() if p.kind in (P.POSITIONAL_ONLY, P.POSITIONAL_OR_KEYWORD)]
     for name in kernel_ref.FUNCTIONS:
         want, got = inspect.signature(launchers[name]), inspect.signature(getattr(kernel_ref, name))
         assert positional(got) == positional(want), name
         keywords = [p.name for p in want.parameters.values() if p.kind == P.KEYWORD_ONLY]
+        takes_kw = any(p.kind == P.VAR_KEYWORD for p in want.parameters.values())
+        assert takes_kw == (name in forwards), '%s: a **kw parameter hides keywords from this test unless `forwards` names ' \
+                                               'where they go' % name
         if name in forwards:
             keywords += [p.name for p in inspect.signature(forwards[name]).parameters.values()
                          if p.kind == P.KEYWORD_ONLY and not p.name.startswith('_')]

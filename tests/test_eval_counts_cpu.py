@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from tests import eval_counts_ref as ER
+from tests import kernel_ref
 from tests import ref64
 
 SHAPES = ((1, 1), (5, 13), (3, 16), (4, 257), (2, 1028))
@@ -108,9 +109,8 @@ def test_raw_moments_without_a_size_source_are_outside_in_every_centred_sum(kind
 # ------------------------------------------------------------------------------------------ 2. the stand-in
 def test_the_stand_in_wraps_kernel_ref_and_states_the_count_kinds(monkeypatch):
     import drvae_amd.kernels as K
-    from tests import kernel_ref
-    ER.install(monkeypatch)
-    assert K.recon_rows is ER.recon_rows and K.recon_finalize is kernel_ref.recon_finalize
+    kernel_ref.install(monkeypatch)
+    assert K.recon_rows is kernel_ref.recon_rows and K.recon_finalize is kernel_ref.recon_finalize
     x, mu, sd = torch.randn(4, 13), torch.randn(4, 13), torch.rand(4, 13) + 0.5
     a, b, la, lb = torch.zeros(4, 6), torch.zeros(4, 6), torch.zeros(4), torch.zeros(4)
     K.recon_rows(a, la, x, mu, sd)
@@ -204,7 +204,7 @@ def test_a_host_dataset_keeps_the_step_by_step_path(type_rec, sw, monkeypatch):
     from drvae_amd import fit as F
     from tests.test_counts_cpu import _counts_dataset
     from tests.test_fit import _tiny_model
-    ER.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     with warnings.catch_warnings():
         warnings.simplefilter('ignore')
         model = _tiny_model('drvae', device='cpu', type_rec=type_rec, add_noise_var=0.0, **sw)

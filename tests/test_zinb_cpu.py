@@ -158,7 +158,7 @@ def test_pi_to_zero_is_the_negative_binomial(grid):
 # --------------------------------------------------------------------------- 3. construction and refusals
 @pytest.mark.parametrize('kind', ['drvae', 'pvae', 'vfae'])
 def test_models_build_the_zero_inflated_decoder(kind, monkeypatch):
-    Z.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     from drvae_amd import blocks as blk
     from drvae_amd import engine as E
     model = tiny_model(kind, type_rec='zinb')
@@ -190,7 +190,7 @@ def test_models_build_the_zero_inflated_decoder(kind, monkeypatch):
         tiny_model(kind, type_rec='zinb', x_transform='sqrt')
     with pytest.raises(ValueError, match='count decoders'):
         tiny_model(kind, type_rec='binary', library_size=True)
-    assert 'zinb' in E.COUNT_DECODERS
+    assert E.REC_FAMILIES['zinb'].counts
     with warnings.catch_warnings(record=True) as w:
         warnings.simplefilter('always')
         drop = tiny_model(kind, type_rec='zinb', dropout_rate=0.25)
@@ -288,10 +288,10 @@ def run_against_reference(kind, variant, sw, dev='cpu', tol=((2e-5, 2e-6), (3e-4
 @pytest.mark.parametrize('variant,sw', CASES)
 @pytest.mark.parametrize('kind', ['drvae', 'pvae', 'vfae'])
 def test_fused_step_matches_the_float64_model_reference(kind, variant, sw, monkeypatch):
-    Z.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     run_against_reference(kind, variant, sw)
     lib = bool(SWITCHES[sw].get('library_size'))
-    assert (Z.CALLS['zinb_lib'] > 0) == lib and (Z.CALLS['zinb'] > 0) == (not lib)
+    assert (kernel_ref.CALLS['zinb_lib'] > 0) == lib and (kernel_ref.CALLS['zinb'] > 0) == (not lib)
     assert kernel_ref.CALLS['nb'] == 0 and kernel_ref.CALLS['other'] == 0 and kernel_ref.CALLS['lib_rows'] == 0
 
 
@@ -335,9 +335,9 @@ def combined_against_reference(dev='cpu', tol=((2e-5, 2e-6), None, (1e-4, 2e-5))
 
 
 def test_combined_riders_match_the_float64_model_reference(monkeypatch):
-    Z.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     combined_against_reference()
-    assert Z.CALLS['zinb_lib'] > 0
+    assert kernel_ref.CALLS['zinb_lib'] > 0
 
 
 def host_fed_equals_feed(kind, dev, extra=None, steps=3, captured=False):
@@ -378,9 +378,9 @@ def host_fed_equals_feed(kind, dev, extra=None, steps=3, captured=False):
 
 
 def test_host_fed_step_equals_feed_step_bit_for_bit(monkeypatch):
-    Z.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     host_fed_equals_feed('drvae', 'cpu')
-    assert kernel_ref.CALLS['split_feed'] >= 6 and Z.CALLS['zinb_lib'] >= 6
+    assert kernel_ref.CALLS['split_feed'] >= 6 and kernel_ref.CALLS['zinb_lib'] >= 6
 
 
 # ------------------------------------------------------------------------ 5. two ranks on gloo == one process
@@ -391,7 +391,6 @@ def _install_refs():
     import drvae_amd.kernels as K
     for name in kernel_ref.FUNCTIONS:
         setattr(K, name, getattr(kernel_ref, name))
-    K.rec_nll_rows = Z.rec_nll_rows
 
 
 def _dp_case(kind):
@@ -442,10 +441,10 @@ def _worker(rank, world, port, kind, q):
 def test_two_ranks_on_gloo_equal_one_process(monkeypatch):
     from tests.test_dp_gloo import _free_port
     kind = 'drvae'
-    Z.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     spec, batch, noises, params = _dp_case(kind)
     single = _run_steps(spec, params, batch, noises, None, None)
-    assert Z.CALLS['zinb_lib'] > 0 and np.isfinite(single[1]).all()
+    assert kernel_ref.CALLS['zinb_lib'] > 0 and np.isfinite(single[1]).all()
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
     port = _free_port()
@@ -498,14 +497,14 @@ def _other_step_log(kind, type_rec, install):
 @pytest.mark.parametrize('type_rec', ['nb', 'poisson', 'diag_gaussian'])
 @pytest.mark.parametrize('kind', ['drvae', 'pvae', 'vfae'])
 def test_other_decoders_record_the_launches_they_did(kind, type_rec):
-    """the launch list and every bit of three train steps are the same under ``kernel_ref.install`` alone and with this
-    feature's stand-in over it; the list itself is the parent's: its digest is pinned in ``tests/golden/zinb_launches.json``
+    """the launch list and every bit of three train steps are the same on two fresh installs of ``tests/kernel_ref.py`` (which
+    states this decoder's rows too); the list itself is the parent's: its digest is pinned in ``tests/golden/zinb_launches.json``
     (recorded on the parent commit by this very function), and the heads' launches are the ones these decoders always had --
     one ``linear_fwd`` for the decoder's last layer, the row launch with its own kind and its five keywords"""
     import hashlib
     import json
     a = _other_step_log(kind, type_rec, kernel_ref.install)
-    b = _other_step_log(kind, type_rec, Z.install)
+    b = _other_step_log(kind, type_rec, kernel_ref.install)
     assert a[0] == b[0] and a[4] == b[4] and all(torch.equal(x, y) for x, y in zip(a[1:4], b[1:4]))
     rec = [kw for n, kw in a[0] if n == 'rec_nll_rows']
     X = C.tiny_spec(kind).dim_x
@@ -523,7 +522,7 @@ def test_other_decoders_record_the_launches_they_did(kind, type_rec):
 # -------------------------------------------------------------------------------------------------- 7. fit
 def test_fit_runs_and_evaluates_step_by_step_without_warnings(monkeypatch, tmp_path):
     from tests.test_fit import _loader
-    Z.install(monkeypatch)
+    kernel_ref.install(monkeypatch)
     model = tiny_model('drvae', type_rec='zinb', x_transform='log1p', library_size=True, epochs=2)
     model.w2log = lambda *a: None
     tr, va = Z.zi_dataset('drvae', 40, 1), Z.zi_dataset('drvae', 24, 2)
@@ -541,4 +540,4 @@ def test_fit_runs_and_evaluates_step_by_step_without_warnings(monkeypatch, tmp_p
     with torch.no_grad():
         direct = float(model.decoder_x.logp_perx(va.x1, mu, th, lg, size=s).mean())
     assert perf['x1_ll'] == pytest.approx(direct, rel=1e-6)
-    assert Z.CALLS['zinb_lib'] > 0
+    assert kernel_ref.CALLS['zinb_lib'] > 0

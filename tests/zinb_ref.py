@@ -1,7 +1,7 @@
 """Float64 reference of the zero-inflated negative-binomial reconstruction rows (``dv_rec_nll_rows``, kinds ``DV_REC_ZINB`` /
 ``DV_REC_ZINB_LIB``; ``type_rec='zinb'``), the bound the kernel is held to, fp32 emulations -- a careful one and five faulty
-ones the bound catches --, a model-level float64 reference, a CPU stand-in of the launcher and a zero-inflated batch
-generator.  Test-only; builds on ``tests/nb_ref.py`` and ``tests/counts_ref.py``.
+ones the bound catches --, a model-level float64 reference and a zero-inflated batch generator (the launcher's CPU stand-in:
+``tests/kernel_ref.py``).  Test-only; builds on ``tests/nb_ref.py`` and ``tests/counts_ref.py``.
 
 With a = the dropout logit (third head, identity), pi = sigmoid(a), q = 1 - pi = sigmoid(-a), logNB the negative-binomial term
 at (m, theta) (m = mu, or s mu under ``library_size``), L0 = logNB(0) = -theta log1p(m / theta), rho = sigmoid(L0 - a):
@@ -181,38 +181,6 @@ def emulate_fp32(x, mu, theta, logit, shift=MU_SHIFT, s=None, zero='careful', dl
         gtz = np.where(pos, gt, gt * rho if rho_in_gt else gt).astype(f)
         gd = np.where(pos, -pi, gd0).astype(f)
     return ll, gmz, gtz, gd
-
-
-# ------------------------------------------------------------------------------------ the launcher's stand-in
-def rec_nll_rows(out, x, v, *, kind, shift=0.0, xidx=None, coef=None, dpre=None, library=False):
-    """CPU stand-in of ``kernels.rec_nll_rows``: ``kind='zinb'`` (``v`` = [mu | theta | logit], ``dpre`` 3X wide; with
-    ``library=True`` the scaled kind) from the float64 reference, rounded once; every other kind is ``tests/kernel_ref``'s.
-    Installed OVER ``kernel_ref.install`` (``install``)"""
-    from tests import kernel_ref
-    if kind != 'zinb':
-        return kernel_ref.rec_nll_rows(out, x, v, kind=kind, shift=shift, xidx=xidx, coef=coef, dpre=dpre, library=library)
-    CALLS['zinb_lib' if library else 'zinb'] += 1
-    xs = x[xidx.long()] if xidx is not None else x
-    X = x.shape[1]
-    assert v.shape[1] == 3 * X and (dpre is None or dpre.shape[1] == 3 * X)
-    ref = reference(xs, v[:, :X], v[:, X:2 * X], v[:, 2 * X:], coef=coef, shift=shift, library=library)
-    out.copy_(ref['rows'].to(out.dtype))
-    if coef is not None:
-        for i, k in enumerate(('gm', 'gt', 'gd')):
-            dpre[:, i * X:(i + 1) * X] = ref[k].to(dpre.dtype)
-
-
-CALLS = {'zinb': 0, 'zinb_lib': 0}
-
-
-def install(monkeypatch):
-    """``kernel_ref.install``, then this module's ``rec_nll_rows`` over it"""
-    from tests import kernel_ref
-    import drvae_amd.kernels as K
-    kernel_ref.install(monkeypatch)
-    monkeypatch.setattr(K, 'rec_nll_rows', rec_nll_rows)
-    for k in CALLS:
-        CALLS[k] = 0
 
 
 # ------------------------------------------------------------------------------- model-level float64 reference
