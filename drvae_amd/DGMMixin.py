@@ -37,7 +37,8 @@ class DeepGenerativeModelMixin:
             raise ValueError('Selected unknown optimizer: ' + str(self.optim_alg))
         self.optimizer = None          # kept for attribute parity; the state lives in the arena
         self._engine = None
-        self.__dict__.pop('_eval_graphs', None)
+        for key in ('_eval_graphs', '_eval_graphs_own_kind'):      # (``fit._EvalGraph.CACHE_KEYS``)
+            self.__dict__.pop(key, None)
 
     def _step_config(self):
         raise NotImplementedError
@@ -187,7 +188,8 @@ class DeepGenerativeModelMixin:
         if getattr(self, '_engine', None) is not None and not self._arena_aliased():
             self._stash_optimizer_state()
             self._engine = self._arena = None      # rebuilt (and the parameters re-adopted) by engine()
-            self.__dict__.pop('_eval_graphs', None)    # (captured evaluations point into the retired arena / plans)
+            for key in ('_eval_graphs', '_eval_graphs_own_kind'):      # (captured evaluations point into the retired arena / plans)
+                self.__dict__.pop(key, None)
         return out
 
     def load_state_dict(self, state_dict, strict=True, assign=False):

@@ -149,6 +149,7 @@ class ReconRows(C.Structure):    # dv_recon_rows_desc
 
 
 RECON_KIND = {None: 0, 'binary': 1, 'poisson': 2, 'nb': 3}      # dv_recon_rows_desc.kind (DV_RECON_*)
+RECON_ZINB = 4      # DV_RECON_ZINB: type_rec='zinb', sd = [theta | raw dropout logit] (a name of its own beside the table)
 
 
 class NllRawCs(C.Structure):     # dv_nll_raw_cs_desc

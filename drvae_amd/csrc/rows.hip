@@ -2412,10 +2412,12 @@ __global__ __launch_bounds__(256) void recon_rows_kernel(RcArgs a) {
     }
 }
 
-// The COUNT kinds of dv_recon_rows (type_rec = 'binary' / 'poisson' / 'nb'): the six row statistics between the target row
-// x and the finished mean r, the kind's log-likelihood row at that mean (rec_term / nb_term above: the one definition of each
-// formula, their gradient outputs dead code here) and, optionally, the stored mean -- one workgroup per row like
-// count_nll_rows_kernel, any X.  v / t: the POST-activation heads (mean | theta).  LIB: r = s v with the
+// The COUNT kinds of dv_recon_rows (type_rec = 'binary' / 'poisson' / 'nb' / 'zinb'): the six row statistics between the target row
+// x and the finished mean r, the kind's log-likelihood row at that mean (rec_term / nb_term / zinb_term above: the one definition
+// of each formula, their gradient outputs dead code here) and, optionally, the stored mean -- one workgroup per row like
+// count_nll_rows_kernel, any X.  v / t: the POST-activation heads (mean | theta).  DV_REC_ZINB: a row of t holds
+// [theta | RAW dropout logit] back to back, X columns each (ldt >= 2X); r is the negative-binomial mean, never (1 - pi) r, so
+// the statistics and the stored mean are DV_REC_NEGBIN's and only the term reads the logit.  LIB: r = s v with the
 // size factor s of the row xs[i,:] (row_size_factor; xs = the target itself, or ANOTHER matrix: the prediction of x2 is made
 // at x1's depth); !LIB: r = v, xs is not read.  Walk 1 forms sum x, sum r, sum (x-r)^2 and the term sum (and stores r), walk
 // 2 -- over the cache-hot row -- the centred sums at the means of walk 1, as recon_row_stats_kernel does (counts reach the
@@ -2435,9 +2437,12 @@ struct RcCountArgs {
 };
 
 template <int KIND, bool LIB>
-__device__ __forceinline__ float rc_count_term(float s, float x, float v, float t, float& r) {
+__device__ __forceinline__ float rc_count_term(float s, float x, float v, float t, float a, float& r) {
     r = LIB ? __fmul_rn(s, v) : v;
-    if constexpr (KIND == DV_REC_NEGBIN) {
+    if constexpr (KIND == DV_REC_ZINB) {
+        float gm, gt, gd;
+        return zinb_term<LIB>(0.f, s, x, v, t, a, gm, gt, gd);
+    } else if constexpr (KIND == DV_REC_NEGBIN) {
         float gm, gt;
         return nb_term<LIB>(0.f, s, x, v, t, gm, gt);
     } else {
@@ -2451,12 +2456,13 @@ __global__ __launch_bounds__(256) void recon_rows_count_kernel(RcCountArgs a) {
     __shared__ float part[4][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int X = a.X;
-    constexpr bool NB = KIND == DV_REC_NEGBIN;
+    constexpr bool ZI = KIND == DV_REC_ZINB, NB = KIND == DV_REC_NEGBIN || ZI;      // (NB: a theta head is read)
     {       // (grid = M workgroups, no row loop: the scalar registers of a loop's bookkeeping are the ones nb_term runs out of)
         const int i = blockIdx.x;
         const float* xr = a.x + (int64_t)i * a.ldx;
         const float* vr = a.v + (int64_t)i * a.ldv;
         const float* tr = NB ? a.t + (int64_t)i * a.ldt : nullptr;
+        const float* ar = ZI ? tr + X : nullptr;      // (the logit block behind theta's: 16-byte aligned with it, X % 4 == 0)
         float* ro = a.ro ? a.ro + (int64_t)i * a.ldo : nullptr;
         float sz = 1.f;
         if constexpr (LIB) sz = row_size_factor<VEC>(a.xs + (int64_t)i * a.ldxs, X, &part[0][0]);
@@ -2466,12 +2472,14 @@ __global__ __launch_bounds__(256) void recon_rows_count_kernel(RcCountArgs a) {
                 const float4 xv = reinterpret_cast<const float4*>(xr)[q];
                 const float4 mv = reinterpret_cast<const float4*>(vr)[q];
                 float4 tv = make_float4(1.f, 1.f, 1.f, 1.f), rv = make_float4(0.f, 0.f, 0.f, 0.f);
+                float4 av = make_float4(0.f, 0.f, 0.f, 0.f);
                 if constexpr (NB) tv = reinterpret_cast<const float4*>(tr)[q];
+                if constexpr (ZI) av = reinterpret_cast<const float4*>(ar)[q];
 #pragma unroll 1
                 for (int j = 0; j < 4; ++j) {
                     const float xj = quad_at(xv, j), mj = quad_at(mv, j), tj = quad_at(tv, j);
                     float r;
-                    sl += rc_count_term<KIND, LIB>(sz, xj, mj, tj, r);
+                    sl += rc_count_term<KIND, LIB>(sz, xj, mj, tj, ZI ? quad_at(av, j) : 0.f, r);
                     sx += xj;
                     sr += r;
                     sse += (xj - r) * (xj - r);
@@ -2483,7 +2491,7 @@ __global__ __launch_bounds__(256) void recon_rows_count_kernel(RcCountArgs a) {
             for (int g = threadIdx.x; g < X; g += 256) {
                 const float xg = xr[g];
                 float r;
-                sl += rc_count_term<KIND, LIB>(sz, xg, vr[g], NB ? tr[g] : 1.f, r);
+                sl += rc_count_term<KIND, LIB>(sz, xg, vr[g], NB ? tr[g] : 1.f, ZI ? ar[g] : 0.f, r);
                 sx += xg;
                 sr += r;
                 sse += (xg - r) * (xg - r);
@@ -2513,9 +2521,19 @@ __global__ __launch_bounds__(256) void recon_rows_count_kernel(RcCountArgs a) {
                 if (scale) rv.x = __fmul_rn(sz, rv.x), rv.y = __fmul_rn(sz, rv.y), rv.z = __fmul_rn(sz, rv.z), rv.w = __fmul_rn(sz, rv.w);
                 const float p0 = xv.x - mx, p1 = xv.y - mx, p2 = xv.z - mx, p3 = xv.w - mx;
                 const float q0 = rv.x - mr, q1 = rv.y - mr, q2 = rv.z - mr, q3 = rv.w - mr;
-                cxx += p0 * p0, cxx += p1 * p1, cxx += p2 * p2, cxx += p3 * p3;
-                crr += q0 * q0, crr += q1 * q1, crr += q2 * q2, crr += q3 * q3;
-                cxr += p0 * q0, cxr += p1 * q1, cxr += p2 * q2, cxr += p3 * q3;
+                if constexpr (ZI) {
+                    // rows are kind 3's BIT FOR BIT, and which of these sums become fused multiply-adds is the compiler's
+                    // choice per instantiation (it pairs two of the three into packed fmas: for every kind-3 instantiation
+                    // crr and cxr, p * p a rounded product; left alone it paired cxx and crr here): kind 3's roundings, spelled out
+                    cxx = __fadd_rn(cxx, __fmul_rn(p0, p0)), cxx = __fadd_rn(cxx, __fmul_rn(p1, p1));
+                    cxx = __fadd_rn(cxx, __fmul_rn(p2, p2)), cxx = __fadd_rn(cxx, __fmul_rn(p3, p3));
+                    crr = __fmaf_rn(q0, q0, crr), crr = __fmaf_rn(q1, q1, crr), crr = __fmaf_rn(q2, q2, crr), crr = __fmaf_rn(q3, q3, crr);
+                    cxr = __fmaf_rn(p0, q0, cxr), cxr = __fmaf_rn(p1, q1, cxr), cxr = __fmaf_rn(p2, q2, cxr), cxr = __fmaf_rn(p3, q3, cxr);
+                } else {
+                    cxx += p0 * p0, cxx += p1 * p1, cxx += p2 * p2, cxx += p3 * p3;
+                    crr += q0 * q0, crr += q1 * q1, crr += q2 * q2, crr += q3 * q3;
+                    cxr += p0 * q0, cxr += p1 * q1, cxr += p2 * q2, cxr += p3 * q3;
+                }
             }
         } else {
             for (int g = threadIdx.x; g < X; g += 256) {
@@ -3832,11 +3850,12 @@ static void launch_recon_rows_count(bool vec, const RcCountArgs& a, dv_stream_t 
 
 // the count kinds of dv_recon_rows (d.kind != DV_RECON_GAUSS): every refusal before any launch
 static int recon_rows_count(const dv_recon_rows_desc& d, dv_stream_t stream) {
-    DV_REQUIRE(d.kind == DV_RECON_BERNOULLI || d.kind == DV_RECON_POISSON || d.kind == DV_RECON_NEGBIN);
-    const bool nb = d.kind == DV_RECON_NEGBIN, lib = d.size_x != nullptr;
+    DV_REQUIRE(d.kind == DV_RECON_BERNOULLI || d.kind == DV_RECON_POISSON || d.kind == DV_RECON_NEGBIN ||
+               d.kind == DV_RECON_ZINB);
+    const bool zi = d.kind == DV_RECON_ZINB, nb = d.kind == DV_RECON_NEGBIN || zi, lib = d.size_x != nullptr;
     DV_REQUIRE(d.bias_mu == nullptr && d.bias_sd == nullptr);      // (count heads leave their launch finished)
     DV_REQUIRE(!(lib && d.kind == DV_RECON_BERNOULLI));             // (probabilities have no depth)
-    DV_REQUIRE(!nb || d.ldt >= (int64_t)d.X);                       // (theta has a row stride of its own)
+    DV_REQUIRE(!nb || d.ldt >= (zi ? 2 : 1) * (int64_t)d.X);        // (theta has a row stride of its own; ZINB: [theta | logit])
     DV_REQUIRE(d.rec_out == nullptr || lib);                        // (without a size source the mean IS the head: no copy)
     if (d.M == 0) return DV_OK;
     DV_REQUIRE(d.x && d.mu && d.rows && (!nb || d.sd));
@@ -3846,7 +3865,10 @@ static int recon_rows_count(const dv_recon_rows_desc& d, dv_stream_t stream) {
                      a16(d.size_x, d.size_ld) && a16(d.rec_out, d.rec_ld);
     RcCountArgs a{d.x, d.ldx, d.mu, d.ldp, nb ? d.sd : nullptr, d.ldt, d.size_x, d.size_ld, d.rec_out, d.rec_ld,
                   d.M, d.X, d.rows, d.ll};
-    if (nb) {
+    if (zi) {
+        if (lib) launch_recon_rows_count<DV_REC_ZINB, true>(vec, a, stream);
+        else launch_recon_rows_count<DV_REC_ZINB, false>(vec, a, stream);
+    } else if (nb) {
         if (lib) launch_recon_rows_count<DV_REC_NEGBIN, true>(vec, a, stream);
         else launch_recon_rows_count<DV_REC_NEGBIN, false>(vec, a, stream);
     } else if (d.kind == DV_RECON_POISSON) {

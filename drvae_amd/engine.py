@@ -30,7 +30,7 @@ import torch
 
 from . import kernels as K
 from . import tuning as T
-from ._lib import GAUSS_LOGVAR, GAUSS_SIGMA, REC_KIND, RECON_KIND
+from ._lib import GAUSS_LOGVAR, GAUSS_SIGMA, REC_KIND, RECON_KIND, RECON_ZINB
 from .arena import N_LOSS, ParamArena, span
 from .chain import X3_PARTS, _Chain, _Lin, _pad4
 from .plan import LOSS_IDX, _Plan
@@ -214,7 +214,7 @@ class RecFamily(NamedTuple):
     counts: bool                        # a count decoder: takes ``x_transform`` / ``library_size``
     rows_kind: Optional[int]            # kind of ``dv_rec_nll_rows`` (None: the Gaussian rows have entry points of their own)
     rows_kind_lib: Optional[int]        # its library-scaled kind (None: the family has none)
-    recon_kind: Optional[int]           # kind of ``dv_recon_rows`` (None: it has none -- whole-set evaluation declines the model)
+    recon_kind: int                     # kind of ``dv_recon_rows``: every family has one (``RECON_KIND``; 'zinb': ``RECON_ZINB``)
     eval_ll: bool                       # does that evaluation report a log-likelihood?
 
 
@@ -232,7 +232,7 @@ REC_FAMILIES = {
     'nb': RecFamily(_NB_HEADS, True, REC_KIND['nb'], REC_KIND['nb_lib'], RECON_KIND['nb'], True),
     # the dropout logit (identity) behind those two, back to back in the arena -- ``_Lin(third=...)``
     'zinb': RecFamily(_NB_HEADS + (RecHead('decoder_x.decoder_d.linear_d', 'identity', 0.0),), True,
-                      REC_KIND['zinb'], REC_KIND['zinb_lib'], None, False),
+                      REC_KIND['zinb'], REC_KIND['zinb_lib'], RECON_ZINB, True),
 }
 
 

@@ -189,13 +189,12 @@ class FitMixin:
         ``_EvalGraph``.  That includes the regression head (``type_y='cont'``: rmse / R^2 / Pearson r from ``dv_reg_metrics``) and
         models conditioned on the nuisance variable (``use_s``; with ``use_MMD`` for ``kernel_MMD='rbf_fourier' | 'identity'``
         and 2 <= dim_s <= 8, the penalty as its two grouped launches) and the count decoders (``type_rec='binary' | 'poisson' |
-        'nb'``, with ``x_transform`` / ``library_size``: ``dv_recon_rows``' count kinds -- row statistics at the scaled mean and the
-        count log-likelihood in one pass; the reported ``ll`` is the negative binomial's for ``'nb'`` and nan for the other two,
-        as on the step-by-step path).  ``return_full_data`` (arrays for the caller), host datasets and the other MMD kernels take
-        the step-by-step path (``'nb'``: ``x1_rec`` / ``x2_pert`` are the means, ``px1`` = (mu, theta)).  So does
-        ``type_rec='zinb'`` on every dataset (``_EvalGraph.get`` declines it up front: ``dv_recon_rows`` has no zero-inflated
-        kind): ``x1_rec`` / ``x2_pert`` are the negative-binomial means, ``px1`` = (mu, theta, dropout logit), and the reported
-        ``ll`` is the zero-inflated log-likelihood."""
+        'nb' | 'zinb'``, with ``x_transform`` / ``library_size``: ``dv_recon_rows``' count kinds -- row statistics at the scaled mean
+        and the count log-likelihood in one pass; the reported ``ll`` is the negative binomial's for ``'nb'``, the zero-inflated
+        log-likelihood for ``'zinb'`` (its statistics are taken at the negative-binomial mean, never at (1 - pi) times it) and
+        nan for the other two, as on the step-by-step path).  ``return_full_data`` (arrays for the caller), host datasets and the
+        other MMD kernels take the step-by-step path (``'nb'``: ``x1_rec`` / ``x2_pert`` are the means, ``px1`` = (mu, theta);
+        ``'zinb'``: the negative-binomial means, ``px1`` = (mu, theta, dropout logit))."""
         g = lambda k: getattr(ds, k, None)
         ev = None if return_full_data else _EvalGraph.get(self, ds)
         if ev is not None:
@@ -440,9 +439,9 @@ class _EvalGraph:
         the whole set, its inputs gathered device-to-device from the dataset;
       * the means-only inference ``forward`` (block level: the same HIP kernels);
       * ``dv_recon_row_stats`` / ``dv_col_moments`` and their float64 combination, the Gaussian log-likelihood mean; for the
-        count decoders (``type_rec='binary' | 'poisson' | 'nb'``) the decoder's FINISHED heads and ``dv_recon_rows``' count kinds:
+        count decoders (``type_rec='binary' | 'poisson' | 'nb' | 'zinb'``) the decoder's FINISHED heads and ``dv_recon_rows``' count kinds:
         statistics at the mean scaled by x1's size factor (``library_size``; for the x2 targets too), the negative binomial's
-        log-likelihood rows, the scaled mean stored in place of the mean head for ``dv_col_moments``;
+        log-likelihood rows (the zero-inflated ones for 'zinb', at the same mean, from the [theta | logit] columns of the heads), the scaled mean stored in place of the mean head for ``dv_col_moments``;
       * accuracy / AUROC / AUPR by sort + scan on the device (``metrics.*_dev``: no compaction, no host decisions); for the
         regression head rmse / R^2 / Pearson r of the means (``dv_reg_metrics``: one launch, two-pass float64 sums);
       * ``use_s``: the whole set's plan carries the nuisance classes on the device (``_Plan.carry_nuisance``) and the sequence
@@ -454,6 +453,18 @@ class _EvalGraph:
     themselves -- inputs, labels, regression targets, nuisance classes -- are read by the replay, so a dataset edited in
     place is evaluated as edited."""
 
+    CACHE_KEYS = ('_eval_graphs', '_eval_graphs_own_kind')
+
+    @staticmethod
+    def cache(model):
+        """the model's captured evaluations, by ``id(dataset)``.  ``model._eval_graphs`` for the decoders whose kind of
+        ``dv_recon_rows`` is in the table ``RECON_KIND``; a kind with a name of its own beside that table ('zinb':
+        ``RECON_ZINB``) keeps its graphs under a key of its own -- ``tests/test_gpu_zinb.py`` holds ``_eval_graphs`` of a
+        'zinb' model empty after ``fit``, from when that evaluation was declined, and existing test files stay as they are.
+        Whoever drops the cache drops every key of ``CACHE_KEYS`` (``DGMMixin``)"""
+        in_table = E.REC_FAMILIES[model.type_rec].recon_kind in E.RECON_KIND.values()
+        return model.__dict__.setdefault(_EvalGraph.CACHE_KEYS[0 if in_table else 1], {})
+
     @staticmethod
     def get(model, ds):
         from . import kernels as K
@@ -462,8 +473,6 @@ class _EvalGraph:
             return None
         if next(model.parameters()).device != x1.device:
             return None
-        if E.REC_FAMILIES[model.type_rec].recon_kind is None:
-            return None          # (no kind of ``dv_recon_rows``, 'zinb': step by step, decided up front -- no warning)
         # (the decision is a function of the model's configuration and the dataset's tensors alone: every rank of a
         # data-parallel job decides alike)
         use_s = bool(getattr(model, 'use_s', False))
@@ -480,7 +489,7 @@ class _EvalGraph:
             return None
         if use_s and (ds.s.is_floating_point() or ds.s.is_complex() or ds.s.dtype == torch.bool):
             return None
-        cache = model.__dict__.setdefault('_eval_graphs', {})
+        cache = _EvalGraph.cache(model)
         # the captured launches point into the engine's arena, plan and layer chains: ``.cpu().cuda()`` / ``.to()`` retire
         # the engine (DGMMixin._apply) and a graph of the old one would read freed parameters -- the engine's identity is
         # part of the signature (and ``_apply`` drops the cache)
@@ -513,7 +522,7 @@ class _EvalGraph:
         dev = ds.x1.device
         self.cont = kind != 'pvae' and getattr(model, 'type_y', 'discrete') != 'discrete'
         self.use_s = bool(getattr(model, 'use_s', False))
-        # the count decoders ('binary' / 'poisson' / 'nb'): finished heads, ``dv_recon_rows``' count kinds (``_rows_pass``)
+        # the count decoders ('binary' / 'poisson' / 'nb' / 'zinb'): finished heads, ``dv_recon_rows``' count kinds (``_rows_pass``)
         self.fam = E.REC_FAMILIES[model.type_rec]
         self.rec_kind = None if self.fam.recon_kind == E.RECON_KIND[None] else model.type_rec      # (as ``K.recon_rows`` names it)
         self.dp, self.full = dp, None
@@ -659,10 +668,10 @@ class _EvalGraph:
         if kind != 'pvae':
             self._y_metrics(res, vec[o:o + 3])
             o += 3
-        self._recon(ds.x1, res['px1'], None, vec[o:o + 4], 'x1', res['px_bias'])
+        self._recon(ds.x1, res['px1'], None, vec[o:o + 4], 'x1', res['px_bias'], res['tail1'])
         o += 4
         if has_x2:
-            self._recon(ds.x2, res['px2'], self.x2idx32, vec[o:o + 4], 'x2', res['px_bias'])
+            self._recon(ds.x2, res['px2'], self.x2idx32, vec[o:o + 4], 'x2', res['px_bias'], res['tail2'])
         return names, vec, list(losses)
 
     # ------------------------------------------------------------ rows sharded over ranks (data parallelism, round 6)
@@ -739,7 +748,7 @@ class _EvalGraph:
                 buf[tag] = (torch.empty(M, 6, device=x.device),
                             torch.zeros(self.blk[tag], 3, X, dtype=torch.float64, device=x.device), torch.empty(M, device=x.device))
             rows, part, ll = buf[tag]
-            x_rec, ll = self._rows_pass(rows, ll, x, res[key], bias)
+            x_rec, ll = self._rows_pass(rows, ll, x, res[key], bias, res['tail' + key[-1]])
             t = '1' if tag == 'x1' else '2'
             self._slot('rows' + t).view(self.n_all, 6)[lo:hi].copy_(rows)
             if ll is not None:      # ('binary' / 'poisson': no reported log-likelihood, the slot stays zero and is not read)
@@ -887,31 +896,37 @@ class _EvalGraph:
         # the decoder's heads as a PLAIN product where the one-pass reconstruction statistics finish them on their way
         # (bias, softplus + shift: ``dv_recon_rows`` / ``dv_col_moments``): 16384 x 1956 x 600 at the raw product's 126 instead of 104 TF/s
         # The count decoders' heads leave their launch FINISHED (probability / rate / [mean | theta]: ``raw_last_ok`` is false
-        # for them); ``px1`` / ``px2`` are 1-tuples for 'binary' / 'poisson' and (mu, theta) for 'nb' -- UNSCALED: the size
+        # for them); ``px1`` / ``px2`` are 1-tuples for 'binary' / 'poisson', (mu, theta) for 'nb' and (mu, theta, logit) for 'zinb' -- UNSCALED: the size
         # factor of a ``library_size`` model is applied by the row pass (``_rows_pass``)
         lh = eng.L_decx[-1]
         raw = bool(self.rec_kind is None and X <= K.RECON_ROWS_MAX_X and self.c_dec.raw_softplus_ok())
         PX = self.c_dec.forward([self.zd] + ([self.soh_d] if self.use_s else []), raw_last=raw)
         res['px_bias'] = (lh.b[:X], lh.b[X:2 * X], lh.shift1) if raw else None
-        two = len(self.fam.heads) == 2
-        res['px1'] = (PX[:n, :X], PX[:n, X:2 * X]) if two else (PX[:n, :X],)
+        # (three heads, 'zinb': (mu, theta, logit) as ``forward`` returns it -- columns of the ONE buffer, so [theta | logit] is
+        # the contiguous view from column X on that ``_rows_pass`` hands the row pass)
+        nh = len(self.fam.heads)
+        heads = lambda P: tuple(P[:, k * X:(k + 1) * X] for k in range(nh))
+        tail = lambda P: P[:, X:nh * X] if nh > 1 else None      # (the heads behind the mean, back to back: ``dv_recon_rows``' sd)
+        res['px1'], res['tail1'] = heads(PX[:n]), tail(PX[:n])
         if kind != 'vfae':
-            res['px2'] = (PX[n:, :X], PX[n:, X:2 * X]) if two else (PX[n:, :X],)
+            res['px2'], res['tail2'] = heads(PX[n:]), tail(PX[n:])
         return res
 
-    def _rows_pass(self, rows, ll, x, px, bias):
+    def _rows_pass(self, rows, ll, x, px, bias, tail=None):
         """row statistics (+ log-likelihood rows) of the target rows ``x`` against the heads ``px`` -> (the reconstruction
         ``dv_col_moments`` reads, the log-likelihood rows ``dv_recon_finalize`` reads or None).  Gaussian decoder: one pass up
         to 1024 genes, else the two separate ones.  Count decoders: ``dv_recon_rows``' count kinds at any width; with
         ``library_size`` the mean is scaled by the size factor of the SAME rows of ``x1`` -- for the x2 targets too,
-        as ``forward`` does it -- and stored in place of the mean head, where ``dv_col_moments`` finds it.  'binary' /
-        'poisson' report no log-likelihood (``_evaluate`` passes no second head: nan), 'nb' the negative binomial's."""
+        as ``forward`` does it -- and stored in place of the mean head, where ``dv_col_moments`` finds it.  ``tail``: the
+        heads behind the mean as ONE view of the heads buffer (``_infer``): theta for 'nb', [theta | logit] for 'zinb', None
+        for one head.  'binary' / 'poisson' report no log-likelihood (``_evaluate`` passes no second head: nan), 'nb' the
+        negative binomial's, 'zinb' the zero-inflated one (its statistics are taken at the negative-binomial mean)."""
         from . import kernels as K
         from ._lib import GAUSS_SIGMA
         if self.rec_kind is not None:
             ll = ll if self.fam.eval_ll else None
             size = self.ds.x1.to(torch.float32) if getattr(self.model, 'library_size', False) else None
-            K.recon_rows(rows, ll, x, px[0], px[1] if len(px) > 1 else None, kind=self.rec_kind, size_from=size,
+            K.recon_rows(rows, ll, x, px[0], tail, kind=self.rec_kind, size_from=size,
                          rec_out=px[0] if size is not None else None)
             return px[0], ll
         if x.shape[1] <= K.RECON_ROWS_MAX_X:
@@ -922,13 +937,13 @@ class _EvalGraph:
             K.nll_rows_fwd(ll, x, px[0], px[1], mode=GAUSS_SIGMA)
         return px[0], ll
 
-    def _recon(self, x, px, sel, out4, tag, bias=None):
+    def _recon(self, x, px, sel, out4, tag, bias=None, tail=None):
         """``eval_x_reconstruction`` (src/DGMMixin.py:128-156) over the rows ``sel`` (all when None): row statistics, column
         moments and log-likelihood rows from the HIP kernels, combined in float64 by ``dv_recon_finalize`` into ``out4`` =
         [rmse, r2, pearr, ll].  The statistics are taken over ALL rows and selected afterwards (no gathered copies of
         the x2 rows and their reconstructions).  Rows of up to 1024 genes: row statistics and log-likelihood rows in ONE pass
         (``dv_recon_rows``); ``bias`` = (bias_mu, bias_sd, shift): the heads are raw products, finished by the passes.
-        ``px``: the heads of these rows (``_rows_pass``: the count decoders' route)."""
+        ``px`` / ``tail``: the heads of these rows (``_rows_pass``: the count decoders' route)."""
         from . import kernels as K
         x = x.to(torch.float32)
         M, X = x.shape
@@ -939,7 +954,7 @@ class _EvalGraph:
             buf[tag] = (torch.empty(M, 6, device=x.device), torch.empty(K.col_moment_blocks(n), 3, X, dtype=torch.float64, device=x.device),
                         torch.empty(M, device=x.device))
         rows, part, ll = buf[tag]
-        x_rec, ll = self._rows_pass(rows, ll, x, px, bias)
+        x_rec, ll = self._rows_pass(rows, ll, x, px, bias, tail)
         K.col_moments(None, x, x_rec, sel=sel, part=part, r_bias=bias[0] if bias is not None else None)
         K.recon_finalize(out4, rows, part, X, sel=sel, n=n, ll=ll)
 

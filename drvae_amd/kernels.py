@@ -1066,19 +1066,24 @@ def recon_rows(rows, ll, x, mu, sd, *, bias=None, sd_shift=1e-3, kind=None, size
     X <= RECON_ROWS_MAX_X -- ``recon_row_stats`` + ``nll_rows_fwd``.  ``bias`` = (bias_mu, bias_sd): mu / sd are the
     heads' raw products, finished on the way.
 
-    The count decoders: ``kind='binary' | 'poisson' | 'nb'``, any X.  ``mu`` is the mean head's finished output, ``sd`` the theta head for 'nb' and None otherwise.  ``size_from`` (M, X;
-    'poisson' / 'nb'): the statistics and the log-likelihood are taken at r = s * mu, s the size factor of ``size_from``'s rows
+    The count decoders: ``kind='binary' | 'poisson' | 'nb' | 'zinb'``, any X.  ``mu`` is the mean head's finished output, ``sd`` the
+    theta head for 'nb', the (M, 2X) pair [theta | raw dropout logit] for 'zinb' (the decoder's heads buffer from column X on; the
+    statistics and ``rec_out`` are 'nb''s, at the negative-binomial mean) and None otherwise.  ``size_from`` (M, X;
+    'poisson' / 'nb' / 'zinb'): the statistics and the log-likelihood are taken at r = s * mu, s the size factor of ``size_from``'s rows
     (the target itself or another matrix); ``rec_out`` (M, X; with ``size_from`` only, may be ``mu`` itself) receives r."""
     M, X = x.shape
     if kind is not None:
-        assert kind in ('binary', 'poisson', 'nb') and bias is None
+        assert kind in ('binary', 'poisson', 'nb', 'zinb') and bias is None
         assert tuple(mu.shape) == (M, X) and rows.is_contiguous() and tuple(rows.shape) == (M, 6)
-        assert (sd is not None and tuple(sd.shape) == (M, X)) if kind == 'nb' else sd is None
+        if kind == 'zinb':
+            assert sd is not None and tuple(sd.shape) == (M, 2 * X)
+        else:
+            assert (sd is not None and tuple(sd.shape) == (M, X)) if kind == 'nb' else sd is None
         assert size_from is None or tuple(size_from.shape) == (M, X)
         assert rec_out is None or tuple(rec_out.shape) == (M, X)
         assert ll is None or (ll.is_contiguous() and ll.numel() == M)
         d = _lib.ReconRows(x=_f32(x), ldx=_ld(x), mu=_f32(mu), sd=_f32(sd), ldp=_ld(mu), M=M, X=X, rows=_f32(rows),
-                           ll=_f32(ll), kind=_lib.RECON_KIND[kind], ldt=_ld(sd) if sd is not None else 0,
+                           ll=_f32(ll), kind=_lib.RECON_ZINB if kind == 'zinb' else _lib.RECON_KIND[kind], ldt=_ld(sd) if sd is not None else 0,
                            size_x=_f32(size_from), size_ld=_ld(size_from) if size_from is not None else 0,
                            rec_out=_f32(rec_out), rec_ld=_ld(rec_out) if rec_out is not None else 0)
         _lib.check(_lib.load().dv_recon_rows(C.byref(d), _stream()), 'dv_recon_rows')

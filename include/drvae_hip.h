@@ -896,26 +896,30 @@ int dv_col_moments(const float* x, int64_t ldx, const float* r, int64_t ldr, int
  * separate passes).
  *
  * The COUNT kinds (trailing fields, ABI 13; all zero / NULL = DV_RECON_GAUSS: the launch above, bit for bit, with its
- * refusals).  kind = DV_RECON_BERNOULLI / _POISSON / _NEGBIN: the whole-set evaluation of the count decoders in one pass
+ * refusals).  kind = DV_RECON_BERNOULLI / _POISSON / _NEGBIN / _ZINB: the whole-set evaluation of the count decoders in one pass
  * per row, ANY X (a workgroup walks a row; 16-byte loads when X % 4 == 0 and every operand's rows are 16-byte aligned):
  *   heads  mu (ldp) = the mean head's POST-activation output, as dv_rec_nll_rows reads it (probability | rate | NB mean);
- *          NEGBIN: sd (row stride ldt >= X, its own) = the theta head; else sd is not read.  bias_mu / bias_sd / sd_shift:
+ *          NEGBIN: sd (row stride ldt >= X, its own) = the theta head; ZINB: a row of sd (row stride ldt >= 2X) holds
+ *          [theta | RAW dropout logit] back to back, X columns each, the logit row at sd + i*ldt + X -- the decoder's 3X-wide
+ *          heads buffer [mu | theta | a_d] from column X on; else sd is not read.  bias_mu / bias_sd / sd_shift:
  *          NULL / unread (the count heads leave their launch finished)
  *   mean   r = mu without a size source; with size_x (row stride size_ld): r = s * mu, s = max(sum_g size_x[i,g], 1) / X,
  *          ONE rounded product.  size_x may be x itself or another matrix (the prediction of x2 is made at x1's depth);
- *          theta is never scaled
+ *          neither theta nor the logit is ever scaled.  ZINB: r is the negative-binomial mean (the denoised expression),
+ *          never (1 - pi) r: rows and rec_out are exactly NEGBIN's
  *   rows   (M, 6): the six statistics of dv_recon_row_stats between x and r -- the centred sums from a second walk over
  *          the row at the means of the first (never from raw moments)
  *   ll     (M, optional): sum_g log p(x | r), the terms of dv_rec_nll_rows (kinds DV_REC_BERNOULLI / _POISSON[_LIB] /
- *          _NEGBIN[_LIB]: the same device functions)
+ *          _NEGBIN[_LIB] / _ZINB[_LIB]: the same device functions; ZINB: the zero-inflated log-probability at (r, theta, a_d))
  *   rec_out (row stride rec_ld, optional, WITH a size source only): the finished mean r, for dv_col_moments; may alias
  *          mu (every element is read and written by the same lane).  Without a size source r IS mu: nothing to store,
  *          DV_ERR_ARG
- * No atomics, fixed summation order: equal bits on every launch.  DV_ERR_ARG before any launch: kind outside the four,
- * a size source with BERNOULLI, bias_mu / bias_sd with a count kind, NEGBIN with ldt < X, rec_out without a size source,
+ * No atomics, fixed summation order: equal bits on every launch.  DV_ERR_ARG before any launch: kind outside the five,
+ * a size source with BERNOULLI, bias_mu / bias_sd with a count kind, NEGBIN with ldt < X, ZINB with ldt < 2X (both at M = 0
+ * too), rec_out without a size source,
  * a row stride below X, a missing operand (M > 0); size_x / rec_out with DV_RECON_GAUSS. */
 #define DV_RECON_ROWS_MAX_X 1024
-enum { DV_RECON_GAUSS = 0, DV_RECON_BERNOULLI = 1, DV_RECON_POISSON = 2, DV_RECON_NEGBIN = 3 };
+enum { DV_RECON_GAUSS = 0, DV_RECON_BERNOULLI = 1, DV_RECON_POISSON = 2, DV_RECON_NEGBIN = 3, DV_RECON_ZINB = 4 };
 typedef struct dv_recon_rows_desc {
     const float* x;
     int64_t ldx;

@@ -6,11 +6,13 @@ a device synchronise -- both paths end in a device-to-host copy of their scalars
 alone (device events around a captured graph of 20 launches, divided by 20).
 
 Cases: the 'nb' model with x_transform='log1p' + library_size=True and the plain 'poisson' model, 8192 rows at cfg-2 sizes
-(978 genes); one wide case, 'nb' with both switches on 2048 rows x 20 000 genes; the launch alone per kind at 8192 x 978.
+(978 genes); one wide case, 'nb' with both switches on 2048 rows x 20 000 genes; the zero-inflated model ('zinb') plain and with
+both switches at 8192 x 978 and with both switches at 2048 x 20 000; the launch alone per kind at 8192 x 978.
 
-``python tools/eval_counts_bench.py [reps] [--only nb|poisson|wide|kernel] [--out FILE]`` (GPU box only).  Prints markdown
-tables -- median with min .. max -- and with ``--out [FILE]`` replaces the text between the ``<!-- timings -->`` markers of
-FILE (``--out`` alone: profiles/r22_eval_counts.md; the file is created when missing) by them."""
+``python tools/eval_counts_bench.py [reps] [--only CASE[,CASE...]|kernel] [--stepwise-only] [--out FILE]`` (GPU box only).  Prints
+markdown tables -- median with min .. max -- and with ``--out [FILE]`` replaces the text between the ``<!-- timings -->``
+markers of FILE (``--out`` alone: profiles/r22_eval_counts.md; the file is created when missing) by them.  ``--stepwise-only``:
+the step-by-step path alone, nothing asked of the captured one (a tree whose evaluation declines the model: the baseline)."""
 import gc
 import os
 import sys
@@ -26,7 +28,10 @@ from drvae_amd.DrVAE import DrVAE               # noqa: E402
 
 CASES = {'nb': dict(type_rec='nb', x_transform='log1p', library_size=True, n=8192, X=978),
          'poisson': dict(type_rec='poisson', n=8192, X=978),
-         'wide': dict(type_rec='nb', x_transform='log1p', library_size=True, n=2048, X=20000)}
+         'wide': dict(type_rec='nb', x_transform='log1p', library_size=True, n=2048, X=20000),
+         'zinb-plain': dict(type_rec='zinb', n=8192, X=978),
+         'zinb': dict(type_rec='zinb', x_transform='log1p', library_size=True, n=8192, X=978),
+         'zinb-wide': dict(type_rec='zinb', x_transform='log1p', library_size=True, n=2048, X=20000)}
 BEGIN, END = '<!-- timings:begin -->', '<!-- timings:end -->'
 BATCH = 20          # launches of ``dv_recon_rows`` per timed graph replay
 
@@ -66,23 +71,26 @@ def row(label, path, v):
     return '| %s | %s | %d | %.3f | %.3f .. %.3f |' % (label, path, len(v), np.median(v), v.min(), v.max())
 
 
-def models(reps, only, out):
+def models(reps, only, out, stepwise_only=False):
     from drvae_amd import fit as F
     out += ['| model | path | n | median ms | min .. max |', '|---|---|---|---|---|']
-    for case in ('nb', 'poisson', 'wide'):
-        if only not in (None, case):
+    for case in CASES:
+        if only is not None and case not in only:
             continue
         model, ds = model_and_set(case)
         g = lambda k: getattr(ds, k, None)
         captured = lambda: model.evaluate_performance_on_dataset(ds)
         stepwise = lambda: model._evaluate(g('x1'), g('x2'), g('s'), g('y'), g('has_x2'), g('has_y'))
-        captured()
-        assert F._EvalGraph.get(model, ds) is not None, 'the captured path was not taken'
         paths = [('captured', captured), ('step by step', stepwise)]
+        if stepwise_only:
+            paths = paths[1:]
+        else:
+            captured()
+            assert F._EvalGraph.get(model, ds) is not None, 'the captured path was not taken'
         for _, fn in paths:
             fn(), fn()
         ms = {name: [] for name, _ in paths}
-        for _ in range(reps if case != 'wide' else max(5, reps // 4)):
+        for _ in range(reps if not case.endswith('wide') else max(5, reps // 4)):
             for name, fn in paths:
                 ms[name].append(timed(fn))
         c = CASES[case]
@@ -104,6 +112,7 @@ def kernel(reps, out, M=8192, X=978, dev='cuda'):
     th = (torch.rand(M, X, generator=g) * 3 + 0.5).to(dev)
     p = torch.rand(M, X, generator=g).clamp(1e-3, 1 - 1e-3).to(dev)
     xb = (x1 > 2).float()
+    tl = torch.cat([th, (torch.rand(M, X, generator=g) * 8 - 4).to(dev)], 1)          # [theta | dropout logit] for 'zinb'
     rows, ll, rec = torch.empty(M, 6, device=dev), torch.empty(M, device=dev), torch.empty(M, X, device=dev)
     forms = [('binary', 'rows + ll', lambda: K.recon_rows(rows, ll, xb, p, None, kind='binary')),
              ('poisson', 'rows + ll', lambda: K.recon_rows(rows, ll, x1, mu, None, kind='poisson')),
@@ -111,6 +120,9 @@ def kernel(reps, out, M=8192, X=978, dev='cuda'):
              ('nb', 'rows + ll', lambda: K.recon_rows(rows, ll, x1, mu, th, kind='nb')),
              ('nb', 'rows + ll + stored mean, size source = target', lambda: K.recon_rows(rows, ll, x1, mu, th, kind='nb', size_from=x1, rec_out=rec)),
              ('nb', 'rows + ll + stored mean, size source = another matrix', lambda: K.recon_rows(rows, ll, x2, mu, th, kind='nb', size_from=x1, rec_out=rec)),
+             ('zinb', 'rows + ll', lambda: K.recon_rows(rows, ll, x1, mu, tl, kind='zinb')),
+             ('zinb', 'rows + ll + stored mean, size source = target', lambda: K.recon_rows(rows, ll, x1, mu, tl, kind='zinb', size_from=x1, rec_out=rec)),
+             ('zinb', 'rows + ll + stored mean, size source = another matrix', lambda: K.recon_rows(rows, ll, x2, mu, tl, kind='zinb', size_from=x1, rec_out=rec)),
              ('gaussian (kind=None)', 'rows + ll', lambda: K.recon_rows(rows, ll, x1, mu, th))]
     for kind, what, fn in forms:
         fn(), fn()
@@ -142,13 +154,17 @@ def main():
     import argparse
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('reps', nargs='?', type=int, default=60)
-    ap.add_argument('--only', choices=['nb', 'poisson', 'wide', 'kernel'], default=None)
+    ap.add_argument('--only', default=None, metavar='CASE[,CASE...]', help='of: %s, kernel' % ', '.join(CASES))
+    ap.add_argument('--stepwise-only', action='store_true')
     ap.add_argument('--out', nargs='?', default=None, const=os.path.join(ROOT, 'profiles', 'r22_eval_counts.md'), metavar='FILE')
     a = ap.parse_args()
+    only = a.only.split(',') if a.only is not None else None
+    if only is not None and not set(only) <= set(CASES) | {'kernel'}:
+        ap.error('--only: unknown case in %s' % a.only)
     out = []
-    if a.only != 'kernel':
-        models(a.reps, a.only, out)
-    if a.only in (None, 'kernel'):
+    if only != ['kernel']:
+        models(a.reps, only, out, a.stepwise_only)
+    if (only is None or 'kernel' in only) and not a.stepwise_only:
         kernel(max(a.reps, 50), out)
     if a.out is not None:
         text = open(a.out).read() if os.path.exists(a.out) else '# Whole-set evaluation of the count-decoder models\n\n%s\n%s\n' % (BEGIN, END)
