@@ -31,7 +31,10 @@ class VFAE(ELBOModel):
     per dataset by ``fit`` / ``DeviceBatcher.bind``): the encoder reads log1p(x) (``'log1p_norm'``: the depth-normalised
     log1p(x / s), s the row's own size factor below) while the likelihood keeps the raw counts
     without training noise, and every decoder mean of a row is multiplied by the row's observed size factor
-    max(sum_g x_g, 1) / dim_x.  Attributes until the engine is built, like the schedules.  Labelled extensions."""
+    max(sum_g x_g, 1) / dim_x.  Attributes until the engine is built, like the schedules.  Labelled extensions.
+    ``dispersion`` (default 'gene-cell' | 'gene'; ``type_rec='nb'`` / ``'zinb'`` only, anything else raises ``ValueError``): 'gene' replaces the
+    theta head by ONE inverse dispersion per gene, the parameter ``decoder_x.decoder_t.raw_theta`` (theta = softplus + 1e-3, started at
+    0); ``px1`` / ``px2`` keep their shape, theta expanded to (rows, dim_x).  Labelled extension."""
     kind = 'vfae'
     fit_patience = 40       # src/VFAE.py:536
 
@@ -44,7 +47,7 @@ class VFAE(ELBOModel):
                  random_seed=12345, log_txt=None, weight_norm=False, device=None, matmul_precision='fp32',
                  max_grad_norm=None, anneal_kl=False, anneal_kl_itermax=100, anneal_yloss=False, anneal_yloss_itermax=1,
                  anneal_learning_rate=False, anneal_lr_itermax=3000, ema_decay=None,
-                 x_transform=None, library_size=False):
+                 x_transform=None, library_size=False, dispersion='gene-cell'):
         super().__init__()
         args = dict(locals())
         args.pop('self')

@@ -155,7 +155,9 @@ RECON_ZINB = 4      # DV_RECON_ZINB: type_rec='zinb', sd = [theta | raw dropout 
 class NllRawCs(C.Structure):     # dv_nll_raw_cs_desc
     _fields_ = [('coef', _p), ('x', _p), ('ldx', _i64), ('xidx', _p), ('mu', _p), ('sd', _p), ('ldp', _i64), ('M', _i32),
                 ('X', _i32), ('shift', _f), ('out_part', _p), ('chunks', _i32), ('dmu', _p), ('dsd', _p), ('ldd', _i64),
-                ('bias_mu', _p), ('bias_sd', _p), ('ws', _p), ('ldw', _i64), ('sd_off', _i64), ('row_blocks', _i32)]
+                ('bias_mu', _p), ('bias_sd', _p), ('ws', _p), ('ldw', _i64), ('sd_off', _i64), ('row_blocks', _i32),
+                # trailing: the count kinds with a gene-wise dispersion (all zero / NULL: the Gaussian pass as it was)
+                ('kind', _i32), ('theta_raw', _p), ('size', _p)]
 
 
 class MmdGrouped(C.Structure):   # dv_mmd_grouped_desc

@@ -50,6 +50,8 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         # raw-count inputs (EXTENSIONS, count decoders only; ``StepConfig.x_transform`` / ``library_size``): the encoder reads
         # log1p(x) while the likelihood keeps the raw counts; every decoder mean is scaled by the row's observed size factor
         x_transform, library_size = args.pop('x_transform', None), args.pop('library_size', False)
+        # 'gene-cell' | 'gene': a theta head, or one inverse dispersion per gene ('nb' / 'zinb'; ``StepConfig.dispersion``)
+        self.dispersion = E.check_dispersion(args.pop('dispersion', 'gene-cell'), args.get('type_rec'))
         for k, v in args.items():
             setattr(self, k, v)
         for k, v in anneal.items():
@@ -147,7 +149,8 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         dec = {'diag_gaussian': blk.DiagGaussianSigmaModule, 'binary': blk.BernoulliDecoder,
                'poisson': blk.PoissonDecoder, 'nb': blk.NegativeBinomialDecoder,
                'zinb': blk.ZeroInflatedNegativeBinomialDecoder}[self.type_rec]      # src/DrVAE.py:124-129
-        self.decoder_x = dec([Z1] + s_in, self.dim_h_de_x, self.dim_x, **hp)
+        gene = dict(dispersion='gene') if self.dispersion == 'gene' else {}       # ('gene-cell': the call as it was)
+        self.decoder_x = dec([Z1] + s_in, self.dim_h_de_x, self.dim_x, **hp, **gene)
 
     def _dropout_notes(self):
         """Hidden-layer dropout in the fused train step (``dropout_rate`` > 0): every hidden activation of every block is
@@ -172,7 +175,7 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         # (one head in the fused step: the classifier -- a regression head's log-variance is fixed, its layer is not in the
         # step's chain (``FusedStep.L_clf``) -- and a Bernoulli / Poisson decoder; the negative binomial has two, its
         # zero-inflated form three: all of them read the one mask)
-        x_heads = len(E.REC_FAMILIES[self.type_rec].heads)
+        x_heads = len(E.rec_family(self.type_rec, self.dispersion).heads)
         two_heads = [n for n, h in hidden.items() if len(h) and n != 'encoder_y' and not (n == 'decoder_x' and x_heads == 1)]
         undropped = [n for n, h in hidden.items() if not len(h)]
         three = ' (all three heads of the zero-inflated decoder_x)' if x_heads == 3 and 'decoder_x' in two_heads else ''
@@ -250,7 +253,8 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
             mmd_rate=float(getattr(self, 'mmd_rate', 1.)), kernel_MMD=getattr(self, 'kernel_MMD', 'rbf_fourier'),
             prior_y=None if (getattr(self, 'prior_y', None) is None or isinstance(getattr(self, 'prior_y', None), str))
             else tuple(float(v) for v in self.prior_y), matmul=self._matmul, dropout_rate=float(self.dropout_rate),
-            max_grad_norm=self._max_grad_norm, ema_decay=self.ema_decay, **self._counts_config(), **self._anneal_config())
+            max_grad_norm=self._max_grad_norm, ema_decay=self.ema_decay, **self._counts_config(), **self._anneal_config(),
+            **(dict(dispersion='gene') if self.dispersion == 'gene' else {}))
 
     # ---------------------------------------------------------------- inference
     @torch.no_grad()

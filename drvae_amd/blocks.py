@@ -481,6 +481,25 @@ class PoissonDecoder(_SingleHeadDecoder):
         return torch.poisson(_size_scaled(rate, size))
 
 
+class GeneDispersion(nn.Module):
+    """EXTENSION (``dispersion='gene'``): the gene-wise inverse dispersion of the 'nb' / 'zinb' decoders, one value per gene
+    shared by all rows -- the parameter ``raw_theta`` (genes,), started at 0, with theta = softplus(raw_theta) + shift: log 2 +
+    1e-3, what the theta head gives at a zero product.  Called with a row count it returns theta as a (rows, genes) broadcast
+    view: the block-level path materialises nothing, and autograd's gradient of ``raw_theta`` is the column sum of the theta
+    block's gradient.  (The fused step reads the vector inside its row pass: ``gene_rows``.)"""
+
+    def __init__(self, n_genes, shift):
+        super().__init__()
+        self.shift = shift
+        self.raw_theta = nn.Parameter(torch.zeros(n_genes))
+
+    def theta(self):
+        return F.softplus(self.raw_theta) + self.shift
+
+    def forward(self, rows):
+        return self.theta().unsqueeze(0).expand(rows, -1)
+
+
 class NegativeBinomialDecoder(nn.Module):
     """EXTENSION (``type_rec='nb'``; no counterpart in the reference): the data decoder for overdispersed counts, a negative
     binomial with mean ``mu`` and inverse dispersion ``theta`` (Var = mu + mu^2 / theta; theta -> inf is the Poisson decoder).
@@ -496,15 +515,23 @@ class NegativeBinomialDecoder(nn.Module):
     MU_SHIFT, THETA_SHIFT = 1e-6, 1e-3
 
     def __init__(self, input_dims, hidden_dims, reconstruction_dim, nonlin='softplus', weight_norm=False,
-                 batch_norm=False, dropout_rate=0., input_dropout_rates=None):
+                 batch_norm=False, dropout_rate=0., input_dropout_rates=None, dispersion='gene-cell'):
+        """``dispersion='gene'`` (default 'gene-cell': the theta head): ONE inverse dispersion per gene, shared by all rows --
+        ``decoder_t`` then holds no Linear but the (reconstruction_dim,) parameter ``raw_theta`` (``GeneDispersion``)"""
         super().__init__()
+        if dispersion not in ('gene-cell', 'gene'):
+            raise ValueError("dispersion must be 'gene-cell' or 'gene', not %r" % (dispersion,))
+        self.dispersion = dispersion
         self.nnet = MLP(input_dims=input_dims, hidden_dims=hidden_dims, nonlin=nonlin, weight_norm=weight_norm,
                         batch_norm=batch_norm, dropout_rate=dropout_rate, input_dropout_rates=input_dropout_rates)
         self.reconstruction_dim = reconstruction_dim
         make = lyr.WeightNormLinear if weight_norm else nn.Linear
         width = _trunk_width(input_dims, hidden_dims)
         # (mean head first, then theta: the parameter-init RNG stream and the arena's head pair follow this order)
-        for head, lin in (('decoder_m', 'linear_m'), ('decoder_t', 'linear_t')):
+        # (a gene-wise theta: the vector in FRONT of the heads, the order of ``engine.param_shapes`` -- it consumes no random draw)
+        if dispersion == 'gene':
+            self.decoder_t = GeneDispersion(reconstruction_dim, self.THETA_SHIFT)
+        for head, lin in (('decoder_m', 'linear_m'), ('decoder_t', 'linear_t'))[:1 if dispersion == 'gene' else 2]:
             mods = OrderedDict()
             if dropout_rate > 0.:
                 mods['dropout'] = Dropout(p=dropout_rate)
@@ -516,10 +543,16 @@ class NegativeBinomialDecoder(nn.Module):
             h = [seq.dropout(h[0] if len(h) == 1 else torch.cat(h, 1))]
         return _apply_linear(getattr(seq, lin), h, act='softplus', shift=shift)
 
+    def _theta(self, h, mu):
+        """the second element of the decoder's output: the theta head over ``h``, or the gene-wise theta as (rows, genes)"""
+        if self.dispersion == 'gene':
+            return self.decoder_t(mu.shape[0])
+        return self._head_out(self.decoder_t, 'linear_t', h, self.THETA_SHIFT)
+
     def forward(self, inputs):
         h = self.nnet.features(inputs)
-        return (self._head_out(self.decoder_m, 'linear_m', h, self.MU_SHIFT),
-                self._head_out(self.decoder_t, 'linear_t', h, self.THETA_SHIFT))
+        mu = self._head_out(self.decoder_m, 'linear_m', h, self.MU_SHIFT)
+        return mu, self._theta(h, mu)
 
     def logp_perx(self, x, mu, theta, size=None):
         """``size`` (rows,): the rows' size factors -- the mean is size * mu, theta as it is (``library_size`` models)"""
@@ -557,9 +590,10 @@ class ZeroInflatedNegativeBinomialDecoder(NegativeBinomialDecoder):
     the mixture's mean is (1 - pi) mu."""
 
     def __init__(self, input_dims, hidden_dims, reconstruction_dim, nonlin='softplus', weight_norm=False,
-                 batch_norm=False, dropout_rate=0., input_dropout_rates=None):
+                 batch_norm=False, dropout_rate=0., input_dropout_rates=None, dispersion='gene-cell'):
         super().__init__(input_dims, hidden_dims, reconstruction_dim, nonlin=nonlin, weight_norm=weight_norm,
-                         batch_norm=batch_norm, dropout_rate=dropout_rate, input_dropout_rates=input_dropout_rates)
+                         batch_norm=batch_norm, dropout_rate=dropout_rate, input_dropout_rates=input_dropout_rates,
+                         dispersion=dispersion)
         # (third, behind mean and theta: the parameter-init RNG stream and the arena's head triple follow this order)
         mods = OrderedDict()
         if dropout_rate > 0.:
@@ -571,9 +605,8 @@ class ZeroInflatedNegativeBinomialDecoder(NegativeBinomialDecoder):
     def forward(self, inputs):
         h = self.nnet.features(inputs)
         hd = [self.decoder_d.dropout(h[0] if len(h) == 1 else torch.cat(h, 1))] if hasattr(self.decoder_d, 'dropout') else h
-        return (self._head_out(self.decoder_m, 'linear_m', h, self.MU_SHIFT),
-                self._head_out(self.decoder_t, 'linear_t', h, self.THETA_SHIFT),
-                _apply_linear(self.decoder_d.linear_d, hd))
+        mu = self._head_out(self.decoder_m, 'linear_m', h, self.MU_SHIFT)
+        return mu, self._theta(h, mu), _apply_linear(self.decoder_d.linear_d, hd)
 
     def logp_perx(self, x, mu, theta, logit, size=None):
         """``size`` (rows,): the rows' size factors -- the mean is size * mu; theta and the logit as they are"""

@@ -1213,6 +1213,123 @@ __global__ __launch_bounds__(256) void count_nll_rows_kernel(int kind, float shi
     }
 }
 
+// The count rows with a GENE-WISE inverse dispersion (dv_gauss_nll_rows_raw_cs with a count kind; dispersion='gene'): theta is
+// one (X,) pre-activation vector shared by all rows, not a head.  A workgroup owns one chunk of up to 1024 genes and one block
+// of R rows; a thread owns four genes of the chunk for all of those rows -- one quad on 16-byte loads and stores (VEC: X % 4
+// == 0, aligned rows; the dispatcher checks), else the genes tid + 256 j.  It forms its four thetas once, walks the rows in
+// ascending order with four theta-gradient accumulators in registers and stores them once, to ws[row block, gene]: no atomics,
+// the caller sums the blocks (dv_colsum).  The per-element term is nb_term / zinb_term above, unchanged: ONE copy of its code,
+// walked four times (j is uniform; see count_nll_rows_kernel).  The row partial out_part[r, chunk]: per-thread partials in
+// index order, the wave sum, the four waves as (p0 + p1) + (p2 + p3).
+// theta = softplus(raw) + DV_NB_THETA_SHIFT is formed in double and rounded once: four per thread per launch, and the
+// value is then the correctly rounded one a float64 reference can name (the row terms' bounds are stated at the fp32 theta the
+// formula receives).
+// LIB: 0 = no size factor; 1 = formed here per row (row_size_factor: chunks == 1, the workgroup reads the whole row anyway;
+// also stored to `size` when given); 2 = read from `size`, which a launch in front has filled (size_rows_kernel: with more
+// than one chunk every chunk would walk the whole target row again).
+struct GeneRowsArgs {
+    const float* coef; const float* x; int64_t ldx; const int32_t* xidx; const float* mu; const float* logit; int64_t ldp;
+    int M, X; float shift; float* out_part; int chunks; float* dmu; float* dlogit; int64_t ldd; const float* theta_raw;
+    float* ws; int64_t ldw; float* size; int R;
+};
+
+__device__ __forceinline__ float gene_theta(float raw) {
+    const double a = (double)raw;
+    return (float)(fmax(a, 0.0) + log1p(exp(-fabs(a))) + (double)DV_NB_THETA_SHIFT);
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void size_rows_kernel(const float* __restrict__ x, int64_t ldx,
+                                                        const int32_t* __restrict__ xidx, int M, int X,
+                                                        float* __restrict__ size) {
+    __shared__ float part[4];
+    for (int r = blockIdx.x; r < M; r += gridDim.x) {
+        const float s = row_size_factor<VEC>(x + (int64_t)(xidx ? xidx[r] : r) * ldx, X, part);
+        if (threadIdx.x == 0) size[r] = s;
+    }
+}
+
+template <bool ZI, int LIB, bool VEC>
+__global__ __launch_bounds__(256) void gene_rows_kernel(GeneRowsArgs a) {
+    __shared__ float part[2][4];
+    __shared__ float spart[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int chunk = blockIdx.x;
+    const int gbase = chunk * 1024 + (VEC ? 4 * tid : tid);       // gene of slot j: gbase + (VEC ? j : 256 j)
+    constexpr int kStep = VEC ? 1 : 256;
+    const int r0 = (int)blockIdx.y * a.R, r1 = r0 + a.R < a.M ? r0 + a.R : a.M;
+    const bool grad = a.dmu != nullptr;
+    const bool quad_on = VEC && gbase < a.X;                      // (X % 4 == 0: a quad is inside or outside as a whole)
+    float4 th = make_float4(1.f, 1.f, 1.f, 1.f), tacc = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int g = gbase + j * kStep;
+        if (g < a.X) quad_put(th, j, gene_theta(a.theta_raw[g]));
+    }
+    for (int r = r0; r < r1; ++r) {
+        const float* xr = a.x + (int64_t)(a.xidx ? a.xidx[r] : r) * a.ldx;
+        const float* mr = a.mu + (int64_t)r * a.ldp;
+        const float* lr = ZI ? a.logit + (int64_t)r * a.ldp : nullptr;
+        float sz = 1.f;
+        if constexpr (LIB == 1) {
+            sz = row_size_factor<VEC>(xr, a.X, spart);
+            if (a.size != nullptr && tid == 0) a.size[r] = sz;
+        } else if constexpr (LIB == 2) {
+            sz = a.size[r];
+        }
+        const float c = grad ? a.coef[r] : 0.f;
+        float4 xv = make_float4(0.f, 0.f, 0.f, 0.f), mv = xv, lv = xv, gmv = xv, gdv = xv;
+        if (quad_on) {
+            const int q = gbase >> 2;
+            xv = reinterpret_cast<const float4*>(xr)[q];
+            mv = reinterpret_cast<const float4*>(mr)[q];
+            if constexpr (ZI) lv = reinterpret_cast<const float4*>(lr)[q];
+        }
+        float acc = 0.f;
+#pragma unroll 1
+        for (int j = 0; j < 4; ++j) {
+            const int g = gbase + j * kStep;
+            if (g < a.X) {
+                const float xe = VEC ? quad_at(xv, j) : xr[g], ve = VEC ? quad_at(mv, j) : mr[g];
+                float gm, gt, gd = 0.f;
+                if constexpr (ZI)
+                    acc += zinb_term<LIB != 0>(a.shift, sz, xe, ve, quad_at(th, j), VEC ? quad_at(lv, j) : lr[g], gm, gt, gd);
+                else
+                    acc += nb_term<LIB != 0>(a.shift, sz, xe, ve, quad_at(th, j), gm, gt);
+                if (grad) {
+                    quad_put(tacc, j, quad_at(tacc, j) + c * gt);
+                    if constexpr (VEC) {
+                        quad_put(gmv, j, c * gm);
+                        if constexpr (ZI) quad_put(gdv, j, c * gd);
+                    } else {
+                        a.dmu[(int64_t)r * a.ldd + g] = c * gm;
+                        if constexpr (ZI) a.dlogit[(int64_t)r * a.ldd + g] = c * gd;
+                    }
+                }
+            }
+        }
+        if (quad_on && grad) {
+            const int q = gbase >> 2;
+            reinterpret_cast<float4*>(a.dmu + (int64_t)r * a.ldd)[q] = gmv;
+            if constexpr (ZI) reinterpret_cast<float4*>(a.dlogit + (int64_t)r * a.ldd)[q] = gdv;
+        }
+        acc = dv_wave_sum_all(acc);
+        // two slots, taken in turn: the next row's partials land in the other one, so one barrier per row is enough
+        float* p = part[(r - r0) & 1];
+        if (lane == 0) p[wave] = acc;
+        __syncthreads();
+        if (tid == 0) a.out_part[(int64_t)r * a.chunks + chunk] = (p[0] + p[1]) + (p[2] + p[3]);
+    }
+    if (grad) {
+        float* w = a.ws + (int64_t)blockIdx.y * a.ldw;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int g = gbase + j * kStep;
+            if (g < a.X) w[g] = quad_at(tacc, j);
+        }
+    }
+}
+
 __global__ void nll_rows_bwd_kernel(const float* __restrict__ coef, const float* __restrict__ x, int64_t ldx,
                                     const int32_t* __restrict__ xidx, const float* __restrict__ mu,
                                     const float* __restrict__ sd, int64_t ldp, int M, int X, int mode, int sd_act,
@@ -3398,9 +3515,62 @@ extern "C" int dv_gauss_nll_rows_fwdbwd(const float* coef, const float* x, int64
     DV_RETURN_LAUNCH();
 }
 
+template <bool ZI, int LIB>
+static void launch_gene_rows(bool vec, const GeneRowsArgs& a, int row_blocks, dv_stream_t stream) {
+    const dim3 grid(a.chunks, row_blocks), block(256);
+    if (vec)
+        hipLaunchKernelGGL((gene_rows_kernel<ZI, LIB, true>), grid, block, 0, ST(stream), a);
+    else
+        hipLaunchKernelGGL((gene_rows_kernel<ZI, LIB, false>), grid, block, 0, ST(stream), a);
+}
+
+// the count kinds of dv_gauss_nll_rows_raw_cs (gene-wise theta): every refusal in front of the first launch, at M == 0 too
+static int gene_rows(const dv_nll_raw_cs_desc& d, dv_stream_t stream) {
+    const bool zi = d.kind == DV_REC_ZINB || d.kind == DV_REC_ZINB_LIB;
+    const bool lib = d.kind == DV_REC_NEGBIN_LIB || d.kind == DV_REC_ZINB_LIB;
+    DV_REQUIRE(zi || lib || d.kind == DV_REC_NEGBIN);
+    DV_REQUIRE(d.M >= 0 && d.X >= 1);
+    DV_REQUIRE(d.theta_raw && d.x && d.mu && d.out_part);
+    DV_REQUIRE(zi ? d.sd != nullptr : d.sd == nullptr);
+    DV_REQUIRE(d.bias_mu == nullptr && d.bias_sd == nullptr && d.sd_off == 0);
+    DV_REQUIRE(d.chunks == (d.X + 1023) / 1024);
+    DV_REQUIRE(d.row_blocks >= 1 && d.row_blocks <= (d.M > 1 ? d.M : 1) && d.row_blocks <= 65535);
+    DV_REQUIRE(d.ldx >= d.X && d.ldp >= d.X);
+    const bool grad = d.dmu != nullptr;
+    if (grad) {
+        DV_REQUIRE(d.ws && d.coef && d.ldw >= d.X && d.ldd >= d.X);
+        DV_REQUIRE(zi ? d.dsd != nullptr : d.dsd == nullptr);
+    } else {
+        DV_REQUIRE(d.ws == nullptr && d.dsd == nullptr);
+    }
+    DV_REQUIRE(!(lib && d.chunks > 1 && d.size == nullptr));
+    if (d.M == 0) return DV_OK;
+    auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const bool vec_x = d.X % 4 == 0 && a16(d.x) && d.ldx % 4 == 0;
+    const bool vec = vec_x && a16(d.mu) && d.ldp % 4 == 0 && (!zi || a16(d.sd)) &&
+                     (!grad || (a16(d.dmu) && d.ldd % 4 == 0 && (!zi || a16(d.dsd))));
+    const int rows = (d.M + d.row_blocks - 1) / d.row_blocks;
+    const GeneRowsArgs a{d.coef, d.x, d.ldx, d.xidx, d.mu, d.sd, d.ldp, d.M, d.X, d.shift, d.out_part, d.chunks, d.dmu, d.dsd,
+                         d.ldd, d.theta_raw, d.ws, d.ldw, d.size, rows};
+    const int libmode = !lib ? 0 : d.chunks == 1 ? 1 : 2;
+    if (libmode == 2) {       // the size factor of every row first: two launches behind one call, as dv_grad_norm_clip is
+        const dim3 grid(grid_for(d.M, 1, 4096)), block(256);
+        if (vec_x)
+            hipLaunchKernelGGL(size_rows_kernel<true>, grid, block, 0, ST(stream), d.x, d.ldx, d.xidx, d.M, d.X, d.size);
+        else
+            hipLaunchKernelGGL(size_rows_kernel<false>, grid, block, 0, ST(stream), d.x, d.ldx, d.xidx, d.M, d.X, d.size);
+    }
+    static constexpr decltype(&launch_gene_rows<false, 0>) launch[2][3] = {
+        {launch_gene_rows<false, 0>, launch_gene_rows<false, 1>, launch_gene_rows<false, 2>},
+        {launch_gene_rows<true, 0>, launch_gene_rows<true, 1>, launch_gene_rows<true, 2>}};
+    launch[zi][libmode](vec, a, d.row_blocks, stream);
+    DV_RETURN_LAUNCH();
+}
+
 extern "C" int dv_gauss_nll_rows_raw_cs(const dv_nll_raw_cs_desc* dsc, dv_stream_t stream) {
     DV_REQUIRE(dsc != nullptr);
     const dv_nll_raw_cs_desc& d = *dsc;
+    if (d.kind != 0) return gene_rows(d, stream);
     DV_REQUIRE(d.M >= 0 && d.X >= 4 && d.X % 4 == 0);
     if (d.M == 0) return DV_OK;
     const bool fwd_only = d.dmu == nullptr;        // (evaluation: row terms only)

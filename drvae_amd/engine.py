@@ -28,6 +28,7 @@ from typing import List, NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
+from . import gene_rows as G
 from . import kernels as K
 from . import tuning as T
 from ._lib import GAUSS_LOGVAR, GAUSS_SIGMA, REC_KIND, RECON_KIND, RECON_ZINB
@@ -139,9 +140,16 @@ class StepConfig:
     # ``dv_batch_feed`` in its split form on every path.  Both off: nothing of this exists, the step as it ever was
     x_transform: Optional[str] = None
     library_size: bool = False
+    # EXTENSION (no counterpart in the reference), 'nb' / 'zinb' only: where the inverse dispersion theta comes from.
+    #   'gene-cell' (default): a decoder head of its own, one theta per (cell, gene) -- the step as it ever was
+    #   'gene'               : ONE theta per gene, shared by all cells -- the (dim_x,) parameter ``GENE_THETA`` in the arena,
+    #                          theta_g = softplus(raw_theta_g) + 1e-3; the theta head and its three products do not exist, the
+    #                          row pass reads the vector (``gene_rows``) and its gradient is a column sum
+    dispersion: str = 'gene-cell'
 
     def __post_init__(self):
         check_counts_config(self.x_transform, self.library_size, self.type_rec, 'StepConfig.')
+        check_dispersion(self.dispersion, self.type_rec, 'StepConfig.')
         self.library_size = bool(self.library_size)
         if self.optim_alg not in OPTIM_ALGS:
             raise ValueError('StepConfig.optim_alg must be one of %s, not %r' % (OPTIM_ALGS, self.optim_alg))
@@ -170,8 +178,8 @@ class StepConfig:
 
     @property
     def rec(self):
-        """the reconstruction family of ``type_rec`` (``REC_FAMILIES``)"""
-        return REC_FAMILIES[self.type_rec]
+        """the reconstruction family of ``type_rec`` (``REC_FAMILIES``; ``dispersion='gene'``: ``GENE_FAMILIES``)"""
+        return rec_family(self.type_rec, self.dispersion)
 
     @property
     def split_x(self):
@@ -216,6 +224,7 @@ class RecFamily(NamedTuple):
     rows_kind_lib: Optional[int]        # its library-scaled kind (None: the family has none)
     recon_kind: int                     # kind of ``dv_recon_rows``: every family has one (``RECON_KIND``; 'zinb': ``RECON_ZINB``)
     eval_ll: bool                       # does that evaluation report a log-likelihood?
+    gene: bool = False                  # theta is the gene-wise vector ``GENE_THETA``, not a head (``GENE_FAMILIES``)
 
 
 # the negative binomial's two heads, mean then inverse dispersion: both softplus + their own shift
@@ -234,6 +243,32 @@ REC_FAMILIES = {
     'zinb': RecFamily(_NB_HEADS + (RecHead('decoder_x.decoder_d.linear_d', 'identity', 0.0),), True,
                       REC_KIND['zinb'], REC_KIND['zinb_lib'], RECON_ZINB, True),
 }
+
+
+# ``dispersion='gene'``: the families without the theta head -- 'nb' the mean head alone (launched as the Poisson decoder's single
+# softplus head is), 'zinb' the pair [mean | dropout logit], back to back in the arena; theta is the (dim_x,) parameter below
+DISPERSIONS = ('gene-cell', 'gene')
+GENE_THETA = 'decoder_x.decoder_t.raw_theta'
+GENE_FAMILIES = {
+    'nb': RecFamily(_NB_HEADS[:1], True, REC_KIND['nb'], REC_KIND['nb_lib'], RECON_KIND['nb'], True, True),
+    'zinb': RecFamily((_NB_HEADS[0], REC_FAMILIES['zinb'].heads[2]), True, REC_KIND['zinb'], REC_KIND['zinb_lib'], RECON_ZINB,
+                      True, True),
+}
+
+
+def rec_family(type_rec, dispersion='gene-cell'):
+    """the ``RecFamily`` of a decoder: ``REC_FAMILIES[type_rec]``, or its gene-wise form"""
+    return GENE_FAMILIES[type_rec] if dispersion == 'gene' else REC_FAMILIES[type_rec]
+
+
+def check_dispersion(dispersion, type_rec, prefix=''):
+    """``dispersion`` as a checked value; ValueError for an unknown one and for 'gene' on a decoder without a theta"""
+    if dispersion not in DISPERSIONS:
+        raise ValueError("%sdispersion must be 'gene-cell' or 'gene', not %r" % (prefix, dispersion))
+    if dispersion == 'gene' and type_rec not in GENE_FAMILIES:
+        raise ValueError("%sdispersion='gene' is for the decoders with an inverse dispersion (type_rec=%s), not type_rec=%r"
+                         % (prefix, ' / '.join(repr(k) for k in GENE_FAMILIES), type_rec))
+    return dispersion
 
 
 def check_counts_config(x_transform, library_size, type_rec, prefix=''):
@@ -305,6 +340,10 @@ def param_shapes(cfg):
         gauss(cfg.top_name, Z1 + Y, cfg.h_en_z3, Z3)
         gauss('decoder_z1', Z3 + Y, cfg.h_de_z1, Z1)
     n = trunk('decoder_x.nnet', Z1 + S, cfg.h_de_x)
+    if cfg.rec.gene:
+        # in FRONT of the heads: they stay the tail of the arena (the half of the sweep the side chain may take,
+        # ``_side_adam_layout``), and the vector lies in the half that follows the whole backward pass
+        out[GENE_THETA] = (X,)
     for h in cfg.rec.heads:
         lin(h.prefix, n, X)
     return out
@@ -947,7 +986,9 @@ class FusedStep(StepSchedule):
         if self._tail.late_fork:      # (chip-filling step: the side chain starts HERE, next to the row pass below)
             self.branch.fork()
         lh = p.c_decx.layers[-1]
-        if r.nll == 'rec':     # Bernoulli / Poisson / (zero-inflated) negative-binomial rows (+ the gradient w.r.t. the head's pre-activation in a train step)
+        if r.nll == 'gene':    # gene-wise theta: the heads are [mean] or [mean | dropout logit], theta is read from its vector
+            self._gene_rows(PX, train)
+        elif r.nll == 'rec':   # Bernoulli / Poisson / (zero-inflated) negative-binomial rows (+ the gradient w.r.t. the head's pre-activation in a train step)
             K.rec_nll_rows(p.NLL, p.XT if cfg.split_x else p.XIN, PX, kind=cfg.type_rec, shift=cfg.rec.heads[0].shift,
                            xidx=p.tgt, coef=p.c_nll if train else None, dpre=p.DPX if train else None, **self._lib_kw())
         elif r.nll in ('raw_cs', 'raw_cs_eval'):
@@ -964,6 +1005,24 @@ class FusedStep(StepSchedule):
         else:                          # 'fwd' | 'raw_eval' (gene counts that are no multiple of 4 -- 978: the wave-per-row pass)
             raw = dict(bias=(lh.b[:X], lh.b[X:]), sd_shift=lh.shift1) if r.raw_last else {}
             K.nll_rows_fwd(p.NLL, p.XIN, PX[:, :X], PX[:, X:], mode=GAUSS_SIGMA, xidx=p.tgt, **raw)
+
+    def _gene_rows(self, PX, grads):
+        """the reconstruction rows of a ``dispersion='gene'`` model (``gene_rows.gene_rows``): per-chunk row partials into
+        ``NLLG``; ``grads``: and the heads' gradients into ``DPX``, the per-block column sums of theta's into ``GWS`` -- summed
+        into the vector's gradient by ``_gene_theta_grad``, behind the decoder's backward products"""
+        cfg, p, X = self.cfg, self.plan, self.cfg.dim_x
+        zi = cfg.type_rec == 'zinb'
+        gk = dict(coef=p.c_nll, dmu=p.DPX[:, :X], dlogit=p.DPX[:, X:] if zi else None, ws=p.GWS) if grads else \
+            dict(row_blocks=p.GWS.shape[0])
+        G.gene_rows(p.NLLG, p.XT if cfg.split_x else p.XIN, PX[:, :X], self.arena.p(GENE_THETA), kind=cfg.type_rec,
+                    shift=cfg.rec.heads[0].shift, logit=PX[:, X:] if zi else None, xidx=p.tgt, library=cfg.library_size,
+                    size=p.GSIZE, **gk)
+
+    def _gene_theta_grad(self):
+        """d loss / d raw_theta = the column sum of ``GWS`` over the row blocks.  Only the optimiser sweep (and a gradient
+        exchange) reads it, so it is no launch in front of the decoder's data gradient: it follows the decoder's backward
+        products, in front of the point where the decoder's gradients count as final"""
+        K.colsum(self.arena.g(GENE_THETA), self.plan.GWS[:, :self.cfg.dim_x])
 
     def _side_forward(self, Qmu, Qlv, Z1blk, r, mid=None, mid_park=None):
         """fprop first: it only needs the z1 samples, so (dual-graph schedule) it can start before
@@ -1266,7 +1325,9 @@ class FusedStep(StepSchedule):
         # ---- main chain: reconstruction terms, d/d(mu, pre-softplus) straight from the per-row
         # coefficients, then back through the decoder (the three big GEMMs)
         PX = p.c_decx.out[-1]
-        if not self.fuse_bwd and cfg.type_rec != 'diag_gaussian':
+        if not self.fuse_bwd and cfg.rec.gene:
+            self._gene_rows(PX, True)
+        elif not self.fuse_bwd and cfg.type_rec != 'diag_gaussian':
             K.rec_nll_rows(p.NLL, p.XT if cfg.split_x else p.XIN, PX, kind=cfg.type_rec, shift=cfg.rec.heads[0].shift,
                            xidx=p.tgt, coef=p.c_nll, dpre=p.DPX, **self._lib_kw())
         elif not self.fuse_bwd:
@@ -1283,6 +1344,8 @@ class FusedStep(StepSchedule):
         p.c_decx.backward(p.DPX, p.dec_in, [[(p.DZDEC, 1.0, 0.0)]] + [None] * (len(p.dec_in) - 1),
                           publish_after_last=self.sync.pub('rows', self.step_dev) if t.side_loss else None,
                           db_last_done=r.db_done, x3_last=r.x3, drop=self._drop)
+        if cfg.rec.gene:
+            self._gene_theta_grad()
         if p.DZMMD is not None:
             # model-level MMD penalty (use_s extension): its gradient w.r.t. the z1 / z2 samples was computed in
             # forward() through the block-level MMD kernels (see ``_mmd_penalty``)

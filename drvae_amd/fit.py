@@ -905,6 +905,24 @@ class _EvalGraph:
         # (three heads, 'zinb': (mu, theta, logit) as ``forward`` returns it -- columns of the ONE buffer, so [theta | logit] is
         # the contiguous view from column X on that ``_rows_pass`` hands the row pass)
         nh = len(self.fam.heads)
+        if getattr(m, 'dispersion', 'gene-cell') == 'gene':
+            # a gene-wise theta: ``dv_recon_rows`` has no broadcast operand, so the finished theta row is written into a theta
+            # block once per replay, as one row repeated (M x X words written and read), with the decoder's logit columns copied
+            # behind it for 'zinb' -- then the recon kinds run as they are, and the numbers are ``_evaluate``'s key by key
+            # (``fam`` is the family of ``type_rec`` as the recon kinds know it -- mean, theta[, logit]; the decoder's own heads
+            # buffer is [mean] or [mean | logit])
+            rows_all, nt = PX.shape[0], nh - 1
+            if not hasattr(self, 'gtail'):
+                self.gtail = torch.zeros(rows_all, nt * X, device=PX.device)
+            T_ = self.gtail
+            T_[:, :X].copy_(m.decoder_x.decoder_t(rows_all))
+            if nt > 1:
+                T_[:, X:].copy_(PX[:, X:2 * X])
+            heads = lambda lo, hi: (PX[lo:hi, :X],) + tuple(T_[lo:hi, k * X:(k + 1) * X] for k in range(nt))
+            res['px1'], res['tail1'] = heads(0, n), T_[:n]
+            if kind != 'vfae':
+                res['px2'], res['tail2'] = heads(n, rows_all), T_[n:]
+            return res
         heads = lambda P: tuple(P[:, k * X:(k + 1) * X] for k in range(nh))
         tail = lambda P: P[:, X:nh * X] if nh > 1 else None      # (the heads behind the mean, back to back: ``dv_recon_rows``' sd)
         res['px1'], res['tail1'] = heads(PX[:n]), tail(PX[:n])

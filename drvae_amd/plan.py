@@ -6,6 +6,7 @@ import math
 import numpy as np
 import torch
 
+from . import gene_rows
 from . import kernels as K
 from .arena import N_LOSS
 from .chain import X3_PARTS, _Chain, _pad4
@@ -212,6 +213,12 @@ class _Plan:
         if nll_cs:
             chunks, rbs = K.nll_raw_cs_shape(Md, X)
             self.NLLC, self.NLLWS = zf(Md, chunks), zf(rbs, 2 * X)
+        # a gene-wise theta (``StepConfig.dispersion='gene'``): the row pass's per-chunk partials, its per-row-block column sums of
+        # theta's gradient (``gene_rows.shape``: the host's row-block rule) and the rows' size factors (library-scaled kinds)
+        if cfg.rec.gene:
+            chunks, rbs = gene_rows.shape(max(Md, 1), X)
+            self.NLLG, self.GWS = zf(Md, chunks), zf(rbs, _pad4(X))
+            self.GSIZE = zf(max(Md, 1)) if cfg.library_size else None
         # opt-in split-bf16 products (``StepConfig.matmul``): exactly one layer changes arithmetic -- the decoder's heads
         # layer where it takes the raw-heads route -- and whether it does is decided HERE, once (raises if its products are
         # not ones ``dv_gemm_x3`` / ``dv_gemm_split`` runs); every other product of the step stays fp32.  The rungs differ in

@@ -127,6 +127,9 @@ TRAIN, LOSS, EVALUATE = 'train pass', 'loss pass, separate backward', 'evaluatio
 # table in DESIGN.md section 6 says when each is taken
 NLL_ROUTES = {'heads': 'NLLP', 'rec': 'NLL', 'raw_cs_eval': 'NLLC', 'raw_eval': 'NLL', 'raw_cs': 'NLLC', 'fwdbwd': 'NLL',
               'fwd': 'NLL'}
+# ... and beside that table (``tests/test_heads_route_cpu.py`` holds every key of it to a 'gene-cell' configuration that takes
+# it): the one route of the ``dispersion='gene'`` models -- ``gene_rows`` at every size, per-chunk partials into ``NLLG``
+GENE_ROUTE, GENE_ROWS = 'gene', 'NLLG'
 
 
 class HeadsRoute(NamedTuple):
@@ -169,7 +172,9 @@ def heads_route(eng, plan, kind):
     raw_last = bool(raw_ok and not (train and epi) and kind != LOSS)
     if gauss and train and epi:      # train step: the heads' launch emits the rows' partials and d/d(mu, pre-softplus)
         nll = 'heads'
-    elif not gauss:                  # Bernoulli / Poisson / (zero-inflated) negative-binomial rows, at every size (``dv_rec_nll_rows``)
+    elif cfg.rec.gene:               # 'nb' / 'zinb' with a gene-wise theta, at every size (``gene_rows``: per-chunk partials)
+        nll = GENE_ROUTE
+    elif not gauss:                 # Bernoulli / Poisson / (zero-inflated) negative-binomial rows, at every size (``dv_rec_nll_rows``)
         nll = 'rec'
     elif raw_last and nll_cs:        # the row pass finishes the heads (+ in a train step: their bias gradient's column sums)
         nll = 'raw_cs' if train else 'raw_cs_eval'
@@ -180,7 +185,8 @@ def heads_route(eng, plan, kind):
     # (``z3_in_heads``: evaluation passes over many fprop rows -- whole-set evaluation: 24576 -- take the plain product + row pass)
     return HeadsRoute(sample_epi=epi, fprop_from_heads=bool(epi and fprop),
                       z3_in_heads=bool(eng.fuse_heads and (train or p.Mf < 8192)),
-                      fprop_tail=bool(train and eng.fuse_heads and fprop and eng.clf_small), nll=nll, rows=NLL_ROUTES[nll],
+                      fprop_tail=bool(train and eng.fuse_heads and fprop and eng.clf_small), nll=nll,
+                      rows=GENE_ROWS if nll == GENE_ROUTE else NLL_ROUTES[nll],
                       raw_last=raw_last, x3=bool(raw_last and p.c_decx.x3_last), db_done=nll == 'raw_cs')
 
 

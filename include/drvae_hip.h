@@ -578,7 +578,39 @@ int dv_rec_nll_rows(int32_t kind, float shift, const float* coef, const float* x
  * Deterministic (fixed summation order, no atomics).
  * dmu == dsd == ws == NULL (coef unused): FORWARD ONLY -- the row partials of an evaluation pass behind a plain heads
  * product (the whole-set evaluation's loss pass: no activation epilogue in the GEMM, no finished heads written and
- * read back). */
+ * read back).
+ *
+ * THE COUNT KINDS WITH A GENE-WISE DISPERSION (trailing fields `kind`, `theta_raw`, `size`; all zero: the Gaussian pass above,
+ * bit for bit -- theta_raw and size are not read then).  kind = DV_REC_NEGBIN / DV_REC_NEGBIN_LIB / DV_REC_ZINB /
+ * DV_REC_ZINB_LIB: the row terms and gradients of dv_rec_nll_rows' kind of that name, with theta not a head but ONE value
+ * per gene, theta_g = softplus(theta_raw[g]) + DV_NB_THETA_SHIFT (theta_raw: X floats; the kernel forms theta itself, in
+ * double, rounded once to fp32).  Under a count kind:
+ *   mu (row stride ldp) = the FINISHED mean head (softplus + shift);  shift = the mean's shift
+ *   sd (same stride)    = the RAW dropout logit for the ZINB kinds; NULL for the NB kinds
+ *   coef, x, ldx, xidx  = as dv_rec_nll_rows
+ *   dmu / dsd (ldd)     = coef[r] * d/da_m and coef[r] * d/da_d (dsd: ZINB kinds only, NULL otherwise)
+ *   out_part            = (M, chunks) row partials, chunks = ceil(X / 1024) -- NOT dv_nll_raw_cs_chunks(X)
+ *   ws[b, g]            = sum over the rows of row block b of coef[r] * d/da_t[r, g], ldw >= X (d/da_t: w.r.t. theta_raw);
+ *                         the caller sums the blocks: dv_colsum(ws, ldw, row_blocks, X, ..) is the gradient of theta_raw
+ *   row_blocks          = the CALLER'S choice in [1, max(M, 1)] (and <= 65535) -- NOT dv_nll_raw_cs_row_blocks(M); block b
+ *                         owns the rows [b R, min(M, (b + 1) R)), R = ceil(M / row_blocks) (a block past M owns none and
+ *                         writes zeros to its row of ws)
+ *   sd_off, bias_mu, bias_sd: unused, must be 0 / NULL
+ *   size                = M floats.  The library-scaled kinds need the size factor s[r] = max(sum_g x[xidx[r], g], 1) / X of
+ *                         every row.  chunks == 1: the workgroup forms it from the row it reads (and stores it to size when
+ *                         size is given).  chunks > 1: REQUIRED -- a small launch in front writes s of every row into it
+ *                         (two launches behind this one call), so that no chunk walks the whole target row again.  Either
+ *                         way s is the one correctly rounded quotient for integer counts with a total below 2^24.
+ *                         The unscaled kinds do not touch it.
+ * A workgroup of 256 threads owns one chunk and one row block; a thread owns four genes for all rows of the block (a quad
+ * on 16-byte accesses with X % 4 == 0 and aligned rows, else the genes tid + 256 j: any X >= 1, any alignment).  Row
+ * partials: per-thread partials in index order, the wave sum, the four waves as (p0 + p1) + (p2 + p3).  ws: ascending row
+ * order in registers, stored once.  No atomics; repeated launches give equal bits.
+ * Forward only: dmu == dsd == ws == NULL (coef unused).
+ * DV_ERR_ARG, before any launch and at M == 0 too: an unknown kind; no theta_raw / x / mu / out_part; a ZINB kind without
+ * sd or an NB kind with sd; biases or sd_off given; chunks or row_blocks outside the above; ldx, ldp (, ldd) < X; with dmu:
+ * no coef, no ws, ldw < X, dsd not as the kind asks; without dmu: ws or dsd given; a library kind with chunks > 1 and no
+ * size. */
 typedef struct dv_nll_raw_cs_desc {
     const float* coef;
     const float* x;
@@ -601,6 +633,10 @@ typedef struct dv_nll_raw_cs_desc {
     int64_t ldw;
     int64_t sd_off;
     int32_t row_blocks;
+    /* trailing (inside ABI 13): the count kinds with a gene-wise dispersion; all zero = the Gaussian pass as it was */
+    int32_t kind;
+    const float* theta_raw;
+    float* size;
 } dv_nll_raw_cs_desc;
 int dv_gauss_nll_rows_raw_cs(const dv_nll_raw_cs_desc* d, dv_stream_t stream);
 int dv_nll_raw_cs_chunks(int32_t X);
