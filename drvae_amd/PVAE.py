@@ -35,7 +35,9 @@ class PVAE(ELBOModel):
     max(sum_g x_g, 1) / dim_x.  Attributes until the engine is built, like the schedules.  Labelled extensions.
     ``dispersion`` (default 'gene-cell' | 'gene'; ``type_rec='nb'`` / ``'zinb'`` only, anything else raises ``ValueError``): 'gene' replaces the
     theta head by ONE inverse dispersion per gene, the parameter ``decoder_x.decoder_t.raw_theta`` (theta = softplus + 1e-3, started at
-    0); ``px1`` / ``px2`` keep their shape, theta expanded to (rows, dim_x).  Labelled extension."""
+    0); ``px1`` / ``px2`` keep their shape, theta expanded to (rows, dim_x).  'gene-batch' (``use_s=True`` only, else
+    ``ValueError``): one inverse dispersion per (gene, nuisance class) -- the same parameter as a (dim_s, dim_x) table, a row of class k
+    reads row k (the x2 rows of a pair: the class of their batch row).  Labelled extension."""
     kind = 'pvae'
     prior_y = None          # read by the reference ctor (src/PVAE.py:77) although PVAE has no y
 

@@ -157,7 +157,9 @@ class NllRawCs(C.Structure):     # dv_nll_raw_cs_desc
                 ('X', _i32), ('shift', _f), ('out_part', _p), ('chunks', _i32), ('dmu', _p), ('dsd', _p), ('ldd', _i64),
                 ('bias_mu', _p), ('bias_sd', _p), ('ws', _p), ('ldw', _i64), ('sd_off', _i64), ('row_blocks', _i32),
                 # trailing: the count kinds with a gene-wise dispersion (all zero / NULL: the Gaussian pass as it was)
-                ('kind', _i32), ('theta_raw', _p), ('size', _p)]
+                ('kind', _i32), ('theta_raw', _p), ('size', _p),
+                # trailing: a dispersion per (nuisance class, gene) (all zero / NULL: the passes as they were)
+                ('n_cls', _i32), ('cls', _p), ('cls_src', _p), ('ldth', _i64)]
 
 
 class MmdGrouped(C.Structure):   # dv_mmd_grouped_desc

@@ -50,8 +50,10 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         # raw-count inputs (EXTENSIONS, count decoders only; ``StepConfig.x_transform`` / ``library_size``): the encoder reads
         # log1p(x) while the likelihood keeps the raw counts; every decoder mean is scaled by the row's observed size factor
         x_transform, library_size = args.pop('x_transform', None), args.pop('library_size', False)
-        # 'gene-cell' | 'gene': a theta head, or one inverse dispersion per gene ('nb' / 'zinb'; ``StepConfig.dispersion``)
-        self.dispersion = E.check_dispersion(args.pop('dispersion', 'gene-cell'), args.get('type_rec'))
+        # 'gene-cell' | 'gene' | 'gene-batch': a theta head, one inverse dispersion per gene, or one per (gene, nuisance class) with
+        # ``use_s`` ('nb' / 'zinb'; ``StepConfig.dispersion``)
+        self.dispersion = E.check_dispersion(args.pop('dispersion', 'gene-cell'), args.get('type_rec'),
+                                             use_s=bool(args.get('use_s', False)))
         for k, v in args.items():
             setattr(self, k, v)
         for k, v in anneal.items():
@@ -149,7 +151,7 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         dec = {'diag_gaussian': blk.DiagGaussianSigmaModule, 'binary': blk.BernoulliDecoder,
                'poisson': blk.PoissonDecoder, 'nb': blk.NegativeBinomialDecoder,
                'zinb': blk.ZeroInflatedNegativeBinomialDecoder}[self.type_rec]      # src/DrVAE.py:124-129
-        gene = dict(dispersion='gene') if self.dispersion == 'gene' else {}       # ('gene-cell': the call as it was)
+        gene = dict(dispersion=self.dispersion) if self.dispersion != 'gene-cell' else {}       # ('gene-cell': the call as it was)
         self.decoder_x = dec([Z1] + s_in, self.dim_h_de_x, self.dim_x, **hp, **gene)
 
     def _dropout_notes(self):
@@ -254,7 +256,7 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
             prior_y=None if (getattr(self, 'prior_y', None) is None or isinstance(getattr(self, 'prior_y', None), str))
             else tuple(float(v) for v in self.prior_y), matmul=self._matmul, dropout_rate=float(self.dropout_rate),
             max_grad_norm=self._max_grad_norm, ema_decay=self.ema_decay, **self._counts_config(), **self._anneal_config(),
-            **(dict(dispersion='gene') if self.dispersion == 'gene' else {}))
+            **(dict(dispersion=self.dispersion) if self.dispersion != 'gene-cell' else {}))
 
     # ---------------------------------------------------------------- inference
     @torch.no_grad()

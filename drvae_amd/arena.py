@@ -60,6 +60,11 @@ def row_stride(shape):
     return shape[-1] if len(shape) else 1
 
 
+# tables that no product reads -- a row pass indexes them, and their gradient is ONE contiguous column sum (the (dim_s, dim_x)
+# inverse dispersions of ``dispersion='gene-batch'``): their rows stay as they are
+DENSE_TABLES = ('.raw_theta',)
+
+
 def span(t):
     """floats from the first to one past the last element of a (row-padded) arena view"""
     if t.dim() == 2 and t.numel():
@@ -128,25 +133,30 @@ class ParamArena:
         """floats the parameter occupies in the arena (rows padded to 16 B: see ``row_stride``)"""
         s = self.shapes[name]
         if len(s) == 2:
-            return s[0] * row_stride(s)
+            return s[0] * self.row_stride(name)
         n = 1
         for d in s:
             n *= d
         return n
 
+    def row_stride(self, name):
+        """floats between consecutive rows of parameter ``name``: ``row_stride`` of its shape, but a dense table's own width"""
+        s = self.shapes[name]
+        return s[-1] if len(s) == 2 and name.endswith(DENSE_TABLES) else row_stride(s)
+
     def _view(self, buf, name):
         o, s = self.offsets[name], self.shapes[name]
-        if len(s) == 2 and row_stride(s) != s[1]:
-            return buf[o:o + self.numel(name)].view(s[0], row_stride(s))[:, :s[1]]
+        if len(s) == 2 and self.row_stride(name) != s[1]:
+            return buf[o:o + self.numel(name)].view(s[0], self.row_stride(name))[:, :s[1]]
         return buf[o:o + self.numel(name)].view(s)
 
     def pads(self, buf):
         """the pad columns of every row-padded parameter inside ``buf`` (param / grad / a moment): zero, always"""
         out = []
         for name, s in self.shapes.items():
-            if len(s) == 2 and row_stride(s) != s[1]:
+            if len(s) == 2 and self.row_stride(name) != s[1]:
                 o = self.offsets[name]
-                out.append(buf[o:o + self.numel(name)].view(s[0], row_stride(s))[:, s[1]:])
+                out.append(buf[o:o + self.numel(name)].view(s[0], self.row_stride(name))[:, s[1]:])
         return out
 
     def p(self, name):

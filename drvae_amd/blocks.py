@@ -488,16 +488,24 @@ class GeneDispersion(nn.Module):
     view: the block-level path materialises nothing, and autograd's gradient of ``raw_theta`` is the column sum of the theta
     block's gradient.  (The fused step reads the vector inside its row pass: ``gene_rows``.)"""
 
-    def __init__(self, n_genes, shift):
+    def __init__(self, n_genes, shift, n_classes=None):
+        """``n_classes`` (``dispersion='gene-batch'``): a theta per (nuisance class, gene) -- ``raw_theta`` is the table
+        (n_classes, genes), and the module is called with the rows' one-hot class block instead of a row count"""
         super().__init__()
         self.shift = shift
-        self.raw_theta = nn.Parameter(torch.zeros(n_genes))
+        self.n_classes = n_classes
+        self.raw_theta = nn.Parameter(torch.zeros(n_genes) if n_classes is None else torch.zeros(n_classes, n_genes))
 
     def theta(self):
         return F.softplus(self.raw_theta) + self.shift
 
     def forward(self, rows):
-        return self.theta().unsqueeze(0).expand(rows, -1)
+        if self.n_classes is None:
+            return self.theta().unsqueeze(0).expand(rows, -1)
+        # (rows: the (rows, n_classes) one-hot block or the rows' int classes -- every row gets its class's row of the table;
+        # autograd's gradient of the table is the per-class column sum)
+        cls = rows.argmax(1) if rows.dim() == 2 else rows.long()
+        return self.theta().index_select(0, cls)
 
 
 class NegativeBinomialDecoder(nn.Module):
@@ -519,8 +527,12 @@ class NegativeBinomialDecoder(nn.Module):
         """``dispersion='gene'`` (default 'gene-cell': the theta head): ONE inverse dispersion per gene, shared by all rows --
         ``decoder_t`` then holds no Linear but the (reconstruction_dim,) parameter ``raw_theta`` (``GeneDispersion``)"""
         super().__init__()
-        if dispersion not in ('gene-cell', 'gene'):
-            raise ValueError("dispersion must be 'gene-cell' or 'gene', not %r" % (dispersion,))
+        if dispersion not in ('gene-cell', 'gene', 'gene-batch'):
+            raise ValueError("dispersion must be 'gene-cell' or 'gene' (or 'gene-batch' with a class block), not %r"
+                             % (dispersion,))
+        if dispersion == 'gene-batch' and not (isinstance(input_dims, (list, tuple)) and len(input_dims) >= 2):
+            raise ValueError("dispersion='gene-batch' needs the one-hot nuisance classes as the decoder's last input "
+                             "(use_s=True), not input_dims=%r" % (input_dims,))
         self.dispersion = dispersion
         self.nnet = MLP(input_dims=input_dims, hidden_dims=hidden_dims, nonlin=nonlin, weight_norm=weight_norm,
                         batch_norm=batch_norm, dropout_rate=dropout_rate, input_dropout_rates=input_dropout_rates)
@@ -529,9 +541,11 @@ class NegativeBinomialDecoder(nn.Module):
         width = _trunk_width(input_dims, hidden_dims)
         # (mean head first, then theta: the parameter-init RNG stream and the arena's head pair follow this order)
         # (a gene-wise theta: the vector in FRONT of the heads, the order of ``engine.param_shapes`` -- it consumes no random draw)
-        if dispersion == 'gene':
-            self.decoder_t = GeneDispersion(reconstruction_dim, self.THETA_SHIFT)
-        for head, lin in (('decoder_m', 'linear_m'), ('decoder_t', 'linear_t'))[:1 if dispersion == 'gene' else 2]:
+        # ('gene-batch': the (classes, genes) table in its place; the class of a row is read from the last input's one-hot block)
+        if dispersion != 'gene-cell':
+            self.decoder_t = GeneDispersion(reconstruction_dim, self.THETA_SHIFT,
+                                            int(input_dims[-1]) if dispersion == 'gene-batch' else None)
+        for head, lin in (('decoder_m', 'linear_m'), ('decoder_t', 'linear_t'))[:2 if dispersion == 'gene-cell' else 1]:
             mods = OrderedDict()
             if dropout_rate > 0.:
                 mods['dropout'] = Dropout(p=dropout_rate)
@@ -543,16 +557,19 @@ class NegativeBinomialDecoder(nn.Module):
             h = [seq.dropout(h[0] if len(h) == 1 else torch.cat(h, 1))]
         return _apply_linear(getattr(seq, lin), h, act='softplus', shift=shift)
 
-    def _theta(self, h, mu):
-        """the second element of the decoder's output: the theta head over ``h``, or the gene-wise theta as (rows, genes)"""
+    def _theta(self, h, mu, inputs=None):
+        """the second element of the decoder's output: the theta head over ``h``, or the gene-wise theta as (rows, genes) --
+        'gene-batch': every row its class's, the class read from the one-hot block that is the last of ``inputs``"""
         if self.dispersion == 'gene':
             return self.decoder_t(mu.shape[0])
+        if self.dispersion == 'gene-batch':
+            return self.decoder_t(inputs[-1])
         return self._head_out(self.decoder_t, 'linear_t', h, self.THETA_SHIFT)
 
     def forward(self, inputs):
         h = self.nnet.features(inputs)
         mu = self._head_out(self.decoder_m, 'linear_m', h, self.MU_SHIFT)
-        return mu, self._theta(h, mu)
+        return mu, self._theta(h, mu, inputs)
 
     def logp_perx(self, x, mu, theta, size=None):
         """``size`` (rows,): the rows' size factors -- the mean is size * mu, theta as it is (``library_size`` models)"""
@@ -606,7 +623,7 @@ class ZeroInflatedNegativeBinomialDecoder(NegativeBinomialDecoder):
         h = self.nnet.features(inputs)
         hd = [self.decoder_d.dropout(h[0] if len(h) == 1 else torch.cat(h, 1))] if hasattr(self.decoder_d, 'dropout') else h
         mu = self._head_out(self.decoder_m, 'linear_m', h, self.MU_SHIFT)
-        return mu, self._theta(h, mu), _apply_linear(self.decoder_d.linear_d, hd)
+        return mu, self._theta(h, mu, inputs), _apply_linear(self.decoder_d.linear_d, hd)
 
     def logp_perx(self, x, mu, theta, logit, size=None):
         """``size`` (rows,): the rows' size factors -- the mean is size * mu; theta and the logit as they are"""

@@ -6,6 +6,8 @@
 // (results are bitwise reproducible).
 #include "dv_common.h"
 
+#include <type_traits>
+
 namespace {
 
 constexpr float kLog2Pi = 1.8378770664093453f;   // float(np.log(2*np.pi)), src/blocks.py:196,234
@@ -1249,8 +1251,20 @@ __global__ __launch_bounds__(256) void size_rows_kernel(const float* __restrict_
     }
 }
 
-template <bool ZI, int LIB, bool VEC>
-__global__ __launch_bounds__(256) void gene_rows_kernel(GeneRowsArgs a) {
+// ... PER NUISANCE CLASS (dispersion='gene-batch'; CLS): theta_raw holds a row of X values per class at stride ldth, and the
+// class is the grid's third dimension -- a workgroup owns one chunk, one row block and ONE class k.  It forms its thetas from
+// row k, walks its block's rows in ascending order and skips a row of another class (cls[cls_src ? cls_src[r] : r] != k: a
+// workgroup-uniform branch in front of every load of the row and of row_size_factor's barriers), and stores its accumulators
+// to ws[row block, k X + gene].  One workgroup takes a row, so every out_part / dmu / dlogit / size element has one writer; a
+// class outside [0, gridDim.z) is taken by none.  Every summation order is the shared-theta pass's.
+struct GeneClsArgs {
+    const int32_t* cls; const int32_t* cls_src; int64_t ldth;
+};
+
+struct GeneNoCls {};
+
+template <bool ZI, int LIB, bool VEC, bool CLS = false>
+__global__ __launch_bounds__(256) void gene_rows_kernel(GeneRowsArgs a, std::conditional_t<CLS, GeneClsArgs, GeneNoCls> cl) {
     __shared__ float part[2][4];
     __shared__ float spart[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1261,12 +1275,18 @@ __global__ __launch_bounds__(256) void gene_rows_kernel(GeneRowsArgs a) {
     const bool grad = a.dmu != nullptr;
     const bool quad_on = VEC && gbase < a.X;                      // (X % 4 == 0: a quad is inside or outside as a whole)
     float4 th = make_float4(1.f, 1.f, 1.f, 1.f), tacc = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float* traw = a.theta_raw;
+    if constexpr (CLS) traw += (int64_t)blockIdx.z * cl.ldth;     // the class's row of the table
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int g = gbase + j * kStep;
-        if (g < a.X) quad_put(th, j, gene_theta(a.theta_raw[g]));
+        if (g < a.X) quad_put(th, j, gene_theta(traw[g]));
     }
+    int taken = 0;                                                // (CLS) rows of this class so far: the slot of `part`
     for (int r = r0; r < r1; ++r) {
+        if constexpr (CLS) {
+            if (cl.cls[cl.cls_src ? cl.cls_src[r] : r] != (int)blockIdx.z) continue;
+        }
         const float* xr = a.x + (int64_t)(a.xidx ? a.xidx[r] : r) * a.ldx;
         const float* mr = a.mu + (int64_t)r * a.ldp;
         const float* lr = ZI ? a.logit + (int64_t)r * a.ldp : nullptr;
@@ -1315,13 +1335,14 @@ __global__ __launch_bounds__(256) void gene_rows_kernel(GeneRowsArgs a) {
         }
         acc = dv_wave_sum_all(acc);
         // two slots, taken in turn: the next row's partials land in the other one, so one barrier per row is enough
-        float* p = part[(r - r0) & 1];
+        // (CLS: in turn over the rows TAKEN -- two taken rows around a skipped one would share a slot of r - r0)
+        float* p = part[(CLS ? taken++ : r - r0) & 1];
         if (lane == 0) p[wave] = acc;
         __syncthreads();
         if (tid == 0) a.out_part[(int64_t)r * a.chunks + chunk] = (p[0] + p[1]) + (p[2] + p[3]);
     }
     if (grad) {
-        float* w = a.ws + (int64_t)blockIdx.y * a.ldw;
+        float* w = a.ws + (int64_t)blockIdx.y * a.ldw + (CLS ? (int64_t)blockIdx.z * a.X : 0);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int g = gbase + j * kStep;
@@ -1329,6 +1350,7 @@ __global__ __launch_bounds__(256) void gene_rows_kernel(GeneRowsArgs a) {
         }
     }
 }
+
 
 __global__ void nll_rows_bwd_kernel(const float* __restrict__ coef, const float* __restrict__ x, int64_t ldx,
                                     const int32_t* __restrict__ xidx, const float* __restrict__ mu,
@@ -3516,12 +3538,18 @@ extern "C" int dv_gauss_nll_rows_fwdbwd(const float* coef, const float* x, int64
 }
 
 template <bool ZI, int LIB>
-static void launch_gene_rows(bool vec, const GeneRowsArgs& a, int row_blocks, dv_stream_t stream) {
-    const dim3 grid(a.chunks, row_blocks), block(256);
-    if (vec)
-        hipLaunchKernelGGL((gene_rows_kernel<ZI, LIB, true>), grid, block, 0, ST(stream), a);
+static void launch_gene_rows(bool vec, const GeneRowsArgs& a, int row_blocks, int n_cls, const GeneClsArgs& cl,
+                             dv_stream_t stream) {
+    const dim3 grid(a.chunks, row_blocks, n_cls > 0 ? n_cls : 1), block(256);
+    if (n_cls > 0) {          // a dispersion per (class, gene): the class is the grid's third dimension
+        if (vec)
+            hipLaunchKernelGGL((gene_rows_kernel<ZI, LIB, true, true>), grid, block, 0, ST(stream), a, cl);
+        else
+            hipLaunchKernelGGL((gene_rows_kernel<ZI, LIB, false, true>), grid, block, 0, ST(stream), a, cl);
+    } else if (vec)
+        hipLaunchKernelGGL((gene_rows_kernel<ZI, LIB, true>), grid, block, 0, ST(stream), a, GeneNoCls{});
     else
-        hipLaunchKernelGGL((gene_rows_kernel<ZI, LIB, false>), grid, block, 0, ST(stream), a);
+        hipLaunchKernelGGL((gene_rows_kernel<ZI, LIB, false>), grid, block, 0, ST(stream), a, GeneNoCls{});
 }
 
 // the count kinds of dv_gauss_nll_rows_raw_cs (gene-wise theta): every refusal in front of the first launch, at M == 0 too
@@ -3536,9 +3564,12 @@ static int gene_rows(const dv_nll_raw_cs_desc& d, dv_stream_t stream) {
     DV_REQUIRE(d.chunks == (d.X + 1023) / 1024);
     DV_REQUIRE(d.row_blocks >= 1 && d.row_blocks <= (d.M > 1 ? d.M : 1) && d.row_blocks <= 65535);
     DV_REQUIRE(d.ldx >= d.X && d.ldp >= d.X);
+    DV_REQUIRE(d.n_cls >= 0 && d.n_cls <= 65535);
+    if (d.n_cls >= 1) DV_REQUIRE(d.cls != nullptr && d.ldth >= d.X);
     const bool grad = d.dmu != nullptr;
     if (grad) {
         DV_REQUIRE(d.ws && d.coef && d.ldw >= d.X && d.ldd >= d.X);
+        DV_REQUIRE(d.ldw >= (int64_t)d.n_cls * d.X);
         DV_REQUIRE(zi ? d.dsd != nullptr : d.dsd == nullptr);
     } else {
         DV_REQUIRE(d.ws == nullptr && d.dsd == nullptr);
@@ -3563,7 +3594,7 @@ static int gene_rows(const dv_nll_raw_cs_desc& d, dv_stream_t stream) {
     static constexpr decltype(&launch_gene_rows<false, 0>) launch[2][3] = {
         {launch_gene_rows<false, 0>, launch_gene_rows<false, 1>, launch_gene_rows<false, 2>},
         {launch_gene_rows<true, 0>, launch_gene_rows<true, 1>, launch_gene_rows<true, 2>}};
-    launch[zi][libmode](vec, a, d.row_blocks, stream);
+    launch[zi][libmode](vec, a, d.row_blocks, d.n_cls, GeneClsArgs{d.cls, d.cls_src, d.ldth}, stream);
     DV_RETURN_LAUNCH();
 }
 
@@ -3571,6 +3602,7 @@ extern "C" int dv_gauss_nll_rows_raw_cs(const dv_nll_raw_cs_desc* dsc, dv_stream
     DV_REQUIRE(dsc != nullptr);
     const dv_nll_raw_cs_desc& d = *dsc;
     if (d.kind != 0) return gene_rows(d, stream);
+    DV_REQUIRE(d.n_cls == 0);                      // (classes: the count kinds only)
     DV_REQUIRE(d.M >= 0 && d.X >= 4 && d.X % 4 == 0);
     if (d.M == 0) return DV_OK;
     const bool fwd_only = d.dmu == nullptr;        // (evaluation: row terms only)

@@ -130,6 +130,26 @@ def require_counts(ds, what):
         pass
 
 
+def require_classes(ds, dim_s, what):
+    """the precondition of ``dispersion='gene-batch'``: every nuisance class of the dataset lies in [0, dim_s) -- the row pass
+    takes no row of a class outside it.  One reduction per dataset (remembered on it), outside any step; ValueError otherwise"""
+    if getattr(ds, '_classes_checked', None) == dim_s:
+        return
+    s = getattr(ds, 's', None)
+    if s is None:
+        raise ValueError("%s: dispersion='gene-batch' needs the nuisance classes of the dataset (s)" % what)
+    s = torch.as_tensor(s)
+    if s.numel():
+        lo, hi = int(s.min()), int(s.max())
+        if lo < 0 or hi >= dim_s:
+            raise ValueError("%s: dispersion='gene-batch' needs nuisance classes 0 <= s < dim_s = %d; the dataset's lie in "
+                             '[%d, %d]' % (what, dim_s, lo, hi))
+    try:
+        ds._classes_checked = dim_s
+    except AttributeError:
+        pass
+
+
 class DeviceBatcher:
     """Stratified, weighted, with-replacement minibatches drawn ON the device and written
     straight into the fused step's input buffers (see the module docstring)."""
@@ -263,6 +283,8 @@ class DeviceBatcher:
             return engine.plan          # (every epoch of ``fit`` binds: nothing to rebuild)
         if engine.cfg.split_x:      # raw-count inputs: log1p and the size factor want x >= 0 (checked once per dataset, here)
             require_counts(self.dataset, 'DeviceBatcher.bind')
+        if engine.cfg.dispersion == 'gene-batch':      # (a theta per class: the classes are in range, checked once too)
+            require_classes(self.dataset, engine.cfg.dim_s, 'DeviceBatcher.bind')
         self.engine = engine
         self.dp = dp
         assert self.dp is None or 0 <= self.dp[0] < self.dp[1]

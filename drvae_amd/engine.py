@@ -28,6 +28,7 @@ from typing import List, NamedTuple, Optional, Tuple
 import numpy as np
 import torch
 
+from . import gene_batch_rows as GB
 from . import gene_rows as G
 from . import kernels as K
 from . import tuning as T
@@ -145,11 +146,14 @@ class StepConfig:
     #   'gene'               : ONE theta per gene, shared by all cells -- the (dim_x,) parameter ``GENE_THETA`` in the arena,
     #                          theta_g = softplus(raw_theta_g) + 1e-3; the theta head and its three products do not exist, the
     #                          row pass reads the vector (``gene_rows``) and its gradient is a column sum
+    #   'gene-batch'         : (``use_s`` only) one theta per (gene, nuisance class) -- the same parameter as a (dim_s, dim_x) table;
+    #                          a decoder row reads the row of its class (``gene_batch_rows``: the class is a grid dimension of the
+    #                          row pass), the x2 and perturbation rows of a pair the class of their batch row
     dispersion: str = 'gene-cell'
 
     def __post_init__(self):
         check_counts_config(self.x_transform, self.library_size, self.type_rec, 'StepConfig.')
-        check_dispersion(self.dispersion, self.type_rec, 'StepConfig.')
+        check_dispersion(self.dispersion, self.type_rec, 'StepConfig.', use_s=self.use_s)
         self.library_size = bool(self.library_size)
         if self.optim_alg not in OPTIM_ALGS:
             raise ValueError('StepConfig.optim_alg must be one of %s, not %r' % (OPTIM_ALGS, self.optim_alg))
@@ -247,7 +251,9 @@ REC_FAMILIES = {
 
 # ``dispersion='gene'``: the families without the theta head -- 'nb' the mean head alone (launched as the Poisson decoder's single
 # softplus head is), 'zinb' the pair [mean | dropout logit], back to back in the arena; theta is the (dim_x,) parameter below
-DISPERSIONS = ('gene-cell', 'gene')
+# ``dispersion='gene-batch'`` (``use_s`` models only): the same families -- the parameter is a (dim_s, dim_x) table at the same
+# place, a row per nuisance class, and the row pass reads the row of a decoder row's class (``gene_batch_rows``)
+DISPERSIONS = ('gene-cell', 'gene', 'gene-batch')
 GENE_THETA = 'decoder_x.decoder_t.raw_theta'
 GENE_FAMILIES = {
     'nb': RecFamily(_NB_HEADS[:1], True, REC_KIND['nb'], REC_KIND['nb_lib'], RECON_KIND['nb'], True, True),
@@ -258,16 +264,20 @@ GENE_FAMILIES = {
 
 def rec_family(type_rec, dispersion='gene-cell'):
     """the ``RecFamily`` of a decoder: ``REC_FAMILIES[type_rec]``, or its gene-wise form"""
-    return GENE_FAMILIES[type_rec] if dispersion == 'gene' else REC_FAMILIES[type_rec]
+    return GENE_FAMILIES[type_rec] if dispersion in ('gene', 'gene-batch') else REC_FAMILIES[type_rec]
 
 
-def check_dispersion(dispersion, type_rec, prefix=''):
-    """``dispersion`` as a checked value; ValueError for an unknown one and for 'gene' on a decoder without a theta"""
+def check_dispersion(dispersion, type_rec, prefix='', use_s=False):
+    """``dispersion`` as a checked value; ValueError for an unknown one, for 'gene' / 'gene-batch' on a decoder without a theta
+    and for 'gene-batch' on a model without nuisance classes (``use_s``)"""
     if dispersion not in DISPERSIONS:
-        raise ValueError("%sdispersion must be 'gene-cell' or 'gene', not %r" % (prefix, dispersion))
-    if dispersion == 'gene' and type_rec not in GENE_FAMILIES:
-        raise ValueError("%sdispersion='gene' is for the decoders with an inverse dispersion (type_rec=%s), not type_rec=%r"
-                         % (prefix, ' / '.join(repr(k) for k in GENE_FAMILIES), type_rec))
+        raise ValueError("%sdispersion must be 'gene-cell' or 'gene' (or 'gene-batch' with use_s=True), not %r"
+                         % (prefix, dispersion))
+    if dispersion != 'gene-cell' and type_rec not in GENE_FAMILIES:
+        raise ValueError("%sdispersion=%r is for the decoders with an inverse dispersion (type_rec=%s), not type_rec=%r"
+                         % (prefix, dispersion, ' / '.join(repr(k) for k in GENE_FAMILIES), type_rec))
+    if dispersion == 'gene-batch' and not use_s:
+        raise ValueError("%sdispersion='gene-batch' is a dispersion per (gene, nuisance class): it needs use_s=True" % prefix)
     return dispersion
 
 
@@ -343,7 +353,7 @@ def param_shapes(cfg):
     if cfg.rec.gene:
         # in FRONT of the heads: they stay the tail of the arena (the half of the sweep the side chain may take,
         # ``_side_adam_layout``), and the vector lies in the half that follows the whole backward pass
-        out[GENE_THETA] = (X,)
+        out[GENE_THETA] = (cfg.dim_s, X) if cfg.dispersion == 'gene-batch' else (X,)
     for h in cfg.rec.heads:
         lin(h.prefix, n, X)
     return out
@@ -1009,20 +1019,27 @@ class FusedStep(StepSchedule):
     def _gene_rows(self, PX, grads):
         """the reconstruction rows of a ``dispersion='gene'`` model (``gene_rows.gene_rows``): per-chunk row partials into
         ``NLLG``; ``grads``: and the heads' gradients into ``DPX``, the per-block column sums of theta's into ``GWS`` -- summed
-        into the vector's gradient by ``_gene_theta_grad``, behind the decoder's backward products"""
+        into the vector's gradient by ``_gene_theta_grad``, behind the decoder's backward products.  ``'gene-batch'``: the same
+        through ``gene_batch_rows`` with the plan's class operands; ``GWS`` then holds a segment of X columns per class"""
         cfg, p, X = self.cfg, self.plan, self.cfg.dim_x
         zi = cfg.type_rec == 'zinb'
         gk = dict(coef=p.c_nll, dmu=p.DPX[:, :X], dlogit=p.DPX[:, X:] if zi else None, ws=p.GWS) if grads else \
             dict(row_blocks=p.GWS.shape[0])
-        G.gene_rows(p.NLLG, p.XT if cfg.split_x else p.XIN, PX[:, :X], self.arena.p(GENE_THETA), kind=cfg.type_rec,
-                    shift=cfg.rec.heads[0].shift, logit=PX[:, X:] if zi else None, xidx=p.tgt, library=cfg.library_size,
-                    size=p.GSIZE, **gk)
+        kw = dict(kind=cfg.type_rec, shift=cfg.rec.heads[0].shift, logit=PX[:, X:] if zi else None, xidx=p.tgt,
+                  library=cfg.library_size, size=p.GSIZE, **gk)
+        if cfg.dispersion == 'gene-batch':     # a theta per (class, gene): the classes of the decoder rows are the plan's
+            cls, cls_src = p.gene_cls()
+            GB.gene_batch_rows(p.NLLG, p.XT if cfg.split_x else p.XIN, PX[:, :X], self.arena.p(GENE_THETA), cls,
+                               cls_src=cls_src, **kw)
+            return
+        G.gene_rows(p.NLLG, p.XT if cfg.split_x else p.XIN, PX[:, :X], self.arena.p(GENE_THETA), **kw)
 
     def _gene_theta_grad(self):
         """d loss / d raw_theta = the column sum of ``GWS`` over the row blocks.  Only the optimiser sweep (and a gradient
         exchange) reads it, so it is no launch in front of the decoder's data gradient: it follows the decoder's backward
         products, in front of the point where the decoder's gradients count as final"""
-        K.colsum(self.arena.g(GENE_THETA), self.plan.GWS[:, :self.cfg.dim_x])
+        g = self.arena.g(GENE_THETA)           # ((dim_s, dim_x) table: the classes' segments of ``GWS`` back to back)
+        K.colsum(g.view(-1), self.plan.GWS[:, :g.numel()])
 
     def _side_forward(self, Qmu, Qlv, Z1blk, r, mid=None, mid_park=None):
         """fprop first: it only needs the z1 samples, so (dual-graph schedule) it can start before

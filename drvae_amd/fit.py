@@ -379,6 +379,11 @@ class FitMixin:
             for ld in (train_loader, valid_loader):      # raw-count inputs: x >= 0, checked once, outside the step
                 if getattr(ld, 'dataset', None) is not None:
                     require_counts(ld.dataset, 'fit')
+        if getattr(self, 'dispersion', 'gene-cell') == 'gene-batch':
+            from .data import require_classes
+            for ld in (train_loader, valid_loader):      # a theta per nuisance class: 0 <= s < dim_s, checked once as well
+                if getattr(ld, 'dataset', None) is not None:
+                    require_classes(ld.dataset, int(self.dim_s), 'fit')
         np.set_printoptions(precision=4)
         ctl = EarlyStopping(self.epochs, early_stop, patience=self.fit_patience)
         self.w2log('Starting training at: {}'.format(time.strftime('%c')))
@@ -905,7 +910,8 @@ class _EvalGraph:
         # (three heads, 'zinb': (mu, theta, logit) as ``forward`` returns it -- columns of the ONE buffer, so [theta | logit] is
         # the contiguous view from column X on that ``_rows_pass`` hands the row pass)
         nh = len(self.fam.heads)
-        if getattr(m, 'dispersion', 'gene-cell') == 'gene':
+        disp = getattr(m, 'dispersion', 'gene-cell')
+        if disp != 'gene-cell':
             # a gene-wise theta: ``dv_recon_rows`` has no broadcast operand, so the finished theta row is written into a theta
             # block once per replay, as one row repeated (M x X words written and read), with the decoder's logit columns copied
             # behind it for 'zinb' -- then the recon kinds run as they are, and the numbers are ``_evaluate``'s key by key
@@ -915,7 +921,12 @@ class _EvalGraph:
             if not hasattr(self, 'gtail'):
                 self.gtail = torch.zeros(rows_all, nt * X, device=PX.device)
             T_ = self.gtail
-            T_[:, :X].copy_(m.decoder_x.decoder_t(rows_all))
+            if disp == 'gene-batch':
+                # a theta per (class, gene): every evaluation row its own class's row of the finished table -- a gather by the
+                # set's class vector (``s_all``: the decoder's stacked rows [z1; z2] use the same classes twice), on the device
+                T_[:, :X].copy_(m.decoder_x.decoder_t(self.s_all.long().repeat(rows_all // n)))
+            else:
+                T_[:, :X].copy_(m.decoder_x.decoder_t(rows_all))
             if nt > 1:
                 T_[:, X:].copy_(PX[:, X:2 * X])
             heads = lambda lo, hi: (PX[lo:hi, :X],) + tuple(T_[lo:hi, k * X:(k + 1) * X] for k in range(nt))

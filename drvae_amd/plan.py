@@ -6,7 +6,7 @@ import math
 import numpy as np
 import torch
 
-from . import gene_rows
+from . import gene_batch_rows, gene_rows
 from . import kernels as K
 from .arena import N_LOSS
 from .chain import X3_PARTS, _Chain, _pad4
@@ -215,9 +215,14 @@ class _Plan:
             self.NLLC, self.NLLWS = zf(Md, chunks), zf(rbs, 2 * X)
         # a gene-wise theta (``StepConfig.dispersion='gene'``): the row pass's per-chunk partials, its per-row-block column sums of
         # theta's gradient (``gene_rows.shape``: the host's row-block rule) and the rows' size factors (library-scaled kinds)
+        # (``'gene-batch'``: a segment of X columns per nuisance class in ``GWS``, and the rule of ``gene_batch_rows``)
         if cfg.rec.gene:
-            chunks, rbs = gene_rows.shape(max(Md, 1), X)
-            self.NLLG, self.GWS = zf(Md, chunks), zf(rbs, _pad4(X))
+            if cfg.dispersion == 'gene-batch':
+                chunks, rbs = gene_batch_rows.shape(max(Md, 1), X, cfg.dim_s)
+                self.NLLG, self.GWS = zf(Md, chunks), zf(rbs, _pad4(cfg.dim_s * X))
+            else:
+                chunks, rbs = gene_rows.shape(max(Md, 1), X)
+                self.NLLG, self.GWS = zf(Md, chunks), zf(rbs, _pad4(X))
             self.GSIZE = zf(max(Md, 1)) if cfg.library_size else None
         # opt-in split-bf16 products (``StepConfig.matmul``): exactly one layer changes arithmetic -- the decoder's heads
         # layer where it takes the raw-heads route -- and whether it does is decided HERE, once (raises if its products are
@@ -350,6 +355,9 @@ class _Plan:
         zf = lambda *s: torch.zeros(*s, device=dev)
         self.carry_s = True
         self.s_cls = i32(np.zeros(B))
+        if cfg.dispersion == 'gene-batch':
+            # the batch row whose class a decoder row has (the indexing ``dv_nuisance_feed`` documents for sohd): constant
+            self.dec_src = i32(np.concatenate([np.tile(np.arange(B), L), np.tile(self.pair_host, 2 * L)]))
         if not cfg.use_MMD:
             return self
         assert cfg.kernel_MMD in K.MMD_GROUPED_KIND, 'use_MMD on device-carried nuisance classes: kernel_MMD rbf_fourier | identity'
@@ -402,6 +410,12 @@ class _Plan:
             W=zf(n_groups * Kc, Z, R) if rff else None, b=zf(n_groups * Kc, R) if rff else None,
             theta=zf(Kc * E, R) if rff else None)
         return self
+
+    def gene_cls(self):
+        """(cls, cls_src) of ``gene_batch_rows`` (``dispersion='gene-batch'``): the classes of the decoder rows -- ``s_dec``
+        as ``set_s_host`` / ``set_s_device`` fill it, or on a plan that carries the classes the batch's ``s_cls`` through the
+        constant map of decoder row to batch row"""
+        return (self.s_cls, self.dec_src) if self.carry_s else (self.s_dec, None)
 
     def set_s_host(self, sv):
         """nuisance classes of this batch's rows (``use_s`` extension): one-hot columns of the stacked encoder

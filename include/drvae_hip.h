@@ -610,7 +610,24 @@ int dv_rec_nll_rows(int32_t kind, float shift, const float* coef, const float* x
  * DV_ERR_ARG, before any launch and at M == 0 too: an unknown kind; no theta_raw / x / mu / out_part; a ZINB kind without
  * sd or an NB kind with sd; biases or sd_off given; chunks or row_blocks outside the above; ldx, ldp (, ldd) < X; with dmu:
  * no coef, no ws, ldw < X, dsd not as the kind asks; without dmu: ws or dsd given; a library kind with chunks > 1 and no
- * size. */
+ * size.
+ *
+ * A DISPERSION PER (NUISANCE CLASS, GENE) (trailing fields `n_cls`, `cls`, `cls_src`, `ldth`; all zero: the passes above, bit
+ * for bit -- none of them is read then).  n_cls = S >= 1 under a count kind:
+ *   theta_raw           = S rows of X floats at stride ldth >= X: theta[k, g] = softplus(theta_raw[k ldth + g]) + shift
+ *   class of row r      = cls[cls_src ? cls_src[r] : r]  (cls_src: M int32, the row of `cls` a decoder row reads -- the batch
+ *                         row of a sample or pair row, the indexing dv_nuisance_feed documents for sohd)
+ *   ws[b, k X + g]      = sum over the rows of row block b that have class k of coef[r] * d/da_t[r, g], ascending rows;
+ *                         ldw >= S X; a block without rows of class k writes zeros to that segment.  One
+ *                         dv_colsum(ws, ldw, row_blocks, S X, ..) is the whole (S, X) gradient, contiguous
+ *   out_part, dmu, dsd, size, chunks, row_blocks: as above
+ * The launch is grid(chunks, row_blocks, S): a workgroup owns one chunk, one row block and one class, walks its block's rows
+ * in ascending order and skips the rows of other classes (a uniform branch in front of every load of the row), so every
+ * output element has one writer and every summation order is the one above: row r's out_part / dmu / dsd / size are, bit
+ * for bit, those of the shared-theta launch at theta_raw row cls(r).  A class outside [0, S) is the caller's error with a
+ * harmless outcome: no workgroup takes the row, nothing of it is written, nothing is read outside the operands.
+ * DV_ERR_ARG, before any launch and at M == 0 too: n_cls != 0 with kind == 0; n_cls < 0 or > 65535; n_cls >= 1 without
+ * cls or with ldth < X; with dmu, ldw < n_cls X. */
 typedef struct dv_nll_raw_cs_desc {
     const float* coef;
     const float* x;
@@ -637,6 +654,11 @@ typedef struct dv_nll_raw_cs_desc {
     int32_t kind;
     const float* theta_raw;
     float* size;
+    /* trailing (inside ABI 13): a dispersion per (nuisance class, gene); all zero = the passes as they were */
+    int32_t n_cls;
+    const int32_t* cls;
+    const int32_t* cls_src;
+    int64_t ldth;
 } dv_nll_raw_cs_desc;
 int dv_gauss_nll_rows_raw_cs(const dv_nll_raw_cs_desc* d, dv_stream_t stream);
 int dv_nll_raw_cs_chunks(int32_t X);
