@@ -117,7 +117,9 @@ class BatchFeed(C.Structure):    # dv_batch_feed_desc
                 ('fp_i', _p), ('fp_lab', _p), ('fp_slot', _p), ('Mf', _i32), ('fp_cls', _p), ('onehot', _p),
                 ('ldh', _i64), ('Y', _i32), ('yf', _p), ('ylab', _p), ('Yc', _i32), ('onehot2', _p), ('ldh2', _i64),
                 # trailing: the split form (raw-count inputs; xt NULL: the launch as it was)
-                ('xt', _p), ('ldt', _i64), ('transform', _i32)]
+                ('xt', _p), ('ldt', _i64), ('transform', _i32),
+                # trailing: sparse rows (CSR triples of matrix 1 / 2; all NULL: the launch as it was)
+                ('csr1_ptr', _p), ('csr1_idx', _p), ('csr1_val', _p), ('csr2_ptr', _p), ('csr2_idx', _p), ('csr2_val', _p)]
 
 
 class KlRows(C.Structure):       # dv_kl_rows_desc

@@ -2219,6 +2219,27 @@ __device__ __forceinline__ float feed_row_partial(const float* __restrict__ src,
     return acc;
 }
 
+// The feed's label blocks, thread t: the label-dependent index buffers of the step.  ONE text for the dense and the sparse feed,
+// expanded in both kernels over their (equally named) arguments -- the dense kernel compiles to the instruction stream it had
+#define DV_FEED_LABEL_BLOCKS()                                                                                             \
+    const int t = ((int)blockIdx.x - row_blocks) * 256 + threadIdx.x;                                                      \
+    if (label_r && t < L * B) {                                                                                            \
+        const int i = t % B;                                                                                               \
+        label_r[t] = has_y[i] ? y[tb[i]] : 0;                                                                              \
+    }                                                                                                                      \
+    if (ylab && t < B * Yc) { /* regression targets (type_y='cont'): ylab[i,:] = yf[row of slot i,:] */                    \
+        const int i = t / Yc, d = t % Yc;                                                                                  \
+        ylab[t] = yf[(int64_t)tb[i] * Yc + d];                                                                             \
+    }                                                                                                                      \
+    if (fp_cls && t < Mf) {                                                                                                \
+        const int cls = fp_lab[t] ? y[tb[fp_i[t]]] : fp_slot[t];                                                           \
+        fp_cls[t] = cls;                                                                                                   \
+        if (onehot)                                                                                                        \
+            for (int c = 0; c < Y; ++c) onehot[(int64_t)t * ldh + c] = c == cls ? 1.f : 0.f;                               \
+        if (onehot2) /* (a second copy of the block: the class columns of both fprop inputs) */                            \
+            for (int c = 0; c < Y; ++c) onehot2[(int64_t)t * ldh2 + c] = c == cls ? 1.f : 0.f;                             \
+    }
+
 template <bool SPLIT, bool NORM>
 __global__ __launch_bounds__(256) void batch_feed_kernel(
     const float* __restrict__ x1, int64_t ld1, const float* __restrict__ x2, int64_t ld2,
@@ -2313,24 +2334,184 @@ __global__ __launch_bounds__(256) void batch_feed_kernel(
         }
         return;
     }
-    const int t = ((int)blockIdx.x - row_blocks) * 256 + threadIdx.x;
-    if (label_r && t < L * B) {
-        const int i = t % B;
-        label_r[t] = has_y[i] ? y[tb[i]] : 0;
-    }
-    if (ylab && t < B * Yc) {      // regression targets (type_y='cont'): ylab[i,:] = yf[row of slot i,:]
-        const int i = t / Yc, d = t % Yc;
-        ylab[t] = yf[(int64_t)tb[i] * Yc + d];
-    }
-    if (fp_cls && t < Mf) {
-        const int cls = fp_lab[t] ? y[tb[fp_i[t]]] : fp_slot[t];
-        fp_cls[t] = cls;
-        if (onehot)
-            for (int c = 0; c < Y; ++c) onehot[(int64_t)t * ldh + c] = c == cls ? 1.f : 0.f;
-        if (onehot2)     // (a second copy of the block: the class columns of both fprop inputs)
-            for (int c = 0; c < Y; ++c) onehot2[(int64_t)t * ldh2 + c] = c == cls ? 1.f : 0.f;
-    }
+    DV_FEED_LABEL_BLOCKS()
 }
+
+// Sparse rows (dv_batch_feed_desc.csr1_* / csr2_*): the CSR triples of the two matrices; ptr == NULL: that matrix is dense
+struct CsrArgs {
+    const int64_t* ptr1;
+    const int32_t* idx1;
+    const float* val1;
+    const int64_t* ptr2;
+    const int32_t* idx2;
+    const float* val2;
+};
+
+constexpr int kCsrChunk = 1024;      // columns a wave stages at a time: the dense kernel's outer iteration (4 x 64 16-byte groups)
+
+// the wave's own LDS writes are ordered before its LDS reads that follow (one wave: no workgroup barrier)
+__device__ __forceinline__ void csr_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Columns [c0, c0 + n) of a CSR row into the wave's chunk `st`: zeroes, then the entries [e, end) of the row whose column
+// lies below c0 + n -- one contiguous range from the running offset e, the row being sorted.  Returns the offset behind them.
+// An entry whose column is outside [c0, c0 + n) is never stored (n <= kCsrChunk, c0 + n <= X): whatever the caller's arrays
+// hold, the stores stay inside the chunk.
+__device__ __forceinline__ int64_t csr_stage_chunk(float* __restrict__ st, const int32_t* __restrict__ idx,
+                                                   const float* __restrict__ val, int64_t e, int64_t end, int c0, int n,
+                                                   int lane) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) reinterpret_cast<float4*>(st)[lane + 64 * u] = make_float4(0.f, 0.f, 0.f, 0.f);
+    while (e < end) {       // (wave-uniform: e and end are)
+        const int64_t k = e + lane;
+        const bool live = k < end;
+        const int64_t off = (live ? (int64_t)idx[k] : 0) - c0;
+        const bool below = live && off < n;
+        if (below && off >= 0) st[off] = val[k];
+        const int took = __popcll(__ballot(below));
+        e += took;
+        if (took < 64) break;
+    }
+    return e;
+}
+
+// ... and the same columns of a dense row (the other matrix of a launch with one sparse matrix may be dense)
+__device__ __forceinline__ void dense_stage_chunk(float* __restrict__ st, const float* __restrict__ src, int c0, int n, int lane) {
+    for (int g = lane; g < n; g += 64) st[g] = src[c0 + g];
+}
+
+// the lane's partial of a CSR row's total over the columns inside [0, X): entries lane, lane + 64, ... in index order
+__device__ __forceinline__ float csr_row_partial(const int32_t* __restrict__ idx, const float* __restrict__ val, int64_t e,
+                                                 int64_t end, int X, int lane) {
+    float acc = 0.f;
+    for (int64_t k = e + lane; k < end; k += 64)
+        if ((unsigned)idx[k] < (unsigned)X) acc += val[k];
+    return acc;
+}
+
+// The feed with one or both matrices held as CSR rows.  Only the way the row's wave obtains the source values differs from
+// batch_feed_kernel: chunk by chunk (kCsrChunk columns = the dense kernel's outer iteration) the wave stages the row in its
+// own 4 KiB of LDS and reads from there the groups / scalars that kernel loads from HBM; the xt store, the transform, the fmaf
+// with the noise and the store pattern are that kernel's, in its order -- the outputs are the bits it writes for the
+// densified matrix.  NORM: a row of up to kCsrChunk columns is summed from the staged row in the dense kernel's order (equal bits
+// for any values), a wider one from the CSR values (exact for integer counts with a total below 2^24)
+template <bool SPLIT, bool NORM>
+__global__ __launch_bounds__(256) void batch_feed_csr_kernel(
+    const float* __restrict__ x1, int64_t ld1, const float* __restrict__ x2, int64_t ld2,
+    const int32_t* __restrict__ y, const int32_t* __restrict__ table, int n_batches,
+    const int32_t* __restrict__ ctr, const int32_t* __restrict__ base, int B, const int32_t* __restrict__ pair_rows,
+    int Np, int X, const float* __restrict__ noise, int64_t ldn, float sigma, float* __restrict__ xin, int64_t ldo,
+    const int32_t* __restrict__ has_y, int L, int32_t* __restrict__ label_r, const int32_t* __restrict__ fp_i,
+    const int32_t* __restrict__ fp_lab, const int32_t* __restrict__ fp_slot, int Mf, int32_t* __restrict__ fp_cls,
+    float* __restrict__ onehot, int64_t ldh, int Y, int row_blocks, int vec4, const float* __restrict__ yf,
+    float* __restrict__ ylab, int Yc, float* __restrict__ onehot2, int64_t ldh2, int mask_block, MaskArgs masks,
+    ParkArgs park, float* __restrict__ xt, int64_t ldt, int transform, CsrArgs csr) {
+    static_assert(SPLIT || !NORM, "the normalised feed is a variant of the split feed");
+    __shared__ __attribute__((aligned(16))) float stage[4][kCsrChunk];
+    park_block(park);
+    if ((int)blockIdx.x == mask_block) {
+        batch_masks_body(masks);
+        return;
+    }
+    int b = ctr[0] - base[0];
+    b = b < 0 ? 0 : (b >= n_batches ? n_batches - 1 : b);
+    const int32_t* tb = table + (int64_t)b * B;
+    if ((int)blockIdx.x < row_blocks) {
+        const int lane = threadIdx.x & 63;
+        const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+        if (r >= B + Np) return;        // (no workgroup barrier below: a wave may leave alone)
+        float* st = stage[threadIdx.x >> 6];
+        const bool first = r < B;
+        const int64_t row = first ? tb[r] : tb[pair_rows[r - B]];
+        // (wave-uniform: this row's matrix is sparse or dense)
+        const int64_t* ptr = first ? csr.ptr1 : csr.ptr2;
+        const int32_t* idx = first ? csr.idx1 : csr.idx2;
+        const float* val = first ? csr.val1 : csr.val2;
+        const float* src = ptr ? nullptr : (first ? x1 + row * ld1 : x2 + row * ld2);
+        int64_t e = 0, end = 0;
+        if (ptr) e = ptr[row], end = ptr[row + 1];
+        const float* nz = noise ? noise + (int64_t)r * ldn : nullptr;
+        float* dst = xin + (int64_t)r * ldo;
+        float* raw = nullptr;
+        if constexpr (SPLIT) raw = xt + (int64_t)r * ldt;
+        const int X4 = vec4 ? X >> 2 : 0;       // (the scalar path: no groups, every column a scalar of its chunk)
+        float sz = 1.f;
+        if constexpr (NORM) {       // (a row wider than one chunk: summed in front, from the entries / by the dense kernel's walk)
+            if (X > kCsrChunk)
+                sz = feed_size(ptr ? csr_row_partial(idx, val, e, end, X, lane) : feed_row_partial(src, X4, X4 << 2, X, lane), X);
+        }
+        for (int c0 = 0; c0 < X; c0 += kCsrChunk) {
+            const int n = X - c0 < kCsrChunk ? X - c0 : kCsrChunk;
+            if (ptr)
+                e = csr_stage_chunk(st, idx, val, e, end, c0, n, lane);
+            else
+                dense_stage_chunk(st, src, c0, n, lane);
+            csr_wave_sync();
+            const int q0 = c0 >> 2;
+            if (q0 < X4) {      // this chunk's 16-byte groups: batch_feed_kernel's outer iteration, its loads from the staged chunk
+                float4 v[4], e4[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int q = q0 + lane + 64 * u, qc = q < X4 ? q : X4 - 1;
+                    v[u] = reinterpret_cast<const float4*>(st)[qc - q0];
+                    e4[u] = nz ? reinterpret_cast<const float4*>(nz)[qc] : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
+                if constexpr (NORM) {
+                    if (X <= kCsrChunk) {        // (the whole row is staged: this is the only chunk)
+                        float acc = 0.f;
+#pragma unroll
+                        for (int u = 0; u < 4; ++u)
+                            if (lane + 64 * u < X4) acc += v[u].x, acc += v[u].y, acc += v[u].z, acc += v[u].w;
+                        for (int g = (X & ~3) + lane; g < X; g += 64) acc += st[g];
+                        sz = feed_size(acc, X);
+                    }
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int q = q0 + lane + 64 * u;
+                    if constexpr (SPLIT) {
+                        if (q < X4) reinterpret_cast<float4*>(raw)[q] = v[u];
+                        if constexpr (NORM)
+                            v[u] = make_float4(feed_Tn(v[u].x, sz), feed_Tn(v[u].y, sz), feed_Tn(v[u].z, sz),
+                                               feed_Tn(v[u].w, sz));
+                        else
+                            v[u] = make_float4(feed_T(transform, v[u].x), feed_T(transform, v[u].y), feed_T(transform, v[u].z),
+                                               feed_T(transform, v[u].w));
+                    }
+                    if (q < X4)
+                        reinterpret_cast<float4*>(dst)[q] = make_float4(fmaf(sigma, e4[u].x, v[u].x), fmaf(sigma, e4[u].y, v[u].y),
+                                                                        fmaf(sigma, e4[u].z, v[u].z), fmaf(sigma, e4[u].w, v[u].w));
+                }
+            } else if constexpr (NORM) {
+                // (no group in the row: X < 4 on the 16-byte path, or the scalar path -- the dense kernel's scalar walk)
+                if (X <= kCsrChunk) {
+                    float acc = 0.f;
+                    for (int g = lane; g < X; g += 64) acc += st[g];
+                    sz = feed_size(acc, X);
+                }
+            }
+            // the chunk's scalars: the columns behind the last group (16-byte path), or every column (scalar path)
+            const int g0 = (X4 << 2) > c0 ? (X4 << 2) : c0;
+            for (int g = g0 + lane; g < c0 + n; g += 64) {
+                const float xv = st[g - c0];
+                if constexpr (SPLIT) {
+                    const float tv = NORM ? feed_Tn(xv, sz) : feed_T(transform, xv);
+                    raw[g] = xv;
+                    dst[g] = nz ? fmaf(sigma, nz[g], tv) : tv;
+                } else {
+                    dst[g] = nz ? fmaf(sigma, nz[g], xv) : xv;
+                }
+            }
+            csr_wave_sync();        // (the next chunk's zeroes come behind this chunk's reads)
+        }
+        return;
+    }
+    DV_FEED_LABEL_BLOCKS()
+}
+#undef DV_FEED_LABEL_BLOCKS
 
 __global__ void rows_segment_sum_kernel(const float* __restrict__ src, int64_t lds,
                                         const int32_t* __restrict__ seg_ptr, const int32_t* __restrict__ seg_rows,
@@ -3945,6 +4126,16 @@ static MaskArgs mask_args(const dv_batch_masks_desc& m, const int32_t* table, in
                     m.mmd_rate, m.sched, m.c_kld, m.w_klz2, m.w_klp, m.w_elbo, m.w_cmpl};
 }
 
+// (ONE list of the feed kernels' common arguments: the variants differ in the descriptor's tail)
+#define DV_FEED_ARGS                                                                                                       \
+    d.x1, d.ld1, d.x2, d.ld2, d.y, d.table, d.n_batches, d.ctr, d.base, B, d.pair_rows, Np, d.X, d.noise, d.ldn, d.sigma,  \
+        d.xin, d.ldo, d.has_y, L, d.label_r, d.fp_i, d.fp_lab, d.fp_slot, Mf, d.fp_cls, d.onehot, d.ldh, d.Y, row_blocks,  \
+        v4 ? 1 : 0, d.yf, d.ylab, d.Yc, d.onehot2, d.ldh2, mask_block, ma, park
+// the sparse feed's launches: defined at the END of this file -- the templates a host function launches are emitted in the order
+// of their first use, so the sparse instantiations come last in the code object and every kernel that was there keeps its place
+static void launch_batch_feed_csr(const dv_batch_feed_desc& d, dim3 grid, dim3 block, int row_blocks, bool v4, int mask_block,
+                                  const MaskArgs& ma, const ParkArgs& park, dv_stream_t stream);
+
 extern "C" int dv_batch_feed(const dv_batch_feed_desc* dsc, const dv_batch_masks_desc* masks, const dv_wait* park_in,
                              dv_stream_t stream) {
     DV_REQUIRE(dsc != nullptr && park_ok(park_in));      // (a malformed wait is refused even where B == 0 launches nothing)
@@ -3952,8 +4143,12 @@ extern "C" int dv_batch_feed(const dv_batch_feed_desc* dsc, const dv_batch_masks
     const int B = d.B, Np = d.Np, L = d.L, Mf = d.Mf;
     DV_REQUIRE(B >= 0 && Np >= 0 && d.X >= 0 && d.n_batches >= 1 && L >= 1 && Mf >= 0 && d.Y >= 0 && d.Yc >= 0);
     DV_REQUIRE(!d.ylab || (d.yf && d.Yc >= 1));
+    // sparse rows: a CSR triple is whole or absent, and a matrix is dense or sparse, never both
+    const bool s1 = d.csr1_ptr != nullptr, s2 = d.csr2_ptr != nullptr;
+    DV_REQUIRE(s1 == (d.csr1_idx != nullptr) && s1 == (d.csr1_val != nullptr) && !(s1 && d.x1));
+    DV_REQUIRE(s2 == (d.csr2_idx != nullptr) && s2 == (d.csr2_val != nullptr) && !(s2 && d.x2));
     if (B == 0) return DV_OK;
-    DV_REQUIRE(d.x1 && d.table && d.ctr && d.base && d.xin && (Np == 0 || (d.x2 && d.pair_rows)));
+    DV_REQUIRE((d.x1 || s1) && d.table && d.ctr && d.base && d.xin && (Np == 0 || ((d.x2 || s2) && d.pair_rows)));
     DV_REQUIRE(!d.label_r || (d.y && d.has_y));
     DV_REQUIRE(!d.fp_cls || Mf == 0 || (d.y && d.fp_i && d.fp_lab && d.fp_slot));
     // split form (raw-count inputs): targets to xt, encoder rows T(x) + sigma*noise to xin
@@ -3964,8 +4159,9 @@ extern "C" int dv_batch_feed(const dv_batch_feed_desc* dsc, const dv_batch_masks
     int nlab = (d.label_r ? L * B : 0) > (d.fp_cls ? Mf : 0) ? (d.label_r ? L * B : 0) : (d.fp_cls ? Mf : 0);
     if (d.ylab && B * d.Yc > nlab) nlab = B * d.Yc;
     const int lab_blocks = (nlab + 255) / 256;
-    const bool v4 = aligned16(d.x1) && (Np == 0 || aligned16(d.x2)) && aligned16(d.xin) && (!d.noise || aligned16(d.noise)) &&
-                    d.ld1 % 4 == 0 && (Np == 0 || d.ld2 % 4 == 0) && d.ldo % 4 == 0 && (!d.noise || d.ldn % 4 == 0) &&
+    // (a sparse matrix has no dense rows to align: its rows are read from the wave's staged chunk)
+    const bool v4 = (s1 || (aligned16(d.x1) && d.ld1 % 4 == 0)) && (Np == 0 || s2 || (aligned16(d.x2) && d.ld2 % 4 == 0)) &&
+                    aligned16(d.xin) && (!d.noise || aligned16(d.noise)) && d.ldo % 4 == 0 && (!d.noise || d.ldn % 4 == 0) &&
                     (!d.xt || d.ldt % 4 == 0);
     MaskArgs ma{};
     if (masks) {
@@ -3977,18 +4173,14 @@ extern "C" int dv_batch_feed(const dv_batch_feed_desc* dsc, const dv_batch_masks
     if (int rc = take_park(park_in, feed_blocks + 1, &park)) return rc;
     const dim3 grid(feed_blocks + (masks ? 1 : 0)), block(256);
     const int mask_block = masks ? feed_blocks : -1;
-    // (ONE list of the common arguments: the two variants differ in the three of the descriptor's tail)
-#define DV_FEED_ARGS                                                                                                       \
-    d.x1, d.ld1, d.x2, d.ld2, d.y, d.table, d.n_batches, d.ctr, d.base, B, d.pair_rows, Np, d.X, d.noise, d.ldn, d.sigma,  \
-        d.xin, d.ldo, d.has_y, L, d.label_r, d.fp_i, d.fp_lab, d.fp_slot, Mf, d.fp_cls, d.onehot, d.ldh, d.Y, row_blocks,  \
-        v4 ? 1 : 0, d.yf, d.ylab, d.Yc, d.onehot2, d.ldh2, mask_block, ma, park
-    if (d.xt && d.transform == 3)
+    if (s1 || (s2 && Np > 0))        // a matrix that is read is sparse: the sibling kernel, chosen by the descriptor alone
+        launch_batch_feed_csr(d, grid, block, row_blocks, v4, mask_block, ma, park, stream);
+    else if (d.xt && d.transform == 3)
         hipLaunchKernelGGL((batch_feed_kernel<true, true>), grid, block, 0, ST(stream), DV_FEED_ARGS, d.xt, d.ldt, d.transform);
     else if (d.xt)
         hipLaunchKernelGGL((batch_feed_kernel<true, false>), grid, block, 0, ST(stream), DV_FEED_ARGS, d.xt, d.ldt, d.transform);
     else
         hipLaunchKernelGGL((batch_feed_kernel<false, false>), grid, block, 0, ST(stream), DV_FEED_ARGS, nullptr, 0, 0);
-#undef DV_FEED_ARGS
     DV_RETURN_LAUNCH();
 }
 
@@ -4263,3 +4455,18 @@ extern "C" int dv_axpby(const float* x, float a, float* y, float b, int64_t n, d
     hipLaunchKernelGGL(axpby_kernel, dim3(grid_for(n, 256)), dim3(256), 0, ST(stream), x, a, y, b, n);
     DV_RETURN_LAUNCH();
 }
+
+
+// (see the declaration in front of dv_batch_feed: last in the file on purpose)
+static void launch_batch_feed_csr(const dv_batch_feed_desc& d, dim3 grid, dim3 block, int row_blocks, bool v4, int mask_block,
+                                  const MaskArgs& ma, const ParkArgs& park, dv_stream_t stream) {
+    const int B = d.B, Np = d.Np, L = d.L, Mf = d.Mf;
+    const CsrArgs csr{d.csr1_ptr, d.csr1_idx, d.csr1_val, d.csr2_ptr, d.csr2_idx, d.csr2_val};
+    if (d.xt && d.transform == 3)
+        hipLaunchKernelGGL((batch_feed_csr_kernel<true, true>), grid, block, 0, ST(stream), DV_FEED_ARGS, d.xt, d.ldt, d.transform, csr);
+    else if (d.xt)
+        hipLaunchKernelGGL((batch_feed_csr_kernel<true, false>), grid, block, 0, ST(stream), DV_FEED_ARGS, d.xt, d.ldt, d.transform, csr);
+    else
+        hipLaunchKernelGGL((batch_feed_csr_kernel<false, false>), grid, block, 0, ST(stream), DV_FEED_ARGS, nullptr, 0, 0, csr);
+}
+#undef DV_FEED_ARGS

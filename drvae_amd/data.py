@@ -17,10 +17,17 @@ import numpy as np
 import torch
 
 from . import kernels as K
+from .sparse_rows import CsrRows
+
+
+def _rows_to(x, device):
+    """a dataset's ``x1`` / ``x2`` on ``device`` as the feed reads it: contiguous fp32, or the three arrays of a ``CsrRows``"""
+    return x.to(device) if isinstance(x, CsrRows) else x.to(device, torch.float32).contiguous()
 
 
 class DrVAEDataset(torch.utils.data.Dataset):
-    """``(x1, x2, s, y, has_x2, has_y)`` rows (src/DrVAE.py:880-905)."""
+    """``(x1, x2, s, y, has_x2, has_y)`` rows (src/DrVAE.py:880-905).  ``x1`` and / or ``x2`` may be a ``CsrRows`` (sparse counts:
+    the device batch feed reads the CSR arrays themselves); ``__getitem__`` returns dense rows either way."""
 
     FIELDS = ('x1', 'x2', 's', 'y', 'has_x2', 'has_y')
 
@@ -37,14 +44,13 @@ class DrVAEDataset(torch.utils.data.Dataset):
         return self.x1.size(0)
 
     def to(self, device):
-        """HBM-resident copy (x1/x2 as contiguous fp32: the gather kernels read them in place)."""
-        return DrVAEDataset(self.x1.to(device, torch.float32).contiguous(),
-                            self.x2.to(device, torch.float32).contiguous(), self.s.to(device), self.y.to(device),
+        """HBM-resident copy (x1/x2 as contiguous fp32, or as their CSR arrays: the gather kernels read them in place)."""
+        return DrVAEDataset(_rows_to(self.x1, device), _rows_to(self.x2, device), self.s.to(device), self.y.to(device),
                             self.has_x2.to(device), self.has_y.to(device))
 
 
 class VFAEDataset(torch.utils.data.Dataset):
-    """``(x1, s, y, has_y)`` rows (src/VFAE.py:658-680)."""
+    """``(x1, s, y, has_y)`` rows (src/VFAE.py:658-680).  ``x1`` may be a ``CsrRows``, as in ``DrVAEDataset``."""
 
     def __init__(self, x1, s, y, has_y):
         n = x1.size(0)
@@ -56,6 +62,10 @@ class VFAEDataset(torch.utils.data.Dataset):
 
     def __len__(self):
         return self.x1.size(0)
+
+    def to(self, device):
+        """HBM-resident copy, as ``DrVAEDataset.to``"""
+        return VFAEDataset(_rows_to(self.x1, device), self.s.to(device), self.y.to(device), self.has_y.to(device))
 
 
 def wrap_in_DrVAEDataset(sing, pair, y_key='y', concat='both', downlabel_to=None, remove_unlabeled=False):
@@ -121,6 +131,10 @@ def require_counts(ds, what):
         x = getattr(ds, name, None)
         if x is None or not len(x):
             continue
+        if isinstance(x, CsrRows):      # (the entries that are not stored are zeros)
+            if not x.nnz:
+                continue
+            x = x.val
         lo = float(torch.as_tensor(x).min())
         if not lo >= 0.0:      # (NaN fails this too)
             raise ValueError('%s: x_transform / library_size need count data, x >= 0; the minimum of %s is %r' % (what, name, lo))
@@ -281,6 +295,9 @@ class DeviceBatcher:
             if dp is not None:
                 engine.row0 = dp[0] * self.batch_size
             return engine.plan          # (every epoch of ``fit`` binds: nothing to rebuild)
+        for name in ('x1', 'x2'):   # sparse rows: the structure the feed relies on (checked once per object, on the device)
+            if isinstance(getattr(self.dataset, name, None), CsrRows):
+                getattr(self.dataset, name).check()
         if engine.cfg.split_x:      # raw-count inputs: log1p and the size factor want x >= 0 (checked once per dataset, here)
             require_counts(self.dataset, 'DeviceBatcher.bind')
         if engine.cfg.dispersion == 'gene-batch':      # (a theta per class: the classes are in range, checked once too)
@@ -467,8 +484,8 @@ class DeviceBatcher:
         steps keep reading the same buffer (round-4 advisor: train and evaluation must see the same data)"""
         for name in ('x1', 'x2'):
             x, cur = getattr(self.ds, name, None), getattr(fd, name, None)
-            if x is None or cur is None or cur.data_ptr() == x.data_ptr():
-                continue
+            if x is None or cur is None or isinstance(x, CsrRows) or cur.data_ptr() == x.data_ptr():
+                continue        # (sparse rows: the feed reads the dataset's own arrays -- nothing to refresh)
             seen = self.__dict__.setdefault('_rows_version', {})
             if seen.get(name) != (x.data_ptr(), x._version):
                 cur.copy_(x)
@@ -478,8 +495,8 @@ class DeviceBatcher:
         """the dataset as the graph-resident feed reads it: fp32 rows 16-B aligned -- a copy with padded rows when the gene
         count is no multiple of 4 (978): the feed's row gather is then 16-B loads instead of 4-B ones (epoch feed 0.1932 ->
         0.1916 ms per step).  Kept current by ``_refresh_feed_rows`` when the dataset is edited in place"""
-        if x is None or x.device.type != 'cuda':
-            return x
+        if x is None or isinstance(x, CsrRows) or x.device.type != 'cuda':
+            return x            # (sparse rows go through untouched: no padded copy)
         if x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0:
             return x
         if x.dim() != 2 or x.numel() * 4 > (2 << 30):
@@ -623,9 +640,11 @@ class DeviceBatcher:
                                                  self.hy32[idx].sum() if self.engine.cfg.has_y else zero]))
             idx = idx.reshape(self.world, self.batch_size)[self.rank]
         self._idx32.copy_(idx)
-        K.rows_gather(p.XSRC[:p.B], self.ds.x1, self._idx32)
-        if self.engine.cfg.has_pert:
-            K.rows_gather(p.XSRC[p.B:], self.ds.x2, self._idx32)
+        for out, x in ((p.XSRC[:p.B], self.ds.x1),) + (((p.XSRC[p.B:], self.ds.x2),) if self.engine.cfg.has_pert else ()):
+            if isinstance(x, CsrRows):
+                x.gather_rows(out, self._idx32)
+            else:
+                K.rows_gather(out, x, self._idx32)
         if self.engine.cfg.use_s:           # one-hot(s) columns of the encoder / decoder inputs (device to device)
             p.set_s_device(self.ds.s.reshape(-1)[idx])
         if self.mode == 'sampler':          # group membership of THIS batch: data for dv_batch_masks

@@ -18,6 +18,7 @@ import torch
 
 from . import engine as E
 from . import metrics as MET
+from .sparse_rows import CsrRows
 
 
 class EarlyStopping:
@@ -199,7 +200,16 @@ class FitMixin:
         ev = None if return_full_data else _EvalGraph.get(self, ds)
         if ev is not None:
             return ev.run()
-        return self._evaluate(g('x1'), g('x2'), g('s'), g('y'), g('has_x2'), g('has_y'), return_full_data)
+
+        def rows(k):
+            # sparse rows (``CsrRows``): the step-by-step path on a TRANSIENT dense copy -- one feed launch (``gather_rows``)
+            # writes the whole set; the copy lives for the duration of this evaluation
+            x = g(k)
+            if not isinstance(x, CsrRows):
+                return x
+            out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+            return x.gather_rows(out, torch.arange(x.shape[0], dtype=torch.int32, device=x.device))
+        return self._evaluate(rows('x1'), rows('x2'), g('s'), g('y'), g('has_x2'), g('has_y'), return_full_data)
 
     # ------------------------------------------------------------- the objective
     def _valid_objective(self, perf):
@@ -474,6 +484,8 @@ class _EvalGraph:
     def get(model, ds):
         from . import kernels as K
         x1 = getattr(ds, 'x1', None)
+        if isinstance(x1, CsrRows) or isinstance(getattr(ds, 'x2', None), CsrRows):
+            return None          # (sparse rows: the captured evaluation reads dense matrices in place -- declined)
         if not (torch.is_tensor(x1) and x1.is_cuda):
             return None
         if next(model.parameters()).device != x1.device:

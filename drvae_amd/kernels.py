@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import ACT, EPI_BWD, EPI_FWD, EPI_KLQ, EPI_PLAIN, GAUSS_LOGVAR, GAUSS_SIGMA, GemmDesc  # noqa: F401
+from .sparse_rows import CsrRows
 
 
 def _stream():
@@ -967,6 +968,15 @@ def _masks_desc(m, B):
 FEED_TRANSFORM = {None: 0, 'log1p': 1, 'log1p_norm': 3}      # dv_batch_feed_desc.transform (2 is no code: refused)
 
 
+def _csr_fields(m):
+    """``CsrRows`` -> the (ptr, idx, val) addresses of dv_batch_feed_desc's csr1_* / csr2_* fields"""
+    if not (m.ptr.is_cuda and m.ptr.dtype == torch.int64 and m.ptr.is_contiguous()):
+        raise RuntimeError('CsrRows.ptr must be a contiguous CUDA int64 tensor (CsrRows.to(device))')
+    if m.nnz == 0:      # (no entry is ever read: any address completes the triple -- an empty tensor has none of its own)
+        return m.ptr.data_ptr(), m.ptr.data_ptr(), m.ptr.data_ptr()
+    return m.ptr.data_ptr(), _i32(m.idx, 'CsrRows.idx'), _f32(m.val, 'CsrRows.val')
+
+
 def batch_feed(xin, x1, x2, y32, table, n_batches, ctr, base, *, pair_rows=None, noise=None, sigma=0.0, has_y=None,
                L=1, label_r=None, fp_i=None, fp_lab=None, fp_slot=None, fp_cls=None, onehot=None, n_classes=0, yf=None,
                ylab=None, onehot2=None, masks=None, park=None, xt=None, transform=None):
@@ -980,6 +990,10 @@ def batch_feed(xin, x1, x2, y32, table, n_batches, ctr, base, *, pair_rows=None,
     Np = pair_rows.numel() if pair_rows is not None else 0
     assert xin.shape[0] == B + Np and table.shape[0] == n_batches and table.is_contiguous()
     Mf = fp_cls.numel() if fp_cls is not None else 0
+    # (a ``CsrRows`` for x1 / x2: the matrix goes in as its CSR triple -- the descriptor's trailing fields -- not as a dense pointer)
+    csr1, csr2 = (x1 if isinstance(x1, CsrRows) else None), (x2 if (isinstance(x2, CsrRows) and Np) else None)
+    x1, x2 = (None if csr1 is not None else x1), (None if isinstance(x2, CsrRows) else x2)
+    assert all(c is None or c.shape[1] == xin.shape[1] for c in (csr1, csr2))
     d = _lib.BatchFeed(x1=_f32(x1), ld1=_ld(x1), x2=_f32(x2) if Np else None, ld2=_ld(x2) if Np else 0, y=_i32(y32),
                        table=_i32(table), n_batches=n_batches, ctr=_i32(ctr), base=_i32(base), B=B,
                        pair_rows=_i32(pair_rows), Np=Np, X=xin.shape[1], noise=_f32(noise), ldn=_ld(noise), sigma=sigma,
@@ -990,6 +1004,10 @@ def batch_feed(xin, x1, x2, y32, table, n_batches, ctr, base, *, pair_rows=None,
     if xt is not None or transform is not None:
         assert xt is None or tuple(xt.shape) == tuple(xin.shape)
         d.xt, d.ldt, d.transform = _f32(xt), _ld(xt), FEED_TRANSFORM[transform]
+    if csr1 is not None:
+        d.csr1_ptr, d.csr1_idx, d.csr1_val = _csr_fields(csr1)
+    if csr2 is not None:
+        d.csr2_ptr, d.csr2_idx, d.csr2_val = _csr_fields(csr2)
     _lib.check(_lib.load().dv_batch_feed(C.byref(d), C.byref(md) if md is not None else None, _wait(park), _stream()),
                'dv_batch_feed')
 

@@ -809,6 +809,25 @@ int dv_rows_gather(const float* src, int64_t lds, const int32_t* idx, int32_t n,
  * ctr = base = a zero word, x1 / x2 = the two halves of the plan's source rows and no label outputs (y, has_y, label_r,
  * fp_* all NULL: the argument checks never required them without label outputs, so none had to be relaxed), so host-fed
  * and graph-resident steps form their inputs with one kernel and agree bit for bit. */
+/* sparse rows (CSR; the six trailing fields csr1_* / csr2_* of the descriptor, all NULL: the launch as it was, bit for bit).
+ * With csr1_ptr given, matrix 1 is held as CSR rows instead of a dense x1: `csr1_ptr` = N + 1 int64 row offsets (nnz may
+ * exceed 2^31), `csr1_idx` = int32 column indices, strictly increasing inside a row, `csr1_val` = the fp32 values; x1 must
+ * then be NULL and ld1 is not read.  csr2_* / x2 / ld2 likewise and independently: one matrix may be dense, the other sparse.
+ * The source row of output row r is the same table / pair_rows indexing, and every other output and rider (labels, fp_*,
+ * one-hots, ylab, the masks workgroup, park, ctr / base and the batch clamp) is unchanged.  The row's wave stages the row
+ * through LDS in chunks of 1024 columns (zeroes its chunk, scatters the row's entries whose column falls inside it, waits
+ * for its own LDS writes) and reads from there the very 16-byte groups / scalars the dense launch loads from HBM; all that
+ * follows -- the xt store, T, fmaf(sigma, noise, T(x)), the store pattern, both access paths (16-byte when xin / noise / xt
+ * rows are 16-byte aligned, scalar for any X >= 1 at any alignment) -- is the dense launch's code, so the outputs are the
+ * bits the dense launch writes for the densified matrix.  `transform` == 3: rows of up to 1024 columns are summed from the
+ * staged row in the dense launch's order (equal bits for any values); wider rows from the CSR values -- lane partials in
+ * index order, then the wave sum: exact, and so bit-equal, for integer counts with a row total below 2^24 (the caveat stated
+ * for s above).  Memory contract: the kernel reads ptr[row], ptr[row + 1] and the entries between them, writes exactly the X
+ * columns of the output rows, and SKIPS an entry whose column is outside [0, X) -- never stores it; the caller validates the
+ * structure once (sorted rows without duplicates, columns in range), the skip only makes a caller's error harmless.  No
+ * atomics: repeated launches give equal bits.  16 KiB of static LDS per workgroup, in the sparse instantiations only.
+ * DV_ERR_ARG, before any launch and at B == 0 too: an incomplete triple (some but not all of ptr / idx / val), a matrix with
+ * both a dense pointer and a triple; and, where rows are read (B > 0; Np > 0 for matrix 2), a matrix with neither. */
 /* `park` (optional): the launch first parks like dv_flag_wait -- the first launch of a step waiting for the previous
  * step's other launch chain (DV_ERR_UNSUPPORTED for grids above DV_MAX_PARKED_GRID workgroups). */
 typedef struct dv_batch_masks_desc {
@@ -884,6 +903,13 @@ typedef struct dv_batch_feed_desc {
     float* xt;
     int64_t ldt;
     int32_t transform;
+    /* sparse rows (trailing fields; all NULL: the launch as it was) -- see "sparse rows" above */
+    const int64_t* csr1_ptr;
+    const int32_t* csr1_idx;
+    const float* csr1_val;
+    const int64_t* csr2_ptr;
+    const int32_t* csr2_idx;
+    const float* csr2_val;
 } dv_batch_feed_desc;
 int dv_batch_feed(const dv_batch_feed_desc* d, const dv_batch_masks_desc* masks, const dv_wait* park,
                   dv_stream_t stream);
