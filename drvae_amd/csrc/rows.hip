@@ -3145,7 +3145,7 @@ __global__ __launch_bounds__(256) void pair_counts_kernel(const float* __restric
 }
 
 // per class c (one workgroup each): out[c*2 + 0] = ROC-AUC, out[c*2 + 1] = average precision (nan / 0 for the degenerate
-// cases like metrics.roc_auc / average_precision); class 0's workgroup also writes acc -> out[2*n_cls].  Zeroes the
+// cases like metrics.roc_auc / average_precision); class 0's workgroup also writes acc -> out[2*n_cls] (nan without pred).  Zeroes the
 // counts it has read: the buffer is ready for the next evaluation.
 __global__ __launch_bounds__(1024) void rank_finalize_kernel(int32_t* __restrict__ counts, const int32_t* __restrict__ y,
                                                              const int32_t* __restrict__ pred, const int32_t* __restrict__ sel,
@@ -3191,7 +3191,8 @@ __global__ __launch_bounds__(1024) void rank_finalize_kernel(int32_t* __restrict
         const long long np = t[1], nn = (long long)n - np;
         out[2 * c + 0] = (n == 0 || np == 0 || nn == 0) ? nan : ((double)t[0] * 0.5) / ((double)np * (double)nn);
         out[2 * c + 1] = (n == 0 || np == 0) ? 0.0 : a / (double)np;
-        if (c == 0) out[2 * n_cls] = n ? (double)((float)t[2] / (float)n) : nan;
+        // (no prediction given is not "0 % correct": nan, like no rows)
+        if (c == 0) out[2 * n_cls] = (n && pred) ? (double)((float)t[2] / (float)n) : nan;
     }
 }
 

@@ -1192,7 +1192,8 @@ int dv_mmd_masked_bwd(const dv_mmd_masked_desc* d, dv_stream_t stream);
  *   above), then   AUC = sum_{negatives j} (#pos above j + #pos tied with j / 2) / (n_pos n_neg)   (integer sums: exact)
  *                  AP  = 1/n_pos sum_{positives i} #pos(score >= s_i) / #rows(score >= s_i)
  *   positive = binary ? y > 0 : y == c; score = proba[row, c].  out[2c] = AUC (nan: one class only / empty), out[2c + 1]
- *   = AP (0: no positive), out[2 n_cls] = accuracy mean(pred == y) (pred optional).  `counts` (n_cls x n x 4 int32) must
+ *   = AP (0: no positive), out[2 n_cls] = accuracy mean(pred == y), hits / n in fp32 (pred optional: nan without one, as
+ *   for n = 0 -- "none given" is not "0 % correct").  `counts` (n_cls x n x 4 int32) must
  *   be zero on entry and is zero again on return.  Deterministic. */
 #define DV_RANK_MAX_ROWS 32768
 int dv_recon_finalize(const float* rows, const int32_t* sel, int32_t n, int32_t X, const double* cols, int32_t row_blocks,

@@ -1128,13 +1128,14 @@ def recon_rows(rows, ll, x, mu, sd, *, bias=None, sd_shift=1e-3, kind=None, size
 
 
 def recon_finalize(out4, rows, part, X, *, sel=None, n=None, ll=None):
-    r = (rows[sel.long()] if sel is not None else rows).double()
-    n = r.shape[0] if n is None else n
+    n = (sel.numel() if sel is not None else rows.shape[0]) if n is None else n
+    idx = sel.long()[:n] if sel is not None else torch.arange(n, device=rows.device)      # (sel NULL: rows 0..n-1)
+    r = rows[idx].double()
     cols = part.sum(0)
     out4[0] = torch.sqrt(r[:, 0].sum() / (n * X)) if n else float('nan')
     out4[1] = 1.0 - cols[2].sum() / (cols[1] - cols[0] ** 2 / n).sum()
     out4[2] = (r[:, 5] / torch.sqrt(r[:, 3] * r[:, 4])).mean() if n else float('nan')
-    out4[3] = (ll[sel.long()] if sel is not None else ll).double().mean() if (ll is not None and n) else float('nan')
+    out4[3] = ll[idx].double().mean() if (ll is not None and n) else float('nan')
 
 
 RANK_MAX_ROWS = 32768
