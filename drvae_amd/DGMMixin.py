@@ -37,7 +37,8 @@ class DeepGenerativeModelMixin:
             raise ValueError('Selected unknown optimizer: ' + str(self.optim_alg))
         self.optimizer = None          # kept for attribute parity; the state lives in the arena
         self._engine = None
-        for key in ('_eval_graphs', '_eval_graphs_own_kind'):      # (``fit._EvalGraph.CACHE_KEYS``)
+        # (``fit._EvalGraph.CACHE_KEYS`` and ``fit._ChunkedEval.CACHE_KEY``)
+        for key in ('_eval_graphs', '_eval_graphs_own_kind', '_eval_chunked'):
             self.__dict__.pop(key, None)
 
     def _step_config(self):
@@ -188,7 +189,8 @@ class DeepGenerativeModelMixin:
         if getattr(self, '_engine', None) is not None and not self._arena_aliased():
             self._stash_optimizer_state()
             self._engine = self._arena = None      # rebuilt (and the parameters re-adopted) by engine()
-            for key in ('_eval_graphs', '_eval_graphs_own_kind'):      # (captured evaluations point into the retired arena / plans)
+            # (captured evaluations point into the retired arena / plans: the one-replay ones and the row-chunked ones)
+            for key in ('_eval_graphs', '_eval_graphs_own_kind', '_eval_chunked'):
                 self.__dict__.pop(key, None)
         return out
 
@@ -196,6 +198,7 @@ class DeepGenerativeModelMixin:
         if getattr(self, '_engine', None) is not None:
             self._engine._refuse_averaged('load_state_dict')
         out = super().load_state_dict(state_dict, strict=strict, assign=assign)
+        self.__dict__.pop('_eval_chunked', None)      # (row-chunked evaluators are rebuilt for reloaded parameters)
         if assign and getattr(self, '_engine', None) is not None and not self._arena_aliased():
             self._arena.adopt(self)                # values copied into the arena, parameters aliased again
         if getattr(self, '_engine', None) is not None:

@@ -36,7 +36,11 @@ class VFAE(ELBOModel):
     theta head by ONE inverse dispersion per gene, the parameter ``decoder_x.decoder_t.raw_theta`` (theta = softplus + 1e-3, started at
     0); ``px1`` / ``px2`` keep their shape, theta expanded to (rows, dim_x).  'gene-batch' (``use_s=True`` only, else
     ``ValueError``): one inverse dispersion per (gene, nuisance class) -- the same parameter as a (dim_s, dim_x) table, a row of class k
-    reads row k (the x2 rows of a pair: the class of their batch row).  Labelled extension."""
+    reads row k (the x2 rows of a pair: the class of their batch row).  Labelled extension.
+    ``eval_chunk_rows`` (default None; an integer >= 1, also a plain attribute): ``evaluate_performance_on_dataset`` -- and so ``fit`` --
+    evaluates a device-resident set in row chunks of at most so many rows: the whole set's numbers in device memory that
+    holds ``eval_chunk_rows`` x dim_x buffers and per-row arrays only; a ``CsrRows`` set is never densified beyond a chunk.
+    ``use_MMD`` models and data parallelism raise ``NotImplementedError``, anything but None or such an integer ``ValueError``."""
     kind = 'vfae'
     fit_patience = 40       # src/VFAE.py:536
 
@@ -49,7 +53,7 @@ class VFAE(ELBOModel):
                  random_seed=12345, log_txt=None, weight_norm=False, device=None, matmul_precision='fp32',
                  max_grad_norm=None, anneal_kl=False, anneal_kl_itermax=100, anneal_yloss=False, anneal_yloss_itermax=1,
                  anneal_learning_rate=False, anneal_lr_itermax=3000, ema_decay=None,
-                 x_transform=None, library_size=False, dispersion='gene-cell'):
+                 x_transform=None, library_size=False, dispersion='gene-cell', eval_chunk_rows=None):
         super().__init__()
         args = dict(locals())
         args.pop('self')

@@ -47,6 +47,9 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         # None | a number in (0, 1): the exponential moving average of the parameters kept by the optimiser sweep, see
         # ``StepConfig.ema_decay``; ``ema_eval``: ``fit`` evaluates and snapshots the averaged weights (default) or the live ones
         ema_decay = E.check_ema_decay(args.pop('ema_decay', None))
+        # None | an integer >= 1: ``evaluate_performance_on_dataset`` (and so ``fit``) evaluates a device-resident set in row
+        # chunks of at most so many rows, in device memory that does not grow with rows x genes (``fit._ChunkedEval``)
+        eval_chunk_rows = args.pop('eval_chunk_rows', None)
         # raw-count inputs (EXTENSIONS, count decoders only; ``StepConfig.x_transform`` / ``library_size``): the encoder reads
         # log1p(x) while the likelihood keeps the raw counts; every decoder mean is scaled by the row's observed size factor
         x_transform, library_size = args.pop('x_transform', None), args.pop('library_size', False)
@@ -59,6 +62,11 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         for k, v in anneal.items():
             setattr(self, k, v)
         self.ema_decay, self.ema_eval = ema_decay, True
+        self.eval_chunk_rows = eval_chunk_rows
+        if eval_chunk_rows is not None:      # (what the configuration alone decides is refused here: ValueError / NotImplementedError)
+            from .fit import _ChunkedEval
+            _ChunkedEval.check_chunk_rows(eval_chunk_rows)
+            _ChunkedEval.check_model(self)
         self.x_transform, self.library_size = x_transform, library_size
         self._counts_config()           # (a bad value, or a switch on a decoder that is no count decoder: ValueError)
         if not hasattr(self, 'anneal_yloss_offset'):

@@ -183,7 +183,7 @@ class FitMixin:
             for k in ('qz1mu_qz2mu_rmse', 'pz2Fz1mu_qz2mu_rmse', 'KL_qz2_qz1', 'KL_qz2_pz2Fz1'):
                 perf[k] = np.nan
 
-    def evaluate_performance_on_dataset(self, ds, return_full_data=False):
+    def evaluate_performance_on_dataset(self, ds, return_full_data=False, chunk_rows=None):
         """Whole-set evaluation (src/DrVAE.py:797,821 call it on the train and on the validation set every epoch).  For
         an HBM-resident dataset it is ONE hipGraph replay and ONE device->host copy: eval-mode losses, means-only
         inference, reconstruction statistics and the prediction metrics captured once per (model, dataset) -- see
@@ -195,7 +195,21 @@ class FitMixin:
         log-likelihood for ``'zinb'`` (its statistics are taken at the negative-binomial mean, never at (1 - pi) times it) and
         nan for the other two, as on the step-by-step path).  ``return_full_data`` (arrays for the caller), host datasets and the
         other MMD kernels take the step-by-step path (``'nb'``: ``x1_rec`` / ``x2_pert`` are the means, ``px1`` = (mu, theta);
-        ``'zinb'``: the negative-binomial means, ``px1`` = (mu, theta, dropout logit))."""
+        ``'zinb'``: the negative-binomial means, ``px1`` = (mu, theta, dropout logit)).
+
+        ``chunk_rows`` (default: ``self.eval_chunk_rows``; None: everything above, unchanged): an integer C >= 1 evaluates the
+        set in row chunks of at most C rows -- the same (perf, text), the whole set's numbers, in device memory that holds
+        C x dim_x buffers and per-row arrays only; a ``CsrRows`` matrix is never densified beyond a chunk (``_ChunkedEval``).
+        Refused, never answered by another path: ``use_MMD`` models and data parallelism (``NotImplementedError``), a
+        host-resident set, ``return_full_data=True``, any other value of C (``ValueError``)."""
+        if chunk_rows is None:
+            chunk_rows = getattr(self, 'eval_chunk_rows', None)
+        if chunk_rows is not None:
+            chunk_rows = _ChunkedEval.check_chunk_rows(chunk_rows)
+            if return_full_data:
+                raise ValueError('evaluate_performance_on_dataset: return_full_data=True returns rows x genes arrays; it cannot '
+                                 'be combined with a chunk size (chunk_rows / eval_chunk_rows = %d)' % chunk_rows)
+            return _ChunkedEval.get(self, ds, chunk_rows).run()
         g = lambda k: getattr(ds, k, None)
         ev = None if return_full_data else _EvalGraph.get(self, ds)
         if ev is not None:
@@ -716,15 +730,20 @@ class _EvalGraph:
         if kind != 'pvae':
             self.full_yidx32 = torch.nonzero(full.has_y.reshape(-1).to(dev)).reshape(-1).to(torch.int32)
         blk1 = max(K.col_moment_blocks(b - a) for a, b in bounds)
+        self.blk = {'x1': blk1, 'x2': blk2}
+        self._alloc_full(n, X, Y, world * blk1, world * blk2, dev)
+
+    def _alloc_full(self, n, X, Y, n_part1, n_part2, dev):
+        """the flat float64 buffer of the WHOLE set's partials -- ``n_part1`` / ``n_part2`` column-moment blocks for x1 / x2 --
+        and the complete per-row arrays the finalising launches read (``_finalize_full``)"""
         o, self.off = 0, {}
         # (regression head: the ``pred`` slot carries the n x Y float means; no class probabilities, no int32 buffers)
         for name, size in (('loss', 8), ('proba', 0 if self.cont else n * Y), ('pred', n * Y if self.cont else (n if Y else 0)),
                            ('rows1', n * 6), ('ll1', n),
-                           ('part1', world * blk1 * 3 * X), ('rows2', n * 6 if self.full_n_x2 else 0),
-                           ('ll2', n if self.full_n_x2 else 0), ('part2', world * blk2 * 3 * X if self.full_n_x2 else 0)):
+                           ('part1', n_part1 * 3 * X), ('rows2', n * 6 if self.full_n_x2 else 0),
+                           ('ll2', n if self.full_n_x2 else 0), ('part2', n_part2 * 3 * X if self.full_n_x2 else 0)):
             self.off[name] = (o, size)
             o += size
-        self.blk = {'x1': blk1, 'x2': blk2}
         self.pack = torch.zeros(o, dtype=torch.float64, device=dev)
         f32 = lambda *shape: torch.zeros(*shape, device=dev)
         self.g_rows = {'x1': f32(n, 6), 'x2': f32(n, 6)}
@@ -1011,7 +1030,11 @@ class _EvalGraph:
             from . import dist as D
             D.allreduce_sum(self.pack)
             self.graph_final.replay()
-        v = dict(zip(self.names, self.vec.cpu().tolist()))  # THE host sync of the evaluation
+        return self._report(dict(zip(self.names, self.vec.cpu().tolist())))  # THE host sync of the evaluation
+
+    def _report(self, v):
+        """(perf, text) of ``evaluate_performance_on_dataset`` from the evaluation's scalars by name"""
+        m, kind = self.model, self.model.kind
         perf = OrderedDict()
         perf['losses'] = OrderedDict((k, torch.tensor(v['loss_' + k])) for k in self.loss_keys)
         parts = []
@@ -1037,3 +1060,347 @@ class _EvalGraph:
                 parts.append('X2: no x2 data')
         perf['model_class'] = m.__class__.__name__
         return perf, '\t '.join(parts)
+
+
+# ------------------------------------------------------------------------------------- whole-set evaluation in row chunks
+_CHUNK_GROUPS = ((True, True), (True, False), (False, True), (False, False))      # (has_x2, has_y): the stable order of the groups
+
+
+def chunk_partition(has_x2, has_y, C, kind):
+    """the rows of a data set as chunks of at most ``C`` rows that are homogeneous in (has_x2, has_y): a list of
+    ((has_x2, has_y), row positions) -- the groups in the order of ``_CHUNK_GROUPS``, the rows of a group in data-set order, cut
+    every ``C`` rows.  Every row is in exactly one chunk.  A flag the model ``kind`` does not read counts as False ('vfae': no
+    second profiles, ``has_x2`` may be None; 'pvae': no labels, ``has_y`` may be None).  A pure function of host arrays."""
+    C = _ChunkedEval.check_chunk_rows(C)
+    flat = lambda a: None if a is None else (np.asarray(a).reshape(-1) != 0)
+    hx, hy = flat(has_x2), flat(has_y)
+    if kind == 'vfae' or hx is None:
+        hx = np.zeros(len(hy), bool)
+    if kind == 'pvae' or hy is None:
+        hy = np.zeros(len(hx), bool)
+    if len(hx) != len(hy):
+        raise ValueError('chunk_partition: has_x2 and has_y flag the same rows (got %d and %d)' % (len(hx), len(hy)))
+    out = []
+    for gx, gy in _CHUNK_GROUPS:
+        rows = np.nonzero((hx == gx) & (hy == gy))[0]
+        out += [((gx, gy), rows[a:a + C]) for a in range(0, len(rows), C)]
+    return out
+
+
+def fold_col_blocks(acc, part):
+    """add a chunk's column-moment blocks ``part`` (blocks, 3, X: raw float64 sums of ``dv_col_moments``) to the (1, 3, X)
+    accumulator ``acc``: the blocks are summed in block order, the chunks arrive in chunk order -- one fixed order"""
+    assert acc.dtype == part.dtype == torch.float64 and acc.shape[0] == 1 and acc.shape[1:] == part.shape[1:]
+    return acc.add_(part.sum(0, keepdim=True))
+
+
+class _ChunkedEval(_EvalGraph):
+    """``_EvalGraph``'s numbers for a data set evaluated ``C`` rows at a time (``evaluate_performance_on_dataset(chunk_rows=C)``,
+    ``model.eval_chunk_rows``): a chunk is a rank in time.  The row-sharded evaluation of data parallelism already evaluates a
+    row range with the whole set's normalisers and Philox keys and leaves partials that the unsharded finalising launches
+    finish (``_finalize_full``); here the partials of every chunk land in ONE buffer of the whole set, one after the other.
+
+      * The rows are grouped by (has_x2, has_y) -- at most four groups, ``chunk_partition`` -- and chunks are cut inside groups:
+        a chunk is homogeneous, so the loss plan of a (group, rows) shape serves every chunk of that shape.  At most one
+        full-size and one tail structure per group (``_ChunkPart``), each captured once per (model, data set, C).
+      * A replay of a structure reads the data-set positions of its rows from a small device buffer the host refills
+        between replays, gathers them into ``C`` x dim_x staging rows (a ``CsrRows`` matrix through the feed launch: never
+        densified beyond the chunk), re-targets the GLOBAL row column of the plan's draw descriptors to those positions
+        (``_Plan.retarget_rows``), draws WITHOUT advancing the Philox counter, runs the loss pass with the whole set's
+        (N_total, N_pairs, N_labeled) and adds its scalars to the float64 sums, runs the means-only inference, and scatters
+        the per-row results -- six row statistics, log-likelihood rows, class probabilities / predictions -- to their
+        data-set positions; the chunk's column-moment blocks are folded into one (1, 3, X) accumulator (``fold_col_blocks``).
+      * Behind the last chunk the counter advances once -- where a one-replay evaluation leaves it -- and ``_finalize_full``
+        runs the same finalising launches over the complete per-row arrays.  No host synchronisation before the ONE copy.
+
+    Device memory that grows with N: the per-row arrays and index lists.  Everything of rows x genes size holds at most ``C``
+    rows, times the (bounded) number of structures.  Building leaves the Philox counter where it found it, so an evaluation
+    advances it by exactly one whatever the number of chunks, and training does not depend on C."""
+
+    CACHE_KEY = '_eval_chunked'
+
+    @staticmethod
+    def check_chunk_rows(c):
+        if isinstance(c, (bool, np.bool_)) or not isinstance(c, (int, np.integer)) or int(c) < 1:
+            raise ValueError('the evaluation chunk size (eval_chunk_rows / chunk_rows) is None or an integer >= 1, not %r' % (c,))
+        return int(c)
+
+    @staticmethod
+    def check_model(model):
+        """what the model's configuration alone decides (every rank of a data-parallel job decides alike)"""
+        if getattr(model, 'use_s', False) and getattr(model, 'use_MMD', False):
+            raise NotImplementedError('use_MMD: the MMD penalty compares every row of a nuisance class with every other row of '
+                                      'the set -- a cross-row term, it cannot be evaluated in row chunks (eval_chunk_rows)')
+        if getattr(model, '_dp', None) is not None:
+            raise NotImplementedError('row-chunked evaluation (eval_chunk_rows) under data parallelism is not built: the '
+                                      'whole-set evaluation is sharded by rows over the ranks there')
+
+    @staticmethod
+    def get(model, ds, C):
+        C = _ChunkedEval.check_chunk_rows(C)
+        _ChunkedEval.check_model(model)
+        kind, use_s = model.kind, bool(getattr(model, 'use_s', False))
+        need = ('x1',) + (('x2', 'has_x2') if kind != 'vfae' else ()) + (('y', 'has_y') if kind != 'pvae' else ()) + \
+            (('s',) if use_s else ())
+        dev = next(model.parameters()).device
+        for k in need:
+            t = getattr(ds, k, None)
+            if not ((torch.is_tensor(t) or isinstance(t, CsrRows)) and t.is_cuda and t.device == dev):
+                raise ValueError('row-chunked evaluation (eval_chunk_rows) reads the data set on the model\'s device (%s): '
+                                 '%r is %s' % (dev, k, 'missing' if t is None else 'host-resident or on another device'))
+        if kind != 'pvae' and getattr(model, 'type_y', 'discrete') != 'discrete' and not ds.y.is_floating_point():
+            raise ValueError("row-chunked evaluation: type_y='cont' reads floating-point targets")
+        if use_s and (ds.s.is_floating_point() or ds.s.is_complex() or ds.s.dtype == torch.bool):
+            raise ValueError('row-chunked evaluation: the nuisance classes are integers')
+        ptrs = lambda t: (int(t.ptr.data_ptr()), int(t.idx.data_ptr()), int(t.val.data_ptr())) if isinstance(t, CsrRows) \
+            else (int(t.data_ptr()),)
+        eng = model.engine()
+        sig = tuple(p for k in need for p in ptrs(getattr(ds, k))) + \
+            (int(ds.x1.shape[0]), C, id(eng), int(eng.arena.param.data_ptr()))
+        cache = model.__dict__.setdefault(_ChunkedEval.CACHE_KEY, {})
+        ev = cache.get((id(ds), C))
+        if ev is None or ev.sig != sig:
+            cache.pop((id(ds), C), None)
+            if len(cache) > 8:
+                cache.clear()
+            ev = cache[(id(ds), C)] = _ChunkedEval(model, ds, C, sig)      # (a failure raises: no other path answers)
+        return ev
+
+    def __init__(self, model, ds, C, sig):
+        import gc
+        import types
+        from . import dist as D
+        self.model, self.sig, self.C, self.full = model, sig, C, ds
+        kind = model.kind
+        eng = model.engine()
+        dev = ds.x1.device
+        n, X = int(ds.x1.shape[0]), int(ds.x1.shape[1])
+        if n < 1:
+            raise ValueError('row-chunked evaluation: the data set has no rows')
+        self.cont = kind != 'pvae' and getattr(model, 'type_y', 'discrete') != 'discrete'
+        self.use_s = bool(getattr(model, 'use_s', False))
+        self.fam = E.REC_FAMILIES[model.type_rec]
+        self.rec_kind = None if self.fam.recon_kind == E.RECON_KIND[None] else model.type_rec
+        self.dp = None
+        # the grouping is data of the DATASET, taken once (a host sync per flag array), like ``x2idx`` / ``yidx`` of ``_EvalGraph``
+        hx = (ds.has_x2.reshape(-1).cpu().numpy() != 0) if kind != 'vfae' else None
+        hy = (ds.has_y.reshape(-1).cpu().numpy() != 0) if kind != 'pvae' else None
+        chunks = chunk_partition(hx, hy, C, kind)
+        zer = np.zeros(n, bool)
+        self.counts = D.global_counts(hx if hx is not None else zer, hy if hy is not None else zer, eng.cfg.kind,
+                                      eng.cfg.semi_supervised, local=True)
+        self.gcounts = torch.tensor([self.counts[1], self.counts[2]], dtype=torch.int32).to(dev)
+        self.all_idx = torch.as_tensor(np.concatenate([r for _, r in chunks]), dtype=torch.int64).to(dev)
+        self.spans, o = [], 0
+        for g, r in chunks:            # (structure key, [a, b) of ``all_idx``)
+            self.spans.append(((g, len(r)), o, o + len(r)))
+            o += len(r)
+        # the whole set's partials and complete per-row arrays: ``_shard_layout``'s buffer with ONE column-moment block per matrix
+        i32 = lambda rows: torch.as_tensor(np.nonzero(rows)[0], dtype=torch.int32).to(dev)
+        self.n_all = n
+        self.full_x2idx32 = i32(hx) if hx is not None else None
+        self.full_yidx32 = i32(hy) if hy is not None else None
+        self.full_n_x2 = int(hx.sum()) if hx is not None else 0
+        self._alloc_full(n, X, model.dim_y if kind != 'pvae' else 0, 1, 1, dev)
+        # staging rows shared by the structures (they run one after the other): at most C rows of each matrix
+        cmax = max(len(r) for _, r in chunks)
+        self.stage = types.SimpleNamespace(
+            x1=torch.zeros(cmax, X, device=dev), x2=torch.zeros(cmax, X, device=dev) if self.full_n_x2 else None,
+            y=torch.zeros(cmax, int(ds.y.numel()) // n, dtype=ds.y.dtype, device=dev) if kind != 'pvae' else None,
+            s=torch.zeros(cmax, dtype=ds.s.dtype, device=dev) if self.use_s else None)
+        names = ['loss_' + k for k in sorted(E.LOSS_IDX, key=E.LOSS_IDX.get)]
+        if kind != 'pvae':
+            names += ['y_rmse', 'y_r2', 'y_pearr'] if self.cont else ['y_auroc', 'y_aupr', 'y_acc']
+        names += ['x1_' + k for k in _NAN4] + (['x2_' + k for k in _NAN4] if self.full_n_x2 else [])
+        self.names, self.vec = names, torch.zeros(len(names), dtype=torch.float64, device=dev)
+        self.loss_keys = list(model._loss_tensors(eng))
+        keep, keep_training, was_training = eng.plan, eng.training, model.training
+        keep_counts, keep_row0, keep_carry = model.__dict__.get('_global_counts'), eng.row0, eng.carry_s
+        keep_pending, keep_ctr = eng._rng_pending, eng.rng_ctr.clone()
+        # (no garbage collection while a stream is capturing: see ``_EvalGraph.__init__``)
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            model.eval()
+            eng.carry_s = self.use_s
+            # every chunk's loss pass normalises by the whole set's counts; its plan is built with local rows (``row0`` 0)
+            model._global_counts, model._row0_override = self.counts, 0
+            self.parts = {}
+            for key, a, b in self.spans:
+                if key not in self.parts:
+                    self.parts[key] = _ChunkPart(self, key, a, b)
+            self._finalize_full()                                   # (warm-up)
+            torch.cuda.synchronize()
+            self.graph_final = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph_final):
+                self._finalize_full()
+            self.graph = self.graph_final
+        finally:
+            if gc_was_on:
+                gc.enable()
+            eng.plan, eng.training, eng.carry_s, eng.row0, eng._rng_pending = keep, keep_training, keep_carry, keep_row0, keep_pending
+            model.train(was_training)
+            model.__dict__.pop('_row0_override', None)
+            if keep_counts is None:
+                model.__dict__.pop('_global_counts', None)
+            else:
+                model._global_counts = keep_counts
+            eng.rng_ctr.copy_(keep_ctr)      # (the warm-up passes drew: building leaves the Philox counter where it found it)
+            eng._noise_stale = True
+
+    def run(self):
+        from . import kernels as K
+        m = self.model
+        eng = m.engine()
+        eng.join_side()
+        eng.iters = m.finished_training_iters
+        keep = eng.plan
+        for plan in {id(p.plan): p.plan for p in self.parts.values() if p.plan is not None}.values():
+            plan.set_beta(*eng.betas())          # (the annealing coefficient is data of the plans, not of the graphs)
+        self.pack.zero_()                        # (loss scalars and column moments are sums over the chunks)
+        for key, a, b in self.spans:             # the host's share per chunk: which rows, then one replay
+            part = self.parts[key]
+            part.idx.copy_(self.all_idx[a:b])
+            part.graph.replay()
+        K.counter_add(eng.rng_ctr, 1)            # every chunk drew at the same counter value: ONE draw event, as in one replay
+        eng._noise_stale = True
+        eng.plan = keep
+        self.graph_final.replay()
+        return self._report(dict(zip(self.names, self.vec.cpu().tolist())))  # THE host sync of the evaluation
+
+
+class _ChunkPart(_EvalGraph):
+    """one STRUCTURE of a row-chunked evaluation: the chunks of ``rows`` rows of one (has_x2, has_y) group -- its loss plan,
+    its inference chains and buffers and its captured sequence, which evaluates the rows ``idx`` (data-set positions, device
+    data refilled by the host before a replay) and leaves their partials in the owner's buffer of the whole set.  A group
+    the loss pass ignores (the supervised-only VFAE's unlabeled rows) has no plan: inference and statistics only."""
+
+    def __init__(self, owner, key, a, b):
+        import types
+        (gx, gy), r = key
+        self.owner, self.model, self.rows_n, self.gx, self.gy = owner, owner.model, r, gx, gy
+        m, kind, st = owner.model, owner.model.kind, owner.stage
+        eng = m.engine()
+        dev = st.x1.device
+        self.cont, self.use_s, self.fam, self.rec_kind, self.dp = owner.cont, owner.use_s, owner.fam, owner.rec_kind, None
+        self.idx = torch.zeros(r, dtype=torch.int64, device=dev)
+        self.idx32 = torch.zeros(r, dtype=torch.int32, device=dev)
+        flag = lambda v: torch.full((r,), int(v), dtype=torch.int64, device=dev)
+        self.ds = types.SimpleNamespace(
+            x1=st.x1[:r], x2=st.x2[:r] if st.x2 is not None else None, s=st.s[:r] if st.s is not None else None,
+            y=st.y[:r] if st.y is not None else None, has_x2=flag(gx) if kind != 'vfae' else None,
+            has_y=flag(gy) if kind != 'pvae' else None)
+        if self.use_s:      # one_hot(s) operands of the inference's encoder / decoder chains, the rows' classes
+            S, reps = eng.cfg.dim_s, (2 if kind != 'vfae' else 1)
+            self.soh_e = torch.zeros(r, (S + 3) // 4 * 4, device=dev)[:, :S]
+            self.soh_d = torch.zeros(r * reps, (S + 3) // 4 * 4, device=dev)[:, :S]
+            self.s_all = torch.zeros(r, dtype=torch.int32, device=dev)
+        self.idx.copy_(owner.all_idx[a:b])
+        self._stage()
+        # the loss plan of this structure, built by the ordinary path on the staged rows (also the warm-up of its kernels)
+        self.plan, self.sel = None, torch.zeros(0, dtype=torch.int64, device=dev)
+        if not (kind == 'vfae' and not eng.cfg.semi_supervised and not gy):
+            ds = self.ds
+            kw = dict(x1=ds.x1, s=ds.s)
+            if kind != 'vfae':
+                kw.update(x2=ds.x2, has_x2=ds.has_x2)
+            if kind != 'pvae':
+                kw.update(y=ds.y, has_y=ds.has_y)
+            with warnings.catch_warnings():      # (a homogeneous chunk has empty data groups by construction)
+                warnings.simplefilter('ignore')
+                m.run_on_batch(train_mode=False, **kw)
+            self.plan, self.sel = eng.plan, None
+            assert len(self.plan.rows) == r and self.plan.B == r
+        self._sequence()                         # warm-up of the rest (allocations, code objects)
+        torch.cuda.synchronize()
+        eng.join_side()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self._sequence()
+
+    def _stage(self):
+        """the rows ``idx`` of the data set into the staging rows: dense rows by one gather, ``CsrRows`` by the feed launch"""
+        full, ds, r = self.owner.full, self.ds, self.rows_n
+        self.idx32.copy_(self.idx)
+        for k in ('x1',) + (('x2',) if (self.gx and ds.x2 is not None) else ()):
+            src, dst = getattr(full, k), getattr(ds, k)
+            if isinstance(src, CsrRows):
+                src.gather_rows(dst, self.idx32)
+            elif src.dtype == torch.float32:
+                torch.index_select(src, 0, self.idx, out=dst)
+            else:
+                dst.copy_(src.index_select(0, self.idx))
+        if ds.y is not None:
+            ds.y.copy_(full.y.reshape(self.owner.n_all, -1).index_select(0, self.idx))
+        if ds.s is not None:
+            ds.s.copy_(full.s.reshape(-1).index_select(0, self.idx))
+
+    def _sequence(self):
+        from . import kernels as K
+        m, ds, own, r = self.model, self.ds, self.owner, self.rows_n
+        eng, p = m.engine(), self.plan
+        cfg = eng.cfg
+        self._stage()
+        if p is not None:
+            # --- evaluation-mode losses of these rows: the fused forward on the structure's plan, the whole set's normalisers
+            eng.plan = p
+            p.feed_active = False
+            p.XSRC[:p.B].copy_(ds.x1)
+            if cfg.has_pert and self.gx:
+                p.XSRC[p.B:].copy_(ds.x2)
+            elif cfg.has_pert and p.universal:
+                p.XSRC[p.B:].zero_()
+            if p.universal:      # the batch-independent plan reads the composition as data: one plan serves every group
+                if cfg.has_pert:
+                    p.hx_dev.fill_(int(self.gx))
+                if cfg.has_y:
+                    p.hy_dev.fill_(int(self.gy))
+                    p.y_dev.copy_(ds.y.reshape(-1))
+                if p.global_counts:
+                    p.gcounts_dev.copy_(own.gcounts)
+            elif self.cont:
+                p.ylab.copy_(ds.y.reshape(r, -1))
+            elif cfg.has_y:
+                p.set_labels_device(ds.y)
+            if self.use_s:
+                K.nuisance_feed(p.SOHe, p.SOHd, p.s_cls, ds.s.to(torch.int32).contiguous(),
+                                pair_rows=p.pair_idx if p.Np else None, L=cfg.L)
+            p.retarget_rows(self.idx32)          # every draw is the one its row gets in a plan of the whole set
+            eng.training = False
+            pending = eng._rng_pending
+            eng.draw_noise(bump=False)           # (the counter advances once, behind the last chunk: ``_ChunkedEval.run``)
+            eng._rng_pending = pending
+            eng.forward()
+            n_loss = len(E.LOSS_IDX)
+            own._slot('loss')[:n_loss].add_(eng.arena.loss[:n_loss])      # float64 sums, in chunk order
+        if self.use_s:
+            K.nuisance_feed(self.soh_e, self.soh_d, self.s_all, ds.s.to(torch.int32).contiguous(), L=2 if m.kind != 'vfae' else 1)
+        self._scatter(self._infer())
+
+    def _scatter(self, res):
+        """this chunk's partials into the owner's buffer: per-row results to their data-set positions, column moments folded"""
+        from . import kernels as K
+        m, ds, own, idx, kind = self.model, self.ds, self.owner, self.idx, self.model.kind
+        n, X = own.n_all, int(ds.x1.shape[1])
+        if kind != 'pvae' and self.cont:
+            own._slot('pred').view(n, m.dim_y).index_copy_(0, idx, res['pred'].to(torch.float64))
+        elif kind != 'pvae':
+            own._slot('proba').view(n, m.dim_y).index_copy_(0, idx, res['proba'].to(torch.float64))
+            own._slot('pred').index_copy_(0, idx, res['pred'].reshape(-1).to(torch.float64))
+        bias = res['px_bias']
+        for tag, t, x in (('x1', '1', ds.x1), ('x2', '2', ds.x2)):
+            if tag == 'x2' and not self.gx:
+                continue
+            buf = self.__dict__.setdefault('_recon_bufs', {})
+            if tag not in buf:
+                buf[tag] = (torch.empty(self.rows_n, 6, device=x.device),
+                            torch.zeros(K.col_moment_blocks(self.rows_n), 3, X, dtype=torch.float64, device=x.device),
+                            torch.empty(self.rows_n, device=x.device))
+            rows, part, ll = buf[tag]
+            x_rec, ll = self._rows_pass(rows, ll, x, res['px' + t], bias, res['tail' + t])
+            own._slot('rows' + t).view(n, 6).index_copy_(0, idx, rows.to(torch.float64))
+            if ll is not None:      # ('binary' / 'poisson': no reported log-likelihood, the slot stays zero and is not read)
+                own._slot('ll' + t).index_copy_(0, idx, ll.to(torch.float64))
+            K.col_moments(None, x, x_rec, sel=None, part=part, r_bias=bias[0] if bias is not None else None)
+            fold_col_blocks(own._slot('part' + t).view(1, 3, X), part)

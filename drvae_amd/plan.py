@@ -172,6 +172,7 @@ class _Plan:
         # (the rows and, behind them, the trailer row the keep rows' kernel reads: ``kernels.noise_table``)
         self.noise_table = K.noise_table(i32(np.concatenate(desc) if desc else np.zeros((0, 4))), self.n_normal_rows, self.keep_thr)
         self.noise_desc = self.noise_table[:-1]
+        self.row0 = int(eng.row0)      # (what the GLOBAL row column was built with: ``retarget_rows``)
         # ---- activations / gradients
         self.XIN = mat(Me, X)
         if cfg.split_x:
@@ -327,6 +328,17 @@ class _Plan:
     def live_feed(self):
         """the installed epoch feed if it is the current input source, else None (inputs come from XSRC)"""
         return self.feed if self.feed_active else None
+
+    def retarget_rows(self, grow_dev):
+        """re-target the GLOBAL row column of the draw descriptors as device data: input row ``j`` of this plan becomes row
+        ``grow_dev[j]`` of the data set its rows were taken from (an integer device tensor with an entry per input row) --
+        every draw of the next ``draw_noise`` is then the one that row gets in a plan of the whole set, whatever rows the
+        plan holds this time.  One gather and one strided copy on the device, capturable; the plan is built once, with local
+        rows, and serves every row chunk of its shape (``fit._ChunkedEval``).  The column stays as written until the next call."""
+        local = self.__dict__.get('_noise_row_local')
+        if local is None:      # (the input row of every descriptor row, from the column as the constructor wrote it)
+            local = self._noise_row_local = self.noise_desc[:, 3].long() - self.row0
+        self.noise_desc[:, 3].copy_(grow_dev.reshape(-1).index_select(0, local))
 
     # device-carried nuisance classes (``carry_nuisance``): the classes of the batch's rows are DEVICE data -- written by
     # ``set_s_device`` or by the epoch feed's dv_nuisance_feed launch -- and the MMD penalty reads them inside its two
