@@ -179,6 +179,15 @@ class MmdMasked(C.Structure):    # dv_mmd_masked_desc
                 ('ldd', _i64)]
 
 
+class DrawDesc(C.Structure):     # dv_draw_desc: the sampler launch of dv_fill_normal
+    _fields_ = [('kind', _i32), ('M', _i32), ('X', _i32), ('S', _i32), ('mu', _p), ('ldm', _i64), ('sd', _p), ('lds', _i64),
+                ('theta', _p), ('ldt', _i64), ('logit', _p), ('ldl', _i64), ('size', _p), ('out', _p), ('ldo', _i64),
+                ('sso', _i64), ('row0', _i64), ('grow', _p), ('k0', _i32)]
+
+
+DRAW_MAX_SAMPLES, DRAW_MAX_ROW = 1 << 24, 1 << 31       # DV_DRAW_MAX_SAMPLES / DV_DRAW_MAX_ROW
+
+
 class LossTerm(C.Structure):
     _fields_ = [('x', _p), ('w', _p), ('n', _i32), ('scale', _f), ('out', _i32), ('row_len', _i32)]
 
@@ -273,7 +282,7 @@ SIGNATURES = {
     'dv_flag_wait': [_p, _p, _i32, _p, _i32, C.POINTER(Publish), _p],
     'dv_counter_add': [_p, _i32, _i64, _p],
     'dv_counters_add2': [_p, _i32, _i64, _p, _i32, _i64, _p, _p],
-    'dv_fill_normal': [_p, _i64, _u64, _p, _p],
+    'dv_fill_normal': [_p, _i64, _u64, _p, _p, C.POINTER(DrawDesc)],
     'dv_fill_normal_rows': [_p, _p, _i32, _u64, _p, _p, _p],
     'dv_fill_noise_rows': [_p, _p, _i32, _u64, _p, _p, _p],
 }

@@ -336,6 +336,46 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         res.update(px2=px2, x2_pert=px2[0], z2=qz2[0], qz2=qz2, px2_rec=px2_rec, x2_rec=px2_rec[0])
         return res
 
+    # ----------------------------------------------------------- posterior-predictive draws
+    @torch.no_grad()
+    def sample_x(self, x1, s=[], *, n_samples=1, latent='mean', size_factor=None, seed=None, event=0, row0=0):
+        """EXTENSION (no reference counterpart): draws of x from the model, on the device (``drvae_amd.count_sample``; the
+        sampler of include/drvae_hip.h) -- ``x1_samp`` (n_samples, rows, dim_x) float32 and, for DrVAE / PVAE, ``x2_samp`` from the
+        perturbed latent z2 = F(z1), drawn at x1's size factor as ``x2_pert`` is.  Every ``type_rec``: mu + sd z, [u <= p],
+        Poisson(s mu), Gamma-Poisson (theta per cell, per gene or per (gene, class)), and its zero-inflated form.
+
+        ``latent='mean'``: the heads of ``forward()`` exactly -- one decoder pass, observation noise only.  ``'sample'``: the full
+        posterior predictive -- per sample z1 ~ q(z1|x1) and z2 ~ p(z2|z1) from the row-keyed normals (draw ids 2k / 2k + 1 of
+        sample k under ``seed ^ count_sample.LATENT_SEED_XOR``), one decoder pass per sample; the result then also carries
+        ``z1_samp`` / ``z2_samp``.  ``size_factor``: as in ``forward`` (ValueError without ``library_size``).
+
+        An element depends on (seed, event, sample index, GLOBAL row ``row0 + r``, gene) and the heads only, so rows sampled in
+        pieces with their ``row0`` equal the rows sampled at once.  ``seed=None``: ``count_sample.default_seed(random_seed)``,
+        which the train step's noise cannot share; a seed of your own must not be the train step's (see the header).  ``x2_samp``
+        is drawn under ``seed ^ count_sample.X2_SEED_XOR``: it does not repeat x1_samp's random numbers."""
+        from . import count_sample as CS
+        S = CS.check_sample_args(self, n_samples, latent)
+        self.eval()
+        x1 = x1.to(next(self.parameters()).device, torch.float32)
+        lat = OrderedDict()
+        a, b = CS.sample_rows(self, x1, s, n_samples=S, latent=latent, size_factor=size_factor, seed=seed, event=event,
+                              row0=int(row0), latents_out=lat)
+        res = OrderedDict(x1_samp=a)
+        if b is not None:
+            res['x2_samp'] = b
+        res.update(lat)
+        return res
+
+    def posterior_predictive(self, ds, n_samples=1, *, chunk_rows=None, out=None, latent='mean', seed=None, event=0):
+        """EXTENSION: ``x1_samp`` of ``sample_x`` for every row of a DEVICE-resident ``DrVAEDataset`` / ``VFAEDataset`` (dense or
+        ``CsrRows``), (n_samples, N, dim_x) float32, ``chunk_rows`` rows at a time (None: one chunk).  The global row of a draw is
+        the row's position in the set: the result is bit for bit independent of ``chunk_rows`` and of dense versus sparse
+        storage; a ``CsrRows`` matrix is gathered one chunk at a time.  ``out``: a float32 tensor of that shape to fill, on the
+        device or pinned on the host (default: a new device tensor).  Touches no training state.  ValueError for a host-resident
+        set, NotImplementedError under data parallelism."""
+        from . import count_sample as CS
+        return CS.posterior_predictive(self, ds, n_samples, chunk_rows=chunk_rows, out=out, latent=latent, seed=seed, event=event)
+
     def _pred_proba(self, qy):
         """(pred, proba) of src/DrVAE.py:212-220: class + probabilities, or mean + log-variance"""
         if getattr(self, 'type_y', 'discrete') == 'cont':

@@ -488,6 +488,186 @@ __global__ __launch_bounds__(256) void fill_normal_kernel(float* __restrict__ ou
     }
 }
 
+// ------------------------------------------------------------------ count sampler (dv_draw_desc)
+// The posterior-predictive draw of every data decoder, element by element as include/drvae_hip.h specifies it ("The
+// sampler", above dv_fill_normal): every value is a function of (seed, event, sample k, global row R, gene g) and the
+// element's operands.  Block b of an element is Philox(counter = (g, R, (k << 8) | b, event_lo), key = (seed_lo,
+// seed_hi ^ event_hi)).  Every loop is bounded (8 Gamma attempts, 64 inversion steps, 16 PTRS attempts); the loop bodies
+// touch registers only.
+struct draw_key {
+    uint32_t k0, k1, g, R, ks, e_lo;      // ks = k << 8
+};
+
+__device__ __forceinline__ void draw_block(const draw_key& q, uint32_t b, uint32_t& w0, uint32_t& w1, uint32_t& w2,
+                                           uint32_t& w3) {
+    w0 = q.g;
+    w1 = q.R;
+    w2 = q.ks | b;
+    w3 = q.e_lo;
+    philox_block(w0, w1, w2, w3, q.k0, q.k1);
+}
+
+#define DV_DRAW_GAMMA_TRIES 8
+#define DV_DRAW_POIS_BLOCK0 8          // the Poisson draw's first block behind a Gamma draw
+#define DV_DRAW_PTRS_TRIES 16
+#define DV_DRAW_INV_STEPS 64
+#define DV_DRAW_GATE_BLOCK 16
+#define DV_DRAW_LAM_MAX 16777216.f     // 2^24
+
+// Poisson(lam), lam >= 0 (not NaN), from the blocks b0, b0 + 1, ...
+__device__ __forceinline__ float draw_poisson(const draw_key& q, uint32_t b0, float lam) {
+    if (!(lam < DV_DRAW_LAM_MAX)) return fminf(lam, 3.4028234663852886e38f);
+    uint32_t w0, w1, w2, w3;
+    draw_block(q, b0, w0, w1, w2, w3);
+    if (lam < 10.f) {
+        // inversion by sequential search from ONE uniform
+        const float u = u01(w0);
+        float p = expf(-lam), cdf = p, k = 0.f;
+        bool done = !(u > cdf);
+#pragma unroll 1
+        for (int i = 1; i <= DV_DRAW_INV_STEPS && !done; ++i) {
+            k = (float)i;
+            p *= lam / k;
+            cdf += p;
+            done = !(u > cdf);
+        }
+        return done ? k : rintf(lam);
+    }
+    // Hoermann's PTRS (transformed rejection with squeeze)
+    const float slam = sqrtf(lam), loglam = logf(lam);
+    const float b = 0.931f + 2.53f * slam, a = -0.059f + 0.02483f * b;
+    const float lia = logf(1.1239f + 1.1328f / (b - 3.4f)), vr = 0.9277f - 3.6224f / (b - 2.f);
+#pragma unroll 1
+    for (int j = 0; j < DV_DRAW_PTRS_TRIES; ++j) {
+        if (j != 0 && !(j & 1)) draw_block(q, b0 + (uint32_t)(j >> 1), w0, w1, w2, w3);
+        const float U = u01((j & 1) ? w2 : w0) - 0.5f, V = u01((j & 1) ? w3 : w1);
+        const float us = 0.5f - fabsf(U);
+        const float k = floorf((2.f * a / us + b) * U + lam + 0.43f);
+        if (us >= 0.07f && V <= vr) return k;
+        if (k < 0.f || (us < 0.013f && V > us)) continue;
+        if (logf(V) + lia - logf(a / (us * us) + b) <= -lam + k * loglam - lgammaf(k + 1.f)) return k;
+    }
+    return rintf(lam);
+}
+
+// the rate of a negative-binomial element: G ~ Gamma(shape theta, scale m / theta) by Marsaglia-Tsang from blocks 0 .. 7
+// (m > 0 finite, theta > 0, neither NaN)
+__device__ __forceinline__ float draw_gamma_rate(const draw_key& q, float m, float theta) {
+    if (theta > 3.4028234663852886e38f) return m;         // theta = +inf: the Poisson limit
+    const bool boost = theta < 1.f;
+    const float d = (boost ? theta + 1.f : theta) - 0.3333333333333333f, c = 1.f / sqrtf(9.f * d);
+    float lg = 0.f, ub = 1.f;
+    bool ok = false;
+#pragma unroll 1
+    for (uint32_t j = 0; j < DV_DRAW_GAMMA_TRIES && !ok; ++j) {
+        uint32_t w0, w1, w2, w3;
+        draw_block(q, j, w0, w1, w2, w3);
+        if (j == 0) ub = u01(w3);
+        const float x = sqrtf(-2.f * logf(u01(w0))) * cosf(6.283185307179586f * u01(w1));
+        const float t = c * x;
+        if (t > -1.f) {
+            const float l1 = log1pf(t);
+            const float h = 0.5f * x * x + d * (3.f * l1 - t * (3.f + t * (3.f + t)));
+            if (logf(u01(w2)) < h) {
+                ok = true;
+                lg = logf(d / theta) + 3.f * l1;      // ln(G / theta): the two logarithms' magnitudes never meet
+            }
+        }
+    }
+    if (!ok) return m;                                     // (past the cap: the Gamma's mean)
+    // theta < 1: + ln u / theta.  A theta so small that the quotient d / theta or ln u / theta overflows (a denormal) has no finite
+    // q: the rate is 0 there, as it is for every q below exp's range
+    if (boost) lg += logf(ub) / theta;
+    if (!(lg < 3.4028234663852886e38f) || lg != lg) return 0.f;
+    return m * expf(lg);
+}
+
+__device__ __forceinline__ float draw_element(int kind, const draw_key& q, float mu, float p2, float lgt, float s) {
+    uint32_t w0, w1, w2, w3;
+    if (kind == DV_RECON_GAUSS) {
+        draw_block(q, 0u, w0, w1, w2, w3);
+        return mu + p2 * (sqrtf(-2.f * logf(u01(w0))) * cosf(6.283185307179586f * u01(w1)));
+    }
+    if (kind == DV_RECON_BERNOULLI) {
+        if (mu != mu) return mu;
+        draw_block(q, 0u, w0, w1, w2, w3);
+        return u01(w0) <= mu ? 1.f : 0.f;
+    }
+    const float m = s * mu;
+    if (m != m) return m;
+    if (kind == DV_RECON_POISSON) return m > 0.f ? draw_poisson(q, 0u, m) : 0.f;
+    if (p2 != p2 || !(p2 > 0.f)) return __int_as_float(0x7fc00000);
+    if (kind == DV_RECON_ZINB) {
+        if (lgt != lgt) return lgt;
+        draw_block(q, DV_DRAW_GATE_BLOCK, w0, w1, w2, w3);
+        if (u01(w0) <= 1.f / (1.f + expf(-lgt))) return 0.f;
+    }
+    if (!(m > 0.f)) return 0.f;
+    if (m > 3.4028234663852886e38f) return 3.4028234663852886e38f;      // m = +inf
+    return draw_poisson(q, DV_DRAW_POIS_BLOCK0, draw_gamma_rate(q, m, p2));
+}
+
+// one workgroup per (1024-gene chunk, row, sample); QUAD: a thread owns four consecutive genes (16-byte loads and stores),
+// else the genes tid, tid + 256, ... of the chunk.  Rows and samples beyond the grid's limits are walked by stride.
+template <bool QUAD>
+__global__ __launch_bounds__(256) void draw_kernel(dv_draw_desc d, uint64_t seed, const int32_t* __restrict__ ctr_dev) {
+    uint32_t e_lo = 0, e_hi = 0;
+    if (ctr_dev) {
+        e_lo = (uint32_t)ctr_dev[0];
+        e_hi = (uint32_t)ctr_dev[1];
+    }
+    draw_key q;
+    q.k0 = (uint32_t)seed;
+    q.k1 = (uint32_t)(seed >> 32) ^ e_hi;
+    q.e_lo = e_lo;
+    const int kind = d.kind;
+    const float* p2 = kind == DV_RECON_GAUSS ? d.sd : d.theta;
+    const int64_t ld2 = kind == DV_RECON_GAUSS ? d.lds : d.ldt;
+    const int g0 = blockIdx.x * 1024;
+    for (int k = blockIdx.z; k < d.S; k += gridDim.z) {
+        q.ks = (uint32_t)(d.k0 + k) << 8;
+        for (int r = blockIdx.y; r < d.M; r += gridDim.y) {
+            q.R = d.grow ? (uint32_t)d.grow[r] : (uint32_t)(d.row0 + r);
+            const float s = d.size ? d.size[r] : 1.f;
+            const float* mu = d.mu + (int64_t)r * d.ldm;
+            const float* pp = p2 ? p2 + (int64_t)r * ld2 : nullptr;
+            const float* lg = d.logit ? d.logit + (int64_t)r * d.ldl : nullptr;
+            float* out = d.out + (int64_t)k * d.sso + (int64_t)r * d.ldo;
+            if (QUAD) {
+                const int g = g0 + (threadIdx.x << 2);
+                if (g < d.X) {      // (X % 4 == 0: the quad is whole)
+                    const float4 m4 = *reinterpret_cast<const float4*>(mu + g);
+                    const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                    const float4 t4 = pp ? *reinterpret_cast<const float4*>(pp + g) : z4;
+                    const float4 l4 = lg ? *reinterpret_cast<const float4*>(lg + g) : z4;
+                    float4 o = z4;
+#pragma unroll 1
+                    for (int e = 0; e < 4; ++e) {      // (one copy of the draw's code; the quad's lanes by selects)
+                        q.g = (uint32_t)(g + e);
+                        const float v = draw_element(kind, q, e == 0 ? m4.x : e == 1 ? m4.y : e == 2 ? m4.z : m4.w,
+                                                     e == 0 ? t4.x : e == 1 ? t4.y : e == 2 ? t4.z : t4.w,
+                                                     e == 0 ? l4.x : e == 1 ? l4.y : e == 2 ? l4.z : l4.w, s);
+                        o.x = e == 0 ? v : o.x;
+                        o.y = e == 1 ? v : o.y;
+                        o.z = e == 2 ? v : o.z;
+                        o.w = e == 3 ? v : o.w;
+                    }
+                    *reinterpret_cast<float4*>(out + g) = o;
+                }
+            } else {
+#pragma unroll 1
+                for (int i = 0; i < 4; ++i) {
+                    const int g = g0 + (int)threadIdx.x + (i << 8);
+                    if (g < d.X) {
+                        q.g = (uint32_t)g;
+                        out[g] = draw_element(kind, q, mu[g], pp ? pp[g] : 0.f, lg ? lg[g] : 0.f, s);
+                    }
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
 
 #define ST(s) static_cast<hipStream_t>(s)
@@ -771,7 +951,41 @@ extern "C" int dv_fill_noise_rows(float* arena, const int32_t* table, int32_t n_
     return fill_rows_launch<true>(arena, table, n_rows, seed, ctr_dev, park, stream);
 }
 
-extern "C" int dv_fill_normal(float* out, int64_t n, uint64_t seed, const int32_t* ctr_dev, dv_stream_t stream) {
+// the sampler launch of dv_fill_normal (draw != NULL): every refusal in front of the launch, at M == 0 / S == 0 too
+static int draw_launch(const dv_draw_desc* dp, uint64_t seed, const int32_t* ctr_dev, dv_stream_t stream) {
+    const dv_draw_desc d = *dp;
+    const int64_t X = d.X;
+    DV_REQUIRE(d.kind >= DV_RECON_GAUSS && d.kind <= DV_RECON_ZINB);
+    DV_REQUIRE(d.M >= 0 && d.X >= 0 && d.S >= 0 && d.k0 >= 0 && (int64_t)d.k0 + d.S <= DV_DRAW_MAX_SAMPLES);
+    DV_REQUIRE(d.row0 >= 0 && d.row0 + (int64_t)d.M <= DV_DRAW_MAX_ROW && (d.grow == nullptr || d.row0 == 0));
+    const bool nb = d.kind == DV_RECON_NEGBIN || d.kind == DV_RECON_ZINB;
+    DV_REQUIRE(d.mu != nullptr && d.ldm >= X);
+    DV_REQUIRE(d.kind != DV_RECON_GAUSS || (d.sd != nullptr && d.lds >= X));
+    DV_REQUIRE(!nb || (d.theta != nullptr && (d.ldt == 0 || d.ldt >= X)));
+    DV_REQUIRE(d.kind != DV_RECON_ZINB || (d.logit != nullptr && d.ldl >= X));
+    DV_REQUIRE(d.size == nullptr || d.kind >= DV_RECON_POISSON);
+    DV_REQUIRE(d.ldo >= X && (d.S <= 1 || d.M == 0 || d.sso >= (int64_t)(d.M - 1) * d.ldo + X));
+    if (d.M == 0 || d.X == 0 || d.S == 0) return DV_OK;
+    DV_REQUIRE(d.out != nullptr);
+    // the quad path: every row of every operand the kind reads starts on a 16-byte boundary
+    auto al = [](const void* p, int64_t ld) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld & 3) == 0; };
+    bool quad = (d.X & 3) == 0 && al(d.mu, d.ldm) && al(d.out, d.ldo) && (d.sso & 3) == 0;
+    if (d.kind == DV_RECON_GAUSS) quad = quad && al(d.sd, d.lds);
+    if (nb) quad = quad && al(d.theta, d.ldt);
+    if (d.kind == DV_RECON_ZINB) quad = quad && al(d.logit, d.ldl);
+    dv_draw_desc k = d;       // (the kernel reads the operands of its kind only)
+    if (d.kind != DV_RECON_GAUSS) k.sd = nullptr;
+    if (!nb) k.theta = nullptr;
+    if (d.kind != DV_RECON_ZINB) k.logit = nullptr;
+    const dim3 grid((unsigned)((d.X + 1023) / 1024), (unsigned)(d.M < 65535 ? d.M : 65535), (unsigned)(d.S < 1024 ? d.S : 1024));
+    if (quad) hipLaunchKernelGGL(draw_kernel<true>, grid, dim3(256), 0, ST(stream), k, seed, ctr_dev);
+    else hipLaunchKernelGGL(draw_kernel<false>, grid, dim3(256), 0, ST(stream), k, seed, ctr_dev);
+    DV_RETURN_LAUNCH();
+}
+
+extern "C" int dv_fill_normal(float* out, int64_t n, uint64_t seed, const int32_t* ctr_dev, dv_stream_t stream,
+                              const dv_draw_desc* draw) {
+    if (draw != nullptr) return draw_launch(draw, seed, ctr_dev, stream);
     DV_REQUIRE(n >= 0);
     if (n == 0) return DV_OK;
     DV_REQUIRE(out);

@@ -1354,5 +1354,5 @@ def fill_noise_rows(arena, table, seed, ctr_dev=None, park=None):
 
 def fill_normal(out, seed, ctr_dev=None):
     assert out.is_contiguous()
-    _lib.check(_lib.load().dv_fill_normal(_f32(out), out.numel(), seed, _i32(ctr_dev), _stream()),
-               'dv_fill_normal')
+    _lib.check(_lib.load().dv_fill_normal(_f32(out), out.numel(), seed, _i32(ctr_dev), _stream(), None),
+               'dv_fill_normal')      # (no draw descriptor: ``count_sample.draw`` is the launch with one)

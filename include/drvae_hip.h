@@ -1374,8 +1374,75 @@ int dv_flag_wait(int32_t* flag, const int32_t* ctr, int32_t add, int32_t* err, i
  * 0, 1 (r cos a, r sin a with r = sqrt(-2 ln u0), a = 2 pi u1), words 2 / 3 those of lanes 2, 3.
  * dv_fill_normal's counter is (lo, hi, 0, 0) of ctr + i/4 under the key (seed_lo, seed_hi): with ctr + i/4 < 2^32 that
  * is the row-keyed stream below at (global row 0, draw id 0, event 0) under the same seed -- the two forms must not
- * share a seed.  (The train step uses the row-keyed form only.) */
-int dv_fill_normal(float* out, int64_t n, uint64_t seed, const int32_t* ctr_dev, dv_stream_t stream);
+ * share a seed.  (The train step uses the row-keyed form only.)
+ *
+ * THE SAMPLER (`draw` != NULL; an optional trailing argument of ABI 13, NULL = the launch above, bit for bit, with its
+ * refusals).  One launch draws S posterior-predictive samples of M rows of X genes from FINISHED decoder heads, as float32:
+ * out[(k - k0) * sso + r * ldo + g] for sample k = k0 .. k0 + S - 1, row r, gene g.  `out` / `n` are unused; `seed` is the
+ * draw's seed and ctr_dev[0..1] its 64-bit EVENT (NULL: event 0).  This paragraph is the specification
+ * (tests/count_sample_ref.py is it in numpy, float64).
+ *   Stream.  The global row of row r is R = row0 + r, or grow[r] (int32, device; row0 must then be 0).  Block b of element
+ *   (k, R, g) is Philox4x32-10(counter = (g, R, (k << 8) | b, event_lo), key = (seed_lo, seed_hi ^ event_hi)), its words w0..w3
+ *   mapped to uniforms u(w) as above.  N(b) = sqrt(-2 ln u(w0)) cos(2 pi u(w1)) of block b (lane 0 of the Box-Muller above).  An
+ *   element depends on (seed, event, k, R, g) and its own operands only -- not on M, S, the grid, the chunk a row arrives in or
+ *   the access path.  The blocks are the row-keyed stream's at (col / 4 = g, global row R, draw id (k << 8) | b): a draw and
+ *   the train step's noise must not share a seed.
+ *   Operands.  mu[r * ldm + g] always; sd[r * lds + g] (Gaussian); theta[r * ldt + g] (NB / ZINB; ldt == 0: ONE row shared by
+ *   all rows, a gene-wise dispersion, nothing expanded); logit[r * ldl + g] (ZINB, the RAW dropout logit); size[r] (optional,
+ *   count kinds: the row's size factor s, else s = 1).  m = s * mu, ONE fp32 product.  theta and the logit are never scaled.
+ *   All arithmetic below is fp32.
+ *   DV_RECON_GAUSS: mu + sd * N(0), plain IEEE arithmetic (NaN / inf propagate).   DV_RECON_BERNOULLI: mu NaN -> NaN; else
+ *   1 if u(w0 of block 0) <= mu, else 0.
+ *   DV_RECON_POISSON: m NaN -> NaN; m <= 0 -> 0; else P(0, m).
+ *   DV_RECON_NEGBIN / _ZINB, in this order: m NaN -> NaN.  theta NaN or theta <= 0 -> NaN.  ZINB: logit NaN -> NaN; u(w0 of
+ *   block 16) <= 1 / (1 + exp(-logit)) -> 0 (a dropout).  m <= 0 -> 0.  m = +inf -> FLT_MAX.  Else P(8, lam) with the rate
+ *     lam = m if theta = +inf (the Poisson limit), else by Marsaglia-Tsang: a = theta + 1 if theta < 1 else theta, d = a - 1/3,
+ *     c = 1 / sqrt(9 d).  Attempt j = 0 .. 7: x = N(j), t = c x; accepted if t > -1 and
+ *         ln u(w2 of block j) < x^2 / 2 + d (3 log1p(t) - t (3 + t (3 + t)))
+ *     (1 - v + ln v at v = (1 + t)^3, formed from t so that no two values of size d are subtracted); then, with G the Gamma
+ *     draw, q = ln(G / theta) = ln(d / theta) + 3 log1p(t) -- the quotient first, so that the logarithm's argument is near 1
+ *     for a large theta and no two logarithms of size ln theta are subtracted.  theta < 1: q += ln u(w3 of block 0) / theta
+ *     (u^(1 / theta) underflows; its logarithm does not).  lam = m * exp(q).  No attempt accepted: lam = m (the Gamma's mean).
+ *     q not finite in fp32 -- a theta so small (a denormal) that d / theta or ln u / theta overflows, +inf, or their difference,
+ *     NaN: lam = 0, as for every q below exp's range.
+ *   P(b0, lam), the Poisson draw from blocks b0, b0 + 1, ...:
+ *     lam >= 2^24 (beyond fp32's exact integers; +inf): min(lam, FLT_MAX), no draw.
+ *     lam < 10: inversion from ONE uniform u = u(w0 of block b0): p_0 = F_0 = exp(-lam), p_i = p_(i-1) * (lam / i), F_i = F_(i-1)
+ *     + p_i; the result is the smallest i in 0 .. 64 with u <= F_i; none: rint(lam).
+ *     lam >= 10: Hoermann's PTRS.  b = 0.931 + 2.53 sqrt(lam), a = -0.059 + 0.02483 b, ia = 1.1239 + 1.1328 / (b - 3.4), vr =
+ *     0.9277 - 3.6224 / (b - 2).  Attempt j = 0 .. 15 reads block b0 + j / 2, words (w0, w1) for even j, (w2, w3) for odd j, as
+ *     (wU, wV): U = u(wU) - 0.5, V = u(wV), us = 0.5 - |U|, k = floor((2 a / us + b) U + lam + 0.43).  us >= 0.07 and V <= vr:
+ *     the result is k.  Else k < 0, or us < 0.013 and V > us: next attempt (us = 0 always lands here).  Else
+ *     ln V + ln ia - ln(a / us^2 + b) <= -lam + k ln lam - lgamma(k + 1): the result is k.  No attempt accepted: rint(lam).
+ *   Every loop is bounded by the counts above: the launch returns on every input.  No atomics, one writer per element, nothing
+ *   is written outside the S x M x X described elements; no operand is written.
+ * DV_ERR_ARG, before any launch and at M == 0 or S == 0 too: kind outside the five; M, X, S or k0 < 0; k0 + S > DV_DRAW_MAX_SAMPLES;
+ * row0 < 0, row0 + M > DV_DRAW_MAX_ROW, grow with row0 != 0; mu NULL; sd NULL with Gaussian; theta NULL with NB / ZINB; logit
+ * NULL with ZINB; size with Gaussian or Bernoulli; ldm / ldo (and lds, ldl of a kind that reads them) below X; ldt below X and
+ * not 0; with S > 1 and M > 0 a sample stride sso below (M - 1) ldo + X; out NULL with elements to write.  Operands the kind does
+ * not read are ignored.  16-byte loads and stores when X % 4 == 0 and every row of every operand read is 16-byte aligned, scalar
+ * ones otherwise: the same values either way. */
+#define DV_DRAW_MAX_SAMPLES 16777216        /* 2^24: the sample index shares a counter word with the block index */
+#define DV_DRAW_MAX_ROW 2147483648LL        /* 2^31 */
+typedef struct dv_draw_desc {
+    int32_t kind, M, X, S;        /* DV_RECON_*; rows, genes, samples */
+    const float* mu;
+    int64_t ldm;
+    const float* sd;
+    int64_t lds;
+    const float* theta;
+    int64_t ldt;
+    const float* logit;
+    int64_t ldl;
+    const float* size;
+    float* out;
+    int64_t ldo, sso;             /* row stride, sample stride */
+    int64_t row0;
+    const int32_t* grow;
+    int32_t k0;                   /* the sample index of out's first sample */
+} dv_draw_desc;
+int dv_fill_normal(float* out, int64_t n, uint64_t seed, const int32_t* ctr_dev, dv_stream_t stream,
+                   const dv_draw_desc* draw);
 /* Row-keyed form for the train step's noise arena (SURVEY.md 8(e) "RNG under DP": results must not depend
  * on the number of ranks).  desc = n_rows x {offset into arena (floats), width, draw id, GLOBAL minibatch
  * row} (int32 x 4, 16-B aligned); element (row, col) = Philox(key = seed (^ ctr_dev[1] in the high word),
