@@ -179,10 +179,20 @@ class MmdMasked(C.Structure):    # dv_mmd_masked_desc
                 ('ldd', _i64)]
 
 
+class EffectDesc(C.Structure):   # dv_effect_desc: the effect reduction carried by dv_draw_desc.fx
+    _fields_ = [('a', _p), ('lda', _i64), ('b', _p), ('ldb', _i64), ('mode', _i32), ('delta', _f), ('pseudo', _f),
+                ('out', _p), ('row_blocks', _i32), ('n_grp', _i32), ('grp', _p)]
+
+
+EFFECT_LFC, EFFECT_DIFF = 0, 1      # dv_effect_desc.mode
+EFFECT_STATS = ('n', 'sum_e', 'sum_e2', 'n_up', 'n_down', 'sum_a', 'sum_b')     # the seven rows of its output
+
+
 class DrawDesc(C.Structure):     # dv_draw_desc: the sampler launch of dv_fill_normal
     _fields_ = [('kind', _i32), ('M', _i32), ('X', _i32), ('S', _i32), ('mu', _p), ('ldm', _i64), ('sd', _p), ('lds', _i64),
                 ('theta', _p), ('ldt', _i64), ('logit', _p), ('ldl', _i64), ('size', _p), ('out', _p), ('ldo', _i64),
-                ('sso', _i64), ('row0', _i64), ('grow', _p), ('k0', _i32)]
+                ('sso', _i64), ('row0', _i64), ('grow', _p), ('k0', _i32),
+                ('fx', _p)]      # (trailing: a dv_effect_desc*; NULL: the sampler as it was)
 
 
 DRAW_MAX_SAMPLES, DRAW_MAX_ROW = 1 << 24, 1 << 31       # DV_DRAW_MAX_SAMPLES / DV_DRAW_MAX_ROW

@@ -376,6 +376,32 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         from . import count_sample as CS
         return CS.posterior_predictive(self, ds, n_samples, chunk_rows=chunk_rows, out=out, latent=latent, seed=seed, event=event)
 
+    def perturbation_effect(self, ds, *, n_samples=1, latent='mean', groups=None, n_groups=None, delta=0.25, pseudocount=0.0,
+                            chunk_rows=None, seed=None, event=0):
+        """EXTENSION (no reference counterpart): which genes the perturbation z2 = F(z1) moves, by how much and how surely, per
+        group of cells of a DEVICE-resident ``DrVAEDataset`` (dense or ``CsrRows``) -- DrVAE / PVAE only.  The effect of one
+        (sample, cell, gene) is e = log2(b + pseudocount) - log2(a + pseudocount) for the count decoders, a and b the UNSCALED
+        mean heads decoded from z1 and z2 (x2_pert is predicted at x1's depth: the size factor cancels), and e = b - a for
+        ``'diag_gaussian'`` (pseudocount must be 0).  An element whose e is not finite (a zero mean without a pseudocount)
+        counts nowhere.
+
+        ``latent='mean'``: the heads of ``forward()`` (n_samples must be 1).  ``'sample'``: per sample z1 ~ q(z1|x1), z2 ~
+        p(z2|z1) -- the latents ``sample_x(latent='sample')`` returns for the same ``seed`` / ``event`` and global row = position
+        in the set, so the statistics do not depend on ``chunk_rows`` beyond the order of float64 sums.  ``groups``: None, or an
+        (N,) integer tensor with ``n_groups``; a negative entry leaves a cell out, an entry >= n_groups is a ValueError.
+
+        Returns (n_groups, dim_x) float64 device tensors: ``n`` (valid elements), ``lfc_mean``, ``lfc_sd`` (population sd),
+        ``p_up`` / ``p_down`` (the share of e > delta / e < -delta, strict), ``mean_base``, ``mean_pert``, and ``raw``, the
+        (n_groups, 7, dim_x) sums they come from (``effect.STATS``).  A gene with n == 0 has NaN ratios.  Per chunk and sample:
+        two decoder passes, one reduction launch (``drvae_amd.effect``), one fold; nothing of size rows x genes outlives a
+        chunk, nothing is copied to the host, training state and the Philox counter are not touched.  ValueError for a
+        host-resident set or ``type_rec='binary'``, NotImplementedError under data parallelism."""
+        if self.kind == 'vfae':
+            raise AttributeError('VFAE has no perturbation path')
+        from . import effect
+        return effect.perturbation_effect(self, ds, n_samples=n_samples, latent=latent, groups=groups, n_groups=n_groups,
+                                          delta=delta, pseudocount=pseudocount, chunk_rows=chunk_rows, seed=seed, event=event)
+
     def _pred_proba(self, qy):
         """(pred, proba) of src/DrVAE.py:212-220: class + probabilities, or mean + log-variance"""
         if getattr(self, 'type_y', 'discrete') == 'cont':

@@ -131,6 +131,33 @@ def _latent_noise(model, S, rows, grow_i32, row0, seed, ev, dev):
     return eps
 
 
+def head_passes(model, x1, s, *, n_samples, latent, seed, ev, row0=0, grow=None, second=True):
+    """the latent and decoder passes of ``sample_x``, shared by the sampler (``sample_rows``) and the effect reduction
+    (``effect.perturbation_effect``): yields ``(k, which, z, px)`` per sample k in order -- ``which`` 1: z = z1 and the UNSCALED
+    heads ``decoder_x([z1] + cond)``; then, with ``second``, ``which`` 2: z = z2 = F(z1) and its heads.  ``latent='mean'``: one
+    pass (k = 0) at the means, the heads of ``forward()``.  ``'sample'``: z1 ~ q(z1|x1), z2 ~ p(z2|z1) from the row-keyed normals
+    of ``_latent_noise`` (``seed``: the resolved 64-bit seed, ``ev``: the event's device words or None).  The consumer works
+    between two yields: nothing of the next pass is launched before it asks for it."""
+    cond = model._s_inputs(s, x1)
+    qz1 = model.encoder_z1([model._enc_x(x1)] + cond)
+    if latent == 'mean':
+        z1 = qz1[0]
+        yield 0, 1, z1, model.decoder_x([z1] + cond)
+        if second:
+            z2 = model.decoder_z2Fz1([z1])[0]
+            yield 0, 2, z2, model.decoder_x([z2] + cond)
+        return
+    eps = _latent_noise(model, n_samples, x1.shape[0], grow, row0, seed, ev, x1.device)
+    sd1 = torch.exp(0.5 * qz1[1])
+    for k in range(n_samples):
+        z1 = qz1[0] + sd1 * eps[k, 0]
+        yield k, 1, z1, model.decoder_x([z1] + cond)
+        if second:
+            pz2 = model.decoder_z2Fz1([z1])
+            z2 = pz2[0] + torch.exp(0.5 * pz2[1]) * eps[k, 1]
+            yield k, 2, z2, model.decoder_x([z2] + cond)
+
+
 @torch.no_grad()
 def sample_rows(model, x1, s, *, n_samples, latent, size_factor, seed, event, row0=0, grow=None, out1=None, want_x2=True,
                 latents_out=None):
@@ -141,7 +168,6 @@ def sample_rows(model, x1, s, *, n_samples, latent, size_factor, seed, event, ro
     dev = x1.device
     rows, X = x1.shape
     has2 = want_x2 and model.kind in ('drvae', 'pvae')
-    cond = model._s_inputs(s, x1)
     size = model._chosen_size(size_factor, x1)
     if getattr(model, 'library_size', False):
         size = (model.size_factor(x1) if size is None else size).to(torch.float32).contiguous()
@@ -151,34 +177,20 @@ def sample_rows(model, x1, s, *, n_samples, latent, size_factor, seed, event, ro
     out1 = new() if out1 is None else out1
     out2 = new() if has2 else None
     where = dict(event=ev, row0=row0, grow=grow)
-    qz1 = model.encoder_z1([model._enc_x(x1)] + cond)
-    if latent == 'mean':
-        z1 = qz1[0]
-        px = model.decoder_x([z1] + cond)
-        draw(out1, px[0], seed=seed, **where, **_head_operands(model, px, size))
-        if has2:
-            px = model.decoder_x([model.decoder_z2Fz1([z1])[0]] + cond)
-            draw(out2, px[0], seed=seed ^ X2_SEED_XOR, **where, **_head_operands(model, px, size))
-        return out1, out2
-    eps = _latent_noise(model, S, rows, grow, row0, seed, ev, dev)
-    if latents_out is not None:
+    sampled = latent != 'mean'
+    if sampled and latents_out is not None:
         latents_out['z1_samp'] = torch.empty(S, rows, model.dim_z1, device=dev)
         if has2:
             latents_out['z2_samp'] = torch.empty(S, rows, model.dim_z1, device=dev)
-    sd1 = torch.exp(0.5 * qz1[1])
-    for k in range(S):
-        z1 = qz1[0] + sd1 * eps[k, 0]
-        px = model.decoder_x([z1] + cond)
-        draw(out1[k:k + 1], px[0], seed=seed, sample0=k, **where, **_head_operands(model, px, size))
-        if latents_out is not None:
-            latents_out['z1_samp'][k] = z1
-        if has2:
-            pz2 = model.decoder_z2Fz1([z1])
-            z2 = pz2[0] + torch.exp(0.5 * pz2[1]) * eps[k, 1]
-            px = model.decoder_x([z2] + cond)
-            draw(out2[k:k + 1], px[0], seed=seed ^ X2_SEED_XOR, sample0=k, **where, **_head_operands(model, px, size))
+    for k, which, z, px in head_passes(model, x1, s, n_samples=S, latent=latent, seed=seed, ev=ev, row0=row0, grow=grow,
+                                       second=has2):
+        out, sd = (out1, seed) if which == 1 else (out2, seed ^ X2_SEED_XOR)
+        if sampled:       # one decoder pass per sample: sample k of the launch is sample k of the result
+            draw(out[k:k + 1], px[0], seed=sd, sample0=k, **where, **_head_operands(model, px, size))
             if latents_out is not None:
-                latents_out['z2_samp'][k] = z2
+                latents_out['z%d_samp' % which][k] = z
+        else:             # the heads of forward(): every sample from the one pass
+            draw(out, px[0], seed=sd, **where, **_head_operands(model, px, size))
     return out1, out2
 
 

@@ -173,3 +173,6 @@ __device__ __forceinline__ void counter_add_words(int32_t* c, int n_words, int64
     }
 }
 
+// the effect reduction behind dv_draw_desc.fx: the kernel and its refusals live in rows.hip, the entry point that carries it
+// (dv_fill_normal) in optim.hip -- a call inside the library, not an exported symbol
+__attribute__((visibility("hidden"))) int dv_effect_cols_launch(const dv_effect_desc& fx, int32_t M, int32_t X, dv_stream_t stream);

@@ -985,6 +985,13 @@ static int draw_launch(const dv_draw_desc* dp, uint64_t seed, const int32_t* ctr
 
 extern "C" int dv_fill_normal(float* out, int64_t n, uint64_t seed, const int32_t* ctr_dev, dv_stream_t stream,
                               const dv_draw_desc* draw) {
+    if (draw != nullptr && draw->fx != nullptr) {       // the effect reduction (rows.hip): the outer descriptor carries M and X only
+        const dv_draw_desc& d = *draw;
+        DV_REQUIRE(out == nullptr && n == 0 && seed == 0 && ctr_dev == nullptr);
+        DV_REQUIRE(d.kind == 0 && d.S == 0 && !d.mu && d.ldm == 0 && !d.sd && d.lds == 0 && !d.theta && d.ldt == 0 && !d.logit &&
+                   d.ldl == 0 && !d.size && !d.out && d.ldo == 0 && d.sso == 0 && d.row0 == 0 && !d.grow && d.k0 == 0);
+        return dv_effect_cols_launch(*d.fx, d.M, d.X, stream);
+    }
     if (draw != nullptr) return draw_launch(draw, seed, ctr_dev, stream);
     DV_REQUIRE(n >= 0);
     if (n == 0) return DV_OK;

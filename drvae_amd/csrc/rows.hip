@@ -2627,6 +2627,86 @@ __global__ __launch_bounds__(64 * kCmRG) void col_moments_kernel(const float* __
     }
 }
 
+// ---- the perturbation effect's column statistics (dv_draw_desc.fx; include/drvae_hip.h, "THE EFFECT REDUCTION", is the
+// specification).  Two finished mean heads a (from z1) and b (from z2) -> per (row block, group, gene) the seven float64
+// sufficient statistics of e = log2f(b + c) - log2f(a + c) (mode 0) or b - a (mode 1) over the VALID (finite e) elements.
+// A workgroup owns 64 genes x one row block x ONE group (the grid's third dimension, as gene_rows_kernel's class): col_moments'
+// 64-column shape, because the partials cost 56 bytes per (block, group, gene) against 8 bytes per (row, gene) read -- 1024-gene
+// chunks would need ~256 row blocks to fill the chip at 978 genes and write more than they read.  Inside the workgroup a
+// thread holds a QUAD of genes (16 lanes span the 64 genes: a 16-byte load each where the rows allow, four dwords otherwise)
+// and one of 16 row slots; a row of another group is skipped in front of its loads.  Both paths add the same numbers in the
+// same order: slots ((s0 + s1) + (s2 + s3)) by two xor shuffles, then the four waves ((w0 + w1) + (w2 + w3)) through LDS.
+struct EffectArgs {
+    const float* a; int64_t lda; const float* b; int64_t ldb; const int32_t* grp; int M, X, R, mode; float delta, c; double* out;
+};
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void effect_cols_kernel(EffectArgs p) {
+    __shared__ double part[4][7][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int q4 = 4 * (tid & 15), slot = tid >> 4;
+    const int g0 = (int)blockIdx.x * 64 + q4;
+    const int k = (int)blockIdx.z;
+    const int64_t r0 = (int64_t)blockIdx.y * p.R, r1 = r0 + p.R < p.M ? r0 + p.R : p.M;
+    const float nan = __int_as_float(0x7fc00000);
+    double se[4], s2[4], sa[4], sb[4];
+    int n[4], up[4], dn[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        se[j] = s2[j] = sa[j] = sb[j] = 0.;
+        n[j] = up[j] = dn[j] = 0;
+    }
+    if (g0 < p.X) {
+        for (int64_t r = r0 + slot; r < r1; r += 16) {
+            if ((p.grp ? p.grp[r] : 0) != k) continue;
+            const float* ar = p.a + r * p.lda;
+            const float* br = p.b + r * p.ldb;
+            float av[4], bv[4];
+            if constexpr (VEC) {          // (X % 4 == 0: a quad is inside or outside as a whole)
+                const float4 x = *reinterpret_cast<const float4*>(ar + g0), y = *reinterpret_cast<const float4*>(br + g0);
+                av[0] = x.x; av[1] = x.y; av[2] = x.z; av[3] = x.w;
+                bv[0] = y.x; bv[1] = y.y; bv[2] = y.z; bv[3] = y.w;
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {      // (a gene past X: NaN, an invalid element)
+                    av[j] = g0 + j < p.X ? ar[g0 + j] : nan;
+                    bv[j] = g0 + j < p.X ? br[g0 + j] : nan;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float e = p.mode == 0 ? log2f(bv[j] + p.c) - log2f(av[j] + p.c) : bv[j] - av[j];
+                if (fabsf(e) <= 3.402823466e38f) {      // finite (a NaN compares false)
+                    const double ed = (double)e;
+                    n[j] += 1;
+                    se[j] += ed;
+                    s2[j] += ed * ed;
+                    up[j] += e > p.delta;
+                    dn[j] += e < -p.delta;
+                    sa[j] += (double)av[j];
+                    sb[j] += (double)bv[j];
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double v[7] = {(double)n[j], se[j], s2[j], (double)up[j], (double)dn[j], sa[j], sb[j]};
+#pragma unroll
+        for (int t = 0; t < 7; ++t) {
+            v[t] += __shfl_xor(v[t], 16, 64);
+            v[t] += __shfl_xor(v[t], 32, 64);
+            if (lane < 16) part[wave][t][q4 + j] = v[t];
+        }
+    }
+    __syncthreads();
+    double* o = p.out + ((int64_t)blockIdx.y * gridDim.z + k) * 7 * p.X;
+    for (int i = tid; i < 7 * 64; i += 256) {
+        const int t = i >> 6, c = i & 63, g = (int)blockIdx.x * 64 + c;
+        if (g < p.X) o[(int64_t)t * p.X + g] = (part[0][t][c] + part[1][t][c]) + (part[2][t][c] + part[3][t][c]);
+    }
+}
+
 // dv_recon_row_stats + the log-likelihood rows in ONE pass over (x, mu, sd) for rows of up to 1024 columns (whole-set
 // evaluation: 978 genes): a wave holds its row in registers (16 columns per lane), the centred second pass costs no
 // memory traffic.  Same outputs (and, on the dword path, summation orders) as recon_row_stats_kernel / nll_rows_fwd_kernel.
@@ -4233,6 +4313,29 @@ extern "C" int dv_col_moments(const float* x, int64_t ldx, const float* r, int64
     const int rpb = (M + row_blocks - 1) / row_blocks;
     hipLaunchKernelGGL(col_moments_kernel, dim3((X + 63) / 64, row_blocks), dim3(64 * kCmRG), 0, ST(stream), x, ldx, r, ldr, M, X, out,
                        rpb > 0 ? rpb : 1, sel, r_bias);
+    DV_RETURN_LAUNCH();
+}
+
+// the effect reduction (dv_draw_desc.fx, carried by dv_fill_normal in optim.hip): every refusal in front of the launch, at
+// M == 0 too
+int dv_effect_cols_launch(const dv_effect_desc& f, int32_t M, int32_t X, dv_stream_t stream) {
+    DV_REQUIRE(M >= 0 && X >= 1 && X <= 0x7fffffc0);             // (the last gene chunk's indices stay inside int32)
+    DV_REQUIRE(f.n_grp >= 1 && f.n_grp <= 65535);
+    DV_REQUIRE(f.row_blocks >= 1 && f.row_blocks <= (M > 1 ? M : 1) && f.row_blocks <= 65535);
+    DV_REQUIRE(f.lda >= X && f.ldb >= X);
+    DV_REQUIRE(f.mode == 0 || f.mode == 1);
+    DV_REQUIRE(f.delta >= 0.f);                                  // (a NaN fails every comparison)
+    DV_REQUIRE(f.pseudo >= 0.f && f.pseudo <= 3.402823466e38f);
+    DV_REQUIRE(f.mode == 0 || f.pseudo == 0.f);
+    if (M == 0) return DV_OK;
+    DV_REQUIRE(f.a && f.b && f.out);
+    auto al = [](const void* p, int64_t ld) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld & 3) == 0; };
+    const bool vec = X % 4 == 0 && al(f.a, f.lda) && al(f.b, f.ldb);
+    const EffectArgs a{f.a, f.lda, f.b, f.ldb, f.grp, M, X, (int)(((int64_t)M + f.row_blocks - 1) / f.row_blocks),
+                       f.mode, f.delta, f.pseudo, f.out};
+    const dim3 grid((unsigned)((X + 63) / 64), (unsigned)f.row_blocks, (unsigned)f.n_grp), block(256);
+    if (vec) hipLaunchKernelGGL(effect_cols_kernel<true>, grid, block, 0, ST(stream), a);
+    else hipLaunchKernelGGL(effect_cols_kernel<false>, grid, block, 0, ST(stream), a);
     DV_RETURN_LAUNCH();
 }
 

@@ -1424,6 +1424,43 @@ int dv_flag_wait(int32_t* flag, const int32_t* ctr, int32_t add, int32_t* err, i
  * ones otherwise: the same values either way. */
 #define DV_DRAW_MAX_SAMPLES 16777216        /* 2^24: the sample index shares a counter word with the block index */
 #define DV_DRAW_MAX_ROW 2147483648LL        /* 2^31 */
+/* THE EFFECT REDUCTION (`draw->fx` != NULL; an optional trailing field of dv_draw_desc inside ABI 13, NULL = the sampler as it
+ * was, bit for bit).  One launch reduces two finished mean-head matrices a (baseline, decoded from z1) and b (perturbed,
+ * decoded from z2) to per (row block, group, gene) sufficient statistics of the perturbation effect, in float64; it draws
+ * nothing.  It rides on the sampler's descriptor because the sampler is the other launch that reads finished heads and
+ * because the descriptors of the evaluation launches have their field tails pinned by tests (docs/history/ABI_history.md,
+ * round 33).  With fx set the outer descriptor supplies M (rows) and X (genes) and nothing else: every other field of it, and
+ * dv_fill_normal's out, n, seed and ctr_dev, must be zero / NULL.
+ *   Element.  e(r, g) = log2f(b + c) - log2f(a + c) with a = a[r * lda + g], b = b[r * ldb + g], c = pseudo (mode 0, the count
+ *   decoders: a log2 fold change; the row's size factor would cancel, the heads are taken UNSCALED), or e = b - a (mode 1,
+ *   Gaussian; c must be 0) -- fp32: one add per side (c != 0), two log2f, one subtraction.  The element is VALID when e is
+ *   finite; an invalid element (a NaN or infinite head, a + c <= 0, ...) adds to no statistic.
+ *   Rows.  Row block q owns rows [q R, min(M, (q + 1) R)), R = ceil(M / row_blocks).  grp[r] (int32, device; NULL: every row in
+ *   group 0) is the row's group; a value outside [0, n_grp), negatives included, leaves the row out: it is not read.
+ *   Output.  out[((q * n_grp + k) * 7 + t) * X + g], float64, EVERY element written (zeros where block q has no row of group k
+ *   or lies past M).  Statistic t over the valid elements of block q's rows of group k: 0 their number n, 1 sum e, 2 sum e^2,
+ *   3 #{e > delta}, 4 #{e < -delta} (strict), 5 sum a, 6 sum b.  Counts are exact integers.  Every sum is accumulated in double
+ *   from the fp32 element (e^2 is the exact double product) in one fixed order, whatever the access path: no atomics, one writer
+ *   per element, two launches give equal bits; a and b may alias each other and may be column views of a wider buffer.
+ *   Geometry.  A workgroup of 256 threads owns 64 genes x one row block x one group (grid = ceil(X / 64) x row_blocks x n_grp):
+ *   thread t holds genes 4 (t % 16) .. + 3 and walks rows q R + t / 16, + 16, ... of its group; its sixteen row slots are added
+ *   as ((s0 + s1) + (s2 + s3)) inside a wave and the four waves as ((w0 + w1) + (w2 + w3)).  16-byte loads where X % 4 == 0
+ *   and both matrices' rows are 16-byte aligned, scalar ones otherwise -- any X >= 1, any alignment, the same bits.
+ * DV_ERR_ARG before any launch, at M == 0 too: another outer field or dv_fill_normal argument set; M < 0, X < 1 or X > 2^31 - 64; n_grp < 1 or
+ * > 65535; row_blocks outside [1, max(M, 1)] or > 65535; lda or ldb < X; a, b or out NULL with M > 0; mode outside {0, 1};
+ * delta < 0 or NaN; pseudo < 0 or not finite; mode 1 with pseudo != 0.  M == 0 with a valid descriptor: DV_OK, no launch,
+ * nothing written. */
+typedef struct dv_effect_desc {
+    const float* a;
+    int64_t lda;
+    const float* b;
+    int64_t ldb;
+    int32_t mode;                 /* 0: log2(b + c) - log2(a + c); 1: b - a */
+    float delta, pseudo;
+    double* out;                  /* (row_blocks, n_grp, 7, X) */
+    int32_t row_blocks, n_grp;
+    const int32_t* grp;
+} dv_effect_desc;
 typedef struct dv_draw_desc {
     int32_t kind, M, X, S;        /* DV_RECON_*; rows, genes, samples */
     const float* mu;
@@ -1440,6 +1477,7 @@ typedef struct dv_draw_desc {
     int64_t row0;
     const int32_t* grow;
     int32_t k0;                   /* the sample index of out's first sample */
+    const dv_effect_desc* fx;     /* trailing: THE EFFECT REDUCTION above (NULL: the sampler as it was) */
 } dv_draw_desc;
 int dv_fill_normal(float* out, int64_t n, uint64_t seed, const int32_t* ctr_dev, dv_stream_t stream,
                    const dv_draw_desc* draw);
