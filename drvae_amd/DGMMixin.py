@@ -37,8 +37,12 @@ class DeepGenerativeModelMixin:
             raise ValueError('Selected unknown optimizer: ' + str(self.optim_alg))
         self.optimizer = None          # kept for attribute parity; the state lives in the arena
         self._engine = None
-        # (``fit._EvalGraph.CACHE_KEYS`` and ``fit._ChunkedEval.CACHE_KEY``)
-        for key in ('_eval_graphs', '_eval_graphs_own_kind', '_eval_chunked'):
+        self._drop_evaluators()
+
+    def _drop_evaluators(self, chunked_only=False):
+        """forget the captured whole-set evaluations (``drvae_amd.evaluate``): every cache of them the model holds"""
+        from .evaluate import CACHE_KEYS, _ChunkedEval
+        for key in (_ChunkedEval.CACHE_KEY,) if chunked_only else CACHE_KEYS:
             self.__dict__.pop(key, None)
 
     def _step_config(self):
@@ -190,15 +194,14 @@ class DeepGenerativeModelMixin:
             self._stash_optimizer_state()
             self._engine = self._arena = None      # rebuilt (and the parameters re-adopted) by engine()
             # (captured evaluations point into the retired arena / plans: the one-replay ones and the row-chunked ones)
-            for key in ('_eval_graphs', '_eval_graphs_own_kind', '_eval_chunked'):
-                self.__dict__.pop(key, None)
+            self._drop_evaluators()
         return out
 
     def load_state_dict(self, state_dict, strict=True, assign=False):
         if getattr(self, '_engine', None) is not None:
             self._engine._refuse_averaged('load_state_dict')
         out = super().load_state_dict(state_dict, strict=strict, assign=assign)
-        self.__dict__.pop('_eval_chunked', None)      # (row-chunked evaluators are rebuilt for reloaded parameters)
+        self._drop_evaluators(chunked_only=True)       # (row-chunked evaluators are rebuilt for reloaded parameters)
         if assign and getattr(self, '_engine', None) is not None and not self._arena_aliased():
             self._arena.adopt(self)                # values copied into the arena, parameters aliased again
         if getattr(self, '_engine', None) is not None:
@@ -278,7 +281,7 @@ class DeepGenerativeModelMixin:
         has_x2 = has_x2 if has_x2 is not None else zeros
         has_y = has_y if has_y is not None else zeros
         counts = getattr(self, '_global_counts', None)
-        eng.row0 = int(getattr(self, '_row0_override', 0))      # (a row shard of a whole-set evaluation: ``fit._EvalGraph``)
+        eng.row0 = int(getattr(self, '_row0_override', 0))      # (a row shard of a whole-set evaluation: ``evaluate._EvalGraph``)
         if dp and self._dp is not None:
             from . import dist as D
             eng.row0 = self._dp[0] * n          # (every rank feeds the same number of rows: ``shard_rows``)

@@ -48,7 +48,7 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         # ``StepConfig.ema_decay``; ``ema_eval``: ``fit`` evaluates and snapshots the averaged weights (default) or the live ones
         ema_decay = E.check_ema_decay(args.pop('ema_decay', None))
         # None | an integer >= 1: ``evaluate_performance_on_dataset`` (and so ``fit``) evaluates a device-resident set in row
-        # chunks of at most so many rows, in device memory that does not grow with rows x genes (``fit._ChunkedEval``)
+        # chunks of at most so many rows, in device memory that does not grow with rows x genes (``evaluate._ChunkedEval``)
         eval_chunk_rows = args.pop('eval_chunk_rows', None)
         # raw-count inputs (EXTENSIONS, count decoders only; ``StepConfig.x_transform`` / ``library_size``): the encoder reads
         # log1p(x) while the likelihood keeps the raw counts; every decoder mean is scaled by the row's observed size factor
@@ -64,7 +64,7 @@ class ELBOModel(FitMixin, DeepGenerativeModelMixin, nn.Module):
         self.ema_decay, self.ema_eval = ema_decay, True
         self.eval_chunk_rows = eval_chunk_rows
         if eval_chunk_rows is not None:      # (what the configuration alone decides is refused here: ValueError / NotImplementedError)
-            from .fit import _ChunkedEval
+            from .evaluate import _ChunkedEval
             _ChunkedEval.check_chunk_rows(eval_chunk_rows)
             _ChunkedEval.check_model(self)
         self.x_transform, self.library_size = x_transform, library_size

@@ -67,7 +67,7 @@ def effect_cols(out, a, b, *, grp=None, n_groups=1, mode, delta, pseudocount=0.0
 
 def fold(acc, part):
     """the (G, 7, X) float64 accumulator ``acc`` += the blocks of ``part`` (row_blocks, G, 7, X), added up over the leading
-    dimension -- the sibling of ``fit.fold_col_blocks``: one fixed order for a given shape, chunks and samples in the order
+    dimension -- the sibling of ``evaluate.fold_col_blocks``: one fixed order for a given shape, chunks and samples in the order
     they arrive"""
     assert acc.dtype == part.dtype == torch.float64 and tuple(acc.shape) == tuple(part.shape[1:])
     return acc.add_(part.sum(0))

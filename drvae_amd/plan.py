@@ -334,7 +334,7 @@ class _Plan:
         ``grow_dev[j]`` of the data set its rows were taken from (an integer device tensor with an entry per input row) --
         every draw of the next ``draw_noise`` is then the one that row gets in a plan of the whole set, whatever rows the
         plan holds this time.  One gather and one strided copy on the device, capturable; the plan is built once, with local
-        rows, and serves every row chunk of its shape (``fit._ChunkedEval``).  The column stays as written until the next call."""
+        rows, and serves every row chunk of its shape (``evaluate._ChunkedEval``).  The column stays as written until the next call."""
         local = self.__dict__.get('_noise_row_local')
         if local is None:      # (the input row of every descriptor row, from the column as the constructor wrote it)
             local = self._noise_row_local = self.noise_desc[:, 3].long() - self.row0

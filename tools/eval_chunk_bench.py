@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Row-chunked whole-set evaluation (``evaluate_performance_on_dataset(chunk_rows=C)``, ``fit._ChunkedEval``) against the
-one-replay evaluation (``fit._EvalGraph``) on the same model and HBM-resident set, the modes alternating inside one process
+"""Row-chunked whole-set evaluation (``evaluate_performance_on_dataset(chunk_rows=C)``, ``evaluate._ChunkedEval``) against the
+one-replay evaluation (``evaluate._EvalGraph``) on the same model and HBM-resident set, the modes alternating inside one process
 (shapes warmed up, evaluators built before the clock starts; host clock around a call that ends in the evaluation's one
 device-to-host copy), and a large ``CsrRows`` set: time and peak device memory of the chunked evaluation and of the densifying path.
 
